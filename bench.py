@@ -27,6 +27,11 @@ runs this one command:
   secondary.encrypt   SURVEY §8 f4: 2^20 encryptions of 2-scalar messages per GPU (k_crypt; construction unpinned)
 (--no-secondary skips them; --workload X makes X the primary and runs no secondary; --log2n scales the primary.)
 
+--dump-outputs DIR (e.g. bench_outputs/) writes, on rank 0, what each timed workload's LAST timed step returned (copied out right after
+the timed region) as DIR/<workload>_<array>.npy: float64, every 64-bit word as its exact (low, high) 32-bit halves on a last axis, plus
+DIR/<workload>_rows.npy, the item indices kept — all of them, or a fixed seeded sample where the 64 MB budget (half for the primary)
+does not hold them.  The inputs depend on the arguments alone (seeded device generators), so two builds compare output for output.
+
 The shader clock is MEASURED inside the run: a one-wave probe kernel (p252_clock_probe_device: s_memtime
 against the 100 MHz s_memrealtime) runs on a second stream beside extra untimed steps immediately before and after
 each timed region — the clock under this very load — and every roofline fraction is given at the nominal 2.4 GHz
@@ -125,6 +130,9 @@ def parse():
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where rank 0 writes the full record (nested models, sources, per-rank arrays, notes); the printed line names it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what each timed workload's last timed step returned as DIR/<workload>_<array>.npy (float64, "
+                         "64-bit words split into exact 32-bit halves; a fixed seeded sample of rows past the 64 MB budget)")
     return ap.parse_args()
 
 
@@ -551,6 +559,13 @@ def make_workload(E, wl, log2n):
         d_out = torch.empty((n, 5, 4), dtype=torch.int64, device=dev)
         W.step = lambda: ctx.hash_batch_device(tag, d_in, 42, 5, d_out, n)
     W.d_out = d_out
+    # what a caller of the timed step receives (--dump-outputs): (name, device array), the per-item arrays first, one row per item
+    if wl == "tree":
+        W.outputs = [("root", (W.d_top if dist.is_initialized() else d_out).view(1, 4))]
+    elif wl == "extract":
+        W.outputs = [("leaves", d_out), ("siblings", W.d_sib), ("positions", W.d_pos), ("out_of_range", W.d_bad)]
+    else:
+        W.outputs = [({"merkle4_digests": "digests", "forest": "roots", "openings": "roots", "encrypt": "ciphertexts"}.get(wl, "outputs"), d_out)]
 
     def self_check():
         """correctness of what was just timed, WITHOUT the oracle (every rank, every N): a slice of the batch is
@@ -655,9 +670,44 @@ def probe_under_load(E, W, step_ms, n_steps=4):
     return r if 0.3 < r["shader_ghz"] < 4.0 else None
 
 
-def run_timed(E, W, steps, warmup):
+DUMP_BUDGET_BYTES = (64 << 20) - (64 << 10)  # --dump-outputs: every file of the directory, .npy headers included, with room to spare
+
+
+def _exact_float64(a):
+    """an integer array as float64 without loss: every 64-bit word as its (low, high) 32-bit halves on a new last axis"""
+    if a.dtype == np.int64:
+        u = a.view(np.uint64)
+        return np.stack([u & 0xFFFFFFFF, u >> 32], axis=-1).astype(np.float64)
+    return a.astype(np.float64)
+
+
+def snapshot_outputs(W, budget):
+    """host copy of W.outputs in at most `budget` bytes of .npy files: every row when they fit, else a fixed seeded sample of rows
+    (the same rows of every per-item array; their indices go along as `rows`)"""
+    import torch
+    n = W.outputs[0][1].shape[0]
+    per_item = [t for _, t in W.outputs if t.shape[0] == n]
+    nbytes = lambda t, rows: rows * (t[0].numel() if t.dim() > 1 else 1) * 8 * (2 if t.dtype == torch.int64 else 1)
+    fixed = sum(nbytes(t, t.shape[0]) for _, t in W.outputs if t.shape[0] != n) + 128 * (len(W.outputs) + 1)
+    k = int(min(n, max(1, (budget - fixed) // (8 + sum(nbytes(t, 1) for t in per_item)))))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0xD0).choice(n, k, replace=False))
+    idx = torch.from_numpy(rows).to(W.outputs[0][1].device)
+    snap = {"rows": rows.astype(np.float64)}
+    for name, t in W.outputs:
+        snap[name] = _exact_float64((t.index_select(0, idx) if k < n and t.shape[0] == n else t).cpu().numpy())
+    return snap
+
+
+def write_outputs(directory, key, snap):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in snap.items():
+        np.save(os.path.join(directory, "%s_%s.npy" % (key, name)), a)
+
+
+def run_timed(E, W, steps, warmup, dump_budget=None):
     """wake-up launches, `warmup` untimed steps, exactly `steps` timed steps between barriers; HIP events per step on the
-    launch stream; the clock probe beside extra untimed steps immediately before and after the timed region"""
+    launch stream; the clock probe beside extra untimed steps immediately before and after the timed region.  With
+    `dump_budget` the outputs of the last timed step are copied out (W.snapshot) before any further step runs."""
     torch = E.torch
     # Device wake-up (setup, reported in the JSON line): an idle MI355X needs ~25 ms of activity before its clocks
     # reach the steady state a running service sees (profiles/r01_bench_kernel_trace_v9.txt: the first ten launches are up
@@ -685,6 +735,7 @@ def run_timed(E, W, steps, warmup):
     E.barrier()
     elapsed = time.perf_counter() - t0
     launch_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
+    W.snapshot = snapshot_outputs(W, dump_budget) if dump_budget else None
     clk_after = probe_under_load(E, W, step_ms_est)
     elapsed = E.max_over_ranks(elapsed)
     W.rank_ms_per_step = [v / steps * 1e3 for v in E.per_rank(own)]
@@ -938,12 +989,6 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC (RCCL across processes on this driver); before the runtime loads
-    if os.environ.get("P252_BENCH_SHARE_GPU") == "1":
-        # test-only configuration (N ranks on ONE GPU): one hardware queue per rank.  With the runtime's default of 4, eight ranks plus the
-        # test runner's own context exceed the chip's hardware queue slots and the driver time-slices oversubscribed runlists at a
-        # granularity of seconds — measured on one box (profiles/r06_shared_gpu_queues.txt): the 8-rank rehearsal 3.8 s with 1 queue per
-        # rank, 95-143 s with 2-4.  One rank per GPU (the driver's run) is not affected and not touched.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "1")
     keep_stdout_for_the_line()
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -991,9 +1036,15 @@ def main():
     secondary_keys = [] if (args.workload or args.no_secondary) else ["tree", "forest", "sponge42", "openings", "encrypt", "extract"]
     sclk0 = sysfs_sclk_mhz(torch, local_rank)
 
+    # --dump-outputs budget: half for the primary, the other half shared by the secondaries
+    dump_share = {k: (DUMP_BUDGET_BYTES // 2 if secondary_keys else DUMP_BUDGET_BYTES) if k == primary_key else DUMP_BUDGET_BYTES // 2 // len(secondary_keys)
+                  for k in [primary_key] + secondary_keys}
+
     def measure(key, log2n, steps, warmup):
         W = make_workload(E, key, log2n)
-        elapsed, launch_ms, cb, ca = run_timed(E, W, steps, warmup)
+        elapsed, launch_ms, cb, ca = run_timed(E, W, steps, warmup, dump_share[key] if (args.dump_outputs and rank == 0) else None)
+        if W.snapshot is not None:
+            write_outputs(args.dump_outputs, key, W.snapshot)
         ok = None
         if not args.no_check:
             ok = W.self_check()

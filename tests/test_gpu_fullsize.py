@@ -207,10 +207,9 @@ def test_config5_per_gpu_share_2pow24_leaves_all_levels(gpu_ctx, oracle_mod):
 
 @pytest.mark.parametrize("log2n", [28, 30, 32])
 def test_beyond_4GiB_leaves_in_one_buffer(gpu_ctx, oracle_mod, log2n):
-    """(The default set runs log2n = 28: 8 GiB of leaves in one buffer — byte offsets beyond 2^32 on every array of the path — in a few
-    seconds.  log2n = 30 (32 GiB + 10 GiB of scratch; in the default set until round 5, 40 s of the driver's 1,200 s) and log2n = 32
-    (2^32 leaves = 128 GiB in one buffer, ~180 GiB in all, more leaves than a uint32 counts) run with P252_TEST_HUGE=1: VERDICT r5 item 3;
-    both ran on an MI355X, profiles/r05_huge_sizes.txt.)
+    """(log2n = 28: 8 GiB of leaves in one buffer — byte offsets beyond 2^32 on every array of the path; log2n = 30: 32 GiB + 10 GiB of
+    scratch; log2n = 32: 2^32 leaves = 128 GiB in one buffer, ~180 GiB in all, more leaves than a uint32 counts.  All three are in the
+    default set: about 1, 4 and 14 s on an MI355X, profiles/r05_huge_sizes.txt, profiles/r06_huge_and_soak.txt.)
     Maximum sizes (MI355X: 288 GB of HBM per GPU — shards are sized for it): 2^30 leaves = 32 GiB in ONE buffer, 64 x one GPU's
     share of BASELINE configs[4].  Every index on this path must be 64-bit: 2^28 digests in one launch (8 GiB out), the 15-level
     tree over the 2^30 leaves (357,913,941 permutations, root only: 10 GiB of per-stream level scratch) and the forest of 2^18 trees
@@ -218,10 +217,9 @@ def test_beyond_4GiB_leaves_in_one_buffer(gpu_ctx, oracle_mod, log2n):
     buffer: tree(leaves) == tree(digests of the groups of four) == tree(forest roots); digests and forest roots against the oracle."""
     import torch
     import poseidon252_amd as P
-    import os
-    if log2n > 28 and os.environ.get("P252_TEST_HUGE") != "1":
-        pytest.skip("2^%d leaves (%d GiB): set P252_TEST_HUGE=1" % (log2n, (32 << log2n) >> 30))
     n = 1 << log2n
+    gpu_ctx.trim()  # what earlier tests left cached (the context's scratch, torch's allocator) is not what this box can hold
+    torch.cuda.empty_cache()
     free, _ = torch.cuda.mem_get_info()
     if free < int(1.8 * n * 32):
         pytest.skip("needs %d GiB of free HBM" % (int(1.8 * n * 32) >> 30))
@@ -251,3 +249,4 @@ def test_beyond_4GiB_leaves_in_one_buffer(gpu_ctx, oracle_mod, log2n):
     assert P.levels_len(n) == (4 ** (log2n // 2) - 1) // 3
     del d, roots
     torch.cuda.empty_cache()
+    gpu_ctx.trim()  # (up to 10 GiB of per-stream level scratch back to the device)
