@@ -135,6 +135,7 @@ impl Drop for Context {
 /// n messages with one io-pattern, one kernel launch; per item identical to `Hash::digest` / `Hash::finalize`.
 pub struct HashBatch {
     ctxs: Vec<Context>,
+    domain: Domain,
     item_len: usize,
     output_len: usize,
     tag: BlsScalar,
@@ -151,7 +152,7 @@ impl HashBatch {
             output_len = 1;
         }
         let (tag, _) = hash_tag(domain, &[item_len], output_len)?;
-        Ok(Self { ctxs: vec![Context::new(0)], item_len, output_len, tag })
+        Ok(Self { ctxs: vec![Context::new(0)], domain, item_len, output_len, tag })
     }
 
     /// One context per visible GPU: `digest` and `merkle4_root` then shard across all of them inside the library.
@@ -188,6 +189,33 @@ impl HashBatch {
         let rc = unsafe {
             p252_hash_batch_truncated(self.ctxs[0].0, self.tag.0.as_ptr(), input.as_ptr() as *const u64, self.item_len, self.output_len,
                                       out.as_mut_ptr() as *mut u64, n)
+        };
+        self.ctxs[0].check(rc);
+        out
+    }
+
+    /// `out[i*output_len..]` equals `Hash::digest(domain, messages[i])` for messages of ANY lengths, in one call
+    /// (`p252_hash_ragged`; the batch's own `item_len` plays no part).  One tag per length 1..=max, each from the real crates
+    /// (`hash_tag`).  Panics where `Hash::finalize` panics: an empty message, a Merkle domain (one fixed length: `digest`).
+    pub fn digest_ragged(&self, messages: &[&[BlsScalar]]) -> Vec<BlsScalar> {
+        let max_len = messages.iter().map(|m| m.len()).max().unwrap_or(0);
+        let mut out = vec![BlsScalar::zero(); messages.len() * self.output_len];
+        if messages.is_empty() {
+            return out;
+        }
+        assert!(messages.iter().all(|m| !m.is_empty()), "io-pattern should be valid");
+        let tags: Vec<BlsScalar> =
+            (1..=max_len).map(|l| hash_tag(self.domain, &[l], self.output_len).expect("io-pattern should be valid").0).collect();
+        let mut offsets = Vec::with_capacity(messages.len() + 1);
+        offsets.push(0u64);
+        let mut flat: Vec<BlsScalar> = Vec::with_capacity(messages.iter().map(|m| m.len()).sum());
+        for m in messages {
+            flat.extend_from_slice(m);
+            offsets.push(flat.len() as u64);
+        }
+        let rc = unsafe {
+            p252_hash_ragged(self.ctxs[0].0, tags.as_ptr() as *const u64, max_len, flat.as_ptr() as *const u64, offsets.as_ptr(),
+                             self.output_len, out.as_mut_ptr() as *mut u64, messages.len())
         };
         self.ctxs[0].check(rc);
         out

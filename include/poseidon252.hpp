@@ -13,6 +13,7 @@
 //   Hash::finalize_truncated / digest[_truncated]   same names                   (hash.rs:164-210)
 //   panic!("io-pattern should be valid")            throws IoPatternError        (hash.rs:124-137)
 //   —                                               HashBatch: n messages, one kernel launch
+//   Hash::digest over messages of any lengths       RaggedHashBatch: n messages of different lengths, one call
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -241,6 +242,64 @@ class HashBatch {
     std::size_t item_len_, output_len_;
     Context& ctx_;
     BlsScalar tag_{};
+};
+
+// n messages of DIFFERENT lengths in one call (p252_hash_ragged*): per message Hash::digest(domain, message), hash.rs:191-195.
+// The tag table (row L - 1 = the tag of [Absorb(L), Squeeze(output_len)]) grows to the longest message seen; the Merkle domains
+// have one fixed length and are refused (HashBatch).
+class RaggedHashBatch {
+  public:
+    explicit RaggedHashBatch(Domain domain = Domain::Other, std::size_t output_len = 1, Context& ctx = Context::default_context())
+        : domain_(domain), output_len_((domain == Domain::Other && output_len > 0) ? output_len : 1), ctx_(ctx) {
+        if (domain == Domain::Merkle4 || domain == Domain::Merkle2)
+            throw IoPatternError(IoPatternError::IOPatternViolation,
+                                 "io-pattern should be valid: IOPatternViolation — Merkle messages have one fixed length; use HashBatch");
+    }
+    std::size_t output_len() const { return output_len_; }
+    // the tag table of lengths 1 .. max_len (computed on first use, kept)
+    const std::vector<BlsScalar>& tags(std::size_t max_len) {
+        while (tags_.size() < max_len) tags_.push_back(compute_tag(domain_, {tags_.size() + 1}, output_len_));
+        return tags_;
+    }
+
+    // host buffers: out[i * output_len ..] = the digest of messages[i]
+    std::vector<BlsScalar> digest(const std::vector<std::vector<BlsScalar>>& messages) { return run<BlsScalar>(messages, false); }
+    std::vector<JubJubRaw> digest_truncated(const std::vector<std::vector<BlsScalar>>& messages) { return run<JubJubRaw>(messages, true); }
+    // device buffers, asynchronous on `stream`: d_offsets = n + 1 uint64 scalar indices into d_in; d_tags = tags(max_len) uploaded by
+    // the caller (this header links no HIP runtime, and a tag is an input of every entry point).  Bad messages (empty, longer than
+    // max_len, decreasing offsets) get zero rows and increment *d_n_bad (device uint32, zeroed by the caller; may be null).
+    void digest_device(const void* d_tags, std::size_t max_len, const void* d_in, const void* d_offsets, std::size_t n, void* d_out,
+                       void* d_n_bad = nullptr, void* stream = nullptr) const {
+        detail::check(p252_hash_ragged_device(ctx_.get(), d_tags, max_len, d_in, d_offsets, output_len_, d_out, n, d_n_bad, stream),
+                      ctx_.get(), "RaggedHashBatch::digest_device");
+    }
+
+  private:
+    template <class Out>
+    std::vector<Out> run(const std::vector<std::vector<BlsScalar>>& messages, bool truncated) {
+        std::vector<uint64_t> offsets(1, 0);
+        std::size_t longest = 0;
+        for (const auto& m : messages) {
+            offsets.push_back(offsets.back() + m.size());
+            longest = m.size() > longest ? m.size() : longest;
+        }
+        std::vector<BlsScalar> flat;
+        flat.reserve(offsets.back());
+        for (const auto& m : messages) flat.insert(flat.end(), m.begin(), m.end());
+        std::vector<Out> out(messages.size() * output_len_);
+        if (messages.empty()) return out;
+        const std::size_t max_len = longest ? longest : 1;
+        const auto& t = tags(max_len);
+        const uint64_t* in = flat.empty() ? t[0].data() : flat[0].data();  // (all-empty input: refused before it is read)
+        const int rc = truncated ? p252_hash_ragged_truncated(ctx_.get(), t[0].data(), max_len, in, offsets.data(), output_len_, out[0].data(), messages.size())
+                                 : p252_hash_ragged(ctx_.get(), t[0].data(), max_len, in, offsets.data(), output_len_, out[0].data(), messages.size());
+        detail::check(rc, ctx_.get(), truncated ? "RaggedHashBatch::digest_truncated" : "RaggedHashBatch::digest");
+        return out;
+    }
+    Domain domain_;
+    std::size_t output_len_;
+    Context& ctx_;
+    std::vector<BlsScalar> tags_;
 };
 
 // Arity-4 Merkle root over Hash::digest(Domain::Merkle4, ..) nodes (empty slots = zero, hash.rs:22-26)

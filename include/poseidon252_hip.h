@@ -49,7 +49,8 @@
  * the caller's with p252_merkle{4,2}_path_batch_device): with d_levels = NULL the graph holds the addresses of the context's
  * per-stream pair and the pair's hand-over event becomes a graph node, so a replay is ordered against nothing the context does
  * later — a fifth stream taking the pair over, p252_trim, a growing build — and would race with it.  The hashing
- * entry points (digests, sponges, permutations, truncated forms) use no context scratch and capture without conditions.
+ * entry points (digests, sponges, permutations, truncated forms) use no context scratch and capture without conditions; the
+ * ragged ones (p252_hash_ragged*_device) sort in the per-stream pair as a tree build does.
  * Multi-GPU = one context per GPU: either one process (or thread) per GPU driving its own context,
  * or the p252_*_multi entry points below, which take the array of contexts and shard inside the library; batches
  * shard with no inter-GPU dependence.
@@ -84,8 +85,9 @@ extern "C" {
  *      deployment needs no RCCL and a process gets ONE copy; + p252_comm_backend (which copy), p252_comm_check (a peer's failed
  *      local build in a sharded tree: the healthy ranks' root becomes all-ones and p252_comm_check / p252_sync return
  *      P252_ERR_COMM — they used to return a garbage root as P252_OK), p252_trim (gives the grow-only scratch back);
- *      p252_scratch_residue no longer counts the encryption call table (it holds nothing of the caller's) */
-#define P252_ABI_VERSION 8
+ *      p252_scratch_residue no longer counts the encryption call table (it holds nothing of the caller's)
+ *   9  + p252_hash_ragged[_truncated][_device]: n messages of different lengths in one call */
+#define P252_ABI_VERSION 9
 
 #define P252_OK 0
 #define P252_ERR_IO_PATTERN_VIOLATION (-1) /* dusk_poseidon::Error::IOPatternViolation, src/error.rs:12-14 */
@@ -171,6 +173,33 @@ int p252_hash_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_i
  * p252_truncate250_device without the second launch and the 64 B / scalar round trip through HBM. */
 int p252_hash_batch_truncated_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_in, size_t in_len,
                                      size_t out_len, void* d_out_raw, size_t n, void* hip_stream);
+/* n independent sponge hashes of DIFFERENT lengths in one call: Hash::digest per message (hash.rs:191-195).
+ * Message i = d_in[offsets[i] .. offsets[i+1]) scalars; d_offsets = n + 1 uint64 scalar indices (64-bit, so one array may hold
+ * more than 2^32 scalars; 8-byte aligned).  d_tags = max_len scalars (Montgomery limbs like every BlsScalar): a message of
+ * length L uses d_tags[L - 1], the tag of [Absorb(L), Squeeze(out_len)] for the caller's domain (p252_tag; since a chunked
+ * Hash::update aggregates to the same tag, one table indexed by total length covers every Domain::Other / Domain::Encryption
+ * message).  d_out = n x out_len scalars in INPUT order.
+ * A message is bad when its length is 0, exceeds max_len, or its offsets decrease (the unsigned difference then wraps above
+ * max_len): its out_len output scalars are written as zero, and *d_n_bad (a device uint32 the caller has zeroed; may be NULL) is
+ * incremented once per bad message.  Valid neighbours are unaffected.  out_len == 0 -> P252_ERR_INVALID_IO_PATTERN; max_len == 0
+ * -> P252_ERR_INVALID_ARGUMENT.
+ * Schedule: the messages are sorted by absorb-block count, longest first, on the device (three small kernels) so that the lanes
+ * of a wave run the same number of permutations; the order and the bucket counters live in the context's scratch of THIS stream
+ * (as the tree builds' levels), so calls on different streams of one context never share it.  P252_RAGGED_SORT=0 (read once per
+ * process) hashes in input order instead.  n <= 8,192: eight lanes per message, as every entry point (P252_COOP_MAX_NODES). */
+int p252_hash_ragged_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
+                            size_t out_len, void* d_out, size_t n, void* d_n_bad, void* hip_stream);
+/* the same with Hash::finalize_truncated's outputs (raw limbs, canonical value & (2^250 - 1)) from the same launch */
+int p252_hash_ragged_truncated_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
+                                      size_t out_len, void* d_out_raw, size_t n, void* d_n_bad, void* hip_stream);
+/* host-buffer twins (synchronous): offsets and lengths are checked on the host before anything is launched — a zero-length
+ * message -> P252_ERR_INVALID_IO_PATTERN, decreasing offsets or a length above max_len -> P252_ERR_INVALID_ARGUMENT (nothing
+ * is hashed; p252_last_error names the message).  The messages, tags and offsets are copied through the context's grow-only
+ * device scratch in one piece: there is no chunked pipeline over pageable memory as p252_hash_batch has. */
+int p252_hash_ragged(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
+                     size_t out_len, uint64_t* out, size_t n);
+int p252_hash_ragged_truncated(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
+                               size_t out_len, uint64_t* out_raw, size_t n);
 /* d_levels may be NULL: the levels then ping-pong in context-owned scratch — one pair per caller stream, so builds queued on
  * different streams of one context never share it (see "Threading and streams"); d_root receives 1 scalar. */
 int p252_merkle4_tree_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,

@@ -39,8 +39,9 @@ ABI_SYMBOLS = (
     "p252_hash_batch_truncated", "p252_hash_batch_truncated_device", "p252_wipe", "p252_scratch_residue",
     "p252_merkle4_verify_batch_device", "p252_merkle2_verify_batch_device",
     "p252_trim", "p252_comm_check", "p252_comm_backend",
+    "p252_hash_ragged", "p252_hash_ragged_truncated", "p252_hash_ragged_device", "p252_hash_ragged_truncated_device",
 )
-ABI_VERSION = 8  # include/poseidon252_hip.h P252_ABI_VERSION this binding was written against
+ABI_VERSION = 9  # include/poseidon252_hip.h P252_ABI_VERSION this binding was written against
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _szp = ctypes.POINTER(ctypes.c_size_t)
@@ -234,6 +235,10 @@ def lib():
     L.p252_comm_check.argtypes = [_vp, _vp]
     L.p252_comm_backend.argtypes = [ctypes.c_char_p, _sz]
     L.p252_scratch_residue.argtypes = [_vp, _u64p]
+    L.p252_hash_ragged.argtypes = [_vp, _u64p, _sz, _u64p, _u64p, _sz, _u64p, _sz]
+    L.p252_hash_ragged_truncated.argtypes = [_vp, _u64p, _sz, _u64p, _u64p, _sz, _u64p, _sz]
+    L.p252_hash_ragged_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp]
+    L.p252_hash_ragged_truncated_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp]
     L.p252_abi_version.restype = ctypes.c_int
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)

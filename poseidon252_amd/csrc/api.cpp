@@ -19,6 +19,7 @@
 #include "hades29.hpp"
 #include "kernels.h"
 #include "openings.h"
+#include "ragged.h"
 #include "tables.hpp"
 #include "_gen/assets.inc"
 
@@ -842,6 +843,101 @@ int p252_hash_batch(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, si
 int p252_hash_batch_truncated(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, size_t in_len, size_t out_len,
                               uint64_t* out_raw, size_t n) {
     return hash_batch_host_impl(ctx, tag, in, in_len, out_len, out_raw, n, true);
+}
+
+// ---- messages of different lengths in one call (ragged.hip): the sort's order array and bucket counters live in the scratch
+// pair of the calling stream (as the verify path's re-hashed roots), so calls on different streams of one context never share them
+static int hash_ragged_device_impl(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
+                                   size_t out_len, void* d_out, size_t n, void* d_n_bad, void* hip_stream, bool trunc250) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (out_len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: out_len must be > 0");
+    if (out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: out_len too large");
+    if (n == 0) return P252_OK;
+    if (max_len == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: max_len must be > 0");
+    if (!d_tags || !d_in || !d_offsets || !d_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
+    if (misaligned(d_tags) || misaligned(d_in) || misaligned(d_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_offsets must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_n_bad must be 4-byte aligned");
+    if (n >= SIZE_MAX / 8 / (out_len > 8 ? out_len : 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!ragged_sort_enabled()) {  // P252_RAGGED_SORT=0: identity order, no scratch
+        HIP_TRY(ctx, launch_hash_ragged(ctx->d_tab, d_tags, max_len, d_in, d_offsets, (unsigned)out_len, d_out, n, d_n_bad, nullptr,
+                                        nullptr, st, trunc250));
+        return P252_OK;
+    }
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    int rc = level_set(ctx, st, ragged_order_bytes(n), ragged_hist_bytes(), &set);
+    if (rc) return rc;
+    const hipError_t e = launch_hash_ragged(ctx->d_tab, d_tags, max_len, d_in, d_offsets, (unsigned)out_len, d_out, n, d_n_bad, set->buf[0],
+                                            set->buf[1], st, trunc250);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string("hash_ragged: ") + hipGetErrorString(e));
+    const std::string msg = ctx->err;
+    const int rc2 = guard.finish();
+    if (rc) ctx->err = msg;
+    return rc ? rc : rc2;
+}
+
+int p252_hash_ragged_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets, size_t out_len,
+                            void* d_out, size_t n, void* d_n_bad, void* hip_stream) {
+    return hash_ragged_device_impl(ctx, d_tags, max_len, d_in, d_offsets, out_len, d_out, n, d_n_bad, hip_stream, false);
+}
+
+int p252_hash_ragged_truncated_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
+                                      size_t out_len, void* d_out_raw, size_t n, void* d_n_bad, void* hip_stream) {
+    return hash_ragged_device_impl(ctx, d_tags, max_len, d_in, d_offsets, out_len, d_out_raw, n, d_n_bad, hip_stream, true);
+}
+
+// host buffers: every message is checked here first, then [messages | tags | offsets rebased to 0] go to the context's grow-only
+// d_in in one copy and the outputs come back from d_out — synchronous, no chunked pipeline
+static int hash_ragged_host_impl(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
+                                 size_t out_len, uint64_t* out, size_t n, bool trunc250) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (out_len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: out_len must be > 0");
+    if (out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: out_len too large");
+    if (n == 0) return P252_OK;
+    if (max_len == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: max_len must be > 0");
+    if (!tags || !offsets || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
+    for (size_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i])
+            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: offsets decrease at message " + std::to_string(i));
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        if (len == 0)  // a zero-length absorb is an invalid io-pattern (dusk-safe; Hash::finalize panics, hash.rs:134-137)
+            return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: message " + std::to_string(i) + " is empty");
+        if (len > max_len)
+            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: message " + std::to_string(i) + " is longer than max_len");
+    }
+    if (!in) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
+    const uint64_t total = offsets[n] - offsets[0];
+    if (total > SIZE_MAX / 64 || max_len > SIZE_MAX / 64 || n > SIZE_MAX / 64 / out_len)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: size overflow");
+    const size_t in_bytes = (size_t)total * 32, tag_bytes = max_len * 32, off_bytes = (n + 1) * 8, out_bytes = n * out_len * 32;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes + tag_bytes + off_bytes);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes);
+    if (rc) return rc;
+    std::vector<uint64_t> rebased(offsets, offsets + n + 1);
+    for (auto& o : rebased) o -= offsets[0];
+    char* d = static_cast<char*>(ctx->d_in);
+    HIP_TRY(ctx, hipMemcpy(d, in + offsets[0] * 4, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d + in_bytes, tags, tag_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d + in_bytes + tag_bytes, rebased.data(), off_bytes, hipMemcpyHostToDevice));
+    rc = hash_ragged_device_impl(ctx, d + in_bytes, max_len, d, d + in_bytes + tag_bytes, out_len, ctx->d_out, n, nullptr, nullptr, trunc250);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost));
+    return P252_OK;
+}
+
+int p252_hash_ragged(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets, size_t out_len,
+                     uint64_t* out, size_t n) {
+    return hash_ragged_host_impl(ctx, tags, max_len, in, offsets, out_len, out, n, false);
+}
+
+int p252_hash_ragged_truncated(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
+                               size_t out_len, uint64_t* out_raw, size_t n) {
+    return hash_ragged_host_impl(ctx, tags, max_len, in, offsets, out_len, out_raw, n, true);
 }
 
 static int merkle_tree_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,

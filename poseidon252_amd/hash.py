@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Domain", "Hash", "HashBatch", "Context", "Error", "IOPatternViolation", "InvalidIOPattern",
+__all__ = ["Domain", "Hash", "HashBatch", "RaggedHashBatch", "Context", "Error", "IOPatternViolation", "InvalidIOPattern",
            "HADES_WIDTH", "compute_tag"]
 
 HADES_WIDTH = 5  # dusk_poseidon::HADES_WIDTH, src/lib.rs:17
@@ -192,6 +192,22 @@ class Context:
         self._check(fn(self._h, tag.ctypes.data_as(_u64p), m.ctypes.data_as(_u64p), in_len, out_len, out.ctypes.data_as(_u64p), m.shape[0]))
         return out
 
+    def hash_ragged(self, tags, flat, offsets, out_len, truncated=False):
+        """n messages of different lengths (p252_hash_ragged[_truncated]): message i = flat[offsets[i]:offsets[i+1]], tags[L-1] = the
+        tag of a message of length L (max_len = len(tags)).  Host numpy buffers -> (n, out_len, 4); the library checks every length
+        (zero -> InvalidIOPattern; decreasing offsets or a length above max_len -> ValueError) before it launches anything."""
+        t = _as_scalars(tags).reshape(-1, 4)
+        x = _as_scalars(flat).reshape(-1, 4)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        n = max(off.shape[0] - 1, 0)
+        if n and int(off[-1]) > x.shape[0]:
+            raise ValueError("hash_ragged: offsets reach past the %d scalars given" % x.shape[0])
+        out = np.empty((n, max(out_len, 0), 4), dtype=np.uint64)
+        fn = _lib.lib().p252_hash_ragged_truncated if truncated else _lib.lib().p252_hash_ragged
+        self._check(fn(self._h, t.ctypes.data_as(_u64p), t.shape[0], x.ctypes.data_as(_u64p), off.ctypes.data_as(_u64p), out_len,
+                       out.ctypes.data_as(_u64p), n))
+        return out
+
     def merkle4_tree(self, tag, leaves, want_levels=False):
         tag = _as_scalars(tag).reshape(4)
         lv = _as_scalars(leaves).reshape(-1, 4)
@@ -237,6 +253,18 @@ class Context:
         assert self._nbytes(d_in) >= n * in_len * 32 and self._nbytes(d_out) >= n * out_len * 32
         fn = _lib.lib().p252_hash_batch_truncated_device if truncated else _lib.lib().p252_hash_batch_device
         self._check(fn(self._h, tag.ctypes.data_as(_u64p), d_in.data_ptr(), in_len, out_len, d_out.data_ptr(), n, self._stream()))
+
+    def hash_ragged_device(self, d_tags, max_len, d_in, d_offsets, out_len, d_out, n, d_n_bad=None, truncated=False):
+        """p252_hash_ragged[_truncated]_device on torch's current stream: d_offsets = n + 1 int64/uint64 scalar indices, d_tags =
+        max_len scalars (tags[L-1] for length L), d_out (n, out_len, 4).  Bad messages (empty, longer than max_len, decreasing
+        offsets) get zero rows and increment d_n_bad (a zeroed device int32/uint32, optional) — nothing is checked on the host."""
+        assert d_tags.is_cuda and d_in.is_cuda and d_offsets.is_cuda and d_out.is_cuda
+        assert d_tags.is_contiguous() and d_in.is_contiguous() and d_offsets.is_contiguous() and d_out.is_contiguous()
+        assert d_offsets.element_size() == 8 and d_offsets.numel() >= n + 1 and self._nbytes(d_tags) >= max_len * 32
+        assert self._nbytes(d_out) >= n * out_len * 32 and (d_n_bad is None or (d_n_bad.is_cuda and d_n_bad.element_size() == 4))
+        fn = _lib.lib().p252_hash_ragged_truncated_device if truncated else _lib.lib().p252_hash_ragged_device
+        self._check(fn(self._h, d_tags.data_ptr(), max_len, d_in.data_ptr(), d_offsets.data_ptr(), out_len, d_out.data_ptr(), n,
+                       d_n_bad.data_ptr() if d_n_bad is not None else None, self._stream()))
 
     def merkle4_tree_device(self, tag, d_leaves, n_leaves, d_root, d_levels=None):
         tag = _as_scalars(tag).reshape(4)
@@ -576,3 +604,99 @@ class HashBatch:
         """Hash::digest_truncated (hash.rs:203-210) per item, host or device buffers: ONE kernel launch — the digest kernel's
         output stage canonicalises, masks to 250 bits and stores the raw limbs JubJubScalar::from_raw receives (SURVEY §8 f2)"""
         return self.digest(scalars, out=out, truncated=True)
+
+
+_RAGGED_TAGS = {}  # (domain, out_len, max_len) -> host tag table; (domain, out_len, max_len, device) -> device tensor
+
+
+def ragged_tags(domain, out_len, max_len):
+    """the tag table of a ragged call: row L-1 = compute_tag(domain, [L], out_len) for L = 1 .. max_len (cached)"""
+    key = (int(domain), int(out_len), int(max_len))
+    t = _RAGGED_TAGS.get(key)
+    if t is None:
+        t = np.stack([compute_tag(domain, [L], out_len) for L in range(1, max_len + 1)])
+        _RAGGED_TAGS[key] = t
+    return t
+
+
+class RaggedHashBatch:
+    """n messages of DIFFERENT lengths in one call: per message the result equals Hash::digest(domain, message) (hash.rs:191-195).
+
+    rb = RaggedHashBatch(Domain.Other, output_len=1)
+    rb.digest([m0, m1, ...])               # list of (L_i, 4) uint64 arrays -> (n, output_len, 4)
+    rb.digest((flat, offsets))             # message i = flat[offsets[i]:offsets[i+1]]
+    rb.digest((d_flat, d_offsets), max_len=64)   # torch CUDA tensors: the device path, asynchronous, returns a device tensor
+    Lengths are checked on the host path (a zero-length message raises InvalidIOPattern, as Hash::finalize panics); on the device
+    path bad messages get zero rows and increment `d_n_bad` when given.  The Merkle domains have one fixed length: HashBatch."""
+
+    def __init__(self, domain=Domain.Other, output_len=1, ctx=None):
+        self.domain = Domain(domain)
+        if self.domain in (Domain.Merkle4, Domain.Merkle2):
+            raise IOPatternViolation("io-pattern should be valid: IOPatternViolation — %s messages have one fixed length; use HashBatch"
+                                     % self.domain.name)
+        self.out_len = int(output_len) if (self.domain == Domain.Other and output_len > 0) else 1  # hash.rs:111-115
+        self._ctx = ctx
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = Context.default()
+        return self._ctx
+
+    def tags(self, max_len):
+        return ragged_tags(self.domain, self.out_len, max_len)
+
+    def _device_tags(self, max_len, device):
+        import torch
+        key = (int(self.domain), self.out_len, int(max_len), str(device))
+        t = _RAGGED_TAGS.get(key)
+        if t is None:
+            t = torch.from_numpy(self.tags(max_len).view(np.int64)).to(device)
+            _RAGGED_TAGS[key] = t
+        return t
+
+    @staticmethod
+    def _host_messages(messages):
+        """-> (flat (S, 4), offsets (n + 1,) uint64), lengths validated like check_io_pattern"""
+        if isinstance(messages, tuple):
+            flat, off = messages
+            flat = _as_scalars(flat).reshape(-1, 4)
+            off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+            lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
+            if (lens < 0).any():
+                raise ValueError("poseidon252_hip: invalid argument — offsets decrease at message %d" % int(np.argmax(lens < 0)))
+            if off.shape[0] and int(off[-1]) > flat.shape[0]:
+                raise ValueError("poseidon252_hip: invalid argument — offsets reach past the %d scalars given" % flat.shape[0])
+        else:
+            parts = [_as_scalars(m).reshape(-1, 4) for m in messages]
+            lens = np.array([p.shape[0] for p in parts], dtype=np.int64)
+            off = np.zeros(len(parts) + 1, dtype=np.uint64)
+            np.cumsum(lens, out=off[1:])
+            flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 4), dtype=np.uint64)
+        if (lens == 0).any():  # a zero-length absorb (dusk-safe rejects it; Hash::finalize panics, hash.rs:134-137)
+            raise InvalidIOPattern("at this point the io-pattern is valid: InvalidIOPattern — message %d is empty" % int(np.argmax(lens == 0)))
+        return flat, off, (int(lens.max()) if lens.size else 0)
+
+    def digest(self, messages, max_len=None, out=None, d_n_bad=None, truncated=False):
+        if isinstance(messages, tuple) and _is_torch(messages[0]):
+            import torch
+            d_in, d_off = messages
+            if max_len is None:
+                raise ValueError("RaggedHashBatch.digest: the device path needs max_len= (offsets are never read back to the host)")
+            n = d_off.numel() - 1
+            if out is None:
+                out = torch.empty((n, self.out_len, 4), dtype=torch.int64, device=d_in.device)
+            self.ctx.hash_ragged_device(self._device_tags(max_len, d_in.device), max_len, d_in, d_off, self.out_len, out, n,
+                                        d_n_bad=d_n_bad, truncated=truncated)
+            return out
+        flat, off, longest = self._host_messages(messages)
+        if off.shape[0] <= 1:
+            return np.empty((0, self.out_len, 4), dtype=np.uint64)
+        max_len = longest if max_len is None else int(max_len)
+        if longest > max_len:
+            raise ValueError("poseidon252_hip: invalid argument — a message of %d scalars is longer than max_len = %d" % (longest, max_len))
+        return self.ctx.hash_ragged(self.tags(max_len), flat, off, self.out_len, truncated=truncated)
+
+    def digest_truncated(self, messages, max_len=None, out=None, d_n_bad=None):
+        """Hash::digest_truncated per message (hash.rs:203-210): the raw limbs from the sponge's own output stage (one launch)"""
+        return self.digest(messages, max_len=max_len, out=out, d_n_bad=d_n_bad, truncated=True)
