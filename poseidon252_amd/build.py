@@ -15,7 +15,7 @@ HIPCC_FLAGS = [
     # silently turns them into scratch-indexed loops
     "-mllvm", "-pragma-unroll-threshold=1000000",
 ]
-SOURCES = ["kernels.hip", "openings.hip", "merkle2.hip", "ragged.hip", "api.cpp", "comm.cpp", "rccl_dyn.cpp"]
+SOURCES = ["kernels.hip", "openings.hip", "merkle2.hip", "ragged.hip", "api.cpp", "host_io.cpp", "comm.cpp", "rccl_dyn.cpp"]
 # comm.cpp: the RCCL communicator of the multi-GPU entry points (ncclBroadcast of the constants, ncclAllGather of subtree roots).
 # RCCL is NOT linked: rccl_dyn.cpp resolves it with dlopen on first use (a hashing-only deployment needs no RCCL, and a
 # process that already holds a copy — torch's — gets that one); only its header is needed at build time.

@@ -4,10 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -122,8 +120,7 @@ const std::vector<int32_t>& p252host::host_tables() {
 static bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 static const char* const ALIGN_MSG = "device scalar arrays must be 16-byte aligned";
 
-// kernel argument for the tag: the scalar itself and lane 0's first-round S-box output (the digest kernels start there)
-static TagArg tag_arg(const uint64_t tag[4]) {
+TagArg p252host::tag_arg(const uint64_t tag[4]) {
     TagArg t;
     std::memcpy(t.w, tag, 32);
     const E29 x0 = hades_pre0(from_mont4(t.w), host_tables().data());
@@ -152,11 +149,11 @@ static int for_each_ctx(p252_ctx* const* ctxs, size_t n_ctx, F&& f) {
 // every sponge state in registers; what outlives a HOST-buffer encrypt / decrypt call is the library's own copy of the
 // caller's arrays: the context's device scratch and the page-locked staging lanes.  wipe_span / wipe_lanes clear exactly
 // those at the end of such a call; wipe_all clears every buffer the context owns (p252_wipe, p252_destroy). ----
-static hipError_t wipe_span(void* d, size_t bytes) { return (d && bytes) ? hipMemsetAsync(d, 0, bytes, nullptr) : hipSuccess; }
+hipError_t p252host::wipe_span(void* d, size_t bytes) { return (d && bytes) ? hipMemsetAsync(d, 0, bytes, nullptr) : hipSuccess; }
 
 // dirty_only: just the bytes calls may have written since the last wipe (staged_run keeps the extent per slot) — what the per-call
 // wipe of a host-buffer encrypt / decrypt needs; the full capacity otherwise (p252_wipe, p252_trim, p252_destroy)
-static hipError_t wipe_lanes(p252_ctx* ctx, bool dirty_only = false) {
+hipError_t p252host::wipe_lanes(p252_ctx* ctx, bool dirty_only) {
     hipError_t first = hipSuccess;
     for (auto& l : ctx->lanes)
         for (auto& sl : l.slot) {
@@ -383,7 +380,8 @@ int p252_hash_batch_truncated_device(p252_ctx* ctx, const uint64_t tag[4], const
     return hash_batch_device_impl(ctx, tag, d_in, in_len, out_len, d_out_raw, n, hip_stream, true);
 }
 
-static size_t levels_len(size_t n_leaves, size_t arity) {
+extern "C++" {
+size_t p252host::levels_len(size_t n_leaves, size_t arity) {
     size_t total = 0, c = n_leaves;
     while (c > 1) {
         c = (c + arity - 1) / arity;
@@ -391,6 +389,7 @@ static size_t levels_len(size_t n_leaves, size_t arity) {
     }
     return total;
 }
+}  // extern "C++"
 size_t p252_merkle4_levels_len(size_t n_leaves) { return levels_len(n_leaves, 4); }
 size_t p252_merkle2_levels_len(size_t n_leaves) { return levels_len(n_leaves, 2); }
 
@@ -507,344 +506,6 @@ int p252_merkle2_tree_device(p252_ctx* ctx, const uint64_t tag[4], const void* d
     return merkle_tree_device(ctx, 2, tag, d_leaves, n_leaves, d_root, d_levels, hip_stream);
 }
 
-// ------------------------------------------------------------------------------------------
-// host-buffer entry points (synchronous)
-// ------------------------------------------------------------------------------------------
-static bool is_pinned(const void* p) {
-    hipPointerAttribute_t a;
-    const bool is = hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return is;
-}
-
-// Pageable caller memory (a Rust Vec<BlsScalar>, a numpy array): page-locking it per call costs as much as the transfer
-// (round 1: 1.9e8 digests/s against 4.0e8 from pinned memory).  So a large host-buffer call is split into chunks of items
-// handled by a few LANES: a worker thread with its own stream and TWO slots (page-locked staging pair + device pair +
-// event).  Per chunk: memcpy in -> H2D -> kernel -> D2H (all asynchronous on the lane's stream) and, one chunk later,
-// memcpy out — the host copies of chunk c+1 overlap the DMA and kernel of chunk c, the lanes overlap each other, and
-// nothing the caller owns is ever registered.  Events are blocking-sync: a waiting worker sleeps instead of spinning (the
-// benchmark box grants 16 CPUs; spinning workers get the whole process throttled).  The host copies themselves are not
-// the limit (EPYC 9575F: memcpy 30 GB/s per thread, bench_tools/ntcopy.cpp; non-temporal stores changed nothing end to
-// end) — in-flight depth is: round 2's first version (one slot per lane, spinning waits, 8-12 lanes) reached 2.0-3.1e8.
-extern "C++" {  // (templates below; the enclosing block is extern "C")
-struct HostSpan {  // one per-item array of a batched call: item i occupies bytes [i * stride, (i + 1) * stride)
-    const char* src;  // input arrays: caller memory to read
-    char* dst;        // output arrays: caller memory to write
-    size_t stride;
-};
-
-// CPUs this process may actually use: min(affinity mask, cgroup quota — v2 cpu.max, else v1 cfs_quota_us / cfs_period_us,
-// as bench.py's usable_cpus() reads them).  The benchmark box shows 256 logical CPUs and grants 16.
-static double cpu_budget() {
-    static const double cpus = [] {
-        double c = (double)std::thread::hardware_concurrency();
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) c = (double)CPU_COUNT(&set);
-        if (FILE* f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "<quota> <period>" or "max <period>"
-            char q[32];
-            double period = 0;
-            if (std::fscanf(f, "%31s %lf", q, &period) == 2 && std::strcmp(q, "max") != 0 && period > 0) {
-                const double quota = std::atof(q) / period;
-                if (quota > 0 && quota < c) c = quota;
-            }
-            std::fclose(f);
-        } else {  // cgroup v1: quota in microseconds per period, -1 = unlimited
-            double quota = -1, period = 0;
-            if (FILE* fq = std::fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
-                if (std::fscanf(fq, "%lf", &quota) != 1) quota = -1;
-                std::fclose(fq);
-            }
-            if (FILE* fp = std::fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
-                if (std::fscanf(fp, "%lf", &period) != 1) period = 0;
-                std::fclose(fp);
-            }
-            if (quota > 0 && period > 0 && quota / period < c) c = quota / period;
-        }
-        return c < 1 ? 1.0 : c;
-    }();
-    return cpus;
-}
-
-static int staging_lanes_env() {  // P252_HOST_LANES: 0 = not set
-    static const int lanes = [] {
-        if (const char* e = std::getenv("P252_HOST_LANES")) {
-            const int v = std::atoi(e);
-            return v < 1 ? 1 : (v > 32 ? 32 : v);
-        }
-        return 0;
-    }();
-    return lanes;
-}
-
-// staging lanes of ONE context driven on its own
-static int staging_lanes_wanted() {
-    if (staging_lanes_env()) return staging_lanes_env();
-    // Three lanes x two slots keep the PCIe link busy; MORE lanes are slower on the benchmark box (16 CPUs of cgroup
-    // budget, 256 visible): 3 lanes 3.6-3.8e8 digests/s, 6 lanes 3.1-3.3e8, 12 lanes 2.0-2.2e8
-    // (profiles/r02_host_path.txt).  Two when the process may use fewer than four CPUs.
-    return cpu_budget() < 4 ? 2 : 3;
-}
-
-// staging lanes per context when n_ctx contexts are driven at once (p252_*_multi: one driver thread per context, which
-// is that context's first lane, plus its extra lanes): the contexts SHARE the CPU budget — 8 contexts x 3 lanes under a
-// 16-CPU quota is the 24-worker configuration the single-context sweep measured at half speed.
-// A lane is host-memcpy work: ONE worker moves 1.66e8 digests/s (26.5 GB/s, profiles/r03_host_path_multi.txt: one context,
-// one lane), a GPU takes 4.1e8, so a GPU wants 2.5 workers and the whole budget is worth using: lanes = floor(CPUs / n_ctx),
-// at most the single-context optimum of 3, at least 1 — never more workers than CPUs (they sleep on blocking-sync events
-// while their chunks are in flight; only the copies cost CPU time).
-static int staging_lanes_per_ctx(size_t n_ctx) {
-    if (staging_lanes_env()) return staging_lanes_env();
-    if (n_ctx <= 1) return staging_lanes_wanted();
-    int per = (int)(cpu_budget() / (double)n_ctx);
-    return per < 1 ? 1 : (per > 3 ? 3 : per);
-}
-
-// Runs `launch(d_in[], d_out[], first_item, count, stream)` over n items in chunks of `chunk`, streaming the input arrays
-// in and the output arrays out through the staging lanes.  d_in[a] / d_out[a] are the device copies of chunk-local slices
-// of ins[a] / outs[a] (256-byte aligned).  `outs` may be empty (results stay on the device: the launch writes them itself).
-template <class Launch>
-static int staged_run(p252_ctx* ctx, size_t n, size_t chunk, const std::vector<HostSpan>& ins, const std::vector<HostSpan>& outs,
-                      Launch&& launch) {
-    const size_t n_chunks = (n + chunk - 1) / chunk;
-    const int lanes_wanted = ctx->lane_budget > 0 ? ctx->lane_budget : staging_lanes_wanted();
-    const int n_lanes = (int)(n_chunks < (size_t)lanes_wanted ? n_chunks : (size_t)lanes_wanted);
-    if ((int)ctx->lanes.size() < n_lanes) ctx->lanes.resize(n_lanes);
-    auto layout = [&](const std::vector<HostSpan>& spans, std::vector<size_t>& offs) {  // sub-buffer offsets, total bytes
-        size_t total = 0;
-        for (const HostSpan& sp : spans) {
-            offs.push_back(total);
-            total += (chunk * sp.stride + 255) & ~(size_t)255;
-        }
-        return total ? total : (size_t)256;
-    };
-    std::vector<size_t> in_off, out_off;
-    const size_t in_chunk_b = layout(ins, in_off), out_chunk_b = layout(outs, out_off);
-    for (int l = 0; l < n_lanes; ++l) {
-        p252_ctx::Lane& L = ctx->lanes[l];
-        if (!L.st) HIP_TRY(ctx, hipStreamCreateWithFlags(&L.st, hipStreamNonBlocking));
-        for (auto& S : L.slot) {
-            if (!S.done) HIP_TRY(ctx, hipEventCreateWithFlags(&S.done, hipEventBlockingSync | hipEventDisableTiming));
-            if (S.in_cap < in_chunk_b) {
-                if (S.h_in) (void)hipHostFree(S.h_in);
-                if (S.d_in) (void)hipFree(S.d_in);
-                S.h_in = S.d_in = nullptr;
-                S.in_cap = 0;
-                HIP_TRY(ctx, hipHostMalloc(&S.h_in, in_chunk_b, hipHostMallocDefault));
-                HIP_TRY(ctx, hipMalloc(&S.d_in, in_chunk_b));
-                S.in_cap = in_chunk_b;
-            }
-            if (S.out_cap < out_chunk_b) {
-                if (S.h_out) (void)hipHostFree(S.h_out);
-                if (S.d_out) (void)hipFree(S.d_out);
-                S.h_out = S.d_out = nullptr;
-                S.out_cap = 0;
-                HIP_TRY(ctx, hipHostMalloc(&S.h_out, out_chunk_b, hipHostMallocDefault));
-                HIP_TRY(ctx, hipMalloc(&S.d_out, out_chunk_b));
-                S.out_cap = out_chunk_b;
-            }
-            if (S.in_dirty < in_chunk_b) S.in_dirty = in_chunk_b;
-            if (S.out_dirty < out_chunk_b) S.out_dirty = out_chunk_b;
-        }
-    }
-    std::atomic<size_t> next{0};
-    std::atomic<int> status{P252_OK};
-    std::mutex err_mu;
-    std::string err;
-    auto work = [&](int l) {
-        p252_ctx::Lane& L = ctx->lanes[l];
-        auto bad = [&](const char* what, hipError_t e) {
-            std::lock_guard<std::mutex> lk(err_mu);
-            if (status.load() == P252_OK) {
-                status.store(P252_ERR_HIP);
-                err = std::string(what) + ": " + hipGetErrorString(e);
-            }
-        };
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e != hipSuccess) return bad("hipSetDevice", e);
-        long pending[2] = {-1, -1};  // chunk whose results sit (or will sit) in the slot's h_out
-        auto retire = [&](int k) {    // wait for slot k's chunk and hand its outputs to the caller
-            if (pending[k] < 0) return true;
-            const hipError_t w = hipEventSynchronize(L.slot[k].done);
-            if (w != hipSuccess) { bad("event sync", w); return false; }
-            const size_t off = (size_t)pending[k] * chunk, cnt = n - off < chunk ? n - off : chunk;
-            for (size_t a = 0; a < outs.size(); ++a)
-                std::memcpy(outs[a].dst + off * outs[a].stride, static_cast<char*>(L.slot[k].h_out) + out_off[a], cnt * outs[a].stride);
-            pending[k] = -1;
-            return true;
-        };
-        std::vector<const void*> d_in(ins.size());
-        std::vector<void*> d_out(outs.size());
-        int k = 0;
-        for (;;) {
-            const size_t c = next.fetch_add(1);
-            if (c >= n_chunks || status.load() != P252_OK) break;
-            if (!retire(k)) return;
-            p252_ctx::Slot& S = L.slot[k];
-            const size_t off = c * chunk, cnt = n - off < chunk ? n - off : chunk;
-            for (size_t a = 0; a < ins.size(); ++a) {
-                char* h = static_cast<char*>(S.h_in) + in_off[a];
-                char* d = static_cast<char*>(S.d_in) + in_off[a];
-                std::memcpy(h, ins[a].src + off * ins[a].stride, cnt * ins[a].stride);
-                e = hipMemcpyAsync(d, h, cnt * ins[a].stride, hipMemcpyHostToDevice, L.st);
-                if (e != hipSuccess) return bad("H2D", e);
-                d_in[a] = d;
-            }
-            for (size_t a = 0; a < outs.size(); ++a) d_out[a] = static_cast<char*>(S.d_out) + out_off[a];
-            e = launch(d_in.data(), d_out.data(), off, cnt, L.st);
-            if (e != hipSuccess) return bad("kernel launch", e);
-            for (size_t a = 0; a < outs.size(); ++a) {
-                e = hipMemcpyAsync(static_cast<char*>(S.h_out) + out_off[a], d_out[a], cnt * outs[a].stride, hipMemcpyDeviceToHost, L.st);
-                if (e != hipSuccess) return bad("D2H", e);
-            }
-            e = hipEventRecord(S.done, L.st);
-            if (e != hipSuccess) return bad("event record", e);
-            pending[k] = (long)c;
-            k ^= 1;
-        }
-        // drain, older chunk first (slot k holds the older one)
-        if (!retire(k)) return;
-        retire(k ^ 1);
-    };
-    std::vector<std::thread> pool;
-    for (int l = 1; l < n_lanes; ++l) pool.emplace_back(work, l);
-    work(0);
-    for (auto& t : pool) t.join();
-    if (status.load() != P252_OK) {
-        for (int l = 0; l < n_lanes; ++l) (void)hipStreamSynchronize(ctx->lanes[l].st);  // never leave work in flight on the staging buffers
-        return fail(ctx, status.load(), err);
-    }
-    return P252_OK;
-}
-
-// items per chunk so that a chunk moves about P252_HOST_CHUNK_MB (default 8) MiB, a multiple of the block size
-static size_t staging_chunk_items(size_t bytes_per_item) {
-    static const size_t chunk_bytes_target = [] {
-        const char* e = std::getenv("P252_HOST_CHUNK_MB");
-        const int mb = e ? std::atoi(e) : 8;
-        return (size_t)(mb < 1 ? 1 : (mb > 256 ? 256 : mb)) << 20;
-    }();
-    size_t chunk = chunk_bytes_target / (bytes_per_item ? bytes_per_item : 1);
-    if (chunk < 4096) chunk = 4096;
-    return chunk & ~(size_t)255;
-}
-
-// n sponge hashes through the staging lanes.  d_resident_out != NULL: the outputs stay on the device (item i at
-// d_resident_out + i * out_len * 32) — the first level of a tree built from host leaves; `out` is then unused.
-static int hash_batch_staged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, size_t in_len, size_t out_len,
-                             uint64_t* out, size_t n, size_t chunk, char* d_resident_out = nullptr, bool trunc250 = false) {
-    const TagArg targ = tag_arg(tag);
-    const bool single = in_len == 4 && out_len == 1, pair = in_len == 2 && out_len == 1;
-    std::vector<HostSpan> ins = {{reinterpret_cast<const char*>(in), nullptr, in_len * 32}}, outs;
-    if (!d_resident_out) outs.push_back({nullptr, reinterpret_cast<char*>(out), out_len * 32});
-    return staged_run(ctx, n, chunk, ins, outs, [&](const void* const* d_in, void* const* d_out, size_t off, size_t cnt, hipStream_t st) {
-        void* d_dst = d_resident_out ? static_cast<void*>(d_resident_out + off * out_len * 32) : d_out[0];
-        if (single) return launch_merkle4(ctx->d_tab, targ, d_in[0], 4 * cnt, d_dst, cnt, st, 4, 0, trunc250);
-        if (pair) return launch_merkle4(ctx->d_tab, targ, d_in[0], 2 * cnt, d_dst, cnt, st, 2, 0, trunc250);
-        return launch_sponge(ctx->d_tab, targ, d_in[0], (unsigned)in_len, (unsigned)out_len, d_dst, cnt, st, trunc250);
-    });
-}
-}  // extern "C++"
-
-int p252_permute_batch(p252_ctx* ctx, const uint64_t* states, uint64_t* out, size_t n) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n == 0) return P252_OK;
-    if (!states || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "permute: NULL buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = n * P252_HADES_WIDTH * 32;
-    {
-        const size_t chunk = staging_chunk_items(P252_HADES_WIDTH * 32);
-        if (n >= 2 * chunk && !(is_pinned(states) && is_pinned(out)))  // large pageable batch: through the staging lanes
-            return staged_run(ctx, n, chunk, {{reinterpret_cast<const char*>(states), nullptr, P252_HADES_WIDTH * 32}},
-                              {{nullptr, reinterpret_cast<char*>(out), P252_HADES_WIDTH * 32}},
-                              [&](const void* const* d_in, void* const* d_out, size_t, size_t cnt, hipStream_t st) {
-                                  return launch_permute(ctx->d_tab, d_in[0], d_out[0], cnt, st);
-                              });
-    }
-    int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, bytes);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, bytes);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_in, states, bytes, hipMemcpyHostToDevice));
-    rc = p252_permute_batch_device(ctx, ctx->d_in, ctx->d_out, n, nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_out, bytes, hipMemcpyDeviceToHost));
-    return P252_OK;
-}
-
-
-static int hash_batch_host_impl(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, size_t in_len, size_t out_len,
-                                uint64_t* out, size_t n, bool trunc250) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (in_len == 0 || out_len == 0)
-        return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash: in_len and out_len must be > 0");
-    if (in_len > 0x7fffffffu || out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash: length too large");
-    if (n == 0) return P252_OK;
-    if (!tag || !in || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash: NULL buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t in_bytes = n * in_len * 32, out_bytes = n * out_len * 32;
-    // P252_HOST_PIPELINE (developer switch): 0 = one serial copy each way, anything else (default) = pipelined
-    static const int mode = [] {
-        const char* e = std::getenv("P252_HOST_PIPELINE");
-        return e ? std::atoi(e) : 2;
-    }();
-    const size_t chunk = staging_chunk_items((in_len > out_len ? in_len : out_len) * 32);
-    if (mode == 0 || n < 2 * chunk) {
-        int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes);
-        if (rc) return rc;
-        rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpy(ctx->d_in, in, in_bytes, hipMemcpyHostToDevice));
-        rc = hash_batch_device_impl(ctx, tag, ctx->d_in, in_len, out_len, ctx->d_out, n, nullptr, trunc250);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpy(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost));
-        return P252_OK;
-    }
-    // caller memory that is not page-locked on BOTH sides goes through the library's own staging lanes
-    if (!is_pinned(in) || !is_pinned(out)) return hash_batch_staged(ctx, tag, in, in_len, out_len, out, n, chunk, nullptr, trunc250);
-    // page-locked on both sides (p252_host_alloc / p252_host_register): zero-copy DMA, chunks round-robin over 3
-    // streams so that the H2D copy of chunk c+1, the kernel of chunk c and the D2H copy of chunk c-1 overlap
-    int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes);
-    if (rc) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (!ctx->streams[i]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->streams[i], hipStreamNonBlocking));
-    int status = P252_OK;
-    std::string err;
-    size_t c = 0;
-    for (size_t off = 0; off < n && status == P252_OK; off += chunk, ++c) {
-        const size_t cnt = n - off < chunk ? n - off : chunk;
-        hipStream_t st = ctx->streams[c % 3];
-        const char* h_in = reinterpret_cast<const char*>(in) + off * in_len * 32;
-        char* h_out = reinterpret_cast<char*>(out) + off * out_len * 32;
-        char* d_in = static_cast<char*>(ctx->d_in) + off * in_len * 32;
-        char* d_out = static_cast<char*>(ctx->d_out) + off * out_len * 32;
-        hipError_t e = hipMemcpyAsync(d_in, h_in, cnt * in_len * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            int r2 = hash_batch_device_impl(ctx, tag, d_in, in_len, out_len, d_out, cnt, st, trunc250);
-            if (r2) { status = r2; err = ctx->err; break; }
-            e = hipMemcpyAsync(h_out, d_out, cnt * out_len * 32, hipMemcpyDeviceToHost, st);
-        }
-        if (e != hipSuccess) { status = P252_ERR_HIP; err = std::string("pipelined copy: ") + hipGetErrorString(e); }
-    }
-    for (int i = 0; i < 3; ++i) {
-        hipError_t e = hipStreamSynchronize(ctx->streams[i]);
-        if (e != hipSuccess && status == P252_OK) { status = P252_ERR_HIP; err = std::string("stream sync: ") + hipGetErrorString(e); }
-    }
-    if (status != P252_OK) return fail(ctx, status, err);
-    return P252_OK;
-}
-
-int p252_hash_batch(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, size_t in_len, size_t out_len,
-                    uint64_t* out, size_t n) {
-    return hash_batch_host_impl(ctx, tag, in, in_len, out_len, out, n, false);
-}
-
-int p252_hash_batch_truncated(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, size_t in_len, size_t out_len,
-                              uint64_t* out_raw, size_t n) {
-    return hash_batch_host_impl(ctx, tag, in, in_len, out_len, out_raw, n, true);
-}
-
 // ---- messages of different lengths in one call (ragged.hip): the sort's order array and bucket counters live in the scratch
 // pair of the calling stream (as the verify path's re-hashed roots), so calls on different streams of one context never share them
 static int hash_ragged_device_impl(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
@@ -889,148 +550,7 @@ int p252_hash_ragged_truncated_device(p252_ctx* ctx, const void* d_tags, size_t 
     return hash_ragged_device_impl(ctx, d_tags, max_len, d_in, d_offsets, out_len, d_out_raw, n, d_n_bad, hip_stream, true);
 }
 
-// host buffers: every message is checked here first, then [messages | tags | offsets rebased to 0] go to the context's grow-only
-// d_in in one copy and the outputs come back from d_out — synchronous, no chunked pipeline
-static int hash_ragged_host_impl(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
-                                 size_t out_len, uint64_t* out, size_t n, bool trunc250) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (out_len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: out_len must be > 0");
-    if (out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: out_len too large");
-    if (n == 0) return P252_OK;
-    if (max_len == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: max_len must be > 0");
-    if (!tags || !offsets || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
-    for (size_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i])
-            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: offsets decrease at message " + std::to_string(i));
-        const uint64_t len = offsets[i + 1] - offsets[i];
-        if (len == 0)  // a zero-length absorb is an invalid io-pattern (dusk-safe; Hash::finalize panics, hash.rs:134-137)
-            return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: message " + std::to_string(i) + " is empty");
-        if (len > max_len)
-            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: message " + std::to_string(i) + " is longer than max_len");
-    }
-    if (!in) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
-    const uint64_t total = offsets[n] - offsets[0];
-    if (total > SIZE_MAX / 64 || max_len > SIZE_MAX / 64 || n > SIZE_MAX / 64 / out_len)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: size overflow");
-    const size_t in_bytes = (size_t)total * 32, tag_bytes = max_len * 32, off_bytes = (n + 1) * 8, out_bytes = n * out_len * 32;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_bytes + tag_bytes + off_bytes);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_bytes);
-    if (rc) return rc;
-    std::vector<uint64_t> rebased(offsets, offsets + n + 1);
-    for (auto& o : rebased) o -= offsets[0];
-    char* d = static_cast<char*>(ctx->d_in);
-    HIP_TRY(ctx, hipMemcpy(d, in + offsets[0] * 4, in_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d + in_bytes, tags, tag_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d + in_bytes + tag_bytes, rebased.data(), off_bytes, hipMemcpyHostToDevice));
-    rc = hash_ragged_device_impl(ctx, d + in_bytes, max_len, d, d + in_bytes + tag_bytes, out_len, ctx->d_out, n, nullptr, nullptr, trunc250);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost));
-    return P252_OK;
-}
-
-int p252_hash_ragged(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets, size_t out_len,
-                     uint64_t* out, size_t n) {
-    return hash_ragged_host_impl(ctx, tags, max_len, in, offsets, out_len, out, n, false);
-}
-
-int p252_hash_ragged_truncated(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
-                               size_t out_len, uint64_t* out_raw, size_t n) {
-    return hash_ragged_host_impl(ctx, tags, max_len, in, offsets, out_len, out_raw, n, true);
-}
-
-static int merkle_tree_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
-                            uint64_t root[4], uint64_t* levels) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: n_leaves must be > 0");
-    if (!tag || !leaves || !root) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: NULL buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t leaf_bytes = n_leaves * 32;
-    const size_t lvl_bytes = levels_len(n_leaves, arity) * 32;
-    int rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, (levels ? lvl_bytes : 0) + 32);
-    if (rc) return rc;
-    char* d_root = static_cast<char*>(ctx->d_out);
-    char* d_levels = levels ? d_root + 32 : nullptr;
-    const size_t n_l1 = n_leaves / arity;
-    const size_t chunk_nodes = (((size_t)8 << 20) / (arity * 32)) & ~(size_t)255;  // 8 MiB of leaves per chunk
-    if (n_leaves % arity == 0 && n_l1 >= 4 * chunk_nodes && !is_pinned(leaves)) {
-        // Big tree from pageable host memory (512 MiB of leaves at 2^24): the upload would take longer than the whole build.
-        // The first level is hashed chunk by chunk WHILE the leaves stream in through the staging lanes (its nodes stay on
-        // the device); the remaining levels run as usual.  The leaves themselves are never resident as a whole.
-        rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, n_l1 * 32);
-        if (rc) return rc;
-        char* d_l1 = levels ? d_levels : static_cast<char*>(ctx->d_in);
-        rc = hash_batch_staged(ctx, tag, leaves, arity, 1, nullptr, n_l1, chunk_nodes, d_l1);
-        if (rc) return rc;
-        rc = merkle_tree_device(ctx, arity, tag, d_l1, n_l1, d_root, levels ? d_levels + n_l1 * 32 : nullptr, nullptr);
-        if (rc) return rc;
-    } else {
-        rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, leaf_bytes);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpy(ctx->d_in, leaves, leaf_bytes, hipMemcpyHostToDevice));
-        rc = merkle_tree_device(ctx, arity, tag, ctx->d_in, n_leaves, d_root, d_levels, nullptr);
-        if (rc) return rc;
-    }
-    HIP_TRY(ctx, hipMemcpy(root, d_root, 32, hipMemcpyDeviceToHost));  // (also orders the download below behind the build)
-    if (levels && lvl_bytes) {
-        const size_t n_sc = lvl_bytes / 32, chunk = staging_chunk_items(32);
-        if (n_sc >= 2 * chunk && !is_pinned(levels)) {
-            // all levels of a big tree (171 MiB at 2^24 leaves) into pageable memory: chunk by chunk through the staging lanes
-            rc = staged_run(ctx, n_sc, chunk, {}, {{nullptr, reinterpret_cast<char*>(levels), 32}},
-                            [&](const void* const*, void* const* d_out, size_t off, size_t cnt, hipStream_t st) {
-                                return hipMemcpyAsync(d_out[0], d_levels + off * 32, cnt * 32, hipMemcpyDeviceToDevice, st);
-                            });
-            if (rc) return rc;
-        } else {
-            HIP_TRY(ctx, hipMemcpy(levels, d_levels, lvl_bytes, hipMemcpyDeviceToHost));
-        }
-    }
-    return P252_OK;
-}
-
-int p252_merkle4_tree(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
-                      uint64_t root[4], uint64_t* levels) {
-    return merkle_tree_host(ctx, 4, tag, leaves, n_leaves, root, levels);
-}
-
-int p252_merkle2_tree(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
-                      uint64_t root[4], uint64_t* levels) {
-    return merkle_tree_host(ctx, 2, tag, leaves, n_leaves, root, levels);
-}
-
-// Forest from HOST leaves (pageable memory is fine).  Large forests: the FIRST level — three quarters of all permutations — is
-// hashed chunk by chunk while the leaves stream in through the staging lanes (8 MiB chunks; its nodes stay on the device, the
-// leaves are never resident as a whole), then the upper levels run ONCE, one launch per level across all trees, so their
-// latency-bound launches are paid once per forest and not once per chunk (a first version that built a whole forest per
-// 32-MiB chunk ran at 2.5e8 perm/s: every chunk paid the five narrow levels).  Trees are independent: no exchange.
-int p252_merkle4_forest(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_trees, size_t leaves_per_tree, uint64_t* roots) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_trees == 0) return P252_OK;
-    if (!power_of_4(leaves_per_tree)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: leaves_per_tree must be arity^k");
-    if (n_trees > (SIZE_MAX / 32) / leaves_per_tree) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: size overflow");
-    if (!tag || !leaves || !roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: NULL buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n_leaves = n_trees * leaves_per_tree, n_l1 = n_leaves / 4;
-    const size_t chunk_nodes = (((size_t)8 << 20) / (4 * 32)) & ~(size_t)255;  // 8 MiB of leaves per chunk, as the tree's host path
-    int rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, n_trees * 32);
-    if (rc) return rc;
-    if (leaves_per_tree >= 4 && n_l1 >= 4 * chunk_nodes && !is_pinned(leaves)) {
-        rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, n_l1 * 32);
-        if (rc) return rc;
-        rc = hash_batch_staged(ctx, tag, leaves, 4, 1, nullptr, n_l1, chunk_nodes, static_cast<char*>(ctx->d_in));
-        if (rc) return rc;
-        rc = forest_device(ctx, 4, tag, ctx->d_in, n_trees, leaves_per_tree / 4, ctx->d_out, nullptr, nullptr);
-    } else {  // small forest (or page-locked leaves: the DMA runs at PCIe speed anyway): one upload, one build
-        rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, n_leaves * 32);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpy(ctx->d_in, leaves, n_leaves * 32, hipMemcpyHostToDevice));
-        rc = forest_device(ctx, 4, tag, ctx->d_in, n_trees, leaves_per_tree, ctx->d_out, nullptr, nullptr);
-    }
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(roots, ctx->d_out, n_trees * 32, hipMemcpyDeviceToHost));
-    return P252_OK;
-}
+// (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)
 
 // page-locked host memory for callers that want the host-buffer entry points at PCIe speed
 void* p252_host_alloc(size_t bytes) {
@@ -1258,47 +778,6 @@ int p252_merkle2_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_l
     return openings_device(ctx, 2, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_siblings, d_positions, d_n_bad, hip_stream);
 }
 
-int p252_merkle4_path_batch(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* siblings,
-                            const uint8_t* positions, size_t depth, uint64_t* roots, size_t n) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n == 0) return P252_OK;
-    if (!tag || !leaves || !roots || (depth && (!siblings || !positions)))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: NULL buffer");
-    for (size_t i = 0; i < n * depth; ++i)
-        if (positions[i] > 3) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: position outside 0..3");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (depth > 0xffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: depth too large");
-    if (depth) {
-        const size_t chunk = staging_chunk_items(64 + depth * 97);
-        if (n >= 2 * chunk) {  // large batch: leaves, sibling blocks and positions stream through the staging lanes
-            const TagArg targ = tag_arg(tag);
-            return staged_run(ctx, n, chunk,
-                              {{reinterpret_cast<const char*>(leaves), nullptr, 32},
-                               {reinterpret_cast<const char*>(siblings), nullptr, depth * 96},
-                               {reinterpret_cast<const char*>(positions), nullptr, depth}},
-                              {{nullptr, reinterpret_cast<char*>(roots), 32}},
-                              [&](const void* const* d_in, void* const* d_out, size_t, size_t cnt, hipStream_t st) {
-                                  return launch_merkle4_path(ctx->d_tab, targ, d_in[0], d_in[1], d_in[2], (unsigned)depth, d_out[0], cnt, st);
-                              });
-        }
-    }
-    const size_t leaf_b = n * 32, sib_b = n * depth * 96, pos_b = (n * depth + 15) & ~(size_t)15;
-    int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, leaf_b + sib_b + pos_b + 16);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, leaf_b);
-    if (rc) return rc;
-    char* base = static_cast<char*>(ctx->d_in);
-    HIP_TRY(ctx, hipMemcpy(base, leaves, leaf_b, hipMemcpyHostToDevice));
-    if (depth) {
-        HIP_TRY(ctx, hipMemcpy(base + leaf_b, siblings, sib_b, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(base + leaf_b + sib_b, positions, n * depth, hipMemcpyHostToDevice));
-    }
-    rc = p252_merkle4_path_batch_device(ctx, tag, base, base + leaf_b, base + leaf_b + sib_b, depth, ctx->d_out, n, nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(roots, ctx->d_out, leaf_b, hipMemcpyDeviceToHost));
-    return P252_OK;
-}
-
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----
 // The sponge-call sequence dusk_safe::encrypt makes, as a table (one word per call: kind << 29 | len; kinds as in
 // kernels.hip k_crypt).  Two candidates (include/poseidon252_hip.h): P252_CRYPT_STREAM — squeeze all `len` masks, then
@@ -1324,10 +803,11 @@ static std::vector<uint32_t> crypt_program(int variant, size_t len) {
     return prog;
 }
 
-static bool crypt_variant_ok(int variant) { return variant == P252_CRYPT_STREAM || variant == P252_CRYPT_DUPLEX; }
+extern "C++" {
+bool p252host::crypt_variant_ok(int variant) { return variant == P252_CRYPT_STREAM || variant == P252_CRYPT_DUPLEX; }
 
 // the sponge-call table of (variant, len) on the device (kept until another one is asked for)
-static int prepare_prog(p252_ctx* ctx, int variant, size_t len) {
+int p252host::prepare_prog(p252_ctx* ctx, int variant, size_t len) {
     if (ctx->prog_variant == variant && ctx->prog_len == len) return P252_OK;
     const std::vector<uint32_t> prog = crypt_program(variant, len);
     // the previous program may still be read by a kernel in flight on another stream: drain before replacing it
@@ -1340,6 +820,7 @@ static int prepare_prog(p252_ctx* ctx, int variant, size_t len) {
     ctx->prog_calls = (unsigned)prog.size();
     return P252_OK;
 }
+}  // extern "C++"
 
 static int crypt_device(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const void* d_in, const void* d_secrets,
                         const void* d_nonces, size_t len, void* d_out, void* d_ok, size_t n, void* hip_stream) {
@@ -1368,97 +849,6 @@ int p252_encrypt_batch_device(p252_ctx* ctx, int variant, const uint64_t tag[4],
 int p252_decrypt_batch_device(p252_ctx* ctx, int variant, const uint64_t tag[4], const void* d_ciphers, const void* d_secrets,
                               const void* d_nonces, size_t len, void* d_messages, void* d_ok, size_t n, void* hip_stream) {
     return crypt_device(ctx, variant, true, tag, d_ciphers, d_secrets, d_nonces, len, d_messages, d_ok, n, hip_stream);
-}
-
-static int crypt_host_run(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const uint64_t* in, const uint64_t* secrets,
-                          const uint64_t* nonces, size_t len, uint64_t* out, uint8_t* ok, size_t n, size_t* used_in, size_t* used_out,
-                          bool* used_lanes) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: unknown variant");
-    if (len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "encrypt/decrypt: empty message");
-    if (n == 0) return P252_OK;
-    if (!tag || !in || !secrets || !nonces || !out || (decrypt && !ok))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: NULL buffer");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    {
-        const size_t in_stride = (decrypt ? len + 1 : len) * 32, out_stride = (decrypt ? len : len + 1) * 32;
-        const size_t chunk = staging_chunk_items(in_stride + out_stride + 96);
-        if (n >= 2 * chunk && len < 0x1ffffff0u) {  // large batch: through the staging lanes, chunk by chunk
-            // the call table is uploaded once, here; the lanes then only launch (no shared state, no lock, and a failure
-            // keeps its own HIP error string)
-            int rc0 = prepare_prog(ctx, variant, len);
-            if (rc0) return rc0;
-            const TagArg targ = tag_arg(tag);
-            const uint32_t* d_prog = ctx->d_prog;
-            const unsigned n_calls = ctx->prog_calls;
-            std::vector<HostSpan> ins = {{reinterpret_cast<const char*>(in), nullptr, in_stride},
-                                         {reinterpret_cast<const char*>(secrets), nullptr, 64},
-                                         {reinterpret_cast<const char*>(nonces), nullptr, 32}};
-            std::vector<HostSpan> outs = {{nullptr, reinterpret_cast<char*>(out), out_stride}};
-            if (decrypt) outs.push_back({nullptr, reinterpret_cast<char*>(ok), 1});
-            *used_lanes = true;
-            return staged_run(ctx, n, chunk, ins, outs,
-                              [&](const void* const* d_in, void* const* d_out, size_t, size_t cnt, hipStream_t st) {
-                                  return launch_crypt(decrypt, ctx->d_tab, targ, d_in[0], d_in[1], d_in[2], (unsigned)len, d_out[0],
-                                                      decrypt ? d_out[1] : nullptr, cnt, d_prog, n_calls, st);
-                              });
-        }
-    }
-    const size_t in_b = n * (decrypt ? len + 1 : len) * 32, out_b = n * (decrypt ? len : len + 1) * 32;
-    const size_t sec_b = n * 64, non_b = n * 32, ok_b = (n + 15) & ~(size_t)15;
-    int rc = ensure(ctx, &ctx->d_in, &ctx->d_in_cap, in_b + sec_b + non_b);
-    if (rc) return rc;
-    rc = ensure(ctx, &ctx->d_out, &ctx->d_out_cap, out_b + ok_b);
-    if (rc) return rc;
-    char* di = static_cast<char*>(ctx->d_in);
-    char* dout = static_cast<char*>(ctx->d_out);
-    *used_in = in_b + sec_b + non_b;
-    *used_out = out_b + ok_b;
-    HIP_TRY(ctx, hipMemcpy(di, in, in_b, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(di + in_b, secrets, sec_b, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(di + in_b + sec_b, nonces, non_b, hipMemcpyHostToDevice));
-    rc = crypt_device(ctx, variant, decrypt, tag, di, di + in_b, di + in_b + sec_b, len, dout, dout + out_b, n, nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, dout, out_b, hipMemcpyDeviceToHost));
-    if (decrypt) HIP_TRY(ctx, hipMemcpy(ok, dout + out_b, n, hipMemcpyDeviceToHost));
-    return P252_OK;
-}
-
-// the host-buffer encrypt / decrypt: whatever the call copied into library-owned memory — shared secrets, nonces, plaintexts
-// and ciphertexts in the context's device scratch or in the staging lanes (page-locked host + device chunks) — is cleared
-// before it returns, on success and on failure (the reference: zeroize, Cargo.toml:14; dusk-safe zeroizes a finished sponge)
-static int crypt_host(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const uint64_t* in, const uint64_t* secrets,
-                      const uint64_t* nonces, size_t len, uint64_t* out, uint8_t* ok, size_t n) {
-    size_t used_in = 0, used_out = 0;
-    bool used_lanes = false;
-    const int rc = crypt_host_run(ctx, variant, decrypt, tag, in, secrets, nonces, len, out, ok, n, &used_in, &used_out, &used_lanes);
-    if (ctx && (used_in || used_out || used_lanes)) {
-        const std::string msg = ctx->err;
-        // nothing of THIS call may still be in flight on what is cleared: the call ran on the staging lanes' streams (non-blocking
-        // streams) or on the null stream — those are synchronised, not the device (other contexts and streams keep running),
-        // and only the bytes the lanes may have written are cleared, not their whole capacity
-        hipError_t e = hipSuccess;
-        for (auto& l : ctx->lanes)
-            if (used_lanes && l.st && e == hipSuccess) e = hipStreamSynchronize(l.st);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess) e = wipe_span(ctx->d_in, used_in);
-        if (e == hipSuccess) e = wipe_span(ctx->d_out, used_out);
-        if (e == hipSuccess && used_lanes) e = wipe_lanes(ctx, /*dirty_only=*/true);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess && rc == P252_OK) return fail(ctx, P252_ERR_HIP, std::string("encrypt/decrypt: wiping the scratch failed: ") + hipGetErrorString(e));
-        ctx->err = msg;
-    }
-    return rc;
-}
-
-int p252_encrypt_batch(p252_ctx* ctx, int variant, const uint64_t tag[4], const uint64_t* messages, const uint64_t* secrets,
-                       const uint64_t* nonces, size_t len, uint64_t* ciphers, size_t n) {
-    return crypt_host(ctx, variant, false, tag, messages, secrets, nonces, len, ciphers, nullptr, n);
-}
-
-int p252_decrypt_batch(p252_ctx* ctx, int variant, const uint64_t tag[4], const uint64_t* ciphers, const uint64_t* secrets,
-                       const uint64_t* nonces, size_t len, uint64_t* messages, uint8_t* ok, size_t n) {
-    return crypt_host(ctx, variant, true, tag, ciphers, secrets, nonces, len, messages, ok, n);
 }
 
 // shared by p252_tag and p252_encryption_tag: tag = hash_to_scalar(io-words (BE u32) || domain separator (BE u64)),

@@ -1,5 +1,5 @@
-// ctx.hpp — the context object and the few host-side helpers shared by api.cpp (the C ABI) and comm.cpp (the RCCL
-// communicator of the multi-GPU entry points).  Internal: nothing here is part of the ABI.
+// ctx.hpp — the context object and the few host-side helpers shared by api.cpp (the C ABI), host_io.cpp (its host-buffer entry
+// points) and comm.cpp (the RCCL communicator of the multi-GPU entry points).  Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/poseidon252_hip.h"
+#include "kernels.h"
 
 struct p252_comm;
 
@@ -52,6 +53,13 @@ struct p252_ctx {
     };
     std::vector<Lane> lanes;
     int lane_budget = 0;  // > 0: staging lanes this call may use (set by the p252_*_multi drivers, which share the CPU quota)
+    // what the host-buffer transfers (host_io.cpp) put in library-owned memory since the last reset: bytes of d_in / d_out, and
+    // whether the staging lanes were used — the extent a host-buffer encrypt / decrypt wipes before it returns
+    struct IoUse {
+        size_t in = 0, out = 0;
+        bool lanes = false;
+    };
+    IoUse io_used;
     // encryption: the sponge-call program of the last (variant, message_len) used, uploaded once (k_crypt interprets it)
     uint32_t* d_prog = nullptr;
     size_t d_prog_cap = 0;
@@ -72,6 +80,15 @@ int level_set_done(p252_ctx* ctx, p252_ctx::LevelSet* set);
 const std::vector<int32_t>& host_tables();
 bool power_of_4(size_t v);
 int check_ctxs(p252_ctx* const* ctxs, size_t n_ctx);
+// kernel argument for the tag: the scalar itself and lane 0's first-round S-box output (the digest kernels start there)
+p252::TagArg tag_arg(const uint64_t tag[4]);
+size_t levels_len(size_t n_leaves, size_t arity);  // nodes above the leaves of a tree
+bool crypt_variant_ok(int variant);
+int prepare_prog(p252_ctx* ctx, int variant, size_t len);  // the encryption call table of (variant, len) on the device
+// secret hygiene (api.cpp): a device span cleared on the null stream; the staging lanes (host and device halves)
+hipError_t wipe_span(void* d, size_t bytes);
+hipError_t wipe_lanes(p252_ctx* ctx, bool dirty_only = false);
+int staging_lanes_per_ctx(size_t n_ctx);  // host_io.cpp
 // the level-by-level tree build on one device (api.cpp): asynchronous on hip_stream, root (32 B) written to d_root
 int merkle_tree_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, void* d_root,
                        void* d_levels, void* hip_stream);

@@ -153,3 +153,109 @@ def test_other_host_entry_points_stream_large_batches(gpu_ctx, oracle_mod):
         good = np.ones(n, dtype=bool)
         good[::5000] = False
         assert np.array_equal(dec[good], msgs[good])
+
+
+def _pinned_copy(a):
+    """a page-locked (p252_host_alloc) copy of a uint64 array, as PinnedScalars"""
+    from poseidon252_amd.hash import PinnedScalars
+    p = PinnedScalars(a.size // 4)
+    p.array[:] = a.reshape(-1, 4)
+    return p
+
+
+def test_large_calls_with_every_array_pinned(gpu_ctx, oracle_mod):
+    """p252_permute_batch (one-shot route when both sides are page-locked), p252_merkle4_path_batch and p252_encrypt_batch
+    (staged either way) on multi-chunk batches whose every array is page-locked: the bytes of the pageable route and the oracle's"""
+    import ctypes
+    import poseidon252_amd as P
+    from poseidon252_amd import _lib
+    from poseidon252_amd.encryption import STREAM, encrypt_batch, encryption_tag
+    from poseidon252_amd.hash import PinnedScalars
+    L, u64p, u8p = _lib.lib(), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8)
+    ptr = lambda p: p.array.ctypes.data_as(u64p)
+    n = 3 * 52224 + 1234
+    st = oracle_mod.fill_random(0xa11, 5 * n).reshape(n, 5, 4)
+    ref = gpu_ctx.permute_batch(st)
+    p_in, p_out = _pinned_copy(st), PinnedScalars(5 * n)
+    assert L.p252_permute_batch(gpu_ctx._h, ptr(p_in), ptr(p_out), n) == 0
+    assert np.array_equal(p_out.array.reshape(ref.shape), ref)
+    idx = np.concatenate([np.arange(0, n, 7919), [52223, 52224, n - 1]])
+    assert np.array_equal(ref[idx], oracle_mod.permute_batch(st[idx]))
+    n, depth = 4 * 6656 + 77, 12
+    tag = P.merkle4_tag()
+    leaves = oracle_mod.fill_random(0xa12, n)
+    sibs = oracle_mod.fill_random(0xa13, n * depth * 3).reshape(n, depth, 3, 4)
+    pos = np.random.default_rng(7).integers(0, 4, size=(n, depth), dtype=np.uint8)
+    ref = gpu_ctx.merkle4_path_batch(tag, leaves, sibs, pos)
+    p_lv, p_sib, p_roots = _pinned_copy(leaves), _pinned_copy(sibs), PinnedScalars(n)
+    p_pos = PinnedScalars((n * depth + 31) // 32)
+    p_pos.array.view(np.uint8).reshape(-1)[:n * depth] = pos.reshape(-1)
+    assert L.p252_merkle4_path_batch(gpu_ctx._h, tag.ctypes.data_as(u64p), ptr(p_lv), ptr(p_sib), p_pos.array.ctypes.data_as(u8p), depth,
+                                     ptr(p_roots), n) == 0
+    assert np.array_equal(p_roots.array, ref)
+    idx = np.concatenate([np.arange(0, n, 997), [6655, 6656, n - 1]])
+    assert np.array_equal(ref[idx], oracle_mod.merkle4_path_batch(tag, leaves[idx], sibs[idx], pos[idx]))
+    ln, n = 2, 2 * 32768 + 999
+    msgs = oracle_mod.fill_random(0xa14, n * ln).reshape(n, ln, 4)
+    secrets = oracle_mod.fill_random(0xa15, 2 * n).reshape(n, 2, 4)
+    nonces = oracle_mod.fill_random(0xa16, n)
+    ref = encrypt_batch(msgs, secrets, nonces, ctx=gpu_ctx)
+    etag = encryption_tag(ln)
+    p_m, p_s, p_n, p_c = _pinned_copy(msgs), _pinned_copy(secrets), _pinned_copy(nonces), PinnedScalars(n * (ln + 1))
+    assert L.p252_encrypt_batch(gpu_ctx._h, STREAM, etag.ctypes.data_as(u64p), ptr(p_m), ptr(p_s), ptr(p_n), ln, ptr(p_c), n) == 0
+    assert np.array_equal(p_c.array.reshape(ref.shape), ref)
+    idx = np.concatenate([np.arange(0, n, 1009), [n - 1]])
+    assert np.array_equal(ref[idx], oracle_mod.encrypt_batch(etag, msgs[idx], secrets[idx], nonces[idx]))
+    for p in (p_in, p_out, p_lv, p_sib, p_roots, p_pos, p_m, p_s, p_n, p_c):
+        p.free()
+
+
+def test_pageable_in_pinned_out_hash(gpu_ctx, oracle_mod):
+    """a large hash from pageable input into a page-locked output goes through the staging lanes: same bytes"""
+    import poseidon252_amd as P
+    from poseidon252_amd.hash import PinnedScalars
+    hb = P.HashBatch(P.Domain.Merkle4, 4, ctx=gpu_ctx)
+    n = 3 * (1 << 17) + 55
+    x = oracle_mod.fill_random(0xa17, 4 * n).reshape(n, 4, 4)
+    ref = hb.digest(x)
+    pin_out = PinnedScalars(n)
+    got = gpu_ctx.hash_batch(hb.tag, x, 4, 1, out=pin_out.array)
+    assert np.array_equal(got.reshape(ref.shape), ref)
+    idx = np.concatenate([np.arange(0, n, 4999), [n - 1, (1 << 17) - 1, 1 << 17]])
+    assert np.array_equal(ref[idx], oracle_mod.hash_batch(hb.tag, x[idx], 4, 1))
+    pin_out.free()
+
+
+def test_host_pipeline_off_takes_the_one_shot_route(gpu_ctx, oracle_mod, tmp_path):
+    """P252_HOST_PIPELINE=0 (read once per process, so in a child): a large hash and a large path batch take one copy each way,
+    with the bytes of the pipelined route"""
+    import os
+    import subprocess
+    import sys
+    import poseidon252_amd as P
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hb = P.HashBatch(P.Domain.Merkle4, 4, ctx=gpu_ctx)
+    n = (1 << 18) + 777
+    x = oracle_mod.fill_random(0xa18, 4 * n).reshape(n, 4, 4)
+    m, depth = 4 * 6656 + 77, 12
+    tag = P.merkle4_tag()
+    leaves = oracle_mod.fill_random(0xa19, m)
+    sibs = oracle_mod.fill_random(0xa1a, m * depth * 3).reshape(m, depth, 3, 4)
+    pos = np.random.default_rng(9).integers(0, 4, size=(m, depth), dtype=np.uint8)
+    np.savez(tmp_path / "in.npz", x=x, tag=hb.tag, mtag=tag, leaves=leaves, sibs=sibs, pos=pos)
+    code = ("import numpy as np, poseidon252_amd as P\n"
+            "d = np.load(%r)\n"
+            "c = P.Context(0)\n"
+            "h = c.hash_batch(d['tag'], d['x'], 4, 1)\n"
+            "r = c.merkle4_path_batch(d['mtag'], d['leaves'], d['sibs'], d['pos'])\n"
+            "np.savez(%r, h=h, r=r)\n"
+            "c.close()\n" % (str(tmp_path / "in.npz"), str(tmp_path / "out.npz")))
+    env = dict(os.environ, P252_HOST_PIPELINE="0")
+    subprocess.check_call([sys.executable, "-c", code], cwd=root, env=env, timeout=300)
+    got = np.load(tmp_path / "out.npz")
+    assert np.array_equal(got["h"], gpu_ctx.hash_batch(hb.tag, x, 4, 1))
+    assert np.array_equal(got["r"], gpu_ctx.merkle4_path_batch(tag, leaves, sibs, pos))
+    idx = np.concatenate([np.arange(0, n, 7001), [n - 1, 1 << 17]])
+    assert np.array_equal(got["h"][idx], oracle_mod.hash_batch(hb.tag, x[idx], 4, 1))
+    idx = np.concatenate([np.arange(0, m, 1999), [6656, m - 1]])
+    assert np.array_equal(got["r"][idx], oracle_mod.merkle4_path_batch(tag, leaves[idx], sibs[idx], pos[idx]))
