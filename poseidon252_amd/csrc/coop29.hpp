@@ -23,7 +23,7 @@
 // deep (mine, then element 4 redundantly) and two rows (mine, row 4): 8 x 6 + 3 + 60 x 3 + 1 + 1 = 233 sequential products.
 //
 // Comm: lane() = index within the group; get<M>(e) = the element held by lane M of my group; swap1(e) = the element held
-// by lane ^ 1.  Device (kernels.hip): 8 lanes — ds_bpermute_b32; 4 lanes — DPP quad_perm broadcast; swap1 — DPP
+// by lane ^ 1.  Device (WaveComm8 / WaveComm4 below): 8 lanes — ds_bpermute_b32; 4 lanes — DPP quad_perm broadcast; swap1 — DPP
 // quad_perm [1,0,3,2].  Host (unit tests): one thread per lane and a barrier (hosttest.cpp).
 #pragma once
 #include "hades29.hpp"
@@ -198,5 +198,45 @@ P252_HD void hades_permute_coop(E29& s, E29& s4, TP tab, Comm& cm, CoopLane<LANE
     s = mul_c(s, tab + Lay::AI_F);
     if (LANES == 4 && ROW4) s4 = mul_c(s4, tab + Lay::AI_F);
 }
+
+#if defined(__HIPCC__)
+// ---- the device Comm (see the header comment) ----
+struct WaveComm8 {
+    int j;      // my index within the group
+    int base4;  // ds_bpermute byte address of my group's lane 0 (within the wave)
+    __device__ __forceinline__ int lane() const { return j; }
+    template <int M>
+    __device__ __forceinline__ E29 get(const E29& v) const {
+        E29 r;
+        const int addr = base4 + 4 * M;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_ds_bpermute(addr, v.d[k]);
+        return r;
+    }
+    __device__ __forceinline__ E29 swap1(const E29& v) const {
+        E29 r;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, true);
+        return r;
+    }
+};
+struct WaveComm4 {  // a group = a quad
+    int j;
+    __device__ __forceinline__ int lane() const { return j; }
+    template <int M>
+    __device__ __forceinline__ E29 get(const E29& v) const {
+        E29 r;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], M * 0x55 /* quad_perm [M,M,M,M] */, 0xf, 0xf, true);
+        return r;
+    }
+    __device__ __forceinline__ E29 swap1(const E29& v) const {
+        E29 r;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], 0xB1, 0xf, 0xf, true);
+        return r;
+    }
+};
+#endif  // __HIPCC__
 
 }  // namespace p252

@@ -601,4 +601,54 @@ P252_HD void to_mont4(const E29& x, uint32_t w[8]) {
     for (int k = 0; k < 8; ++k) w[k] = u[k];
 }
 
+#if defined(__HIPCC__)
+// ---- device scalar I/O: one BlsScalar record as it lies in HBM, read and written as two 16-byte accesses ----
+struct alignas(16) Scalar32 {
+    uint32_t w[8];
+};
+
+__device__ __forceinline__ E29 load_scalar(const Scalar32* __restrict__ p) {
+    const uint4 lo = *reinterpret_cast<const uint4*>(p);
+    const uint4 hi = *(reinterpret_cast<const uint4*>(p) + 1);
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    return from_mont4(w);
+}
+
+__device__ __forceinline__ void store_zero(Scalar32* __restrict__ p) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(0u, 0u, 0u, 0u);
+    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__device__ __forceinline__ void store_scalar(Scalar32* __restrict__ p, const E29& e) {
+    uint32_t w[8];
+    to_mont4(e, w);
+    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// Hash::finalize_truncated's output (hash.rs:164-183) from the kernel that already holds the value: the canonical
+// value (Montgomery form dropped: redc(V * 2^5) = V * 2^5 / 2^261 = V / 2^256) & (2^250 - 1), stored as the raw limbs
+// JubJubScalar::from_raw receives.  e is a tight residue (|V| < 2p < 2^256), so the reduction lands in [-p, 0]: two conditional
+// subtractions canonicalise.  One product + one reduction per OUTPUT scalar (~110 of a digest's 77,000 instructions) instead of
+// a second launch and a 64 B / scalar round trip through HBM (k_to_canonical<true>, kept for scalars that are already stored).
+__device__ __forceinline__ void store_truncated(Scalar32* __restrict__ p, const E29& e) {
+    const int32_t c32[NL] = {32, 0, 0, 0, 0, 0, 0, 0, 0};
+    A29 t;
+    acc_zero(t);
+    acc_mul(t, e, c32);
+    uint32_t w[8];
+    to_mont4<2>(redc(t), w);
+    w[7] &= 0x03ffffffu;  // TRUNCATION_MASK: keep the low 250 bits
+    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(w[4], w[5], w[6], w[7]);
+}
+template <bool TRUNC>
+__device__ __forceinline__ void store_output(Scalar32* __restrict__ p, const E29& e) {
+    if (TRUNC)
+        store_truncated(p, e);
+    else
+        store_scalar(p, e);
+}
+#endif  // __HIPCC__
+
 }  // namespace p252

@@ -1,4 +1,4 @@
-// kernels.h — launch interface between api.cpp (host, C ABI) and kernels.hip (device).
+// kernels.h — launch interface between api.cpp (host, C ABI) and the kernel files (device).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,5 +47,19 @@ hipError_t launch_merkle4_path(const int32_t* tab, const TagArg& tag, const void
 
 // measurement aid (bench.py): one wave samples the shader-clock and real-time counters around a sleep of spin_ticks (100 MHz ticks)
 hipError_t launch_clock_probe(void* out6, unsigned spin_ticks, hipStream_t st);
+
+// ---- launch rules of the launchers (kernels.hip, ragged.hip) ----
+inline unsigned grid_for(size_t lanes) { return (unsigned)((lanes + P252_BLOCK - 1) / P252_BLOCK); }
+// largest batch that runs on the cooperative (several lanes per state) kernels: P252_COOP_MAX_NODES, default 16384
+// (8 lanes per state up to 8,192 — every entry point; 4 lanes up to 16,384 — Merkle digests only); 0 = never
+size_t coop_max_nodes();
+// the 8-lane group kernels take a batch of n states
+inline bool coop8(size_t n) { return n <= coop_max_nodes() && n * 8 <= (size_t)65536; }
+// kernel k over `lanes` lanes in blocks of P252_BLOCK on st
+template <class... P, class... A>
+hipError_t launch(void (*k)(P...), size_t lanes, hipStream_t st, const A&... args) {
+    hipLaunchKernelGGL(k, dim3(grid_for(lanes)), dim3(P252_BLOCK), 0, st, args...);
+    return hipGetLastError();
+}
 
 }  // namespace p252

@@ -24,17 +24,6 @@
 
 namespace p252 {
 
-struct alignas(16) Scalar32 {
-    uint32_t w[8];
-};
-
-__device__ __forceinline__ E29 load_scalar(const Scalar32* __restrict__ p) {
-    const uint4 lo = *reinterpret_cast<const uint4*>(p);
-    const uint4 hi = *(reinterpret_cast<const uint4*>(p) + 1);
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return from_mont4(w);
-}
-
 // a record as it lies in memory (two 16-byte halves): fetched whole cache lines at a time by the sponge and opening
 // kernels, kept raw across a permutation and converted where it is consumed
 struct Raw32 {
@@ -61,37 +50,6 @@ __device__ __forceinline__ Raw32 raw_select(bool first, const Raw32& a, const Ra
 __device__ __forceinline__ E29 raw_to_e29(const Raw32& r) {
     const uint32_t w[8] = {r.lo.x, r.lo.y, r.lo.z, r.lo.w, r.hi.x, r.hi.y, r.hi.z, r.hi.w};
     return from_mont4(w);
-}
-
-__device__ __forceinline__ void store_scalar(Scalar32* __restrict__ p, const E29& e) {
-    uint32_t w[8];
-    to_mont4(e, w);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
-// Hash::finalize_truncated's output (hash.rs:164-183) from the kernel that already holds the value: the canonical
-// value (Montgomery form dropped: redc(V * 2^5) = V * 2^5 / 2^261 = V / 2^256) & (2^250 - 1), stored as the raw limbs
-// JubJubScalar::from_raw receives.  e is a tight residue (|V| < 2p < 2^256), so the reduction lands in [-p, 0]: two conditional
-// subtractions canonicalise.  One product + one reduction per OUTPUT scalar (~110 of a digest's 77,000 instructions) instead of
-// a second launch and a 64 B / scalar round trip through HBM (k_to_canonical<true>, kept for scalars that are already stored).
-__device__ __forceinline__ void store_truncated(Scalar32* __restrict__ p, const E29& e) {
-    const int32_t c32[NL] = {32, 0, 0, 0, 0, 0, 0, 0, 0};
-    A29 t;
-    acc_zero(t);
-    acc_mul(t, e, c32);
-    uint32_t w[8];
-    to_mont4<2>(redc(t), w);
-    w[7] &= 0x03ffffffu;  // TRUNCATION_MASK: keep the low 250 bits
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(w[4], w[5], w[6], w[7]);
-}
-template <bool TRUNC>
-__device__ __forceinline__ void store_output(Scalar32* __restrict__ p, const E29& e) {
-    if (TRUNC)
-        store_truncated(p, e);
-    else
-        store_scalar(p, e);
 }
 
 // ---- n independent permutations (Safe::permute, scalar.rs:25-27) ----
@@ -195,42 +153,6 @@ __global__ void __launch_bounds__(P252_BLOCK) k_merkle4_pad(const int32_t* __res
 // DPP quad_perm broadcast on v_mov_b32 (VALU, no wait).  The one element a partial round swaps inside a lane pair:
 // DPP quad_perm [1,0,3,2].  `lanes` >= LANES * n: as in k_merkle4_pad, group g hashes node g mod n so that a large
 // tree's narrow levels keep every SIMD busy. ----
-struct WaveComm8 {
-    int j;      // my index within the group
-    int base4;  // ds_bpermute byte address of my group's lane 0 (within the wave)
-    __device__ __forceinline__ int lane() const { return j; }
-    template <int M>
-    __device__ __forceinline__ E29 get(const E29& v) const {
-        E29 r;
-        const int addr = base4 + 4 * M;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_ds_bpermute(addr, v.d[k]);
-        return r;
-    }
-    __device__ __forceinline__ E29 swap1(const E29& v) const {
-        E29 r;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, true);
-        return r;
-    }
-};
-struct WaveComm4 {  // a group = a quad
-    int j;
-    __device__ __forceinline__ int lane() const { return j; }
-    template <int M>
-    __device__ __forceinline__ E29 get(const E29& v) const {
-        E29 r;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], M * 0x55 /* quad_perm [M,M,M,M] */, 0xf, 0xf, true);
-        return r;
-    }
-    __device__ __forceinline__ E29 swap1(const E29& v) const {
-        E29 r;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], 0xB1, 0xf, 0xf, true);
-        return r;
-    }
-};
 __device__ __forceinline__ E29 load_child_or_zero(const Scalar32* __restrict__ children, size_t n_children, size_t idx,
                                                   unsigned arity, int k /* child number, < 0: none */) {
     const size_t c = idx * arity + (size_t)(k > 0 ? k : 0);
@@ -909,11 +831,7 @@ __global__ void __launch_bounds__(64) k_clock_probe(uint64_t* __restrict__ out, 
 // ---------------------------------------------------------------------------------------------
 namespace p252 {
 
-static inline unsigned grid_for(size_t n) { return (unsigned)((n + P252_BLOCK - 1) / P252_BLOCK); }
-
-// largest batch that runs on the cooperative (several lanes per state) kernels: P252_COOP_MAX_NODES, default 16384
-// (8 lanes per state up to 8,192 — every entry point; 4 lanes up to 16,384 — Merkle digests only); 0 = never
-static size_t coop_max_nodes() {
+size_t coop_max_nodes() {
     static const size_t v = [] {
         const char* e = std::getenv("P252_COOP_MAX_NODES");
         return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)16384;
@@ -928,33 +846,22 @@ static bool line_fetch() {
     }();
     return on;
 }
-static inline bool coop8(size_t n) { return n <= coop_max_nodes() && n * 8 <= (size_t)65536; }
 
 hipError_t launch_permute(const int32_t* tab, const void* in, void* out, size_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    if (coop8(n)) {
-        hipLaunchKernelGGL(k_permute_coop, dim3(grid_for(n * 8)), dim3(P252_BLOCK), 0, st, tab,
-                           static_cast<const Scalar32*>(in), static_cast<Scalar32*>(out), n);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_permute, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab,
-                       static_cast<const Scalar32*>(in), static_cast<Scalar32*>(out), n);
-    return hipGetLastError();
+    const bool coop = coop8(n);
+    return launch(coop ? k_permute_coop : k_permute, coop ? n * 8 : n, st, tab, static_cast<const Scalar32*>(in),
+                  static_cast<Scalar32*>(out), n);
 }
 
 hipError_t launch_merkle4(const int32_t* tab, const TagArg& tag, const void* children, size_t n_children,
                           void* out, size_t n, hipStream_t st, unsigned arity, size_t pad_lanes, bool trunc250) {
     if (n == 0) return hipSuccess;
+    const Scalar32* c = static_cast<const Scalar32*>(children);
+    Scalar32* y = static_cast<Scalar32*>(out);
     if (trunc250) {  // digest_truncated: lane groups for what cannot fill the chip, the 3-waves-per-SIMD build otherwise
-        if (coop8(n)) {
-            const size_t lanes = n * 8;
-            hipLaunchKernelGGL(k_merkle4_coop8_trunc, dim3(grid_for(lanes)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity, lanes);
-        } else {
-            hipLaunchKernelGGL(k_merkle4_trunc, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity);
-        }
-        return hipGetLastError();
+        if (coop8(n)) return launch(k_merkle4_coop8_trunc, n * 8, st, tab, tag, c, n_children, y, n, arity, n * 8);
+        return launch(k_merkle4_trunc, n, st, tab, tag, c, n_children, y, n, arity);
     }
     if (pad_lanes >= ((size_t)1 << 31)) pad_lanes = 0;  // (the padded kernels index with 32 bits)
     // launches of at most one wave per SIMD with 8 (4) lanes per node: the cooperative low-latency builds
@@ -964,19 +871,9 @@ hipError_t launch_merkle4(const int32_t* tab, const TagArg& tag, const void* chi
         const size_t want = n * group;
         // whole groups only: a partial last group would exchange with lanes that have already left the kernel
         const size_t lanes = ((want < pad_lanes ? pad_lanes : want) + group - 1) & ~(group - 1);
-        if (eight)
-            hipLaunchKernelGGL(k_merkle4_coop<8>, dim3(grid_for(lanes)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity, lanes);
-        else
-            hipLaunchKernelGGL(k_merkle4_coop<4>, dim3(grid_for(lanes)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity, lanes);
-        return hipGetLastError();
+        return launch(eight ? k_merkle4_coop<8> : k_merkle4_coop<4>, lanes, st, tab, tag, c, n_children, y, n, arity, lanes);
     }
-    if (n < pad_lanes) {
-        hipLaunchKernelGGL(k_merkle4_pad, dim3(grid_for(pad_lanes)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity, pad_lanes);
-        return hipGetLastError();
-    }
+    if (n < pad_lanes) return launch(k_merkle4_pad, pad_lanes, st, tab, tag, c, n_children, y, n, arity, pad_lanes);
     // <= one wave per SIMD on the whole chip (256 CUs x 4 SIMDs x 64 lanes): the latency build (169 VGPRs: two waves per
     // SIMD).  It also takes launches of two and of FOUR waves per SIMD: at three resident waves a fourth runs alone
     // afterwards at a lone wave's latency (3 + 1), two and two do not (2^18 digests: see profiles/r02_ab_coop.txt).
@@ -986,115 +883,59 @@ hipError_t launch_merkle4(const int32_t* tab, const TagArg& tag, const void* chi
         return e ? (unsigned)std::strtoul(e, nullptr, 0) : 0x16u;
     }();
     const size_t waves_per_simd = (n + 65535) / 65536;
-    if (waves_per_simd < 32 && ((lat_mask >> waves_per_simd) & 1u))
-        hipLaunchKernelGGL(k_merkle4_lat, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity);
-    else
-        hipLaunchKernelGGL(k_merkle4, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), n, arity);
-    return hipGetLastError();
+    const bool lat = waves_per_simd < 32 && ((lat_mask >> waves_per_simd) & 1u);
+    return launch(lat ? k_merkle4_lat : k_merkle4, n, st, tab, tag, c, n_children, y, n, arity);
 }
 
 hipError_t launch_scatter_scalars(const void* index, const void* values, void* dst, size_t k, size_t n_dst, void* n_bad, hipStream_t st) {
     if (k == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scatter_scalars, dim3(grid_for(k)), dim3(P252_BLOCK), 0, st, static_cast<const uint32_t*>(index),
-                       static_cast<const Scalar32*>(values), static_cast<Scalar32*>(dst), k, n_dst, static_cast<unsigned*>(n_bad));
-    return hipGetLastError();
+    return launch(k_scatter_scalars, k, st, static_cast<const uint32_t*>(index), static_cast<const Scalar32*>(values),
+                  static_cast<Scalar32*>(dst), k, n_dst, static_cast<unsigned*>(n_bad));
 }
 
 hipError_t launch_merkle4_update(const int32_t* tab, const TagArg& tag, const void* index, unsigned shift, const void* children,
                                  size_t n_children, void* out, size_t k, hipStream_t st) {
     if (k == 0) return hipSuccess;
-    if (coop8(k))
-        hipLaunchKernelGGL(k_merkle4_update_coop, dim3(grid_for(k * 8)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const uint32_t*>(index), shift, static_cast<const Scalar32*>(children), n_children,
-                           static_cast<Scalar32*>(out), k);
-    else
-        hipLaunchKernelGGL(k_merkle4_update, dim3(grid_for(k)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const uint32_t*>(index), shift, static_cast<const Scalar32*>(children), n_children,
-                           static_cast<Scalar32*>(out), k);
-    return hipGetLastError();
+    const bool coop = coop8(k);
+    return launch(coop ? k_merkle4_update_coop : k_merkle4_update, coop ? k * 8 : k, st, tab, tag, static_cast<const uint32_t*>(index),
+                  shift, static_cast<const Scalar32*>(children), n_children, static_cast<Scalar32*>(out), k);
 }
 
 hipError_t launch_sponge(const int32_t* tab, const TagArg& tag, const void* in, unsigned in_len,
                          unsigned out_len, void* out, size_t n, hipStream_t st, bool trunc250) {
     if (n == 0) return hipSuccess;
-    if (trunc250) {
-        if (coop8(n))
-            hipLaunchKernelGGL(k_sponge_coop_trunc, dim3(grid_for(n * 8)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
-        else if (line_fetch() && (in_len & 1u) == 0 && (reinterpret_cast<uintptr_t>(in) & 63u) == 0)
-            hipLaunchKernelGGL(k_sponge_lines_trunc, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
-        else
-            hipLaunchKernelGGL(k_sponge_trunc, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
-        return hipGetLastError();
-    }
-    if (coop8(n)) {
-        hipLaunchKernelGGL(k_sponge_coop, dim3(grid_for(n * 8)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
-        return hipGetLastError();
-    }
+    const bool coop = coop8(n);
     // whole-line fetches when every message starts on a 64-byte boundary (P252_LINE_FETCH=0: never — A/B and tests)
-    if (line_fetch() && (in_len & 1u) == 0 && (reinterpret_cast<uintptr_t>(in) & 63u) == 0)
-        hipLaunchKernelGGL(k_sponge_lines, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
-    else
-        hipLaunchKernelGGL(k_sponge, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
-    return hipGetLastError();
+    const bool lines = !coop && line_fetch() && (in_len & 1u) == 0 && (reinterpret_cast<uintptr_t>(in) & 63u) == 0;
+    auto k = coop ? (trunc250 ? k_sponge_coop_trunc : k_sponge_coop)
+             : lines ? (trunc250 ? k_sponge_lines_trunc : k_sponge_lines)
+                     : (trunc250 ? k_sponge_trunc : k_sponge);
+    return launch(k, coop ? n * 8 : n, st, tab, tag, static_cast<const Scalar32*>(in), in_len, out_len, static_cast<Scalar32*>(out), n);
 }
 
 hipError_t launch_crypt(bool decrypt, const int32_t* tab, const TagArg& tag, const void* in, const void* secrets,
                         const void* nonces, unsigned len, void* out, void* flags, size_t n, const uint32_t* prog,
                         unsigned n_calls, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    if (coop8(n)) {
-        if (decrypt)
-            hipLaunchKernelGGL(k_crypt_coop<true>, dim3(grid_for(n * 8)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
-                               static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out),
-                               static_cast<uint8_t*>(flags), n, prog, n_calls);
-        else
-            hipLaunchKernelGGL(k_crypt_coop<false>, dim3(grid_for(n * 8)), dim3(P252_BLOCK), 0, st, tab, tag,
-                               static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
-                               static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out),
-                               static_cast<uint8_t*>(flags), n, prog, n_calls);
-        return hipGetLastError();
-    }
-    if (decrypt)
-        hipLaunchKernelGGL(k_crypt<true>, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
-                           static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out),
-                           static_cast<uint8_t*>(flags), n, prog, n_calls);
-    else
-        hipLaunchKernelGGL(k_crypt<false>, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
-                           static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out),
-                           static_cast<uint8_t*>(flags), n, prog, n_calls);
-    return hipGetLastError();
+    const bool coop = coop8(n);
+    auto k = coop ? (decrypt ? k_crypt_coop<true> : k_crypt_coop<false>) : (decrypt ? k_crypt<true> : k_crypt<false>);
+    return launch(k, coop ? n * 8 : n, st, tab, tag, static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
+                  static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out), static_cast<uint8_t*>(flags), n, prog, n_calls);
 }
 
 hipError_t launch_truncate250(const void* in, void* out, size_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_to_canonical<true>, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, static_cast<const Scalar32*>(in),
-                       static_cast<Scalar32*>(out), n);
-    return hipGetLastError();
+    return launch(k_to_canonical<true>, n, st, static_cast<const Scalar32*>(in), static_cast<Scalar32*>(out), n);
 }
 
 hipError_t launch_to_canonical(const void* in, void* out, size_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_to_canonical<false>, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, static_cast<const Scalar32*>(in),
-                       static_cast<Scalar32*>(out), n);
-    return hipGetLastError();
+    return launch(k_to_canonical<false>, n, st, static_cast<const Scalar32*>(in), static_cast<Scalar32*>(out), n);
 }
 
 hipError_t launch_from_canonical(const void* in, void* out, void* ok, size_t n, const Digits9& r2, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_from_canonical, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, static_cast<const Scalar32*>(in),
-                       static_cast<Scalar32*>(out), static_cast<uint8_t*>(ok), n, r2);
-    return hipGetLastError();
+    return launch(k_from_canonical, n, st, static_cast<const Scalar32*>(in), static_cast<Scalar32*>(out), static_cast<uint8_t*>(ok), n, r2);
 }
 
 hipError_t launch_clock_probe(void* out6, unsigned spin_ticks, hipStream_t st) {
@@ -1105,23 +946,13 @@ hipError_t launch_clock_probe(void* out6, unsigned spin_ticks, hipStream_t st) {
 hipError_t launch_merkle4_path(const int32_t* tab, const TagArg& tag, const void* leaves, const void* siblings,
                                const void* positions, unsigned depth, void* roots, size_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    if (coop8(n)) {
-        hipLaunchKernelGGL(k_merkle4_path_coop, dim3(grid_for(n * 8)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(leaves), static_cast<const Scalar32*>(siblings),
-                           static_cast<const uint8_t*>(positions), depth, static_cast<Scalar32*>(roots), n);
-        return hipGetLastError();
-    }
+    const bool coop = coop8(n);
     // whole-line fetches when every lane's sibling path starts on a line boundary (depth x 96 B a multiple of 128 B)
-    if (line_fetch() && depth != 0 && (depth & 3u) == 0 && (reinterpret_cast<uintptr_t>(siblings) & 127u) == 0 &&
-        (reinterpret_cast<uintptr_t>(positions) & 3u) == 0)
-        hipLaunchKernelGGL(k_merkle4_path_lines, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(leaves), static_cast<const Scalar32*>(siblings),
-                           static_cast<const uint8_t*>(positions), depth, static_cast<Scalar32*>(roots), n);
-    else
-        hipLaunchKernelGGL(k_merkle4_path, dim3(grid_for(n)), dim3(P252_BLOCK), 0, st, tab, tag,
-                           static_cast<const Scalar32*>(leaves), static_cast<const Scalar32*>(siblings),
-                           static_cast<const uint8_t*>(positions), depth, static_cast<Scalar32*>(roots), n);
-    return hipGetLastError();
+    const bool lines = !coop && line_fetch() && depth != 0 && (depth & 3u) == 0 && (reinterpret_cast<uintptr_t>(siblings) & 127u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(positions) & 3u) == 0;
+    return launch(coop ? k_merkle4_path_coop : lines ? k_merkle4_path_lines : k_merkle4_path, coop ? n * 8 : n, st, tab, tag,
+                  static_cast<const Scalar32*>(leaves), static_cast<const Scalar32*>(siblings), static_cast<const uint8_t*>(positions),
+                  depth, static_cast<Scalar32*>(roots), n);
 }
 
 }  // namespace p252

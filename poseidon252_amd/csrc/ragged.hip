@@ -17,12 +17,7 @@
 //
 // Sponge.  k_sponge_ragged: one lane per message, the loop of k_sponge (kernels.hip) with a per-lane length and tag.
 // k_sponge_ragged_coop: eight lanes per message (coop29.hpp), for launches that cannot fill the chip, under the rule every entry
-// point of kernels.hip applies (n <= P252_COOP_MAX_NODES, default 16384, and n * 8 <= 65536).  No whole-line fetch variant: the
-// kernel is compute-bound.
-//
-// kernels.hip is not touched (the committed counter passes and ISA counts are keyed to its source digest), so the few helpers
-// below that kernels.hip keeps file-local — the 16-byte scalar load / store, the truncating output stage (store_truncated,
-// hash.rs:164-183) and the 8-lane exchange WaveComm8 — are restated here, unchanged.
+// point of kernels.hip applies (coop8, kernels.h).  No whole-line fetch variant: the kernel is compute-bound.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -35,72 +30,6 @@
 namespace p252 {
 
 namespace {
-
-struct alignas(16) Scalar32 {
-    uint32_t w[8];
-};
-
-__device__ __forceinline__ E29 load_scalar(const Scalar32* __restrict__ p) {
-    const uint4 lo = *reinterpret_cast<const uint4*>(p);
-    const uint4 hi = *(reinterpret_cast<const uint4*>(p) + 1);
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return from_mont4(w);
-}
-
-__device__ __forceinline__ void store_zero(Scalar32* __restrict__ p) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(0u, 0u, 0u, 0u);
-    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(0u, 0u, 0u, 0u);
-}
-
-__device__ __forceinline__ void store_scalar(Scalar32* __restrict__ p, const E29& e) {
-    uint32_t w[8];
-    to_mont4(e, w);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
-// Hash::finalize_truncated's output stage (hash.rs:164-183), as kernels.hip's store_truncated: canonical value (Montgomery form
-// dropped by one product with 2^5 and a reduction: V * 2^5 / 2^261 = V / 2^256) & (2^250 - 1), stored as the raw limbs
-// JubJubScalar::from_raw receives
-__device__ __forceinline__ void store_truncated(Scalar32* __restrict__ p, const E29& e) {
-    const int32_t c32[NL] = {32, 0, 0, 0, 0, 0, 0, 0, 0};
-    A29 t;
-    acc_zero(t);
-    acc_mul(t, e, c32);
-    uint32_t w[8];
-    to_mont4<2>(redc(t), w);
-    w[7] &= 0x03ffffffu;  // TRUNCATION_MASK: keep the low 250 bits
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    *(reinterpret_cast<uint4*>(p) + 1) = make_uint4(w[4], w[5], w[6], w[7]);
-}
-template <bool TRUNC>
-__device__ __forceinline__ void store_output(Scalar32* __restrict__ p, const E29& e) {
-    if (TRUNC)
-        store_truncated(p, e);
-    else
-        store_scalar(p, e);
-}
-
-// the 8-lane group exchange of kernels.hip (ds_bpermute_b32 for a lane's element, DPP quad_perm [1,0,3,2] inside a pair)
-struct WaveComm8 {
-    int j;
-    int base4;
-    __device__ __forceinline__ int lane() const { return j; }
-    template <int M>
-    __device__ __forceinline__ E29 get(const E29& v) const {
-        E29 r;
-        const int addr = base4 + 4 * M;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_ds_bpermute(addr, v.d[k]);
-        return r;
-    }
-    __device__ __forceinline__ E29 swap1(const E29& v) const {
-        E29 r;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) r.d[k] = __builtin_amdgcn_mov_dpp(v.d[k], 0xB1, 0xf, 0xf, true);
-        return r;
-    }
-};
 
 constexpr unsigned SORT_BLOCK = 256;
 constexpr unsigned SORT_ITEMS = 8;  // messages per thread of a sort block
@@ -315,15 +244,6 @@ __global__ void __launch_bounds__(P252_BLOCK) k_sponge_ragged_coop_trunc(const i
 // ---------------------------------------------------------------------------------------------
 // launcher (C++ linkage, called from api.cpp)
 // ---------------------------------------------------------------------------------------------
-// P252_COOP_MAX_NODES as kernels.hip reads it (default 16384; 0 = never the lane-group kernel)
-static size_t ragged_coop_max_nodes() {
-    static const size_t v = [] {
-        const char* e = std::getenv("P252_COOP_MAX_NODES");
-        return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)16384;
-    }();
-    return v;
-}
-
 bool ragged_sort_enabled() {
     static const bool on = [] {
         const char* e = std::getenv("P252_RAGGED_SORT");
@@ -351,24 +271,10 @@ hipError_t launch_hash_ragged(const int32_t* tab, const void* tags, size_t max_l
         if (e != hipSuccess) return e;
         ord = static_cast<const uint64_t*>(order);
     }
-    const Scalar32* t = static_cast<const Scalar32*>(tags);
-    const Scalar32* x = static_cast<const Scalar32*>(in);
-    Scalar32* y = static_cast<Scalar32*>(out);
-    unsigned* bad = static_cast<unsigned*>(n_bad);
-    if (n <= ragged_coop_max_nodes() && n * 8 <= (size_t)65536) {
-        const unsigned grid = (unsigned)((n * 8 + P252_BLOCK - 1) / P252_BLOCK);
-        if (trunc250)
-            hipLaunchKernelGGL(k_sponge_ragged_coop_trunc, dim3(grid), dim3(P252_BLOCK), 0, st, tab, t, (uint64_t)max_len, x, off, ord, out_len, y, n, bad);
-        else
-            hipLaunchKernelGGL(k_sponge_ragged_coop, dim3(grid), dim3(P252_BLOCK), 0, st, tab, t, (uint64_t)max_len, x, off, ord, out_len, y, n, bad);
-    } else {
-        const unsigned grid = (unsigned)((n + P252_BLOCK - 1) / P252_BLOCK);
-        if (trunc250)
-            hipLaunchKernelGGL(k_sponge_ragged_trunc, dim3(grid), dim3(P252_BLOCK), 0, st, tab, t, (uint64_t)max_len, x, off, ord, out_len, y, n, bad);
-        else
-            hipLaunchKernelGGL(k_sponge_ragged, dim3(grid), dim3(P252_BLOCK), 0, st, tab, t, (uint64_t)max_len, x, off, ord, out_len, y, n, bad);
-    }
-    return hipGetLastError();
+    const bool coop = coop8(n);
+    auto k = coop ? (trunc250 ? k_sponge_ragged_coop_trunc : k_sponge_ragged_coop) : (trunc250 ? k_sponge_ragged_trunc : k_sponge_ragged);
+    return launch(k, coop ? n * 8 : n, st, tab, static_cast<const Scalar32*>(tags), (uint64_t)max_len, static_cast<const Scalar32*>(in), off,
+                  ord, out_len, static_cast<Scalar32*>(out), n, static_cast<unsigned*>(n_bad));
 }
 
 }  // namespace p252

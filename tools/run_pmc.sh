@@ -36,14 +36,17 @@ counters() {
 for p in $PASSES; do
     if [ "$p" = ktrace ]; then
         rm -rf "$O/ktrace_$TAG"
-        timeout 300 rocprofv3 --kernel-trace --stats -d "$O/ktrace_$TAG" -o kt -- \
+        timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/ktrace_$TAG" -o kt -- \
             python "$ROOT/bench.py" --workload "$WL" --no-cpu-baseline $EXTRA > "$O/ktrace_$TAG.log" 2>&1
     else
         rm -rf "$O/pmc_${TAG}_$p"
-        timeout 300 rocprofv3 --pmc $(counters $p) --kernel-trace --output-format csv -d "$O/pmc_${TAG}_$p" -o pmc -- \
+        timeout -k 10 300 rocprofv3 --pmc $(counters $p) --kernel-trace --output-format csv -d "$O/pmc_${TAG}_$p" -o pmc -- \
             python "$ROOT/bench.py" --workload "$WL" --steps 5 --warmup 1 --no-cpu-baseline $EXTRA > "$O/pmc_${TAG}_$p.log" 2>&1
     fi
-    echo "pass $p rc=$?"
+    rc=$?
+    echo "pass $p rc=$rc"
+    # a failed, faulted or timed-out pass (124/134/137/139 among them) ends the script: nothing more is started on the GPU
+    [ $rc -eq 0 ] || exit $rc
 done
 cd "$ROOT"
 U20=1048576
