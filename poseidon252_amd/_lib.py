@@ -19,34 +19,102 @@ ERR_NO_DEVICE = -5
 ERR_COMM = -6
 COMM_ID_BYTES = 128
 
-# every symbol include/poseidon252_hip.h declares (tests check the .so exports all of them)
-ABI_SYMBOLS = (
-    "p252_device_count", "p252_create", "p252_destroy", "p252_last_error",
-    "p252_permute_batch", "p252_hash_batch", "p252_merkle4_tree", "p252_merkle4_levels_len",
-    "p252_permute_batch_device", "p252_hash_batch_device", "p252_merkle4_tree_device", "p252_sync",
-    "p252_truncate250_device", "p252_merkle4_path_batch", "p252_merkle4_path_batch_device",
-    "p252_host_alloc", "p252_host_free", "p252_host_register", "p252_host_unregister", "p252_merkle2_tree", "p252_merkle2_levels_len", "p252_merkle2_tree_device",
-    "p252_encryption_tag", "p252_encrypt_batch", "p252_decrypt_batch", "p252_encrypt_batch_device",
-    "p252_decrypt_batch_device",
-    "p252_hash_batch_multi", "p252_hash_batch_multi_device", "p252_merkle4_tree_multi", "p252_merkle4_tree_multi_device",
-    "p252_tables_size", "p252_tables_export", "p252_tables_import",
-    "p252_to_bytes_device", "p252_from_bytes_device", "p252_to_bytes", "p252_from_bytes", "p252_merkle4_update_device",
-    "p252_domain_separator", "p252_check_io_pattern", "p252_tag", "p252_truncate250", "p252_version",
-    "p252_abi_version", "p252_merkle4_update_checked_device", "p252_clock_probe_device", "p252_staging_lanes",
-    "p252_comm_unique_id", "p252_comm_create_rank", "p252_comm_create_all", "p252_comm_destroy", "p252_comm_rank", "p252_comm_size",
-    "p252_merkle4_tree_sharded_device", "p252_merkle4_tree_multi_device_resident", "p252_merkle4_forest_device", "p252_merkle2_forest_device", "p252_merkle4_forest", "p252_merkle4_openings_device", "p252_merkle4_depth",
-    "p252_merkle2_openings_device", "p252_merkle2_depth", "p252_merkle2_path_batch_device",
-    "p252_hash_batch_truncated", "p252_hash_batch_truncated_device", "p252_wipe", "p252_scratch_residue",
-    "p252_merkle4_verify_batch_device", "p252_merkle2_verify_batch_device",
-    "p252_trim", "p252_comm_check", "p252_comm_backend",
-    "p252_hash_ragged", "p252_hash_ragged_truncated", "p252_hash_ragged_device", "p252_hash_ragged_truncated_device",
-)
 ABI_VERSION = 9  # include/poseidon252_hip.h P252_ABI_VERSION this binding was written against
 
+_int, _uint, _sz, _vp, _str = ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 _szp = ctypes.POINTER(ctypes.c_size_t)
-_vp = ctypes.c_void_p
-_sz = ctypes.c_size_t
+_vpp = ctypes.POINTER(ctypes.c_void_p)
+
+
+def _f(*argtypes, ret=_int):
+    """(argtypes, restype) of one C entry point; a (void) function keeps argtypes None"""
+    return list(argtypes) or None, ret
+
+
+# the C prototypes of every symbol include/poseidon252_hip.h declares, in its order (tests check the .so exports all of them and
+# compare each argument list with the header).  Device buffers and streams are void*: the binding passes integer addresses.
+PROTOTYPES = {
+    "p252_device_count": _f(),
+    "p252_create": _f(_int, _vpp),
+    "p252_destroy": _f(_vp, ret=None),
+    "p252_last_error": _f(_vp, ret=_str),
+    "p252_permute_batch": _f(_vp, _u64p, _u64p, _sz),
+    "p252_hash_batch": _f(_vp, _u64p, _u64p, _sz, _sz, _u64p, _sz),
+    "p252_hash_batch_truncated": _f(_vp, _u64p, _u64p, _sz, _sz, _u64p, _sz),
+    "p252_merkle4_tree": _f(_vp, _u64p, _u64p, _sz, _u64p, _u64p),
+    "p252_merkle4_levels_len": _f(_sz, ret=_sz),
+    "p252_merkle2_tree": _f(_vp, _u64p, _u64p, _sz, _u64p, _u64p),
+    "p252_merkle2_levels_len": _f(_sz, ret=_sz),
+    "p252_host_alloc": _f(_sz, ret=_vp),
+    "p252_host_free": _f(_vp, ret=None),
+    "p252_host_register": _f(_vp, _sz),
+    "p252_host_unregister": _f(_vp),
+    "p252_permute_batch_device": _f(_vp, _vp, _vp, _sz, _vp),
+    "p252_hash_batch_device": _f(_vp, _u64p, _vp, _sz, _sz, _vp, _sz, _vp),
+    "p252_hash_batch_truncated_device": _f(_vp, _u64p, _vp, _sz, _sz, _vp, _sz, _vp),
+    "p252_hash_ragged_device": _f(_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp),
+    "p252_hash_ragged_truncated_device": _f(_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp),
+    "p252_hash_ragged": _f(_vp, _u64p, _sz, _u64p, _u64p, _sz, _u64p, _sz),
+    "p252_hash_ragged_truncated": _f(_vp, _u64p, _sz, _u64p, _u64p, _sz, _u64p, _sz),
+    "p252_merkle4_tree_device": _f(_vp, _u64p, _vp, _sz, _vp, _vp, _vp),
+    "p252_merkle2_tree_device": _f(_vp, _u64p, _vp, _sz, _vp, _vp, _vp),
+    "p252_sync": _f(_vp, _vp),
+    "p252_wipe": _f(_vp),
+    "p252_scratch_residue": _f(_vp, _u64p),
+    "p252_trim": _f(_vp),
+    "p252_truncate250_device": _f(_vp, _vp, _vp, _sz, _vp),
+    "p252_merkle4_update_device": _f(_vp, _u64p, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp),
+    "p252_merkle4_update_checked_device": _f(_vp, _u64p, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp),
+    "p252_to_bytes_device": _f(_vp, _vp, _vp, _sz, _vp),
+    "p252_from_bytes_device": _f(_vp, _vp, _vp, _vp, _sz, _vp),
+    "p252_merkle4_path_batch": _f(_vp, _u64p, _u64p, _u64p, _u8p, _sz, _u64p, _sz),
+    "p252_merkle4_path_batch_device": _f(_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp),
+    "p252_encryption_tag": _f(_int, _sz, _u64p),
+    "p252_encrypt_batch": _f(_vp, _int, _u64p, _u64p, _u64p, _u64p, _sz, _u64p, _sz),
+    "p252_decrypt_batch": _f(_vp, _int, _u64p, _u64p, _u64p, _u64p, _sz, _u64p, _u8p, _sz),
+    "p252_encrypt_batch_device": _f(_vp, _int, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp),
+    "p252_decrypt_batch_device": _f(_vp, _int, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp),
+    "p252_merkle4_depth": _f(_sz, ret=_sz),
+    "p252_merkle4_openings_device": _f(_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp),
+    "p252_merkle2_depth": _f(_sz, ret=_sz),
+    "p252_merkle2_openings_device": _f(_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp),
+    "p252_merkle2_path_batch_device": _f(_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp),
+    "p252_merkle4_verify_batch_device": _f(_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp),
+    "p252_merkle2_verify_batch_device": _f(_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp),
+    "p252_merkle4_forest_device": _f(_vp, _u64p, _vp, _sz, _sz, _vp, _vp, _vp),
+    "p252_merkle4_forest": _f(_vp, _u64p, _u64p, _sz, _sz, _u64p),
+    "p252_merkle2_forest_device": _f(_vp, _u64p, _vp, _sz, _sz, _vp, _vp, _vp),
+    "p252_hash_batch_multi": _f(_vpp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz),
+    "p252_hash_batch_multi_device": _f(_vpp, _sz, _u64p, _vpp, _sz, _sz, _vpp, _szp, _vpp),
+    "p252_merkle4_tree_multi": _f(_vpp, _sz, _u64p, _u64p, _sz, _u64p),
+    "p252_merkle4_tree_multi_device": _f(_vpp, _sz, _u64p, _vpp, _sz, _u64p),
+    "p252_merkle4_tree_multi_device_resident": _f(_vpp, _sz, _u64p, _vpp, _sz, _vpp, _vpp),
+    "p252_comm_unique_id": _f(_vp, _sz),
+    "p252_comm_create_rank": _f(_vp, _vp, _sz, _int, _int, _vpp),
+    "p252_comm_create_all": _f(_vpp, _sz, _vpp),
+    "p252_comm_destroy": _f(_vp, ret=None),
+    "p252_comm_rank": _f(_vp),
+    "p252_comm_size": _f(_vp),
+    "p252_comm_check": _f(_vp, _vp),
+    "p252_comm_backend": _f(_str, _sz),
+    "p252_merkle4_tree_sharded_device": _f(_vp, _u64p, _vp, _sz, _vp, _vp),
+    "p252_tables_size": _f(ret=_sz),
+    "p252_tables_export": _f(_vp, _vp, _sz),
+    "p252_tables_import": _f(_vp, _vp, _sz),
+    "p252_domain_separator": _f(_int, _u64p),
+    "p252_check_io_pattern": _f(_int, _szp, _sz, _sz),
+    "p252_tag": _f(_int, _szp, _sz, _sz, _u64p),
+    "p252_truncate250": _f(_u64p, _u64p, _sz),
+    "p252_to_bytes": _f(_u64p, _u8p, _sz),
+    "p252_from_bytes": _f(_u8p, _u64p, _u8p, _sz),
+    "p252_clock_probe_device": _f(_vp, _vp, _uint, _vp),
+    "p252_staging_lanes": _f(_sz),
+    "p252_abi_version": _f(),
+    "p252_version": _f(ret=_str),
+}
+ABI_SYMBOLS = tuple(PROTOTYPES)
 _lib = None
 
 
@@ -151,98 +219,8 @@ def lib():
                     self.__dict__[name] = m
                     return m
         L = _Tolerant(L)
-    L.p252_device_count.restype = ctypes.c_int
-    L.p252_create.argtypes = [ctypes.c_int, ctypes.POINTER(_vp)]
-    L.p252_destroy.argtypes = [_vp]
-    L.p252_destroy.restype = None
-    L.p252_last_error.argtypes = [_vp]
-    L.p252_last_error.restype = ctypes.c_char_p
-    L.p252_permute_batch.argtypes = [_vp, _u64p, _u64p, _sz]
-    L.p252_hash_batch.argtypes = [_vp, _u64p, _u64p, _sz, _sz, _u64p, _sz]
-    L.p252_merkle4_tree.argtypes = [_vp, _u64p, _u64p, _sz, _u64p, _u64p]
-    L.p252_merkle4_levels_len.argtypes = [_sz]
-    L.p252_merkle4_levels_len.restype = _sz
-    L.p252_merkle2_tree.argtypes = [_vp, _u64p, _u64p, _sz, _u64p, _u64p]
-    L.p252_merkle2_levels_len.argtypes = [_sz]
-    L.p252_merkle2_levels_len.restype = _sz
-    L.p252_merkle2_tree_device.argtypes = [_vp, _u64p, _vp, _sz, _vp, _vp, _vp]
-    L.p252_permute_batch_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
-    L.p252_hash_batch_device.argtypes = [_vp, _u64p, _vp, _sz, _sz, _vp, _sz, _vp]
-    L.p252_merkle4_tree_device.argtypes = [_vp, _u64p, _vp, _sz, _vp, _vp, _vp]
-    L.p252_sync.argtypes = [_vp, _vp]
-    _u8p2 = ctypes.POINTER(ctypes.c_uint8)
-    L.p252_encryption_tag.argtypes = [ctypes.c_int, _sz, _u64p]
-    L.p252_encrypt_batch.argtypes = [_vp, ctypes.c_int, _u64p, _u64p, _u64p, _u64p, _sz, _u64p, _sz]
-    L.p252_decrypt_batch.argtypes = [_vp, ctypes.c_int, _u64p, _u64p, _u64p, _u64p, _sz, _u64p, _u8p2, _sz]
-    L.p252_encrypt_batch_device.argtypes = [_vp, ctypes.c_int, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
-    L.p252_decrypt_batch_device.argtypes = [_vp, ctypes.c_int, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
-    _vpp = ctypes.POINTER(_vp)
-    L.p252_hash_batch_multi.argtypes = [_vpp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz]
-    L.p252_hash_batch_multi_device.argtypes = [_vpp, _sz, _u64p, _vpp, _sz, _sz, _vpp, _szp, _vpp]
-    L.p252_merkle4_tree_multi.argtypes = [_vpp, _sz, _u64p, _u64p, _sz, _u64p]
-    L.p252_merkle4_tree_multi_device.argtypes = [_vpp, _sz, _u64p, _vpp, _sz, _u64p]
-    L.p252_host_alloc.argtypes = [_sz]
-    L.p252_host_alloc.restype = _vp
-    L.p252_host_free.argtypes = [_vp]
-    L.p252_host_free.restype = None
-    L.p252_host_register.argtypes = [_vp, _sz]
-    L.p252_host_unregister.argtypes = [_vp]
-    L.p252_truncate250_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
-    _u8p = ctypes.POINTER(ctypes.c_uint8)
-    L.p252_merkle4_path_batch.argtypes = [_vp, _u64p, _u64p, _u64p, _u8p, _sz, _u64p, _sz]
-    L.p252_merkle4_path_batch_device.argtypes = [_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
-    L.p252_tables_size.restype = _sz
-    L.p252_tables_export.argtypes = [_vp, _vp, _sz]
-    L.p252_tables_import.argtypes = [_vp, _vp, _sz]
-    L.p252_domain_separator.argtypes = [ctypes.c_int, _u64p]
-    L.p252_check_io_pattern.argtypes = [ctypes.c_int, _szp, _sz, _sz]
-    L.p252_tag.argtypes = [ctypes.c_int, _szp, _sz, _sz, _u64p]
-    L.p252_truncate250.argtypes = [_u64p, _u64p, _sz]
-    L.p252_merkle4_update_device.argtypes = [_vp, _u64p, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]
-    L.p252_to_bytes_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
-    L.p252_from_bytes_device.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp]
-    L.p252_to_bytes.argtypes = [_u64p, _u8p, _sz]
-    L.p252_from_bytes.argtypes = [_u8p, _u64p, _u8p, _sz]
-    L.p252_version.restype = ctypes.c_char_p
-    L.p252_merkle4_update_checked_device.argtypes = [_vp, _u64p, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp]
-    L.p252_clock_probe_device.argtypes = [_vp, _vp, ctypes.c_uint, _vp]
-    L.p252_staging_lanes.argtypes = [_sz]
-    L.p252_comm_unique_id.argtypes = [_vp, _sz]
-    L.p252_comm_create_rank.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]
-    L.p252_comm_create_all.argtypes = [_vpp, _sz, _vpp]
-    L.p252_comm_destroy.argtypes = [_vp]
-    L.p252_comm_destroy.restype = None
-    L.p252_comm_rank.argtypes = [_vp]
-    L.p252_comm_size.argtypes = [_vp]
-    L.p252_merkle4_tree_sharded_device.argtypes = [_vp, _u64p, _vp, _sz, _vp, _vp]
-    L.p252_merkle4_tree_multi_device_resident.argtypes = [_vpp, _sz, _u64p, _vpp, _sz, _vpp, _vpp]
-    L.p252_merkle4_forest_device.argtypes = [_vp, _u64p, _vp, _sz, _sz, _vp, _vp, _vp]
-    L.p252_merkle2_forest_device.argtypes = [_vp, _u64p, _vp, _sz, _sz, _vp, _vp, _vp]
-    L.p252_merkle4_forest.argtypes = [_vp, _u64p, _u64p, _sz, _sz, _u64p]
-    L.p252_merkle4_openings_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
-    L.p252_merkle4_depth.argtypes = [_sz]
-    L.p252_merkle4_depth.restype = _sz
-    L.p252_merkle2_openings_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
-    L.p252_merkle2_depth.argtypes = [_sz]
-    L.p252_merkle2_depth.restype = _sz
-    L.p252_merkle2_path_batch_device.argtypes = [_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp]
-    L.p252_hash_batch_truncated.argtypes = [_vp, _u64p, _u64p, _sz, _sz, _u64p, _sz]
-    L.p252_hash_batch_truncated_device.argtypes = [_vp, _u64p, _vp, _sz, _sz, _vp, _sz, _vp]
-    L.p252_merkle4_verify_batch_device.argtypes = [_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
-    L.p252_merkle2_verify_batch_device.argtypes = [_vp, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
-    L.p252_wipe.argtypes = [_vp]
-    L.p252_trim.argtypes = [_vp]
-    L.p252_comm_check.argtypes = [_vp, _vp]
-    L.p252_comm_backend.argtypes = [ctypes.c_char_p, _sz]
-    L.p252_scratch_residue.argtypes = [_vp, _u64p]
-    L.p252_hash_ragged.argtypes = [_vp, _u64p, _sz, _u64p, _u64p, _sz, _u64p, _sz]
-    L.p252_hash_ragged_truncated.argtypes = [_vp, _u64p, _sz, _u64p, _u64p, _sz, _u64p, _sz]
-    L.p252_hash_ragged_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp]
-    L.p252_hash_ragged_truncated_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp]
-    L.p252_abi_version.restype = ctypes.c_int
-    for name in ABI_SYMBOLS:
+    for name, (argtypes, restype) in PROTOTYPES.items():
         fn = getattr(L, name)
-        if fn.restype is ctypes.c_int and name not in ("p252_device_count",):
-            pass
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L

@@ -8,12 +8,9 @@ One process per GPU: `Comm.create_rank(ctx, rank, world, exchange)` where `excha
 One process, several GPUs: `Comm.create_all(ctxs)`."""
 import ctypes
 
-import numpy as np
-
 from . import _lib
-from .hash import _as_scalars, _raise
-
-_u64p = ctypes.POINTER(ctypes.c_uint64)
+from .hash import _dev_ptr, _dev_ptrs, _raise, _stream, _tag
+from .multi import _ctx_array
 
 
 def backend():
@@ -59,7 +56,8 @@ class Comm:
     @classmethod
     def create_rank(cls, ctx, rank, world, exchange):
         id_bytes = exchange(unique_id() if rank == 0 else None)
-        assert len(id_bytes) == _lib.COMM_ID_BYTES
+        if len(id_bytes) != _lib.COMM_ID_BYTES:
+            raise ValueError("create_rank: the exchange returned %d id bytes, not %d" % (len(id_bytes), _lib.COMM_ID_BYTES))
         h = ctypes.c_void_p()
         _lib.prefer_torch_rccl()
         rc = _lib.lib().p252_comm_create_rank(ctx._h, id_bytes, _lib.COMM_ID_BYTES, rank, world, ctypes.byref(h))
@@ -70,10 +68,9 @@ class Comm:
     @classmethod
     def create_all(cls, ctxs):
         k = len(ctxs)
-        arr = (ctypes.c_void_p * k)(*[c._h for c in ctxs])
         out = (ctypes.c_void_p * k)()
         _lib.prefer_torch_rccl()
-        rc = _lib.lib().p252_comm_create_all(arr, k, out)
+        rc = _lib.lib().p252_comm_create_all(_ctx_array(ctxs), k, out)
         if rc:
             _raise(rc, ctxs[0]._h)
         return [cls(ctypes.c_void_p(out[t]), ctxs[t]) for t in range(k)]
@@ -89,20 +86,16 @@ class Comm:
     def merkle4_tree_sharded_device(self, tag, d_leaves, n_leaves_local, d_root):
         """this rank's 4^k resident leaves -> subtree root -> ncclAllGather of the `size` roots -> top levels, all on the
         current torch stream; d_root (32 B, device) = the root over the concatenation of all ranks' leaves, on every rank"""
-        import torch
-        tag = _as_scalars(tag).reshape(4)
-        assert d_leaves.numel() * d_leaves.element_size() >= n_leaves_local * 32 and d_root.numel() * d_root.element_size() >= 32
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = _lib.lib().p252_merkle4_tree_sharded_device(self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), n_leaves_local, d_root.data_ptr(), st)
+        f = "merkle4_tree_sharded_device"
+        rc = _lib.lib().p252_merkle4_tree_sharded_device(self._h, _tag(tag), _dev_ptr(self.ctx, f, "d_leaves", d_leaves, n_leaves_local * 32),
+                                                         n_leaves_local, _dev_ptr(self.ctx, f, "d_root", d_root, 32), _stream(self.ctx))
         if rc:
             _raise(rc, self.ctx._h)
 
     def check(self):
         """wait for the current torch stream, then raise DeviceError if a sharded build of this communicator met a failed peer since
         the last check (p252_comm_check): such a build's root is all-ones on every healthy rank"""
-        import torch
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = _lib.lib().p252_comm_check(self._h, st)
+        rc = _lib.lib().p252_comm_check(self._h, _stream(self.ctx))
         if rc:
             _raise(rc, self.ctx._h)
 
@@ -121,12 +114,10 @@ class Comm:
 def merkle4_tree_multi_device_resident(ctxs, tag, d_leaves, leaves_per_ctx, d_roots):
     """p252_merkle4_tree_multi_device_resident: one process, contexts on distinct devices; the root lands in d_roots[t] on
     every device, asynchronously on the default streams"""
-    tag = _as_scalars(tag).reshape(4)
-    k = len(ctxs)
-    arr = (ctypes.c_void_p * k)(*[c._h for c in ctxs])
-    ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in d_leaves])
-    outs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in d_roots])
+    f, k = "merkle4_tree_multi_device_resident", len(ctxs)
+    ptrs = _dev_ptrs(ctxs, f, "d_leaves", d_leaves, [leaves_per_ctx * 32] * k)
+    outs = _dev_ptrs(ctxs, f, "d_roots", d_roots, [32] * k)
     _lib.prefer_torch_rccl()
-    rc = _lib.lib().p252_merkle4_tree_multi_device_resident(arr, k, tag.ctypes.data_as(_u64p), ptrs, leaves_per_ctx, outs, None)
+    rc = _lib.lib().p252_merkle4_tree_multi_device_resident(_ctx_array(ctxs), k, _tag(tag), ptrs, leaves_per_ctx, outs, None)
     if rc:
         _raise(rc, ctxs[0]._h)

@@ -11,15 +11,11 @@ the byte level.  The library interprets the literal sponge-call 
 shared_secret: (2,4) uint64 — the (u, v) coordinates of the shared JubJubAffine as BlsScalars
                (encryption.rs:66-69: `shared_secret.get_u(), shared_secret.get_v()`); nonce: (4,) uint64.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
-from .hash import Context, Error, _as_scalars, _raise
-
-_u64p = ctypes.POINTER(ctypes.c_uint64)
-
+from ._lib import _u8p
+from .hash import Context, Error, _as_scalars, _dev_ptr, _ptr, _raise, _stream, _tag
 
 STREAM, DUPLEX = 0, 1  # P252_CRYPT_STREAM / P252_CRYPT_DUPLEX (include/poseidon252_hip.h)
 
@@ -31,7 +27,7 @@ class DecryptionFailed(Error):
 def encryption_tag(message_len, variant=STREAM):
     """Safe::tag of the encryption io-pattern for a message of `message_len` scalars.  UNPINNED recipe."""
     out = np.empty(4, dtype=np.uint64)
-    rc = _lib.lib().p252_encryption_tag(int(variant), int(message_len), out.ctypes.data_as(_u64p))
+    rc = _lib.lib().p252_encryption_tag(int(variant), int(message_len), _ptr(out))
     if rc:
         _raise(rc)
     return out
@@ -45,11 +41,9 @@ def encrypt_batch(messages, shared_secrets, nonces, ctx=None, tag=None, variant=
     non = _as_scalars(nonces).reshape(n, 4)
     ln = msgs.shape[1]
     ctx = ctx or Context.default()
-    tag = encryption_tag(ln, variant) if tag is None else _as_scalars(tag).reshape(4)
+    tag = encryption_tag(ln, variant) if tag is None else tag
     out = np.empty((n, ln + 1, 4), dtype=np.uint64)
-    ctx._check(_lib.lib().p252_encrypt_batch(ctx._h, int(variant), tag.ctypes.data_as(_u64p), msgs.ctypes.data_as(_u64p),
-                                             secrets.ctypes.data_as(_u64p), non.ctypes.data_as(_u64p), ln,
-                                             out.ctypes.data_as(_u64p), n))
+    ctx._check(_lib.lib().p252_encrypt_batch(ctx._h, int(variant), _tag(tag), _ptr(msgs), _ptr(secrets), _ptr(non), ln, _ptr(out), n))
     return out
 
 
@@ -63,12 +57,11 @@ def decrypt_batch(ciphers, shared_secrets, nonces, ctx=None, tag=None, variant=S
     ctx = ctx or Context.default()
     if ln < 1:
         ctx._check(_lib.ERR_INVALID_IO_PATTERN)
-    tag = encryption_tag(ln, variant) if tag is None else _as_scalars(tag).reshape(4)
+    tag = encryption_tag(ln, variant) if tag is None else tag
     out = np.empty((n, ln, 4), dtype=np.uint64)
     ok = np.zeros(n, dtype=np.uint8)
-    ctx._check(_lib.lib().p252_decrypt_batch(ctx._h, int(variant), tag.ctypes.data_as(_u64p), cph.ctypes.data_as(_u64p),
-                                             secrets.ctypes.data_as(_u64p), non.ctypes.data_as(_u64p), ln,
-                                             out.ctypes.data_as(_u64p), ok.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), n))
+    ctx._check(_lib.lib().p252_decrypt_batch(ctx._h, int(variant), _tag(tag), _ptr(cph), _ptr(secrets), _ptr(non), ln, _ptr(out),
+                                             _ptr(ok, _u8p), n))
     return out, ok.astype(bool)
 
 
@@ -90,22 +83,19 @@ def decrypt(cipher, shared_secret, nonce, ctx=None, tag=None, variant=STREAM):
 def encrypt_batch_device(d_messages, d_secrets, d_nonces, message_len, d_ciphers, n, ctx=None, tag=None, variant=STREAM):
     """device-resident variant (torch CUDA tensors of int64 limbs): messages n*len, secrets n*2, nonces n scalars in,
     ciphers n*(len+1) scalars out; asynchronous on torch's current stream"""
-    import torch
-    ctx = ctx or Context.default()
-    tag = encryption_tag(message_len, variant) if tag is None else _as_scalars(tag).reshape(4)
-    assert all(t.is_cuda for t in (d_messages, d_secrets, d_nonces, d_ciphers))
-    assert d_ciphers.numel() * d_ciphers.element_size() >= n * (message_len + 1) * 32
-    ctx._check(_lib.lib().p252_encrypt_batch_device(ctx._h, int(variant), tag.ctypes.data_as(_u64p), d_messages.data_ptr(), d_secrets.data_ptr(),
-                                                    d_nonces.data_ptr(), message_len, d_ciphers.data_ptr(), n,
-                                                    torch.cuda.current_stream().cuda_stream))
+    ctx, f = ctx or Context.default(), "encrypt_batch_device"
+    ctx._check(_lib.lib().p252_encrypt_batch_device(
+        ctx._h, int(variant), _tag(encryption_tag(message_len, variant) if tag is None else tag),
+        _dev_ptr(ctx, f, "d_messages", d_messages, n * message_len * 32), _dev_ptr(ctx, f, "d_secrets", d_secrets, n * 64),
+        _dev_ptr(ctx, f, "d_nonces", d_nonces, n * 32), message_len,
+        _dev_ptr(ctx, f, "d_ciphers", d_ciphers, n * (message_len + 1) * 32), n, _stream(ctx)))
 
 
 def decrypt_batch_device(d_ciphers, d_secrets, d_nonces, message_len, d_messages, d_ok, n, ctx=None, tag=None, variant=STREAM):
     """device-resident variant: d_ok is a uint8 tensor of n flags (0 = DecryptionFailed for that item)"""
-    import torch
-    ctx = ctx or Context.default()
-    tag = encryption_tag(message_len, variant) if tag is None else _as_scalars(tag).reshape(4)
-    assert all(t.is_cuda for t in (d_ciphers, d_secrets, d_nonces, d_messages, d_ok)) and d_ok.numel() >= n
-    ctx._check(_lib.lib().p252_decrypt_batch_device(ctx._h, int(variant), tag.ctypes.data_as(_u64p), d_ciphers.data_ptr(), d_secrets.data_ptr(),
-                                                    d_nonces.data_ptr(), message_len, d_messages.data_ptr(), d_ok.data_ptr(), n,
-                                                    torch.cuda.current_stream().cuda_stream))
+    ctx, f = ctx or Context.default(), "decrypt_batch_device"
+    ctx._check(_lib.lib().p252_decrypt_batch_device(
+        ctx._h, int(variant), _tag(encryption_tag(message_len, variant) if tag is None else tag),
+        _dev_ptr(ctx, f, "d_ciphers", d_ciphers, n * (message_len + 1) * 32), _dev_ptr(ctx, f, "d_secrets", d_secrets, n * 64),
+        _dev_ptr(ctx, f, "d_nonces", d_nonces, n * 32), message_len, _dev_ptr(ctx, f, "d_messages", d_messages, n * message_len * 32),
+        _dev_ptr(ctx, f, "d_ok", d_ok, n), n, _stream(ctx)))

@@ -15,13 +15,12 @@ import enum
 import numpy as np
 
 from . import _lib
+from ._lib import _u64p, _u8p
 
 __all__ = ["Domain", "Hash", "HashBatch", "RaggedHashBatch", "Context", "Error", "IOPatternViolation", "InvalidIOPattern",
            "HADES_WIDTH", "compute_tag"]
 
 HADES_WIDTH = 5  # dusk_poseidon::HADES_WIDTH, src/lib.rs:17
-
-_u64p = ctypes.POINTER(ctypes.c_uint64)
 
 
 class Error(Exception):
@@ -84,7 +83,7 @@ def compute_tag(domain, absorb_lens, output_len):
     pass the value from the real crates instead (every entry point accepts `tag=`)."""
     lens = (ctypes.c_size_t * max(1, len(absorb_lens)))(*absorb_lens)
     out = np.empty(4, dtype=np.uint64)
-    rc = _lib.lib().p252_tag(int(domain), lens, len(absorb_lens), output_len, out.ctypes.data_as(_u64p))
+    rc = _lib.lib().p252_tag(int(domain), lens, len(absorb_lens), output_len, _ptr(out))
     if rc:
         _raise(rc)
     return out
@@ -95,6 +94,58 @@ def _as_scalars(a):
     if a.shape[-1] != 4:
         raise ValueError("scalar arrays need a trailing axis of 4 u64 limbs")
     return a
+
+
+def _ptr(a, kind=_u64p):
+    """C pointer to a C-contiguous numpy array (the pointer holds a reference to the array)"""
+    return a.ctypes.data_as(kind)
+
+
+def _tag(tag):
+    return _ptr(_as_scalars(tag).reshape(4))
+
+
+def _host_out(call, out, n_scalars):
+    """a caller-provided host output buffer: C-contiguous uint64, exactly n_scalars scalars"""
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous and out.size == n_scalars * 4):
+        raise ValueError("%s: out must be a C-contiguous uint64 array of %d scalars" % (call, n_scalars))
+    return out
+
+
+def _dev_ptr(ctx, call, arg, t, need, elem=0, null_ok=False):
+    """the device address the C call `call` takes for argument `arg`: t must be a contiguous torch CUDA tensor on ctx's device
+    holding at least the `need` bytes the call touches (and, if `elem` is given, of elem-byte elements), else ValueError — the
+    library can only check alignment, and a host pointer or a short view would reach a kernel.  null_ok: None passes as NULL.
+    Reads metadata only (no synchronisation, no allocation): these calls are captured into graphs."""
+    if t is None and null_ok:
+        return None
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: %s must be a torch tensor, not %s" % (call, arg, type(t).__name__))
+    if not t.is_cuda:
+        raise ValueError("%s: %s is on %s, not on the GPU" % (call, arg, t.device))
+    if t.get_device() != ctx.device:
+        raise ValueError("%s: %s is on cuda:%d, the context is on cuda:%d" % (call, arg, t.get_device(), ctx.device))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s is not contiguous" % (call, arg))
+    if elem and t.element_size() != elem:
+        raise ValueError("%s: %s needs %d-byte elements, not %d" % (call, arg, elem, t.element_size()))
+    if t.numel() * t.element_size() < need:
+        raise ValueError("%s: %s holds %d bytes, the call touches %d" % (call, arg, t.numel() * t.element_size(), need))
+    return t.data_ptr()
+
+
+def _dev_ptrs(ctxs, call, arg, ts, needs):
+    """_dev_ptr for each context of a multi-device call: ts[i] on ctxs[i]'s device, needs[i] bytes -> a void* array"""
+    if len(ts) != len(ctxs) or len(needs) != len(ctxs):
+        raise ValueError("%s: %d contexts, %d tensors in %s, %d sizes" % (call, len(ctxs), len(ts), arg, len(needs)))
+    return (ctypes.c_void_p * len(ctxs))(*[_dev_ptr(c, call, "%s[%d]" % (arg, i), ts[i], needs[i]) for i, c in enumerate(ctxs)])
+
+
+def _stream(ctx):
+    """the current torch stream of ctx's device: where the *_device calls launch"""
+    import torch
+    return torch.cuda.current_stream(ctx.device).cuda_stream
 
 
 def _is_torch(x):
@@ -149,16 +200,13 @@ class Context:
         """n x [BlsScalar; 5] -> n permuted states (Safe::permute, scalar.rs:25-27)."""
         s = _as_scalars(states).reshape(-1, 5, 4)
         out = np.empty_like(s)
-        self._check(_lib.lib().p252_permute_batch(self._h, s.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p), s.shape[0]))
+        self._check(_lib.lib().p252_permute_batch(self._h, _ptr(s), _ptr(out), s.shape[0]))
         return out
 
     def sync(self, stream=None):
         """wait for `stream` (a torch stream; default: the current one) — p252_sync; raises DeviceError if a sharded tree build of this
         context's communicator met a failed peer since the last check (comm.Comm.check)"""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream()
-        self._check(_lib.lib().p252_sync(self._h, ctypes.c_void_p(stream.cuda_stream)))
+        self._check(_lib.lib().p252_sync(self._h, stream.cuda_stream if stream is not None else _stream(self)))
 
     def wipe(self):
         """clear every scratch buffer the context owns (p252_wipe: device scratch, level scratch, staging lanes).  The host-buffer
@@ -178,7 +226,6 @@ class Context:
 
     def hash_batch(self, tag, messages, in_len, out_len, out=None, truncated=False):
         """truncated=True: Hash::finalize_truncated's raw limbs (hash.rs:164-183), produced by the digest kernel's output stage"""
-        tag = _as_scalars(tag).reshape(4)
         m = _as_scalars(messages)
         if in_len <= 0:
             self._check(_lib.ERR_INVALID_IO_PATTERN)
@@ -186,10 +233,9 @@ class Context:
         if out is None:
             out = np.empty((m.shape[0], max(out_len, 0), 4), dtype=np.uint64)
         else:  # caller-provided (e.g. pinned) output buffer
-            assert out.dtype == np.uint64 and out.flags.c_contiguous and out.size == m.shape[0] * out_len * 4
-            out = out.reshape(m.shape[0], out_len, 4)
+            out = _host_out("hash_batch", out, m.shape[0] * out_len).reshape(m.shape[0], out_len, 4)
         fn = _lib.lib().p252_hash_batch_truncated if truncated else _lib.lib().p252_hash_batch
-        self._check(fn(self._h, tag.ctypes.data_as(_u64p), m.ctypes.data_as(_u64p), in_len, out_len, out.ctypes.data_as(_u64p), m.shape[0]))
+        self._check(fn(self._h, _tag(tag), _ptr(m), in_len, out_len, _ptr(out), m.shape[0]))
         return out
 
     def hash_ragged(self, tags, flat, offsets, out_len, truncated=False):
@@ -204,116 +250,97 @@ class Context:
             raise ValueError("hash_ragged: offsets reach past the %d scalars given" % x.shape[0])
         out = np.empty((n, max(out_len, 0), 4), dtype=np.uint64)
         fn = _lib.lib().p252_hash_ragged_truncated if truncated else _lib.lib().p252_hash_ragged
-        self._check(fn(self._h, t.ctypes.data_as(_u64p), t.shape[0], x.ctypes.data_as(_u64p), off.ctypes.data_as(_u64p), out_len,
-                       out.ctypes.data_as(_u64p), n))
+        self._check(fn(self._h, _ptr(t), t.shape[0], _ptr(x), _ptr(off), out_len, _ptr(out), n))
         return out
 
     def merkle4_tree(self, tag, leaves, want_levels=False):
-        tag = _as_scalars(tag).reshape(4)
-        lv = _as_scalars(leaves).reshape(-1, 4)
-        n = lv.shape[0]
-        root = np.empty(4, dtype=np.uint64)
-        levels = np.empty((_lib.lib().p252_merkle4_levels_len(n), 4), dtype=np.uint64) if want_levels else None
-        self._check(_lib.lib().p252_merkle4_tree(self._h, tag.ctypes.data_as(_u64p), lv.ctypes.data_as(_u64p), n,
-                                                  root.ctypes.data_as(_u64p),
-                                                  levels.ctypes.data_as(_u64p) if want_levels else None))
-        return (root, levels) if want_levels else root
+        return self._tree(_lib.lib().p252_merkle4_tree, _lib.lib().p252_merkle4_levels_len, tag, leaves, want_levels)
 
     def merkle2_tree(self, tag, leaves, want_levels=False):
         """arity-2 tree over Hash::digest(Domain::Merkle2, [c0, c1]) nodes (hash.rs:27-31)"""
-        tag = _as_scalars(tag).reshape(4)
+        return self._tree(_lib.lib().p252_merkle2_tree, _lib.lib().p252_merkle2_levels_len, tag, leaves, want_levels)
+
+    def _tree(self, fn, levels_len, tag, leaves, want_levels):
         lv = _as_scalars(leaves).reshape(-1, 4)
-        n = lv.shape[0]
         root = np.empty(4, dtype=np.uint64)
-        levels = np.empty((_lib.lib().p252_merkle2_levels_len(n), 4), dtype=np.uint64) if want_levels else None
-        self._check(_lib.lib().p252_merkle2_tree(self._h, tag.ctypes.data_as(_u64p), lv.ctypes.data_as(_u64p), n,
-                                                  root.ctypes.data_as(_u64p),
-                                                  levels.ctypes.data_as(_u64p) if want_levels else None))
+        levels = np.empty((levels_len(lv.shape[0]), 4), dtype=np.uint64) if want_levels else None
+        self._check(fn(self._h, _tag(tag), _ptr(lv), lv.shape[0], _ptr(root), _ptr(levels) if want_levels else None))
         return (root, levels) if want_levels else root
 
-    # ---- device buffers (torch CUDA tensors; asynchronous on torch's current stream) ----
-    @staticmethod
-    def _stream():
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    @staticmethod
-    def _nbytes(t):
-        return t.numel() * t.element_size()
-
+    # ---- device buffers (torch CUDA tensors on the context's device; asynchronous on torch's current stream there) ----
     def permute_batch_device(self, d_states, d_out, n):
-        assert d_states.is_cuda and d_out.is_cuda and d_states.is_contiguous() and d_out.is_contiguous()
-        assert self._nbytes(d_states) >= n * 160 and self._nbytes(d_out) >= n * 160
-        self._check(_lib.lib().p252_permute_batch_device(self._h, d_states.data_ptr(), d_out.data_ptr(), n, self._stream()))
+        f = "permute_batch_device"
+        self._check(_lib.lib().p252_permute_batch_device(self._h, _dev_ptr(self, f, "d_states", d_states, n * 160),
+                                                         _dev_ptr(self, f, "d_out", d_out, n * 160), n, _stream(self)))
 
     def hash_batch_device(self, tag, d_in, in_len, out_len, d_out, n, truncated=False):
         """truncated=True: p252_hash_batch_truncated_device — finalize_truncated's raw limbs from the SAME launch (hash.rs:164-183)"""
-        tag = _as_scalars(tag).reshape(4)
-        assert d_in.is_cuda and d_out.is_cuda and d_in.is_contiguous() and d_out.is_contiguous()
-        assert self._nbytes(d_in) >= n * in_len * 32 and self._nbytes(d_out) >= n * out_len * 32
+        f = "hash_batch_device"
         fn = _lib.lib().p252_hash_batch_truncated_device if truncated else _lib.lib().p252_hash_batch_device
-        self._check(fn(self._h, tag.ctypes.data_as(_u64p), d_in.data_ptr(), in_len, out_len, d_out.data_ptr(), n, self._stream()))
+        self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_in", d_in, n * in_len * 32), in_len, out_len,
+                       _dev_ptr(self, f, "d_out", d_out, n * out_len * 32), n, _stream(self)))
 
     def hash_ragged_device(self, d_tags, max_len, d_in, d_offsets, out_len, d_out, n, d_n_bad=None, truncated=False):
         """p252_hash_ragged[_truncated]_device on torch's current stream: d_offsets = n + 1 int64/uint64 scalar indices, d_tags =
         max_len scalars (tags[L-1] for length L), d_out (n, out_len, 4).  Bad messages (empty, longer than max_len, decreasing
-        offsets) get zero rows and increment d_n_bad (a zeroed device int32/uint32, optional) — nothing is checked on the host."""
-        assert d_tags.is_cuda and d_in.is_cuda and d_offsets.is_cuda and d_out.is_cuda
-        assert d_tags.is_contiguous() and d_in.is_contiguous() and d_offsets.is_contiguous() and d_out.is_contiguous()
-        assert d_offsets.element_size() == 8 and d_offsets.numel() >= n + 1 and self._nbytes(d_tags) >= max_len * 32
-        assert self._nbytes(d_out) >= n * out_len * 32 and (d_n_bad is None or (d_n_bad.is_cuda and d_n_bad.element_size() == 4))
+        offsets) get zero rows and increment d_n_bad (a zeroed device int32/uint32, optional) — nothing is checked on the host
+        (so the extent of d_in, which the offsets give, is not checked either)."""
+        f = "hash_ragged_device"
         fn = _lib.lib().p252_hash_ragged_truncated_device if truncated else _lib.lib().p252_hash_ragged_device
-        self._check(fn(self._h, d_tags.data_ptr(), max_len, d_in.data_ptr(), d_offsets.data_ptr(), out_len, d_out.data_ptr(), n,
-                       d_n_bad.data_ptr() if d_n_bad is not None else None, self._stream()))
+        self._check(fn(self._h, _dev_ptr(self, f, "d_tags", d_tags, max_len * 32), max_len, _dev_ptr(self, f, "d_in", d_in, 0),
+                       _dev_ptr(self, f, "d_offsets", d_offsets, (n + 1) * 8, elem=8), out_len,
+                       _dev_ptr(self, f, "d_out", d_out, n * out_len * 32), n,
+                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
     def merkle4_tree_device(self, tag, d_leaves, n_leaves, d_root, d_levels=None):
-        tag = _as_scalars(tag).reshape(4)
-        assert d_leaves.is_cuda and d_root.is_cuda and d_leaves.is_contiguous()
-        assert self._nbytes(d_leaves) >= n_leaves * 32 and self._nbytes(d_root) >= 32
-        if d_levels is not None:
-            assert self._nbytes(d_levels) >= _lib.lib().p252_merkle4_levels_len(n_leaves) * 32
-        self._check(_lib.lib().p252_merkle4_tree_device(self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), n_leaves,
-                                                         d_root.data_ptr(),
-                                                         d_levels.data_ptr() if d_levels is not None else None,
-                                                         self._stream()))
+        f = "merkle4_tree_device"
+        L = _lib.lib()
+        levels = L.p252_merkle4_levels_len(n_leaves) * 32 if d_levels is not None else 0
+        self._check(L.p252_merkle4_tree_device(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n_leaves * 32), n_leaves,
+                                               _dev_ptr(self, f, "d_root", d_root, 32),
+                                               _dev_ptr(self, f, "d_levels", d_levels, levels, null_ok=True), _stream(self)))
 
     def merkle4_forest(self, tag, leaves, leaves_per_tree):
         """host leaves (numpy, pageable is fine) -> roots (n_trees, 4) numpy: p252_merkle4_forest hashes the first level while the
         leaves stream in through the staging lanes, then the upper levels once across all trees"""
-        tag = _as_scalars(tag).reshape(4)
         lv = _as_scalars(leaves).reshape(-1, 4)
         if leaves_per_tree < 1 or lv.shape[0] % leaves_per_tree:
             raise ValueError("forest: %d leaves are not a whole number of %d-leaf trees" % (lv.shape[0], leaves_per_tree))
         n_trees = lv.shape[0] // leaves_per_tree
         roots = np.empty((n_trees, 4), dtype=np.uint64)
-        self._check(_lib.lib().p252_merkle4_forest(self._h, tag.ctypes.data_as(_u64p), lv.ctypes.data_as(_u64p), n_trees, leaves_per_tree,
-                                                    roots.ctypes.data_as(_u64p)))
+        self._check(_lib.lib().p252_merkle4_forest(self._h, _tag(tag), _ptr(lv), n_trees, leaves_per_tree, _ptr(roots)))
         return roots
 
     def merkle4_forest_device(self, tag, d_leaves, n_trees, leaves_per_tree, d_roots, d_levels=None, arity=4):
         """n_trees independent complete 4^k-leaf trees, tree-major in d_leaves: one launch per level across ALL trees
         (p252_merkle4_forest_device); d_roots (n_trees, 4); d_levels: level-major, n_trees * levels_len(leaves_per_tree) scalars"""
-        tag = _as_scalars(tag).reshape(4)
-        assert d_leaves.is_cuda and d_roots.is_cuda and d_leaves.is_contiguous() and d_roots.is_contiguous()
-        assert self._nbytes(d_leaves) >= n_trees * leaves_per_tree * 32 and self._nbytes(d_roots) >= n_trees * 32
-        if d_levels is not None:
-            ll = _lib.lib().p252_merkle4_levels_len if arity == 4 else _lib.lib().p252_merkle2_levels_len
-            assert self._nbytes(d_levels) >= n_trees * ll(leaves_per_tree) * 32
-        fn = _lib.lib().p252_merkle4_forest_device if arity == 4 else _lib.lib().p252_merkle2_forest_device
-        self._check(fn(self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), n_trees, leaves_per_tree,
-                       d_roots.data_ptr(), d_levels.data_ptr() if d_levels is not None else None, self._stream()))
+        f = "merkle4_forest_device"
+        L = _lib.lib()
+        ll = L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len
+        levels = n_trees * ll(leaves_per_tree) * 32 if d_levels is not None else 0
+        fn = L.p252_merkle4_forest_device if arity == 4 else L.p252_merkle2_forest_device
+        self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n_trees * leaves_per_tree * 32), n_trees, leaves_per_tree,
+                       _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_levels", d_levels, levels, null_ok=True),
+                       _stream(self)))
 
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
-        assert d_scalars.is_cuda and d_out.is_cuda and self._nbytes(d_scalars) >= n * 32 and self._nbytes(d_out) >= n * 32
-        self._check(_lib.lib().p252_truncate250_device(self._h, d_scalars.data_ptr(), d_out.data_ptr(), n, self._stream()))
+        f = "truncate250_device"
+        self._check(_lib.lib().p252_truncate250_device(self._h, _dev_ptr(self, f, "d_scalars", d_scalars, n * 32),
+                                                       _dev_ptr(self, f, "d_out", d_out, n * 32), n, _stream(self)))
 
     def merkle4_update_device(self, tag, d_leaves, n_leaves, d_levels, d_indices, d_new_leaves, k, d_root=None, check=False):
         """incremental update of a stored tree: d_leaves[d_indices[i]] = d_new_leaves[i] (k distinct positions, int32/uint32
         tensor) and every ancestor in d_levels (the layout merkle4_tree_device fills) re-hashed; d_root gets the new root.
         Positions >= n_leaves are skipped by the kernels.  check=True (a debugging aid: it synchronises) raises ValueError
         when the list holds an out-of-range or a repeated position."""
-        tag = _as_scalars(tag).reshape(4)
+        f = "merkle4_update_device"
+        L = _lib.lib()
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, n_leaves * 32)
+        levels = _dev_ptr(self, f, "d_levels", d_levels, L.p252_merkle4_levels_len(n_leaves) * 32, null_ok=n_leaves == 1)
+        indices = _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4) if k else None
+        new_leaves = _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32) if k else None
+        root = _dev_ptr(self, f, "d_root", d_root, 32, null_ok=True)
         if check and k:
             import torch
             idx = d_indices[:k].to(torch.int64) & 0xFFFFFFFF
@@ -321,40 +348,29 @@ class Context:
                 raise ValueError("merkle4_update: position %d is outside the tree (%d leaves)" % (int(idx.max()), n_leaves))
             if int(torch.unique(idx).numel()) != k:
                 raise ValueError("merkle4_update: the positions are not distinct")
-        assert d_leaves.is_cuda and self._nbytes(d_leaves) >= n_leaves * 32
-        assert n_leaves == 1 or (d_levels.is_cuda and self._nbytes(d_levels) >= _lib.lib().p252_merkle4_levels_len(n_leaves) * 32)
-        if k:
-            assert d_indices.is_cuda and d_indices.element_size() == 4 and d_indices.numel() >= k
-            assert d_new_leaves.is_cuda and self._nbytes(d_new_leaves) >= k * 32
-        self._check(_lib.lib().p252_merkle4_update_device(
-            self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), n_leaves, d_levels.data_ptr() if d_levels is not None else None,
-            d_indices.data_ptr() if k else None, d_new_leaves.data_ptr() if k else None, k,
-            d_root.data_ptr() if d_root is not None else None, self._stream()))
+        self._check(L.p252_merkle4_update_device(self._h, _tag(tag), leaves, n_leaves, levels, indices, new_leaves, k, root, _stream(self)))
 
     # ---- the canonical byte format (BlsScalar::to_bytes / from_bytes) on device-resident arrays ----
     def to_bytes_device(self, d_scalars, d_bytes, n):
-        assert d_scalars.is_cuda and d_bytes.is_cuda and self._nbytes(d_scalars) >= n * 32 and self._nbytes(d_bytes) >= n * 32
-        self._check(_lib.lib().p252_to_bytes_device(self._h, d_scalars.data_ptr(), d_bytes.data_ptr(), n, self._stream()))
+        f = "to_bytes_device"
+        self._check(_lib.lib().p252_to_bytes_device(self._h, _dev_ptr(self, f, "d_scalars", d_scalars, n * 32),
+                                                    _dev_ptr(self, f, "d_bytes", d_bytes, n * 32), n, _stream(self)))
 
     def from_bytes_device(self, d_bytes, d_scalars, n, d_ok=None):
-        assert d_scalars.is_cuda and d_bytes.is_cuda and self._nbytes(d_scalars) >= n * 32 and self._nbytes(d_bytes) >= n * 32
-        assert d_ok is None or (d_ok.is_cuda and self._nbytes(d_ok) >= n)
-        self._check(_lib.lib().p252_from_bytes_device(self._h, d_bytes.data_ptr(), d_scalars.data_ptr(),
-                                                      d_ok.data_ptr() if d_ok is not None else None, n, self._stream()))
+        f = "from_bytes_device"
+        self._check(_lib.lib().p252_from_bytes_device(self._h, _dev_ptr(self, f, "d_bytes", d_bytes, n * 32),
+                                                      _dev_ptr(self, f, "d_scalars", d_scalars, n * 32),
+                                                      _dev_ptr(self, f, "d_ok", d_ok, n, null_ok=True), n, _stream(self)))
 
     def merkle4_path_batch(self, tag, leaves, siblings, positions):
         """leaves (n,4) u64; siblings (n,depth,3,4) u64; positions (n,depth) u8 in 0..3 -> roots (n,4)"""
-        tag = _as_scalars(tag).reshape(4)
         lv = _as_scalars(leaves).reshape(-1, 4)
         n = lv.shape[0]
         pos = np.ascontiguousarray(positions, dtype=np.uint8).reshape(n, -1)
         depth = pos.shape[1]
         sib = _as_scalars(siblings).reshape(n, depth, 3, 4) if depth else np.zeros((n, 0, 3, 4), dtype=np.uint64)
         roots = np.empty((n, 4), dtype=np.uint64)
-        u8p = ctypes.POINTER(ctypes.c_uint8)
-        self._check(_lib.lib().p252_merkle4_path_batch(self._h, tag.ctypes.data_as(_u64p), lv.ctypes.data_as(_u64p),
-                                                        sib.ctypes.data_as(_u64p), pos.ctypes.data_as(u8p), depth,
-                                                        roots.ctypes.data_as(_u64p), n))
+        self._check(_lib.lib().p252_merkle4_path_batch(self._h, _tag(tag), _ptr(lv), _ptr(sib), _ptr(pos, _u8p), depth, _ptr(roots), n))
         return roots
 
     def merkle4_openings_device(self, d_leaves, n_leaves, d_levels, d_indices, k, check=False, out=None, arity=4):
@@ -364,62 +380,65 @@ class Context:
         out = (d_leaves_out, d_siblings, d_positions, d_n_bad) to write into caller-owned tensors (no allocation per call).
         arity=2: a Merkle2 tree (p252_merkle2_openings_device): one sibling per level, d_siblings (k,depth,1,4)."""
         import torch
-        assert d_leaves.is_cuda and d_indices.is_cuda and d_indices.element_size() == 4 and d_indices.is_contiguous() and arity in (2, 4)
+        f = "merkle4_openings_device"
+        if arity not in (2, 4):
+            raise ValueError("%s: arity is 2 or 4, not %r" % (f, arity))
         L = _lib.lib()
         depth = int((L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(n_leaves))
         ll = (L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len)(n_leaves)
-        assert self._nbytes(d_leaves) >= n_leaves * 32 and (depth == 0 or self._nbytes(d_levels) >= ll * 32)
-        dev = d_leaves.device
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, n_leaves * 32)
+        levels = _dev_ptr(self, f, "d_levels", d_levels, ll * 32) if depth else None
+        indices = _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4)
         if out is not None:
             out, sib, pos, bad = out
-            assert self._nbytes(out) >= k * 32 and self._nbytes(sib) >= k * depth * 32 * (arity - 1) and self._nbytes(pos) >= k * depth and self._nbytes(bad) >= 4
         else:
+            dev = d_leaves.device
             out = torch.empty((k, 4), dtype=torch.int64, device=dev)
             sib = torch.empty((k, depth, arity - 1, 4), dtype=torch.int64, device=dev)
             pos = torch.empty((k, depth), dtype=torch.uint8, device=dev)
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
         fn = L.p252_merkle4_openings_device if arity == 4 else L.p252_merkle2_openings_device
-        self._check(fn(self._h, d_leaves.data_ptr(), n_leaves, d_levels.data_ptr() if depth else None, d_indices.data_ptr(), k, out.data_ptr(),
-                       sib.data_ptr() if depth else None, pos.data_ptr() if depth else None, bad.data_ptr(), self._stream()))
+        self._check(fn(self._h, leaves, n_leaves, levels, indices, k, _dev_ptr(self, f, "d_leaves_out", out, k * 32),
+                       _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * (arity - 1)) if depth else None,
+                       _dev_ptr(self, f, "d_positions", pos, k * depth) if depth else None, _dev_ptr(self, f, "d_n_bad", bad, 4),
+                       _stream(self)))
         if check and int(bad.item()):
             raise ValueError("merkle4_openings: %d position(s) outside the tree" % int(bad.item()))
         return out, sib, pos, depth
 
     def merkle2_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
         """re-hash of n arity-2 openings (Domain::Merkle2; pass the Merkle2 tag): d_siblings (n,depth[,1],4), d_positions (n,depth) in 0..1"""
-        tag = _as_scalars(tag).reshape(4)
-        assert d_leaves.is_cuda and d_roots.is_cuda and self._nbytes(d_leaves) >= n * 32 and self._nbytes(d_roots) >= n * 32
-        assert depth == 0 or (self._nbytes(d_siblings) >= n * depth * 32 and self._nbytes(d_positions) >= n * depth)
-        self._check(_lib.lib().p252_merkle2_path_batch_device(self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), d_siblings.data_ptr() if depth else None,
-                                                               d_positions.data_ptr() if depth else None, depth, d_roots.data_ptr(), n, self._stream()))
+        self._path_batch_device("merkle2_path_batch_device", _lib.lib().p252_merkle2_path_batch_device, 1, tag, d_leaves, d_siblings,
+                                d_positions, depth, d_roots, n)
 
     def merkle4_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
-        tag = _as_scalars(tag).reshape(4)
-        assert d_leaves.is_cuda and d_roots.is_cuda and self._nbytes(d_leaves) >= n * 32 and self._nbytes(d_roots) >= n * 32
-        if depth:
-            assert self._nbytes(d_siblings) >= n * depth * 96 and self._nbytes(d_positions) >= n * depth
-        self._check(_lib.lib().p252_merkle4_path_batch_device(
-            self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), d_siblings.data_ptr() if depth else None,
-            d_positions.data_ptr() if depth else None, depth, d_roots.data_ptr(), n, self._stream()))
+        self._path_batch_device("merkle4_path_batch_device", _lib.lib().p252_merkle4_path_batch_device, 3, tag, d_leaves, d_siblings,
+                                d_positions, depth, d_roots, n)
+
+    def _path_batch_device(self, f, fn, per, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
+        """per = siblings per level (arity - 1)"""
+        self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
+                       _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * per * 32) if depth else None,
+                       _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
+                       _dev_ptr(self, f, "d_roots", d_roots, n * 32), n, _stream(self)))
 
     def merkle_verify_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_root, d_ok, n, arity=4):
         """`Opening::verify` in bulk (the downstream poseidon-merkle verifier, AGENTS.md:62-66): d_ok[i] (uint8) = 1 iff opening i
         re-hashes to the ONE root at d_root — p252_merkle{4,2}_verify_batch_device; n bytes come back instead of n x 32"""
-        tag = _as_scalars(tag).reshape(4)
+        f = "merkle_verify_batch_device"
         per = 3 if arity == 4 else 1
-        assert d_leaves.is_cuda and d_root.is_cuda and d_ok.is_cuda and self._nbytes(d_leaves) >= n * 32 and self._nbytes(d_root) >= 32 and self._nbytes(d_ok) >= n
-        if depth:
-            assert self._nbytes(d_siblings) >= n * depth * per * 32 and self._nbytes(d_positions) >= n * depth
         fn = _lib.lib().p252_merkle4_verify_batch_device if arity == 4 else _lib.lib().p252_merkle2_verify_batch_device
-        self._check(fn(self._h, tag.ctypes.data_as(_u64p), d_leaves.data_ptr(), d_siblings.data_ptr() if depth else None,
-                       d_positions.data_ptr() if depth else None, depth, d_root.data_ptr(), d_ok.data_ptr(), n, self._stream()))
+        self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
+                       _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * per * 32) if depth else None,
+                       _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
+                       _dev_ptr(self, f, "d_root", d_root, 32), _dev_ptr(self, f, "d_ok", d_ok, n), n, _stream(self)))
 
     # ---- measurement aid: the shader clock (bench.py) ----
     def clock_probe(self, spin_us=1000, stream=None):
         """launches the one-wave clock probe (p252_clock_probe_device) on `stream` (a torch.cuda.Stream; default: the current
         one) and returns the device tensor it fills; read it with `clock_probe_result` after synchronising"""
         import torch
-        stream = stream if stream is not None else torch.cuda.current_stream()
+        stream = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.stream(stream):  # the buffer is zeroed on the probe's own stream: ordered before the kernel
             out = torch.zeros(6, dtype=torch.int64, device="cuda:%d" % self.device)
         self._check(_lib.lib().p252_clock_probe_device(self._h, out.data_ptr(), int(spin_us), ctypes.c_void_p(stream.cuda_stream)))
@@ -437,12 +456,12 @@ class Context:
     def tables_export(self):
         size = _lib.lib().p252_tables_size()
         buf = np.empty(size // 4, dtype=np.int32)
-        self._check(_lib.lib().p252_tables_export(self._h, buf.ctypes.data_as(ctypes.c_void_p), size))
+        self._check(_lib.lib().p252_tables_export(self._h, _ptr(buf, ctypes.c_void_p), size))
         return buf
 
     def tables_import(self, buf):
         buf = np.ascontiguousarray(buf, dtype=np.int32)
-        self._check(_lib.lib().p252_tables_import(self._h, buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes))
+        self._check(_lib.lib().p252_tables_import(self._h, _ptr(buf, ctypes.c_void_p), buf.nbytes))
 
 
 class PinnedScalars:
@@ -475,8 +494,9 @@ class registered:
     (p252_host_register / p252_host_unregister): host-buffer calls on it then copy at PCIe speed."""
 
     def __init__(self, array):
+        if not array.flags["C_CONTIGUOUS"]:
+            raise ValueError("registered: the array is not C-contiguous")
         self._a = array
-        assert array.flags["C_CONTIGUOUS"]
 
     def __enter__(self):
         rc = _lib.lib().p252_host_register(self._a.ctypes.data, self._a.nbytes)
@@ -493,7 +513,7 @@ def truncate250(scalars):
     """finalize_truncated's post-processing (hash.rs:164-183): raw limbs for JubJubScalar::from_raw."""
     s = _as_scalars(scalars)
     out = np.empty_like(s)
-    rc = _lib.lib().p252_truncate250(s.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p), s.size // 4)
+    rc = _lib.lib().p252_truncate250(_ptr(s), _ptr(out), s.size // 4)
     if rc:
         _raise(rc)
     return out
@@ -504,7 +524,7 @@ def to_bytes(scalars):
     canonical values (host-side; `Context.to_bytes_device` for device-resident arrays)"""
     s = _as_scalars(scalars).reshape(-1, 4)
     out = np.empty((s.shape[0], 32), dtype=np.uint8)
-    rc = _lib.lib().p252_to_bytes(s.ctypes.data_as(_u64p), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), s.shape[0])
+    rc = _lib.lib().p252_to_bytes(_ptr(s), _ptr(out, _u8p), s.shape[0])
     if rc:
         _raise(rc)
     return out
@@ -516,8 +536,7 @@ def from_bytes(data):
     b = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, 32)
     out = np.empty((b.shape[0], 4), dtype=np.uint64)
     ok = np.zeros(b.shape[0], dtype=np.uint8)
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    rc = _lib.lib().p252_from_bytes(b.ctypes.data_as(u8p), out.ctypes.data_as(_u64p), ok.ctypes.data_as(u8p), b.shape[0])
+    rc = _lib.lib().p252_from_bytes(_ptr(b, _u8p), _ptr(out), _ptr(ok, _u8p), b.shape[0])
     if rc:
         _raise(rc)
     return out, ok.astype(bool)

@@ -1,0 +1,199 @@
+"""The Python binding's two tables of truth, checked without a GPU: every ctypes prototype in _lib.PROTOTYPES against
+include/poseidon252_hip.h, and every function that hands a device pointer to the library refusing a CPU tensor with a
+ValueError before the library is reached (a host pointer in a kernel is a GPU memory fault, not an exception)."""
+import ctypes
+import os
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def _c_kind(ctype):
+    if ctype.endswith("*"):
+        return "pointer"
+    return {"int": "int32", "unsigned": "uint32", "size_t": "size_t", "void": None}[ctype]
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return None
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int: "int32", ctypes.c_uint: "uint32", ctypes.c_size_t: "size_t"}[t]
+
+
+def test_prototypes_match_the_header():
+    """a wrong argtypes entry silently truncates a size_t or a pointer: each argument's kind and the return kind must be the header's"""
+    import gen_rust_sys
+    from poseidon252_amd import _lib
+    _, protos = gen_rust_sys.parse_header()
+    assert sorted(name for name, _, _ in protos) == sorted(_lib.PROTOTYPES) == sorted(_lib.ABI_SYMBOLS)
+    for name, ret, params in protos:
+        argtypes, restype = _lib.PROTOTYPES[name]
+        argtypes = argtypes or []
+        assert len(argtypes) == len(params), name
+        for (pname, ctype), t in zip(params, argtypes):
+            assert _c_kind(ctype) == _ctypes_kind(t), "%s(%s): %s bound as %s" % (name, pname, ctype, t.__name__)
+        assert _c_kind(ret) == _ctypes_kind(restype), "%s returns %s, bound as %s" % (name, ret, restype)
+
+
+# host helpers that take no context and touch no device: the recorder may forward them to the real library
+HOST_HELPERS = {"p252_merkle4_levels_len", "p252_merkle2_levels_len", "p252_merkle4_depth", "p252_merkle2_depth", "p252_tag",
+                "p252_encryption_tag"}
+
+
+class Recorder:
+    """stands in for the library: records every other call and returns P252_OK without forwarding it"""
+
+    def __init__(self, real):
+        self.real, self.calls = real, []
+
+    def __getattr__(self, name):
+        if name in HOST_HELPERS:
+            return getattr(self.real, name)
+
+        def call(*args):
+            self.calls.append(name)
+            return 0
+        return call
+
+
+class OnDevice(torch.Tensor):
+    """a CPU tensor that reports itself to be on cuda:0 — passes the binding's checks; only the recorder ever sees its address"""
+
+    @property
+    def is_cuda(self):
+        return True
+
+    def get_device(self):
+        return 0
+
+
+def dev(dtype=torch.int64):
+    return torch.zeros(64, dtype=dtype).as_subclass(OnDevice)  # 512 bytes as int64: more than any call below touches
+
+
+def cases():
+    """(the C entry point, the call, its arguments): every function that hands a device pointer to the library"""
+    from poseidon252_amd import Context, encryption, multi
+    from poseidon252_amd.comm import Comm, merkle4_tree_multi_device_resident
+    ctx, ctx2 = Context.__new__(Context), Context.__new__(Context)  # no device: nothing below may reach one
+    ctx._h = ctx2._h = None
+    ctx.device = ctx2.device = 0
+    tag = np.zeros(4, dtype=np.uint64)
+    i32 = torch.int32
+    c = ctx  # (short: the table below is wide)
+    return [
+        ("p252_permute_batch_device", lambda a: c.permute_batch_device(a["d_states"], a["d_out"], 2),
+         dict(d_states=dev(), d_out=dev())),
+        ("p252_hash_batch_device", lambda a: c.hash_batch_device(tag, a["d_in"], 4, 1, a["d_out"], 2),
+         dict(d_in=dev(), d_out=dev())),
+        ("p252_hash_ragged_device", lambda a: c.hash_ragged_device(a["d_tags"], 2, a["d_in"], a["d_offsets"], 1, a["d_out"], 2, a["d_n_bad"]),
+         dict(d_tags=dev(), d_in=dev(), d_offsets=dev(), d_out=dev(), d_n_bad=dev(i32))),
+        ("p252_merkle4_tree_device", lambda a: c.merkle4_tree_device(tag, a["d_leaves"], 16, a["d_root"], a["d_levels"]),
+         dict(d_leaves=dev(), d_root=dev(), d_levels=dev())),
+        ("p252_merkle4_forest_device", lambda a: c.merkle4_forest_device(tag, a["d_leaves"], 2, 4, a["d_roots"], a["d_levels"]),
+         dict(d_leaves=dev(), d_roots=dev(), d_levels=dev())),
+        ("p252_truncate250_device", lambda a: c.truncate250_device(a["d_scalars"], a["d_out"], 2),
+         dict(d_scalars=dev(), d_out=dev())),
+        ("p252_merkle4_update_device",
+         lambda a: c.merkle4_update_device(tag, a["d_leaves"], 16, a["d_levels"], a["d_indices"], a["d_new_leaves"], 2, a["d_root"]),
+         dict(d_leaves=dev(), d_levels=dev(), d_indices=dev(i32), d_new_leaves=dev(), d_root=dev())),
+        ("p252_to_bytes_device", lambda a: c.to_bytes_device(a["d_scalars"], a["d_bytes"], 2),
+         dict(d_scalars=dev(), d_bytes=dev())),
+        ("p252_from_bytes_device", lambda a: c.from_bytes_device(a["d_bytes"], a["d_scalars"], 2, a["d_ok"]),
+         dict(d_bytes=dev(), d_scalars=dev(), d_ok=dev())),
+        ("p252_merkle4_openings_device", lambda a: c.merkle4_openings_device(a["d_leaves"], 16, a["d_levels"], a["d_indices"], 2, out=a["out"]),
+         dict(d_leaves=dev(), d_levels=dev(), d_indices=dev(i32), out=(dev(), dev(), dev(), dev(i32)))),
+        ("p252_merkle2_path_batch_device",
+         lambda a: c.merkle2_path_batch_device(tag, a["d_leaves"], a["d_siblings"], a["d_positions"], 2, a["d_roots"], 2),
+         dict(d_leaves=dev(), d_siblings=dev(), d_positions=dev(), d_roots=dev())),
+        ("p252_merkle4_path_batch_device",
+         lambda a: c.merkle4_path_batch_device(tag, a["d_leaves"], a["d_siblings"], a["d_positions"], 2, a["d_roots"], 2),
+         dict(d_leaves=dev(), d_siblings=dev(), d_positions=dev(), d_roots=dev())),
+        ("p252_merkle4_verify_batch_device",
+         lambda a: c.merkle_verify_batch_device(tag, a["d_leaves"], a["d_siblings"], a["d_positions"], 2, a["d_root"], a["d_ok"], 2),
+         dict(d_leaves=dev(), d_siblings=dev(), d_positions=dev(), d_root=dev(), d_ok=dev())),
+        ("p252_encrypt_batch_device",
+         lambda a: encryption.encrypt_batch_device(a["d_messages"], a["d_secrets"], a["d_nonces"], 2, a["d_ciphers"], 2, ctx=c),
+         dict(d_messages=dev(), d_secrets=dev(), d_nonces=dev(), d_ciphers=dev())),
+        ("p252_decrypt_batch_device",
+         lambda a: encryption.decrypt_batch_device(a["d_ciphers"], a["d_secrets"], a["d_nonces"], 2, a["d_messages"], a["d_ok"], 2, ctx=c),
+         dict(d_ciphers=dev(), d_secrets=dev(), d_nonces=dev(), d_messages=dev(), d_ok=dev())),
+        ("p252_hash_batch_multi_device", lambda a: multi.hash_batch_multi_device([c, ctx2], tag, a["d_ins"], 4, 1, a["d_outs"], [2, 2]),
+         dict(d_ins=[dev(), dev()], d_outs=[dev(), dev()])),
+        ("p252_merkle4_tree_multi_device", lambda a: multi.merkle4_tree_multi_device([c, ctx2], tag, a["d_leaves"], 4),
+         dict(d_leaves=[dev(), dev()])),
+        ("p252_merkle4_tree_sharded_device", lambda a: Comm(None, c).merkle4_tree_sharded_device(tag, a["d_leaves"], 16, a["d_root"]),
+         dict(d_leaves=dev(), d_root=dev())),
+        ("p252_merkle4_tree_multi_device_resident",
+         lambda a: merkle4_tree_multi_device_resident([c, ctx2], tag, a["d_leaves"], 4, a["d_roots"]),
+         dict(d_leaves=[dev(), dev()], d_roots=[dev(), dev()])),
+    ]
+
+
+def with_cpu_tensor(args):
+    """every variant of `args` with one device tensor (an argument, or an entry of a list / tuple argument) replaced by a CPU one"""
+    def cpu(t):
+        return torch.zeros_like(t.as_subclass(torch.Tensor))
+    for name, v in args.items():
+        if isinstance(v, OnDevice):
+            yield name, dict(args, **{name: cpu(v)})
+        elif isinstance(v, (list, tuple)):
+            for i in range(len(v)):
+                seq = list(v)
+                seq[i] = cpu(seq[i])
+                yield "%s[%d]" % (name, i), dict(args, **{name: type(v)(seq)})
+
+
+@pytest.fixture
+def recorder(monkeypatch):
+    from poseidon252_amd import _lib
+    rec = Recorder(_lib.lib())
+    monkeypatch.setattr(_lib, "_lib", rec)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=0))
+    return rec
+
+
+def test_every_device_pointer_refuses_a_cpu_tensor(recorder):
+    n_refused = 0
+    for symbol, call, args in cases():
+        call(args)  # the control: with every tensor "on the device" the call reaches the library, once
+        assert recorder.calls == [symbol], (symbol, recorder.calls)
+        del recorder.calls[:]
+        for where, bad in with_cpu_tensor(args):
+            with pytest.raises(ValueError, match="is on cpu") as e:
+                call(bad)
+            # the message names the argument (the entries of openings' out= by their own names: d_leaves_out, d_siblings, ...)
+            assert where + " is on cpu" in str(e.value) or where.startswith("out["), (symbol, where, str(e.value))
+            assert recorder.calls == [], (symbol, where, recorder.calls)
+            n_refused += 1
+    assert n_refused >= 50
+
+
+def test_refusals_survive_python_O():
+    """the checks are not asserts: `python -O` keeps them"""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import torch\n"
+            "from poseidon252_amd import _lib, hash as H\n"
+            "assert sys.flags.optimize  # (stripped, like every assert here)\n"
+            "class NoLibrary:\n"
+            "    def __getattr__(self, name):\n"
+            "        def call(*a):\n"
+            "            raise SystemExit('the library was reached: ' + name)\n"
+            "        return call\n"
+            "_lib._lib = NoLibrary()\n"
+            "ctx = H.Context.__new__(H.Context); ctx._h = None; ctx.device = 0\n"
+            "try:\n"
+            "    ctx.truncate250_device(torch.zeros(8, dtype=torch.int64), torch.zeros(8, dtype=torch.int64), 2)\n"
+            "except ValueError as e:\n"
+            "    print('REFUSED', sys.flags.optimize, e)\n" % ROOT)
+    out = subprocess.run([sys.executable, "-O", "-c", code], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "REFUSED 1 truncate250_device: d_scalars is on cpu" in out.stdout, (out.stdout, out.stderr)

@@ -116,8 +116,27 @@ def test_misaligned_device_pointers_are_refused(gpu_ctx, oracle_mod):
         gpu_ctx.hash_batch_device(tag, buf, 4, 1, out[1:], 64)
     with pytest.raises(ValueError):
         gpu_ctx.permute_batch_device(buf[1:], buf, 32)
+    # the binding's own checks: a strided view, a view too short for the call, a tensor on another device.  Every view starts
+    # inside a buffer that holds what the call would touch, so a missing check would stay inside the allocation.
+    wide = torch.zeros((2 * 64 * 4, 4), dtype=torch.int64, device="cuda")
+    with pytest.raises(ValueError, match="d_in is not contiguous"):
+        gpu_ctx.hash_batch_device(tag, wide[::2], 4, 1, out, 64)
+    with pytest.raises(ValueError, match="d_out is not contiguous"):
+        gpu_ctx.hash_batch_device(tag, buf, 4, 1, wide[:128, :2], 64)
+    with pytest.raises(ValueError, match="d_in holds 8064 bytes, the call touches 8192"):
+        gpu_ctx.hash_batch_device(tag, buf[:4 * 63 * 4], 4, 1, out, 64)
+    with pytest.raises(ValueError, match="d_out holds 2016 bytes"):
+        gpu_ctx.hash_batch_device(tag, buf, 4, 1, out[:63 * 4], 64)
+    with pytest.raises(ValueError, match="d_root holds 16 bytes"):
+        gpu_ctx.merkle4_tree_device(tag, buf, 64, out[:2])
+    if torch.cuda.device_count() > 1:
+        other = torch.zeros_like(buf, device="cuda:1")
+        with pytest.raises(ValueError, match="d_in is on cuda:1, the context is on cuda:0"):
+            gpu_ctx.hash_batch_device(tag, other, 4, 1, out, 64)
     gpu_ctx.hash_batch_device(tag, buf[4:], 4, 1, out[4:], 63)  # whole-scalar offsets are fine
     torch.cuda.synchronize()
+    exp = oracle_mod.hash_batch(tag, np.zeros((63, 4, 4), dtype=np.uint64), 4, 1).reshape(-1)
+    assert np.array_equal(out[4:4 + 63 * 4].cpu().numpy().view(np.uint64), exp)  # and the context still works
 
 
 def test_hash_api_like_reference_tests(gpu_ctx, oracle_mod):
