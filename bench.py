@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: width-5 Poseidon permutations/s (= Merkle4 digests/s).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM:
@@ -12,9 +12,14 @@ are independent); rank 0 broadcasts the constant table over RCCL once, before th
 untimed wake-up launches of the step (so that an idle GPU's clocks are at steady state whatever W is), W untimed
 warm-up steps, then exactly K timed steps between barriers + synchronisation, MAX over ranks.
 
-The same command then times the other BASELINE configs as SECONDARY workloads, reported under "secondary" with the
-same discipline (their own wake-up, warm-up, barriers, max over ranks) — so that every config is measured by whoever
-runs this one command:
+A plain run does only what the headline figure needs: it sets up, times the primary, checks it (the oracle-free
+self-consistency check below: one extra launch) and prints the line.  The secondary workloads below run with --full, or
+with --dump-outputs, whose files hold their outputs too; the cpu_baseline leg with its oracle check of a sample of every
+workload's outputs runs with --full alone.
+
+With --full (or --dump-outputs) the same command then times the other BASELINE configs as SECONDARY workloads, reported under
+"secondary" with the same discipline (their own wake-up, warm-up, barriers, max over ranks) — so that every config is measured by
+whoever runs this one command:
   secondary.tree      BASELINE configs[2]: 2^24-leaf arity-4 Merkle tree per GPU, all levels; at N > 1 every rank
                       reduces its subtree, the N roots (32 B each) are all-gathered — the path's only exchange step —
                       and the top levels are hashed on every rank: at N = 8 that IS configs[4] (2^27 leaves)
@@ -44,10 +49,10 @@ to bench_detail.json next to this file (`detail_file` on the line; --detail-file
 record of it also goes to stderr ("bench.py primary: {...}").
 
 The line carries `roofline` (VALU int32-MAC bound — DESIGN.md §3; HBM figures are
-included, the path is not HBM- or MFMA-bound) and, at N=1, `cpu_baseline` (the C oracle, kind "port",
+included, the path is not HBM- or MFMA-bound) and, with --full at N=1, `cpu_baseline` (the C oracle, kind "port",
 timed on the host cores on a bounded sample).  oracle/ is touched ONLY inside that cpu_baseline leg,
 where it is timed and, as a by-product, checks a sample of the GPU output of every workload just measured; every
-run (any N) additionally performs an oracle-free GPU self-consistency check per workload.
+run (any N) additionally performs an oracle-free GPU self-consistency check per workload it times.
 """
 import argparse
 import hashlib
@@ -123,10 +128,14 @@ def parse():
     ap.add_argument("--workload", default=None, choices=["merkle4_digests", "tree", "forest", "sponge42", "openings", "encrypt", "extract"],
                     help="primary workload (default merkle4_digests = BASELINE configs[1], followed by the secondary workloads)")
     ap.add_argument("--log2n", type=int, default=None, help="log2 of units per GPU per step of the primary (default: 20; tree: 24 leaves)")
-    ap.add_argument("--no-secondary", action="store_true", help="do not time the secondary workloads (tree, sponge42)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the primary, also time the secondary workloads and (N = 1) run the cpu_baseline leg, which checks a sample "
+                         "of every workload's outputs against the oracle; a plain run times, self-checks and reports the primary alone "
+                         "(and, with --dump-outputs, the secondary workloads whose outputs it writes)")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full, --dump-outputs) do not time the secondary workloads")
     ap.add_argument("--secondary-log2n", type=int, default=None, help="(tests) scale the secondary workloads: 2^k sponge messages, 2^(k+4) tree leaves")
     ap.add_argument("--secondary-timeout", type=int, default=240, help="N > 1: seconds a secondary workload may take before the line is printed without it (0 = no watchdog)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline leg")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where rank 0 writes the full record (nested models, sources, per-rank arrays, notes); the printed line names it")
@@ -1033,7 +1042,10 @@ def main():
 
     primary_key = args.workload or "merkle4_digests"
     # BASELINE configs[2] / [3] (configs[4] at 8 ranks), then the SURVEY §8(f) rows that have kernels of their own
-    secondary_keys = [] if (args.workload or args.no_secondary) else ["tree", "forest", "sponge42", "openings", "encrypt", "extract"]
+    # (a plain run leaves them out unless --dump-outputs asks for what their timed steps return)
+    secondary_keys = ([] if (args.workload or args.no_secondary or not (args.full or args.dump_outputs)) else
+                      ["tree", "forest", "sponge42", "openings", "encrypt", "extract"])
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
     sclk0 = sysfs_sclk_mhz(torch, local_rank)
 
     # --dump-outputs budget: half for the primary, the other half shared by the secondaries
@@ -1051,7 +1063,7 @@ def main():
             if not ok:
                 print("SELF-CONSISTENCY FAILURE on rank %d (%s)" % (rank, key), file=sys.stderr)
                 sys.exit(3)
-        sample = W.oracle_sample() if (rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_check) else None
+        sample = W.oracle_sample() if (rank == 0 and cpu_leg and not args.no_check) else None
         return W, elapsed, launch_ms, cb, ca, ok, sample
 
     if rank == 0:
@@ -1098,7 +1110,7 @@ def main():
     del W
     torch.cuda.empty_cache()
 
-    # ---- secondary workloads: the other BASELINE configs, same discipline, same command ----
+    # ---- secondary workloads (--full, --dump-outputs): the other BASELINE configs, same discipline, same command ----
     secondary = {}
     # Watchdog (N > 1 only): the primary line above is what the scaling curve is made of.  A secondary workload that HANGS — a
     # collective that never completes on a node this code has never seen (no 8-GPU box was ever available to the builder) — must
@@ -1160,7 +1172,7 @@ def main():
     if rank == 0:
         if secondary_keys:
             line["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_leg:
             # the cpu_baseline leg is the ONLY place bench.py touches oracle/: it times the CPU restatement and,
             # as a by-product, checks a strided sample of the GPU output of every workload just measured against it
             import poseidon252_amd as P2

@@ -34,3 +34,13 @@ def test_gpus_without_launcher_spawns_ranks_and_fails_loudly_without_gpus():
 
 def test_bad_gpus_value():
     assert _run(["--gpus", "0"]).returncode == 2
+
+
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """the cpu_baseline leg runs with --full alone, the secondary workloads with --full or --dump-outputs: a plain run times the primary"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    assert bench.parse().full is True

@@ -75,7 +75,7 @@ def test_bench_single_gpu_json_line(gpu_ctx):
     assert r["hbm"]["frac"] < 0.05 and r["hbm_frac"] == r["hbm"]["frac"]
     _check_roofline_scalars(r)
     _check_clock(r)
-    assert "secondary" not in d  # (--no-secondary below: the default line carries them, see the next test)
+    assert "secondary" not in d  # (a plain run: only a --full line carries them, see the next test)
 
 
 def _check_roofline_scalars(r):
@@ -108,11 +108,11 @@ def _check_clock(r):
 
 
 def test_bench_default_line_carries_the_secondary_workloads(gpu_ctx):
-    """the one command the driver runs times every BASELINE config — configs[1] as the primary keys, the tree
+    """one command times every BASELINE config (with --full) — configs[1] as the primary keys, the tree
     (configs[2]; configs[4] at 8 ranks) and the 42 -> 5 sponge (configs[3]) under "secondary", each with its own
     self-consistency check, roofline, measured clock and (N = 1) oracle check of a sample.  Scaled down here."""
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log2n", "15",
-                                   "--secondary-log2n", "14"], cwd=ROOT, timeout=900, stderr=subprocess.DEVNULL)
+                                   "--secondary-log2n", "14", "--full"], cwd=ROOT, timeout=900, stderr=subprocess.DEVNULL)
     line, d = _one_json_line(out, want_detail=True)  # (the length budget and scalars-only shape are asserted on the real line in there)
     for k in REQUIRED + ["cpu_baseline", "secondary"]:
         assert k in d and k in line, k
@@ -183,7 +183,7 @@ def test_bench_rccl_backend_single_rank(gpu_ctx):
     env = dict(os.environ, P252_BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                                   "--log2n", "14", "--secondary-log2n", "12", "--no-cpu-baseline"], cwd=ROOT, env=env, timeout=600,
+                                   "--log2n", "14", "--secondary-log2n", "12", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, timeout=600,
                                   stderr=subprocess.DEVNULL)
     line, d = _one_json_line(out, want_detail=True)
     assert d["n_gpus"] == 1 and d["self_consistency_ok"] is True and line["config"]["constants_identical_on_all_ranks"] is True
@@ -235,7 +235,7 @@ def test_bench_two_ranks_share_gpu_gloo(gpu_ctx):
     env = dict(os.environ, P252_BENCH_SHARE_GPU="1", P252_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--log2n", "16", "--secondary-log2n", "12"]
+           "--warmup", "1", "--log2n", "16", "--secondary-log2n", "12", "--full"]
     out = subprocess.check_output(cmd, cwd=ROOT, env=env, timeout=900, stderr=subprocess.DEVNULL)
     line, d = _one_json_line(out, want_detail=True)
     assert line["n_gpus"] == 2 and line["config"]["ranks"] == 2 and line["value"] == pytest.approx(2 * line["config"]["units_per_gpu_per_step"] * 3 / (line["ms_per_step"] * 3e-3), rel=1e-6)
@@ -259,7 +259,7 @@ def test_bench_two_ranks_share_gpu_gloo(gpu_ctx):
 
 
 def _rehearse_the_driver_command(oracle_mod, world, share_gpu):
-    """`python bench.py --gpus <world> --steps K --warmup W` at scaled-down sizes: rendezvous, the world-way configs[4] composition of
+    """`python bench.py --gpus <world> --steps K --warmup W --full` at scaled-down sizes: rendezvous, the world-way configs[4] composition of
     the secondary tree (world subtrees, all-gather of world x 32-byte roots, zero-padded top levels), the whole-job unit count,
     per-rank times — and the root equals the oracle's tree over the CONCATENATION of the ranks' leaves"""
     import numpy as np
@@ -271,7 +271,7 @@ def _rehearse_the_driver_command(oracle_mod, world, share_gpu):
     for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR"):
         env.pop(key, None)
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-                                   "--log2n", "12", "--secondary-log2n", str(2 * k - 4)], cwd=ROOT, env=env, timeout=1500, stderr=subprocess.DEVNULL)
+                                   "--log2n", "12", "--secondary-log2n", str(2 * k - 4), "--full"], cwd=ROOT, env=env, timeout=1500, stderr=subprocess.DEVNULL)
     line, d = _one_json_line(out, want_detail=True)  # the multi-rank line (per-rank arrays live in the side file) stays inside the budget too
     top = P.levels_len(world)
     assert line["n_gpus"] == world and line["config"]["ranks"] == world and line["ms_per_step_rank_min"] <= line["ms_per_step_rank_max"]
@@ -321,7 +321,7 @@ def test_bench_watchdog_prints_the_line_when_a_secondary_hangs(gpu_ctx):
     env = dict(os.environ, P252_BENCH_SHARE_GPU="1", P252_BENCH_BACKEND="gloo", P252_BENCH_TEST_HANG="sponge42")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--log2n", "12", "--secondary-log2n", "8", "--secondary-timeout", "8"]
+           "--warmup", "1", "--log2n", "12", "--secondary-log2n", "8", "--secondary-timeout", "8", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, timeout=600, capture_output=True)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d, full = _one_json_line(r.stdout, want_detail=True)  # (the watchdog prints the same bounded line)
@@ -362,6 +362,32 @@ def test_bench_refuses_more_ranks_than_devices(gpu_ctx):
                         "--no-cpu-baseline"], cwd=ROOT, env=env, timeout=600, capture_output=True)
     assert r.returncode != 0
     assert not [l for l in r.stdout.decode().splitlines() if l.strip().startswith("{")]
+
+
+def test_bench_plain_run_times_the_primary_alone_and_dumps_what_full_dumps(gpu_ctx, tmp_path):
+    """a plain run (no --full) times and self-checks the primary and nothing else: no secondary workload, no cpu_baseline leg.  With
+    --dump-outputs it times the secondaries too, whose outputs the files hold, and writes what a --full run of the same command line
+    writes, file for file (the default primary, 2^20 digests, is a sample of rows in half the budget)"""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--secondary-log2n", "8"]
+    runs = {}
+    for name, extra in (("plain", []), ("plain_dump", ["--dump-outputs", str(tmp_path / "plain_dump")]),
+                        ("full_dump", ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full_dump")])):
+        r = subprocess.run(base + extra, cwd=ROOT, timeout=900, capture_output=True)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        runs[name] = (_one_json_line(r.stdout), r.stderr.decode())
+    line, err = runs["plain"]
+    assert "secondary" not in line and "cpu_baseline" not in line and line["self_consistency_ok"] is True
+    assert line["steps"] == 2 and line["config"]["units_per_gpu_per_step"] == 1 << 20 and "bench.py: secondary" not in err
+    secondaries = ["encrypt", "extract", "forest", "openings", "sponge42", "tree"]
+    for name in ("plain_dump", "full_dump"):
+        assert sorted(runs[name][0]["secondary"]) == secondaries and "cpu_baseline" not in runs[name][0]
+    files = sorted(os.listdir(str(tmp_path / "plain_dump")))
+    assert files == sorted(os.listdir(str(tmp_path / "full_dump")))
+    assert set(k + "_rows.npy" for k in ["merkle4_digests"] + secondaries) <= set(files)
+    assert 0 < len(np.load(str(tmp_path / "plain_dump" / "merkle4_digests_rows.npy"))) < (1 << 20)
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "plain_dump" / f)), np.load(str(tmp_path / "full_dump" / f))), f
 
 
 def test_bench_dump_outputs_are_what_the_timed_steps_computed(gpu_ctx, oracle_mod, tmp_path):

@@ -53,7 +53,7 @@ def main(path, title="", warm=10, steps=50):
             print("%-60s %8d %12.1f %12.1f %12.1f %14.1f" % (short_name(name, 58), len(rest), sum(rest) / len(rest) / 1e3, min(rest) / 1e3,
                                                              max(rest) / 1e3, sum(head) / len(head) / 1e3))
     print()
-    print("# the library's kernels per launch size (one default bench.py run launches several: configs[1]'s 2^20 digests, the tree's")
+    print("# the library's kernels per launch size (one bench.py --full run launches several: configs[1]'s 2^20 digests, the tree's")
     print("# twelve levels, the sponge).  `steady` = the launches after the first %d of that size (wake-up, warm-up, probe steps)." % warm)
     print("%-44s %10s %7s %12s %12s %12s %12s" % ("kernel", "grid", "calls", "avg_us", "min_us", "steady_calls", "steady_avg_us"))
     for name, grid in list(cur.execute("select name, grid_x from kernels where name like '%p252::%' group by name, grid_x order by name, grid_x desc")):
