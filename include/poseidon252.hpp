@@ -14,6 +14,7 @@
 //   panic!("io-pattern should be valid")            throws IoPatternError        (hash.rs:124-137)
 //   —                                               HashBatch: n messages, one kernel launch
 //   Hash::digest over messages of any lengths       RaggedHashBatch: n messages of different lengths, one call
+//   —                                               merkle_forest_ragged: trees of different sizes, one call
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -413,6 +414,54 @@ inline void merkle4_forest_device(const void* d_leaves, std::size_t n_trees, std
     const BlsScalar tag = compute_tag(Domain::Merkle4, {4}, 1);
     detail::check(p252_merkle4_forest_device(ctx.get(), tag.data(), d_leaves, n_trees, leaves_per_tree, d_roots, d_levels, stream), ctx.get(),
                   "merkle4_forest_device");
+}
+
+// Trees of DIFFERENT sizes in one call (p252_merkle{4,2}_forest_ragged): roots[t] = the root of trees[t] alone (what
+// p252_merkle{4,2}_tree returns), one launch per level across all trees.  With want_levels, `levels` is TREE-MAJOR — tree t's
+// block, at level_offsets[t], is byte for byte what the single-tree call writes (not the level-major layout of
+// merkle4_forest_device) — and level_offsets holds the n_trees + 1 prefix sums of p252_merkle{4,2}_levels_len(n_t).
+struct RaggedForest {
+    std::vector<BlsScalar> roots;
+    std::vector<BlsScalar> levels;
+    std::vector<std::uint64_t> level_offsets;
+};
+inline RaggedForest merkle_forest_ragged(const std::vector<std::vector<BlsScalar>>& trees, unsigned arity = 4, bool want_levels = false,
+                                         Context& ctx = Context::default_context()) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged: arity must be 4 or 2");
+    RaggedForest f;
+    std::vector<BlsScalar> flat;
+    std::vector<std::uint64_t> offsets(1, 0);
+    f.level_offsets.assign(1, 0);
+    for (std::size_t t = 0; t < trees.size(); ++t) {
+        if (trees[t].empty()) throw std::invalid_argument("merkle_forest_ragged: tree " + std::to_string(t) + " is empty");
+        flat.insert(flat.end(), trees[t].begin(), trees[t].end());
+        offsets.push_back(flat.size());
+        const std::size_t ll = arity == 4 ? p252_merkle4_levels_len(trees[t].size()) : p252_merkle2_levels_len(trees[t].size());
+        f.level_offsets.push_back(f.level_offsets.back() + ll);
+    }
+    f.roots.resize(trees.size());
+    if (want_levels) f.levels.resize(f.level_offsets.back());
+    if (trees.empty()) return f;
+    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
+    std::uint64_t* lv = f.levels.empty() ? nullptr : f.levels[0].data();
+    const int rc = arity == 4 ? p252_merkle4_forest_ragged(ctx.get(), tag.data(), flat[0].data(), offsets.data(), trees.size(), f.roots[0].data(), lv)
+                              : p252_merkle2_forest_ragged(ctx.get(), tag.data(), flat[0].data(), offsets.data(), trees.size(), f.roots[0].data(), lv);
+    detail::check(rc, ctx.get(), "merkle_forest_ragged");
+    if (!want_levels) f.level_offsets.clear();
+    return f;
+}
+
+// The device form (p252_merkle{4,2}_forest_ragged_device), asynchronous on `stream`: tree t = d_leaves[d_offsets[t] .. d_offsets[t+1])
+// (n_trees + 1 device uint64 offsets), n_leaves = the scalars d_leaves holds.  Bad trees get zero roots and increment *d_n_bad.
+// d_levels (tree-major) must hold n_leaves / (arity - 1) + n_trees * p252_merkle{4,2}_depth(max_leaves) scalars.
+inline void merkle_forest_ragged_device(const void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
+                                        std::size_t max_leaves, void* d_roots, unsigned arity = 4, Context& ctx = Context::default_context(),
+                                        void* d_levels = nullptr, void* d_n_bad = nullptr, void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_device: arity must be 4 or 2");
+    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
+    auto fn = arity == 4 ? p252_merkle4_forest_ragged_device : p252_merkle2_forest_ragged_device;
+    detail::check(fn(ctx.get(), tag.data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels, d_n_bad, stream), ctx.get(),
+                  "merkle_forest_ragged_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

@@ -86,7 +86,8 @@ extern "C" {
  *      local build in a sharded tree: the healthy ranks' root becomes all-ones and p252_comm_check / p252_sync return
  *      P252_ERR_COMM — they used to return a garbage root as P252_OK), p252_trim (gives the grow-only scratch back);
  *      p252_scratch_residue no longer counts the encryption call table (it holds nothing of the caller's)
- *   9  + p252_hash_ragged[_truncated][_device]: n messages of different lengths in one call */
+ *   9  + p252_hash_ragged[_truncated][_device]: n messages of different lengths in one call;
+ *      + p252_merkle{4,2}_forest_ragged[_device] (additive, same version): trees of different sizes in one call */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -342,6 +343,39 @@ int p252_merkle4_forest(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* le
 /* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag): leaves_per_tree = 2^k, p252_merkle2_levels_len per tree */
 int p252_merkle2_forest_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_trees, size_t leaves_per_tree,
                                void* d_roots, void* d_levels, void* hip_stream);
+
+/* A forest of n_trees trees of DIFFERENT sizes in one call.  Tree t = d_leaves[offsets[t] .. offsets[t+1]) (n_trees + 1 uint64
+ * offsets, device, 8-byte aligned; offsets[0] need not be 0), n_t = offsets[t+1] - offsets[t] leaves; n_leaves = the length of
+ * d_leaves in scalars.  d_roots[t] (device) = what p252_merkle4_tree returns for those leaves (each level zero-padded to a multiple
+ * of the arity, a single leaf is its own root).  Each level is ONE launch across all trees, as in p252_merkle4_forest_device.
+ * d_levels (device, may be NULL = roots only) is TREE-MAJOR, unlike the level-major layout of p252_merkle4_forest_device: tree t's
+ * block starts at LO[t] = the sum over good trees s < t of p252_merkle4_levels_len(n_s) and holds byte for byte what
+ * p252_merkle4_tree writes for it alone — so a tree's block goes unchanged into p252_merkle4_openings_device, the verify calls and
+ * p252_merkle4_update_device.  A caller with device-only offsets can size d_levels as
+ * n_leaves / 3 + n_trees * p252_merkle4_depth(max_leaves) scalars.
+ * A tree is bad when n_t == 0, n_t > max_leaves, its offsets decrease, offsets[t+1] > n_leaves, or n_t plus the leaf counts of the
+ * trees before it that pass those checks exceed n_leaves (only possible when trees overlap behind decreasing offsets): its root is
+ * written as zero, it has no level storage, and *d_n_bad (device uint32 the caller has zeroed; may be NULL) is incremented once per
+ * bad tree.  Good trees are unaffected.  max_leaves == 0 -> P252_ERR_INVALID_ARGUMENT; n_trees == 0 -> P252_OK, nothing enqueued.
+ * The bookkeeping (scans over the trees) and, without d_levels, the level ping-pong live in the context's scratch of THIS stream
+ * (p252_trim / p252_wipe cover it).  Asynchronous on hip_stream: no host synchronisation, no allocation once that scratch is
+ * warm — it can be captured into a hipGraph. */
+int p252_merkle4_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                      const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels,
+                                      void* d_n_bad, void* hip_stream);
+/* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag): p252_merkle2_levels_len per tree, d_levels bound
+ * n_leaves + n_trees * p252_merkle2_depth(max_leaves) */
+int p252_merkle2_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                      const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels,
+                                      void* d_n_bad, void* hip_stream);
+/* host-buffer twins (synchronous): leaves = the scalars offsets[0] .. offsets[n_trees]; every tree is checked first — an empty tree
+ * or decreasing offsets -> P252_ERR_INVALID_ARGUMENT (nothing is hashed; p252_last_error names the tree).  roots[n_trees];
+ * levels (may be NULL): the tree-major layout above, sum of p252_merkle{4,2}_levels_len(n_t) scalars.  The leaves and offsets go
+ * through the context's grow-only device scratch in one piece: there is no chunked pipeline over pageable memory. */
+int p252_merkle4_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets,
+                               size_t n_trees, uint64_t* roots, uint64_t* levels);
+int p252_merkle2_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets,
+                               size_t n_trees, uint64_t* roots, uint64_t* levels);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

@@ -86,6 +86,10 @@ PROTOTYPES = {
     "p252_merkle4_forest_device": _f(_vp, _u64p, _vp, _sz, _sz, _vp, _vp, _vp),
     "p252_merkle4_forest": _f(_vp, _u64p, _u64p, _sz, _sz, _u64p),
     "p252_merkle2_forest_device": _f(_vp, _u64p, _vp, _sz, _sz, _vp, _vp, _vp),
+    "p252_merkle4_forest_ragged_device": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp),
+    "p252_merkle2_forest_ragged_device": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp),
+    "p252_merkle4_forest_ragged": _f(_vp, _u64p, _u64p, _u64p, _sz, _u64p, _u64p),
+    "p252_merkle2_forest_ragged": _f(_vp, _u64p, _u64p, _u64p, _sz, _u64p, _u64p),
     "p252_hash_batch_multi": _f(_vpp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz),
     "p252_hash_batch_multi_device": _f(_vpp, _sz, _u64p, _vpp, _sz, _sz, _vpp, _szp, _vpp),
     "p252_merkle4_tree_multi": _f(_vpp, _sz, _u64p, _u64p, _sz, _u64p),
@@ -220,7 +224,13 @@ def lib():
                     return m
         L = _Tolerant(L)
     for name, (argtypes, restype) in PROTOTYPES.items():
-        fn = getattr(L, name)
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            # entry points added within one ABI version (additive): a build from before them reports the right version but
+            # lacks the symbol — name it instead of a raw AttributeError
+            raise ExtensionMissing("%s does not export %s, which this binding declares: it is a stale build — rebuild it "
+                                   "(python -m poseidon252_amd.build)" % (LIB_PATH, name)) from None
         fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L

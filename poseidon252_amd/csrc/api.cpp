@@ -14,6 +14,7 @@
 #include "../../include/poseidon252_hip.h"
 #include "blake2b.hpp"
 #include "ctx.hpp"
+#include "forest_ragged.h"
 #include "hades29.hpp"
 #include "kernels.h"
 #include "openings.h"
@@ -548,6 +549,53 @@ int p252_hash_ragged_device(p252_ctx* ctx, const void* d_tags, size_t max_len, c
 int p252_hash_ragged_truncated_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
                                       size_t out_len, void* d_out_raw, size_t n, void* d_n_bad, void* hip_stream) {
     return hash_ragged_device_impl(ctx, d_tags, max_len, d_in, d_offsets, out_len, d_out_raw, n, d_n_bad, hip_stream, true);
+}
+
+// ---- a forest of trees of different sizes in one call (forest_ragged.hip): the bookkeeping (leaf counts, scans, first tree of
+// each block) and, without d_levels, the level-major ping-pong live in the scratch pair of the calling stream
+static int forest_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels, void* d_n_bad,
+                                void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (n_trees == 0) return P252_OK;
+    if (max_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: max_leaves must be > 0");
+    if (!tag || !d_leaves || !d_offsets || !d_roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_roots) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: d_offsets must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: d_n_bad must be 4-byte aligned");
+    // (the leaf counts of the good trees are summed on the device: n_trees x their largest size stays below 2^63)
+    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;
+    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) ||
+        (eff_max && n_trees > (SIZE_MAX / 2) / eff_max))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestRaggedPlan plan = forest_ragged_plan(arity, n_leaves, n_trees, max_leaves, d_levels != nullptr);
+    const bool ping = !d_levels && plan.depth > 0;
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    int rc = level_set(ctx, st, plan.meta_bytes + (ping ? plan.bound[1] * 32 : 0), ping && plan.depth > 1 ? plan.bound[2] * 32 : 0, &set);
+    if (rc) return rc;
+    char* meta = static_cast<char*>(set->buf[0]);
+    const hipError_t e = launch_forest_ragged(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, max_leaves, d_roots, d_levels, d_n_bad,
+                                              meta, ping ? meta + plan.meta_bytes : nullptr, set->buf[1], st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string("merkle_forest_ragged: ") + hipGetErrorString(e));
+    const std::string msg = ctx->err;
+    const int rc2 = guard.finish();
+    if (rc) ctx->err = msg;
+    return rc ? rc : rc2;
+}
+
+int p252_merkle4_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                      size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                      size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels, d_n_bad, hip_stream);
 }
 
 // (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)

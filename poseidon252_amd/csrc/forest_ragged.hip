@@ -1,0 +1,411 @@
+// forest_ragged.hip — a forest of Merkle trees of DIFFERENT sizes in one call (p252_merkle{4,2}_forest_ragged*).  Tree t =
+// leaves[offsets[t] .. offsets[t+1]), n_t leaves; each tree is what p252_merkle{4,2}_tree builds: level l has
+// s_l(t) = ceil(n_t / a^l) nodes while level l-1 had more than one, missing children are the zero scalar, a single leaf is its
+// own root.
+//
+// Why new digest kernels: a level's node count depends on the tree sizes, and in the device form those live on the device, so
+// launch_merkle4 (an exact count, children contiguous and aligned to the arity) cannot be used.  Instead each level is ONE
+// launch over the concatenation of all trees' nodes at that level:
+//   k_fr_prep          per tree: n_t, or 0 for a bad tree (empty, longer than max_leaves, decreasing offsets, past n_leaves)
+//   k_fr_tile_sums / k_fr_scan_tiles / k_fr_scan_apply   an exclusive device-wide scan, three passes (tiles of 2,048 trees),
+//                      over several rows at once (gridDim.y).  First over n_t alone: a tree whose n_t takes the running sum of
+//                      the leaf counts before it past n_leaves is bad as well — that only happens when trees overlap behind
+//                      decreasing offsets, and it is what keeps every level within the host's bound n_leaves / a^l + n_trees.
+//                      The same pass writes the roots of bad trees (zero) and of single-leaf trees (the leaf).  Then over
+//                      every level l at once: C_l = the scan of s_l (row l), and LO = the scan of levels_len(n_t) (row 0,
+//                      only when the caller's d_levels is written).
+//   k_fr_block_first   per level and 256-node block b: the tree that holds node 256 b — so a digest lane looks for its tree
+//                      only between the first trees of its block and of the next one (<= 8 probes on a dense level)
+//   k_fr_digest / k_fr_digest_coop   lane (group of 8 lanes) g hashes node g of level l: t with C_l[t] <= g < C_l[t+1],
+//                      i = g - C_l[t]; children a i .. a i + a - 1 of tree t's level l-1 (zero at or past s_{l-1}(t)).
+//                      Level 0 is the tree's leaves; level l-1 >= 1 is read from the tree's block of d_levels (tree-major,
+//                      closed-form offset) or from the level-major scratch at C_{l-1}[t].  A node that is its tree's only
+//                      node at level l is its root: in the level-major mode it goes to d_roots[t] instead of the scratch; in
+//                      the tree-major mode k_fr_roots_from_levels copies it from the end of the tree's block after the last
+//                      level (one output pointer per lane: the lane groups then hold their 256 VGPRs without AGPR spills).
+// The permutation is the library's: hades_permute<0x02u, true> with the hoisted tag S-box (the k_merkle4 build, 3 waves per
+// SIMD) and hades_permute_coop<8> (coop29.hpp) for levels that cannot fill the chip (the coop8 rule of kernels.h).
+#include <hip/hip_runtime.h>
+
+#include "coop29.hpp"
+#include "forest_ragged.h"
+#include "hades29.hpp"
+#include "kernels.h"
+
+namespace p252 {
+
+namespace {
+
+constexpr unsigned FR_BLOCK = 256;
+constexpr unsigned FR_ITEMS = 8;  // trees per thread of a scan block
+constexpr unsigned FR_TILE = FR_BLOCK * FR_ITEMS;
+constexpr unsigned FR_ROW_LEAVES = 0xffffffffu;  // scan row of the leaf counts n_t themselves
+
+// ceil(n / 2^k) for any k
+__device__ __forceinline__ uint64_t ceil_shift(uint64_t n, unsigned k) {
+    if (k >= 64) return n != 0;
+    return (n >> k) + ((n & ((1ull << k) - 1)) != 0);
+}
+// nodes of level l >= 1 of a tree of n leaves (0: the tree ended below l)
+__device__ __forceinline__ uint64_t level_nodes(uint64_t n, unsigned l, unsigned la) {
+    return ceil_shift(n, (l - 1) * la) > 1 ? ceil_shift(n, l * la) : 0;
+}
+// p252_merkle{4,2}_levels_len(n)
+__device__ __forceinline__ uint64_t levels_len_dev(uint64_t n, unsigned la) {
+    uint64_t total = 0;
+#pragma unroll 1
+    for (uint64_t c = n; c > 1;) {
+        c = ceil_shift(c, la);
+        total += c;
+    }
+    return total;
+}
+// start of level l >= 1 inside the levels block of a tree of n leaves (levels 1 .. l-1 before it)
+__device__ __forceinline__ uint64_t level_start(uint64_t n, unsigned l, unsigned la) {
+    uint64_t w = 0;
+#pragma unroll 1
+    for (unsigned j = 1; j < l; ++j) w += ceil_shift(n, j * la);
+    return w;
+}
+
+__device__ __forceinline__ uint64_t row_value(const uint64_t* __restrict__ ntree, size_t t, unsigned row, unsigned la) {
+    const uint64_t n = ntree[t];
+    if (row == FR_ROW_LEAVES) return n;
+    return row == 0 ? levels_len_dev(n, la) : level_nodes(n, row, la);
+}
+
+// exclusive scan of one value per thread over the block (returns the block total in *total)
+__device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* total) {
+    __shared__ uint64_t part[FR_BLOCK];
+    const unsigned t = threadIdx.x;
+    part[t] = v;
+    __syncthreads();
+    for (unsigned off = 1; off < FR_BLOCK; off <<= 1) {
+        const uint64_t o = t >= off ? part[t - off] : 0ull;
+        __syncthreads();
+        part[t] += o;
+        __syncthreads();
+    }
+    const uint64_t incl = part[t];
+    *total = part[FR_BLOCK - 1];
+    __syncthreads();  // (part is reused by the caller's next call)
+    return incl - v;
+}
+
+}  // namespace
+
+// ---- validation ----
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_prep(const uint64_t* __restrict__ offsets, size_t n_trees, uint64_t n_leaves,
+                                                      uint64_t max_leaves, uint64_t* __restrict__ ntree) {
+    const size_t t = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
+    if (t >= n_trees) return;
+    const uint64_t lo = offsets[t], hi = offsets[t + 1];
+    const uint64_t n = hi - lo;
+    const bool good = hi >= lo && n >= 1 && n <= max_leaves && hi <= n_leaves;
+    ntree[t] = good ? n : 0;
+}
+
+// ---- the scan: rows row0 + blockIdx.y (row0 == FR_ROW_LEAVES: that one row), tiles of FR_TILE trees ----
+__device__ __forceinline__ unsigned scan_row(unsigned row0) { return row0 == FR_ROW_LEAVES ? row0 : row0 + blockIdx.y; }
+
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_tile_sums(const uint64_t* __restrict__ ntree, size_t n_trees, unsigned row0, unsigned la,
+                                                           uint64_t* __restrict__ tsum) {
+    const unsigned row = scan_row(row0);
+    const size_t t0 = (size_t)blockIdx.x * FR_TILE + (size_t)threadIdx.x * FR_ITEMS;
+    uint64_t sum = 0;
+#pragma unroll 1
+    for (unsigned k = 0; k < FR_ITEMS; ++k)
+        if (t0 + k < n_trees) sum += row_value(ntree, t0 + k, row, la);
+    uint64_t total;
+    (void)block_exclusive(sum, &total);
+    if (threadIdx.x == 0) tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// one block per row: the tile sums of the row -> their exclusive scan, in place
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_tiles(uint64_t* __restrict__ tsum, size_t tiles) {
+    uint64_t* row = tsum + (size_t)blockIdx.x * tiles;
+    uint64_t carry = 0;
+#pragma unroll 1
+    for (size_t base = 0; base < tiles; base += FR_BLOCK) {
+        const size_t i = base + threadIdx.x;
+        const uint64_t v = i < tiles ? row[i] : 0ull;
+        uint64_t total;
+        const uint64_t ex = block_exclusive(v, &total);
+        if (i < tiles) row[i] = carry + ex;
+        carry += total;
+    }
+}
+
+// FIRST (the leaf-count row): the sum rule above, then the roots of bad and single-leaf trees.  Otherwise: C[row][t] for every
+// tree and C[row][n_trees] = the row's total.
+template <bool FIRST>
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_apply(uint64_t* __restrict__ ntree, size_t n_trees, unsigned row0, unsigned la,
+                                                            const uint64_t* __restrict__ tsum, uint64_t* __restrict__ C,
+                                                            uint64_t n_leaves, const uint64_t* __restrict__ offsets,
+                                                            const Scalar32* __restrict__ leaves, Scalar32* __restrict__ roots,
+                                                            unsigned* __restrict__ n_bad) {
+    const unsigned row = scan_row(row0);
+    const size_t t0 = (size_t)blockIdx.x * FR_TILE + (size_t)threadIdx.x * FR_ITEMS;
+    uint64_t v[FR_ITEMS], sum = 0;
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k) {
+        v[k] = t0 + k < n_trees ? row_value(ntree, t0 + k, row, la) : 0ull;
+        sum += v[k];
+    }
+    uint64_t total;
+    uint64_t run = tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive(sum, &total);
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k) {
+        const size_t t = t0 + k;
+        if (t >= n_trees) break;
+        if (FIRST) {
+            uint64_t n = v[k];
+            if (run > n_leaves || n > n_leaves - run) {  // (run <= n_trees * max_leaves < 2^63: api.cpp refuses larger)
+                n = 0;
+                ntree[t] = 0;
+            }
+            if (n == 0) {
+                store_zero(roots + t);
+                if (n_bad) atomicAdd(n_bad, 1u);
+            } else if (n == 1) {
+                const uint4* src = reinterpret_cast<const uint4*>(leaves + offsets[t]);
+                uint4* dst = reinterpret_cast<uint4*>(roots + t);
+                dst[0] = src[0];
+                dst[1] = src[1];
+            }
+        } else {
+            uint64_t* Crow = C + (size_t)row * (n_trees + 1);
+            Crow[t] = run;
+            if (t == n_trees - 1) Crow[n_trees] = run + v[k];
+        }
+        run += v[k];
+    }
+}
+
+// the tree that holds node 256 b of level l = blockIdx.y + 1: the largest t with C_l[t] <= 256 b
+struct FirstRows {
+    uint64_t off[FOREST_RAGGED_MAX_DEPTH + 1];
+    uint64_t len[FOREST_RAGGED_MAX_DEPTH + 1];
+};
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_block_first(const uint64_t* __restrict__ C, size_t n_trees, FirstRows fr,
+                                                             uint64_t* __restrict__ first) {
+    const unsigned l = blockIdx.y + 1;
+    const size_t b = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
+    if (b >= fr.len[l]) return;
+    const uint64_t* Crow = C + (size_t)l * (n_trees + 1);
+    const uint64_t g = (uint64_t)b * 256;
+    size_t lo = 0, hi = n_trees - 1;  // C[0] = 0 <= g
+    while (lo < hi) {
+        const size_t mid = (lo + hi + 1) >> 1;
+        if (Crow[mid] <= g)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    first[fr.off[l] + b] = lo;
+}
+
+// ---- the digests of one level ----
+struct FrLevel {
+    const uint64_t* C;      // this level's node starts, n_trees + 1
+    const uint64_t* Cprev;  // level l-1's (level-major scratch, l >= 2)
+    const uint64_t* first;  // first tree of each 256-node block
+    const uint64_t* LO;     // tree-major levels: each tree's block
+    const uint64_t* ntree;
+    const uint64_t* offsets;
+    const Scalar32* leaves;
+    const Scalar32* src;    // level-major scratch: level l-1
+    Scalar32* dst;          // level-major scratch: level l
+    Scalar32* levels;       // the caller's d_levels (tree-major), or null
+    Scalar32* roots;
+    size_t n_trees;
+    size_t lanes;
+    unsigned level, la;
+};
+
+// node g's tree and position, its children's array and its output slot.  false: no such node (g at or past the level's total).
+struct FrNode {
+    const Scalar32* children;
+    uint64_t i, n_children;
+    Scalar32* out;
+};
+__device__ __forceinline__ bool fr_node(const FrLevel& P, uint64_t g, FrNode& nd) {
+    const uint64_t* __restrict__ C = P.C;
+    if (g >= C[P.n_trees]) return false;
+    size_t lo = P.first[g >> 8], hi = P.first[(g >> 8) + 1];
+    while (lo < hi) {
+        const size_t mid = (lo + hi + 1) >> 1;
+        if (C[mid] <= g)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const size_t t = lo;
+    const uint64_t n = P.ntree[t];
+    const unsigned l = P.level;
+    nd.i = g - C[t];
+    nd.n_children = ceil_shift(n, (l - 1) * P.la);
+    if (P.levels) {
+        Scalar32* blk = P.levels + P.LO[t];
+        nd.children = l == 1 ? P.leaves + P.offsets[t] : blk + level_start(n, l - 1, P.la);
+        nd.out = blk + level_start(n, l, P.la) + nd.i;
+    } else {  // (a root is read by no later level: it goes to d_roots only)
+        nd.children = l == 1 ? P.leaves + P.offsets[t] : P.src + P.Cprev[t];
+        nd.out = ceil_shift(n, l * P.la) == 1 ? P.roots + t : P.dst + g;
+    }
+    return true;
+}
+
+template <unsigned ARITY>
+__global__ void __launch_bounds__(P252_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 3)))
+k_fr_digest(const int32_t* __restrict__ tab, TagArg tag, FrLevel P) {
+    const uint64_t g = (uint64_t)blockIdx.x * P252_BLOCK + threadIdx.x;
+    if (g >= P.lanes) return;
+    FrNode nd;
+    if (!fr_node(P, g, nd)) return;
+    E29 s[WIDTH];
+#pragma unroll
+    for (int k = 0; k < NL; ++k) s[0].d[k] = tag.x0[k];  // lane 0 enters after its first S-box (hades_permute PRE0)
+#pragma unroll
+    for (unsigned k = 0; k < 4; ++k) {
+        const uint64_t c = nd.i * ARITY + k;
+        if (k < ARITY && c < nd.n_children)
+            s[1 + k] = load_scalar(nd.children + c);
+        else
+            s[1 + k] = e29_zero();
+    }
+    hades_permute<0x02u, true>(s, tab);  // only lane 1 is squeezed
+    store_scalar(nd.out, s[1]);
+}
+
+template <unsigned ARITY>
+__global__ void __launch_bounds__(P252_BLOCK) k_fr_digest_coop(const int32_t* __restrict__ tab, TagArg tag, FrLevel P) {
+    const uint64_t lane = (uint64_t)blockIdx.x * P252_BLOCK + threadIdx.x;
+    if (lane >= P.lanes) return;  // (lanes is a multiple of 8: whole groups only)
+    FrNode nd;
+    if (!fr_node(P, lane >> 3, nd)) return;  // (the whole group: one node)
+    const int j = (int)(threadIdx.x & 7u);
+    const int el = j < WIDTH ? j : WIDTH - 1;  // the state element this lane brings: 0 = tag, 1..4 = children
+    E29 mine = from_mont4(tag.w);
+    if (el > 0) {
+        const uint64_t c = nd.i * ARITY + (uint64_t)(el - 1);
+        mine = (unsigned)(el - 1) < ARITY && c < nd.n_children ? load_scalar(nd.children + c) : e29_zero();
+    }
+    E29 last = mine;
+    WaveComm8 cm{j, (int)(((threadIdx.x & 63u) & ~7u) * 4u)};
+    CoopLane<8> L = coop_lane<8>(tab, cm);
+    hades_permute_coop<8, false>(mine, last, tab, cm, L);
+    if (j == 1) store_scalar(nd.out, mine);  // the digest is element 1 of the permuted state: lane 1's
+}
+
+// tree-major levels: each tree's root is the last scalar of its block (trees of one leaf and bad trees have theirs already)
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_roots_from_levels(const uint64_t* __restrict__ ntree, const uint64_t* __restrict__ LO,
+                                                                   size_t n_trees, unsigned la, const Scalar32* __restrict__ levels,
+                                                                   Scalar32* __restrict__ roots) {
+    const size_t t = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
+    if (t >= n_trees) return;
+    const uint64_t n = ntree[t];
+    if (n < 2) return;
+    const uint4* src = reinterpret_cast<const uint4*>(levels + LO[t] + levels_len_dev(n, la) - 1);
+    uint4* dst = reinterpret_cast<uint4*>(roots + t);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
+// ---------------------------------------------------------------------------------------------
+// launcher (C++ linkage, called from api.cpp)
+// ---------------------------------------------------------------------------------------------
+unsigned forest_ragged_depth(size_t max_leaves, unsigned arity) {
+    unsigned d = 0;
+    for (size_t c = max_leaves; c > 1; c = (c + arity - 1) / arity) ++d;
+    return d;
+}
+
+ForestRaggedPlan forest_ragged_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, bool levels) {
+    ForestRaggedPlan p;
+    p.arity = arity;
+    p.log2a = arity == 4 ? 2 : 1;
+    p.levels = levels;
+    p.n_trees = n_trees;
+    p.n_leaves = n_leaves;
+    // a good tree has at most min(max_leaves, n_leaves) leaves
+    p.depth = forest_ragged_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
+    p.tiles = (n_trees + FR_TILE - 1) / FR_TILE;
+    size_t words = n_trees + (size_t)(p.depth + 1) * (n_trees + 1) + (size_t)(p.depth + 1) * p.tiles;
+    for (unsigned l = 1; l <= p.depth; ++l) {
+        p.bound[l] = (n_leaves >> (l * p.log2a)) + n_trees;
+        p.first_off[l] = words;
+        p.first_len[l] = (p.bound[l] >> 8) + 2;
+        words += p.first_len[l];
+    }
+    p.meta_bytes = (words * 8 + 255) & ~(size_t)255;
+    return p;
+}
+
+hipError_t launch_forest_ragged(const int32_t* tab, const TagArg& tag, const ForestRaggedPlan& p, const void* leaves,
+                                const void* offsets, size_t max_leaves, void* roots, void* levels, void* n_bad, void* meta,
+                                void* lvl_a, void* lvl_b, hipStream_t st) {
+    const size_t n = p.n_trees;
+    if (n == 0) return hipSuccess;
+    const uint64_t* off = static_cast<const uint64_t*>(offsets);
+    const Scalar32* lv = static_cast<const Scalar32*>(leaves);
+    Scalar32* rt = static_cast<Scalar32*>(roots);
+    unsigned* nb = static_cast<unsigned*>(n_bad);
+    uint64_t* ntree = static_cast<uint64_t*>(meta);
+    uint64_t* C = ntree + n;
+    uint64_t* tsum = C + (size_t)(p.depth + 1) * (n + 1);
+    uint64_t* first = static_cast<uint64_t*>(meta);
+    const unsigned la = p.log2a;
+    const dim3 blk(FR_BLOCK);
+    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)p.n_leaves, (uint64_t)max_leaves, ntree);
+    // the leaf counts: the sum rule, the roots of bad and single-leaf trees
+    hipLaunchKernelGGL(k_fr_tile_sums, dim3((unsigned)p.tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, p.tiles);
+    hipLaunchKernelGGL(k_fr_scan_apply<true>, dim3((unsigned)p.tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum, C,
+                       (uint64_t)p.n_leaves, off, lv, rt, nb);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || p.depth == 0) return e;
+    // every level's node starts (and LO, the tree-major levels' block starts, in row 0)
+    const unsigned row0 = p.levels ? 0u : 1u, rows = p.depth + 1 - row0;
+    hipLaunchKernelGGL(k_fr_tile_sums, dim3((unsigned)p.tiles, rows), blk, 0, st, ntree, n, row0, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(rows), blk, 0, st, tsum, p.tiles);
+    hipLaunchKernelGGL(k_fr_scan_apply<false>, dim3((unsigned)p.tiles, rows), blk, 0, st, ntree, n, row0, la, tsum, C,
+                       (uint64_t)p.n_leaves, off, lv, rt, nb);
+    FirstRows fr = {};
+    for (unsigned l = 1; l <= p.depth; ++l) {
+        fr.off[l] = p.first_off[l];
+        fr.len[l] = p.first_len[l];
+    }
+    hipLaunchKernelGGL(k_fr_block_first, dim3(grid_for(p.first_len[1]), p.depth), blk, 0, st, C, n, fr, first);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    for (unsigned l = 1; l <= p.depth; ++l) {
+        FrLevel P;
+        P.C = C + (size_t)l * (n + 1);
+        P.Cprev = C + (size_t)(l - 1) * (n + 1);
+        P.first = first + p.first_off[l];
+        P.LO = C;
+        P.ntree = ntree;
+        P.offsets = off;
+        P.leaves = lv;
+        P.src = static_cast<const Scalar32*>((l & 1) ? lvl_b : lvl_a);  // level l-1 (odd levels live in lvl_a)
+        P.dst = static_cast<Scalar32*>((l & 1) ? lvl_a : lvl_b);
+        P.levels = static_cast<Scalar32*>(levels);
+        P.roots = rt;
+        P.n_trees = n;
+        P.level = l;
+        P.la = la;
+        const bool coop = coop8(p.bound[l]);
+        P.lanes = coop ? p.bound[l] * 8 : p.bound[l];
+        if (p.arity == 4)
+            e = launch(coop ? k_fr_digest_coop<4> : k_fr_digest<4>, P.lanes, st, tab, tag, P);
+        else
+            e = launch(coop ? k_fr_digest_coop<2> : k_fr_digest<2>, P.lanes, st, tab, tag, P);
+        if (e != hipSuccess) return e;
+    }
+    if (p.levels)
+        hipLaunchKernelGGL(k_fr_roots_from_levels, dim3(grid_for(n)), blk, 0, st, ntree, C, n, la, static_cast<const Scalar32*>(levels), rt);
+    return hipGetLastError();
+}
+
+}  // namespace p252

@@ -426,6 +426,44 @@ static int hash_ragged_host_impl(p252_ctx* ctx, const uint64_t* tags, size_t max
     return dev_rc ? dev_rc : rc;
 }
 
+// trees of different sizes: every tree is checked here first, then [leaves | offsets rebased to 0] go to the device in one copy
+// each and the roots (and the tree-major levels) come back — synchronous, no chunked pipeline
+static int forest_ragged_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets,
+                              size_t n_trees, uint64_t* roots, uint64_t* levels) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (n_trees == 0) return P252_OK;
+    if (!tag || !leaves || !offsets || !roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: NULL buffer");
+    size_t max_leaves = 0, lvl_n = 0;
+    for (size_t t = 0; t < n_trees; ++t) {
+        if (offsets[t + 1] < offsets[t])
+            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: offsets decrease at tree " + std::to_string(t));
+        const uint64_t n = offsets[t + 1] - offsets[t];
+        if (n == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: tree " + std::to_string(t) + " is empty");
+        if (n > max_leaves) max_leaves = n;
+    }
+    const uint64_t total = offsets[n_trees] - offsets[0];
+    if (total > SIZE_MAX / 64 || n_trees > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: size overflow");
+    if (levels)
+        for (size_t t = 0; t < n_trees; ++t) lvl_n += levels_len(offsets[t + 1] - offsets[t], arity);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> rebased(offsets, offsets + n_trees + 1);
+    for (auto& o : rebased) o -= offsets[0];
+    // the arrays are not per tree: each is one item of its whole size
+    const std::vector<HostSpan> ins = {{reinterpret_cast<const char*>(leaves + offsets[0] * 4), nullptr, (size_t)total * 32},
+                                       {reinterpret_cast<const char*>(rebased.data()), nullptr, (n_trees + 1) * 8}};
+    std::vector<HostSpan> outs = {{nullptr, reinterpret_cast<char*>(roots), n_trees * 32}};
+    if (lvl_n) outs.push_back({nullptr, reinterpret_cast<char*>(levels), lvl_n * 32});
+    int dev_rc = P252_OK;  // (the `_device` call takes the scratch pair of the stream; its status is an entry-point code)
+    const int rc = host_batch(ctx, Route::ONE_SHOT, 1, 1, ins, outs,
+                              [&](const void* const* d_in, void* const* d_out, size_t, size_t, hipStream_t st) {
+                                  dev_rc = (arity == 4 ? p252_merkle4_forest_ragged_device : p252_merkle2_forest_ragged_device)(
+                                      ctx, tag, d_in[0], (size_t)total, d_in[1], n_trees, max_leaves, d_out[0], lvl_n ? d_out[1] : nullptr,
+                                      nullptr, st);
+                                  return hipSuccess;
+                              });
+    return dev_rc ? dev_rc : rc;
+}
+
 static int merkle_tree_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
                             uint64_t root[4], uint64_t* levels) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
@@ -496,6 +534,16 @@ int p252_merkle4_tree(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leav
 int p252_merkle2_tree(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
                       uint64_t root[4], uint64_t* levels) {
     return merkle_tree_host(ctx, 2, tag, leaves, n_leaves, root, levels);
+}
+
+int p252_merkle4_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets, size_t n_trees,
+                               uint64_t* roots, uint64_t* levels) {
+    return forest_ragged_host(ctx, 4, tag, leaves, offsets, n_trees, roots, levels);
+}
+
+int p252_merkle2_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets, size_t n_trees,
+                               uint64_t* roots, uint64_t* levels) {
+    return forest_ragged_host(ctx, 2, tag, leaves, offsets, n_trees, roots, levels);
 }
 
 // Forest from HOST leaves (pageable memory is fine).  Large forests stream the FIRST level — three quarters of all permutations —

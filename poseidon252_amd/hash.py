@@ -323,6 +323,47 @@ class Context:
                        _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_levels", d_levels, levels, null_ok=True),
                        _stream(self)))
 
+    def merkle_forest_ragged(self, tag, flat, offsets, arity=4, want_levels=False):
+        """trees of different sizes from host buffers (p252_merkle{4,2}_forest_ragged): tree t = flat[offsets[t]:offsets[t+1]].
+        Returns roots (n_trees, 4) and, with want_levels, the tree-major levels (sum of levels_len(n_t) scalars).  The library
+        checks every tree first (empty, decreasing offsets -> ValueError)."""
+        if arity not in (2, 4):
+            raise ValueError("merkle_forest_ragged: arity must be 4 or 2, not %r" % (arity,))
+        x = _as_scalars(flat).reshape(-1, 4)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        n = max(off.shape[0] - 1, 0)
+        if n and int(off[-1]) > x.shape[0]:
+            raise ValueError("merkle_forest_ragged: offsets reach past the %d scalars given" % x.shape[0])
+        L = _lib.lib()
+        ll = L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len
+        lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
+        n_levels = sum(ll(int(c)) for c in lens if c > 0) if want_levels else 0
+        roots = np.empty((n, 4), dtype=np.uint64)
+        levels = np.empty((n_levels, 4), dtype=np.uint64) if want_levels else None
+        fn = L.p252_merkle4_forest_ragged if arity == 4 else L.p252_merkle2_forest_ragged
+        self._check(fn(self._h, _tag(tag), _ptr(x), _ptr(off), n, _ptr(roots), _ptr(levels) if n_levels else None))
+        return (roots, levels) if want_levels else roots
+
+    def merkle_forest_ragged_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels=None, d_n_bad=None, arity=4):
+        """p252_merkle{4,2}_forest_ragged_device on torch's current stream: tree t = d_leaves[d_offsets[t]:d_offsets[t+1]]
+        (d_offsets: n_trees + 1 int64/uint64 scalar indices; n_leaves = the scalars d_leaves holds).  d_roots (n_trees, 4);
+        d_levels (tree-major) must hold the bound n_leaves // (arity - 1) + n_trees * depth(max_leaves) scalars, as the offsets
+        are never read back to the host.  Bad trees get zero roots and increment d_n_bad (a zeroed device int32/uint32,
+        optional)."""
+        f = "merkle_forest_ragged_device"
+        if arity not in (2, 4):
+            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+        L = _lib.lib()
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 0)
+        n_leaves = d_leaves.numel() * d_leaves.element_size() // 32
+        depth = L.p252_merkle4_depth(max_leaves) if arity == 4 else L.p252_merkle2_depth(max_leaves)
+        need = (n_leaves // (arity - 1) + n_trees * depth) * 32 if d_levels is not None else 0
+        fn = L.p252_merkle4_forest_ragged_device if arity == 4 else L.p252_merkle2_forest_ragged_device
+        self._check(fn(self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8),
+                       n_trees, max_leaves, _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32),
+                       _dev_ptr(self, f, "d_levels", d_levels, need, null_ok=True),
+                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
         f = "truncate250_device"

@@ -18,10 +18,14 @@ def merkle4_tag():
     return compute_tag(Domain.Merkle4, [4], 1)
 
 
-def levels_len(n_leaves):
+def merkle2_tag():
+    return compute_tag(Domain.Merkle2, [2], 1)
+
+
+def levels_len(n_leaves, arity=4):
     total, c = 0, n_leaves
     while c > 1:
-        c = (c + 3) // 4
+        c = (c + arity - 1) // arity
         total += c
     return total
 
@@ -69,6 +73,61 @@ def merkle4_forest(leaves, leaves_per_tree, tag=None, ctx=None, want_levels=Fals
         roots = roots.cpu().numpy().view(np.uint64)
         levels = levels.cpu().numpy().view(np.uint64) if want_levels else None
     return (roots, levels) if want_levels else roots
+
+
+def _integer_array(a, what):
+    a = np.asarray(a)
+    if a.dtype not in (np.uint64, np.int64):
+        raise ValueError("merkle_forest_ragged: %s must be uint64 or int64, not %s" % (what, a.dtype))
+    return a
+
+
+def _forest_trees(trees):
+    """(flat (S, 4) uint64, offsets (n_trees + 1,) uint64) of a list of (n_t, 4) leaf arrays or of a (flat, offsets) pair, as
+    RaggedHashBatch takes messages; every tree is checked here (dtype, empty, decreasing offsets, extent) before any device work"""
+    if isinstance(trees, tuple):
+        flat, off = trees
+        flat = _as_scalars(_integer_array(flat, "the leaves")).reshape(-1, 4)
+        off = np.ascontiguousarray(_integer_array(off, "the offsets"), dtype=np.uint64).reshape(-1)
+        if off.shape[0] == 0:
+            raise ValueError("merkle_forest_ragged: offsets need n_trees + 1 entries")
+        lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
+        if (lens < 0).any():
+            raise ValueError("merkle_forest_ragged: offsets decrease at tree %d" % int(np.argmax(lens < 0)))
+        if int(off[-1]) > flat.shape[0]:
+            raise ValueError("merkle_forest_ragged: offsets reach past the %d leaves given" % flat.shape[0])
+    else:
+        parts = [_as_scalars(_integer_array(t, "tree %d" % i)).reshape(-1, 4) for i, t in enumerate(trees)]
+        lens = np.array([p.shape[0] for p in parts], dtype=np.int64)
+        off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=off[1:])
+        flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 4), dtype=np.uint64)
+    if (lens == 0).any():
+        raise ValueError("merkle_forest_ragged: tree %d is empty" % int(np.argmax(lens == 0)))
+    return flat, off, lens
+
+
+def merkle_forest_ragged(trees, arity=4, tag=None, ctx=None, want_levels=False):
+    """roots of trees of DIFFERENT sizes in one call (p252_merkle{4,2}_forest_ragged): each root is what merkle4_tree (arity 2:
+    Context.merkle2_tree) returns for that tree alone, and every level is one kernel launch across all trees.  trees: a list of
+    (n_t, 4) uint64 leaf arrays, or (flat, offsets) with tree t = flat[offsets[t]:offsets[t+1]].  Returns roots (n_trees, 4)
+    uint64; with want_levels also (levels, level_offsets): levels tree-major — tree t's block, at level_offsets[t], is byte for
+    byte what the single-tree call writes (unlike merkle4_forest's level-major layout) — and level_offsets the n_trees + 1
+    prefix sums of levels_len(n_t, arity)."""
+    if arity not in (2, 4):
+        raise ValueError("merkle_forest_ragged: arity must be 4 or 2, not %r" % (arity,))
+    flat, off, lens = _forest_trees(trees)
+    level_offsets = np.zeros(lens.shape[0] + 1, dtype=np.uint64)
+    np.cumsum([levels_len(int(n), arity) for n in lens], out=level_offsets[1:])
+    if tag is None:
+        tag = merkle4_tag() if arity == 4 else merkle2_tag()
+    tag = _as_scalars(tag).reshape(4)
+    if lens.shape[0] == 0:
+        roots = np.zeros((0, 4), dtype=np.uint64)
+        return (roots, np.zeros((0, 4), dtype=np.uint64), level_offsets) if want_levels else roots
+    ctx = ctx or Context.default()
+    res = ctx.merkle_forest_ragged(tag, flat, off, arity=arity, want_levels=want_levels)
+    return (res[0], res[1], level_offsets) if want_levels else res
 
 
 def merkle4_openings(leaves, levels, indices):
