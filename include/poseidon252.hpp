@@ -15,6 +15,8 @@
 //   —                                               HashBatch: n messages, one kernel launch
 //   Hash::digest over messages of any lengths       RaggedHashBatch: n messages of different lengths, one call
 //   —                                               merkle_forest_ragged: trees of different sizes, one call
+//   —                                               merkle_forest_ragged_openings_device / merkle_path_ragged_device /
+//                                                   merkle_forest_ragged_verify_device: openings out of such a forest
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -462,6 +464,51 @@ inline void merkle_forest_ragged_device(const void* d_leaves, std::size_t n_leav
     auto fn = arity == 4 ? p252_merkle4_forest_ragged_device : p252_merkle2_forest_ragged_device;
     detail::check(fn(ctx.get(), tag.data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels, d_n_bad, stream), ctx.get(),
                   "merkle_forest_ragged_device");
+}
+
+// Openings out of such a forest in one call (p252_merkle{4,2}_forest_ragged_openings_device): opening i = leaf d_leaf_ids[i] (uint64)
+// of tree d_tree_ids[i] (uint32); the forest arguments exactly as the build took them (d_levels required unless every tree is a
+// single leaf).  Outputs at the stride D = forest_openings_stride(max_leaves, arity): d_leaves_out[k], d_siblings[k][D][arity - 1],
+// d_positions[k][D], d_depths[k] (uint8; 0xFF = a bad opening, all zero, counted in *d_n_bad).
+inline std::size_t forest_openings_stride(std::size_t max_leaves, unsigned arity = 4) {
+    return arity == 4 ? p252_merkle4_depth(max_leaves) : p252_merkle2_depth(max_leaves);
+}
+inline void merkle_forest_ragged_openings_device(const void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
+                                                 std::size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                 const void* d_leaf_ids, std::size_t k, void* d_leaves_out, void* d_siblings,
+                                                 void* d_positions, void* d_depths, unsigned arity = 4,
+                                                 Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_openings_device: arity must be 4 or 2");
+    auto fn = arity == 4 ? p252_merkle4_forest_ragged_openings_device : p252_merkle2_forest_ragged_openings_device;
+    detail::check(fn(ctx.get(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out,
+                     d_siblings, d_positions, d_depths, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_openings_device");
+}
+
+// The re-hash with a depth per opening (p252_merkle{4,2}_path_ragged_device): d_roots_out[i] from the first d_depths[i] levels of
+// opening i in the layout above; a depth above stride_depth (0xFF included) gives a zero root and is counted in *d_n_bad.
+inline void merkle_path_ragged_device(const void* d_leaves, const void* d_siblings, const void* d_positions, const void* d_depths,
+                                      std::size_t stride_depth, void* d_roots_out, std::size_t k, unsigned arity = 4,
+                                      Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_path_ragged_device: arity must be 4 or 2");
+    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
+    auto fn = arity == 4 ? p252_merkle4_path_ragged_device : p252_merkle2_path_ragged_device;
+    detail::check(fn(ctx.get(), tag.data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_roots_out, k, d_n_bad, stream),
+                  ctx.get(), "merkle_path_ragged_device");
+}
+
+// `Opening::verify` across a forest (p252_merkle{4,2}_forest_ragged_verify_device): d_ok[i] = 1 iff opening i is well-formed and
+// re-hashes to d_roots[d_tree_ids[i]], the root of ITS tree.
+inline void merkle_forest_ragged_verify_device(const void* d_leaves, const void* d_siblings, const void* d_positions, const void* d_depths,
+                                               std::size_t stride_depth, const void* d_tree_ids, const void* d_roots, std::size_t n_trees,
+                                               void* d_ok, std::size_t k, unsigned arity = 4, Context& ctx = Context::default_context(),
+                                               void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_verify_device: arity must be 4 or 2");
+    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
+    auto fn = arity == 4 ? p252_merkle4_forest_ragged_verify_device : p252_merkle2_forest_ragged_verify_device;
+    detail::check(fn(ctx.get(), tag.data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots, n_trees, d_ok, k,
+                     stream),
+                  ctx.get(), "merkle_forest_ragged_verify_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

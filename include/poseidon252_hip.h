@@ -87,7 +87,9 @@ extern "C" {
  *      P252_ERR_COMM — they used to return a garbage root as P252_OK), p252_trim (gives the grow-only scratch back);
  *      p252_scratch_residue no longer counts the encryption call table (it holds nothing of the caller's)
  *   9  + p252_hash_ragged[_truncated][_device]: n messages of different lengths in one call;
- *      + p252_merkle{4,2}_forest_ragged[_device] (additive, same version): trees of different sizes in one call */
+ *      + p252_merkle{4,2}_forest_ragged[_device] (additive, same version): trees of different sizes in one call;
+ *      + p252_merkle{4,2}_forest_ragged_openings_device, p252_merkle{4,2}_path_ragged_device,
+ *      p252_merkle{4,2}_forest_ragged_verify_device (additive, same version): openings out of such a forest in one call */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -376,6 +378,49 @@ int p252_merkle4_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint6
                                size_t n_trees, uint64_t* roots, uint64_t* levels);
 int p252_merkle2_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets,
                                size_t n_trees, uint64_t* roots, uint64_t* levels);
+
+/* Openings out of such a forest in one call (no hashing).  d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels: exactly
+ * what p252_merkle{4,2}_forest_ragged_device was given (d_levels, tree-major, is required unless every tree is a single leaf; all
+ * three sizes > 0).  The call recomputes the per-tree leaf counts and block starts with the build's own validation and scan, so a
+ * bad tree means the same in both and nothing is needed from the host.  Opening i = leaf d_leaf_ids[i] (uint64, a position inside
+ * the tree) of tree d_tree_ids[i] (uint32); k of each, device.  Every output uses the stride D = p252_merkle4_depth(max_leaves):
+ * d_leaves_out[k], d_siblings[k][D][3], d_positions[k][D], d_depths[k] (uint8) = p252_merkle4_depth(n_t).  Rows l < d_depths[i] of
+ * opening i are byte for byte what p252_merkle4_openings_device writes for that tree's block alone; rows at or past it are zero.
+ * A bad opening (tree id >= n_trees, a bad tree, leaf id >= n_t) is all zero with d_depths[i] = 0xFF — the re-hash and verify calls
+ * below refuse that depth, so a zero leaf never "verifies" against a bad tree's zero root — and is counted once in *d_n_bad (device
+ * uint32 the caller has zeroed; may be NULL).  D == 0 copies the leaves.  k == 0 -> P252_OK, nothing enqueued.  The forest's index
+ * and one 32-byte record per opening live in the context's scratch of THIS stream.  Asynchronous, no host synchronisation, no
+ * allocation once that scratch is warm. */
+int p252_merkle4_forest_ragged_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                               size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                               size_t k, void* d_leaves_out, void* d_siblings, void* d_positions, void* d_depths,
+                                               void* d_n_bad, void* hip_stream);
+/* arity 2: d_siblings[k][D] with D = p252_merkle2_depth(max_leaves), positions in 0..1 */
+int p252_merkle2_forest_ragged_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                               size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                               size_t k, void* d_leaves_out, void* d_siblings, void* d_positions, void* d_depths,
+                                               void* d_n_bad, void* hip_stream);
+/* The re-hash with a depth per opening: d_roots_out[i] = the root recomputed from the first d_depths[i] levels of opening i (the
+ * layout above at stride_depth <= 64; the rows past the depth are not read).  d_depths[i] == 0 copies the leaf; d_depths[i] >
+ * stride_depth (the 0xFF of a bad opening included) writes a zero root and is counted in *d_n_bad (zeroed by the caller; may be
+ * NULL).  With d_depths[i] == stride_depth everywhere the roots are those of p252_merkle{4,2}_path_batch_device.  The openings are
+ * sorted by depth on the device first (a wave runs to its deepest lane; P252_RAGGED_SORT=0 turns that off); the order lives in the
+ * context's scratch of this stream.  Asynchronous. */
+int p252_merkle4_path_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                    const void* d_positions, const void* d_depths, size_t stride_depth, void* d_roots_out, size_t k,
+                                    void* d_n_bad, void* hip_stream);
+int p252_merkle2_path_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                    const void* d_positions, const void* d_depths, size_t stride_depth, void* d_roots_out, size_t k,
+                                    void* d_n_bad, void* hip_stream);
+/* Opening::verify across a forest: d_ok[i] = 1 iff d_depths[i] <= stride_depth, d_tree_ids[i] < n_trees and opening i re-hashes to
+ * d_roots[d_tree_ids[i]] (the n_trees roots of the build, device) — k bytes leave the device.  The recomputed roots live in the
+ * context's scratch of this stream, as in p252_merkle{4,2}_verify_batch_device.  Asynchronous. */
+int p252_merkle4_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                             const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
+                                             const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream);
+int p252_merkle2_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                             const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
+                                             const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

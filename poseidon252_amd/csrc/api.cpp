@@ -14,6 +14,7 @@
 #include "../../include/poseidon252_hip.h"
 #include "blake2b.hpp"
 #include "ctx.hpp"
+#include "forest_openings.h"
 #include "forest_ragged.h"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -596,6 +597,170 @@ int p252_merkle4_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], cons
 int p252_merkle2_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, const void* d_offsets,
                                       size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels, void* d_n_bad, void* hip_stream) {
     return forest_ragged_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels, d_n_bad, hip_stream);
+}
+
+// ---- openings out of such a forest, their re-hash with a depth per opening, and a root per opening (forest_openings.hip).  The
+// scratch — the forest's index and the opening records; the sort's order and counters; the recomputed roots — is the pair of the
+// calling stream, as for the build ----
+static size_t ceil_depth(size_t n, size_t arity) {  // p252_merkle{4,2}_depth without the overflow at the top of size_t
+    size_t d = 0;
+    for (size_t c = n; c > 1; c = c / arity + (c % arity != 0)) ++d;
+    return d;
+}
+
+static int finish_guarded(p252_ctx* ctx, LevelSetGuard& guard, int rc) {
+    const std::string msg = ctx->err;
+    const int rc2 = guard.finish();
+    if (rc) ctx->err = msg;
+    return rc ? rc : rc2;
+}
+
+static int forest_ragged_openings_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                         size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                         const void* d_leaf_ids, size_t k, void* d_leaves_out, void* d_siblings, void* d_positions,
+                                         void* d_depths, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (k == 0) return P252_OK;
+    const char* who = "merkle_forest_ragged_openings";
+    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
+    const size_t depth = ceil_depth(max_leaves, arity);
+    if (!d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_leaves_out || !d_depths ||
+        (depth && (!d_levels || !d_siblings || !d_positions)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_siblings))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_leaf_ids) & 7u))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets and d_leaf_ids must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_tree_ids) & 3u) || (reinterpret_cast<uintptr_t>(d_n_bad) & 3u))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
+    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;  // (the build's own limits)
+    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) || n_trees > (SIZE_MAX / 2) / eff_max ||
+        k > SIZE_MAX / 128 / (depth ? depth : 1))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t index_bytes = forest_ragged_index_bytes(n_trees);
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    int rc = level_set(ctx, st, index_bytes + forest_openings_record_bytes(k), 0, &set);
+    if (rc) return rc;
+    char* meta = static_cast<char*>(set->buf[0]);
+    const uint64_t *ntree = nullptr, *lo = nullptr;
+    hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
+    if (e == hipSuccess)
+        e = launch_forest_openings(arity, d_leaves, d_levels, d_offsets, ntree, lo, n_trees, d_tree_ids, d_leaf_ids, k, (unsigned)depth,
+                                   meta + index_bytes, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return finish_guarded(ctx, guard, rc);
+}
+
+// the argument checks of the re-hash (shared with the verify call)
+static int path_ragged_check(p252_ctx* ctx, const char* who, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                             const void* d_positions, const void* d_depths, size_t stride_depth, size_t k) {
+    if (stride_depth > FOREST_OPENINGS_MAX_DEPTH) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": stride_depth must be <= 64");
+    if (!tag || !d_leaves_in || !d_depths || (stride_depth && (!d_siblings || !d_positions)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_leaves_in) || (stride_depth && misaligned(d_siblings))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (k > SIZE_MAX / 128 / (stride_depth ? stride_depth : 1)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    return P252_OK;
+}
+
+static int path_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                              const void* d_positions, const void* d_depths, size_t stride_depth, void* d_roots_out, size_t k,
+                              void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (k == 0) return P252_OK;
+    const char* who = "merkle_path_ragged";
+    int rc = path_ragged_check(ctx, who, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, k);
+    if (rc) return rc;
+    if (!d_roots_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_roots_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_n_bad must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!ragged_sort_enabled()) {  // P252_RAGGED_SORT=0: identity order, no scratch
+        HIP_TRY(ctx, launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths, (unsigned)stride_depth,
+                                        d_roots_out, k, d_n_bad, nullptr, nullptr, st));
+        return P252_OK;
+    }
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    rc = level_set(ctx, st, forest_openings_order_bytes(k), forest_openings_hist_bytes(), &set);
+    if (rc) return rc;
+    const hipError_t e = launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths,
+                                            (unsigned)stride_depth, d_roots_out, k, d_n_bad, set->buf[0], set->buf[1], st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return finish_guarded(ctx, guard, rc);
+}
+
+static int forest_ragged_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                       const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
+                                       const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (k == 0) return P252_OK;
+    const char* who = "merkle_forest_ragged_verify";
+    int rc = path_ragged_check(ctx, who, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, k);
+    if (rc) return rc;
+    if (!d_tree_ids || !d_ok || (n_trees && !d_roots)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_roots)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if ((reinterpret_cast<uintptr_t>(d_tree_ids) & 3u) != 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const bool sort = ragged_sort_enabled();
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;  // the recomputed roots (k x 32 bytes), then the sort's order; the counters in the second buffer
+    rc = level_set(ctx, st, k * 32 + (sort ? forest_openings_order_bytes(k) : 0), sort ? forest_openings_hist_bytes() : 0, &set);
+    if (rc) return rc;
+    char* roots = static_cast<char*>(set->buf[0]);
+    hipError_t e = launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths, (unsigned)stride_depth,
+                                      roots, k, nullptr, sort ? roots + k * 32 : nullptr, sort ? set->buf[1] : nullptr, st);
+    if (e == hipSuccess) e = launch_compare_roots_gather(roots, d_depths, (unsigned)stride_depth, d_tree_ids, d_roots, n_trees, d_ok, k, st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return finish_guarded(ctx, guard, rc);
+}
+
+int p252_merkle4_forest_ragged_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                               size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                               size_t k, void* d_leaves_out, void* d_siblings, void* d_positions, void* d_depths,
+                                               void* d_n_bad, void* hip_stream) {
+    return forest_ragged_openings_device(ctx, 4, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                         d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                               size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                               size_t k, void* d_leaves_out, void* d_siblings, void* d_positions, void* d_depths,
+                                               void* d_n_bad, void* hip_stream) {
+    return forest_ragged_openings_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                         d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, hip_stream);
+}
+
+int p252_merkle4_path_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                    const void* d_positions, const void* d_depths, size_t stride_depth, void* d_roots_out, size_t k,
+                                    void* d_n_bad, void* hip_stream) {
+    return path_ragged_device(ctx, 4, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, d_roots_out, k, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_path_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                    const void* d_positions, const void* d_depths, size_t stride_depth, void* d_roots_out, size_t k,
+                                    void* d_n_bad, void* hip_stream) {
+    return path_ragged_device(ctx, 2, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, d_roots_out, k, d_n_bad, hip_stream);
+}
+
+int p252_merkle4_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                             const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
+                                             const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream) {
+    return forest_ragged_verify_device(ctx, 4, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots, n_trees,
+                                       d_ok, k, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
+                                             const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
+                                             const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream) {
+    return forest_ragged_verify_device(ctx, 2, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots, n_trees,
+                                       d_ok, k, hip_stream);
 }
 
 // (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)

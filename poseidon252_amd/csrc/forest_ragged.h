@@ -37,4 +37,11 @@ hipError_t launch_forest_ragged(const int32_t* tab, const TagArg& tag, const For
                                 const void* offsets, size_t max_leaves, void* roots, void* levels, void* n_bad, void* meta,
                                 void* lvl_a, void* lvl_b, hipStream_t st);
 
+// The forest's index alone, for calls that READ a built forest (forest_openings.hip): the build's own validation and scans into
+// `meta` (forest_ragged_index_bytes(n_trees) of scratch) — *ntree = the n_trees leaf counts (0: a bad tree), *lo = the n_trees + 1
+// block starts of the tree-major levels.  No root is written and nothing is counted.
+size_t forest_ragged_index_bytes(size_t n_trees);
+hipError_t launch_forest_ragged_index(unsigned arity, const void* offsets, size_t n_trees, size_t n_leaves, size_t max_leaves, void* meta,
+                                      const uint64_t** ntree, const uint64_t** lo, hipStream_t st);
+
 }  // namespace p252

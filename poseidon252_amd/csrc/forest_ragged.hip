@@ -164,7 +164,8 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_apply(uint64_t* __restrict
                 n = 0;
                 ntree[t] = 0;
             }
-            if (n == 0) {
+            if (!roots) {  // (the index alone: launch_forest_ragged_index)
+            } else if (n == 0) {
                 store_zero(roots + t);
                 if (n_bad) atomicAdd(n_bad, 1u);
             } else if (n == 1) {
@@ -340,6 +341,37 @@ ForestRaggedPlan forest_ragged_plan(unsigned arity, size_t n_leaves, size_t n_tr
     }
     p.meta_bytes = (words * 8 + 255) & ~(size_t)255;
     return p;
+}
+
+// the forest's index alone, for callers that read a built forest (forest_openings.hip): the validation and the leaf-count scan of
+// the build (no roots written, nothing counted), then LO = the scan of levels_len(n_t)
+size_t forest_ragged_index_bytes(size_t n_trees) {
+    const size_t tiles = (n_trees + FR_TILE - 1) / FR_TILE;
+    return ((2 * n_trees + 1 + tiles) * 8 + 255) & ~(size_t)255;
+}
+
+hipError_t launch_forest_ragged_index(unsigned arity, const void* offsets, size_t n_trees, size_t n_leaves, size_t max_leaves, void* meta,
+                                      const uint64_t** ntree_out, const uint64_t** lo_out, hipStream_t st) {
+    const size_t n = n_trees;
+    const unsigned tiles = (unsigned)((n + FR_TILE - 1) / FR_TILE), la = arity == 4 ? 2 : 1;
+    const uint64_t* off = static_cast<const uint64_t*>(offsets);
+    uint64_t* ntree = static_cast<uint64_t*>(meta);
+    uint64_t* LO = ntree + n;  // row 0 of C: n + 1 entries
+    uint64_t* tsum = LO + n + 1;
+    const dim3 blk(FR_BLOCK);
+    *ntree_out = ntree;
+    *lo_out = LO;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)n_leaves, (uint64_t)max_leaves, ntree);
+    hipLaunchKernelGGL(k_fr_tile_sums, dim3(tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, (size_t)tiles);
+    hipLaunchKernelGGL(k_fr_scan_apply<true>, dim3(tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum, LO, (uint64_t)n_leaves, off,
+                       (const Scalar32*)nullptr, (Scalar32*)nullptr, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k_fr_tile_sums, dim3(tiles, 1), blk, 0, st, ntree, n, 0u, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, (size_t)tiles);
+    hipLaunchKernelGGL(k_fr_scan_apply<false>, dim3(tiles, 1), blk, 0, st, ntree, n, 0u, la, tsum, LO, (uint64_t)n_leaves, off,
+                       (const Scalar32*)nullptr, (Scalar32*)nullptr, (unsigned*)nullptr);
+    return hipGetLastError();
 }
 
 hipError_t launch_forest_ragged(const int32_t* tab, const TagArg& tag, const ForestRaggedPlan& p, const void* leaves,

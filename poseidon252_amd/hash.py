@@ -364,6 +364,74 @@ class Context:
                        _dev_ptr(self, f, "d_levels", d_levels, need, null_ok=True),
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
+    def merkle_forest_ragged_openings_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                             out=None, d_n_bad=None, arity=4):
+        """openings out of a forest merkle_forest_ragged_device built with d_levels (p252_merkle{4,2}_forest_ragged_openings_device):
+        opening i = leaf d_leaf_ids[i] (int64/uint64, a position inside the tree) of tree d_tree_ids[i] (int32/uint32); d_leaves,
+        d_offsets, n_trees, max_leaves, d_levels exactly as the build took them.  Returns (d_leaves_out (k,4), d_siblings
+        (k,D,arity-1,4), d_positions (k,D) uint8, d_depths (k,) uint8, D) with D = depth(max_leaves); rows at or past d_depths[i]
+        are zero, a bad opening is all zero with depth 0xFF and counted in d_n_bad (a zeroed device int32/uint32, optional).
+        out = (d_leaves_out, d_siblings, d_positions, d_depths) writes into caller-owned tensors (no allocation per call)."""
+        import torch
+        f = "merkle_forest_ragged_openings_device"
+        if arity not in (2, 4):
+            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+        L = _lib.lib()
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = d_leaves.numel() * d_leaves.element_size() // 32
+        depth = int((L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(max_leaves))
+        offsets = _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8)
+        levels = _dev_ptr(self, f, "d_levels", d_levels, (n_leaves // (arity - 1) + n_trees * depth) * 32, null_ok=depth == 0)
+        tree_ids = _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4)
+        leaf_ids = _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8)
+        if out is not None:
+            lv, sib, pos, dep = out
+        else:
+            dev = d_leaves.device
+            lv = torch.empty((k, 4), dtype=torch.int64, device=dev)
+            sib = torch.empty((k, depth, arity - 1, 4), dtype=torch.int64, device=dev)
+            pos = torch.empty((k, depth), dtype=torch.uint8, device=dev)
+            dep = torch.empty((k,), dtype=torch.uint8, device=dev)
+        fn = L.p252_merkle4_forest_ragged_openings_device if arity == 4 else L.p252_merkle2_forest_ragged_openings_device
+        self._check(fn(self._h, leaves, n_leaves, offsets, n_trees, max_leaves, levels, tree_ids, leaf_ids, k,
+                       _dev_ptr(self, f, "d_leaves_out", lv, k * 32),
+                       _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * (arity - 1)) if depth else None,
+                       _dev_ptr(self, f, "d_positions", pos, k * depth, elem=1) if depth else None,
+                       _dev_ptr(self, f, "d_depths", dep, k, elem=1), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+                       _stream(self)))
+        return lv, sib, pos, dep, depth
+
+    def _ragged_opening_ptrs(self, f, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, arity):
+        if arity not in (2, 4):
+            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+        if not 0 <= stride_depth <= 64:
+            raise ValueError("%s: stride_depth must be in 0 .. 64, not %r" % (f, stride_depth))
+        return (_dev_ptr(self, f, "d_leaves", d_leaves, k * 32),
+                _dev_ptr(self, f, "d_siblings", d_siblings, k * stride_depth * (arity - 1) * 32) if stride_depth else None,
+                _dev_ptr(self, f, "d_positions", d_positions, k * stride_depth, elem=1) if stride_depth else None,
+                _dev_ptr(self, f, "d_depths", d_depths, k, elem=1))
+
+    def merkle_path_ragged_device(self, tag, d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_roots, k, d_n_bad=None, arity=4):
+        """re-hash of k openings of DIFFERENT depths (p252_merkle{4,2}_path_ragged_device): d_roots[i] from the first d_depths[i]
+        (uint8) levels of opening i in the layout merkle_forest_ragged_openings_device writes, at stride stride_depth.  A depth
+        above the stride (0xFF: a bad opening) gives a zero root and is counted in d_n_bad (zeroed device int32/uint32, optional)."""
+        f = "merkle_path_ragged_device"
+        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, arity)
+        fn = _lib.lib().p252_merkle4_path_ragged_device if arity == 4 else _lib.lib().p252_merkle2_path_ragged_device
+        self._check(fn(self._h, _tag(tag), leaves, sib, pos, dep, stride_depth, _dev_ptr(self, f, "d_roots", d_roots, k * 32), k,
+                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
+    def merkle_forest_ragged_verify_device(self, tag, d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots,
+                                           n_trees, d_ok, k, arity=4):
+        """`Opening::verify` across a forest (p252_merkle{4,2}_forest_ragged_verify_device): d_ok[i] (uint8) = 1 iff opening i is
+        well-formed and re-hashes to d_roots[d_tree_ids[i]], the root of ITS tree; k bytes come back"""
+        f = "merkle_forest_ragged_verify_device"
+        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, arity)
+        fn = _lib.lib().p252_merkle4_forest_ragged_verify_device if arity == 4 else _lib.lib().p252_merkle2_forest_ragged_verify_device
+        self._check(fn(self._h, _tag(tag), leaves, sib, pos, dep, stride_depth, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
+                       _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=n_trees == 0), n_trees,
+                       _dev_ptr(self, f, "d_ok", d_ok, k, elem=1), k, _stream(self)))
+
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
         f = "truncate250_device"
