@@ -17,6 +17,7 @@
 //   —                                               merkle_forest_ragged: trees of different sizes, one call
 //   —                                               merkle_forest_ragged_openings_device / merkle_path_ragged_device /
 //                                                   merkle_forest_ragged_verify_device: openings out of such a forest
+//   —                                               merkle_forest_ragged_update_device: leaf updates anywhere in such a forest
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -509,6 +510,23 @@ inline void merkle_forest_ragged_verify_device(const void* d_leaves, const void*
     detail::check(fn(ctx.get(), tag.data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots, n_trees, d_ok, k,
                      stream),
                   ctx.get(), "merkle_forest_ragged_verify_device");
+}
+
+// Leaf updates anywhere in such a forest in one call (p252_merkle{4,2}_forest_ragged_update_device): update i writes d_new_leaves[i]
+// to leaf d_leaf_ids[i] (uint64) of tree d_tree_ids[i] (uint32) and every dirty ancestor is re-hashed once, in place; the forest
+// arguments exactly as the build took them.  d_roots[t] is rewritten for the trees that were touched; a bad update writes nothing
+// and is counted in *d_n_bad; *d_n_hashed (device uint64, zeroed by the caller) grows by the number of digests computed.
+inline void merkle_forest_ragged_update_device(void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
+                                               std::size_t max_leaves, void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                               const void* d_new_leaves, std::size_t k, unsigned arity = 4,
+                                               Context& ctx = Context::default_context(), void* d_roots = nullptr, void* d_n_bad = nullptr,
+                                               void* d_n_hashed = nullptr, void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_update_device: arity must be 4 or 2");
+    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
+    auto fn = arity == 4 ? p252_merkle4_forest_ragged_update_device : p252_merkle2_forest_ragged_update_device;
+    detail::check(fn(ctx.get(), tag.data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves,
+                     k, d_roots, d_n_bad, d_n_hashed, stream),
+                  ctx.get(), "merkle_forest_ragged_update_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

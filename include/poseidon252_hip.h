@@ -89,7 +89,9 @@ extern "C" {
  *   9  + p252_hash_ragged[_truncated][_device]: n messages of different lengths in one call;
  *      + p252_merkle{4,2}_forest_ragged[_device] (additive, same version): trees of different sizes in one call;
  *      + p252_merkle{4,2}_forest_ragged_openings_device, p252_merkle{4,2}_path_ragged_device,
- *      p252_merkle{4,2}_forest_ragged_verify_device (additive, same version): openings out of such a forest in one call */
+ *      p252_merkle{4,2}_forest_ragged_verify_device (additive, same version): openings out of such a forest in one call;
+ *      + p252_merkle{4,2}_forest_ragged_update_device (additive, same version): leaf updates anywhere in such a forest in one
+ *      call, each dirty node hashed once */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -353,7 +355,8 @@ int p252_merkle2_forest_device(p252_ctx* ctx, const uint64_t tag[4], const void*
  * d_levels (device, may be NULL = roots only) is TREE-MAJOR, unlike the level-major layout of p252_merkle4_forest_device: tree t's
  * block starts at LO[t] = the sum over good trees s < t of p252_merkle4_levels_len(n_s) and holds byte for byte what
  * p252_merkle4_tree writes for it alone — so a tree's block goes unchanged into p252_merkle4_openings_device, the verify calls and
- * p252_merkle4_update_device.  A caller with device-only offsets can size d_levels as
+ * p252_merkle4_update_device (one tree per call; p252_merkle{4,2}_forest_ragged_update_device below updates leaves of any number
+ * of trees in one).  A caller with device-only offsets can size d_levels as
  * n_leaves / 3 + n_trees * p252_merkle4_depth(max_leaves) scalars.
  * A tree is bad when n_t == 0, n_t > max_leaves, its offsets decrease, offsets[t+1] > n_leaves, or n_t plus the leaf counts of the
  * trees before it that pass those checks exceed n_leaves (only possible when trees overlap behind decreasing offsets): its root is
@@ -421,6 +424,40 @@ int p252_merkle4_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4
 int p252_merkle2_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
                                              const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
                                              const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream);
+
+/* Leaf updates anywhere in such a forest in one call.  d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels: exactly what
+ * p252_merkle{4,2}_forest_ragged_device was given (d_levels, tree-major, is required unless every tree is a single leaf; all three
+ * sizes > 0); the per-tree leaf counts and block starts are recomputed with the build's own validation and scans, as the openings
+ * call does, so a bad tree means the same in all three and nothing is needed from the host.  Update i writes d_new_leaves[i] (one
+ * scalar) to leaf d_leaf_ids[i] (uint64, a position inside the tree) of tree d_tree_ids[i] (uint32); k of each, device.  Then every
+ * ancestor of a changed leaf is re-hashed, level by level, in place in its tree's block — each dirty node ONCE, however many
+ * updates lie below it (p252_merkle4_update_device hashes k nodes on every level).  Afterwards d_leaves and the used part of
+ * d_levels are byte for byte what a fresh p252_merkle{4,2}_forest_ragged_device build of the modified leaves writes; nothing
+ * outside the touched trees' blocks and nothing past the used length of d_levels is written.  d_roots (device, n_trees scalars,
+ * may be NULL): entry t is rewritten for every tree that received a valid update (a single-leaf tree's root is its leaf), the
+ * other entries are left alone.  A bad update (tree id >= n_trees, a bad tree, leaf id >= n_t) writes nothing and is counted once
+ * in *d_n_bad (device uint32 the caller has zeroed; may be NULL).  The (tree, leaf) pairs must be distinct, with the contract of
+ * p252_merkle4_update_device: the same pair twice with the same value is harmless; with different values one of them (or a mix of
+ * their 16-byte halves) lands and the levels are consistent with whatever was stored.  *d_n_hashed (device uint64 the caller has
+ * zeroed, 8-byte aligned; may be NULL) is incremented by the number of node digests computed = the number of DISTINCT dirty
+ * ancestors.  k == 0 -> P252_OK, nothing enqueued.  Scratch, in the context's pair of THIS stream (p252_trim / p252_wipe cover
+ * it): the forest's index (16 bytes per tree) and ids only, never a copy of the new leaves — two 16-byte records and at most
+ * 32 bytes of claim table per update, i.e. at most 64 bytes per update plus 1 KiB, whatever the size of the forest.
+ * Asynchronous on hip_stream: no host synchronisation, no allocation once that scratch is warm — it can be captured into a
+ * hipGraph (it holds memset nodes).  Cost: three graph nodes per level, so for a handful of updates of ONE tree
+ * p252_merkle4_update_device (one launch per level) is quicker; measured on one 4^12-leaf tree (profiles/forest_update.txt) this
+ * call wins from about 2^16 updates (1.1x; 4.2x at 2^20), and above ~N/4 changed leaves of a tree of N, rebuild: a fresh build is
+ * then as quick (1.07x at N/4) or quicker (the update takes 1.4x the build's time at k = N).  There is no host-buffer twin: the
+ * call acts on a forest that lives on the device. */
+int p252_merkle4_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                             size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
+                                             const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
+                                             void* d_n_hashed, void* hip_stream);
+/* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag) */
+int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                             size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
+                                             const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
+                                             void* d_n_hashed, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

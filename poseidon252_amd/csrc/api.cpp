@@ -16,6 +16,7 @@
 #include "ctx.hpp"
 #include "forest_openings.h"
 #include "forest_ragged.h"
+#include "forest_update.h"
 #include "hades29.hpp"
 #include "kernels.h"
 #include "openings.h"
@@ -761,6 +762,66 @@ int p252_merkle2_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4
                                              const void* d_roots, size_t n_trees, void* d_ok, size_t k, void* hip_stream) {
     return forest_ragged_verify_device(ctx, 2, tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots, n_trees,
                                        d_ok, k, hip_stream);
+}
+
+// ---- leaf updates anywhere in such a forest in one call, every dirty node hashed once (forest_update.hip).  The scratch — the
+// forest's index, two lists of node ids and the per-level counters; the claim table in the second buffer — is the pair of the
+// calling stream; it holds ids only, never a copy of the new leaves ----
+static int forest_ragged_update_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                       const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
+                                       const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
+                                       void* d_n_hashed, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (k == 0) return P252_OK;
+    const char* who = "merkle_forest_ragged_update";
+    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
+    const size_t depth = ceil_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
+    if (!tag || !d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_new_leaves || (depth && !d_levels))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_new_leaves) || misaligned(d_roots))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_leaf_ids) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_n_hashed) & 7u))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets, d_leaf_ids and d_n_hashed must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_tree_ids) & 3u) || (reinterpret_cast<uintptr_t>(d_n_bad) & 3u))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
+    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;  // (the build's own limits)
+    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) || n_trees > (SIZE_MAX / 2) / eff_max ||
+        k > SIZE_MAX / 128)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t index_bytes = forest_ragged_index_bytes(n_trees);
+    const ForestUpdatePlan plan = forest_update_plan(arity, n_leaves, n_trees, max_leaves, k);
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    int rc = level_set(ctx, st, index_bytes + plan.ids_bytes(), plan.table_bytes, &set);
+    if (rc) return rc;
+    char* meta = static_cast<char*>(set->buf[0]);
+    const uint64_t *ntree = nullptr, *lo = nullptr;
+    hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
+    if (e == hipSuccess)
+        e = launch_forest_update(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids,
+                                 d_new_leaves, d_roots, d_n_bad, d_n_hashed, meta + index_bytes, set->buf[1], st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return finish_guarded(ctx, guard, rc);
+}
+
+int p252_merkle4_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                             size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
+                                             const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
+                                             void* d_n_hashed, void* hip_stream) {
+    return forest_ragged_update_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                             size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
+                                             const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
+                                             void* d_n_hashed, void* hip_stream) {
+    return forest_ragged_update_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, hip_stream);
 }
 
 // (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)

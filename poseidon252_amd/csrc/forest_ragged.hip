@@ -41,33 +41,6 @@ constexpr unsigned FR_ITEMS = 8;  // trees per thread of a scan block
 constexpr unsigned FR_TILE = FR_BLOCK * FR_ITEMS;
 constexpr unsigned FR_ROW_LEAVES = 0xffffffffu;  // scan row of the leaf counts n_t themselves
 
-// ceil(n / 2^k) for any k
-__device__ __forceinline__ uint64_t ceil_shift(uint64_t n, unsigned k) {
-    if (k >= 64) return n != 0;
-    return (n >> k) + ((n & ((1ull << k) - 1)) != 0);
-}
-// nodes of level l >= 1 of a tree of n leaves (0: the tree ended below l)
-__device__ __forceinline__ uint64_t level_nodes(uint64_t n, unsigned l, unsigned la) {
-    return ceil_shift(n, (l - 1) * la) > 1 ? ceil_shift(n, l * la) : 0;
-}
-// p252_merkle{4,2}_levels_len(n)
-__device__ __forceinline__ uint64_t levels_len_dev(uint64_t n, unsigned la) {
-    uint64_t total = 0;
-#pragma unroll 1
-    for (uint64_t c = n; c > 1;) {
-        c = ceil_shift(c, la);
-        total += c;
-    }
-    return total;
-}
-// start of level l >= 1 inside the levels block of a tree of n leaves (levels 1 .. l-1 before it)
-__device__ __forceinline__ uint64_t level_start(uint64_t n, unsigned l, unsigned la) {
-    uint64_t w = 0;
-#pragma unroll 1
-    for (unsigned j = 1; j < l; ++j) w += ceil_shift(n, j * la);
-    return w;
-}
-
 __device__ __forceinline__ uint64_t row_value(const uint64_t* __restrict__ ntree, size_t t, unsigned row, unsigned la) {
     const uint64_t n = ntree[t];
     if (row == FR_ROW_LEAVES) return n;

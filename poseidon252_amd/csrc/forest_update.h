@@ -1,0 +1,34 @@
+// forest_update.h — launch interface between api.cpp and forest_update.hip: k leaf updates (tree id, leaf id, new leaf) anywhere
+// in a built forest of trees of DIFFERENT sizes (p252_merkle{4,2}_forest_ragged_update_device), every dirty node hashed once.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "forest_ragged.h"
+#include "kernels.h"
+
+namespace p252 {
+
+// The host's view of one call, all derived from (n_leaves, n_trees, max_leaves, k).  Level l (1 .. depth) has at most
+// in[l] = min(k, bound[l]) dirty nodes (bound[l] = n_leaves / arity^l + n_trees: ForestRaggedPlan; in[0] = k, the updates
+// themselves).  The scratch holds ids only: two lists of k 16-byte records (tree id, node index), level l - 1's and level l's, one
+// uint64 counter per level, and the claim table of the widest level.
+struct ForestUpdatePlan {
+    unsigned arity = 4, log2a = 2, depth = 0;
+    size_t n_trees = 0, k = 0;
+    size_t in[FOREST_RAGGED_MAX_DEPTH + 1] = {};     // most records of level l's list
+    size_t slots[FOREST_RAGGED_MAX_DEPTH + 1] = {};  // claim-table slots of level l: a power of two >= 2 in[l - 1]
+    size_t list_bytes = 0, count_bytes = 0, table_bytes = 0;
+    size_t ids_bytes() const { return 2 * list_bytes + count_bytes; }  // beside the forest's index, in one buffer
+};
+ForestUpdatePlan forest_update_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
+
+// The whole update on `st`: ntree / lo = the forest's index (launch_forest_ragged_index); ids = plan.ids_bytes() and table =
+// plan.table_bytes of scratch.  roots, n_bad (uint32), n_hashed (uint64) may be null; levels may be null when plan.depth == 0.
+hipError_t launch_forest_update(const int32_t* tab, const TagArg& tag, const ForestUpdatePlan& plan, void* leaves, const void* offsets,
+                                const uint64_t* ntree, const uint64_t* lo, void* levels, const void* tree_ids, const void* leaf_ids,
+                                const void* new_leaves, void* roots, void* n_bad, void* n_hashed, void* ids, void* table, hipStream_t st);
+
+}  // namespace p252

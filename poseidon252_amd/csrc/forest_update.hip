@@ -1,0 +1,266 @@
+// forest_update.hip — k leaf updates (tree id, leaf id, new leaf) anywhere in a built forest of trees of DIFFERENT sizes
+// (forest_ragged.hip, tree-major levels) in one call, for both arities, every dirty node hashed ONCE.  k_merkle4_update
+// (kernels.hip) hashes k nodes on every level — at the root level all k lanes hash the same node; here each level's dirty nodes are
+// first made distinct, then hashed:
+//   k_fu_scatter   one lane per update: validated as k_fo_record validates an opening (tree id < n_trees, a good tree, leaf id <
+//                  n_t — one count in *n_bad otherwise, nothing written), the new leaf stored (two 16-byte stores), a 16-byte
+//                  record (tree id, valid, leaf id) written as list 0; a single-leaf tree's root is its leaf
+//   k_fu_claim     level l = 1 .. D, one lane per record of list l - 1: the parent (t, i >> log2 arity), keyed by its slot in d_levels
+//                  (LO[t] + level_start(n_t, l) + i, unique across the forest), is claimed in an open-addressing table with one
+//                  64-bit compare-and-swap (empty -> key, linear probing, at most half full).  The lane whose swap installs the
+//                  key appends the parent to list l (one atomic add per wave: ballot, popcount, the leader's base broadcast);
+//                  every other lane drops out, and so do the records of trees that ended below level l.
+//   k_fu_digest / k_fu_digest_coop   lane (group of 8 lanes) g < count[l] hashes record g of list l: children a i .. a i + a - 1 of
+//                  level l - 1 of the tree (its leaves for l = 1; zero at or past s_{l-1}(t)), output to level l of the tree's
+//                  block, and to d_roots[t] when the node is the tree's only one at that level.  The launch has min(k, bound[l])
+//                  lanes and leaves on the device-side count: the host never learns it.  Lane 0 adds the count to *n_hashed.
+// A level's digest launch reads level l - 1 and writes level l only, so updating in place is race-free across launch boundaries.
+// The permutation is the library's, as in k_fr_digest / k_fr_digest_coop: hades_permute<0x02u, true> with the hoisted tag S-box at
+// 3 waves per SIMD, hades_permute_coop<8> when the level cannot fill the chip (the coop8 rule of kernels.h on min(k, bound[l])).
+#include <hip/hip_runtime.h>
+
+#include "coop29.hpp"
+#include "forest_update.h"
+#include "hades29.hpp"
+#include "kernels.h"
+
+namespace p252 {
+
+namespace {
+
+constexpr unsigned FU_BLOCK = 256;
+constexpr unsigned long long FU_EMPTY = ~0ull;  // (the table is cleared to 0xFF bytes; no slot of d_levels has this number)
+constexpr size_t FU_MIN_SLOTS = 64;
+
+__device__ __forceinline__ uint64_t u64_of(unsigned lo, unsigned hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+__device__ __forceinline__ uint4 record(uint32_t t, uint64_t i) { return make_uint4(t, 1u, (unsigned)i, (unsigned)(i >> 32)); }
+
+}  // namespace
+
+// ---- the leaves, and list 0 ----
+__global__ void __launch_bounds__(FU_BLOCK) k_fu_scatter(const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ ntree,
+                                                         size_t n_trees, const uint32_t* __restrict__ tree_ids,
+                                                         const uint64_t* __restrict__ leaf_ids, const uint4* __restrict__ new_leaves,
+                                                         size_t k, uint4* __restrict__ leaves, uint4* __restrict__ roots,
+                                                         uint4* __restrict__ list, unsigned* __restrict__ n_bad) {
+    const size_t i = (size_t)blockIdx.x * FU_BLOCK + threadIdx.x;
+    if (i >= k) return;
+    const uint32_t t = tree_ids[i];
+    const uint64_t leaf = leaf_ids[i];
+    const bool known = t < n_trees;
+    const size_t ts = known ? t : 0;  // (n_trees >= 1: entry 0 exists)
+    const uint64_t n = known ? ntree[ts] : 0ull;
+    if (n == 0 || leaf >= n) {  // a bad update: nothing written, no record
+        list[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (n_bad) atomicAdd(n_bad, 1u);
+        return;
+    }
+    const uint4 lo = new_leaves[2 * i], hi = new_leaves[2 * i + 1];
+    const size_t at = 2 * (size_t)(offsets[ts] + leaf);  // (inside the tree: k_fr_prep checked offsets[t + 1] <= n_leaves)
+    leaves[at] = lo;
+    leaves[at + 1] = hi;
+    if (n == 1 && roots) {
+        roots[2 * ts] = lo;
+        roots[2 * ts + 1] = hi;
+    }
+    list[i] = record(t, leaf);
+}
+
+// ---- level l's distinct dirty nodes: list l - 1 -> list l ----
+__global__ void __launch_bounds__(FU_BLOCK) k_fu_claim(const uint4* __restrict__ in, const unsigned long long* __restrict__ in_count,
+                                                       size_t lanes, const uint64_t* __restrict__ ntree, const uint64_t* __restrict__ LO,
+                                                       unsigned l, unsigned la, unsigned long long* __restrict__ table, unsigned shift,
+                                                       uint4* __restrict__ out, unsigned long long* __restrict__ out_count) {
+    const size_t g = (size_t)blockIdx.x * FU_BLOCK + threadIdx.x;
+    // (no early return: the whole wave takes part in the append below)
+    bool live = g < lanes && (!in_count || g < *in_count);
+    const uint4 r = live ? in[g] : make_uint4(0u, 0u, 0u, 0u);
+    live = live && r.y != 0;
+    const uint32_t t = r.x;
+    const uint64_t n = live ? ntree[t] : 0ull;
+    live = live && ceil_shift(n, (l - 1) * la) > 1;  // level l - 1 has more than one node: the tree has a level l
+    const uint64_t parent = u64_of(r.z, r.w) >> la;
+    bool won = false;
+    if (live) {
+        const unsigned long long key = LO[t] + level_start(n, l, la) + parent;
+        const size_t mask = ((size_t)1 << (64 - shift)) - 1;
+        size_t h = (size_t)((key * 0x9E3779B97F4A7C15ull) >> shift);
+        for (;;) {  // (the table is at most half full: an empty slot is met)
+            const unsigned long long seen = atomicCAS(table + h, FU_EMPTY, key);
+            if (seen == FU_EMPTY) won = true;
+            if (seen == FU_EMPTY || seen == key) break;
+            h = (h + 1) & mask;
+        }
+    }
+    const unsigned long long winners = __ballot(won);
+    if (winners == 0) return;
+    const unsigned lane = threadIdx.x & 63u;
+    const int leader = __ffsll((long long)winners) - 1;
+    unsigned long long base = 0;
+    if ((int)lane == leader) base = atomicAdd(out_count, (unsigned long long)__popcll(winners));
+    base = __shfl(base, leader);
+    if (won) out[base + __popcll(winners & ((1ull << lane) - 1))] = record(t, parent);
+}
+
+// ---- the digests of one level ----
+struct FuLevel {
+    const uint4* list;                 // this level's records
+    const unsigned long long* count;   // how many
+    const uint64_t* ntree;
+    const uint64_t* LO;
+    const uint64_t* offsets;
+    const Scalar32* leaves;
+    Scalar32* levels;
+    Scalar32* roots;                   // may be null
+    unsigned long long* n_hashed;      // may be null
+    size_t lanes;
+    unsigned level, la;
+};
+
+struct FuNode {
+    const Scalar32* children;
+    uint64_t i, n_children;
+    Scalar32* out;
+    Scalar32* root;  // null unless the node is its tree's root and the caller wants the roots
+};
+__device__ __forceinline__ bool fu_node(const FuLevel& P, uint64_t g, FuNode& nd) {
+    if (g >= *P.count) return false;
+    const uint4 r = P.list[g];
+    const size_t t = r.x;
+    const uint64_t n = P.ntree[t];
+    const unsigned l = P.level;
+    nd.i = u64_of(r.z, r.w);
+    nd.n_children = ceil_shift(n, (l - 1) * P.la);
+    Scalar32* blk = P.levels + P.LO[t];
+    const uint64_t below = level_start(n, l - 1, P.la);  // (level_start(n, 0) = level_start(n, 1) = 0)
+    nd.children = l == 1 ? P.leaves + P.offsets[t] : blk + below;
+    nd.out = blk + (l == 1 ? 0 : below + nd.n_children) + nd.i;
+    nd.root = P.roots && ceil_shift(n, l * P.la) == 1 ? P.roots + t : nullptr;
+    return true;
+}
+
+template <unsigned ARITY>
+__global__ void __launch_bounds__(P252_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 3)))
+k_fu_digest(const int32_t* __restrict__ tab, TagArg tag, FuLevel P) {
+    const uint64_t g = (uint64_t)blockIdx.x * P252_BLOCK + threadIdx.x;
+    if (g >= P.lanes) return;
+    if (g == 0 && P.n_hashed) atomicAdd(P.n_hashed, *P.count);
+    FuNode nd;
+    if (!fu_node(P, g, nd)) return;
+    E29 s[WIDTH];
+#pragma unroll
+    for (int k = 0; k < NL; ++k) s[0].d[k] = tag.x0[k];  // lane 0 enters after its first S-box (hades_permute PRE0)
+#pragma unroll
+    for (unsigned k = 0; k < 4; ++k) {
+        const uint64_t c = nd.i * ARITY + k;
+        if (k < ARITY && c < nd.n_children)
+            s[1 + k] = load_scalar(nd.children + c);
+        else
+            s[1 + k] = e29_zero();
+    }
+    hades_permute<0x02u, true>(s, tab);  // only lane 1 is squeezed
+    store_scalar(nd.out, s[1]);
+    if (nd.root) store_scalar(nd.root, s[1]);
+}
+
+template <unsigned ARITY>
+__global__ void __launch_bounds__(P252_BLOCK) k_fu_digest_coop(const int32_t* __restrict__ tab, TagArg tag, FuLevel P) {
+    const uint64_t lane = (uint64_t)blockIdx.x * P252_BLOCK + threadIdx.x;
+    if (lane >= P.lanes) return;  // (lanes is a multiple of 8: whole groups only)
+    if (lane == 0 && P.n_hashed) atomicAdd(P.n_hashed, *P.count);
+    FuNode nd;
+    if (!fu_node(P, lane >> 3, nd)) return;  // (the whole group: one node)
+    const int j = (int)(threadIdx.x & 7u);
+    const int el = j < WIDTH ? j : WIDTH - 1;  // the state element this lane brings: 0 = tag, 1..4 = children
+    E29 mine = from_mont4(tag.w);
+    if (el > 0) {
+        const uint64_t c = nd.i * ARITY + (uint64_t)(el - 1);
+        mine = (unsigned)(el - 1) < ARITY && c < nd.n_children ? load_scalar(nd.children + c) : e29_zero();
+    }
+    E29 last = mine;
+    WaveComm8 cm{j, (int)(((threadIdx.x & 63u) & ~7u) * 4u)};
+    CoopLane<8> L = coop_lane<8>(tab, cm);
+    hades_permute_coop<8, false>(mine, last, tab, cm, L);
+    if (j == 1) {  // the digest is element 1 of the permuted state: lane 1's
+        store_scalar(nd.out, mine);
+        if (nd.root) store_scalar(nd.root, mine);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// launcher (C++ linkage, called from api.cpp)
+// ---------------------------------------------------------------------------------------------
+ForestUpdatePlan forest_update_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
+    const ForestRaggedPlan fr = forest_ragged_plan(arity, n_leaves, n_trees, max_leaves, true);
+    ForestUpdatePlan p;
+    p.arity = arity;
+    p.log2a = fr.log2a;
+    p.depth = fr.depth;
+    p.n_trees = n_trees;
+    p.k = k;
+    p.in[0] = k;
+    size_t widest = 0;
+    for (unsigned l = 1; l <= p.depth; ++l) {
+        p.in[l] = k < fr.bound[l] ? k : fr.bound[l];
+        size_t slots = FU_MIN_SLOTS;
+        while (slots < 2 * p.in[l - 1]) slots <<= 1;
+        p.slots[l] = slots;
+        if (slots > widest) widest = slots;
+    }
+    p.list_bytes = k * sizeof(uint4);
+    p.count_bytes = ((size_t)(p.depth + 1) * sizeof(unsigned long long) + 255) & ~(size_t)255;
+    p.table_bytes = widest * sizeof(unsigned long long);
+    return p;
+}
+
+hipError_t launch_forest_update(const int32_t* tab, const TagArg& tag, const ForestUpdatePlan& p, void* leaves, const void* offsets,
+                                const uint64_t* ntree, const uint64_t* lo, void* levels, const void* tree_ids, const void* leaf_ids,
+                                const void* new_leaves, void* roots, void* n_bad, void* n_hashed, void* ids, void* table, hipStream_t st) {
+    if (p.k == 0) return hipSuccess;
+    char* base = static_cast<char*>(ids);
+    unsigned long long* count = reinterpret_cast<unsigned long long*>(base);
+    uint4* list[2] = {reinterpret_cast<uint4*>(base + p.count_bytes), reinterpret_cast<uint4*>(base + p.count_bytes + p.list_bytes)};
+    unsigned long long* tb = static_cast<unsigned long long*>(table);
+    const uint64_t* off = static_cast<const uint64_t*>(offsets);
+    hipLaunchKernelGGL(k_fu_scatter, dim3((unsigned)((p.k + FU_BLOCK - 1) / FU_BLOCK)), dim3(FU_BLOCK), 0, st, off, ntree, p.n_trees,
+                       static_cast<const uint32_t*>(tree_ids), static_cast<const uint64_t*>(leaf_ids), static_cast<const uint4*>(new_leaves),
+                       p.k, static_cast<uint4*>(leaves), static_cast<uint4*>(roots), list[0], static_cast<unsigned*>(n_bad));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || p.depth == 0) return e;
+    e = hipMemsetAsync(count, 0, p.count_bytes, st);
+    if (e != hipSuccess) return e;
+    for (unsigned l = 1; l <= p.depth; ++l) {
+        e = hipMemsetAsync(tb, 0xFF, p.slots[l] * sizeof(unsigned long long), st);
+        if (e != hipSuccess) return e;
+        unsigned shift = 64;
+        for (size_t s = p.slots[l]; s > 1; s >>= 1) --shift;
+        const size_t lanes = p.in[l - 1];
+        hipLaunchKernelGGL(k_fu_claim, dim3((unsigned)((lanes + FU_BLOCK - 1) / FU_BLOCK)), dim3(FU_BLOCK), 0, st, list[(l - 1) & 1],
+                           l == 1 ? (const unsigned long long*)nullptr : count + (l - 1), lanes, ntree, lo, l, p.log2a, tb, shift,
+                           list[l & 1], count + l);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        FuLevel P;
+        P.list = list[l & 1];
+        P.count = count + l;
+        P.ntree = ntree;
+        P.LO = lo;
+        P.offsets = off;
+        P.leaves = static_cast<const Scalar32*>(leaves);
+        P.levels = static_cast<Scalar32*>(levels);
+        P.roots = static_cast<Scalar32*>(roots);
+        P.n_hashed = static_cast<unsigned long long*>(n_hashed);
+        P.level = l;
+        P.la = p.log2a;
+        const bool coop = coop8(p.in[l]);
+        P.lanes = coop ? p.in[l] * 8 : p.in[l];
+        if (p.arity == 4)
+            e = launch(coop ? k_fu_digest_coop<4> : k_fu_digest<4>, P.lanes, st, tab, tag, P);
+        else
+            e = launch(coop ? k_fu_digest_coop<2> : k_fu_digest<2>, P.lanes, st, tab, tag, P);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace p252

@@ -432,6 +432,30 @@ class Context:
                        _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=n_trees == 0), n_trees,
                        _dev_ptr(self, f, "d_ok", d_ok, k, elem=1), k, _stream(self)))
 
+    def merkle_forest_ragged_update_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                           d_new_leaves, k, d_roots=None, d_n_bad=None, d_n_hashed=None, arity=4):
+        """k leaf updates anywhere in a forest merkle_forest_ragged_device built with d_levels, in one call
+        (p252_merkle{4,2}_forest_ragged_update_device): update i writes d_new_leaves[i] to leaf d_leaf_ids[i] (int64/uint64, a position
+        inside the tree) of tree d_tree_ids[i] (int32/uint32), then every dirty ancestor is re-hashed ONCE, in place; d_leaves,
+        d_offsets, n_trees, max_leaves, d_levels exactly as the build took them.  d_roots (n_trees, 4; optional) is rewritten for
+        the touched trees only.  A bad update writes nothing and is counted in d_n_bad (a zeroed device int32/uint32, optional);
+        d_n_hashed (a zeroed device int64/uint64, optional) grows by the number of digests computed."""
+        f = "merkle_forest_ragged_update_device"
+        if arity not in (2, 4):
+            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+        L = _lib.lib()
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = d_leaves.numel() * d_leaves.element_size() // 32
+        depth = int((L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(max_leaves))
+        fn = L.p252_merkle4_forest_ragged_update_device if arity == 4 else L.p252_merkle2_forest_ragged_update_device
+        self._check(fn(self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees,
+                       max_leaves, _dev_ptr(self, f, "d_levels", d_levels, (n_leaves // (arity - 1) + n_trees * depth) * 32, null_ok=depth == 0),
+                       _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
+                       _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32), k,
+                       _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
+                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+                       _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
+
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
         f = "truncate250_device"
