@@ -82,5 +82,35 @@ def build_hosttest(force=False):
     return HOSTTEST_LIB
 
 
+PRIMTEST_HOST_LIB = os.path.join(CSRC, "libp252_primtest_host.so")
+PRIMTEST_DEV_LIB = os.path.join(CSRC, "libp252_primtest_dev.so")
+PRIMTEST_HEADERS = ["primtest.hpp", "fr29.hpp", "hades29.hpp", "tables.hpp", "fr_host.hpp", "kernels.h"]
+
+
+PRIMTEST_HOST_SOURCES = ["primtest.cpp", "primtest.hpp", "fr29.hpp", "hades29.hpp", "tables.hpp", "fr_host.hpp"]
+
+
+def primtest_host_cmd(src, out, extra=()):
+    """the g++ line of the primitive harness (tests/test_primitives_cpu.py reuses it for a UBSan build and for copies of
+    PRIMTEST_HOST_SOURCES with one header mutated: `extra` = more flags, the headers are those next to `src`)"""
+    return ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas"] + list(extra) + [src, "-o", out]
+
+
+def build_primtest_host(force=False):
+    """CPU build of csrc/primtest.cpp: one entry point per field primitive (tests/test_primitives_cpu.py).  Seconds."""
+    deps = [os.path.join(CSRC, f) for f in ["primtest.cpp"] + PRIMTEST_HEADERS]
+    if force or _stale(PRIMTEST_HOST_LIB, deps):
+        subprocess.check_call(primtest_host_cmd(os.path.join(CSRC, "primtest.cpp"), PRIMTEST_HOST_LIB))
+    return PRIMTEST_HOST_LIB
+
+
+def build_primtest_device(force=False):
+    """gfx950 build of csrc/primtest.hip: one kernel per field primitive (tests/test_primitives_gpu.py)."""
+    deps = [os.path.join(CSRC, f) for f in ["primtest.hip"] + PRIMTEST_HEADERS]
+    if force or _stale(PRIMTEST_DEV_LIB, deps):
+        subprocess.check_call([_hipcc()] + HIPCC_FLAGS + ["-shared", os.path.join(CSRC, "primtest.hip"), "-o", PRIMTEST_DEV_LIB], cwd=CSRC)
+    return PRIMTEST_DEV_LIB
+
+
 if __name__ == "__main__":
     print(build_library(force="--force" in sys.argv, verbose=True))
