@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Calls the ten ragged-forest entry points once each per shape, for a kernel trace: p252_merkle{4,2}_forest_ragged_device with and
+without d_levels, ..._forest_ragged_openings_device, ..._path_ragged_device, ..._forest_ragged_verify_device and
+..._forest_ragged_update_device, on a small forest (every level on the 8-lane-group digests) and a large one (the low levels on
+the one-lane digests, the narrow top levels on the groups), with few and with many updates.
+
+  rocprofv3 --kernel-trace -d DIR -o NAME --output-format csv -- python bench_tools/forest_dispatch_driver.py
+  python bench_tools/forest_dispatch_driver.py --dispatches DIR/.../NAME_kernel_trace.csv     # the ordered dispatch list
+
+Two builds of the library launch the same kernels in the same order with the same grids exactly when the lists are equal
+(P252_LIB_PATH selects the library; P252_RAGGED_SORT=0, read once per process, the unsorted re-hash).  Every verify call must
+accept every opening, before and after the updates: the driver exits non-zero otherwise."""
+import argparse
+import csv
+import os
+import re
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def dispatches(path):
+    """the trace's (kernel base name, grid, workgroup) rows in dispatch order, one per line"""
+    rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
+    for r in rows:
+        base = re.sub(r"\(.*", "", re.sub(r"^void ", "", r["Kernel_Name"])).replace("p252::", "").replace(".kd", "")
+        print(base, r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"], r["Workgroup_Size_X"], r["Workgroup_Size_Y"], r["Workgroup_Size_Z"])
+
+
+def _dev(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
+    return torch.from_numpy(a).to("cuda:0")
+
+
+def _depth(n, arity):
+    d = 0
+    while n > 1:
+        n, d = (n + arity - 1) // arity, d + 1
+    return d
+
+
+def run(ctx, arity, sizes, ks, seed):
+    import torch
+    from poseidon252_amd import merkle as M
+    rng = np.random.default_rng(seed)
+    tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
+    sizes = np.asarray(sizes, np.int64)
+    n_trees, max_leaves = len(sizes), int(sizes.max())
+    off = np.zeros(n_trees + 1, np.uint64)
+    np.cumsum(sizes.astype(np.uint64), out=off[1:])
+    n_leaves, D = int(off[-1]), _depth(max_leaves, arity)
+    dev = torch.device("cuda:0")
+    d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
+    d_off = _dev(off)
+    roots, roots2 = (torch.empty((n_trees, 4), dtype=torch.int64, device=dev) for _ in range(2))
+    d_lv = torch.empty((n_leaves // (arity - 1) + n_trees * D + 1, 4), dtype=torch.int64, device=dev)
+    ctx.merkle_forest_ragged_device(tag, d, d_off, n_trees, max_leaves, roots, None, arity=arity)   # level-major scratch
+    ctx.merkle_forest_ragged_device(tag, d, d_off, n_trees, max_leaves, roots2, d_lv, arity=arity)  # tree-major d_levels
+    torch.cuda.synchronize()
+    assert torch.equal(roots, roots2), "the two builds disagree"
+    for k in ks:
+        tid = rng.integers(0, n_trees, k)
+        lid = (rng.random(k) * sizes[tid]).astype(np.int64)
+        d_tid, d_lid = _dev(tid.astype(np.uint32)), _dev(lid.astype(np.uint64))
+        out = (torch.empty((k, 4), dtype=torch.int64, device=dev), torch.empty((k, D, arity - 1, 4), dtype=torch.int64, device=dev),
+               torch.empty((k, D), dtype=torch.uint8, device=dev), torch.empty((k,), dtype=torch.uint8, device=dev))
+        back = torch.empty((k, 4), dtype=torch.int64, device=dev)
+        ok = torch.zeros((k,), dtype=torch.uint8, device=dev)
+
+        def open_and_verify(what):
+            ctx.merkle_forest_ragged_openings_device(d, d_off, n_trees, max_leaves, d_lv, d_tid, d_lid, k, out=out, arity=arity)
+            ctx.merkle_path_ragged_device(tag, out[0], out[1], out[2], out[3], D, back, k, arity=arity)
+            ctx.merkle_forest_ragged_verify_device(tag, out[0], out[1], out[2], out[3], D, d_tid, roots, n_trees, ok, k, arity=arity)
+            torch.cuda.synchronize()
+            assert int(ok.sum()) == k, "%s: %d of %d openings verify" % (what, int(ok.sum()), k)
+            assert torch.equal(back, roots[torch.from_numpy(tid).to(dev)]), what
+
+        open_and_verify("built")
+        new = torch.randint(0, 1 << 60, (k, 4), dtype=torch.int64, device=dev)
+        ctx.merkle_forest_ragged_update_device(tag, d, d_off, n_trees, max_leaves, d_lv, d_tid, d_lid, new, k, d_roots=roots, arity=arity)
+        open_and_verify("updated")
+    print("arity %d, %d trees, %d leaves, depth %d, k = %s: ok" % (arity, n_trees, n_leaves, D, list(ks)))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--dispatches", metavar="CSV", help="print the ordered dispatch list of a rocprofv3 kernel trace and exit")
+    a = ap.parse_args()
+    if a.dispatches:
+        return dispatches(a.dispatches)
+    import poseidon252_amd as P
+    ctx = P.Context(0)
+    rng = np.random.default_rng(5)
+    small = [1, 2, 3, 5, 17, 64, 65, 300, 1000]                      # level 1: 1,457 / 4 + 9 nodes — the groups throughout
+    large = np.floor(np.exp(rng.uniform(0, np.log(4 ** 5 + 1), 3000))).astype(np.int64).clip(1, 4 ** 5)  # level 1 past 8,192 nodes
+    for arity in (4, 2):
+        run(ctx, arity, small, (50,), 1)
+        run(ctx, arity, large, (50, 40000), 2)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -106,6 +106,14 @@ struct LevelSetGuard {
         ctx->err = msg;
     }
 };
+
+// the way out of a builder whose launches may have failed (rc): records the pair's event, keeps the failure's message and code
+int finish_guarded(p252_ctx* ctx, LevelSetGuard& guard, int rc) {
+    const std::string msg = ctx->err;
+    const int rc2 = guard.finish();
+    if (rc) ctx->err = msg;
+    return rc ? rc : rc2;
+}
 }  // namespace
 
 const std::vector<int32_t>& p252host::host_tables() {
@@ -121,6 +129,8 @@ const std::vector<int32_t>& p252host::host_tables() {
 // device-resident scalar arrays are read and written with 16-byte accesses (a BlsScalar array from hipMalloc, or any
 // 32-byte-multiple offset into one, qualifies); anything else would fault on the GPU, so it is refused here
 static bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+// the id, offset and counter arrays beside them: `bytes` = the size of one element (a power of two); null is aligned
+static bool misaligned_to(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 static const char* const ALIGN_MSG = "device scalar arrays must be 16-byte aligned";
 
 TagArg p252host::tag_arg(const uint64_t tag[4]) {
@@ -520,8 +530,8 @@ static int hash_ragged_device_impl(p252_ctx* ctx, const void* d_tags, size_t max
     if (max_len == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: max_len must be > 0");
     if (!d_tags || !d_in || !d_offsets || !d_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
     if (misaligned(d_tags) || misaligned(d_in) || misaligned(d_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_offsets must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_n_bad must be 4-byte aligned");
+    if (misaligned_to(d_offsets, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_offsets must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_n_bad must be 4-byte aligned");
     if (n >= SIZE_MAX / 8 / (out_len > 8 ? out_len : 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -537,10 +547,7 @@ static int hash_ragged_device_impl(p252_ctx* ctx, const void* d_tags, size_t max
     const hipError_t e = launch_hash_ragged(ctx->d_tab, d_tags, max_len, d_in, d_offsets, (unsigned)out_len, d_out, n, d_n_bad, set->buf[0],
                                             set->buf[1], st, trunc250);
     if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string("hash_ragged: ") + hipGetErrorString(e));
-    const std::string msg = ctx->err;
-    const int rc2 = guard.finish();
-    if (rc) ctx->err = msg;
-    return rc ? rc : rc2;
+    return finish_guarded(ctx, guard, rc);
 }
 
 int p252_hash_ragged_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets, size_t out_len,
@@ -555,6 +562,14 @@ int p252_hash_ragged_truncated_device(p252_ctx* ctx, const void* d_tags, size_t 
 
 // ---- a forest of trees of different sizes in one call (forest_ragged.hip): the bookkeeping (leaf counts, scans, first tree of
 // each block) and, without d_levels, the level-major ping-pong live in the scratch pair of the calling stream
+// every forest call's sizes: the bookkeeping inside size_t; the good trees' leaf counts, summed on the device, below 2^63.  k: the callers'.
+static int forest_shape_check(p252_ctx* ctx, const char* who, size_t n_leaves, size_t n_trees, size_t max_leaves) {
+    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;
+    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) || (eff_max && n_trees > (SIZE_MAX / 2) / eff_max))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    return P252_OK;
+}
+
 static int forest_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
                                 const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_roots, void* d_levels, void* d_n_bad,
                                 void* hip_stream) {
@@ -563,15 +578,9 @@ static int forest_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t ta
     if (max_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: max_leaves must be > 0");
     if (!tag || !d_leaves || !d_offsets || !d_roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: NULL buffer");
     if (misaligned(d_leaves) || misaligned(d_roots) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) != 0)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: d_offsets must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: d_n_bad must be 4-byte aligned");
-    // (the leaf counts of the good trees are summed on the device: n_trees x their largest size stays below 2^63)
-    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;
-    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) ||
-        (eff_max && n_trees > (SIZE_MAX / 2) / eff_max))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: size overflow");
+    if (misaligned_to(d_offsets, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: d_offsets must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, "merkle_forest_ragged", n_leaves, n_trees, max_leaves)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const ForestRaggedPlan plan = forest_ragged_plan(arity, n_leaves, n_trees, max_leaves, d_levels != nullptr);
@@ -584,10 +593,7 @@ static int forest_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t ta
     const hipError_t e = launch_forest_ragged(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, max_leaves, d_roots, d_levels, d_n_bad,
                                               meta, ping ? meta + plan.meta_bytes : nullptr, set->buf[1], st);
     if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string("merkle_forest_ragged: ") + hipGetErrorString(e));
-    const std::string msg = ctx->err;
-    const int rc2 = guard.finish();
-    if (rc) ctx->err = msg;
-    return rc ? rc : rc2;
+    return finish_guarded(ctx, guard, rc);
 }
 
 int p252_merkle4_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, const void* d_offsets,
@@ -603,19 +609,6 @@ int p252_merkle2_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], cons
 // ---- openings out of such a forest, their re-hash with a depth per opening, and a root per opening (forest_openings.hip).  The
 // scratch — the forest's index and the opening records; the sort's order and counters; the recomputed roots — is the pair of the
 // calling stream, as for the build ----
-static size_t ceil_depth(size_t n, size_t arity) {  // p252_merkle{4,2}_depth without the overflow at the top of size_t
-    size_t d = 0;
-    for (size_t c = n; c > 1; c = c / arity + (c % arity != 0)) ++d;
-    return d;
-}
-
-static int finish_guarded(p252_ctx* ctx, LevelSetGuard& guard, int rc) {
-    const std::string msg = ctx->err;
-    const int rc2 = guard.finish();
-    if (rc) ctx->err = msg;
-    return rc ? rc : rc2;
-}
-
 static int forest_ragged_openings_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,
                                          size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
                                          const void* d_leaf_ids, size_t k, void* d_leaves_out, void* d_siblings, void* d_positions,
@@ -625,20 +618,18 @@ static int forest_ragged_openings_device(p252_ctx* ctx, unsigned arity, const vo
     const char* who = "merkle_forest_ragged_openings";
     if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
-    const size_t depth = ceil_depth(max_leaves, arity);
+    const size_t depth = forest_ragged_depth(max_leaves, arity);
     if (!d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_leaves_out || !d_depths ||
         (depth && (!d_levels || !d_siblings || !d_positions)))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
     if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_siblings))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_leaf_ids) & 7u))
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets and d_leaf_ids must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_tree_ids) & 3u) || (reinterpret_cast<uintptr_t>(d_n_bad) & 3u))
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
-    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;  // (the build's own limits)
-    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) || n_trees > (SIZE_MAX / 2) / eff_max ||
-        k > SIZE_MAX / 128 / (depth ? depth : 1))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    if (k > SIZE_MAX / 128 / (depth ? depth : 1)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t index_bytes = forest_ragged_index_bytes(n_trees);
@@ -677,7 +668,7 @@ static int path_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[
     if (rc) return rc;
     if (!d_roots_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
     if (misaligned(d_roots_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_n_bad must be 4-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_n_bad must be 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (!ragged_sort_enabled()) {  // P252_RAGGED_SORT=0: identity order, no scratch
@@ -705,8 +696,7 @@ static int forest_ragged_verify_device(p252_ctx* ctx, unsigned arity, const uint
     if (rc) return rc;
     if (!d_tree_ids || !d_ok || (n_trees && !d_roots)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
     if (misaligned(d_roots)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_tree_ids) & 3u) != 0)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids must be 4-byte aligned");
+    if (misaligned_to(d_tree_ids, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids must be 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const bool sort = ragged_sort_enabled();
@@ -776,20 +766,17 @@ static int forest_ragged_update_device(p252_ctx* ctx, unsigned arity, const uint
     const char* who = "merkle_forest_ragged_update";
     if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
-    const size_t depth = ceil_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
+    const size_t depth = forest_ragged_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
     if (!tag || !d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_new_leaves || (depth && !d_levels))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
     if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_new_leaves) || misaligned(d_roots))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_leaf_ids) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_n_hashed) & 7u))
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_n_hashed, 8))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets, d_leaf_ids and d_n_hashed must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d_tree_ids) & 3u) || (reinterpret_cast<uintptr_t>(d_n_bad) & 3u))
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
-    const size_t eff_max = max_leaves < n_leaves ? max_leaves : n_leaves;  // (the build's own limits)
-    if (n_leaves > SIZE_MAX / 64 || n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) || n_trees > (SIZE_MAX / 2) / eff_max ||
-        k > SIZE_MAX / 128)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    if (k > SIZE_MAX / 128) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t index_bytes = forest_ragged_index_bytes(n_trees);
@@ -910,7 +897,7 @@ int p252_merkle4_update_checked_device(p252_ctx* ctx, const uint64_t tag[4], voi
                                        const void* d_indices, const void* d_new_leaves, size_t k, void* d_root, void* d_n_bad,
                                        void* hip_stream) {
     if (!d_n_bad) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update_checked: d_n_bad is NULL");
-    if ((reinterpret_cast<uintptr_t>(d_n_bad) & 3u) != 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update_checked: d_n_bad must be 4-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update_checked: d_n_bad must be 4-byte aligned");
     return merkle4_update_device(ctx, tag, d_leaves, n_leaves, d_levels, d_indices, d_new_leaves, k, d_root, d_n_bad, hip_stream);
 }
 
@@ -990,10 +977,7 @@ static int verify_batch_device(p252_ctx* ctx, unsigned arity, const uint64_t tag
         const hipError_t e = launch_compare_roots(set->buf[0], d_root, d_ok, n, st);
         if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
     }
-    const std::string msg = ctx->err;
-    const int rc2 = guard.finish();
-    if (rc) ctx->err = msg;
-    return rc ? rc : rc2;
+    return finish_guarded(ctx, guard, rc);
 }
 
 int p252_merkle4_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
@@ -1032,7 +1016,7 @@ static int openings_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, 
     if (!d_leaves || !d_indices || !d_leaves_out || (depth && (!d_levels || !d_siblings || !d_positions)))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
     if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_siblings)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if ((reinterpret_cast<uintptr_t>(d_indices) & 3u) || (reinterpret_cast<uintptr_t>(d_n_bad) & 3u))
+    if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / counter must be 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -1334,7 +1318,7 @@ int p252_merkle4_tree_multi_device(p252_ctx* const* ctxs, size_t n_ctx, const ui
 // ------------------------------------------------------------------------------------------
 int p252_clock_probe_device(p252_ctx* ctx, void* d_out6, unsigned spin_us, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (!d_out6 || (reinterpret_cast<uintptr_t>(d_out6) & 7u)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "clock_probe: d_out6 must be an 8-byte aligned device buffer of 6 x uint64");
+    if (!d_out6 || misaligned_to(d_out6, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "clock_probe: d_out6 must be an 8-byte aligned device buffer of 6 x uint64");
     if (spin_us > 1000000u) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "clock_probe: spin_us > 1 s");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_clock_probe(d_out6, spin_us * 100u, (hipStream_t)hip_stream));  // real-time counter: 100 MHz

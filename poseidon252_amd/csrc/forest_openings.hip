@@ -22,9 +22,12 @@
 //                    hoisted tag S-box), 3 waves per SIMD.  One fetch scheme: record by record (the whole-line scheme of
 //                    k_merkle4_path_lines needs a wave-uniform level phase; the kernel is multiply-add-bound).
 //   k_compare_roots_gather   ok[i] from roots[i] against expected[tree_ids[i]]
+// ceil_shift, u64_of and the tree lookup are forest_node.hpp's.  k_fr_openings' level start, k_fo_record's depth and load_or_zero
+// (openings.hip's) stay written out here: profiles/forest_kernels_refactor.txt has the reasons.
 #include <hip/hip_runtime.h>
 
 #include "fastdiv.hpp"
+#include "forest_node.hpp"
 #include "forest_openings.h"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -38,12 +41,6 @@ constexpr unsigned FO_ITEMS = 8;  // openings per thread of a sort block
 constexpr unsigned FO_TILE = FO_BLOCK * FO_ITEMS;
 constexpr unsigned FO_BAD_BIN = FOREST_OPENINGS_BINS - 1;
 
-// ceil(n / 2^k) for any k
-__device__ __forceinline__ uint64_t ceil_shift(uint64_t n, unsigned k) {
-    if (k >= 64) return n != 0;
-    return (n >> k) + ((n & ((1ull << k) - 1)) != 0);
-}
-
 // a value select, not a pointer select (openings.hip: the pointer-select form parks the zero in scratch); word 0 of `base` exists
 __device__ __forceinline__ uint4 load_or_zero(const uint4* __restrict__ base, size_t word, bool ok) {
     uint4 v = base[ok ? word : 0];
@@ -53,8 +50,6 @@ __device__ __forceinline__ uint4 load_or_zero(const uint4* __restrict__ base, si
     v.w = ok ? v.w : 0u;
     return v;
 }
-
-__device__ __forceinline__ uint64_t u64_of(unsigned lo, unsigned hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 
 }  // namespace
 
@@ -68,12 +63,11 @@ __global__ void __launch_bounds__(FO_BLOCK) k_fo_record(const uint64_t* __restri
     if (i >= k) return;
     const size_t t = tree_ids[i];
     const uint64_t leaf = leaf_ids[i];
-    const bool known = t < n_trees;
-    const size_t ts = known ? t : 0;  // (n_trees >= 1: entry 0 exists)
-    const uint64_t n = known ? ntree[ts] : 0ull;
+    size_t ts;
+    const uint64_t n = forest_tree_leaves(ntree, n_trees, t, &ts);
     const bool good = n != 0 && leaf < n;
     const uint64_t leaf0 = good ? offsets[ts] : 0ull, lo = good ? LO[ts] : 0ull, nn = good ? n : 0ull, lf = good ? leaf : 0ull;
-    unsigned d = 0;
+    unsigned d = 0;  // p252_merkle{4,2}_depth(nn)
 #pragma unroll 1
     for (uint64_t c = nn; c > 1; c = ceil_shift(c, la)) ++d;
     rec[2 * i] = make_uint4((unsigned)leaf0, (unsigned)(leaf0 >> 32), (unsigned)nn, (unsigned)(nn >> 32));
@@ -111,7 +105,7 @@ __global__ void __launch_bounds__(FO_BLOCK) k_fr_openings(const uint4* __restric
     // level l of the tree (level 0 = its leaves) has cnt nodes; the opening has a row l while that level has more than one
     const uint64_t cnt = ceil_shift(n, l * SHIFT);
     const bool live = good && cnt > 1;
-    uint64_t first = l == 0 ? leaf0 : lo;  // the level's first node, in scalars of its array
+    uint64_t first = l == 0 ? leaf0 : lo;  // the level's first node, in scalars of its array: lo + level_start(n, l, SHIFT), written out
 #pragma unroll 1
     for (unsigned j = 1; j < l; ++j) first += ceil_shift(n, j * SHIFT);  // (levels 1 .. l-1 of the block before it)
     const uint64_t node = leaf >> (SHIFT * l);  // (l < D <= 64 / SHIFT)

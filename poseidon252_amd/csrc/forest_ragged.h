@@ -26,39 +26,8 @@ struct ForestRaggedPlan {
     size_t meta_bytes = 0;  // the bookkeeping: per-tree leaf counts, the scans, the first-tree rows (a multiple of 256 bytes)
 };
 
-#if defined(__HIPCC__)
-// ---- the closed forms of one tree's levels, for every kernel that finds a node inside a tree-major block (forest_ragged.hip,
-// forest_update.hip) ----
-// ceil(n / 2^k) for any k
-__device__ __forceinline__ uint64_t ceil_shift(uint64_t n, unsigned k) {
-    if (k >= 64) return n != 0;
-    return (n >> k) + ((n & ((1ull << k) - 1)) != 0);
-}
-// nodes of level l >= 1 of a tree of n leaves (0: the tree ended below l)
-__device__ __forceinline__ uint64_t level_nodes(uint64_t n, unsigned l, unsigned la) {
-    return ceil_shift(n, (l - 1) * la) > 1 ? ceil_shift(n, l * la) : 0;
-}
-// p252_merkle{4,2}_levels_len(n)
-__device__ __forceinline__ uint64_t levels_len_dev(uint64_t n, unsigned la) {
-    uint64_t total = 0;
-#pragma unroll 1
-    for (uint64_t c = n; c > 1;) {
-        c = ceil_shift(c, la);
-        total += c;
-    }
-    return total;
-}
-// start of level l >= 1 inside the levels block of a tree of n leaves (levels 1 .. l-1 before it)
-__device__ __forceinline__ uint64_t level_start(uint64_t n, unsigned l, unsigned la) {
-    uint64_t w = 0;
-#pragma unroll 1
-    for (unsigned j = 1; j < l; ++j) w += ceil_shift(n, j * la);
-    return w;
-}
-#endif
-
-// levels above the leaves of the largest tree (0 when every tree is a single leaf)
-unsigned forest_ragged_depth(size_t max_leaves, unsigned arity);
+// levels above the leaves of a tree of n leaves, for the plans and api.cpp's checks: p252_merkle{4,2}_depth without its wrap-around at SIZE_MAX
+unsigned forest_ragged_depth(size_t n, unsigned arity);
 ForestRaggedPlan forest_ragged_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, bool levels);
 
 // The whole build on `st`: validation and scans over the trees, then one digest launch per level across all trees.  meta =

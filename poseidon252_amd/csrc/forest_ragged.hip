@@ -23,11 +23,13 @@
 //                      node at level l is its root: in the level-major mode it goes to d_roots[t] instead of the scratch; in
 //                      the tree-major mode k_fr_roots_from_levels copies it from the end of the tree's block after the last
 //                      level (one output pointer per lane: the lane groups then hold their 256 VGPRs without AGPR spills).
-// The permutation is the library's: hades_permute<0x02u, true> with the hoisted tag S-box (the k_merkle4 build, 3 waves per
-// SIMD) and hades_permute_coop<8> (coop29.hpp) for levels that cannot fill the chip (the coop8 rule of kernels.h).
+// The permutation is the library's: hades_permute<0x02u, true> with the hoisted tag S-box (the k_merkle4 build, 3 waves per SIMD),
+// written out in k_fr_digest and again in k_fu_digest (through a shared function both come out with other instruction streams:
+// profiles/forest_kernels_refactor.txt), and hades_permute_coop<8> for levels that cannot fill the chip (the coop8 rule of
+// kernels.h) — node_digest_coop of forest_node.hpp, which holds what the three forest files share.
 #include <hip/hip_runtime.h>
 
-#include "coop29.hpp"
+#include "forest_node.hpp"
 #include "forest_ragged.h"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -237,7 +239,7 @@ k_fr_digest(const int32_t* __restrict__ tab, TagArg tag, FrLevel P) {
     if (g >= P.lanes) return;
     FrNode nd;
     if (!fr_node(P, g, nd)) return;
-    E29 s[WIDTH];
+    E29 s[WIDTH];  // (written out, as in k_fu_digest: see the head of this file)
 #pragma unroll
     for (int k = 0; k < NL; ++k) s[0].d[k] = tag.x0[k];  // lane 0 enters after its first S-box (hades_permute PRE0)
 #pragma unroll
@@ -259,17 +261,8 @@ __global__ void __launch_bounds__(P252_BLOCK) k_fr_digest_coop(const int32_t* __
     FrNode nd;
     if (!fr_node(P, lane >> 3, nd)) return;  // (the whole group: one node)
     const int j = (int)(threadIdx.x & 7u);
-    const int el = j < WIDTH ? j : WIDTH - 1;  // the state element this lane brings: 0 = tag, 1..4 = children
-    E29 mine = from_mont4(tag.w);
-    if (el > 0) {
-        const uint64_t c = nd.i * ARITY + (uint64_t)(el - 1);
-        mine = (unsigned)(el - 1) < ARITY && c < nd.n_children ? load_scalar(nd.children + c) : e29_zero();
-    }
-    E29 last = mine;
-    WaveComm8 cm{j, (int)(((threadIdx.x & 63u) & ~7u) * 4u)};
-    CoopLane<8> L = coop_lane<8>(tab, cm);
-    hades_permute_coop<8, false>(mine, last, tab, cm, L);
-    if (j == 1) store_scalar(nd.out, mine);  // the digest is element 1 of the permuted state: lane 1's
+    const E29 digest = node_digest_coop<ARITY>(tab, tag, nd.children, nd.i, nd.n_children, j);
+    if (j == 1) store_scalar(nd.out, digest);  // the digest is element 1 of the permuted state: lane 1's
 }
 
 // tree-major levels: each tree's root is the last scalar of its block (trees of one leaf and bad trees have theirs already)
@@ -289,9 +282,9 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_roots_from_levels(const uint64_
 // ---------------------------------------------------------------------------------------------
 // launcher (C++ linkage, called from api.cpp)
 // ---------------------------------------------------------------------------------------------
-unsigned forest_ragged_depth(size_t max_leaves, unsigned arity) {
+unsigned forest_ragged_depth(size_t n, unsigned arity) {
     unsigned d = 0;
-    for (size_t c = max_leaves; c > 1; c = (c + arity - 1) / arity) ++d;
+    for (size_t c = n; c > 1; c = c / arity + (c % arity != 0)) ++d;
     return d;
 }
 
@@ -316,6 +309,16 @@ ForestRaggedPlan forest_ragged_plan(unsigned arity, size_t n_leaves, size_t n_tr
     return p;
 }
 
+// how the build and the index both start: k_fr_prep, then the scan of the leaf counts (with `roots`: those of bad and one-leaf trees)
+static void launch_leaf_counts(const uint64_t* off, size_t n, size_t n_leaves, size_t max_leaves, size_t tiles, unsigned la, uint64_t* ntree,
+                               uint64_t* tsum, uint64_t* C, const Scalar32* leaves, Scalar32* roots, unsigned* n_bad, hipStream_t st) {
+    const dim3 blk(FR_BLOCK), grid((unsigned)tiles, 1);
+    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)n_leaves, (uint64_t)max_leaves, ntree);
+    hipLaunchKernelGGL(k_fr_tile_sums, grid, blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, tiles);
+    hipLaunchKernelGGL(k_fr_scan_apply<true>, grid, blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum, C, (uint64_t)n_leaves, off, leaves, roots, n_bad);
+}
+
 // the forest's index alone, for callers that read a built forest (forest_openings.hip): the validation and the leaf-count scan of
 // the build (no roots written, nothing counted), then LO = the scan of levels_len(n_t)
 size_t forest_ragged_index_bytes(size_t n_trees) {
@@ -335,11 +338,7 @@ hipError_t launch_forest_ragged_index(unsigned arity, const void* offsets, size_
     *ntree_out = ntree;
     *lo_out = LO;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)n_leaves, (uint64_t)max_leaves, ntree);
-    hipLaunchKernelGGL(k_fr_tile_sums, dim3(tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum);
-    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, (size_t)tiles);
-    hipLaunchKernelGGL(k_fr_scan_apply<true>, dim3(tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum, LO, (uint64_t)n_leaves, off,
-                       (const Scalar32*)nullptr, (Scalar32*)nullptr, (unsigned*)nullptr);
+    launch_leaf_counts(off, n, n_leaves, max_leaves, tiles, la, ntree, tsum, LO, nullptr, nullptr, nullptr, st);  // (no roots, nothing counted)
     hipLaunchKernelGGL(k_fr_tile_sums, dim3(tiles, 1), blk, 0, st, ntree, n, 0u, la, tsum);
     hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, (size_t)tiles);
     hipLaunchKernelGGL(k_fr_scan_apply<false>, dim3(tiles, 1), blk, 0, st, ntree, n, 0u, la, tsum, LO, (uint64_t)n_leaves, off,
@@ -362,12 +361,7 @@ hipError_t launch_forest_ragged(const int32_t* tab, const TagArg& tag, const For
     uint64_t* first = static_cast<uint64_t*>(meta);
     const unsigned la = p.log2a;
     const dim3 blk(FR_BLOCK);
-    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)p.n_leaves, (uint64_t)max_leaves, ntree);
-    // the leaf counts: the sum rule, the roots of bad and single-leaf trees
-    hipLaunchKernelGGL(k_fr_tile_sums, dim3((unsigned)p.tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum);
-    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, p.tiles);
-    hipLaunchKernelGGL(k_fr_scan_apply<true>, dim3((unsigned)p.tiles, 1), blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum, C,
-                       (uint64_t)p.n_leaves, off, lv, rt, nb);
+    launch_leaf_counts(off, n, p.n_leaves, max_leaves, p.tiles, la, ntree, tsum, C, lv, rt, nb, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.depth == 0) return e;
     // every level's node starts (and LO, the tree-major levels' block starts, in row 0)

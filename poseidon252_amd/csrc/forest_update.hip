@@ -2,8 +2,8 @@
 // (forest_ragged.hip, tree-major levels) in one call, for both arities, every dirty node hashed ONCE.  k_merkle4_update
 // (kernels.hip) hashes k nodes on every level — at the root level all k lanes hash the same node; here each level's dirty nodes are
 // first made distinct, then hashed:
-//   k_fu_scatter   one lane per update: validated as k_fo_record validates an opening (tree id < n_trees, a good tree, leaf id <
-//                  n_t — one count in *n_bad otherwise, nothing written), the new leaf stored (two 16-byte stores), a 16-byte
+//   k_fu_scatter   one lane per update: validated as k_fo_record validates an opening, through forest_tree_leaves (tree id <
+//                  n_trees, a good tree, leaf id < n_t — one count in *n_bad otherwise, nothing written), the new leaf stored (two 16-byte stores), a 16-byte
 //                  record (tree id, valid, leaf id) written as list 0; a single-leaf tree's root is its leaf
 //   k_fu_claim     level l = 1 .. D, one lane per record of list l - 1: the parent (t, i >> log2 arity), keyed by its slot in d_levels
 //                  (LO[t] + level_start(n_t, l) + i, unique across the forest), is claimed in an open-addressing table with one
@@ -16,10 +16,11 @@
 //                  lanes and leaves on the device-side count: the host never learns it.  Lane 0 adds the count to *n_hashed.
 // A level's digest launch reads level l - 1 and writes level l only, so updating in place is race-free across launch boundaries.
 // The permutation is the library's, as in k_fr_digest / k_fr_digest_coop: hades_permute<0x02u, true> with the hoisted tag S-box at
-// 3 waves per SIMD, hades_permute_coop<8> when the level cannot fill the chip (the coop8 rule of kernels.h on min(k, bound[l])).
+// 3 waves per SIMD (written out here as there: forest_ragged.hip says why), node_digest_coop when the level cannot fill the chip (the
+// coop8 rule of kernels.h on min(k, bound[l])).  The closed forms, u64_of and the tree lookup are forest_node.hpp's too.
 #include <hip/hip_runtime.h>
 
-#include "coop29.hpp"
+#include "forest_node.hpp"
 #include "forest_update.h"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -32,7 +33,6 @@ constexpr unsigned FU_BLOCK = 256;
 constexpr unsigned long long FU_EMPTY = ~0ull;  // (the table is cleared to 0xFF bytes; no slot of d_levels has this number)
 constexpr size_t FU_MIN_SLOTS = 64;
 
-__device__ __forceinline__ uint64_t u64_of(unsigned lo, unsigned hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 __device__ __forceinline__ uint4 record(uint32_t t, uint64_t i) { return make_uint4(t, 1u, (unsigned)i, (unsigned)(i >> 32)); }
 
 }  // namespace
@@ -47,9 +47,8 @@ __global__ void __launch_bounds__(FU_BLOCK) k_fu_scatter(const uint64_t* __restr
     if (i >= k) return;
     const uint32_t t = tree_ids[i];
     const uint64_t leaf = leaf_ids[i];
-    const bool known = t < n_trees;
-    const size_t ts = known ? t : 0;  // (n_trees >= 1: entry 0 exists)
-    const uint64_t n = known ? ntree[ts] : 0ull;
+    size_t ts;
+    const uint64_t n = forest_tree_leaves(ntree, n_trees, t, &ts);
     if (n == 0 || leaf >= n) {  // a bad update: nothing written, no record
         list[i] = make_uint4(0u, 0u, 0u, 0u);
         if (n_bad) atomicAdd(n_bad, 1u);
@@ -147,7 +146,7 @@ k_fu_digest(const int32_t* __restrict__ tab, TagArg tag, FuLevel P) {
     if (g == 0 && P.n_hashed) atomicAdd(P.n_hashed, *P.count);
     FuNode nd;
     if (!fu_node(P, g, nd)) return;
-    E29 s[WIDTH];
+    E29 s[WIDTH];  // (written out, as in k_fr_digest: see the head of this file)
 #pragma unroll
     for (int k = 0; k < NL; ++k) s[0].d[k] = tag.x0[k];  // lane 0 enters after its first S-box (hades_permute PRE0)
 #pragma unroll
@@ -171,16 +170,7 @@ __global__ void __launch_bounds__(P252_BLOCK) k_fu_digest_coop(const int32_t* __
     FuNode nd;
     if (!fu_node(P, lane >> 3, nd)) return;  // (the whole group: one node)
     const int j = (int)(threadIdx.x & 7u);
-    const int el = j < WIDTH ? j : WIDTH - 1;  // the state element this lane brings: 0 = tag, 1..4 = children
-    E29 mine = from_mont4(tag.w);
-    if (el > 0) {
-        const uint64_t c = nd.i * ARITY + (uint64_t)(el - 1);
-        mine = (unsigned)(el - 1) < ARITY && c < nd.n_children ? load_scalar(nd.children + c) : e29_zero();
-    }
-    E29 last = mine;
-    WaveComm8 cm{j, (int)(((threadIdx.x & 63u) & ~7u) * 4u)};
-    CoopLane<8> L = coop_lane<8>(tab, cm);
-    hades_permute_coop<8, false>(mine, last, tab, cm, L);
+    const E29 mine = node_digest_coop<ARITY>(tab, tag, nd.children, nd.i, nd.n_children, j);
     if (j == 1) {  // the digest is element 1 of the permuted state: lane 1's
         store_scalar(nd.out, mine);
         if (nd.root) store_scalar(nd.root, mine);

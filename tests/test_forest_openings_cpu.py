@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers.kernel_resources import kernel_resources
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 ARGS = {"p252_merkle4_forest_ragged_openings_device": 16, "p252_merkle2_forest_ragged_openings_device": 16,
@@ -41,19 +43,7 @@ def test_six_symbols_declared_exported_and_in_sys_rs():
 
 @pytest.fixture(scope="module")
 def resources():
-    from poseidon252_amd import build as b
-    b._gen_assets()
-    out = os.path.join(CSRC, "_gen", "forest_openings_test.s")
-    cmd = [b._hipcc()] + [f for f in b.HIPCC_FLAGS if f != "-fPIC"] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                                                      "-o", out, os.path.join(CSRC, "forest_openings.hip")]
-    proc = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert proc.returncode == 0, proc.stderr[-3000:]
-    r = proc.stderr
-    names = re.findall(r"Function Name: (\S+)", r)
-    cols = [[int(x) for x in re.findall(pat, r)] for pat in (r"\bVGPRs: (\d+)", r"\bAGPRs: (\d+)", r"ScratchSize \[bytes/lane\]: (\d+)",
-                                                               r"Occupancy \[waves/SIMD\]: (\d+)")]
-    assert all(len(c) == len(names) for c in cols), r[-2000:]
-    return {n: dict(zip(("vgpr", "agpr", "scratch", "occ"), vals)) for n, *vals in zip(names, *cols)}
+    return kernel_resources("forest_openings.hip", os.path.join(CSRC, "_gen", "forest_openings_test.s"))[0]
 
 
 def test_kernels_meet_resource_targets(resources):

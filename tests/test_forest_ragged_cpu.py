@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers.kernel_resources import kernel_resources
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 FOREST = ("p252_merkle4_forest_ragged_device", "p252_merkle2_forest_ragged_device", "p252_merkle4_forest_ragged",
@@ -37,19 +39,7 @@ def test_forest_ragged_symbols_declared_exported_and_in_sys_rs():
 
 @pytest.fixture(scope="module")
 def forest_resources():
-    from poseidon252_amd import build as b
-    b._gen_assets()
-    out = os.path.join(CSRC, "_gen", "forest_ragged_test.s")
-    cmd = [b._hipcc()] + [f for f in b.HIPCC_FLAGS if f != "-fPIC"] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                                                      "-o", out, os.path.join(CSRC, "forest_ragged.hip")]
-    proc = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert proc.returncode == 0, proc.stderr[-3000:]
-    r = proc.stderr
-    names = re.findall(r"Function Name: (\S+)", r)
-    cols = [[int(x) for x in re.findall(pat, r)] for pat in (r"\bVGPRs: (\d+)", r"\bAGPRs: (\d+)", r"ScratchSize \[bytes/lane\]: (\d+)",
-                                                               r"Occupancy \[waves/SIMD\]: (\d+)")]
-    assert all(len(c) == len(names) for c in cols), r[-2000:]
-    return {n: dict(zip(("vgpr", "agpr", "scratch", "occ"), vals)) for n, *vals in zip(names, *cols)}
+    return kernel_resources("forest_ragged.hip", os.path.join(CSRC, "_gen", "forest_ragged_test.s"))[0]
 
 
 def test_forest_ragged_kernels_meet_resource_targets(forest_resources):
@@ -70,9 +60,13 @@ def test_forest_ragged_is_its_own_translation_unit_and_the_hashed_sources_stay()
     from poseidon252_amd import build as b
     assert "forest_ragged.hip" in b.SOURCES and "forest_ragged.h" in b.HEADERS
     src = open(os.path.join(CSRC, "forest_ragged.hip")).read()
-    # the permutation is included, not copied
-    assert '#include "hades29.hpp"' in src and '#include "coop29.hpp"' in src
-    assert "hades_permute<0x02u, true>" in src and "hades_permute_coop<8, false>" in src
+    node = open(os.path.join(CSRC, "forest_node.hpp")).read()
+    # the permutation is included, not copied: through forest_node.hpp, which holds the 8-lane digest of a node (the one-lane
+    # digest is written out in the kernel); no function named hades_* is defined here
+    assert "forest_node.hpp" in b.HEADERS and '#include "forest_node.hpp"' in src
+    assert '#include "hades29.hpp"' in src and '#include "hades29.hpp"' in node and '#include "coop29.hpp"' in node
+    assert "hades_permute<0x02u, true>" in src and "hades_permute_coop<8, false>" in node and "node_digest_coop<ARITY>(" in src
+    assert not re.search(r"\bhades_\w+\s*\([^;{]*\)\s*\{", src)
     assert "forest_ragged" not in open(os.path.join(CSRC, "kernels.hip")).read()
     assert "forest_ragged" not in open(os.path.join(CSRC, "kernels.h")).read()
 

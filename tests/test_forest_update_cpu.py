@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 from forest_update_bench import dirty_nodes as dirty_count  # noqa: E402  (the numpy model of what one call may hash; checked below)
+from helpers.kernel_resources import kernel_resources  # noqa: E402
 from test_forest_openings_cpu import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
 
 ARGS = {"p252_merkle4_forest_ragged_update_device": 16, "p252_merkle2_forest_ragged_update_device": 16}
@@ -43,19 +44,7 @@ def test_two_symbols_declared_exported_and_in_sys_rs():
 
 @pytest.fixture(scope="module")
 def compiled():
-    from poseidon252_amd import build as b
-    b._gen_assets()
-    out = os.path.join(CSRC, "_gen", "forest_update_test.s")
-    cmd = [b._hipcc()] + [f for f in b.HIPCC_FLAGS if f != "-fPIC"] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                                                      "-o", out, os.path.join(CSRC, "forest_update.hip")]
-    proc = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert proc.returncode == 0, proc.stderr[-3000:]
-    r = proc.stderr
-    names = re.findall(r"Function Name: (\S+)", r)
-    cols = [[int(x) for x in re.findall(pat, r)] for pat in (r"\bVGPRs: (\d+)", r"\bAGPRs: (\d+)", r"ScratchSize \[bytes/lane\]: (\d+)",
-                                                               r"Occupancy \[waves/SIMD\]: (\d+)")]
-    assert all(len(c) == len(names) for c in cols), r[-2000:]
-    return {n: dict(zip(("vgpr", "agpr", "scratch", "occ"), vals)) for n, *vals in zip(names, *cols)}, open(out).read()
+    return kernel_resources("forest_update.hip", os.path.join(CSRC, "_gen", "forest_update_test.s"))
 
 
 def test_kernels_meet_resource_targets(compiled):
@@ -78,8 +67,12 @@ def test_own_translation_unit_and_the_permutation_is_included():
     from poseidon252_amd import build as b
     assert "forest_update.hip" in b.SOURCES and "forest_update.h" in b.HEADERS
     src = open(os.path.join(CSRC, "forest_update.hip")).read()
-    assert '#include "hades29.hpp"' in src and '#include "coop29.hpp"' in src
-    assert "hades_permute<0x02u, true>" in src and "hades_permute_coop<8, false>" in src
+    node = open(os.path.join(CSRC, "forest_node.hpp")).read()
+    # through forest_node.hpp, which holds the 8-lane digest of a node (the one-lane digest is written out in the kernel)
+    assert "forest_node.hpp" in b.HEADERS and '#include "forest_node.hpp"' in src
+    assert '#include "hades29.hpp"' in src and '#include "hades29.hpp"' in node and '#include "coop29.hpp"' in node
+    assert "hades_permute<0x02u, true>" in src and "hades_permute_coop<8, false>" in node and "node_digest_coop<ARITY>(" in src
+    assert not re.search(r"\bhades_\w+\s*\([^;{]*\)\s*\{", src)
     assert "amdgpu_waves_per_eu(3, 3)" in src
     assert "asm" not in src  # plain C++ and vector stores only
     assert "forest_update" not in open(os.path.join(CSRC, "kernels.hip")).read()

@@ -4,7 +4,6 @@ performance are: private-memory (scratch) use when an unroll budget is missed, a
 blowing the instruction cache, and products lowered to two multiply-adds."""
 import os
 import re
-import subprocess
 
 import pytest
 
@@ -49,26 +48,19 @@ def test_data_movement_kernels_use_no_scratch(tmp_path):
     bytes — `cond ? array[i] : zero` had been compiled into a pointer select with the zero parked in SCRATCH (16 bytes stored per
     lane).  A data-movement kernel must not touch private memory at all, and must stay far below the register budget of full
     occupancy (8 waves per SIMD: 64 VGPRs)."""
-    from poseidon252_amd import build as b
-    out = tmp_path / "openings.s"
-    cmd = [b._hipcc()] + [f for f in b.HIPCC_FLAGS if f != "-fPIC"] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                                                      "-o", str(out), os.path.join(CSRC, "openings.hip")]
-    proc = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", proc.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", proc.stderr)]
-    vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", proc.stderr)]
+    from helpers.kernel_resources import kernel_resources
+    res, text = kernel_resources("openings.hip", tmp_path / "openings.s")
+    names, scratch, vgprs = list(res), [v["scratch"] for v in res.values()], [v["vgpr"] for v in res.values()]
     # {uint32 FAST (multiply-shift + level table in LDS, round 5), uint32, size_t} lane index x {arity 4, arity 2}
-    assert len(names) == 6 and len(scratch) == 6 and len(vgprs) == 6, proc.stderr[-1500:]
+    assert len(names) == 6, names
     assert scratch == [0] * 6 and max(vgprs) <= 32, (names, scratch, vgprs)
     # the FAST builds hold no division (v_rcp_iflag_f32 is the 32-bit udiv expansion's reciprocal) and read the level table from LDS
-    text = open(out).read()
     for n in names:
         body = text[text.index("\n" + n + ":"):]
         body = body[:body.index("s_endpgm")]
         fast = "ELb1EEE" in n
         assert (body.count("v_rcp") == 0 and body.count("ds_read") + body.count("ds_load") >= 1) if fast else body.count("v_rcp") >= 1, n
-    assert "scratch_" not in open(out).read()
+    assert "scratch_" not in text
 
 
 def test_code_size_fits_instruction_cache_phases(isa):
