@@ -18,6 +18,8 @@
 //   —                                               merkle_forest_ragged_openings_device / merkle_path_ragged_device /
 //                                                   merkle_forest_ragged_verify_device: openings out of such a forest
 //   —                                               merkle_forest_ragged_update_device: leaf updates anywhere in such a forest
+//   —                                               merkle_multiproof_device / merkle_multiproof_verify_device /
+//                                                   merkle_multiproof_bound: many leaves of one tree, one shared proof
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -527,6 +529,36 @@ inline void merkle_forest_ragged_update_device(void* d_leaves, std::size_t n_lea
     detail::check(fn(ctx.get(), tag.data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves,
                      k, d_roots, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_update_device");
+}
+
+// Many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; the format is in poseidon252_hip.h).
+// merkle_multiproof_bound: the most scalars such a proof holds.
+inline std::size_t merkle_multiproof_bound(std::size_t n_leaves, std::size_t k, unsigned arity = 4) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_multiproof_bound: arity must be 4 or 2");
+    return arity == 4 ? p252_merkle4_multiproof_bound(n_leaves, k) : p252_merkle2_multiproof_bound(n_leaves, k);
+}
+// Extraction: d_indices = k strictly ascending uint32 positions; d_leaves_out[k], d_proof (nothing written at or past proof_cap
+// scalars) and *d_proof_len (device uint64: the scalars the proof needs; 0 after a bad position, which *d_n_bad counts).
+inline void merkle_multiproof_device(const void* d_leaves, std::size_t n_leaves, const void* d_levels, const void* d_indices, std::size_t k,
+                                     void* d_leaves_out, void* d_proof, std::size_t proof_cap, void* d_proof_len, unsigned arity = 4,
+                                     Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_multiproof_device: arity must be 4 or 2");
+    auto fn = arity == 4 ? p252_merkle4_multiproof_device : p252_merkle2_multiproof_device;
+    detail::check(fn(ctx.get(), d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, stream),
+                  ctx.get(), "merkle_multiproof_device");
+}
+// Verification, every ancestor hashed once: *d_ok (1 byte) = 1 iff no position is bad, the structure of (n_leaves, d_indices)
+// consumes exactly proof_len scalars and the recomputed root equals *d_root.
+inline void merkle_multiproof_verify_device(std::size_t n_leaves, const void* d_indices, const void* d_leaves_in, std::size_t k,
+                                            const void* d_proof, std::size_t proof_len, const void* d_root, void* d_ok, unsigned arity = 4,
+                                            Context& ctx = Context::default_context(), void* d_root_out = nullptr,
+                                            void* d_n_hashed = nullptr, void* d_n_bad = nullptr, void* stream = nullptr) {
+    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_multiproof_verify_device: arity must be 4 or 2");
+    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
+    auto fn = arity == 4 ? p252_merkle4_multiproof_verify_device : p252_merkle2_multiproof_verify_device;
+    detail::check(fn(ctx.get(), tag.data(), n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
+                     d_n_bad, stream),
+                  ctx.get(), "merkle_multiproof_verify_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

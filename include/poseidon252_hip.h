@@ -91,7 +91,9 @@ extern "C" {
  *      + p252_merkle{4,2}_forest_ragged_openings_device, p252_merkle{4,2}_path_ragged_device,
  *      p252_merkle{4,2}_forest_ragged_verify_device (additive, same version): openings out of such a forest in one call;
  *      + p252_merkle{4,2}_forest_ragged_update_device (additive, same version): leaf updates anywhere in such a forest in one
- *      call, each dirty node hashed once */
+ *      call, each dirty node hashed once;
+ *      + p252_merkle{4,2}_multiproof_bound, p252_merkle{4,2}_multiproof_device, p252_merkle{4,2}_multiproof_verify_device
+ *      (additive, same version): many leaves of one tree behind one shared proof, each ancestor hashed once */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -458,6 +460,50 @@ int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
                                              size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
                                              const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
                                              void* d_n_hashed, void* hip_stream);
+
+/* ---- many leaves of ONE tree behind one shared proof.  The tree is what p252_merkle{4,2}_tree_device stored (d_leaves + d_levels;
+ * one tree block of a ragged forest is the same layout); only the proof object is new.  The per-leaf openings above write
+ * depth x (arity - 1) siblings for each leaf and their verification hashes k x depth nodes; when the k leaves share a tree most of
+ * those siblings follow from other leaves of the batch and most of those digests are the same node again.
+ * The format, A = arity: the k positions are STRICTLY ASCENDING, each < n_leaves.  w_0 = n_leaves, w_{l+1} = ceil(w_l / A);
+ * S_0 = the positions, S_{l+1} = the distinct i / A of S_l, ascending.  For l = 0, 1, .. while w_l > 1; for every parent p of
+ * S_{l+1}, ascending; for every child slot c = pA .. pA + A - 1, ascending: the proof receives node c of level l iff c < w_l and c
+ * is not in S_l (slots at or past w_l are the zero scalar, hash.rs:22-26, and never stored).  The proof is the concatenation of
+ * these scalars in that order: deterministic, and empty when n_leaves == 1 or k == n_leaves.
+ * p252_merkle{4,2}_multiproof_bound: an upper bound of its length in scalars,
+ * sum over those levels of min((A - 1) min(k, w_{l+1}), w_l - min(k, w_l)); reached by k == 1 on a complete tree.
+ * No host-buffer twin: the calls act on a tree that lives on the device. ---- */
+size_t p252_merkle4_multiproof_bound(size_t n_leaves, size_t k);
+size_t p252_merkle2_multiproof_bound(size_t n_leaves, size_t k);
+/* Extraction (no hashing): d_indices = k uint32 positions (device), d_leaves_out[k] = the leaves at them, d_proof = the proof,
+ * *d_proof_len (device uint64, 8-byte aligned) = the scalars the proof NEEDS: nothing is written at or past proof_cap (scalars), so
+ * a short buffer costs a second call, never memory; a buffer of _bound scalars always suffices.  d_proof may be NULL when
+ * proof_cap == 0.  A position that is >= n_leaves or not greater than its predecessor is bad: counted once in *d_n_bad (device
+ * uint32 the caller has zeroed; may be NULL), the call then reports *d_proof_len = 0, reads nothing through a bad position, and
+ * leaves the contents of d_leaves_out and d_proof unspecified.  k == 0 or n_leaves == 0 (or either >= 2^32: positions are uint32)
+ * -> P252_ERR_INVALID_ARGUMENT.  Asynchronous on hip_stream; scratch (counters, scan tiles, two work lists of 16 bytes per
+ * parent: at most 33 bytes per position plus 2 KiB) in the context's pair of THIS stream, covered by p252_trim / p252_wipe.
+ * Cost: up to three launches per level, so for a few leaves p252_merkle{4,2}_openings_device (one launch) is quicker. */
+int p252_merkle4_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
+                                   void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream);
+int p252_merkle2_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
+                                   void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream);
+/* Verification: the structure is derived from (n_leaves, d_indices) alone; every node of S_1, S_2, .. is hashed ONCE with
+ * Hash::digest(Domain::Merkle4 / Merkle2, children) (pass that domain's tag), each child taken from the level below, from the
+ * proof stream, or as zero.  *d_ok (device, 1 byte) = 1 iff no position is bad, the structure consumes exactly proof_len scalars,
+ * and the recomputed root equals *d_root (device, 1 scalar); 0 otherwise.  Positions and proof are untrusted: nothing is read at
+ * or past proof_len or k whatever they contain.  d_root_out (device, 1 scalar; may be NULL) receives the recomputed root when the
+ * first two conditions hold and is left alone otherwise; *d_n_hashed (device uint64, 8-byte aligned; may be NULL) receives the
+ * digests computed, sum over l >= 1 of |S_l| (0 after a bad position); *d_n_bad as above.  d_proof may be NULL when
+ * proof_len == 0.  Asynchronous on hip_stream; scratch as for extraction plus two lists of at most min(k, ceil(n_leaves / A))
+ * node values, in the same pair.  Cost: up to four launches per level: see profiles/multiproof.txt for the k from which this beats
+ * p252_merkle{4,2}_verify_batch_device. */
+int p252_merkle4_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
+                                          size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
+                                          void* d_n_hashed, void* d_n_bad, void* hip_stream);
+int p252_merkle2_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
+                                          size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
+                                          void* d_n_hashed, void* d_n_bad, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

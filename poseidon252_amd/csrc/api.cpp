@@ -19,6 +19,7 @@
 #include "forest_update.h"
 #include "hades29.hpp"
 #include "kernels.h"
+#include "multiproof.h"
 #include "openings.h"
 #include "ragged.h"
 #include "tables.hpp"
@@ -1034,6 +1035,94 @@ int p252_merkle4_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_l
 int p252_merkle2_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
                                  void* d_leaves_out, void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream) {
     return openings_device(ctx, 2, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_siblings, d_positions, d_n_bad, hip_stream);
+}
+
+// ---- many leaves of ONE stored tree behind one shared proof (multiproof.hip): a sibling that another leaf of the batch determines
+// is not stored, and verification hashes every ancestor once.  The scratch — the counters, the scan tiles and two work lists in the
+// first buffer; the verify's two lists of node values in the second — is the pair of the calling stream ----
+size_t p252_merkle4_multiproof_bound(size_t n_leaves, size_t k) { return n_leaves && k ? multiproof_plan(4, n_leaves, k).bound : 0; }
+size_t p252_merkle2_multiproof_bound(size_t n_leaves, size_t k) { return n_leaves && k ? multiproof_plan(2, n_leaves, k).bound : 0; }
+
+static int multiproof_shape_check(p252_ctx* ctx, const std::string& who, size_t n_leaves, size_t k) {
+    if (k == 0 || n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves and k must be > 0");
+    if (n_leaves > 0xffffffffu || k > 0xffffffffu)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves and k must be below 2^32 (positions are uint32)");
+    return P252_OK;
+}
+
+static int multiproof_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_levels,
+                             const void* d_indices, size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len,
+                             void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_multiproof" : "merkle2_multiproof";
+    if (int rc = multiproof_shape_check(ctx, who, n_leaves, k)) return rc;
+    const MultiproofPlan plan = multiproof_plan(arity, n_leaves, k);
+    if (!d_leaves || !d_indices || !d_leaves_out || !d_proof_len || (plan.depth && !d_levels) || (proof_cap && !d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4) || misaligned_to(d_proof_len, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / d_n_bad must be 4-byte, d_proof_len 8-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    int rc = level_set(ctx, st, plan.work_bytes(), 0, &set);
+    if (rc) return rc;
+    const hipError_t e = launch_multiproof(plan, d_leaves, d_levels, d_indices, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad,
+                                           set->buf[0], st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
+    return finish_guarded(ctx, guard, rc);
+}
+
+static int multiproof_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], size_t n_leaves, const void* d_indices,
+                                    const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len, const void* d_root,
+                                    void* d_ok, void* d_root_out, void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_multiproof_verify" : "merkle2_multiproof_verify";
+    if (int rc = multiproof_shape_check(ctx, who, n_leaves, k)) return rc;
+    if (!tag || !d_indices || !d_leaves_in || !d_root || !d_ok || (proof_len && !d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves_in) || misaligned(d_proof) || misaligned(d_root) || misaligned(d_root_out))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / d_n_bad must be 4-byte, d_n_hashed 8-byte aligned");
+    if (proof_len > SIZE_MAX / 32) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const MultiproofPlan plan = multiproof_plan(arity, n_leaves, k);
+    LevelSetGuard guard(ctx);
+    p252_ctx::LevelSet*& set = guard.set;
+    int rc = level_set(ctx, st, plan.work_bytes(), plan.values_bytes(), &set);
+    if (rc) return rc;
+    const hipError_t e = launch_multiproof_verify(ctx->d_tab, tag_arg(tag), plan, d_indices, d_leaves_in, d_proof, proof_len, d_root, d_ok,
+                                                  d_root_out, d_n_hashed, d_n_bad, set->buf[0], set->buf[1], st);
+    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
+    return finish_guarded(ctx, guard, rc);
+}
+
+int p252_merkle4_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
+                                   void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream) {
+    return multiproof_device(ctx, 4, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
+                                   void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream) {
+    return multiproof_device(ctx, 2, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, hip_stream);
+}
+
+int p252_merkle4_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
+                                          size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
+                                          void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    return multiproof_verify_device(ctx, 4, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
+                                    d_n_bad, hip_stream);
+}
+
+int p252_merkle2_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
+                                          size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
+                                          void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    return multiproof_verify_device(ctx, 2, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
+                                    d_n_bad, hip_stream);
 }
 
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----

@@ -539,6 +539,58 @@ class Context:
             raise ValueError("merkle4_openings: %d position(s) outside the tree" % int(bad.item()))
         return out, sib, pos, depth
 
+    # ---- many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; csrc/multiproof.hip) ----
+    def merkle_multiproof_bound(self, n_leaves, k, arity=4):
+        """upper bound, in scalars, of the shared proof of k leaves of a tree of n_leaves (p252_merkle{4,2}_multiproof_bound)"""
+        if arity not in (2, 4):
+            raise ValueError("merkle_multiproof_bound: arity must be 4 or 2, not %r" % (arity,))
+        L = _lib.lib()
+        return int((L.p252_merkle4_multiproof_bound if arity == 4 else L.p252_merkle2_multiproof_bound)(n_leaves, k))
+
+    def merkle_multiproof_device(self, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, d_proof_len, d_n_bad=None,
+                                 arity=4):
+        """one shared proof for k leaves of a tree stored as merkle{4,2}_tree_device filled it (p252_merkle{4,2}_multiproof_device; no
+        hashing): d_indices = k STRICTLY ASCENDING positions (int32/uint32), d_leaves_out (k, 4) receives the leaves, d_proof the
+        proof — its capacity is the tensor's length, nothing is written past it (None: capacity 0, to learn the length) — and
+        d_proof_len (one int64/uint64) the scalars the proof needs.  A position outside the tree or not above its predecessor is
+        counted in d_n_bad (a zeroed device int32/uint32, optional) and makes the length 0.  Asynchronous on the current stream."""
+        f = "merkle_multiproof_device"
+        if arity not in (2, 4):
+            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+        L = _lib.lib()
+        levels, c = 0, n_leaves
+        while c > 1:
+            c = (c + arity - 1) // arity
+            levels += c
+        proof_cap = d_proof.numel() * d_proof.element_size() // 32 if hasattr(d_proof, "element_size") else 0
+        fn = L.p252_merkle4_multiproof_device if arity == 4 else L.p252_merkle2_multiproof_device
+        self._check(fn(self._h, _dev_ptr(self, f, "d_leaves", d_leaves, n_leaves * 32), n_leaves,
+                       _dev_ptr(self, f, "d_levels", d_levels, levels * 32, null_ok=levels == 0),
+                       _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4), k, _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32),
+                       _dev_ptr(self, f, "d_proof", d_proof, proof_cap * 32, null_ok=True), proof_cap,
+                       _dev_ptr(self, f, "d_proof_len", d_proof_len, 8, elem=8),
+                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
+    def merkle_multiproof_verify_device(self, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out=None,
+                                        d_n_hashed=None, d_n_bad=None, arity=4):
+        """checks such a proof with every ancestor hashed ONCE (p252_merkle{4,2}_multiproof_verify_device; tag = that arity's Merkle
+        tag): d_ok (one uint8) = 1 iff no position is bad, the structure that (n_leaves, d_indices) define consumes exactly
+        proof_len scalars of d_proof (None when proof_len == 0), and the recomputed root equals d_root.  Optional outputs: d_root_out
+        (4,) the recomputed root, d_n_hashed (one int64/uint64) the digests computed, d_n_bad (a zeroed int32/uint32) the bad
+        positions.  Asynchronous on the current stream."""
+        f = "merkle_multiproof_verify_device"
+        if arity not in (2, 4):
+            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+        L = _lib.lib()
+        fn = L.p252_merkle4_multiproof_verify_device if arity == 4 else L.p252_merkle2_multiproof_verify_device
+        self._check(fn(self._h, _tag(tag), n_leaves, _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4),
+                       _dev_ptr(self, f, "d_leaves_in", d_leaves_in, k * 32), k,
+                       _dev_ptr(self, f, "d_proof", d_proof, proof_len * 32, null_ok=proof_len == 0), proof_len,
+                       _dev_ptr(self, f, "d_root", d_root, 32), _dev_ptr(self, f, "d_ok", d_ok, 1, elem=1),
+                       _dev_ptr(self, f, "d_root_out", d_root_out, 32, null_ok=True),
+                       _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
+                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
     def merkle2_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
         """re-hash of n arity-2 openings (Domain::Merkle2; pass the Merkle2 tag): d_siblings (n,depth[,1],4), d_positions (n,depth) in 0..1"""
         self._path_batch_device("merkle2_path_batch_device", _lib.lib().p252_merkle2_path_batch_device, 1, tag, d_leaves, d_siblings,

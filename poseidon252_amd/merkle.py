@@ -160,6 +160,44 @@ def merkle4_openings(leaves, levels, indices):
     return sib, pos
 
 
+def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
+    """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
+    as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are
+    sorted and de-duplicated on the device.  Returns (indices (k,) int32, leaves (k, 4), proof (len, 4)), all on the device — what
+    merkle_multiproof_verify takes; one synchronisation, to read the proof's length.  A position outside the tree: ValueError."""
+    import torch
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    n = d_leaves.numel() * d_leaves.element_size() // 32
+    idx = torch.unique(torch.as_tensor(indices, device=dev).to(torch.int64).reshape(-1) & 0xFFFFFFFF).to(torch.int32)  # (sorted)
+    k = idx.numel()
+    if k == 0:
+        raise ValueError("merkle_multiproof: no positions")
+    out = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    proof = torch.empty((ctx.merkle_multiproof_bound(n, k, arity), 4), dtype=torch.int64, device=dev)
+    meta = torch.zeros(2, dtype=torch.int64, device=dev)  # the length; the bad positions (its low 32 bits)
+    ctx.merkle_multiproof_device(d_leaves, n, d_levels if n > 1 else None, idx, k, out, proof if proof.numel() else None, meta[:1],
+                                 meta[1:].view(torch.int32)[:1], arity=arity)
+    length, bad = (int(v) for v in meta.cpu())
+    if bad:
+        raise ValueError("merkle_multiproof: %d position(s) outside the tree (%d leaves)" % (bad, n))
+    return idx, out, proof[:length]
+
+
+def merkle_multiproof_verify(n_leaves, indices, leaves, proof, root, arity=4, tag=None, ctx=None):
+    """True iff (indices, leaves, proof) — torch CUDA tensors as merkle_multiproof returns them — re-hash to `root` (4,) for a tree of
+    n_leaves, every ancestor hashed once (Context.merkle_multiproof_verify_device).  Synchronises to read the verdict."""
+    import torch
+    ctx = ctx or Context.default()
+    if tag is None:
+        tag = merkle4_tag() if arity == 4 else merkle2_tag()
+    ok = torch.zeros(1, dtype=torch.uint8, device=leaves.device)
+    proof_len = proof.numel() * proof.element_size() // 32
+    ctx.merkle_multiproof_verify_device(_as_scalars(tag).reshape(4), n_leaves, indices, leaves, indices.numel(), proof if proof_len else None,
+                                        proof_len, root, ok, arity=arity)
+    return bool(ok.item())
+
+
 def merkle4_path_roots(leaves, siblings, positions, tag=None, ctx=None):
     """Roots recomputed from n openings (numpy host buffers); compare with the tree root to verify."""
     ctx = ctx or Context.default()
