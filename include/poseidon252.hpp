@@ -421,6 +421,30 @@ inline void merkle4_forest_device(const void* d_leaves, std::size_t n_trees, std
                   "merkle4_forest_device");
 }
 
+namespace detail {
+// The p252_merkle{4,2}_* entry points of ONE arity that the functions below call — a member per name of the list, so that no merkle2
+// slot can hold a merkle4 function — and the io-pattern of that arity's node hash (tag(): computed per call, as compute_tag is).
+#define P252_MERKLE_FNS(X, N)                                                                                                                \
+    X(N, levels_len) X(N, depth) X(N, forest_ragged) X(N, forest_ragged_device) X(N, forest_ragged_openings_device) X(N, path_ragged_device) \
+    X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, multiproof_bound) X(N, multiproof_device) X(N, multiproof_verify_device)
+#define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
+#define P252_SYMBOL(N, f) p252_merkle##N##_##f,
+struct MerkleAbi {
+    Domain domain;
+    std::size_t width;
+    P252_MERKLE_FNS(P252_MEMBER, 4)
+    BlsScalar tag() const { return compute_tag(domain, {width}, 1); }
+};
+inline const MerkleAbi& merkle_abi(const char* who, unsigned arity) {
+    static const MerkleAbi merkle4{Domain::Merkle4, 4, P252_MERKLE_FNS(P252_SYMBOL, 4)}, merkle2{Domain::Merkle2, 2, P252_MERKLE_FNS(P252_SYMBOL, 2)};
+    if (arity != 4 && arity != 2) throw std::invalid_argument(std::string(who) + ": arity must be 4 or 2");
+    return arity == 4 ? merkle4 : merkle2;
+}
+#undef P252_MERKLE_FNS
+#undef P252_MEMBER
+#undef P252_SYMBOL
+}  // namespace detail
+
 // Trees of DIFFERENT sizes in one call (p252_merkle{4,2}_forest_ragged): roots[t] = the root of trees[t] alone (what
 // p252_merkle{4,2}_tree returns), one launch per level across all trees.  With want_levels, `levels` is TREE-MAJOR — tree t's
 // block, at level_offsets[t], is byte for byte what the single-tree call writes (not the level-major layout of
@@ -432,7 +456,7 @@ struct RaggedForest {
 };
 inline RaggedForest merkle_forest_ragged(const std::vector<std::vector<BlsScalar>>& trees, unsigned arity = 4, bool want_levels = false,
                                          Context& ctx = Context::default_context()) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged: arity must be 4 or 2");
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged", arity);
     RaggedForest f;
     std::vector<BlsScalar> flat;
     std::vector<std::uint64_t> offsets(1, 0);
@@ -441,17 +465,14 @@ inline RaggedForest merkle_forest_ragged(const std::vector<std::vector<BlsScalar
         if (trees[t].empty()) throw std::invalid_argument("merkle_forest_ragged: tree " + std::to_string(t) + " is empty");
         flat.insert(flat.end(), trees[t].begin(), trees[t].end());
         offsets.push_back(flat.size());
-        const std::size_t ll = arity == 4 ? p252_merkle4_levels_len(trees[t].size()) : p252_merkle2_levels_len(trees[t].size());
-        f.level_offsets.push_back(f.level_offsets.back() + ll);
+        f.level_offsets.push_back(f.level_offsets.back() + m.levels_len(trees[t].size()));
     }
     f.roots.resize(trees.size());
     if (want_levels) f.levels.resize(f.level_offsets.back());
     if (trees.empty()) return f;
-    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
     std::uint64_t* lv = f.levels.empty() ? nullptr : f.levels[0].data();
-    const int rc = arity == 4 ? p252_merkle4_forest_ragged(ctx.get(), tag.data(), flat[0].data(), offsets.data(), trees.size(), f.roots[0].data(), lv)
-                              : p252_merkle2_forest_ragged(ctx.get(), tag.data(), flat[0].data(), offsets.data(), trees.size(), f.roots[0].data(), lv);
-    detail::check(rc, ctx.get(), "merkle_forest_ragged");
+    detail::check(m.forest_ragged(ctx.get(), m.tag().data(), flat[0].data(), offsets.data(), trees.size(), f.roots[0].data(), lv), ctx.get(),
+                  "merkle_forest_ragged");
     if (!want_levels) f.level_offsets.clear();
     return f;
 }
@@ -462,11 +483,9 @@ inline RaggedForest merkle_forest_ragged(const std::vector<std::vector<BlsScalar
 inline void merkle_forest_ragged_device(const void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
                                         std::size_t max_leaves, void* d_roots, unsigned arity = 4, Context& ctx = Context::default_context(),
                                         void* d_levels = nullptr, void* d_n_bad = nullptr, void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_device: arity must be 4 or 2");
-    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
-    auto fn = arity == 4 ? p252_merkle4_forest_ragged_device : p252_merkle2_forest_ragged_device;
-    detail::check(fn(ctx.get(), tag.data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels, d_n_bad, stream), ctx.get(),
-                  "merkle_forest_ragged_device");
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_device", arity);
+    detail::check(m.forest_ragged_device(ctx.get(), m.tag().data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels,
+                                         d_n_bad, stream), ctx.get(), "merkle_forest_ragged_device");
 }
 
 // Openings out of such a forest in one call (p252_merkle{4,2}_forest_ragged_openings_device): opening i = leaf d_leaf_ids[i] (uint64)
@@ -474,17 +493,16 @@ inline void merkle_forest_ragged_device(const void* d_leaves, std::size_t n_leav
 // single leaf).  Outputs at the stride D = forest_openings_stride(max_leaves, arity): d_leaves_out[k], d_siblings[k][D][arity - 1],
 // d_positions[k][D], d_depths[k] (uint8; 0xFF = a bad opening, all zero, counted in *d_n_bad).
 inline std::size_t forest_openings_stride(std::size_t max_leaves, unsigned arity = 4) {
-    return arity == 4 ? p252_merkle4_depth(max_leaves) : p252_merkle2_depth(max_leaves);
+    return detail::merkle_abi("forest_openings_stride", arity).depth(max_leaves);
 }
 inline void merkle_forest_ragged_openings_device(const void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
                                                  std::size_t max_leaves, const void* d_levels, const void* d_tree_ids,
                                                  const void* d_leaf_ids, std::size_t k, void* d_leaves_out, void* d_siblings,
                                                  void* d_positions, void* d_depths, unsigned arity = 4,
                                                  Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_openings_device: arity must be 4 or 2");
-    auto fn = arity == 4 ? p252_merkle4_forest_ragged_openings_device : p252_merkle2_forest_ragged_openings_device;
-    detail::check(fn(ctx.get(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out,
-                     d_siblings, d_positions, d_depths, d_n_bad, stream),
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_openings_device", arity);
+    detail::check(m.forest_ragged_openings_device(ctx.get(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                                  k, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, stream),
                   ctx.get(), "merkle_forest_ragged_openings_device");
 }
 
@@ -493,11 +511,9 @@ inline void merkle_forest_ragged_openings_device(const void* d_leaves, std::size
 inline void merkle_path_ragged_device(const void* d_leaves, const void* d_siblings, const void* d_positions, const void* d_depths,
                                       std::size_t stride_depth, void* d_roots_out, std::size_t k, unsigned arity = 4,
                                       Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_path_ragged_device: arity must be 4 or 2");
-    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
-    auto fn = arity == 4 ? p252_merkle4_path_ragged_device : p252_merkle2_path_ragged_device;
-    detail::check(fn(ctx.get(), tag.data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_roots_out, k, d_n_bad, stream),
-                  ctx.get(), "merkle_path_ragged_device");
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_path_ragged_device", arity);
+    detail::check(m.path_ragged_device(ctx.get(), m.tag().data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_roots_out, k,
+                                       d_n_bad, stream), ctx.get(), "merkle_path_ragged_device");
 }
 
 // `Opening::verify` across a forest (p252_merkle{4,2}_forest_ragged_verify_device): d_ok[i] = 1 iff opening i is well-formed and
@@ -506,12 +522,9 @@ inline void merkle_forest_ragged_verify_device(const void* d_leaves, const void*
                                                std::size_t stride_depth, const void* d_tree_ids, const void* d_roots, std::size_t n_trees,
                                                void* d_ok, std::size_t k, unsigned arity = 4, Context& ctx = Context::default_context(),
                                                void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_verify_device: arity must be 4 or 2");
-    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
-    auto fn = arity == 4 ? p252_merkle4_forest_ragged_verify_device : p252_merkle2_forest_ragged_verify_device;
-    detail::check(fn(ctx.get(), tag.data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids, d_roots, n_trees, d_ok, k,
-                     stream),
-                  ctx.get(), "merkle_forest_ragged_verify_device");
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_verify_device", arity);
+    detail::check(m.forest_ragged_verify_device(ctx.get(), m.tag().data(), d_leaves, d_siblings, d_positions, d_depths, stride_depth, d_tree_ids,
+                                                d_roots, n_trees, d_ok, k, stream), ctx.get(), "merkle_forest_ragged_verify_device");
 }
 
 // Leaf updates anywhere in such a forest in one call (p252_merkle{4,2}_forest_ragged_update_device): update i writes d_new_leaves[i]
@@ -523,29 +536,25 @@ inline void merkle_forest_ragged_update_device(void* d_leaves, std::size_t n_lea
                                                const void* d_new_leaves, std::size_t k, unsigned arity = 4,
                                                Context& ctx = Context::default_context(), void* d_roots = nullptr, void* d_n_bad = nullptr,
                                                void* d_n_hashed = nullptr, void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_forest_ragged_update_device: arity must be 4 or 2");
-    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
-    auto fn = arity == 4 ? p252_merkle4_forest_ragged_update_device : p252_merkle2_forest_ragged_update_device;
-    detail::check(fn(ctx.get(), tag.data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves,
-                     k, d_roots, d_n_bad, d_n_hashed, stream),
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_update_device", arity);
+    detail::check(m.forest_ragged_update_device(ctx.get(), m.tag().data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
+                                                d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_update_device");
 }
 
 // Many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; the format is in poseidon252_hip.h).
 // merkle_multiproof_bound: the most scalars such a proof holds.
 inline std::size_t merkle_multiproof_bound(std::size_t n_leaves, std::size_t k, unsigned arity = 4) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_multiproof_bound: arity must be 4 or 2");
-    return arity == 4 ? p252_merkle4_multiproof_bound(n_leaves, k) : p252_merkle2_multiproof_bound(n_leaves, k);
+    return detail::merkle_abi("merkle_multiproof_bound", arity).multiproof_bound(n_leaves, k);
 }
 // Extraction: d_indices = k strictly ascending uint32 positions; d_leaves_out[k], d_proof (nothing written at or past proof_cap
 // scalars) and *d_proof_len (device uint64: the scalars the proof needs; 0 after a bad position, which *d_n_bad counts).
 inline void merkle_multiproof_device(const void* d_leaves, std::size_t n_leaves, const void* d_levels, const void* d_indices, std::size_t k,
                                      void* d_leaves_out, void* d_proof, std::size_t proof_cap, void* d_proof_len, unsigned arity = 4,
                                      Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_multiproof_device: arity must be 4 or 2");
-    auto fn = arity == 4 ? p252_merkle4_multiproof_device : p252_merkle2_multiproof_device;
-    detail::check(fn(ctx.get(), d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, stream),
-                  ctx.get(), "merkle_multiproof_device");
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_multiproof_device", arity);
+    detail::check(m.multiproof_device(ctx.get(), d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad,
+                                      stream), ctx.get(), "merkle_multiproof_device");
 }
 // Verification, every ancestor hashed once: *d_ok (1 byte) = 1 iff no position is bad, the structure of (n_leaves, d_indices)
 // consumes exactly proof_len scalars and the recomputed root equals *d_root.
@@ -553,12 +562,9 @@ inline void merkle_multiproof_verify_device(std::size_t n_leaves, const void* d_
                                             const void* d_proof, std::size_t proof_len, const void* d_root, void* d_ok, unsigned arity = 4,
                                             Context& ctx = Context::default_context(), void* d_root_out = nullptr,
                                             void* d_n_hashed = nullptr, void* d_n_bad = nullptr, void* stream = nullptr) {
-    if (arity != 4 && arity != 2) throw std::invalid_argument("merkle_multiproof_verify_device: arity must be 4 or 2");
-    const BlsScalar tag = arity == 4 ? compute_tag(Domain::Merkle4, {4}, 1) : compute_tag(Domain::Merkle2, {2}, 1);
-    auto fn = arity == 4 ? p252_merkle4_multiproof_verify_device : p252_merkle2_multiproof_verify_device;
-    detail::check(fn(ctx.get(), tag.data(), n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
-                     d_n_bad, stream),
-                  ctx.get(), "merkle_multiproof_verify_device");
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_multiproof_verify_device", arity);
+    detail::check(m.multiproof_verify_device(ctx.get(), m.tag().data(), n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok,
+                                             d_root_out, d_n_hashed, d_n_bad, stream), ctx.get(), "merkle_multiproof_verify_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

@@ -152,6 +152,85 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _n_scalars(t):  # the BlsScalars a tensor holds
+    return t.numel() * t.element_size() // 32
+
+
+def levels_len(n_leaves, arity=4):  # (public as merkle.levels_len) a tree's upper levels in scalars, as p252_merkle{4,2}_levels_len
+    total, c = 0, n_leaves
+    while c > 1:
+        c = (c + arity - 1) // arity
+        total += c
+    return total
+
+
+class _Arity:
+    """One supported Merkle arity: its C entry points p252_merkle<arity>_<stem> (named once, from _lib.PROTOTYPES; looked up in the
+    library of each call, which tests and P252_LIB_PATH replace), the siblings per level `per`, the domain of its node hash."""
+
+    def __init__(self, arity, domain):
+        self.arity, self.per, self.domain = arity, arity - 1, domain
+        prefix = "p252_merkle%d_" % arity
+        self._names = {name[len(prefix):]: name for name in _lib.PROTOTYPES if name.startswith(prefix)}
+
+    def fn(self, stem):
+        return getattr(_lib.lib(), self._names[stem])
+
+    def depth(self, n_leaves):
+        return int(self.fn("depth")(n_leaves))
+
+    def levels_len(self, n_leaves):
+        return int(self.fn("levels_len")(n_leaves))
+
+    def forest_levels_bytes(self, n_leaves, n_trees, depth):  # of a ragged forest's d_levels: a bound, the offsets are never read back
+        return (n_leaves // self.per + n_trees * depth) * 32
+
+    def tag(self):
+        return compute_tag(self.domain, [self.arity], 1)
+
+
+_ARITIES = {4: _Arity(4, Domain.Merkle4), 2: _Arity(2, Domain.Merkle2)}
+
+
+def _arity(f, arity):
+    if arity not in (2, 4):
+        raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+    return _ARITIES[arity]
+
+
+def _offsets_fit(prefix, off, flat, holds):
+    if off.shape[0] and int(off[-1]) > flat.shape[0]:
+        raise ValueError("%soffsets reach past the %d %s given" % (prefix, flat.shape[0], holds))
+
+
+def _ragged_items(items, prefix, noun, holds, empty, strict=False):
+    """(flat (S, 4) uint64, offsets (n + 1,) uint64, lengths (n,) int64) of a list of (n_i, 4) arrays or of a (flat, offsets) pair with
+    item i = flat[offsets[i]:offsets[i+1]].  Refused, in this order: decreasing offsets, offsets past flat (ValueError: prefix, the items
+    named by `noun`, flat by what it `holds`), an empty item (empty = exception type, prefix); strict: first, arrays other than (u)int64."""
+    def ints(a, what):
+        if strict and np.asarray(a).dtype not in (np.uint64, np.int64):
+            raise ValueError("%s%s must be uint64 or int64, not %s" % (prefix, what, np.asarray(a).dtype))
+        return a
+    if isinstance(items, tuple):
+        flat, off = items
+        flat = _as_scalars(ints(flat, "the " + holds)).reshape(-1, 4)
+        off = np.ascontiguousarray(ints(off, "the offsets"), dtype=np.uint64).reshape(-1)
+        if strict and off.shape[0] == 0:
+            raise ValueError("%soffsets need n_%ss + 1 entries" % (prefix, noun))
+        lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
+        if (lens < 0).any():
+            raise ValueError("%soffsets decrease at %s %d" % (prefix, noun, int(np.argmax(lens < 0))))
+        _offsets_fit(prefix, off, flat, holds)
+    else:
+        parts = [_as_scalars(ints(m, "%s %d" % (noun, i))).reshape(-1, 4) for i, m in enumerate(items)]
+        lens = np.array([p.shape[0] for p in parts], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 4), dtype=np.uint64)
+    if (lens == 0).any():
+        raise empty[0]("%s%s %d is empty" % (empty[1], noun, int(np.argmax(lens == 0))))
+    return flat, off, lens
+
+
 class Context:
     """One `p252_ctx`: bound to one HIP device (one process per GPU)."""
 
@@ -246,25 +325,25 @@ class Context:
         x = _as_scalars(flat).reshape(-1, 4)
         off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
         n = max(off.shape[0] - 1, 0)
-        if n and int(off[-1]) > x.shape[0]:
-            raise ValueError("hash_ragged: offsets reach past the %d scalars given" % x.shape[0])
+        if n:
+            _offsets_fit("hash_ragged: ", off, x, "scalars")
         out = np.empty((n, max(out_len, 0), 4), dtype=np.uint64)
         fn = _lib.lib().p252_hash_ragged_truncated if truncated else _lib.lib().p252_hash_ragged
         self._check(fn(self._h, _ptr(t), t.shape[0], _ptr(x), _ptr(off), out_len, _ptr(out), n))
         return out
 
     def merkle4_tree(self, tag, leaves, want_levels=False):
-        return self._tree(_lib.lib().p252_merkle4_tree, _lib.lib().p252_merkle4_levels_len, tag, leaves, want_levels)
+        return self._tree(_ARITIES[4], tag, leaves, want_levels)
 
     def merkle2_tree(self, tag, leaves, want_levels=False):
         """arity-2 tree over Hash::digest(Domain::Merkle2, [c0, c1]) nodes (hash.rs:27-31)"""
-        return self._tree(_lib.lib().p252_merkle2_tree, _lib.lib().p252_merkle2_levels_len, tag, leaves, want_levels)
+        return self._tree(_ARITIES[2], tag, leaves, want_levels)
 
-    def _tree(self, fn, levels_len, tag, leaves, want_levels):
+    def _tree(self, a, tag, leaves, want_levels):
         lv = _as_scalars(leaves).reshape(-1, 4)
         root = np.empty(4, dtype=np.uint64)
-        levels = np.empty((levels_len(lv.shape[0]), 4), dtype=np.uint64) if want_levels else None
-        self._check(fn(self._h, _tag(tag), _ptr(lv), lv.shape[0], _ptr(root), _ptr(levels) if want_levels else None))
+        levels = np.empty((a.levels_len(lv.shape[0]), 4), dtype=np.uint64) if want_levels else None
+        self._check(a.fn("tree")(self._h, _tag(tag), _ptr(lv), lv.shape[0], _ptr(root), _ptr(levels) if want_levels else None))
         return (root, levels) if want_levels else root
 
     # ---- device buffers (torch CUDA tensors on the context's device; asynchronous on torch's current stream there) ----
@@ -315,10 +394,9 @@ class Context:
         """n_trees independent complete 4^k-leaf trees, tree-major in d_leaves: one launch per level across ALL trees
         (p252_merkle4_forest_device); d_roots (n_trees, 4); d_levels: level-major, n_trees * levels_len(leaves_per_tree) scalars"""
         f = "merkle4_forest_device"
-        L = _lib.lib()
-        ll = L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len
-        levels = n_trees * ll(leaves_per_tree) * 32 if d_levels is not None else 0
-        fn = L.p252_merkle4_forest_device if arity == 4 else L.p252_merkle2_forest_device
+        a = _arity(f, arity)
+        levels = n_trees * a.levels_len(leaves_per_tree) * 32 if d_levels is not None else 0
+        fn = a.fn("forest_device")
         self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n_trees * leaves_per_tree * 32), n_trees, leaves_per_tree,
                        _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_levels", d_levels, levels, null_ok=True),
                        _stream(self)))
@@ -327,21 +405,17 @@ class Context:
         """trees of different sizes from host buffers (p252_merkle{4,2}_forest_ragged): tree t = flat[offsets[t]:offsets[t+1]].
         Returns roots (n_trees, 4) and, with want_levels, the tree-major levels (sum of levels_len(n_t) scalars).  The library
         checks every tree first (empty, decreasing offsets -> ValueError)."""
-        if arity not in (2, 4):
-            raise ValueError("merkle_forest_ragged: arity must be 4 or 2, not %r" % (arity,))
+        a = _arity("merkle_forest_ragged", arity)
         x = _as_scalars(flat).reshape(-1, 4)
         off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
         n = max(off.shape[0] - 1, 0)
-        if n and int(off[-1]) > x.shape[0]:
-            raise ValueError("merkle_forest_ragged: offsets reach past the %d scalars given" % x.shape[0])
-        L = _lib.lib()
-        ll = L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len
+        if n:
+            _offsets_fit("merkle_forest_ragged: ", off, x, "scalars")
         lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
-        n_levels = sum(ll(int(c)) for c in lens if c > 0) if want_levels else 0
+        n_levels = sum(a.levels_len(int(c)) for c in lens if c > 0) if want_levels else 0
         roots = np.empty((n, 4), dtype=np.uint64)
         levels = np.empty((n_levels, 4), dtype=np.uint64) if want_levels else None
-        fn = L.p252_merkle4_forest_ragged if arity == 4 else L.p252_merkle2_forest_ragged
-        self._check(fn(self._h, _tag(tag), _ptr(x), _ptr(off), n, _ptr(roots), _ptr(levels) if n_levels else None))
+        self._check(a.fn("forest_ragged")(self._h, _tag(tag), _ptr(x), _ptr(off), n, _ptr(roots), _ptr(levels) if n_levels else None))
         return (roots, levels) if want_levels else roots
 
     def merkle_forest_ragged_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels=None, d_n_bad=None, arity=4):
@@ -351,14 +425,11 @@ class Context:
         are never read back to the host.  Bad trees get zero roots and increment d_n_bad (a zeroed device int32/uint32,
         optional)."""
         f = "merkle_forest_ragged_device"
-        if arity not in (2, 4):
-            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
-        L = _lib.lib()
+        a = _arity(f, arity)
         leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 0)
-        n_leaves = d_leaves.numel() * d_leaves.element_size() // 32
-        depth = L.p252_merkle4_depth(max_leaves) if arity == 4 else L.p252_merkle2_depth(max_leaves)
-        need = (n_leaves // (arity - 1) + n_trees * depth) * 32 if d_levels is not None else 0
-        fn = L.p252_merkle4_forest_ragged_device if arity == 4 else L.p252_merkle2_forest_ragged_device
+        n_leaves = _n_scalars(d_leaves)
+        need = a.forest_levels_bytes(n_leaves, n_trees, a.depth(max_leaves)) if d_levels is not None else 0
+        fn = a.fn("forest_ragged_device")
         self._check(fn(self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8),
                        n_trees, max_leaves, _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32),
                        _dev_ptr(self, f, "d_levels", d_levels, need, null_ok=True),
@@ -374,14 +445,12 @@ class Context:
         out = (d_leaves_out, d_siblings, d_positions, d_depths) writes into caller-owned tensors (no allocation per call)."""
         import torch
         f = "merkle_forest_ragged_openings_device"
-        if arity not in (2, 4):
-            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
-        L = _lib.lib()
+        a = _arity(f, arity)
         leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = d_leaves.numel() * d_leaves.element_size() // 32
-        depth = int((L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(max_leaves))
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
         offsets = _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8)
-        levels = _dev_ptr(self, f, "d_levels", d_levels, (n_leaves // (arity - 1) + n_trees * depth) * 32, null_ok=depth == 0)
+        levels = _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0)
         tree_ids = _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4)
         leaf_ids = _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8)
         if out is not None:
@@ -389,25 +458,21 @@ class Context:
         else:
             dev = d_leaves.device
             lv = torch.empty((k, 4), dtype=torch.int64, device=dev)
-            sib = torch.empty((k, depth, arity - 1, 4), dtype=torch.int64, device=dev)
+            sib = torch.empty((k, depth, a.per, 4), dtype=torch.int64, device=dev)
             pos = torch.empty((k, depth), dtype=torch.uint8, device=dev)
             dep = torch.empty((k,), dtype=torch.uint8, device=dev)
-        fn = L.p252_merkle4_forest_ragged_openings_device if arity == 4 else L.p252_merkle2_forest_ragged_openings_device
-        self._check(fn(self._h, leaves, n_leaves, offsets, n_trees, max_leaves, levels, tree_ids, leaf_ids, k,
-                       _dev_ptr(self, f, "d_leaves_out", lv, k * 32),
-                       _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * (arity - 1)) if depth else None,
-                       _dev_ptr(self, f, "d_positions", pos, k * depth, elem=1) if depth else None,
-                       _dev_ptr(self, f, "d_depths", dep, k, elem=1), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
-                       _stream(self)))
+        self._check(a.fn("forest_ragged_openings_device")(
+            self._h, leaves, n_leaves, offsets, n_trees, max_leaves, levels, tree_ids, leaf_ids, k,
+            _dev_ptr(self, f, "d_leaves_out", lv, k * 32), _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * a.per) if depth else None,
+            _dev_ptr(self, f, "d_positions", pos, k * depth, elem=1) if depth else None, _dev_ptr(self, f, "d_depths", dep, k, elem=1),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
         return lv, sib, pos, dep, depth
 
-    def _ragged_opening_ptrs(self, f, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, arity):
-        if arity not in (2, 4):
-            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
+    def _ragged_opening_ptrs(self, f, a, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k):
         if not 0 <= stride_depth <= 64:
             raise ValueError("%s: stride_depth must be in 0 .. 64, not %r" % (f, stride_depth))
         return (_dev_ptr(self, f, "d_leaves", d_leaves, k * 32),
-                _dev_ptr(self, f, "d_siblings", d_siblings, k * stride_depth * (arity - 1) * 32) if stride_depth else None,
+                _dev_ptr(self, f, "d_siblings", d_siblings, k * stride_depth * a.per * 32) if stride_depth else None,
                 _dev_ptr(self, f, "d_positions", d_positions, k * stride_depth, elem=1) if stride_depth else None,
                 _dev_ptr(self, f, "d_depths", d_depths, k, elem=1))
 
@@ -416,8 +481,9 @@ class Context:
         (uint8) levels of opening i in the layout merkle_forest_ragged_openings_device writes, at stride stride_depth.  A depth
         above the stride (0xFF: a bad opening) gives a zero root and is counted in d_n_bad (zeroed device int32/uint32, optional)."""
         f = "merkle_path_ragged_device"
-        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, arity)
-        fn = _lib.lib().p252_merkle4_path_ragged_device if arity == 4 else _lib.lib().p252_merkle2_path_ragged_device
+        a = _arity(f, arity)
+        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, a, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k)
+        fn = a.fn("path_ragged_device")
         self._check(fn(self._h, _tag(tag), leaves, sib, pos, dep, stride_depth, _dev_ptr(self, f, "d_roots", d_roots, k * 32), k,
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
@@ -426,8 +492,9 @@ class Context:
         """`Opening::verify` across a forest (p252_merkle{4,2}_forest_ragged_verify_device): d_ok[i] (uint8) = 1 iff opening i is
         well-formed and re-hashes to d_roots[d_tree_ids[i]], the root of ITS tree; k bytes come back"""
         f = "merkle_forest_ragged_verify_device"
-        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, arity)
-        fn = _lib.lib().p252_merkle4_forest_ragged_verify_device if arity == 4 else _lib.lib().p252_merkle2_forest_ragged_verify_device
+        a = _arity(f, arity)
+        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, a, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k)
+        fn = a.fn("forest_ragged_verify_device")
         self._check(fn(self._h, _tag(tag), leaves, sib, pos, dep, stride_depth, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
                        _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=n_trees == 0), n_trees,
                        _dev_ptr(self, f, "d_ok", d_ok, k, elem=1), k, _stream(self)))
@@ -441,20 +508,17 @@ class Context:
         the touched trees only.  A bad update writes nothing and is counted in d_n_bad (a zeroed device int32/uint32, optional);
         d_n_hashed (a zeroed device int64/uint64, optional) grows by the number of digests computed."""
         f = "merkle_forest_ragged_update_device"
-        if arity not in (2, 4):
-            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
-        L = _lib.lib()
+        a = _arity(f, arity)
         leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = d_leaves.numel() * d_leaves.element_size() // 32
-        depth = int((L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(max_leaves))
-        fn = L.p252_merkle4_forest_ragged_update_device if arity == 4 else L.p252_merkle2_forest_ragged_update_device
-        self._check(fn(self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees,
-                       max_leaves, _dev_ptr(self, f, "d_levels", d_levels, (n_leaves // (arity - 1) + n_trees * depth) * 32, null_ok=depth == 0),
-                       _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
-                       _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32), k,
-                       _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
-                       _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
-                       _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        self._check(a.fn("forest_ragged_update_device")(
+            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
+            _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32), k, _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
@@ -514,27 +578,23 @@ class Context:
         arity=2: a Merkle2 tree (p252_merkle2_openings_device): one sibling per level, d_siblings (k,depth,1,4)."""
         import torch
         f = "merkle4_openings_device"
-        if arity not in (2, 4):
-            raise ValueError("%s: arity is 2 or 4, not %r" % (f, arity))
-        L = _lib.lib()
-        depth = int((L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(n_leaves))
-        ll = (L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len)(n_leaves)
+        a = _arity(f, arity)
+        depth = a.depth(n_leaves)
         leaves = _dev_ptr(self, f, "d_leaves", d_leaves, n_leaves * 32)
-        levels = _dev_ptr(self, f, "d_levels", d_levels, ll * 32) if depth else None
+        levels = _dev_ptr(self, f, "d_levels", d_levels, a.levels_len(n_leaves) * 32) if depth else None
         indices = _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4)
         if out is not None:
             out, sib, pos, bad = out
         else:
             dev = d_leaves.device
             out = torch.empty((k, 4), dtype=torch.int64, device=dev)
-            sib = torch.empty((k, depth, arity - 1, 4), dtype=torch.int64, device=dev)
+            sib = torch.empty((k, depth, a.per, 4), dtype=torch.int64, device=dev)
             pos = torch.empty((k, depth), dtype=torch.uint8, device=dev)
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        fn = L.p252_merkle4_openings_device if arity == 4 else L.p252_merkle2_openings_device
-        self._check(fn(self._h, leaves, n_leaves, levels, indices, k, _dev_ptr(self, f, "d_leaves_out", out, k * 32),
-                       _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * (arity - 1)) if depth else None,
-                       _dev_ptr(self, f, "d_positions", pos, k * depth) if depth else None, _dev_ptr(self, f, "d_n_bad", bad, 4),
-                       _stream(self)))
+        self._check(a.fn("openings_device")(
+            self._h, leaves, n_leaves, levels, indices, k, _dev_ptr(self, f, "d_leaves_out", out, k * 32),
+            _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * a.per) if depth else None,
+            _dev_ptr(self, f, "d_positions", pos, k * depth) if depth else None, _dev_ptr(self, f, "d_n_bad", bad, 4), _stream(self)))
         if check and int(bad.item()):
             raise ValueError("merkle4_openings: %d position(s) outside the tree" % int(bad.item()))
         return out, sib, pos, depth
@@ -542,10 +602,7 @@ class Context:
     # ---- many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; csrc/multiproof.hip) ----
     def merkle_multiproof_bound(self, n_leaves, k, arity=4):
         """upper bound, in scalars, of the shared proof of k leaves of a tree of n_leaves (p252_merkle{4,2}_multiproof_bound)"""
-        if arity not in (2, 4):
-            raise ValueError("merkle_multiproof_bound: arity must be 4 or 2, not %r" % (arity,))
-        L = _lib.lib()
-        return int((L.p252_merkle4_multiproof_bound if arity == 4 else L.p252_merkle2_multiproof_bound)(n_leaves, k))
+        return int(_arity("merkle_multiproof_bound", arity).fn("multiproof_bound")(n_leaves, k))
 
     def merkle_multiproof_device(self, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, d_proof_len, d_n_bad=None,
                                  arity=4):
@@ -555,15 +612,10 @@ class Context:
         d_proof_len (one int64/uint64) the scalars the proof needs.  A position outside the tree or not above its predecessor is
         counted in d_n_bad (a zeroed device int32/uint32, optional) and makes the length 0.  Asynchronous on the current stream."""
         f = "merkle_multiproof_device"
-        if arity not in (2, 4):
-            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
-        L = _lib.lib()
-        levels, c = 0, n_leaves
-        while c > 1:
-            c = (c + arity - 1) // arity
-            levels += c
-        proof_cap = d_proof.numel() * d_proof.element_size() // 32 if hasattr(d_proof, "element_size") else 0
-        fn = L.p252_merkle4_multiproof_device if arity == 4 else L.p252_merkle2_multiproof_device
+        a = _arity(f, arity)
+        levels = levels_len(n_leaves, arity)
+        proof_cap = _n_scalars(d_proof) if hasattr(d_proof, "element_size") else 0
+        fn = a.fn("multiproof_device")
         self._check(fn(self._h, _dev_ptr(self, f, "d_leaves", d_leaves, n_leaves * 32), n_leaves,
                        _dev_ptr(self, f, "d_levels", d_levels, levels * 32, null_ok=levels == 0),
                        _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4), k, _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32),
@@ -579,10 +631,7 @@ class Context:
         (4,) the recomputed root, d_n_hashed (one int64/uint64) the digests computed, d_n_bad (a zeroed int32/uint32) the bad
         positions.  Asynchronous on the current stream."""
         f = "merkle_multiproof_verify_device"
-        if arity not in (2, 4):
-            raise ValueError("%s: arity must be 4 or 2, not %r" % (f, arity))
-        L = _lib.lib()
-        fn = L.p252_merkle4_multiproof_verify_device if arity == 4 else L.p252_merkle2_multiproof_verify_device
+        fn = _arity(f, arity).fn("multiproof_verify_device")
         self._check(fn(self._h, _tag(tag), n_leaves, _dev_ptr(self, f, "d_indices", d_indices, k * 4, elem=4),
                        _dev_ptr(self, f, "d_leaves_in", d_leaves_in, k * 32), k,
                        _dev_ptr(self, f, "d_proof", d_proof, proof_len * 32, null_ok=proof_len == 0), proof_len,
@@ -593,30 +642,26 @@ class Context:
 
     def merkle2_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
         """re-hash of n arity-2 openings (Domain::Merkle2; pass the Merkle2 tag): d_siblings (n,depth[,1],4), d_positions (n,depth) in 0..1"""
-        self._path_batch_device("merkle2_path_batch_device", _lib.lib().p252_merkle2_path_batch_device, 1, tag, d_leaves, d_siblings,
-                                d_positions, depth, d_roots, n)
+        self._path_batch_device("merkle2_path_batch_device", _ARITIES[2], tag, d_leaves, d_siblings, d_positions, depth, d_roots, n)
 
     def merkle4_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
-        self._path_batch_device("merkle4_path_batch_device", _lib.lib().p252_merkle4_path_batch_device, 3, tag, d_leaves, d_siblings,
-                                d_positions, depth, d_roots, n)
+        self._path_batch_device("merkle4_path_batch_device", _ARITIES[4], tag, d_leaves, d_siblings, d_positions, depth, d_roots, n)
 
-    def _path_batch_device(self, f, fn, per, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
-        """per = siblings per level (arity - 1)"""
-        self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
-                       _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * per * 32) if depth else None,
-                       _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
-                       _dev_ptr(self, f, "d_roots", d_roots, n * 32), n, _stream(self)))
+    def _path_batch_device(self, f, a, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
+        self._check(a.fn("path_batch_device")(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
+            _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * a.per * 32) if depth else None,
+            _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
+            _dev_ptr(self, f, "d_roots", d_roots, n * 32), n, _stream(self)))
 
     def merkle_verify_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_root, d_ok, n, arity=4):
         """`Opening::verify` in bulk (the downstream poseidon-merkle verifier, AGENTS.md:62-66): d_ok[i] (uint8) = 1 iff opening i
         re-hashes to the ONE root at d_root — p252_merkle{4,2}_verify_batch_device; n bytes come back instead of n x 32"""
         f = "merkle_verify_batch_device"
-        per = 3 if arity == 4 else 1
-        fn = _lib.lib().p252_merkle4_verify_batch_device if arity == 4 else _lib.lib().p252_merkle2_verify_batch_device
-        self._check(fn(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
-                       _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * per * 32) if depth else None,
-                       _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
-                       _dev_ptr(self, f, "d_root", d_root, 32), _dev_ptr(self, f, "d_ok", d_ok, n), n, _stream(self)))
+        a = _arity(f, arity)
+        self._check(a.fn("verify_batch_device")(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
+            _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * a.per * 32) if depth else None,
+            _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
+            _dev_ptr(self, f, "d_root", d_root, 32), _dev_ptr(self, f, "d_ok", d_ok, n), n, _stream(self)))
 
     # ---- measurement aid: the shader clock (bench.py) ----
     def clock_probe(self, spin_us=1000, stream=None):
@@ -797,7 +842,7 @@ class HashBatch:
     def digest(self, scalars, out=None, truncated=False):
         if _is_torch(scalars):
             import torch
-            n = scalars.numel() * scalars.element_size() // (self.item_len * 32)
+            n = _n_scalars(scalars) // self.item_len
             if out is None:
                 out = torch.empty((n, self.out_len, 4), dtype=torch.int64, device=scalars.device)
             self.ctx.hash_batch_device(self.tag, scalars, self.item_len, self.out_len, out, n, truncated=truncated)
@@ -861,24 +906,9 @@ class RaggedHashBatch:
 
     @staticmethod
     def _host_messages(messages):
-        """-> (flat (S, 4), offsets (n + 1,) uint64), lengths validated like check_io_pattern"""
-        if isinstance(messages, tuple):
-            flat, off = messages
-            flat = _as_scalars(flat).reshape(-1, 4)
-            off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
-            lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
-            if (lens < 0).any():
-                raise ValueError("poseidon252_hip: invalid argument — offsets decrease at message %d" % int(np.argmax(lens < 0)))
-            if off.shape[0] and int(off[-1]) > flat.shape[0]:
-                raise ValueError("poseidon252_hip: invalid argument — offsets reach past the %d scalars given" % flat.shape[0])
-        else:
-            parts = [_as_scalars(m).reshape(-1, 4) for m in messages]
-            lens = np.array([p.shape[0] for p in parts], dtype=np.int64)
-            off = np.zeros(len(parts) + 1, dtype=np.uint64)
-            np.cumsum(lens, out=off[1:])
-            flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 4), dtype=np.uint64)
-        if (lens == 0).any():  # a zero-length absorb (dusk-safe rejects it; Hash::finalize panics, hash.rs:134-137)
-            raise InvalidIOPattern("at this point the io-pattern is valid: InvalidIOPattern — message %d is empty" % int(np.argmax(lens == 0)))
+        """-> (flat (S, 4), offsets (n + 1,) uint64, the longest length), validated like check_io_pattern (an empty absorb: hash.rs:134-137)"""
+        flat, off, lens = _ragged_items(messages, "poseidon252_hip: invalid argument — ", "message", "scalars",
+                                        (InvalidIOPattern, "at this point the io-pattern is valid: InvalidIOPattern — "))
         return flat, off, (int(lens.max()) if lens.size else 0)
 
     def digest(self, messages, max_len=None, out=None, d_n_bad=None, truncated=False):

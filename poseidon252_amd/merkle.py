@@ -11,23 +11,15 @@ parent's children; `merkle4_path_roots` re-hashes n such branches in one kernel 
 """
 import numpy as np
 
-from .hash import Context, Domain, compute_tag, _as_scalars, _is_torch
+from .hash import Context, levels_len, _ARITIES, _arity, _as_scalars, _is_torch, _n_scalars, _ragged_items  # noqa: F401 (levels_len: public here)
 
 
 def merkle4_tag():
-    return compute_tag(Domain.Merkle4, [4], 1)
+    return _ARITIES[4].tag()
 
 
 def merkle2_tag():
-    return compute_tag(Domain.Merkle2, [2], 1)
-
-
-def levels_len(n_leaves, arity=4):
-    total, c = 0, n_leaves
-    while c > 1:
-        c = (c + arity - 1) // arity
-        total += c
-    return total
+    return _ARITIES[2].tag()
 
 
 def permutations(n_leaves):
@@ -42,7 +34,7 @@ def merkle4_tree(leaves, tag=None, ctx=None, want_levels=False):
     tag = merkle4_tag() if tag is None else _as_scalars(tag).reshape(4)
     if _is_torch(leaves):
         import torch
-        n = leaves.numel() * leaves.element_size() // 32
+        n = _n_scalars(leaves)
         root = torch.empty(4, dtype=torch.int64, device=leaves.device)
         levels = torch.empty((max(levels_len(n), 1), 4), dtype=torch.int64, device=leaves.device) if want_levels else None
         ctx.merkle4_tree_device(tag, leaves, n, root, levels)
@@ -61,7 +53,7 @@ def merkle4_forest(leaves, leaves_per_tree, tag=None, ctx=None, want_levels=Fals
         return ctx.merkle4_forest(tag, leaves, leaves_per_tree)
     import torch
     d = leaves if dev_in else torch.from_numpy(_as_scalars(leaves).reshape(-1, 4).view(np.int64)).to("cuda:%d" % ctx.device)
-    n = d.numel() * d.element_size() // 32
+    n = _n_scalars(d)
     if leaves_per_tree < 1 or n % leaves_per_tree:
         raise ValueError("forest: %d leaves are not a whole number of %d-leaf trees" % (n, leaves_per_tree))
     n_trees = n // leaves_per_tree
@@ -75,36 +67,10 @@ def merkle4_forest(leaves, leaves_per_tree, tag=None, ctx=None, want_levels=Fals
     return (roots, levels) if want_levels else roots
 
 
-def _integer_array(a, what):
-    a = np.asarray(a)
-    if a.dtype not in (np.uint64, np.int64):
-        raise ValueError("merkle_forest_ragged: %s must be uint64 or int64, not %s" % (what, a.dtype))
-    return a
-
-
 def _forest_trees(trees):
-    """(flat (S, 4) uint64, offsets (n_trees + 1,) uint64) of a list of (n_t, 4) leaf arrays or of a (flat, offsets) pair, as
+    """(flat (S, 4) uint64, offsets (n_trees + 1,) uint64, leaf counts) of a list of (n_t, 4) leaf arrays or of a (flat, offsets) pair, as
     RaggedHashBatch takes messages; every tree is checked here (dtype, empty, decreasing offsets, extent) before any device work"""
-    if isinstance(trees, tuple):
-        flat, off = trees
-        flat = _as_scalars(_integer_array(flat, "the leaves")).reshape(-1, 4)
-        off = np.ascontiguousarray(_integer_array(off, "the offsets"), dtype=np.uint64).reshape(-1)
-        if off.shape[0] == 0:
-            raise ValueError("merkle_forest_ragged: offsets need n_trees + 1 entries")
-        lens = off[1:].astype(np.int64) - off[:-1].astype(np.int64)
-        if (lens < 0).any():
-            raise ValueError("merkle_forest_ragged: offsets decrease at tree %d" % int(np.argmax(lens < 0)))
-        if int(off[-1]) > flat.shape[0]:
-            raise ValueError("merkle_forest_ragged: offsets reach past the %d leaves given" % flat.shape[0])
-    else:
-        parts = [_as_scalars(_integer_array(t, "tree %d" % i)).reshape(-1, 4) for i, t in enumerate(trees)]
-        lens = np.array([p.shape[0] for p in parts], dtype=np.int64)
-        off = np.zeros(len(parts) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=off[1:])
-        flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 4), dtype=np.uint64)
-    if (lens == 0).any():
-        raise ValueError("merkle_forest_ragged: tree %d is empty" % int(np.argmax(lens == 0)))
-    return flat, off, lens
+    return _ragged_items(trees, "merkle_forest_ragged: ", "tree", "leaves", (ValueError, "merkle_forest_ragged: "), strict=True)
 
 
 def merkle_forest_ragged(trees, arity=4, tag=None, ctx=None, want_levels=False):
@@ -114,14 +80,11 @@ def merkle_forest_ragged(trees, arity=4, tag=None, ctx=None, want_levels=False):
     uint64; with want_levels also (levels, level_offsets): levels tree-major — tree t's block, at level_offsets[t], is byte for
     byte what the single-tree call writes (unlike merkle4_forest's level-major layout) — and level_offsets the n_trees + 1
     prefix sums of levels_len(n_t, arity)."""
-    if arity not in (2, 4):
-        raise ValueError("merkle_forest_ragged: arity must be 4 or 2, not %r" % (arity,))
+    a = _arity("merkle_forest_ragged", arity)
     flat, off, lens = _forest_trees(trees)
     level_offsets = np.zeros(lens.shape[0] + 1, dtype=np.uint64)
     np.cumsum([levels_len(int(n), arity) for n in lens], out=level_offsets[1:])
-    if tag is None:
-        tag = merkle4_tag() if arity == 4 else merkle2_tag()
-    tag = _as_scalars(tag).reshape(4)
+    tag = _as_scalars(a.tag() if tag is None else tag).reshape(4)
     if lens.shape[0] == 0:
         roots = np.zeros((0, 4), dtype=np.uint64)
         return (roots, np.zeros((0, 4), dtype=np.uint64), level_offsets) if want_levels else roots
@@ -168,7 +131,7 @@ def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     import torch
     ctx = ctx or Context.default()
     dev = d_leaves.device
-    n = d_leaves.numel() * d_leaves.element_size() // 32
+    n = _n_scalars(d_leaves)
     idx = torch.unique(torch.as_tensor(indices, device=dev).to(torch.int64).reshape(-1) & 0xFFFFFFFF).to(torch.int32)  # (sorted)
     k = idx.numel()
     if k == 0:
@@ -189,10 +152,10 @@ def merkle_multiproof_verify(n_leaves, indices, leaves, proof, root, arity=4, ta
     n_leaves, every ancestor hashed once (Context.merkle_multiproof_verify_device).  Synchronises to read the verdict."""
     import torch
     ctx = ctx or Context.default()
-    if tag is None:
-        tag = merkle4_tag() if arity == 4 else merkle2_tag()
+    if tag is None:  # (an arity that is neither is refused in the name of the call below, which refused it before)
+        tag = _arity("merkle_multiproof_verify_device", arity).tag()
     ok = torch.zeros(1, dtype=torch.uint8, device=leaves.device)
-    proof_len = proof.numel() * proof.element_size() // 32
+    proof_len = _n_scalars(proof)
     ctx.merkle_multiproof_verify_device(_as_scalars(tag).reshape(4), n_leaves, indices, leaves, indices.numel(), proof if proof_len else None,
                                         proof_len, root, ok, arity=arity)
     return bool(ok.item())
