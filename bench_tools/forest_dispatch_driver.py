@@ -2,7 +2,10 @@
 """Calls the ten ragged-forest entry points once each per shape, for a kernel trace: p252_merkle{4,2}_forest_ragged_device with and
 without d_levels, ..._forest_ragged_openings_device, ..._path_ragged_device, ..._forest_ragged_verify_device and
 ..._forest_ragged_update_device, on a small forest (every level on the 8-lane-group digests) and a large one (the low levels on
-the one-lane digests, the narrow top levels on the groups), with few and with many updates.
+the one-lane digests, the narrow top levels on the groups), with few and with many updates.  Then the other calls that work in the
+context's per-stream scratch, at one small and one chip-filling shape each: p252_hash_ragged_device, root-only
+p252_merkle{4,2}_tree_device and p252_merkle{4,2}_forest_device, p252_merkle{4,2}_verify_batch_device and
+p252_merkle{4,2}_multiproof[_verify]_device.
 
   rocprofv3 --kernel-trace -d DIR -o NAME --output-format csv -- python bench_tools/forest_dispatch_driver.py
   python bench_tools/forest_dispatch_driver.py --dispatches DIR/.../NAME_kernel_trace.csv     # the ordered dispatch list
@@ -20,6 +23,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 
 
 def dispatches(path):
@@ -66,6 +70,8 @@ def run(ctx, arity, sizes, ks, seed):
     for k in ks:
         tid = rng.integers(0, n_trees, k)
         lid = (rng.random(k) * sizes[tid]).astype(np.int64)
+        pairs = np.unique(tid.astype(np.int64) << 32 | lid)  # the update call wants distinct (tree, leaf) pairs: a pair drawn twice
+        tid, lid, k = pairs >> 32, pairs & 0xffffffff, pairs.size  # with two values leaves whichever landed, and its opening may not verify
         d_tid, d_lid = _dev(tid.astype(np.uint32)), _dev(lid.astype(np.uint64))
         out = (torch.empty((k, 4), dtype=torch.int64, device=dev), torch.empty((k, D, arity - 1, 4), dtype=torch.int64, device=dev),
                torch.empty((k, D), dtype=torch.uint8, device=dev), torch.empty((k,), dtype=torch.uint8, device=dev))
@@ -87,6 +93,54 @@ def run(ctx, arity, sizes, ks, seed):
     print("arity %d, %d trees, %d leaves, depth %d, k = %s: ok" % (arity, n_trees, n_leaves, D, list(ks)))
 
 
+def run_hash_ragged(ctx, n, max_len):
+    import torch
+    from poseidon252_amd import hash as H
+    lens = 1 + np.arange(n) % max_len
+    off = np.zeros(n + 1, np.uint64)
+    np.cumsum(lens.astype(np.uint64), out=off[1:])
+    d_in = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device="cuda:0")
+    out = torch.empty((n, 1, 4), dtype=torch.int64, device="cuda:0")
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+    ctx.hash_ragged_device(_dev(H.ragged_tags(H.Domain.Other, 1, max_len)), max_len, d_in, _dev(off), 1, out, n, d_n_bad=bad)
+    torch.cuda.synchronize()
+    assert int(bad) == 0
+    print("hash_ragged, %d messages of 1 .. %d scalars: ok" % (n, max_len))
+
+
+def run_tree_families(ctx, arity, n_leaves, k, n_trees, per):
+    """root-only tree and equal-size forest; k openings of the stored tree verified in bulk; a shared proof of k leaves, verified"""
+    import torch
+    from multiproof_bench import tree_device
+    from poseidon252_amd import levels_len
+    from poseidon252_amd import merkle as M
+    dev = torch.device("cuda:0")
+    tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
+    d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
+    root, root2 = (torch.empty(4, dtype=torch.int64, device=dev) for _ in range(2))
+    d_lv = torch.empty((levels_len(n_leaves, arity), 4), dtype=torch.int64, device=dev)
+    tree_device(ctx, arity, tag, d, n_leaves, root, None)   # root only: the scratch pair
+    tree_device(ctx, arity, tag, d, n_leaves, root2, d_lv)  # stored
+    f_leaves = torch.randint(0, 1 << 60, (n_trees * per, 4), dtype=torch.int64, device=dev)
+    f_roots = torch.empty((n_trees, 4), dtype=torch.int64, device=dev)
+    ctx.merkle4_forest_device(tag, f_leaves, n_trees, per, f_roots, arity=arity)
+    idx = np.sort(np.random.default_rng(7).permutation(n_leaves)[:k]).astype(np.uint32)
+    d_idx = _dev(idx)
+    o_l, o_s, o_p, depth = ctx.merkle4_openings_device(d, n_leaves, d_lv, d_idx, k, arity=arity)
+    ok = torch.zeros(k, dtype=torch.uint8, device=dev)
+    ctx.merkle_verify_batch_device(tag, o_l, o_s, o_p, depth, root2, ok, k, arity=arity)
+    m_l = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    m_p = torch.empty((ctx.merkle_multiproof_bound(n_leaves, k, arity=arity), 4), dtype=torch.int64, device=dev)
+    m_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    ctx.merkle_multiproof_device(d, n_leaves, d_lv, d_idx, k, m_l, m_p, m_len, arity=arity)
+    m_ok = torch.zeros(1, dtype=torch.uint8, device=dev)
+    ctx.merkle_multiproof_verify_device(tag, n_leaves, d_idx, m_l, k, m_p, int(m_len), root2, m_ok, arity=arity)
+    torch.cuda.synchronize()
+    assert torch.equal(root, root2), "the two tree builds disagree"
+    assert int(ok.sum()) == k and int(m_ok) == 1, "%d of %d openings verify, the shared proof: %d" % (int(ok.sum()), k, int(m_ok))
+    print("arity %d, tree of %d leaves, k = %d, forest of %d x %d: ok" % (arity, n_leaves, k, n_trees, per))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dispatches", metavar="CSV", help="print the ordered dispatch list of a rocprofv3 kernel trace and exit")
@@ -101,6 +155,11 @@ def main():
     for arity in (4, 2):
         run(ctx, arity, small, (50,), 1)
         run(ctx, arity, large, (50, 40000), 2)
+    run_hash_ragged(ctx, 200, 40)
+    run_hash_ragged(ctx, 70000, 8)                  # past the chip's 65,536 lanes
+    for arity in (4, 2):
+        run_tree_families(ctx, arity, 1000, 37, 64, 16)
+        run_tree_families(ctx, arity, 4 ** 10, 70000, 4096, 4 ** 4)  # first levels past 65,536 nodes: the padded narrow levels too
 
 
 if __name__ == "__main__":

@@ -51,7 +51,9 @@ int p252host::ensure(p252_ctx* ctx, void** buf, size_t* cap, size_t need) {
     return P252_OK;
 }
 
-int p252host::level_set(p252_ctx* ctx, hipStream_t st, size_t need0, size_t need1, p252_ctx::LevelSet** out) {
+// the scratch pair of a call on `st` (at least need0 / need1 bytes) and, below, the record of its event behind the call's last launch:
+// used through with_stream_scratch only
+static int level_set(p252_ctx* ctx, hipStream_t st, size_t need0, size_t need1, p252_ctx::LevelSet** out) {
     p252_ctx::LevelSet* set = nullptr;
     for (auto& s : ctx->lvl)
         if (s.st == st) set = &s;
@@ -81,39 +83,32 @@ int p252host::level_set(p252_ctx* ctx, hipStream_t st, size_t need0, size_t need
     return P252_OK;
 }
 
-int p252host::level_set_done(p252_ctx* ctx, p252_ctx::LevelSet* set) {
+static int level_set_done(p252_ctx* ctx, p252_ctx::LevelSet* set) {
     set->stamp = ++ctx->lvl_clock;
     HIP_TRY(ctx, hipEventRecord(set->done, set->st));
     return P252_OK;
 }
 
 namespace {
-// Records the pair's event on EVERY way out of a builder — also when a launch failed half way: the launches before it are queued and
-// touch the pair, and a later takeover by another stream waits on this event (the early returns used to skip it and
-// left the event of an OLDER build for the next takeover).  finish() on the success path returns the record's own status.
-struct LevelSetGuard {
-    p252_ctx* ctx;
-    p252_ctx::LevelSet* set = nullptr;
-    explicit LevelSetGuard(p252_ctx* c) : ctx(c) {}
-    int finish() {
-        p252_ctx::LevelSet* s = set;
-        set = nullptr;
-        return s ? p252host::level_set_done(ctx, s) : P252_OK;
-    }
-    ~LevelSetGuard() {
-        if (!set) return;
-        const std::string msg = ctx->err;  // (the failure being reported stays the message)
-        (void)p252host::level_set_done(ctx, set);
-        ctx->err = msg;
-    }
-};
+// what a call's launches on the device came to, as the entry point's return value
+int launched(p252_ctx* ctx, const std::string& who, hipError_t e) {
+    return e == hipSuccess ? P252_OK : fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
+}
 
-// the way out of a builder whose launches may have failed (rc): records the pair's event, keeps the failure's message and code
-int finish_guarded(p252_ctx* ctx, LevelSetGuard& guard, int rc) {
+// The ONE way to the scratch pair of the calling stream (ctx.hpp): body(set) enqueues the call's launches on `st` and returns their
+// hipError_t.  Once the pair is acquired its event is recorded on EVERY way out — also when a launch failed half way: the launches
+// before it are queued and touch the pair, and a later takeover by another stream waits on this event (early
+// returns used to skip it and left the event of an OLDER build for the next takeover).  A failure of the body keeps its code and
+// message over the record's; on success the record's own status is returned.
+template <class Body>
+int with_stream_scratch(p252_ctx* ctx, const std::string& who, hipStream_t st, size_t need0, size_t need1, Body&& body) {
+    p252_ctx::LevelSet* set = nullptr;
+    if (int rc = level_set(ctx, st, need0, need1, &set)) return rc;
+    const int rc = launched(ctx, who, body(*set));
     const std::string msg = ctx->err;
-    const int rc2 = guard.finish();
+    const int rc_done = level_set_done(ctx, set);
     if (rc) ctx->err = msg;
-    return rc ? rc : rc2;
+    return rc ? rc : rc_done;
 }
 }  // namespace
 
@@ -212,6 +207,127 @@ static hipError_t count_nonzero_device(const void* d, size_t bytes, uint64_t* to
         for (size_t i = 0; i < cnt; ++i) *total += b[i] != 0;
     }
     return hipSuccess;
+}
+
+size_t p252host::levels_len(size_t n_leaves, size_t arity) {
+    size_t total = 0, c = n_leaves;
+    while (c > 1) {
+        c = (c + arity - 1) / arity;
+        total += c;
+    }
+    return total;
+}
+
+int p252host::merkle_tree_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                              void* d_root, void* d_levels, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: n_leaves must be > 0");
+    if (!tag || !d_leaves || !d_root) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);  // d_root: plain copy
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const TagArg t = tag_arg(tag);
+    // A build with wide levels (more nodes than the chip has lanes at one wave per SIMD: 65,536) keeps every SIMD
+    // loaded through its narrow levels by computing them redundantly (kernels.hip k_merkle4_pad: the next wide launch
+    // would otherwise start at a dipped clock).  P252_TREE_PAD_LANES overrides the lane count; 0 = off.
+    static const long pad_env = [] {
+        const char* e = std::getenv("P252_TREE_PAD_LANES");
+        return e ? std::atol(e) : -1L;
+    }();
+    const size_t chip_lanes = 65536;
+    const size_t l1 = (n_leaves + arity - 1) / arity, l2 = (l1 + arity - 1) / arity;
+    const size_t pad = pad_env >= 0 ? (size_t)pad_env : (l1 > chip_lanes ? chip_lanes : 0);
+    auto build = [&](void* const* ping) {  // the levels go to d_levels, or ping-pong between ping[0] and ping[1]
+        const char* cur = static_cast<const char*>(d_leaves);
+        size_t cur_n = n_leaves;
+        char* lv = static_cast<char*>(d_levels);
+        int parity = 0;
+        while (cur_n > 1) {  // a single leaf is its own root: an arity^k-leaf tree costs exactly k levels
+            const size_t next_n = (cur_n + arity - 1) / arity;
+            char* next = d_levels ? lv : static_cast<char*>(ping[parity]);
+            const hipError_t e = launch_merkle4(ctx->d_tab, t, cur, cur_n, next, next_n, st, arity, pad);
+            if (e != hipSuccess) return e;
+            cur = next;
+            cur_n = next_n;
+            if (d_levels) lv += next_n * 32;
+            parity ^= 1;
+        }
+        return hipMemcpyAsync(d_root, cur, 32, hipMemcpyDeviceToDevice, st);
+    };
+    if (d_levels || n_leaves == 1) return launched(ctx, "merkle_tree", build(nullptr));  // no context scratch
+    // ping-pong in context-owned scratch: the pair of THIS stream (ctx.hpp)
+    return with_stream_scratch(ctx, "merkle_tree", st, l1 * 32, l2 * 32, [&](p252_ctx::LevelSet& set) { return build(set.buf); });
+}
+
+// The sponge-call sequence dusk_safe::encrypt makes, as a table (one word per call: kind << 29 | len; kinds as in
+// kernels.hip k_crypt).  Two candidates (include/poseidon252_hip.h): P252_CRYPT_STREAM — squeeze all `len` masks, then
+// absorb the whole message — and P252_CRYPT_DUPLEX — squeeze / absorb per chunk of <= 4.  Adding a third is one more
+// branch here: the kernel, the tag and the oracle all derive from the table.
+static std::vector<uint32_t> crypt_program(int variant, size_t len) {
+    std::vector<uint32_t> prog;
+    auto call = [&](uint32_t kind, size_t n) { prog.push_back((kind << 29) | (uint32_t)n); };
+    call(0, 2);  // Absorb(2): shared secret (u, v)
+    call(1, 1);  // Absorb(1): nonce
+    if (variant == P252_CRYPT_STREAM) {
+        call(2, len);  // Squeeze(len): masks
+        call(3, len);  // Absorb(len): message
+    } else {
+        for (size_t left = len; left;) {
+            const size_t c = left < 4 ? left : 4;
+            call(2, c);
+            call(3, c);
+            left -= c;
+        }
+    }
+    call(4, 1);  // Squeeze(1): MAC
+    return prog;
+}
+
+bool p252host::crypt_variant_ok(int variant) { return variant == P252_CRYPT_STREAM || variant == P252_CRYPT_DUPLEX; }
+
+// the sponge-call table of (variant, len) on the device (kept until another one is asked for)
+int p252host::prepare_prog(p252_ctx* ctx, int variant, size_t len) {
+    if (ctx->prog_variant == variant && ctx->prog_len == len) return P252_OK;
+    const std::vector<uint32_t> prog = crypt_program(variant, len);
+    // the previous program may still be read by a kernel in flight on another stream: drain before replacing it
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    int rc = ensure(ctx, (void**)&ctx->d_prog, &ctx->d_prog_cap, prog.size() * sizeof(uint32_t));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_prog, prog.data(), prog.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->prog_variant = variant;
+    ctx->prog_len = len;
+    ctx->prog_calls = (unsigned)prog.size();
+    return P252_OK;
+}
+
+bool p252host::power_of_4(size_t v) {
+    if (v == 0 || (v & (v - 1))) return false;
+    int tz = 0;
+    while (!((v >> tz) & 1)) ++tz;
+    return (tz & 1) == 0;
+}
+
+int p252host::check_ctxs(p252_ctx* const* ctxs, size_t n_ctx) {
+    if (!ctxs || n_ctx == 0) return P252_ERR_INVALID_ARGUMENT;
+    for (size_t t = 0; t < n_ctx; ++t)
+        if (!ctxs[t]) return P252_ERR_INVALID_ARGUMENT;
+    for (size_t a = 0; a < n_ctx; ++a)  // a context is used by one thread at a time: no duplicates
+        for (size_t b = a + 1; b < n_ctx; ++b)
+            if (ctxs[a] == ctxs[b]) return fail(ctxs[0], P252_ERR_INVALID_ARGUMENT, "multi: the same context appears twice");
+    // one context per GPU is the point of these entry points: when the node has at least n_ctx devices, two contexts on the
+    // same device are a caller's mistake (every shard would land on one GPU).  Fewer devices than contexts — the
+    // single-GPU test configuration — is allowed.  P252_MULTI_ALLOW_SHARED_DEVICE=1 lifts the check.
+    static const bool allow_shared = [] {
+        const char* e = std::getenv("P252_MULTI_ALLOW_SHARED_DEVICE");
+        return e && e[0] == '1';
+    }();
+    if (!allow_shared && (size_t)p252_device_count() >= n_ctx)
+        for (size_t a = 0; a < n_ctx; ++a)
+            for (size_t b = a + 1; b < n_ctx; ++b)
+                if (ctxs[a]->device == ctxs[b]->device)
+                    return fail(ctxs[0], P252_ERR_INVALID_ARGUMENT,
+                                "multi: contexts " + std::to_string(a) + " and " + std::to_string(b) + " are bound to the same device although the node has one per context");
+    return P252_OK;
 }
 
 extern "C" {
@@ -394,63 +510,8 @@ int p252_hash_batch_truncated_device(p252_ctx* ctx, const uint64_t tag[4], const
     return hash_batch_device_impl(ctx, tag, d_in, in_len, out_len, d_out_raw, n, hip_stream, true);
 }
 
-extern "C++" {
-size_t p252host::levels_len(size_t n_leaves, size_t arity) {
-    size_t total = 0, c = n_leaves;
-    while (c > 1) {
-        c = (c + arity - 1) / arity;
-        total += c;
-    }
-    return total;
-}
-}  // extern "C++"
 size_t p252_merkle4_levels_len(size_t n_leaves) { return levels_len(n_leaves, 4); }
 size_t p252_merkle2_levels_len(size_t n_leaves) { return levels_len(n_leaves, 2); }
-
-extern "C++" {
-int p252host::merkle_tree_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
-                              void* d_root, void* d_levels, void* hip_stream) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: n_leaves must be > 0");
-    if (!tag || !d_leaves || !d_root) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: NULL buffer");
-    if (misaligned(d_leaves) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);  // d_root: plain copy
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    const TagArg t = tag_arg(tag);
-    const char* cur = static_cast<const char*>(d_leaves);
-    size_t cur_n = n_leaves;
-    char* lv = static_cast<char*>(d_levels);
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    if (!d_levels && n_leaves > 1) {  // ping-pong in context-owned scratch: the pair of THIS stream (ctx.hpp)
-        const size_t l1 = (n_leaves + arity - 1) / arity, l2 = (l1 + arity - 1) / arity;
-        int rc = level_set(ctx, st, l1 * 32, l2 * 32, &set);
-        if (rc) return rc;
-    }
-    // A build with wide levels (more nodes than the chip has lanes at one wave per SIMD: 65,536) keeps every SIMD
-    // loaded through its narrow levels by computing them redundantly (kernels.hip k_merkle4_pad: the next wide launch
-    // would otherwise start at a dipped clock).  P252_TREE_PAD_LANES overrides the lane count; 0 = off.
-    static const long pad_env = [] {
-        const char* e = std::getenv("P252_TREE_PAD_LANES");
-        return e ? std::atol(e) : -1L;
-    }();
-    const size_t chip_lanes = 65536;
-    const size_t first_level = (n_leaves + arity - 1) / arity;
-    const size_t pad = pad_env >= 0 ? (size_t)pad_env : (first_level > chip_lanes ? chip_lanes : 0);
-    int parity = 0;
-    while (cur_n > 1) {  // a single leaf is its own root: an arity^k-leaf tree costs exactly k levels
-        const size_t next_n = (cur_n + arity - 1) / arity;
-        char* next = d_levels ? lv : static_cast<char*>(set->buf[parity]);
-        HIP_TRY(ctx, launch_merkle4(ctx->d_tab, t, cur, cur_n, next, next_n, st, arity, pad));
-        cur = next;
-        cur_n = next_n;
-        if (d_levels) lv += next_n * 32;
-        parity ^= 1;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d_root, cur, 32, hipMemcpyDeviceToDevice, st));
-    return guard.finish();
-}
-}  // extern "C++"
 
 int p252_merkle4_tree_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
                              void* d_root, void* d_levels, void* hip_stream) {
@@ -473,36 +534,36 @@ static int forest_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], c
     if (misaligned(d_leaves) || misaligned(d_roots) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    size_t cur_n = n_trees * leaves_per_tree;
+    const size_t cur_n = n_trees * leaves_per_tree;
     if (leaves_per_tree == 1) {  // a single leaf is its own root (as in p252_merkle4_tree_device)
         HIP_TRY(ctx, hipMemcpyAsync(d_roots, d_leaves, cur_n * 32, hipMemcpyDeviceToDevice, st));
         return P252_OK;
     }
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    if (!d_levels) {  // ping-pong in context-owned scratch, this stream's pair (the last level goes straight to d_roots)
-        int rc = level_set(ctx, st, cur_n / arity * 32, cur_n / arity / arity * 32 + 32, &set);
-        if (rc) return rc;
-    }
     const TagArg t = tag_arg(tag);
-    const char* cur = static_cast<const char*>(d_leaves);
-    char* lv = static_cast<char*>(d_levels);
     // narrow levels after wide ones are computed redundantly on every SIMD, as in the tree builder (clock dip)
     const size_t pad = cur_n / arity > 65536 ? 65536 : 0;
-    int parity = 0;
-    while (cur_n > n_trees) {
-        const size_t next_n = cur_n / arity;
-        char* next = next_n == n_trees ? static_cast<char*>(d_roots) : (d_levels ? lv : static_cast<char*>(set->buf[parity]));
-        HIP_TRY(ctx, launch_merkle4(ctx->d_tab, t, cur, cur_n, next, next_n, st, arity, pad));
-        if (d_levels) {
-            if (next_n == n_trees) HIP_TRY(ctx, hipMemcpyAsync(lv, d_roots, next_n * 32, hipMemcpyDeviceToDevice, st));  // levels hold the roots too
-            lv += next_n * 32;
+    auto build = [&](void* const* ping) {  // the levels go to d_levels, or ping-pong between ping[0] and ping[1]
+        const char* cur = static_cast<const char*>(d_leaves);
+        char* lv = static_cast<char*>(d_levels);
+        size_t level_n = cur_n;
+        int parity = 0;
+        while (level_n > n_trees) {
+            const size_t next_n = level_n / arity;
+            char* next = next_n == n_trees ? static_cast<char*>(d_roots) : (d_levels ? lv : static_cast<char*>(ping[parity]));
+            hipError_t e = launch_merkle4(ctx->d_tab, t, cur, level_n, next, next_n, st, arity, pad);
+            if (e == hipSuccess && d_levels && next_n == n_trees) e = hipMemcpyAsync(lv, d_roots, next_n * 32, hipMemcpyDeviceToDevice, st);  // levels hold the roots too
+            if (e != hipSuccess) return e;
+            if (d_levels) lv += next_n * 32;
+            cur = next;
+            level_n = next_n;
+            parity ^= 1;
         }
-        cur = next;
-        cur_n = next_n;
-        parity ^= 1;
-    }
-    return guard.finish();
+        return hipSuccess;
+    };
+    if (d_levels) return launched(ctx, "merkle_forest", build(nullptr));  // no context scratch
+    // ping-pong in context-owned scratch, this stream's pair (the last level goes straight to d_roots)
+    return with_stream_scratch(ctx, "merkle_forest", st, cur_n / arity * 32, cur_n / arity / arity * 32 + 32,
+                               [&](p252_ctx::LevelSet& set) { return build(set.buf); });
 }
 
 int p252_merkle4_forest_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_trees, size_t leaves_per_tree,
@@ -541,14 +602,10 @@ static int hash_ragged_device_impl(p252_ctx* ctx, const void* d_tags, size_t max
                                         nullptr, st, trunc250));
         return P252_OK;
     }
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    int rc = level_set(ctx, st, ragged_order_bytes(n), ragged_hist_bytes(), &set);
-    if (rc) return rc;
-    const hipError_t e = launch_hash_ragged(ctx->d_tab, d_tags, max_len, d_in, d_offsets, (unsigned)out_len, d_out, n, d_n_bad, set->buf[0],
-                                            set->buf[1], st, trunc250);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string("hash_ragged: ") + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, "hash_ragged", st, ragged_order_bytes(n), ragged_hist_bytes(), [&](p252_ctx::LevelSet& set) {
+        return launch_hash_ragged(ctx->d_tab, d_tags, max_len, d_in, d_offsets, (unsigned)out_len, d_out, n, d_n_bad, set.buf[0], set.buf[1], st,
+                                  trunc250);
+    });
 }
 
 int p252_hash_ragged_device(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets, size_t out_len,
@@ -586,15 +643,12 @@ static int forest_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t ta
     hipStream_t st = (hipStream_t)hip_stream;
     const ForestRaggedPlan plan = forest_ragged_plan(arity, n_leaves, n_trees, max_leaves, d_levels != nullptr);
     const bool ping = !d_levels && plan.depth > 0;
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    int rc = level_set(ctx, st, plan.meta_bytes + (ping ? plan.bound[1] * 32 : 0), ping && plan.depth > 1 ? plan.bound[2] * 32 : 0, &set);
-    if (rc) return rc;
-    char* meta = static_cast<char*>(set->buf[0]);
-    const hipError_t e = launch_forest_ragged(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, max_leaves, d_roots, d_levels, d_n_bad,
-                                              meta, ping ? meta + plan.meta_bytes : nullptr, set->buf[1], st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string("merkle_forest_ragged: ") + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, "merkle_forest_ragged", st, plan.meta_bytes + (ping ? plan.bound[1] * 32 : 0),
+                               ping && plan.depth > 1 ? plan.bound[2] * 32 : 0, [&](p252_ctx::LevelSet& set) {
+                                   char* meta = static_cast<char*>(set.buf[0]);
+                                   return launch_forest_ragged(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, max_leaves, d_roots, d_levels,
+                                                               d_n_bad, meta, ping ? meta + plan.meta_bytes : nullptr, set.buf[1], st);
+                               });
 }
 
 int p252_merkle4_forest_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, const void* d_offsets,
@@ -634,18 +688,14 @@ static int forest_ragged_openings_device(p252_ctx* ctx, unsigned arity, const vo
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t index_bytes = forest_ragged_index_bytes(n_trees);
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    int rc = level_set(ctx, st, index_bytes + forest_openings_record_bytes(k), 0, &set);
-    if (rc) return rc;
-    char* meta = static_cast<char*>(set->buf[0]);
-    const uint64_t *ntree = nullptr, *lo = nullptr;
-    hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
-    if (e == hipSuccess)
-        e = launch_forest_openings(arity, d_leaves, d_levels, d_offsets, ntree, lo, n_trees, d_tree_ids, d_leaf_ids, k, (unsigned)depth,
-                                   meta + index_bytes, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, who, st, index_bytes + forest_openings_record_bytes(k), 0, [&](p252_ctx::LevelSet& set) {
+        char* meta = static_cast<char*>(set.buf[0]);
+        const uint64_t *ntree = nullptr, *lo = nullptr;
+        const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
+        if (e != hipSuccess) return e;
+        return launch_forest_openings(arity, d_leaves, d_levels, d_offsets, ntree, lo, n_trees, d_tree_ids, d_leaf_ids, k, (unsigned)depth,
+                                      meta + index_bytes, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, st);
+    });
 }
 
 // the argument checks of the re-hash (shared with the verify call)
@@ -677,14 +727,10 @@ static int path_ragged_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[
                                         d_roots_out, k, d_n_bad, nullptr, nullptr, st));
         return P252_OK;
     }
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    rc = level_set(ctx, st, forest_openings_order_bytes(k), forest_openings_hist_bytes(), &set);
-    if (rc) return rc;
-    const hipError_t e = launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths,
-                                            (unsigned)stride_depth, d_roots_out, k, d_n_bad, set->buf[0], set->buf[1], st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, who, st, forest_openings_order_bytes(k), forest_openings_hist_bytes(), [&](p252_ctx::LevelSet& set) {
+        return launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths, (unsigned)stride_depth,
+                                  d_roots_out, k, d_n_bad, set.buf[0], set.buf[1], st);
+    });
 }
 
 static int forest_ragged_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
@@ -701,16 +747,16 @@ static int forest_ragged_verify_device(p252_ctx* ctx, unsigned arity, const uint
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const bool sort = ragged_sort_enabled();
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;  // the recomputed roots (k x 32 bytes), then the sort's order; the counters in the second buffer
-    rc = level_set(ctx, st, k * 32 + (sort ? forest_openings_order_bytes(k) : 0), sort ? forest_openings_hist_bytes() : 0, &set);
-    if (rc) return rc;
-    char* roots = static_cast<char*>(set->buf[0]);
-    hipError_t e = launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths, (unsigned)stride_depth,
-                                      roots, k, nullptr, sort ? roots + k * 32 : nullptr, sort ? set->buf[1] : nullptr, st);
-    if (e == hipSuccess) e = launch_compare_roots_gather(roots, d_depths, (unsigned)stride_depth, d_tree_ids, d_roots, n_trees, d_ok, k, st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    // the recomputed roots (k x 32 bytes), then the sort's order; the counters in the second buffer
+    return with_stream_scratch(ctx, who, st, k * 32 + (sort ? forest_openings_order_bytes(k) : 0), sort ? forest_openings_hist_bytes() : 0,
+                               [&](p252_ctx::LevelSet& set) {
+                                   char* roots = static_cast<char*>(set.buf[0]);
+                                   const hipError_t e = launch_path_ragged(arity, ctx->d_tab, tag_arg(tag), d_leaves_in, d_siblings, d_positions, d_depths,
+                                                                           (unsigned)stride_depth, roots, k, nullptr, sort ? roots + k * 32 : nullptr,
+                                                                           sort ? set.buf[1] : nullptr, st);
+                                   if (e != hipSuccess) return e;
+                                   return launch_compare_roots_gather(roots, d_depths, (unsigned)stride_depth, d_tree_ids, d_roots, n_trees, d_ok, k, st);
+                               });
 }
 
 int p252_merkle4_forest_ragged_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
@@ -782,18 +828,14 @@ static int forest_ragged_update_device(p252_ctx* ctx, unsigned arity, const uint
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t index_bytes = forest_ragged_index_bytes(n_trees);
     const ForestUpdatePlan plan = forest_update_plan(arity, n_leaves, n_trees, max_leaves, k);
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    int rc = level_set(ctx, st, index_bytes + plan.ids_bytes(), plan.table_bytes, &set);
-    if (rc) return rc;
-    char* meta = static_cast<char*>(set->buf[0]);
-    const uint64_t *ntree = nullptr, *lo = nullptr;
-    hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
-    if (e == hipSuccess)
-        e = launch_forest_update(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids,
-                                 d_new_leaves, d_roots, d_n_bad, d_n_hashed, meta + index_bytes, set->buf[1], st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, who, st, index_bytes + plan.ids_bytes(), plan.table_bytes, [&](p252_ctx::LevelSet& set) {
+        char* meta = static_cast<char*>(set.buf[0]);
+        const uint64_t *ntree = nullptr, *lo = nullptr;
+        const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
+        if (e != hipSuccess) return e;
+        return launch_forest_update(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves,
+                                    d_roots, d_n_bad, d_n_hashed, meta + index_bytes, set.buf[1], st);
+    });
 }
 
 int p252_merkle4_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, const void* d_offsets,
@@ -929,32 +971,40 @@ int p252_from_bytes_device(p252_ctx* ctx, const void* d_bytes, void* d_scalars, 
     return P252_OK;
 }
 
-int p252_merkle4_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
-                                   const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n == 0) return P252_OK;
-    if (!tag || !d_leaves || !d_roots || (depth && (!d_siblings || !d_positions)))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: NULL buffer");
-    if (depth > 0xffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: depth too large");
+// the argument checks of the fixed-depth re-hash (shared with the verify call)
+static int path_batch_check(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
+                            const void* d_positions, size_t depth, const void* d_roots) {
+    const std::string who = arity == 4 ? "merkle4_path" : "merkle2_path";
+    if (!tag || !d_leaves || !d_roots || (depth && (!d_siblings || !d_positions))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (depth > 0xffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": depth too large");
     if (misaligned(d_leaves) || misaligned(d_roots) || (depth && misaligned(d_siblings))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_merkle4_path(ctx->d_tab, tag_arg(tag), d_leaves, d_siblings, d_positions, (unsigned)depth,
-                                     d_roots, n, (hipStream_t)hip_stream));
     return P252_OK;
 }
 
-// arity-2 twin of p252_merkle4_path_batch_device (Domain::Merkle2 nodes; pass the Merkle2 tag): siblings[n][depth], positions 0..1
-int p252_merkle2_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
-                                   const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
+static hipError_t launch_path(unsigned arity, const int32_t* tab, const TagArg& tag, const void* d_leaves, const void* d_siblings,
+                              const void* d_positions, size_t depth, void* d_roots, size_t n, hipStream_t st) {
+    return (arity == 4 ? launch_merkle4_path : launch_merkle2_path)(tab, tag, d_leaves, d_siblings, d_positions, (unsigned)depth, d_roots, n, st);
+}
+
+// both arities (arity 2: Domain::Merkle2 nodes, pass the Merkle2 tag; siblings[n][depth], positions 0..1)
+static int path_batch_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
+                             const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
     if (n == 0) return P252_OK;
-    if (!tag || !d_leaves || !d_roots || (depth && (!d_siblings || !d_positions)))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle2_path: NULL buffer");
-    if (depth > 0xffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle2_path: depth too large");
-    if (misaligned(d_leaves) || misaligned(d_roots) || (depth && misaligned(d_siblings))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (int rc = path_batch_check(ctx, arity, tag, d_leaves, d_siblings, d_positions, depth, d_roots)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_merkle2_path(ctx->d_tab, tag_arg(tag), d_leaves, d_siblings, d_positions, (unsigned)depth, d_roots, n, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, launch_path(arity, ctx->d_tab, tag_arg(tag), d_leaves, d_siblings, d_positions, depth, d_roots, n, (hipStream_t)hip_stream));
     return P252_OK;
+}
+
+int p252_merkle4_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
+                                   const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
+    return path_batch_device(ctx, 4, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n, hip_stream);
+}
+
+int p252_merkle2_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
+                                   const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
+    return path_batch_device(ctx, 2, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n, hip_stream);
 }
 
 // Opening::verify in bulk: re-hash (either arity) into this stream's scratch, then one byte per opening
@@ -966,19 +1016,16 @@ static int verify_batch_device(p252_ctx* ctx, unsigned arity, const uint64_t tag
     if (!d_root || !d_ok) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
     if (misaligned(d_root)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
     if (n > (SIZE_MAX / 32)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    // the re-hash's own refusals, before any scratch is taken (its output is the scratch: d_root, checked above, stands in for it)
+    if (int rc = path_batch_check(ctx, arity, tag, d_leaves, d_siblings, d_positions, depth, d_root)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;  // the recomputed roots live in the scratch pair of THIS stream (ctx.hpp): n x 32 bytes
-    int rc = level_set(ctx, st, n * 32, 0, &set);
-    if (rc) return rc;
-    rc = arity == 4 ? p252_merkle4_path_batch_device(ctx, tag, d_leaves, d_siblings, d_positions, depth, set->buf[0], n, hip_stream)
-                    : p252_merkle2_path_batch_device(ctx, tag, d_leaves, d_siblings, d_positions, depth, set->buf[0], n, hip_stream);
-    if (rc == P252_OK) {
-        const hipError_t e = launch_compare_roots(set->buf[0], d_root, d_ok, n, st);
-        if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
-    }
-    return finish_guarded(ctx, guard, rc);
+    // the recomputed roots live in the scratch pair of THIS stream (ctx.hpp): n x 32 bytes
+    return with_stream_scratch(ctx, who, st, n * 32, 0, [&](p252_ctx::LevelSet& set) {
+        const hipError_t e = launch_path(arity, ctx->d_tab, tag_arg(tag), d_leaves, d_siblings, d_positions, depth, set.buf[0], n, st);
+        if (e != hipSuccess) return e;
+        return launch_compare_roots(set.buf[0], d_root, d_ok, n, st);
+    });
 }
 
 int p252_merkle4_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
@@ -991,18 +1038,15 @@ int p252_merkle2_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const
     return verify_batch_device(ctx, 2, tag, d_leaves, d_siblings, d_positions, depth, d_root, d_ok, n, hip_stream);
 }
 
-size_t p252_merkle2_depth(size_t n_leaves) {
+// depth of the tree over n_leaves = number of levels above the leaves (an arity^k-leaf tree: k; a single leaf: 0).  The sum wraps
+// at the top of size_t, which callers see (ABI): the depth of SIZE_MAX leaves is 1.
+static size_t tree_depth(size_t n_leaves, size_t arity) {
     size_t d = 0;
-    for (size_t c = n_leaves; c > 1; c = (c + 1) / 2) ++d;
+    for (size_t c = n_leaves; c > 1; c = (c + arity - 1) / arity) ++d;
     return d;
 }
-
-// depth of the arity-4 tree over n_leaves = number of levels above the leaves (a 4^k-leaf tree: k; a single leaf: 0)
-size_t p252_merkle4_depth(size_t n_leaves) {
-    size_t d = 0;
-    for (size_t c = n_leaves; c > 1; c = (c + 3) / 4) ++d;
-    return d;
-}
+size_t p252_merkle4_depth(size_t n_leaves) { return tree_depth(n_leaves, 4); }
+size_t p252_merkle2_depth(size_t n_leaves) { return tree_depth(n_leaves, 2); }
 
 // Openings of a STORED tree, extracted on the device (openings.hip: pure data movement): for each of the k leaf positions the
 // leaf, the three siblings per level and the position bytes, in exactly the layout p252_merkle4_path_batch_device takes — build
@@ -1013,7 +1057,7 @@ static int openings_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, 
     if (k == 0) return P252_OK;
     const std::string who = arity == 4 ? "merkle4_openings" : "merkle2_openings";
     if (n_leaves == 0 || n_leaves > 0xffffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves must be in 1 .. 2^32 - 1 (positions are uint32)");
-    const size_t depth = arity == 4 ? p252_merkle4_depth(n_leaves) : p252_merkle2_depth(n_leaves);
+    const size_t depth = tree_depth(n_leaves, arity);
     if (!d_leaves || !d_indices || !d_leaves_out || (depth && (!d_levels || !d_siblings || !d_positions)))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
     if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_siblings)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
@@ -1065,14 +1109,9 @@ static int multiproof_device(p252_ctx* ctx, unsigned arity, const void* d_leaves
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / d_n_bad must be 4-byte, d_proof_len 8-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    int rc = level_set(ctx, st, plan.work_bytes(), 0, &set);
-    if (rc) return rc;
-    const hipError_t e = launch_multiproof(plan, d_leaves, d_levels, d_indices, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad,
-                                           set->buf[0], st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, who, st, plan.work_bytes(), 0, [&](p252_ctx::LevelSet& set) {
+        return launch_multiproof(plan, d_leaves, d_levels, d_indices, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, set.buf[0], st);
+    });
 }
 
 static int multiproof_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], size_t n_leaves, const void* d_indices,
@@ -1091,14 +1130,10 @@ static int multiproof_verify_device(p252_ctx* ctx, unsigned arity, const uint64_
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const MultiproofPlan plan = multiproof_plan(arity, n_leaves, k);
-    LevelSetGuard guard(ctx);
-    p252_ctx::LevelSet*& set = guard.set;
-    int rc = level_set(ctx, st, plan.work_bytes(), plan.values_bytes(), &set);
-    if (rc) return rc;
-    const hipError_t e = launch_multiproof_verify(ctx->d_tab, tag_arg(tag), plan, d_indices, d_leaves_in, d_proof, proof_len, d_root, d_ok,
-                                                  d_root_out, d_n_hashed, d_n_bad, set->buf[0], set->buf[1], st);
-    if (e != hipSuccess) rc = fail(ctx, P252_ERR_HIP, who + ": " + hipGetErrorString(e));
-    return finish_guarded(ctx, guard, rc);
+    return with_stream_scratch(ctx, who, st, plan.work_bytes(), plan.values_bytes(), [&](p252_ctx::LevelSet& set) {
+        return launch_multiproof_verify(ctx->d_tab, tag_arg(tag), plan, d_indices, d_leaves_in, d_proof, proof_len, d_root, d_ok, d_root_out,
+                                        d_n_hashed, d_n_bad, set.buf[0], set.buf[1], st);
+    });
 }
 
 int p252_merkle4_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
@@ -1126,49 +1161,6 @@ int p252_merkle2_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], 
 }
 
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----
-// The sponge-call sequence dusk_safe::encrypt makes, as a table (one word per call: kind << 29 | len; kinds as in
-// kernels.hip k_crypt).  Two candidates (include/poseidon252_hip.h): P252_CRYPT_STREAM — squeeze all `len` masks, then
-// absorb the whole message — and P252_CRYPT_DUPLEX — squeeze / absorb per chunk of <= 4.  Adding a third is one more
-// branch here: the kernel, the tag and the oracle all derive from the table.
-static std::vector<uint32_t> crypt_program(int variant, size_t len) {
-    std::vector<uint32_t> prog;
-    auto call = [&](uint32_t kind, size_t n) { prog.push_back((kind << 29) | (uint32_t)n); };
-    call(0, 2);  // Absorb(2): shared secret (u, v)
-    call(1, 1);  // Absorb(1): nonce
-    if (variant == P252_CRYPT_STREAM) {
-        call(2, len);  // Squeeze(len): masks
-        call(3, len);  // Absorb(len): message
-    } else {
-        for (size_t left = len; left;) {
-            const size_t c = left < 4 ? left : 4;
-            call(2, c);
-            call(3, c);
-            left -= c;
-        }
-    }
-    call(4, 1);  // Squeeze(1): MAC
-    return prog;
-}
-
-extern "C++" {
-bool p252host::crypt_variant_ok(int variant) { return variant == P252_CRYPT_STREAM || variant == P252_CRYPT_DUPLEX; }
-
-// the sponge-call table of (variant, len) on the device (kept until another one is asked for)
-int p252host::prepare_prog(p252_ctx* ctx, int variant, size_t len) {
-    if (ctx->prog_variant == variant && ctx->prog_len == len) return P252_OK;
-    const std::vector<uint32_t> prog = crypt_program(variant, len);
-    // the previous program may still be read by a kernel in flight on another stream: drain before replacing it
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    int rc = ensure(ctx, (void**)&ctx->d_prog, &ctx->d_prog_cap, prog.size() * sizeof(uint32_t));
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_prog, prog.data(), prog.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    ctx->prog_variant = variant;
-    ctx->prog_len = len;
-    ctx->prog_calls = (unsigned)prog.size();
-    return P252_OK;
-}
-}  // extern "C++"
-
 static int crypt_device(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const void* d_in, const void* d_secrets,
                         const void* d_nonces, size_t len, void* d_out, void* d_ok, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
@@ -1243,40 +1235,6 @@ int p252_encryption_tag(int variant, size_t message_len, uint64_t tag_out[4]) {
 // independent — no inter-GPU dependence, no collective on the data path; the only exchange of the sharded tree is the
 // 32-byte subtree root of every device, gathered by the host.  One host thread per context for the duration of the call.
 // ------------------------------------------------------------------------------------------
-extern "C++" {
-bool p252host::power_of_4(size_t v) {
-    if (v == 0 || (v & (v - 1))) return false;
-    int tz = 0;
-    while (!((v >> tz) & 1)) ++tz;
-    return (tz & 1) == 0;
-}
-}  // extern "C++"
-
-extern "C++" {
-int p252host::check_ctxs(p252_ctx* const* ctxs, size_t n_ctx) {
-    if (!ctxs || n_ctx == 0) return P252_ERR_INVALID_ARGUMENT;
-    for (size_t t = 0; t < n_ctx; ++t)
-        if (!ctxs[t]) return P252_ERR_INVALID_ARGUMENT;
-    for (size_t a = 0; a < n_ctx; ++a)  // a context is used by one thread at a time: no duplicates
-        for (size_t b = a + 1; b < n_ctx; ++b)
-            if (ctxs[a] == ctxs[b]) return fail(ctxs[0], P252_ERR_INVALID_ARGUMENT, "multi: the same context appears twice");
-    // one context per GPU is the point of these entry points: when the node has at least n_ctx devices, two contexts on the
-    // same device are a caller's mistake (every shard would land on one GPU).  Fewer devices than contexts — the
-    // single-GPU test configuration — is allowed.  P252_MULTI_ALLOW_SHARED_DEVICE=1 lifts the check.
-    static const bool allow_shared = [] {
-        const char* e = std::getenv("P252_MULTI_ALLOW_SHARED_DEVICE");
-        return e && e[0] == '1';
-    }();
-    if (!allow_shared && (size_t)p252_device_count() >= n_ctx)
-        for (size_t a = 0; a < n_ctx; ++a)
-            for (size_t b = a + 1; b < n_ctx; ++b)
-                if (ctxs[a]->device == ctxs[b]->device)
-                    return fail(ctxs[0], P252_ERR_INVALID_ARGUMENT,
-                                "multi: contexts " + std::to_string(a) + " and " + std::to_string(b) + " are bound to the same device although the node has one per context");
-    return P252_OK;
-}
-}  // extern "C++"
-
 // for the duration of one multi call every context works within its share of the CPU budget
 struct LaneBudgetScope {
     p252_ctx* const* ctxs;
@@ -1517,4 +1475,4 @@ int p252_from_bytes(const uint8_t* bytes, uint64_t* scalars, uint8_t* ok, size_t
     return P252_OK;
 }
 
-}  // extern "C"
+}  // (the C ABI)

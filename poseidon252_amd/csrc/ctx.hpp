@@ -25,6 +25,7 @@ struct p252_ctx {
     // stream, so ONE pair per context would be shared by builds queued on different streams (round 4: silent wrong roots).  Each
     // caller stream therefore owns a pair (up to MAX_LEVEL_SETS); a further stream takes over the least recently used pair after
     // waiting on the event recorded behind that pair's last build — builds on different streams overlap, none ever shares scratch.
+    // Every call that uses a pair goes through api.cpp's with_stream_scratch, which records that event on every way out.
     struct LevelSet {
         hipStream_t st = nullptr;
         void* buf[2] = {nullptr, nullptr};
@@ -74,9 +75,6 @@ struct p252_ctx {
 namespace p252host {
 int fail(p252_ctx* ctx, int code, const std::string& msg);
 int ensure(p252_ctx* ctx, void** buf, size_t* cap, size_t need);
-// the level-scratch pair of a root-only build on `st` (at least need0 / need1 bytes); level_set_done() after the build's last launch
-int level_set(p252_ctx* ctx, hipStream_t st, size_t need0, size_t need1, p252_ctx::LevelSet** out);
-int level_set_done(p252_ctx* ctx, p252_ctx::LevelSet* set);
 const std::vector<int32_t>& host_tables();
 bool power_of_4(size_t v);
 int check_ctxs(p252_ctx* const* ctxs, size_t n_ctx);
