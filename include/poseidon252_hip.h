@@ -12,9 +12,20 @@
  * the Rust `extern "C"` block and the `HashBatch` wrapper a maintainer would add.
  *
  * Scalars: every `uint64_t*` scalar buffer is an array of BlsScalar in the reference's memory
- * layout — 4 little-endian u64 limbs of the Montgomery residue a*2^256 mod p, fully reduced — so a
- * Rust `&[BlsScalar]` is passed as a pointer with zero conversion.  Outputs are fully reduced too
- * (bit-exact equality with the reference is limb equality).
+ * layout — 4 little-endian u64 limbs of the Montgomery residue a*2^256 mod p — so a Rust
+ * `&[BlsScalar]` is passed as a pointer with zero conversion.  Callers should pass fully reduced
+ * scalars, as the reference holds them.  A scalar whose limbs are >= p (any 256-bit pattern V, up to
+ * 2^256 - 1) is hashed / absorbed / encrypted / decrypted as V mod p by every entry point: tags,
+ * messages, leaves, siblings, proof nodes, secrets, nonces, cipher elements.  Values that are
+ * COMPARED rather than hashed are compared as the 32 bytes they are: the stored MAC of a cipher
+ * (p252_decrypt_batch*), the expected root of a verification (p252_merkle{4,2}_verify_batch_device,
+ * _forest_ragged_verify_device, _multiproof_verify_device) — MAC + p or root + p is refused, as by the
+ * reference, whose scalar equality is limb equality.  Calls that only move scalars (openings and
+ * multiproof extraction, the leaves an update stores) copy their bytes.  Outputs that are computed
+ * are always fully reduced (bit-exact equality with the reference is limb equality); that includes
+ * the root of a one-leaf tree of a ragged forest (the leaf mod p: what re-hashing its opening of
+ * depth 0 gives), while the single-tree builds hand a lone leaf back as the 32 bytes it is.
+ * tests/test_edge_values_gpu.py holds every hashing kernel to this.
  *
  * Tag: the sponge capacity element state[0] = Safe::tag(...) = BlsScalar::hash_to_scalar(tag_input)
  * (scalar.rs:29-31) is an explicit INPUT of every hashing call.  A Rust caller passes the value

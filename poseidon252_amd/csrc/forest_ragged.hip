@@ -11,7 +11,8 @@
 //                      over several rows at once (gridDim.y).  First over n_t alone: a tree whose n_t takes the running sum of
 //                      the leaf counts before it past n_leaves is bad as well — that only happens when trees overlap behind
 //                      decreasing offsets, and it is what keeps every level within the host's bound n_leaves / a^l + n_trees.
-//                      The same pass writes the roots of bad trees (zero) and of single-leaf trees (the leaf).  Then over
+//                      The same pass writes the roots of bad trees (zero); k_fr_prep wrote those of single-leaf trees (the
+//                      leaf, reduced).  Then over
 //                      every level l at once: C_l = the scan of s_l (row l), and LO = the scan of levels_len(n_t) (row 0,
 //                      only when the caller's d_levels is written).
 //   k_fr_block_first   per level and 256-node block b: the tree that holds node 256 b — so a digest lane looks for its tree
@@ -70,14 +71,18 @@ __device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* total)
 }  // namespace
 
 // ---- validation ----
+// (with `roots`: the root of a single-leaf tree, its leaf REDUCED as every output is — what k_path_ragged gives for the tree's only
+// opening, of depth 0; the scan's first pass overwrites it with zero if the sum rule finds the tree bad after all)
 __global__ void __launch_bounds__(FR_BLOCK) k_fr_prep(const uint64_t* __restrict__ offsets, size_t n_trees, uint64_t n_leaves,
-                                                      uint64_t max_leaves, uint64_t* __restrict__ ntree) {
+                                                      uint64_t max_leaves, uint64_t* __restrict__ ntree,
+                                                      const Scalar32* __restrict__ leaves, Scalar32* __restrict__ roots) {
     const size_t t = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
     if (t >= n_trees) return;
     const uint64_t lo = offsets[t], hi = offsets[t + 1];
     const uint64_t n = hi - lo;
     const bool good = hi >= lo && n >= 1 && n <= max_leaves && hi <= n_leaves;
     ntree[t] = good ? n : 0;
+    if (good && n == 1 && roots) store_scalar(roots + t, load_scalar(leaves + lo));
 }
 
 // ---- the scan: rows row0 + blockIdx.y (row0 == FR_ROW_LEAVES: that one row), tiles of FR_TILE trees ----
@@ -111,7 +116,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_tiles(uint64_t* __restrict
     }
 }
 
-// FIRST (the leaf-count row): the sum rule above, then the roots of bad and single-leaf trees.  Otherwise: C[row][t] for every
+// FIRST (the leaf-count row): the sum rule above, then the roots of bad trees (zero).  Otherwise: C[row][t] for every
 // tree and C[row][n_trees] = the row's total.
 template <bool FIRST>
 __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_apply(uint64_t* __restrict__ ntree, size_t n_trees, unsigned row0, unsigned la,
@@ -143,12 +148,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_apply(uint64_t* __restrict
             } else if (n == 0) {
                 store_zero(roots + t);
                 if (n_bad) atomicAdd(n_bad, 1u);
-            } else if (n == 1) {
-                const uint4* src = reinterpret_cast<const uint4*>(leaves + offsets[t]);
-                uint4* dst = reinterpret_cast<uint4*>(roots + t);
-                dst[0] = src[0];
-                dst[1] = src[1];
-            }
+            }  // (n == 1: k_fr_prep wrote the root)
         } else {
             uint64_t* Crow = C + (size_t)row * (n_trees + 1);
             Crow[t] = run;
@@ -313,7 +313,7 @@ ForestRaggedPlan forest_ragged_plan(unsigned arity, size_t n_leaves, size_t n_tr
 static void launch_leaf_counts(const uint64_t* off, size_t n, size_t n_leaves, size_t max_leaves, size_t tiles, unsigned la, uint64_t* ntree,
                                uint64_t* tsum, uint64_t* C, const Scalar32* leaves, Scalar32* roots, unsigned* n_bad, hipStream_t st) {
     const dim3 blk(FR_BLOCK), grid((unsigned)tiles, 1);
-    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)n_leaves, (uint64_t)max_leaves, ntree);
+    hipLaunchKernelGGL(k_fr_prep, dim3(grid_for(n)), blk, 0, st, off, n, (uint64_t)n_leaves, (uint64_t)max_leaves, ntree, leaves, roots);
     hipLaunchKernelGGL(k_fr_tile_sums, grid, blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum);
     hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, tiles);
     hipLaunchKernelGGL(k_fr_scan_apply<true>, grid, blk, 0, st, ntree, n, FR_ROW_LEAVES, la, tsum, C, (uint64_t)n_leaves, off, leaves, roots, n_bad);

@@ -4,7 +4,7 @@
 // first made distinct, then hashed:
 //   k_fu_scatter   one lane per update: validated as k_fo_record validates an opening, through forest_tree_leaves (tree id <
 //                  n_trees, a good tree, leaf id < n_t — one count in *n_bad otherwise, nothing written), the new leaf stored (two 16-byte stores), a 16-byte
-//                  record (tree id, valid, leaf id) written as list 0; a single-leaf tree's root is its leaf
+//                  record (tree id, valid, leaf id) written as list 0; a single-leaf tree's root is its leaf, reduced
 //   k_fu_claim     level l = 1 .. D, one lane per record of list l - 1: the parent (t, i >> log2 arity), keyed by its slot in d_levels
 //                  (LO[t] + level_start(n_t, l) + i, unique across the forest), is claimed in an open-addressing table with one
 //                  64-bit compare-and-swap (empty -> key, linear probing, at most half full).  The lane whose swap installs the
@@ -58,10 +58,8 @@ __global__ void __launch_bounds__(FU_BLOCK) k_fu_scatter(const uint64_t* __restr
     const size_t at = 2 * (size_t)(offsets[ts] + leaf);  // (inside the tree: k_fr_prep checked offsets[t + 1] <= n_leaves)
     leaves[at] = lo;
     leaves[at + 1] = hi;
-    if (n == 1 && roots) {
-        roots[2 * ts] = lo;
-        roots[2 * ts + 1] = hi;
-    }
+    if (n == 1 && roots)  // (the leaf keeps its bytes; the root is reduced, as every output and as the forest's build writes it)
+        store_scalar(reinterpret_cast<Scalar32*>(roots) + ts, load_scalar(reinterpret_cast<const Scalar32*>(new_leaves) + i));
     list[i] = record(t, leaf);
 }
 
