@@ -18,6 +18,7 @@
 //   —                                               merkle_forest_ragged_openings_device / merkle_path_ragged_device /
 //                                                   merkle_forest_ragged_verify_device: openings out of such a forest
 //   —                                               merkle_forest_ragged_update_device: leaf updates anywhere in such a forest
+//   —                                               merkle_forest_ragged_append_device: leaves appended to its trees, into a new forest
 //   —                                               merkle_multiproof_device / merkle_multiproof_verify_device /
 //                                                   merkle_multiproof_bound: many leaves of one tree, one shared proof
 //
@@ -426,7 +427,8 @@ namespace detail {
 // slot can hold a merkle4 function — and the io-pattern of that arity's node hash (tag(): computed per call, as compute_tag is).
 #define P252_MERKLE_FNS(X, N)                                                                                                                \
     X(N, levels_len) X(N, depth) X(N, forest_ragged) X(N, forest_ragged_device) X(N, forest_ragged_openings_device) X(N, path_ragged_device) \
-    X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, multiproof_bound) X(N, multiproof_device) X(N, multiproof_verify_device)
+    X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, forest_ragged_append_device_into) X(N, multiproof_bound)        \
+    X(N, multiproof_device) X(N, multiproof_verify_device)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -540,6 +542,42 @@ inline void merkle_forest_ragged_update_device(void* d_leaves, std::size_t n_lea
     detail::check(m.forest_ragged_update_device(ctx.get(), m.tag().data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
                                                 d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_update_device");
+}
+
+// Leaves appended to the trees of such a forest, written INTO a new compact forest (p252_merkle{4,2}_forest_ragged_append_device_into):
+// `old_forest` exactly as the build took and filled it (read-only); tree t of the n_trees_new >= old.n_trees new trees receives
+// d_add[d_add_offsets[t] .. d_add_offsets[t + 1]) (n_trees_new + 1 device uint64).  `grown` names the caller's output buffers and their
+// capacities in scalars (leaves_cap >= old.n_leaves + n_add; levels_cap >= forest_append_levels_cap(..)): afterwards they hold byte for
+// byte a fresh build of the new forest — the unchanged nodes moved, only the nodes above a new leaf hashed.  A refused append or an
+// empty new tree is counted in *d_n_bad; *d_n_hashed (device uint64, zeroed by the caller) receives the digests computed.
+struct ForestView {  // the old forest
+    const void* d_leaves;
+    std::size_t n_leaves;
+    const void* d_offsets;
+    std::size_t n_trees, max_leaves;
+    const void* d_levels;
+};
+struct ForestOut {  // where the new one goes
+    void* d_leaves;
+    std::size_t leaves_cap;
+    void* d_offsets;
+    void* d_levels;
+    std::size_t levels_cap;
+    void* d_roots;
+};
+inline std::size_t forest_append_levels_cap(std::size_t n_leaves_total, std::size_t n_trees_new, std::size_t max_leaves_new, unsigned arity = 4) {
+    return n_leaves_total / (arity - 1) + n_trees_new * detail::merkle_abi("forest_append_levels_cap", arity).depth(max_leaves_new);
+}
+inline void merkle_forest_ragged_append_device(const ForestView& old_forest, const void* d_add, std::size_t n_add, const void* d_add_offsets,
+                                               std::size_t n_trees_new, std::size_t max_leaves_new, const ForestOut& grown, unsigned arity = 4,
+                                               Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* d_n_hashed = nullptr,
+                                               void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_append_device", arity);
+    detail::check(m.forest_ragged_append_device_into(ctx.get(), m.tag().data(), old_forest.d_leaves, old_forest.n_leaves, old_forest.d_offsets,
+                                                     old_forest.n_trees, old_forest.max_leaves, old_forest.d_levels, d_add, n_add, d_add_offsets,
+                                                     n_trees_new, max_leaves_new, grown.d_leaves, grown.leaves_cap, grown.d_offsets, grown.d_levels,
+                                                     grown.levels_cap, grown.d_roots, d_n_bad, d_n_hashed, stream),
+                  ctx.get(), "merkle_forest_ragged_append_device");
 }
 
 // Many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; the format is in poseidon252_hip.h).

@@ -14,6 +14,7 @@
 #include "../../include/poseidon252_hip.h"
 #include "blake2b.hpp"
 #include "ctx.hpp"
+#include "forest_append.h"
 #include "forest_openings.h"
 #include "forest_ragged.h"
 #include "forest_update.h"
@@ -852,6 +853,97 @@ int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
                                              void* d_n_hashed, void* hip_stream) {
     return forest_ragged_update_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
                                        d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, hip_stream);
+}
+
+// ---- leaves appended to the trees of such a forest, written as a new compact forest: clean nodes moved, dirty ones hashed once
+// (forest_append.hip).  The scratch — the indices of both forests, two words per tree, one scan row per level, the first-tree rows of
+// the relocation tiles; the dirty lists in the second buffer — is the pair of the calling stream; it holds ids and counts only ----
+namespace {
+struct ByteRange {
+    const void* p;
+    size_t bytes;
+    const char* name;
+};
+bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
+    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+}  // namespace
+
+static int forest_ragged_append_device_into(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                            const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_add,
+                                            size_t n_add, const void* d_add_offsets, size_t n_trees_new, size_t max_leaves_new,
+                                            void* d_leaves_new, size_t leaves_cap, void* d_offsets_new, void* d_levels_new, size_t levels_cap,
+                                            void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (n_trees_new == 0) return P252_OK;
+    const std::string who = "merkle_forest_ragged_append";
+    if (max_leaves_new == 0 || max_leaves_new < max_leaves)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves_new must be > 0 and >= max_leaves");
+    if (n_trees_new < n_trees) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_trees_new must be >= n_trees");
+    if (n_trees && max_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves must be > 0");
+    if (n_leaves > SIZE_MAX / 64 || n_add > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const size_t total = n_leaves + n_add;
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits, both forests)
+    if (int rc = forest_shape_check(ctx, who.c_str(), total, n_trees_new, max_leaves_new)) return rc;
+    if (leaves_cap > SIZE_MAX / 64 || levels_cap > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    if (leaves_cap < total) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": leaves_cap must be >= n_leaves + n_add");
+    const size_t levels_old = n_leaves / (arity - 1) + n_trees * forest_ragged_depth(max_leaves, arity);
+    const size_t levels_need = total / (arity - 1) + n_trees_new * forest_ragged_depth(max_leaves_new, arity);
+    if (levels_cap < levels_need)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT,
+                    who + ": levels_cap must be >= (n_leaves + n_add) / (arity - 1) + n_trees_new * depth(max_leaves_new)");
+    if (!tag || !d_add_offsets || !d_offsets_new || !d_roots || (total && !d_leaves_new) || (n_add && !d_add) ||
+        (n_trees && (!d_leaves || !d_offsets)) || (n_trees && max_leaves > 1 && !d_levels) || (max_leaves_new > 1 && !d_levels_new))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_add) || misaligned(d_leaves_new) || misaligned(d_levels_new) ||
+        misaligned(d_roots))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_add_offsets, 8) || misaligned_to(d_offsets_new, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT,
+                    who + ": d_offsets, d_add_offsets, d_offsets_new and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
+    const ByteRange in[] = {{d_leaves, n_trees ? n_leaves * 32 : 0, "d_leaves"},
+                            {d_offsets, n_trees ? (n_trees + 1) * 8 : 0, "d_offsets"},
+                            {d_levels, n_trees ? levels_old * 32 : 0, "d_levels"},
+                            {d_add, n_add * 32, "d_add"},
+                            {d_add_offsets, (n_trees_new + 1) * 8, "d_add_offsets"}};
+    const ByteRange out[] = {{d_leaves_new, leaves_cap * 32, "d_leaves_new"}, {d_offsets_new, (n_trees_new + 1) * 8, "d_offsets_new"},
+                             {d_levels_new, levels_cap * 32, "d_levels_new"}, {d_roots, n_trees_new * 32, "d_roots"},
+                             {d_n_bad, 4, "d_n_bad"},                         {d_n_hashed, 8, "d_n_hashed"}};
+    for (const ByteRange& o : out)
+        for (const ByteRange& i : in)
+            if (ranges_overlap(o, i)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + o.name + " overlaps " + i.name);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestAppendPlan plan = forest_append_plan(arity, n_leaves, n_trees, max_leaves, n_add, n_trees_new, max_leaves_new, leaves_cap);
+    return with_stream_scratch(ctx, who, st, plan.meta_bytes(), plan.list_bytes, [&](p252_ctx::LevelSet& set) {
+        return launch_forest_append(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, d_levels, d_add, d_add_offsets, d_leaves_new, d_offsets_new,
+                                    d_levels_new, d_roots, d_n_bad, d_n_hashed, set.buf[0], set.buf[1], st);
+    });
+}
+
+int p252_merkle4_forest_ragged_append_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                  const void* d_add, size_t n_add, const void* d_add_offsets, size_t n_trees_new,
+                                                  size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                                  void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad, void* d_n_hashed,
+                                                  void* hip_stream) {
+    return forest_ragged_append_device_into(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, n_add, d_add_offsets,
+                                            n_trees_new, max_leaves_new, d_leaves_new, leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots,
+                                            d_n_bad, d_n_hashed, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_append_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                  const void* d_add, size_t n_add, const void* d_add_offsets, size_t n_trees_new,
+                                                  size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                                  void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad, void* d_n_hashed,
+                                                  void* hip_stream) {
+    return forest_ragged_append_device_into(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, n_add, d_add_offsets,
+                                            n_trees_new, max_leaves_new, d_leaves_new, leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots,
+                                            d_n_bad, d_n_hashed, hip_stream);
 }
 
 // (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)

@@ -1,0 +1,43 @@
+// forest_append.h — launch interface between api.cpp and forest_append.hip: leaves appended to the trees of a built forest of trees
+// of DIFFERENT sizes, written as a new compact forest (p252_merkle{4,2}_forest_ragged_append_device_into).  Clean nodes are moved,
+// only the nodes above a new leaf are hashed (by forest_update.hip's digest kernels, on lists this unit makes).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "forest_ragged.h"
+#include "kernels.h"
+
+namespace p252 {
+
+constexpr unsigned FOREST_APPEND_SCAN_TILE = 2048;  // trees per block of the unit's scans
+constexpr unsigned FOREST_APPEND_MOVE_TILE = 512;   // scalars (leaves or nodes) per block of the two relocation kernels
+
+// The host's view of one call, all derived from (n_leaves, n_trees, n_add, n_trees_new, max_leaves_new).  N = n_leaves + n_add bounds
+// the leaves of the new forest (the old good trees hold at most n_leaves: the build's sum rule; the accepted appends at most n_add:
+// this unit's).  Level l (1 .. depth) of the new forest has at most bound[l] = N / arity^l + n_trees_new nodes (ForestRaggedPlan) and
+// at most n_add / arity^l + 2 n_trees_new dirty ones (ceil((n + m) / B) - floor(n / B) <= floor(m / B) + 2): in[l] = the smaller.
+struct ForestAppendPlan {
+    unsigned arity = 4, log2a = 2, depth = 0;
+    size_t n_trees_old = 0, n_trees = 0, n_leaves_old = 0, n_add = 0, leaves = 0;  // leaves = N
+    size_t max_leaves_old = 0, max_leaves = 0, leaves_cap = 0;
+    size_t nodes = 0;  // bound of the used part of the new d_levels, in scalars: N / (arity - 1) + n_trees_new * depth
+    size_t in[FOREST_RAGGED_MAX_DEPTH + 1] = {};        // most records of level l's dirty list
+    size_t list_off[FOREST_RAGGED_MAX_DEPTH + 1] = {};  // where level l's list starts, in records
+    size_t tiles = 0, leaf_tiles = 0, node_tiles = 0;
+    size_t index_old_bytes = 0, index_new_bytes = 0, work_bytes = 0, list_bytes = 0;
+    size_t meta_bytes() const { return index_old_bytes + index_new_bytes + work_bytes; }  // the two indices and the unit's own words
+};
+ForestAppendPlan forest_append_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t n_add, size_t n_trees_new,
+                                    size_t max_leaves_new, size_t leaves_cap);
+
+// The whole append on `st`: meta = plan.meta_bytes() and lists = plan.list_bytes of scratch.  n_bad (uint32) and n_hashed (uint64)
+// may be null; leaves / offsets / levels may be null when the old forest has no tree, add when n_add == 0, the levels when no tree
+// of that forest can have one.
+hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const ForestAppendPlan& plan, const void* leaves, const void* offsets,
+                                const void* levels, const void* add, const void* add_offsets, void* leaves_new, void* offsets_new,
+                                void* levels_new, void* roots, void* n_bad, void* n_hashed, void* meta, void* lists, hipStream_t st);
+
+}  // namespace p252

@@ -25,6 +25,26 @@ struct ForestUpdatePlan {
 };
 ForestUpdatePlan forest_update_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
 
+// One level's digests on a list the caller made: record g < *count of `list` (16 bytes: tree id, valid, node index low and high, as
+// k_fu_claim writes them) names node i of level `level` >= 1 of tree t; it is hashed from level - 1 of the tree (its leaves for level
+// 1) into the tree's block of `levels`, and into roots[t] when it is the tree's top.  bound = the host's bound of *count: it sizes
+// the launch and picks the kernel.  *n_hashed (may be null, as roots) grows by *count.  ntree / lo / offsets: the forest's index.
+struct ForestDigestList {
+    const void* list = nullptr;
+    const unsigned long long* count = nullptr;
+    size_t bound = 0;
+    const uint64_t* ntree = nullptr;
+    const uint64_t* lo = nullptr;
+    const void* offsets = nullptr;
+    const void* leaves = nullptr;
+    void* levels = nullptr;
+    void* roots = nullptr;
+    void* n_hashed = nullptr;
+    unsigned level = 1;
+};
+hipError_t launch_forest_digest_list(const int32_t* tab, const TagArg& tag, unsigned arity, unsigned log2a, const ForestDigestList& list,
+                                     hipStream_t st);
+
 // The whole update on `st`: ntree / lo = the forest's index (launch_forest_ragged_index); ids = plan.ids_bytes() and table =
 // plan.table_bytes of scratch.  roots, n_bad (uint32), n_hashed (uint64) may be null; levels may be null when plan.depth == 0.
 hipError_t launch_forest_update(const int32_t* tab, const TagArg& tag, const ForestUpdatePlan& plan, void* leaves, const void* offsets,

@@ -201,6 +201,29 @@ ForestUpdatePlan forest_update_plan(unsigned arity, size_t n_leaves, size_t n_tr
     return p;
 }
 
+// one level's digests over a list made by the caller (launch_forest_update below, forest_append.hip): the 8-lane kernel when the
+// list's host bound cannot fill the chip (the coop8 rule of kernels.h)
+hipError_t launch_forest_digest_list(const int32_t* tab, const TagArg& tag, unsigned arity, unsigned log2a, const ForestDigestList& d,
+                                     hipStream_t st) {
+    if (d.bound == 0) return hipSuccess;
+    FuLevel P;
+    P.list = static_cast<const uint4*>(d.list);
+    P.count = d.count;
+    P.ntree = d.ntree;
+    P.LO = d.lo;
+    P.offsets = static_cast<const uint64_t*>(d.offsets);
+    P.leaves = static_cast<const Scalar32*>(d.leaves);
+    P.levels = static_cast<Scalar32*>(d.levels);
+    P.roots = static_cast<Scalar32*>(d.roots);
+    P.n_hashed = static_cast<unsigned long long*>(d.n_hashed);
+    P.level = d.level;
+    P.la = log2a;
+    const bool coop = coop8(d.bound);
+    P.lanes = coop ? d.bound * 8 : d.bound;
+    if (arity == 4) return launch(coop ? k_fu_digest_coop<4> : k_fu_digest<4>, P.lanes, st, tab, tag, P);
+    return launch(coop ? k_fu_digest_coop<2> : k_fu_digest<2>, P.lanes, st, tab, tag, P);
+}
+
 hipError_t launch_forest_update(const int32_t* tab, const TagArg& tag, const ForestUpdatePlan& p, void* leaves, const void* offsets,
                                 const uint64_t* ntree, const uint64_t* lo, void* levels, const void* tree_ids, const void* leaf_ids,
                                 const void* new_leaves, void* roots, void* n_bad, void* n_hashed, void* ids, void* table, hipStream_t st) {
@@ -228,24 +251,19 @@ hipError_t launch_forest_update(const int32_t* tab, const TagArg& tag, const For
                            list[l & 1], count + l);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        FuLevel P;
-        P.list = list[l & 1];
-        P.count = count + l;
-        P.ntree = ntree;
-        P.LO = lo;
-        P.offsets = off;
-        P.leaves = static_cast<const Scalar32*>(leaves);
-        P.levels = static_cast<Scalar32*>(levels);
-        P.roots = static_cast<Scalar32*>(roots);
-        P.n_hashed = static_cast<unsigned long long*>(n_hashed);
-        P.level = l;
-        P.la = p.log2a;
-        const bool coop = coop8(p.in[l]);
-        P.lanes = coop ? p.in[l] * 8 : p.in[l];
-        if (p.arity == 4)
-            e = launch(coop ? k_fu_digest_coop<4> : k_fu_digest<4>, P.lanes, st, tab, tag, P);
-        else
-            e = launch(coop ? k_fu_digest_coop<2> : k_fu_digest<2>, P.lanes, st, tab, tag, P);
+        ForestDigestList d;
+        d.list = list[l & 1];
+        d.count = count + l;
+        d.bound = p.in[l];
+        d.ntree = ntree;
+        d.lo = lo;
+        d.offsets = offsets;
+        d.leaves = leaves;
+        d.levels = levels;
+        d.roots = roots;
+        d.n_hashed = n_hashed;
+        d.level = l;
+        e = launch_forest_digest_list(tab, tag, p.arity, p.log2a, d, st);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -520,6 +520,48 @@ class Context:
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
+    def merkle4_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
+                                            max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None):
+        """leaves appended to the trees of a forest merkle_forest_ragged_device built with d_levels, written INTO a new compact forest
+        (p252_merkle4_forest_ragged_append_device_into): d_leaves, d_offsets, n_trees, max_leaves, d_levels exactly as the build took
+        them (read-only; None when n_trees == 0); tree t of the n_trees_new >= n_trees new trees receives
+        d_add[d_add_offsets[t]:d_add_offsets[t+1]] (n_trees_new + 1 int64/uint64; d_add None: a compaction copy).  Written: d_leaves_new
+        (its length is the capacity, at least the old leaves plus d_add), d_offsets_new (n_trees_new + 1), d_levels_new (the bound of
+        merkle_forest_ragged_device for the new shape), d_roots (n_trees_new, 4) — byte for byte a fresh build of the new forest,
+        with the unchanged nodes moved and only the others hashed.  A refused append or an empty new tree is counted in d_n_bad (a
+        zeroed device int32/uint32, optional); d_n_hashed (a zeroed device int64/uint64, optional) receives the digests computed."""
+        self._forest_ragged_append_device("merkle4_forest_ragged_append_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees, max_leaves,
+                                          d_levels, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
+                                          d_levels_new, d_roots, d_n_bad, d_n_hashed)
+
+    def merkle2_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
+                                            max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None):
+        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
+        self._forest_ragged_append_device("merkle2_forest_ragged_append_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees, max_leaves,
+                                          d_levels, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
+                                          d_levels_new, d_roots, d_n_bad, d_n_hashed)
+
+    def _forest_ragged_append_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
+                                     max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed):
+        none = n_trees == 0  # no old forest
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 0, null_ok=none)
+        n_leaves = _n_scalars(d_leaves) if d_leaves is not None else 0
+        add = _dev_ptr(self, f, "d_add", d_add, 0, null_ok=True)
+        n_add = _n_scalars(d_add) if d_add is not None else 0
+        depth, depth_new = a.depth(max_leaves) if not none else 0, a.depth(max_leaves_new)
+        leaves_new = _dev_ptr(self, f, "d_leaves_new", d_leaves_new, (n_leaves + n_add) * 32, null_ok=n_leaves + n_add == 0)
+        levels_need = a.forest_levels_bytes(n_leaves + n_add, n_trees_new, depth_new)
+        levels_new = _dev_ptr(self, f, "d_levels_new", d_levels_new, levels_need, null_ok=depth_new == 0)
+        self._check(a.fn("forest_ragged_append_device_into")(
+            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8, null_ok=none), n_trees,
+            max_leaves, _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            add, n_add, _dev_ptr(self, f, "d_add_offsets", d_add_offsets, (n_trees_new + 1) * 8, elem=8), n_trees_new, max_leaves_new,
+            leaves_new, _n_scalars(d_leaves_new) if d_leaves_new is not None else 0,
+            _dev_ptr(self, f, "d_offsets_new", d_offsets_new, (n_trees_new + 1) * 8, elem=8),
+            levels_new, _n_scalars(d_levels_new) if d_levels_new is not None else levels_need // 32,  # (no level: nothing is written)
+            _dev_ptr(self, f, "d_roots", d_roots, n_trees_new * 32), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
+
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
         f = "truncate250_device"

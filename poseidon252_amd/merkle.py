@@ -123,6 +123,37 @@ def merkle4_openings(leaves, levels, indices):
     return sib, pos
 
 
+def forest_ragged_append(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new=None,
+                         max_leaves_new=None, arity=4):
+    """Leaves appended to the trees of a built forest (Context.merkle{4,2}_forest_ragged_append_device): the forest = torch CUDA tensors
+    as Context.merkle_forest_ragged_device took and filled them; tree t receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (d_add None:
+    a compaction copy).  n_trees_new defaults to the trees d_add_offsets names, max_leaves_new to max_leaves plus the scalars of d_add (no
+    append can then be too long).  Sizes and allocates the new forest and returns (d_leaves_new, d_offsets_new, d_levels_new, d_roots,
+    d_n_bad (1,) int32, d_n_hashed (1,) int64), all on the device; d_leaves_new is exact-sized (old leaves plus d_add: rows past
+    d_offsets_new[-1] are unused), d_levels_new holds the bound of the new shape.  No synchronisation."""
+    import torch
+    a = _arity("forest_ragged_append", arity)
+    ctx = ctx or Context.default()
+    dev = d_add_offsets.device
+    n_add = _n_scalars(d_add) if d_add is not None else 0
+    n_leaves = _n_scalars(d_leaves) if d_leaves is not None else 0
+    if n_trees_new is None:
+        n_trees_new = d_add_offsets.numel() - 1
+    if max_leaves_new is None:
+        max_leaves_new = max(max_leaves + n_add, 1)
+    total = n_leaves + n_add
+    leaves_new = torch.empty((total, 4), dtype=torch.int64, device=dev)
+    offsets_new = torch.empty(n_trees_new + 1, dtype=torch.int64, device=dev)
+    levels_new = torch.empty((a.forest_levels_bytes(total, n_trees_new, a.depth(max_leaves_new)) // 32, 4), dtype=torch.int64, device=dev)
+    roots = torch.empty((n_trees_new, 4), dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
+    call = ctx.merkle4_forest_ragged_append_device if arity == 4 else ctx.merkle2_forest_ragged_append_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets,
+         n_trees_new, max_leaves_new, leaves_new if total else None, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad, n_hashed)
+    return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
+
+
 def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
     as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are

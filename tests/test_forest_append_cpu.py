@@ -1,0 +1,308 @@
+"""Leaves appended to the trees of a forest of trees of different sizes (p252_merkle{4,2}_forest_ragged_append_device_into;
+csrc/forest_append.hip) — what can be checked without a GPU: the numpy model the GPU tests compare the call with agrees with a
+brute-force construction of both trees and with trees hashed by the big-int model of the permutation; the two entry points are
+declared, exported and mirrored in the Rust FFI under ABI 9, under a name the refusal table of the `_device(` symbols does not catch;
+forest_append.hip compiles for gfx950 within its resource targets and hashes nothing itself; the host refusals, as a table of their
+own; the Python methods validate every buffer before the library is reached and hand the C call the right sizes."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
+sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
+from forest_append_bench import forest_append_model, level_widths, model_leaves  # noqa: E402
+from helpers.kernel_resources import kernel_resources  # noqa: E402
+from test_binding_checks import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
+
+SYMBOLS = ("p252_merkle4_forest_ragged_append_device_into", "p252_merkle2_forest_ragged_append_device_into")
+N_ARGS = 22
+ERR_HIP = -4
+
+
+# ---- the model ----
+def _brute_levels(n, arity):
+    """levels 1.. of a tree of n leaves, each node the tuple of its children (None: a missing child); leaf i is ("leaf", i)"""
+    cur, out = [("leaf", i) for i in range(n)], []
+    while len(cur) > 1:
+        cur = [tuple(cur[j * arity + c] if j * arity + c < len(cur) else None for c in range(arity)) for j in range((len(cur) + arity - 1) // arity)]
+        out.append(cur)
+    return out
+
+
+def _single(n, m, arity):
+    return forest_append_model([0, n], n, max(n, 1), [0, m], m, max(n + m, 1), arity)
+
+
+def test_model_agrees_with_a_brute_force_construction_of_both_trees():
+    for arity in (4, 2):
+        for n in range(70):
+            old = _brute_levels(n, arity)
+            for m in range(70):
+                new = _brute_levels(n + m, arity)
+                M = _single(n, m, arity)
+                assert M["n_old"] == [n] and M["m"] == [m] and M["offsets_new"].tolist() == [0, n + m]
+                assert M["n_bad"] == (1 if n + m == 0 else 0)
+                assert M["leaf_src"].tolist() == list(range(n)) + [-1 - i for i in range(m)]
+                # every slot of the new tree: clean iff the same node sits at the same (level, index) of the old tree
+                slot, want_dirty, old_start = 0, {}, 0
+                assert len(M["node_src"]) == sum(len(lv) for lv in new) and len(M["node_id"]) == len(M["node_src"])
+                for l, lv in enumerate(new, 1):
+                    for j, node in enumerate(lv):
+                        clean = l <= len(old) and j < len(old[l - 1]) and old[l - 1][j] == node
+                        assert M["node_id"][slot] == (0, l, j)
+                        assert M["node_src"][slot] == (old_start + j if clean else -1), (arity, n, m, l, j)
+                        assert clean == (m == 0 or j < n // arity ** l)  # the rule of the header
+                        if not clean:
+                            want_dirty.setdefault(l, []).append((0, j))
+                        slot += 1
+                    old_start += len(old[l - 1]) if l <= len(old) else 0
+                assert M["dirty"] == want_dirty
+                count = sum(-(-(n + m) // arity ** l) - n // arity ** l for l in range(1, len(new) + 1)) if m else 0
+                assert M["n_hashed"] == sum(len(v) for v in want_dirty.values()) == count, (arity, n, m)
+
+
+def test_model_of_a_forest_new_trees_refusals_and_the_sum_rule():
+    # old forest: offsets start at 5; tree 1 empty, tree 3 longer than max_leaves (bad: its leaves are dropped)
+    off, n_leaves, max_leaves = [5, 8, 8, 12, 30, 31], 40, 10
+    # appends to 7 trees: tree 0 +2, tree 1 (empty) +3, tree 2 decreasing (refused), tree 3 (bad) +1, tree 4 too long, two new trees
+    aoff, n_add = [0, 2, 5, 4, 5, 20, 20, 26], 26
+    M = forest_append_model(off, n_leaves, max_leaves, aoff, n_add, 12, 4)
+    assert M["n_old"] == [3, 0, 4, 0, 1, 0, 0]
+    assert M["m"] == [2, 3, 0, 1, 0, 0, 6] and M["refused"] == [False, False, True, False, True, False, False]
+    assert M["offsets_new"].tolist() == [0, 5, 8, 12, 13, 14, 14, 20]
+    assert M["n_bad"] == 3  # two refused, one empty
+    leaves, add = np.arange(40 * 4).reshape(40, 4), 1000 + np.arange(26 * 4).reshape(26, 4)
+    got = model_leaves(M, leaves, add)
+    assert np.array_equal(got[:5], np.concatenate([leaves[5:8], add[0:2]])) and np.array_equal(got[5:8], add[2:5])
+    assert np.array_equal(got[8:12], leaves[8:12]) and np.array_equal(got[12:13], add[4:5]) and np.array_equal(got[13:14], leaves[30:31])
+    assert np.array_equal(got[14:20], add[20:26])
+    # the sum rule: ranges that overlap behind a decrease cannot take the forest past n_add
+    M = forest_append_model([], 0, 0, [0, 5, 2, 7], 7, 100, 2)
+    assert M["m"] == [5, 0, 0] and M["refused"] == [False, True, True] and M["n_bad"] == 2
+    # past n_add
+    M = forest_append_model([], 0, 0, [0, 3, 9], 8, 100, 2)
+    assert M["m"] == [3, 0] and M["refused"] == [False, True]
+
+
+def _pymodel_levels(leaves, arity, tag):
+    import pymodel
+    cur, out = list(leaves), []
+    while len(cur) > 1:
+        cur = [pymodel.sponge(tag, [cur[j * arity + c] if j * arity + c < len(cur) else 0 for c in range(arity)], 1)[0]
+               for j in range((len(cur) + arity - 1) // arity)]
+        out += cur
+    return out
+
+
+@pytest.mark.parametrize("arity,n,m", [(4, 5, 3), (4, 16, 1), (4, 1, 4), (2, 5, 2), (2, 8, 1), (2, 3, 0)])
+def test_model_against_trees_hashed_by_the_big_int_model(oracle_mod, arity, n, m):
+    """the clean slots of the grown tree hold the old tree's values, the dirty ones do not; one root of each shape is the oracle's"""
+    import pymodel
+    from poseidon252_amd import merkle
+    R = 1 << 256
+    to_int = lambda a: [int.from_bytes(np.ascontiguousarray(s).tobytes(), "little") * pow(R, -1, pymodel.P) % pymodel.P for s in a]  # noqa: E731
+    tag_limbs = merkle.merkle4_tag() if arity == 4 else merkle.merkle2_tag()
+    tag = to_int([tag_limbs])[0]
+    limbs = oracle_mod.fill_random(0xA99 + n, n + m)
+    vals = to_int(limbs)
+    old, new = _pymodel_levels(vals[:n], arity, tag), _pymodel_levels(vals, arity, tag)
+    M = _single(n, m, arity)
+    assert len(new) == len(M["node_src"])
+    for slot, src in enumerate(M["node_src"].tolist()):
+        t, l, j = M["node_id"][slot]
+        if src >= 0:
+            assert new[slot] == old[src], (slot, src)
+        else:  # a new leaf below it: not the value the old tree had at (l, j), if it had one
+            w_old = level_widths(n, arity)
+            if l <= len(w_old) and j < w_old[l - 1]:
+                assert new[slot] != old[sum(w_old[:l - 1]) + j], slot
+    tree = oracle_mod.merkle4_tree if arity == 4 else oracle_mod.merkle2_tree
+    root = tree(tag_limbs, limbs)[0]
+    assert (new[-1] if new else vals[0]) == to_int([root])[0]
+
+
+# ---- the symbols ----
+def test_two_symbols_declared_exported_and_in_sys_rs():
+    from poseidon252_amd import _lib
+    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
+    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
+    for name in SYMBOLS:
+        m = re.search(r"\bint %s\s*\((.*?)\);" % name, header, flags=re.S)
+        assert m, name
+        assert m.group(1).count(",") + 1 == N_ARGS, name
+        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
+        assert len(_lib.PROTOTYPES[name][0]) == N_ARGS, name
+        assert rust[name].count(":") == N_ARGS, (name, rust[name])
+    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
+    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_rust_sys.py"), "--check"], stdout=subprocess.DEVNULL)
+    # no new name that the refusal table of the `_device(` symbols would have to hold: that table stays as it is
+    declared = set(re.findall(r"\b(p252_[a-z0-9_]+_device)\s*\(", header))
+    table = {line.split("\t")[0] for line in open(os.path.join(ROOT, "tests", "golden", "api_refusals.txt")).read().splitlines()}
+    assert declared == table and not any("append" in s for s in declared)
+
+
+# ---- the kernels ----
+@pytest.fixture(scope="module")
+def compiled():
+    return kernel_resources("forest_append.hip", os.path.join(CSRC, "_gen", "forest_append_test.s"))
+
+
+def test_kernels_meet_resource_targets(compiled):
+    res, isa = compiled
+    assert len(res) >= 8 and all("k_fa_" in n for n in res), sorted(res)
+    for want in ("k_fa_sizes", "k_fa_scan_apply", "k_fa_tile_first", "k_fa_move_leaves", "k_fa_move_nodes", "k_fa_roots", "k_fa_expand"):
+        assert any(want in n for n in res), want
+    for name, v in res.items():  # data movement and bookkeeping: no private memory, a quarter of the register file at the most
+        assert v["scratch"] == 0 and v["agpr"] == 0 and v["vgpr"] <= 64, (name, v)
+    assert "scratch_" not in isa
+
+
+def test_the_unit_hashes_nothing_itself():
+    from poseidon252_amd import build as b
+    import edgecases
+    assert "forest_append.hip" in b.SOURCES and "forest_append.h" in b.HEADERS
+    src = open(os.path.join(CSRC, "forest_append.hip")).read()
+    for word in ("hades_permute", "node_digest_coop", "asm"):
+        assert word not in src, word
+    assert "launch_forest_digest_list" in src and "launch_forest_ragged_index" in src
+    assert not re.search(r"\bk_fr_\w+\s*[(<]", src) and not re.search(r"\bk_fu_\w+\s*[(<]", src)  # the neighbours' kernels through their launchers only
+    assert set(edgecases.hashing_kernels()) <= set(edgecases.named_kernels())
+    res, _ = kernel_resources("forest_update.hip", os.path.join(CSRC, "_gen", "forest_update_append_test.s"))
+    assert len(res) == 6, sorted(res)  # the new launcher added no kernel
+
+
+# ---- the host refusals ----
+def _rows(text):
+    rows = [line.split("\t") for line in text.splitlines()]
+    assert all(len(r) == 4 for r in rows), [r for r in rows if len(r) != 4][:3]
+    return [(r[0], r[1], int(r[2]), r[3].split(": ")[0] if int(r[2]) == ERR_HIP else r[3]) for r in rows]
+
+
+@pytest.fixture(scope="module")
+def table(tmp_path_factory):
+    from poseidon252_amd import build as B
+    exe = str(tmp_path_factory.mktemp("append_refusals") / "append_refusals")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(B.ROCM, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "append_refusals.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"), "-lposeidon252_hip",
+                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
+    return _rows(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+
+
+def test_every_refusal_row_equals_the_recorded_one(table):
+    golden = _rows(open(os.path.join(ROOT, "tests", "golden", "append_refusals.txt")).read())
+    assert [r[:2] for r in table] == [r[:2] for r in golden]
+    assert [r for r, g in zip(table, golden) if r != g] == []
+
+
+def test_refusal_table_has_a_control_row_and_every_host_refusal(table):
+    for sym in SYMBOLS:
+        by = {r[1]: r[2:] for r in table if r[0] == sym}
+        assert by["control"] == (ERR_HIP, "hipSetDevice(ctx->device)")  # past validation: without this the other rows prove nothing
+        refused = lambda case, word: by[case][0] == -3 and word in by[case][1]  # noqa: E731
+        accepted = lambda case: by[case] == by["control"]  # noqa: E731
+        assert by["ctx=NULL"][0] == -3 and by["n_trees_new=0"] == (0, "")
+        assert refused("max_leaves_new=max_leaves-1", "max_leaves_new") and accepted("max_leaves_new=max_leaves")
+        assert refused("n_trees_new=n_trees-1", "n_trees_new") and accepted("n_trees_new=n_trees")
+        assert refused("leaves_cap=n_leaves+n_add-1", "leaves_cap") and accepted("leaves_cap=n_leaves+n_add+7")
+        assert refused("levels_cap=need-1", "levels_cap") and accepted("levels_cap=need+1")
+        assert refused("max_leaves=1,max_leaves_new=2,d_levels=d_levels_new=NULL", "NULL") and accepted("max_leaves=1,d_levels=NULL")
+        assert accepted("max_leaves=max_leaves_new=1,d_levels=d_levels_new=NULL") and accepted("n_add=0,d_add=NULL")
+        assert accepted("n_trees=0,d_leaves=d_offsets=d_levels=NULL,n_leaves=0")
+        for case in ("n_leaves=SIZE_MAX/64+1", "n_add=SIZE_MAX", "leaves_cap=SIZE_MAX/64+1", "n_trees_new=SIZE_MAX/8/66+1"):
+            assert refused(case, "size overflow"), case
+        for buf in ("d_leaves", "d_offsets", "d_levels", "d_add", "d_add_offsets", "d_leaves_new", "d_offsets_new", "d_levels_new", "d_roots"):
+            assert refused(buf + "=NULL", "NULL buffer"), buf
+        for buf in ("d_n_bad", "d_n_hashed"):
+            assert accepted(buf + "=NULL"), buf
+        misaligned = [c for c in by if re.fullmatch(r"d_\w+\+\d", c)]
+        assert len(misaligned) == 11 and all(refused(c, "aligned") for c in misaligned)
+        outs = ("d_leaves_new", "d_offsets_new", "d_levels_new", "d_roots", "d_n_bad", "d_n_hashed")
+        ins = ("d_leaves", "d_offsets", "d_levels", "d_add", "d_add_offsets")
+        for o in outs:  # every output against every input, on both sides of the input's end
+            for i in ins:
+                assert refused("%s=%s+last" % (o, i), "%s overlaps %s" % (o, i)), (o, i)
+                assert accepted("%s=%s+end" % (o, i)), (o, i)
+        assert refused("d_roots=d_add-16", "overlaps") and accepted("d_roots=d_add-4*32")
+
+
+# ---- the Python methods ----
+@pytest.mark.parametrize("arity", [4, 2])
+def test_python_methods_refuse_cpu_tensors_and_pass_the_sizes(recorder, monkeypatch, arity):
+    ctx = _no_device_context()
+    tag = np.zeros(4, dtype=np.uint64)
+    i32 = torch.int32
+    n_leaves, n_add, n_trees, n_trees_new, max_leaves, max_new, cap = 16, 8, 2, 3, 9, 12, 30
+    D = {4: 2, 2: 4}[arity]
+    levels_cap = 24 // (arity - 1) + n_trees_new * D + 5
+    args = dict(d_leaves=dev(n=n_leaves * 4), d_offsets=dev(), d_levels=dev(n=256), d_add=dev(n=n_add * 4), d_add_offsets=dev(),
+                d_leaves_new=dev(n=cap * 4), d_offsets_new=dev(), d_levels_new=dev(n=levels_cap * 4), d_roots=dev(), d_n_bad=dev(i32), d_n_hashed=dev())
+    method = ctx.merkle4_forest_ragged_append_device if arity == 4 else ctx.merkle2_forest_ragged_append_device
+
+    def call(a):
+        return method(tag, a["d_leaves"], a["d_offsets"], n_trees, max_leaves, a["d_levels"], a["d_add"], a["d_add_offsets"], n_trees_new, max_new,
+                      a["d_leaves_new"], a["d_offsets_new"], a["d_levels_new"], a["d_roots"], a["d_n_bad"], a["d_n_hashed"])
+    symbol = "p252_merkle%d_forest_ragged_append_device_into" % arity
+    call(args)
+    assert recorder.calls == [symbol]  # the control: the library is reached, once, under this arity's symbol
+    del recorder.calls[:]
+    n_refused = 0
+    for where, bad in with_cpu_tensor(args):
+        with pytest.raises(ValueError, match=where + " is on cpu"):
+            call(bad)
+        assert recorder.calls == [], where
+        n_refused += 1
+    assert n_refused == 11
+    for name, short in (("d_offsets", dev(n=n_trees)), ("d_add_offsets", dev(n=n_trees_new)), ("d_offsets_new", dev(n=n_trees_new)),
+                        ("d_leaves_new", dev(n=(n_leaves + n_add) * 4 - 1)), ("d_levels_new", dev(n=(24 // (arity - 1) + n_trees_new * D) * 4 - 1)),
+                        ("d_roots", dev(n=n_trees_new * 4 - 1)), ("d_levels", dev(n=(16 // (arity - 1) + n_trees * D) * 4 - 1))):
+        with pytest.raises(ValueError, match=name + " holds"):
+            call(dict(args, **{name: short}))
+    for name in ("d_offsets", "d_add_offsets", "d_offsets_new", "d_n_hashed"):
+        with pytest.raises(ValueError, match=name + " needs 8-byte elements"):
+            call(dict(args, **{name: dev(i32)}))
+    assert recorder.calls == []
+    assert "arity" not in __import__("inspect").signature(method).parameters
+    # the sizes the C call receives
+    seen = []
+    from poseidon252_amd import _lib
+    real = _lib.lib().real
+
+    class Spy:
+        def __getattr__(self, name):
+            if name == symbol:
+                return lambda *a: seen.append(a) or 0
+            return getattr(real, name)
+    monkeypatch.setattr(_lib, "_lib", Spy())
+    call(args)
+    call(dict(args, d_add=None, d_n_bad=None, d_n_hashed=None))
+    a, b = seen
+    ptr = lambda t: t.data_ptr()  # noqa: E731
+    assert a[2:] == (ptr(args["d_leaves"]), n_leaves, ptr(args["d_offsets"]), n_trees, max_leaves, ptr(args["d_levels"]), ptr(args["d_add"]), n_add,
+                     ptr(args["d_add_offsets"]), n_trees_new, max_new, ptr(args["d_leaves_new"]), cap, ptr(args["d_offsets_new"]),
+                     ptr(args["d_levels_new"]), levels_cap, ptr(args["d_roots"]), ptr(args["d_n_bad"]), ptr(args["d_n_hashed"]), 0)
+    assert b[8:10] == (None, 0) and b[-4:] == (ptr(args["d_roots"]), None, None, 0)
+
+
+def test_cpp_mirror_test_compiles(tmp_path, oracle_mod):
+    exe = str(tmp_path / "test_forest_append_api")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "test_forest_append_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
+                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
+                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
+    assert os.path.exists(exe)
+
+
+def test_bench_tool_parses():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_append_bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--quick" in r.stdout, r.stderr
