@@ -21,6 +21,8 @@
 //   —                                               merkle_forest_ragged_append_device: leaves appended to its trees, into a new forest
 //   —                                               merkle_multiproof_device / merkle_multiproof_verify_device /
 //                                                   merkle_multiproof_bound: many leaves of one tree, one shared proof
+//   —                                               merkle_forest_ragged_multiproof_device / _verify_device / _bound: leaves of many
+//                                                   trees of a ragged forest, one tree-major shared proof
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -428,7 +430,8 @@ namespace detail {
 #define P252_MERKLE_FNS(X, N)                                                                                                                \
     X(N, levels_len) X(N, depth) X(N, forest_ragged) X(N, forest_ragged_device) X(N, forest_ragged_openings_device) X(N, path_ragged_device) \
     X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, forest_ragged_append_device_into) X(N, multiproof_bound)        \
-    X(N, multiproof_device) X(N, multiproof_verify_device)
+    X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
+    X(N, forest_ragged_multiproof_verify_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -603,6 +606,41 @@ inline void merkle_multiproof_verify_device(std::size_t n_leaves, const void* d_
     const detail::MerkleAbi& m = detail::merkle_abi("merkle_multiproof_verify_device", arity);
     detail::check(m.multiproof_verify_device(ctx.get(), m.tag().data(), n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok,
                                              d_root_out, d_n_hashed, d_n_bad, stream), ctx.get(), "merkle_multiproof_verify_device");
+}
+
+// The shared proof across a forest of trees of DIFFERENT sizes (p252_merkle{4,2}_forest_ragged_multiproof_*; the format is in
+// poseidon252_hip.h): k (tree id: uint32, leaf id: uint64) pairs, strictly ascending in (tree, leaf), anywhere in `forest` — exactly
+// as the build took and filled it.  merkle_forest_ragged_multiproof_bound: the most scalars such a proof holds.
+inline std::size_t merkle_forest_ragged_multiproof_bound(std::size_t n_leaves, std::size_t n_trees, std::size_t max_leaves, std::size_t k,
+                                                         unsigned arity = 4) {
+    return detail::merkle_abi("merkle_forest_ragged_multiproof_bound", arity).forest_ragged_multiproof_bound(n_leaves, n_trees, max_leaves, k);
+}
+// Extraction: d_leaves_out[k], d_proof (tree-major; nothing written at or past proof_cap scalars) and d_proof_offsets (n_trees + 1 device
+// uint64: where each tree's single-tree proof starts, the last entry the scalars the proof needs; all zero after a bad pair, which
+// *d_n_bad counts).
+inline void merkle_forest_ragged_multiproof_device(const ForestView& forest, const void* d_tree_ids, const void* d_leaf_ids, std::size_t k,
+                                                   void* d_leaves_out, void* d_proof, std::size_t proof_cap, void* d_proof_offsets,
+                                                   unsigned arity = 4, Context& ctx = Context::default_context(), void* d_n_bad = nullptr,
+                                                   void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_multiproof_device", arity);
+    detail::check(m.forest_ragged_multiproof_device_into(ctx.get(), forest.d_leaves, forest.n_leaves, forest.d_offsets, forest.n_trees,
+                                                    forest.max_leaves, forest.d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof,
+                                                    proof_cap, d_proof_offsets, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_multiproof_device");
+}
+// Verification, every ancestor hashed once, from the forest's shape alone (forest.d_leaves and forest.d_levels are not read): d_ok[t]
+// (n_trees bytes) = 1 iff tree t has a pair, no pair is bad, its offsets are in order and inside proof_len, its structure consumes
+// exactly its part of the proof and the recomputed root equals d_roots[t].
+inline void merkle_forest_ragged_multiproof_verify_device(const ForestView& forest, const void* d_tree_ids, const void* d_leaf_ids,
+                                                          const void* d_leaves_in, std::size_t k, const void* d_proof, std::size_t proof_len,
+                                                          const void* d_proof_offsets, const void* d_roots, void* d_ok, unsigned arity = 4,
+                                                          Context& ctx = Context::default_context(), void* d_roots_out = nullptr,
+                                                          void* d_n_hashed = nullptr, void* d_n_bad = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_multiproof_verify_device", arity);
+    detail::check(m.forest_ragged_multiproof_verify_device_into(ctx.get(), m.tag().data(), forest.d_offsets, forest.n_leaves, forest.n_trees,
+                                                           forest.max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in, k, d_proof, proof_len,
+                                                           d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_multiproof_verify_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

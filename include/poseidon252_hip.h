@@ -106,7 +106,10 @@ extern "C" {
  *      + p252_merkle{4,2}_multiproof_bound, p252_merkle{4,2}_multiproof_device, p252_merkle{4,2}_multiproof_verify_device
  *      (additive, same version): many leaves of one tree behind one shared proof, each ancestor hashed once;
  *      + p252_merkle{4,2}_forest_ragged_append_device_into (additive, same version): leaves appended to the trees of such a
- *      forest, written as a new compact forest; unchanged nodes are moved, not hashed again */
+ *      forest, written as a new compact forest; unchanged nodes are moved, not hashed again;
+ *      + p252_merkle{4,2}_forest_ragged_multiproof_bound, _multiproof_device_into, _multiproof_verify_device_into (additive, same
+ *      version; `_into` as the append: every result goes into buffers the caller owns):
+ *      leaves of many trees of such a forest behind one tree-major shared proof, each ancestor hashed once */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -567,6 +570,67 @@ int p252_merkle4_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], 
 int p252_merkle2_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
                                           size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
                                           void* d_n_hashed, void* d_n_bad, void* hip_stream);
+
+/* ---- the shared proof across a forest of trees of DIFFERENT sizes: k (tree id, leaf id) pairs anywhere in a built ragged forest,
+ * one call to extract and one to verify, every launch sized by the whole batch.  The forest arguments (d_leaves, n_leaves, d_offsets,
+ * n_trees, max_leaves, d_levels) are exactly those of p252_merkle{4,2}_forest_ragged_device and _forest_ragged_openings_device; n_t and
+ * the level block starts are derived on the device, and a bad tree is what it is there (empty, longer than max_leaves, decreasing
+ * offsets, past n_leaves).  Pair i = (tree_ids[i]: uint32, leaf_ids[i]: uint64), STRICTLY ASCENDING in (tree id, leaf id).
+ * The format: for a tree t with at least one pair, P_t is byte for byte what p252_merkle{A}_multiproof_device writes for that tree's
+ * block (leaves[offsets[t] .. offsets[t+1]), its block of d_levels) and its own positions; the forest proof is
+ * P_0 | P_1 | .. | P_{n_trees-1} (P_t empty for a tree without pairs, of one leaf, or with every leaf asked for), and
+ * proof_offsets (n_trees + 1 uint64) has proof_offsets[0] = 0, proof_offsets[t+1] - proof_offsets[t] = |P_t|,
+ * proof_offsets[n_trees] = the proof length.  proof[proof_offsets[t] .. proof_offsets[t+1]) can be cut out and checked alone with
+ * p252_merkle{4,2}_multiproof_verify_device.
+ * _bound: with D = p252_merkle{4,2}_depth(max_leaves), min(k D (A - 1), n_leaves + n_leaves / (A - 1) + n_trees D) — every proof scalar
+ * is a distinct stored node and a pair needs at most D (A - 1) of them; 0 when k, n_leaves or n_trees is 0; reached by one leaf in
+ * each complete tree of a forest of equal complete trees. ---- */
+size_t p252_merkle4_forest_ragged_multiproof_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
+size_t p252_merkle2_forest_ragged_multiproof_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
+/* Extraction (no hashing): d_leaves_out[i] = the leaf of pair i, byte for byte; d_proof = the forest proof; d_proof_offsets (device,
+ * n_trees + 1 uint64, 8-byte aligned) is always written in full, and proof_offsets[n_trees] is the length the proof NEEDS: nothing is
+ * written at or past proof_cap (scalars), so a short buffer costs a second call, never memory; a buffer of _bound scalars always
+ * suffices.  d_proof may be NULL when proof_cap == 0.  A bad pair — tree id >= n_trees, a bad tree, leaf id >= n_t, or a pair not
+ * greater than its predecessor — is counted once in *d_n_bad (device uint32 the caller has zeroed; may be NULL); after any bad pair
+ * all of d_proof_offsets is zero, nothing is read through a bad pair, and the contents of d_leaves_out and d_proof are unspecified:
+ * the batch is one object.  k, n_trees, n_leaves or max_leaves == 0, k or max_leaves >= 2^32 (a node index is a 32-bit record
+ * word), a NULL or misaligned buffer, size overflow -> P252_ERR_INVALID_ARGUMENT, nothing enqueued.  Asynchronous on hip_stream, no
+ * host synchronisation, no allocation once the scratch is warm; scratch in the context's pair of THIS stream, covered by p252_trim /
+ * p252_wipe: 52 bytes per pair (the elements of level 0, two work lists of 16-byte records with their tree ids, the level widths)
+ * and 20 bytes per 256 pairs, 76 bytes per tree (the forest's index, two consumption counters and the total, the first pair, the
+ * root) and 16 bytes per 2,048 trees, plus 4 KiB — nothing grows with the forest's leaves.  Cost: the structure pass runs twice (a
+ * counting pass, a scan over the trees, a writing pass), up to three launches per level each. */
+int p252_merkle4_forest_ragged_multiproof_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                 size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                                 size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_offsets,
+                                                 void* d_n_bad, void* hip_stream);
+int p252_merkle2_forest_ragged_multiproof_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                 size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                                 size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_offsets,
+                                                 void* d_n_bad, void* hip_stream);
+/* Verification needs neither leaves nor levels: the structure follows from (d_offsets -> n_t, tree ids, leaf ids) alone.  Every node
+ * of every tree's S_1, S_2, .. is hashed ONCE with Hash::digest(Domain::Merkle4 / Merkle2, children) (pass that domain's tag), each
+ * child from the level below, from tree t's segment of the proof, or zero.  d_ok (device, n_trees bytes): d_ok[t] = 1 iff tree t has
+ * at least one pair, no pair of the batch is bad, proof_offsets[t] <= proof_offsets[t+1] <= proof_len, tree t's structure consumes
+ * exactly proof_offsets[t+1] - proof_offsets[t] scalars, and the recomputed root equals d_roots[t] (device, n_trees scalars) as the
+ * 32 bytes they are; 0 otherwise, also for a tree nobody asked about.  d_roots_out (n_trees scalars; may be NULL): entry t is written
+ * when every condition except the root comparison holds and left alone otherwise; the recomputed root of a one-leaf tree is its leaf
+ * mod p (the forest's convention, see the edge-value paragraph above).  *d_n_hashed (device uint64; may be NULL) = the digests
+ * computed, the sum over trees and l >= 1 of |S_l| (0 after a bad pair); *d_n_bad as above.  Pairs, proof and proof offsets are
+ * untrusted: nothing is read at or past proof_len, k or n_trees + 1 whatever they contain, and a tree whose offsets lie leaves the
+ * other trees' verdicts alone.  d_proof may be NULL when proof_len == 0.  Refusals and calling conventions as for extraction;
+ * scratch as for extraction plus two lists of k node values (64 bytes per pair) in the same pair.  Cost: up to four launches per
+ * level of the deepest tree, whatever the number of trees. */
+int p252_merkle4_forest_ragged_multiproof_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_offsets, size_t n_leaves,
+                                                        size_t n_trees, size_t max_leaves, const void* d_tree_ids, const void* d_leaf_ids,
+                                                        const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len,
+                                                        const void* d_proof_offsets, const void* d_roots, void* d_ok, void* d_roots_out,
+                                                        void* d_n_hashed, void* d_n_bad, void* hip_stream);
+int p252_merkle2_forest_ragged_multiproof_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_offsets, size_t n_leaves,
+                                                        size_t n_trees, size_t max_leaves, const void* d_tree_ids, const void* d_leaf_ids,
+                                                        const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len,
+                                                        const void* d_proof_offsets, const void* d_roots, void* d_ok, void* d_roots_out,
+                                                        void* d_n_hashed, void* d_n_bad, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

@@ -21,6 +21,7 @@
 #include "hades29.hpp"
 #include "kernels.h"
 #include "multiproof.h"
+#include "forest_multiproof.h"
 #include "openings.h"
 #include "ragged.h"
 #include "tables.hpp"
@@ -1250,6 +1251,113 @@ int p252_merkle2_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], 
                                           void* d_n_hashed, void* d_n_bad, void* hip_stream) {
     return multiproof_verify_device(ctx, 2, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
                                     d_n_bad, hip_stream);
+}
+
+// ---- the same across a forest of trees of DIFFERENT sizes (forest_multiproof.hip): k (tree id, leaf id) pairs behind one tree-major
+// proof, every needed sibling stored once and every ancestor hashed once.  The scratch — the forest's index, the per-tree counters and
+// the per-pair work lists in the first buffer; the verify's two lists of node values in the second — is the pair of the calling stream ----
+size_t p252_merkle4_forest_ragged_multiproof_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
+    return forest_multiproof_plan(4, n_leaves, n_trees, max_leaves, k).bound;
+}
+size_t p252_merkle2_forest_ragged_multiproof_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
+    return forest_multiproof_plan(2, n_leaves, n_trees, max_leaves, k).bound;
+}
+
+static int forest_multiproof_shape_check(p252_ctx* ctx, const std::string& who, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
+    if (k == 0 || n_trees == 0 || n_leaves == 0 || max_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k, n_leaves, n_trees and max_leaves must be > 0");
+    if (k > 0xffffffffu || max_leaves > 0xffffffffu)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k and max_leaves must be below 2^32 (a node index is a record word)");
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    return P252_OK;
+}
+
+static int forest_ragged_multiproof_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                           size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                           const void* d_leaf_ids, size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap,
+                                           void* d_proof_offsets, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_forest_ragged_multiproof" : "merkle2_forest_ragged_multiproof";
+    if (int rc = forest_multiproof_shape_check(ctx, who, n_leaves, n_trees, max_leaves, k)) return rc;
+    const ForestMultiproofPlan plan = forest_multiproof_plan(arity, n_leaves, n_trees, max_leaves, k);
+    if (!d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_leaves_out || !d_proof_offsets || (plan.depth && !d_levels) ||
+        (proof_cap && !d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_proof_offsets, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets, d_leaf_ids and d_proof_offsets must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids and d_n_bad must be 4-byte aligned");
+    if (proof_cap > SIZE_MAX / 32) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    return with_stream_scratch(ctx, who, st, plan.work_bytes(), 0, [&](p252_ctx::LevelSet& set) {
+        return launch_forest_multiproof(plan, d_leaves, d_offsets, d_levels, d_tree_ids, d_leaf_ids, d_leaves_out, d_proof, proof_cap,
+                                        d_proof_offsets, d_n_bad, set.buf[0], st);
+    });
+}
+
+static int forest_ragged_multiproof_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_offsets, size_t n_leaves,
+                                                  size_t n_trees, size_t max_leaves, const void* d_tree_ids, const void* d_leaf_ids,
+                                                  const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len,
+                                                  const void* d_proof_offsets, const void* d_roots, void* d_ok, void* d_roots_out,
+                                                  void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_forest_ragged_multiproof_verify" : "merkle2_forest_ragged_multiproof_verify";
+    if (int rc = forest_multiproof_shape_check(ctx, who, n_leaves, n_trees, max_leaves, k)) return rc;
+    if (!tag || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_leaves_in || !d_proof_offsets || !d_roots || !d_ok || (proof_len && !d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves_in) || misaligned(d_proof) || misaligned(d_roots) || misaligned(d_roots_out))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_proof_offsets, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets, d_leaf_ids, d_proof_offsets and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids and d_n_bad must be 4-byte aligned");
+    if (proof_len > SIZE_MAX / 32) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestMultiproofPlan plan = forest_multiproof_plan(arity, n_leaves, n_trees, max_leaves, k);
+    return with_stream_scratch(ctx, who, st, plan.work_bytes(), plan.values_bytes(), [&](p252_ctx::LevelSet& set) {
+        return launch_forest_multiproof_verify(ctx->d_tab, tag_arg(tag), plan, d_offsets, d_tree_ids, d_leaf_ids, d_leaves_in, d_proof, proof_len,
+                                               d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad, set.buf[0], set.buf[1], st);
+    });
+}
+
+int p252_merkle4_forest_ragged_multiproof_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                 size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                                 size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_offsets,
+                                                 void* d_n_bad, void* hip_stream) {
+    return forest_ragged_multiproof_device(ctx, 4, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                           d_leaves_out, d_proof, proof_cap, d_proof_offsets, d_n_bad, hip_stream);
+}
+
+int p252_merkle4_forest_ragged_multiproof_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_offsets, size_t n_leaves,
+                                                        size_t n_trees, size_t max_leaves, const void* d_tree_ids, const void* d_leaf_ids,
+                                                        const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len,
+                                                        const void* d_proof_offsets, const void* d_roots, void* d_ok, void* d_roots_out,
+                                                        void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_multiproof_verify_device(ctx, 4, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
+                                                  k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad,
+                                                  hip_stream);
+}
+
+int p252_merkle2_forest_ragged_multiproof_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                 size_t max_leaves, const void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                                 size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_offsets,
+                                                 void* d_n_bad, void* hip_stream) {
+    return forest_ragged_multiproof_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                           d_leaves_out, d_proof, proof_cap, d_proof_offsets, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_multiproof_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_offsets, size_t n_leaves,
+                                                        size_t n_trees, size_t max_leaves, const void* d_tree_ids, const void* d_leaf_ids,
+                                                        const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len,
+                                                        const void* d_proof_offsets, const void* d_roots, void* d_ok, void* d_roots_out,
+                                                        void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_multiproof_verify_device(ctx, 2, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
+                                                  k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad,
+                                                  hip_stream);
 }
 
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----

@@ -40,4 +40,21 @@ hipError_t launch_multiproof_verify(const int32_t* tab, const TagArg& tag, const
                                     const void* leaves_in, const void* proof, size_t proof_len, const void* root, void* ok, void* root_out,
                                     void* n_hashed, void* n_bad, void* work, void* values, hipStream_t st);
 
+// One level's digests over a record list that the CALLER made (forest_multiproof.hip), by the kernels of the verification above.
+// Record g < *count (16 bytes): parent index, start of its run in vals_in, proof offset bits 0 .. 59 with the mask of the child
+// slots that vals_in holds above them.  Child slot j of record g exists while parent * arity + j < w_node[g]; it comes from vals_in,
+// from proof (zero at or past proof_len) or is zero; the digest goes to vals_out[g].  bound = the host's bound of *count.
+struct MultiproofDigestList {
+    const void* list = nullptr;
+    const unsigned long long* count = nullptr;
+    const void* vals_in = nullptr;
+    void* vals_out = nullptr;
+    const void* proof = nullptr;
+    size_t proof_len = 0;
+    const uint32_t* w_node = nullptr;
+    size_t bound = 0;
+};
+hipError_t launch_multiproof_digest_list(const int32_t* tab, const TagArg& tag, unsigned arity, const MultiproofDigestList& list,
+                                         hipStream_t st);
+
 }  // namespace p252

@@ -23,6 +23,9 @@
 //                    hades_permute<0x02u, true> with the hoisted tag S-box at 3 waves per SIMD, node_digest_coop when the level
 //                    cannot fill the chip (coop8 of the host bound).
 //   k_mp_finish_*    the proof length; or the one-byte verdict: no bad position, exactly proof_len scalars consumed, root equal.
+// launch_multiproof_digest_list runs the two digest kernels over records that another unit made (forest_multiproof.hip: the shared
+// proof across a ragged forest); there every record belongs to a tree of its own size, so the number of child slots that exist is
+// read per record (MpDigest::w_node) instead of once per launch (w_below; w_node == null: this file's own calls).
 #include <hip/hip_runtime.h>
 
 #include "forest_node.hpp"
@@ -208,11 +211,13 @@ struct MpDigest {
     const Scalar32* proof;
     uint64_t proof_len;
     uint64_t w_below;          // nodes of level l
+    const uint32_t* w_node;    // null, or the nodes of level l PER RECORD (a forest: every record has its own tree) instead of w_below
     size_t lanes;
 };
 
 struct MpNode {
     uint64_t first, run, off;  // first child slot; the run's start in S_l; the node's offset in the proof
+    uint64_t w;                // nodes of the level below: child slots at or past it do not exist
     unsigned mask;
 };
 __device__ __forceinline__ bool mp_node(const MpDigest& P, uint64_t g, unsigned arity, MpNode& nd) {
@@ -222,12 +227,13 @@ __device__ __forceinline__ bool mp_node(const MpDigest& P, uint64_t g, unsigned 
     nd.run = r.y;
     nd.mask = r.w >> MP_MASK_SHIFT;
     nd.off = u64_of(r.z, r.w & ((1u << MP_MASK_SHIFT) - 1));
+    nd.w = P.w_node ? (uint64_t)P.w_node[g] : P.w_below;
     return true;
 }
 // where child slot j of the node comes from: level l's values, the proof, or nowhere (null: zero)
 template <unsigned ARITY>
 __device__ __forceinline__ const Scalar32* mp_child(const MpDigest& P, const MpNode& nd, unsigned j) {
-    if (j >= ARITY || nd.first + j >= P.w_below) return nullptr;
+    if (j >= ARITY || nd.first + j >= nd.w) return nullptr;
     const unsigned below = (unsigned)__popc(nd.mask & ((1u << j) - 1u));  // slots before j that S_l holds
     if ((nd.mask >> j) & 1u) return P.vals_in + nd.run + below;
     const uint64_t at = nd.off + (j - below);
@@ -347,7 +353,31 @@ hipError_t mp_step(const MultiproofPlan& p, const MpWork& w, unsigned l, const v
     return hipGetLastError();
 }
 
+// one level's digests: the 8-lane kernel when the level's host bound cannot fill the chip (the coop8 rule of kernels.h)
+hipError_t mp_digests(const int32_t* tab, const TagArg& tag, unsigned arity, MpDigest& P, size_t bound, hipStream_t st) {
+    const bool coop = coop8(bound);
+    P.lanes = coop ? bound * 8 : bound;
+    if (arity == 4) return launch(coop ? k_mp_digest_coop<4> : k_mp_digest<4>, P.lanes, st, tab, tag, P);
+    return launch(coop ? k_mp_digest_coop<2> : k_mp_digest<2>, P.lanes, st, tab, tag, P);
+}
+
 }  // namespace
+
+// the same over a record list made by the caller (forest_multiproof.hip): every record brings the width of the level below it
+hipError_t launch_multiproof_digest_list(const int32_t* tab, const TagArg& tag, unsigned arity, const MultiproofDigestList& d,
+                                         hipStream_t st) {
+    if (d.bound == 0) return hipSuccess;
+    MpDigest P;
+    P.list = static_cast<const uint4*>(d.list);
+    P.count = d.count;
+    P.vals_in = static_cast<const Scalar32*>(d.vals_in);
+    P.vals_out = static_cast<Scalar32*>(d.vals_out);
+    P.proof = static_cast<const Scalar32*>(d.proof);
+    P.proof_len = d.proof_len;
+    P.w_below = 0;
+    P.w_node = d.w_node;
+    return mp_digests(tab, tag, arity, P, d.bound, st);
+}
 
 MultiproofPlan multiproof_plan(unsigned arity, size_t n_leaves, size_t k) {
     MultiproofPlan p;
@@ -406,12 +436,8 @@ hipError_t launch_multiproof_verify(const int32_t* tab, const TagArg& tag, const
         P.proof = static_cast<const Scalar32*>(proof);
         P.proof_len = proof_len;
         P.w_below = p.w[l];
-        const bool coop = coop8(p.in[l + 1]);
-        P.lanes = coop ? p.in[l + 1] * 8 : p.in[l + 1];
-        if (p.arity == 4)
-            e = launch(coop ? k_mp_digest_coop<4> : k_mp_digest<4>, P.lanes, st, tab, tag, P);
-        else
-            e = launch(coop ? k_mp_digest_coop<2> : k_mp_digest<2>, P.lanes, st, tab, tag, P);
+        P.w_node = nullptr;
+        e = mp_digests(tab, tag, p.arity, P, p.in[l + 1], st);
     }
     if (e != hipSuccess) return e;
     const void* top = p.depth == 0 ? leaves_in : static_cast<const void*>(vals[p.depth & 1]);

@@ -682,6 +682,82 @@ class Context:
                        _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
+    # ---- the shared proof across a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_*; csrc/forest_multiproof.hip) ----
+    def merkle4_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
+        """upper bound, in scalars, of the shared proof of k pairs of a ragged forest (p252_merkle4_forest_ragged_multiproof_bound)"""
+        return int(_ARITIES[4].fn("forest_ragged_multiproof_bound")(n_leaves, n_trees, max_leaves, k))
+
+    def merkle2_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
+        """the same for arity 2"""
+        return int(_ARITIES[2].fn("forest_ragged_multiproof_bound")(n_leaves, n_trees, max_leaves, k))
+
+    def merkle4_forest_ragged_multiproof_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                                d_leaves_out, d_proof, d_proof_offsets, d_n_bad=None):
+        """one shared, tree-major proof for k (tree id, leaf id) pairs anywhere in a forest merkle_forest_ragged_device built with d_levels
+        (p252_merkle4_forest_ragged_multiproof_device_into; no hashing): d_leaves, d_offsets, n_trees, max_leaves, d_levels exactly as the
+        build took them; d_tree_ids (int32/uint32) and d_leaf_ids (int64/uint64) STRICTLY ASCENDING in (tree, leaf).  d_leaves_out (k, 4)
+        receives the leaves, d_proof the proof — its capacity is the tensor's length, nothing is written past it (None: capacity 0) —
+        and d_proof_offsets (n_trees + 1 int64/uint64) where each tree's single-tree proof starts, the last entry the length the
+        proof needs.  A bad pair is counted in d_n_bad (a zeroed device int32/uint32, optional) and makes every offset 0.
+        Asynchronous on the current stream."""
+        self._forest_ragged_multiproof_device("merkle4_forest_ragged_multiproof_device", _ARITIES[4], d_leaves, d_offsets, n_trees, max_leaves,
+                                              d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof, d_proof_offsets, d_n_bad)
+
+    def merkle2_forest_ragged_multiproof_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                                d_leaves_out, d_proof, d_proof_offsets, d_n_bad=None):
+        """the same for arity 2"""
+        self._forest_ragged_multiproof_device("merkle2_forest_ragged_multiproof_device", _ARITIES[2], d_leaves, d_offsets, n_trees, max_leaves,
+                                              d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof, d_proof_offsets, d_n_bad)
+
+    def _forest_ragged_multiproof_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                         d_leaves_out, d_proof, d_proof_offsets, d_n_bad):
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        proof_cap = _n_scalars(d_proof) if hasattr(d_proof, "element_size") else 0
+        self._check(a.fn("forest_ragged_multiproof_device_into")(
+            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8), k,
+            _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32), _dev_ptr(self, f, "d_proof", d_proof, proof_cap * 32, null_ok=True),
+            proof_cap, _dev_ptr(self, f, "d_proof_offsets", d_proof_offsets, (n_trees + 1) * 8, elem=8),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
+    def merkle4_forest_ragged_multiproof_verify_device(self, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
+                                                       k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out=None,
+                                                       d_n_hashed=None, d_n_bad=None):
+        """checks such a proof with every ancestor hashed ONCE (p252_merkle4_forest_ragged_multiproof_verify_device_into; tag = the Merkle4
+        tag); needs neither leaves nor levels: d_offsets and n_leaves, n_trees, max_leaves as the build took them, the pairs and
+        d_leaves_in (k, 4) as extraction returned them, proof_len scalars of d_proof (None when 0), d_proof_offsets (n_trees + 1),
+        d_roots (n_trees, 4).  d_ok[t] (n_trees uint8) = 1 iff tree t has a pair, no pair is bad, its offsets are in order and inside
+        proof_len, its structure consumes exactly its part and the recomputed root equals d_roots[t].  Optional outputs: d_roots_out
+        (n_trees, 4) the recomputed roots, d_n_hashed (one int64/uint64) the digests computed, d_n_bad (a zeroed int32/uint32) the bad
+        pairs.  Asynchronous on the current stream."""
+        self._forest_ragged_multiproof_verify_device("merkle4_forest_ragged_multiproof_verify_device", _ARITIES[4], tag, d_offsets, n_leaves,
+                                                     n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in, k, d_proof, proof_len,
+                                                     d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad)
+
+    def merkle2_forest_ragged_multiproof_verify_device(self, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
+                                                       k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out=None,
+                                                       d_n_hashed=None, d_n_bad=None):
+        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
+        self._forest_ragged_multiproof_verify_device("merkle2_forest_ragged_multiproof_verify_device", _ARITIES[2], tag, d_offsets, n_leaves,
+                                                     n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in, k, d_proof, proof_len,
+                                                     d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad)
+
+    def _forest_ragged_multiproof_verify_device(self, f, a, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
+                                                k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad):
+        self._check(a.fn("forest_ragged_multiproof_verify_device_into")(
+            self._h, _tag(tag), _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_leaves, n_trees, max_leaves,
+            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
+            _dev_ptr(self, f, "d_leaves_in", d_leaves_in, k * 32), k,
+            _dev_ptr(self, f, "d_proof", d_proof, proof_len * 32, null_ok=proof_len == 0), proof_len,
+            _dev_ptr(self, f, "d_proof_offsets", d_proof_offsets, (n_trees + 1) * 8, elem=8),
+            _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_ok", d_ok, n_trees, elem=1),
+            _dev_ptr(self, f, "d_roots_out", d_roots_out, n_trees * 32, null_ok=True),
+            _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
     def merkle2_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
         """re-hash of n arity-2 openings (Domain::Merkle2; pass the Merkle2 tag): d_siblings (n,depth[,1],4), d_positions (n,depth) in 0..1"""
         self._path_batch_device("merkle2_path_batch_device", _ARITIES[2], tag, d_leaves, d_siblings, d_positions, depth, d_roots, n)

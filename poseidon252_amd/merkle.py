@@ -192,6 +192,63 @@ def merkle_multiproof_verify(n_leaves, indices, leaves, proof, root, arity=4, ta
     return bool(ok.item())
 
 
+def forest_ragged_multiproof(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, leaf_ids, arity=4):
+    """One shared, tree-major proof for leaves of many trees of a ragged forest (Context.merkle{4,2}_forest_ragged_multiproof_device):
+    d_leaves, d_offsets, n_trees, max_leaves, d_levels as merkle_forest_ragged_device took and filled them; (tree_ids[i], leaf_ids[i])
+    in any order (sequences, numpy or torch): they are sorted and de-duplicated on the device.  Returns (tree_ids (k,) int32, leaf_ids
+    (k,) int64, leaves (k, 4), proof (len, 4), proof_offsets (n_trees + 1,) int64), all on the device — what
+    forest_ragged_multiproof_verify takes; proof[proof_offsets[t]:proof_offsets[t+1]] is tree t's single-tree proof.  One
+    synchronisation, to read the proof's length.  A pair outside the forest: ValueError."""
+    import torch
+    f = "forest_ragged_multiproof"
+    a = _arity(f, arity)
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    t = torch.as_tensor(tree_ids, device=dev).to(torch.int64).reshape(-1)
+    l = torch.as_tensor(leaf_ids, device=dev).to(torch.int64).reshape(-1)
+    if t.numel() != l.numel():
+        raise ValueError("%s: %d tree ids, %d leaf ids" % (f, t.numel(), l.numel()))
+    if t.numel() == 0:
+        raise ValueError("%s: no pairs" % f)
+    if not 0 < n_trees < 1 << 31 or not 0 < max_leaves < 1 << 32:
+        raise ValueError("%s: n_trees must be in 1 .. 2^31 - 1 and max_leaves in 1 .. 2^32 - 1" % f)
+    outside = int(((t < 0) | (t >= n_trees) | (l < 0) | (l >= max_leaves)).sum())
+    if outside:
+        raise ValueError("%s: %d pair(s) outside the forest (%d trees of at most %d leaves)" % (f, outside, n_trees, max_leaves))
+    key = torch.unique((t << 32) | l)  # (sorted by tree, then leaf)
+    k = key.numel()
+    tid, lid = (key >> 32).to(torch.int32), key & 0xFFFFFFFF
+    n_leaves = _n_scalars(d_leaves)
+    bound = (ctx.merkle4_forest_ragged_multiproof_bound if arity == 4 else ctx.merkle2_forest_ragged_multiproof_bound)(n_leaves, n_trees, max_leaves, k)
+    out = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    proof = torch.empty((bound, 4), dtype=torch.int64, device=dev)
+    offs = torch.empty(n_trees + 1, dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    call = ctx.merkle4_forest_ragged_multiproof_device if arity == 4 else ctx.merkle2_forest_ragged_multiproof_device
+    call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None, tid, lid, k, out, proof if bound else None, offs, n_bad)
+    bad, length = int(n_bad.item()), int(offs[-1].item())
+    if bad:
+        raise ValueError("%s: %d pair(s) outside the forest (a bad tree, or a leaf id past its tree)" % (f, bad))
+    return tid, lid, out, proof[:length], offs
+
+
+def forest_ragged_multiproof_verify(ctx, d_offsets, n_leaves, n_trees, max_leaves, tree_ids, leaf_ids, leaves, proof, proof_offsets, d_roots,
+                                    arity=4, tag=None):
+    """The n_trees verdicts (a torch bool tensor on the host) of (tree_ids, leaf_ids, leaves, proof, proof_offsets) — torch CUDA tensors as
+    forest_ragged_multiproof returns them — against d_roots (n_trees, 4) for a forest of the shape (d_offsets, n_leaves, n_trees,
+    max_leaves), every ancestor hashed once (Context.merkle{4,2}_forest_ragged_multiproof_verify_device): entry t is True iff tree t has a
+    pair and its part of the proof re-hashes to d_roots[t].  Synchronises to read the verdicts."""
+    import torch
+    a = _arity("forest_ragged_multiproof_verify", arity)
+    ctx = ctx or Context.default()
+    ok = torch.zeros(n_trees, dtype=torch.uint8, device=leaves.device)
+    proof_len = _n_scalars(proof)
+    call = ctx.merkle4_forest_ragged_multiproof_verify_device if arity == 4 else ctx.merkle2_forest_ragged_multiproof_verify_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_offsets, n_leaves, n_trees, max_leaves, tree_ids, leaf_ids, leaves,
+         tree_ids.numel(), proof if proof_len else None, proof_len, proof_offsets, d_roots, ok)
+    return ok.cpu().to(torch.bool)
+
+
 def merkle4_path_roots(leaves, siblings, positions, tag=None, ctx=None):
     """Roots recomputed from n openings (numpy host buffers); compare with the tree root to verify."""
     ctx = ctx or Context.default()
