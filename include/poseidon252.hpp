@@ -19,6 +19,7 @@
 //                                                   merkle_forest_ragged_verify_device: openings out of such a forest
 //   —                                               merkle_forest_ragged_update_device: leaf updates anywhere in such a forest
 //   —                                               merkle_forest_ragged_append_device: leaves appended to its trees, into a new forest
+//   —                                               merkle_forest_ragged_resize_device: its trees cut, then appended to; trailing trees dropped
 //   —                                               merkle_multiproof_device / merkle_multiproof_verify_device /
 //                                                   merkle_multiproof_bound: many leaves of one tree, one shared proof
 //   —                                               merkle_forest_ragged_multiproof_device / _verify_device / _bound: leaves of many
@@ -430,6 +431,7 @@ namespace detail {
 #define P252_MERKLE_FNS(X, N)                                                                                                                \
     X(N, levels_len) X(N, depth) X(N, forest_ragged) X(N, forest_ragged_device) X(N, forest_ragged_openings_device) X(N, path_ragged_device) \
     X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, forest_ragged_append_device_into) X(N, multiproof_bound)        \
+    X(N, forest_ragged_resize_device_into)                                                                                                    \
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
     X(N, forest_ragged_multiproof_verify_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
@@ -581,6 +583,24 @@ inline void merkle_forest_ragged_append_device(const ForestView& old_forest, con
                                                      n_trees_new, max_leaves_new, grown.d_leaves, grown.leaves_cap, grown.d_offsets, grown.d_levels,
                                                      grown.levels_cap, grown.d_roots, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_append_device");
+}
+
+// Such a forest rolled back and forward in one call (p252_merkle{4,2}_forest_ragged_resize_device_into): the append above after tree t
+// was cut to its first min(d_keep[t], n_t) leaves (d_keep: n_trees_new device uint64, nullptr = every tree whole; a value >= n_t keeps
+// the tree whole).  n_trees_new may be smaller than old.n_trees: the trailing trees are dropped.  d_add may be nullptr with n_add == 0
+// (a pure rollback: at most one node per tree and level is hashed); a refused append still leaves its tree cut.  `resized` is sized as
+// `grown` above; afterwards it holds byte for byte a fresh build of the new forest.
+inline void merkle_forest_ragged_resize_device(const ForestView& old_forest, const void* d_keep, const void* d_add, std::size_t n_add,
+                                               const void* d_add_offsets, std::size_t n_trees_new, std::size_t max_leaves_new,
+                                               const ForestOut& resized, unsigned arity = 4, Context& ctx = Context::default_context(),
+                                               void* d_n_bad = nullptr, void* d_n_hashed = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_resize_device", arity);
+    detail::check(m.forest_ragged_resize_device_into(ctx.get(), m.tag().data(), old_forest.d_leaves, old_forest.n_leaves, old_forest.d_offsets,
+                                                     old_forest.n_trees, old_forest.max_leaves, old_forest.d_levels, d_keep, d_add, n_add,
+                                                     d_add_offsets, n_trees_new, max_leaves_new, resized.d_leaves, resized.leaves_cap,
+                                                     resized.d_offsets, resized.d_levels, resized.levels_cap, resized.d_roots, d_n_bad, d_n_hashed,
+                                                     stream),
+                  ctx.get(), "merkle_forest_ragged_resize_device");
 }
 
 // Many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; the format is in poseidon252_hip.h).

@@ -107,6 +107,8 @@ extern "C" {
  *      (additive, same version): many leaves of one tree behind one shared proof, each ancestor hashed once;
  *      + p252_merkle{4,2}_forest_ragged_append_device_into (additive, same version): leaves appended to the trees of such a
  *      forest, written as a new compact forest; unchanged nodes are moved, not hashed again;
+ *      + p252_merkle{4,2}_forest_ragged_resize_device_into (additive, same version): the same after each tree was cut to its
+ *      first k_t leaves, trailing trees dropped: a rollback, a reorg or a prune without a rebuild;
  *      + p252_merkle{4,2}_forest_ragged_multiproof_bound, _multiproof_device_into, _multiproof_verify_device_into (additive, same
  *      version; `_into` as the append: every result goes into buffers the caller owns):
  *      leaves of many trees of such a forest behind one tree-major shared proof, each ancestor hashed once */
@@ -504,7 +506,7 @@ int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
  * <= 1), size overflow, or any output range that overlaps any input range (all sizes are known on the host).  n_trees_new == 0 ->
  * P252_OK, nothing enqueued.  Asynchronous on hip_stream: no host synchronisation, no allocation once the scratch is warm, no
  * memset node — it can be captured into a hipGraph.  Scratch, in the context's pair of THIS stream (p252_trim / p252_wipe cover
- * it), ids and counts only: 16 bytes per tree per forest for the indices, 16 + 8 (depth + 1) bytes per new tree, 8 bytes per 512
+ * it), ids and counts only: 16 bytes per tree per forest for the indices, 24 + 8 (depth + 1) bytes per new tree, 8 bytes per 512
  * scalars moved, and one 16-byte record per dirty node (at most n_add / A^l + 2 n_trees_new on level l).
  * Cost: a fixed sequence of about 30 small launches plus one digest launch per level; the relocation reads and writes every clean
  * byte once.  Measured (profiles/forest_append.txt) against a fresh build of the same new forest in the same run: 7.2x ahead for 1
@@ -526,6 +528,43 @@ int p252_merkle2_forest_ragged_append_device_into(p252_ctx* ctx, const uint64_t 
                                                   size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
                                                   void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad, void* d_n_hashed,
                                                   void* hip_stream);
+
+/* Such a forest rolled back, and forward again, in one call: every tree is cut to its first k_t leaves, then receives its appended
+ * ones, and the trailing trees may be dropped — a reorg (the last blocks' notes come off, the competing ones go on), a roll-back to
+ * a checkpoint, a prune.  Of a tree cut from n to k leaves (0 < k < n) that receives m more, node j of level l is byte for byte the
+ * old node (l, j) iff j < floor(k / A^l): the append is the k = n case of this rule, and this call is the append call with a kept
+ * count — the same launcher, kernels, scratch and outputs.  With m = 0 at most ONE node per level of a tree is hashed.
+ * Every argument the append call has means what it means there, with these differences.  n_trees_new may be smaller than n_trees:
+ * old trees at or past n_trees_new are dropped (trees past n_trees are new, as there).  d_keep = n_trees_new uint64 (device, 8-byte
+ * aligned; read-only, it may overlap no output): k_t = min(d_keep[t], n_t), so any value >= n_t, UINT64_MAX included, keeps the
+ * tree whole; d_keep == NULL keeps every tree whole.  The append's refusal rules hold with k_t in place of n_t (k_t + m_t >
+ * max_leaves_new), and a refused append counts as m_t = 0 while the cut to k_t still applies: it is always valid.  The new tree t
+ * holds its first k_t old leaves, then its m_t appended ones; d_offsets_new, d_leaves_new, the used part of d_levels_new and d_roots
+ * are byte for byte a fresh build's.  A tree with k_t + m_t == 0 is an empty tree of the new forest: a zero root, no storage, its id
+ * kept (no tree is renumbered).  *d_n_bad grows once per tree whose append was refused or that is empty in the new forest;
+ * *d_n_hashed receives exactly the sum over l = 1 .. depth(k_t + m_t) of ceil((k_t + m_t) / A^l) - floor(k_t / A^l), over the trees
+ * with k_t < n_t or m_t > 0 — an unchanged tree hashes nothing.  max_leaves_new >= max_leaves and the caps (leaves_cap >= n_leaves +
+ * n_add, the append's levels_cap) stay as they are: they are known on the host, the kept counts are not.  Asynchronous, no host
+ * synchronisation, no allocation once the scratch is warm, no memset node; the scratch is the append's plus 8 bytes per new tree.
+ * Measured (profiles/forest_resize.txt) against a fresh build of the same new forest in the same run: one 4^12-leaf tree rolled back
+ * by 1 leaf 1.82 ms, 7.5x ahead, by 2^20 leaves 0.62 ms, 20x (arity 2, 2^24 leaves: 3.39 ms / 11x and 1.01 ms / 35x); 20,000 mixed
+ * trees cut by 1-16 leaves each 12.8x, 1 % of them 13.1x; a reorg in one call 1.94 ms against 3.93 ms for resize-then-append.  A
+ * rebuild is as quick at no point of that sweep.  The relocation alone moves 3.8-4.1 TB/s read + written, 0.71-0.79 of a
+ * device-to-device copy of the same bytes; a one-leaf rollback costs that (0.38 ms) plus one one-node digest launch per level,
+ * 0.12 ms each.  The append entry points cost what they did before (both builds alternating in one session). */
+int p252_merkle4_forest_ragged_resize_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                  const void* d_keep, const void* d_add, size_t n_add, const void* d_add_offsets,
+                                                  size_t n_trees_new, size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap,
+                                                  void* d_offsets_new, void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad,
+                                                  void* d_n_hashed, void* hip_stream);
+/* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag) */
+int p252_merkle2_forest_ragged_resize_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                  const void* d_keep, const void* d_add, size_t n_add, const void* d_add_offsets,
+                                                  size_t n_trees_new, size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap,
+                                                  void* d_offsets_new, void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad,
+                                                  void* d_n_hashed, void* hip_stream);
 
 /* ---- many leaves of ONE tree behind one shared proof.  The tree is what p252_merkle{4,2}_tree_device stored (d_leaves + d_levels;
  * one tree block of a ragged forest is the same layout); only the proof object is new.  The per-leaf openings above write

@@ -872,17 +872,20 @@ bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
 }
 }  // namespace
 
-static int forest_ragged_append_device_into(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
-                                            const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_add,
-                                            size_t n_add, const void* d_add_offsets, size_t n_trees_new, size_t max_leaves_new,
-                                            void* d_leaves_new, size_t leaves_cap, void* d_offsets_new, void* d_levels_new, size_t levels_cap,
-                                            void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+// resize: the call that also cuts (d_keep, NULL = every tree whole) and may drop trailing trees; the append is its d_keep == NULL,
+// n_trees_new >= n_trees case, under its own name in the messages
+static int forest_ragged_append_device_into(p252_ctx* ctx, bool resize, unsigned arity, const uint64_t tag[4], const void* d_leaves,
+                                            size_t n_leaves, const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                            const void* d_keep, const void* d_add, size_t n_add, const void* d_add_offsets, size_t n_trees_new,
+                                            size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                            void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad, void* d_n_hashed,
+                                            void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
     if (n_trees_new == 0) return P252_OK;
-    const std::string who = "merkle_forest_ragged_append";
+    const std::string who = resize ? "merkle_forest_ragged_resize" : "merkle_forest_ragged_append";
     if (max_leaves_new == 0 || max_leaves_new < max_leaves)
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves_new must be > 0 and >= max_leaves");
-    if (n_trees_new < n_trees) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_trees_new must be >= n_trees");
+    if (!resize && n_trees_new < n_trees) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_trees_new must be >= n_trees");
     if (n_trees && max_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves must be > 0");
     if (n_leaves > SIZE_MAX / 64 || n_add > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
     const size_t total = n_leaves + n_add;
@@ -904,12 +907,14 @@ static int forest_ragged_append_device_into(p252_ctx* ctx, unsigned arity, const
     if (misaligned_to(d_offsets, 8) || misaligned_to(d_add_offsets, 8) || misaligned_to(d_offsets_new, 8) || misaligned_to(d_n_hashed, 8))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT,
                     who + ": d_offsets, d_add_offsets, d_offsets_new and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_keep, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_keep must be 8-byte aligned");
     if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
     const ByteRange in[] = {{d_leaves, n_trees ? n_leaves * 32 : 0, "d_leaves"},
                             {d_offsets, n_trees ? (n_trees + 1) * 8 : 0, "d_offsets"},
                             {d_levels, n_trees ? levels_old * 32 : 0, "d_levels"},
                             {d_add, n_add * 32, "d_add"},
-                            {d_add_offsets, (n_trees_new + 1) * 8, "d_add_offsets"}};
+                            {d_add_offsets, (n_trees_new + 1) * 8, "d_add_offsets"},
+                            {d_keep, n_trees_new * 8, "d_keep"}};
     const ByteRange out[] = {{d_leaves_new, leaves_cap * 32, "d_leaves_new"}, {d_offsets_new, (n_trees_new + 1) * 8, "d_offsets_new"},
                              {d_levels_new, levels_cap * 32, "d_levels_new"}, {d_roots, n_trees_new * 32, "d_roots"},
                              {d_n_bad, 4, "d_n_bad"},                         {d_n_hashed, 8, "d_n_hashed"}};
@@ -920,8 +925,8 @@ static int forest_ragged_append_device_into(p252_ctx* ctx, unsigned arity, const
     hipStream_t st = (hipStream_t)hip_stream;
     const ForestAppendPlan plan = forest_append_plan(arity, n_leaves, n_trees, max_leaves, n_add, n_trees_new, max_leaves_new, leaves_cap);
     return with_stream_scratch(ctx, who, st, plan.meta_bytes(), plan.list_bytes, [&](p252_ctx::LevelSet& set) {
-        return launch_forest_append(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, d_levels, d_add, d_add_offsets, d_leaves_new, d_offsets_new,
-                                    d_levels_new, d_roots, d_n_bad, d_n_hashed, set.buf[0], set.buf[1], st);
+        return launch_forest_append(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, d_levels, d_keep, d_add, d_add_offsets, d_leaves_new,
+                                    d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed, set.buf[0], set.buf[1], st);
     });
 }
 
@@ -931,7 +936,7 @@ int p252_merkle4_forest_ragged_append_device_into(p252_ctx* ctx, const uint64_t 
                                                   size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
                                                   void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad, void* d_n_hashed,
                                                   void* hip_stream) {
-    return forest_ragged_append_device_into(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, n_add, d_add_offsets,
+    return forest_ragged_append_device_into(ctx, false, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, nullptr, d_add, n_add, d_add_offsets,
                                             n_trees_new, max_leaves_new, d_leaves_new, leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots,
                                             d_n_bad, d_n_hashed, hip_stream);
 }
@@ -942,9 +947,33 @@ int p252_merkle2_forest_ragged_append_device_into(p252_ctx* ctx, const uint64_t 
                                                   size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
                                                   void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad, void* d_n_hashed,
                                                   void* hip_stream) {
-    return forest_ragged_append_device_into(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, n_add, d_add_offsets,
+    return forest_ragged_append_device_into(ctx, false, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, nullptr, d_add, n_add, d_add_offsets,
                                             n_trees_new, max_leaves_new, d_leaves_new, leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots,
                                             d_n_bad, d_n_hashed, hip_stream);
+}
+
+// ---- the same forest with each tree cut to its first k_t leaves before the append, and with trailing trees dropped: a rollback,
+// a reorg, a prune.  One launcher (forest_append.hip); there is no host-buffer twin ----
+int p252_merkle4_forest_ragged_resize_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                  const void* d_keep, const void* d_add, size_t n_add, const void* d_add_offsets,
+                                                  size_t n_trees_new, size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap,
+                                                  void* d_offsets_new, void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad,
+                                                  void* d_n_hashed, void* hip_stream) {
+    return forest_ragged_append_device_into(ctx, true, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, n_add,
+                                            d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, leaves_cap, d_offsets_new, d_levels_new,
+                                            levels_cap, d_roots, d_n_bad, d_n_hashed, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_resize_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                  const void* d_keep, const void* d_add, size_t n_add, const void* d_add_offsets,
+                                                  size_t n_trees_new, size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap,
+                                                  void* d_offsets_new, void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad,
+                                                  void* d_n_hashed, void* hip_stream) {
+    return forest_ragged_append_device_into(ctx, true, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, n_add,
+                                            d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, leaves_cap, d_offsets_new, d_levels_new,
+                                            levels_cap, d_roots, d_n_bad, d_n_hashed, hip_stream);
 }
 
 // (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)

@@ -1,6 +1,7 @@
 // forest_append.h — launch interface between api.cpp and forest_append.hip: leaves appended to the trees of a built forest of trees
-// of DIFFERENT sizes, written as a new compact forest (p252_merkle{4,2}_forest_ragged_append_device_into).  Clean nodes are moved,
-// only the nodes above a new leaf are hashed (by forest_update.hip's digest kernels, on lists this unit makes).
+// of DIFFERENT sizes, written as a new compact forest (p252_merkle{4,2}_forest_ragged_append_device_into), and the same after each
+// tree was cut to its first k_t leaves (p252_merkle{4,2}_forest_ragged_resize_device_into).  Clean nodes are moved, only the nodes
+// above a new leaf or a cut are hashed (by forest_update.hip's digest kernels, on lists this unit makes).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,8 @@ constexpr unsigned FOREST_APPEND_MOVE_TILE = 512;   // scalars (leaves or nodes)
 // The host's view of one call, all derived from (n_leaves, n_trees, n_add, n_trees_new, max_leaves_new).  N = n_leaves + n_add bounds
 // the leaves of the new forest (the old good trees hold at most n_leaves: the build's sum rule; the accepted appends at most n_add:
 // this unit's).  Level l (1 .. depth) of the new forest has at most bound[l] = N / arity^l + n_trees_new nodes (ForestRaggedPlan) and
-// at most n_add / arity^l + 2 n_trees_new dirty ones (ceil((n + m) / B) - floor(n / B) <= floor(m / B) + 2): in[l] = the smaller.
+// at most n_add / arity^l + 2 n_trees_new dirty ones (ceil((k + m) / B) - floor(k / B) <= floor(m / B) + 2 for every kept count
+// k <= n, the append's k = n included): in[l] = the smaller.
 struct ForestAppendPlan {
     unsigned arity = 4, log2a = 2, depth = 0;
     size_t n_trees_old = 0, n_trees = 0, n_leaves_old = 0, n_add = 0, leaves = 0;  // leaves = N
@@ -33,11 +35,14 @@ struct ForestAppendPlan {
 ForestAppendPlan forest_append_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t n_add, size_t n_trees_new,
                                     size_t max_leaves_new, size_t leaves_cap);
 
-// The whole append on `st`: meta = plan.meta_bytes() and lists = plan.list_bytes of scratch.  n_bad (uint32) and n_hashed (uint64)
-// may be null; leaves / offsets / levels may be null when the old forest has no tree, add when n_add == 0, the levels when no tree
-// of that forest can have one.
+// The whole call on `st`: meta = plan.meta_bytes() and lists = plan.list_bytes of scratch.  keep (n_trees_new uint64: tree t keeps its
+// first min(keep[t], n_t) leaves) is null for an append: every tree whole, plan.n_trees >= plan.n_trees_old.  With keep the new forest
+// may have fewer trees than the old one (the trailing ones are dropped), and a call that appends nothing still hashes: at most one
+// node per tree and level.  n_bad (uint32) and n_hashed (uint64) may be null; leaves / offsets / levels may be null when the old
+// forest has no tree, add when n_add == 0, the levels when no tree of that forest can have one.
 hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const ForestAppendPlan& plan, const void* leaves, const void* offsets,
-                                const void* levels, const void* add, const void* add_offsets, void* leaves_new, void* offsets_new,
-                                void* levels_new, void* roots, void* n_bad, void* n_hashed, void* meta, void* lists, hipStream_t st);
+                                const void* levels, const void* keep, const void* add, const void* add_offsets, void* leaves_new,
+                                void* offsets_new, void* levels_new, void* roots, void* n_bad, void* n_hashed, void* meta, void* lists,
+                                hipStream_t st);
 
 }  // namespace p252

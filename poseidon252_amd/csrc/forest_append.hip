@@ -1,28 +1,32 @@
 // forest_append.hip — leaves appended to the trees of a built forest of trees of DIFFERENT sizes (forest_ragged.hip, tree-major
-// levels), written as a new compact forest, for both arities (p252_merkle{4,2}_forest_ragged_append_device_into).  A tree's size
-// fixes its level layout, so a tree that grows moves; but of a tree of n leaves that receives m > 0 more, node j of level l is
-// unchanged iff j < floor(n / a^l), and it sits at the same (l, j) in the old tree (with m == 0 every node is unchanged — the last,
-// partly filled parent too: floor(n / a^l) is NOT the old level's width).  Every other node of the new tree has a new leaf below it.
-// So the call MOVES the clean nodes and hashes only the dirty ones, sum over l >= 1 of ceil((n + m) / a^l) - floor(n / a^l) per tree:
-//   k_fa_sizes        per tree of the new forest: n_t of the old forest's index (0: a bad tree, or none) and the append m_t, or
-//                     "refused" (decreasing add offsets, a range past n_add, n_t + m_t > max_leaves_new)
+// levels), written as a new compact forest, for both arities (p252_merkle{4,2}_forest_ragged_append_device_into) — and the same after
+// every tree was cut to its first k_t <= n_t leaves (p252_merkle{4,2}_forest_ragged_resize_device_into: a rollback, a reorg, a prune;
+// the new forest may also have fewer trees than the old one).  A tree's size fixes its level layout, so a tree that changes moves;
+// but of a tree of n leaves that keeps its first k and receives m more, node j of level l is unchanged iff j < floor(k / a^l), and
+// it sits at the same (l, j) in the old tree (with k == n and m == 0 every node is unchanged — the last, partly filled parent too:
+// floor(n / a^l) is NOT the old level's width).  Every other node of the new tree has a new leaf or the cut below it.  The append is
+// the k == n case.  So the call MOVES the clean nodes and hashes only the dirty ones, sum over l >= 1 of ceil((k + m) / a^l) -
+// floor(k / a^l) per tree that changes — with m == 0 at most one node per level:
+//   k_fa_sizes        per tree of the new forest: n_t of the old forest's index (0: a bad tree, or none), the kept count k_t =
+//                     min(keep[t], n_t) (no keep array: n_t) and the append m_t, or "refused" (decreasing add offsets, a range past
+//                     n_add, k_t + m_t > max_leaves_new); the cut holds for a refused append too
 //   k_fa_tile_sums / k_fa_scan_tiles / k_fa_scan_apply   the unit's exclusive device-wide scan (tiles of 2,048 trees), three uses:
 //                     SUM  over m_t: an append that takes the running sum of the appends before it past n_add is refused as well
 //                          (that only happens when ranges overlap behind decreasing offsets; it keeps the new leaves within
 //                          n_leaves + n_add and every dirty list within the host's bound); a refused append counts as m_t = 0;
 //                          *n_bad grows once per tree that is refused or empty in the new forest, whose root is written as zero
-//                     OFFS over n_t + m_t: d_offsets_new
+//                     OFFS over k_t + m_t: d_offsets_new
 //                     DIRTY over every level's dirty count at once (gridDim.y): row l = where tree t's records start in list l
 //   (launch_forest_ragged_index on d_offsets_new: the new forest's leaf counts and block starts are the build's own)
 //   k_fa_tile_first   per 512-scalar tile of the new leaves / of the new levels: the tree that holds its first scalar, so a
 //                     relocation lane looks for its tree between the first trees of its tile and of the next (no probe inside a
 //                     large tree, <= 9 over trees of one leaf)
-//   k_fa_move_leaves  one lane per 16-byte half of four new leaves: from the tree's old leaves or from d_add
+//   k_fa_move_leaves  one lane per 16-byte half of four new leaves: leaf i < k_t from the tree's old leaves, the others from d_add
 //   k_fa_move_nodes   one lane per 16-byte half of four slots of the new levels: a clean node comes from its old block (both
 //                     addresses by the closed forms of forest_node.hpp), a dirty slot is left to the digests
-//   k_fa_roots        the roots no digest writes: zero (an empty tree), the reduced leaf (one leaf, as k_fu_scatter), the top of the
-//                     block (an unchanged tree)
-//   k_fa_expand       every level at once (gridDim.y): record g of list l = (tree, floor(n / a^l) + g - row_l[t]), in the 16-byte
+//   k_fa_roots        the roots no digest writes: zero (an empty tree), the reduced leaf (one leaf, as k_fu_scatter: a tree cut to one
+//                     leaf too), the top of the block (an unchanged tree, and a tree cut to a whole power of the arity)
+//   k_fa_expand       every level at once (gridDim.y): record g of list l = (tree, floor(k / a^l) + g - row_l[t]), in the 16-byte
 //                     format of forest_update.hip; the list's count is row_l[n_trees]
 // then launch_forest_digest_list (forest_update.hip) per level: level l reads level l - 1 of the NEW forest only — moved or hashed
 // by an earlier launch.  No kernel here hashes.
@@ -44,6 +48,7 @@ enum { FA_SUM = 0, FA_OFFS = 1, FA_DIRTY = 2 };
 
 struct FaTrees {
     uint64_t* nold;  // n_t in the old forest
+    uint64_t* keep;  // k_t <= n_t: the old leaves the tree keeps (an append: n_t)
     uint64_t* madd;  // m_t (FA_REFUSED between k_fa_sizes and the SUM scan)
     size_t n_trees;
     uint64_t n_add;
@@ -52,19 +57,19 @@ struct FaTrees {
 
 __device__ __forceinline__ uint64_t floor_shift(uint64_t n, unsigned k) { return k >= 64 ? 0ull : n >> k; }
 
-// dirty nodes of level l of a tree that grows from n to n + m leaves
-__device__ __forceinline__ uint64_t dirty_nodes(uint64_t n, uint64_t m, unsigned l, unsigned la) {
-    if (m == 0) return 0;
-    const uint64_t w = level_nodes(n + m, l, la);
-    return w ? w - floor_shift(n, l * la) : 0ull;
+// dirty nodes of level l of a tree of n leaves that keeps its first k and receives m more
+__device__ __forceinline__ uint64_t dirty_nodes(uint64_t n, uint64_t k, uint64_t m, unsigned l, unsigned la) {
+    if (m == 0 && k == n) return 0;
+    const uint64_t w = level_nodes(k + m, l, la);
+    return w ? w - floor_shift(k, l * la) : 0ull;
 }
 
 template <int MODE>
 __device__ __forceinline__ uint64_t scan_value(const FaTrees& T, size_t t, unsigned l) {
     const uint64_t m = T.madd[t];
     if (MODE == FA_SUM) return m == FA_REFUSED ? 0ull : m;
-    if (MODE == FA_OFFS) return T.nold[t] + m;
-    return dirty_nodes(T.nold[t], m, l, T.la);
+    if (MODE == FA_OFFS) return T.keep[t] + m;
+    return dirty_nodes(T.nold[t], T.keep[t], m, l, T.la);
 }
 
 // exclusive scan of one value per thread over the block (the block total in *total)
@@ -100,16 +105,20 @@ __device__ __forceinline__ size_t last_at_or_below(const uint64_t* __restrict__ 
 
 }  // namespace
 
-// ---- per tree: the old leaf count and the append ----
+// ---- per tree: the old leaf count, the kept count (keep_in null: every tree whole) and the append ----
 __global__ void __launch_bounds__(FA_BLOCK) k_fa_sizes(const uint64_t* __restrict__ ntree_old, size_t n_trees_old,
-                                                       const uint64_t* __restrict__ add_offsets, uint64_t max_leaves_new, FaTrees T) {
+                                                       const uint64_t* __restrict__ keep_in, const uint64_t* __restrict__ add_offsets,
+                                                       uint64_t max_leaves_new, FaTrees T) {
     const size_t t = (size_t)blockIdx.x * FA_BLOCK + threadIdx.x;
     if (t >= T.n_trees) return;
     const uint64_t n = t < n_trees_old ? ntree_old[t] : 0ull;  // (n <= max_leaves <= max_leaves_new: api.cpp)
+    const uint64_t want = keep_in ? keep_in[t] : n;
+    const uint64_t k = want < n ? want : n;  // (the truncation is always valid: it holds for a refused append too)
     const uint64_t lo = add_offsets[t], hi = add_offsets[t + 1];
     const uint64_t m = hi - lo;
-    const bool ok = hi >= lo && hi <= T.n_add && m <= max_leaves_new - n;
+    const bool ok = hi >= lo && hi <= T.n_add && m <= max_leaves_new - k;
     T.nold[t] = n;
+    T.keep[t] = k;
     T.madd[t] = ok ? m : FA_REFUSED;
 }
 
@@ -166,7 +175,7 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_scan_apply(FaTrees T, const uin
             const bool refused = T.madd[t] == FA_REFUSED || (v != 0 && (run > T.n_add || v > T.n_add - run));  // (nothing appended: nothing to refuse)
             const uint64_t m = refused ? 0ull : v;
             T.madd[t] = m;
-            const bool empty = T.nold[t] + m == 0;
+            const bool empty = T.keep[t] + m == 0;
             if (empty) store_zero(roots + t);
             if ((refused || empty) && n_bad) atomicAdd(n_bad, 1u);
         } else {
@@ -185,7 +194,7 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_tile_first(const uint64_t* __re
     first[b] = last_at_or_below(B, 0, n_trees - 1, (uint64_t)b * FOREST_APPEND_MOVE_TILE);  // (B[0] = 0)
 }
 
-// ---- the leaves: each tree's old ones, then its appended ones ----
+// ---- the leaves: each tree's kept ones, then its appended ones ----
 __global__ void __launch_bounds__(FA_BLOCK) k_fa_move_leaves(const uint64_t* __restrict__ off_new, const uint64_t* __restrict__ first,
                                                              const uint64_t* __restrict__ off_old, const uint64_t* __restrict__ add_offsets,
                                                              FaTrees T, const uint4* __restrict__ leaves, const uint4* __restrict__ add,
@@ -198,8 +207,8 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_move_leaves(const uint64_t* __r
         const uint64_t j = h >> 1;
         if (j >= total) return;
         const size_t t = last_at_or_below(off_new, lo, hi, j);
-        const uint64_t i = j - off_new[t], n = T.nold[t];
-        const uint4* src = i < n ? leaves + 2 * (off_old[t] + i) : add + 2 * (add_offsets[t] + (i - n));
+        const uint64_t i = j - off_new[t], k = T.keep[t];
+        const uint4* src = i < k ? leaves + 2 * (off_old[t] + i) : add + 2 * (add_offsets[t] + (i - k));
         leaves_new[h] = src[h & 1];
     }
 }
@@ -216,20 +225,20 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_move_nodes(const uint64_t* __re
         const uint64_t s = h >> 1;
         if (s >= total) return;
         const size_t t = last_at_or_below(lo_new, lo, hi, s);
-        const uint64_t p = s - lo_new[t], n = T.nold[t], m = T.madd[t];
-        uint64_t from = p;  // (m == 0: the same tree, the same layout)
-        if (m != 0) {
-            // the level of slot p of the new block, and its place in it
-            uint64_t start = 0, w = ceil_shift(n + m, T.la);
+        const uint64_t p = s - lo_new[t], n = T.nold[t], k = T.keep[t], m = T.madd[t];
+        uint64_t from = p;  // (k == n, m == 0: the same tree, the same layout)
+        if (m != 0 || k != n) {
+            // the level of slot p of the new block (of k + m leaves), and its place in it
+            uint64_t start = 0, w = ceil_shift(k + m, T.la);
             unsigned l = 1;
 #pragma unroll 1
             while (p >= start + w && w > 1) {  // (w == 1: the top; the index and n + m agree, so p never lies past it)
                 start += w;
                 ++l;
-                w = ceil_shift(n + m, l * T.la);
+                w = ceil_shift(k + m, l * T.la);
             }
             const uint64_t j = p - start;
-            if (j >= floor_shift(n, l * T.la)) continue;  // dirty: a digest writes it
+            if (j >= floor_shift(k, l * T.la)) continue;  // dirty: a digest writes it
             from = level_start(n, l, T.la) + j;
         }
         levels_new[h] = levels[2 * (lo_old[t] + from) + (h & 1)];
@@ -242,10 +251,12 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_roots(const uint64_t* __restric
                                                        Scalar32* __restrict__ roots) {
     const size_t t = (size_t)blockIdx.x * FA_BLOCK + threadIdx.x;
     if (t >= T.n_trees) return;
-    const uint64_t m = T.madd[t], n = T.nold[t] + m;
-    if (n == 1) {  // (the leaf keeps its bytes; the root is reduced, as the forest's build writes it)
+    const uint64_t m = T.madd[t], k = T.keep[t], n = k + m;
+    // the top node is clean in an unchanged tree, and in a tree cut to a whole power of the arity: its old subtree of that height
+    const bool top_clean = m == 0 && (k == T.nold[t] || ((k & (k - 1)) == 0 && (unsigned)(__ffsll((long long)k) - 1) % T.la == 0));
+    if (n == 1) {  // (the leaf keeps its bytes; the root is reduced, as the forest's build writes it: a tree cut to one leaf too)
         store_scalar(roots + t, load_scalar(leaves_new + off_new[t]));
-    } else if (n > 1 && m == 0) {  // an unchanged tree: the last scalar of its block
+    } else if (n > 1 && top_clean) {  // no digest writes it: the last scalar of its block, moved there
         const uint4* src = reinterpret_cast<const uint4*>(levels_new + lo_new[t + 1] - 1);
         uint4* dst = reinterpret_cast<uint4*>(roots + t);
         dst[0] = src[0];
@@ -264,7 +275,7 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_expand(const uint64_t* __restri
     const uint64_t* __restrict__ row = rows + (size_t)l * (T.n_trees + 1);
     if (g >= L.in[l] || g >= row[T.n_trees]) return;
     const size_t t = last_at_or_below(row, 0, T.n_trees - 1, g);
-    const uint64_t i = floor_shift(T.nold[t], l * T.la) + (g - row[t]);
+    const uint64_t i = floor_shift(T.keep[t], l * T.la) + (g - row[t]);
     lists[L.off[l] + g] = make_uint4((unsigned)t, 1u, (unsigned)i, (unsigned)(i >> 32));
 }
 
@@ -300,16 +311,17 @@ ForestAppendPlan forest_append_plan(unsigned arity, size_t n_leaves, size_t n_tr
     p.node_tiles = (p.nodes + FOREST_APPEND_MOVE_TILE - 1) / FOREST_APPEND_MOVE_TILE;
     p.index_old_bytes = forest_ragged_index_bytes(n_trees);
     p.index_new_bytes = forest_ragged_index_bytes(T);
-    // n_t and m_t, the rows (row 0 unused), the scans' tile sums, the two first-tree rows
-    const size_t words = 2 * T + (size_t)(p.depth + 1) * (T + 1) + (size_t)(p.depth + 1) * p.tiles + p.leaf_tiles + 1 + p.node_tiles + 1;
+    // n_t, k_t and m_t, the rows (row 0 unused), the scans' tile sums, the two first-tree rows
+    const size_t words = 3 * T + (size_t)(p.depth + 1) * (T + 1) + (size_t)(p.depth + 1) * p.tiles + p.leaf_tiles + 1 + p.node_tiles + 1;
     p.work_bytes = (words * 8 + 255) & ~(size_t)255;
     p.list_bytes = records * sizeof(uint4);
     return p;
 }
 
 hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const ForestAppendPlan& p, const void* leaves, const void* offsets,
-                                const void* levels, const void* add, const void* add_offsets, void* leaves_new, void* offsets_new,
-                                void* levels_new, void* roots, void* n_bad, void* n_hashed, void* meta, void* lists, hipStream_t st) {
+                                const void* levels, const void* keep, const void* add, const void* add_offsets, void* leaves_new,
+                                void* offsets_new, void* levels_new, void* roots, void* n_bad, void* n_hashed, void* meta, void* lists,
+                                hipStream_t st) {
     const size_t T = p.n_trees;
     if (T == 0) return hipSuccess;
     char* base = static_cast<char*>(meta);
@@ -319,11 +331,12 @@ hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const For
     uint64_t* w = reinterpret_cast<uint64_t*>(base + p.index_old_bytes + p.index_new_bytes);
     FaTrees trees;
     trees.nold = w;
-    trees.madd = w + T;
+    trees.keep = w + T;
+    trees.madd = w + 2 * T;
     trees.n_trees = T;
     trees.n_add = p.n_add;
     trees.la = p.log2a;
-    uint64_t* rows = w + 2 * T;
+    uint64_t* rows = w + 3 * T;
     uint64_t* tsum = rows + (size_t)(p.depth + 1) * (T + 1);
     uint64_t* first_leaf = tsum + (size_t)(p.depth + 1) * p.tiles;
     uint64_t* first_node = first_leaf + p.leaf_tiles + 1;
@@ -332,7 +345,8 @@ hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const For
     Scalar32* rt = static_cast<Scalar32*>(roots);
     const dim3 blk(FA_BLOCK), per_tree((unsigned)((T + FA_BLOCK - 1) / FA_BLOCK)), tiles((unsigned)p.tiles);
 
-    hipLaunchKernelGGL(k_fa_sizes, per_tree, blk, 0, st, ntree_old, p.n_trees_old, aoff, (uint64_t)p.max_leaves, trees);
+    hipLaunchKernelGGL(k_fa_sizes, per_tree, blk, 0, st, ntree_old, p.n_trees_old, static_cast<const uint64_t*>(keep), aoff,
+                       (uint64_t)p.max_leaves, trees);
     hipLaunchKernelGGL(k_fa_tile_sums<FA_SUM>, tiles, blk, 0, st, trees, tsum);
     hipLaunchKernelGGL(k_fa_scan_tiles, dim3(1), blk, 0, st, tsum, p.tiles);
     hipLaunchKernelGGL(k_fa_scan_apply<FA_SUM>, tiles, blk, 0, st, trees, tsum, (uint64_t*)nullptr, rt, static_cast<unsigned*>(n_bad));
@@ -360,7 +374,7 @@ hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const For
     hipLaunchKernelGGL(k_fa_roots, per_tree, blk, 0, st, off_new, lo_new, trees, static_cast<const Scalar32*>(leaves_new),
                        static_cast<const Scalar32*>(levels_new), rt);
     e = hipGetLastError();
-    if (e != hipSuccess || p.depth == 0 || p.n_add == 0) return e;  // (nothing appended: a compaction copy, every node clean)
+    if (e != hipSuccess || p.depth == 0 || (p.n_add == 0 && !keep)) return e;  // (nothing appended, nothing cut: a compaction copy, every node clean)
 
     FaLists L = {};
     for (unsigned l = 1; l <= p.depth; ++l) {

@@ -531,18 +531,42 @@ class Context:
         with the unchanged nodes moved and only the others hashed.  A refused append or an empty new tree is counted in d_n_bad (a
         zeroed device int32/uint32, optional); d_n_hashed (a zeroed device int64/uint64, optional) receives the digests computed."""
         self._forest_ragged_append_device("merkle4_forest_ragged_append_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees, max_leaves,
-                                          d_levels, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
+                                          d_levels, None, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
                                           d_levels_new, d_roots, d_n_bad, d_n_hashed)
 
     def merkle2_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
                                             max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None):
         """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
         self._forest_ragged_append_device("merkle2_forest_ragged_append_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees, max_leaves,
-                                          d_levels, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
+                                          d_levels, None, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
                                           d_levels_new, d_roots, d_n_bad, d_n_hashed)
 
-    def _forest_ragged_append_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
-                                     max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed):
+    def merkle4_forest_ragged_resize_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+                                            n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None,
+                                            d_n_hashed=None):
+        """such a forest rolled back and forward in one call (p252_merkle4_forest_ragged_resize_device_into): the append above after
+        tree t was cut to its first min(d_keep[t], n_t) leaves.  d_keep = n_trees_new int64/uint64 on the device (-1, i.e. UINT64_MAX,
+        or any value >= n_t keeps the tree whole; None keeps every tree whole).  n_trees_new may be smaller than n_trees: the
+        trailing trees are dropped.  d_add None: a pure rollback, at most one node per tree and level hashed.  A refused append
+        still leaves its tree cut.  Everything else, the sizes of the outputs included, as merkle4_forest_ragged_append_device."""
+        self._forest_ragged_append_device("merkle4_forest_ragged_resize_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees, max_leaves,
+                                          d_levels, d_keep, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
+                                          d_levels_new, d_roots, d_n_bad, d_n_hashed, stem="forest_ragged_resize_device_into")
+
+    def merkle2_forest_ragged_resize_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+                                            n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None,
+                                            d_n_hashed=None):
+        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
+        self._forest_ragged_append_device("merkle2_forest_ragged_resize_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees, max_leaves,
+                                          d_levels, d_keep, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
+                                          d_levels_new, d_roots, d_n_bad, d_n_hashed, stem="forest_ragged_resize_device_into")
+
+    def _forest_ragged_append_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+                                     n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed,
+                                     stem="forest_ragged_append_device_into"):
+        """the append and the resize: one set of checks; the resize's C call takes d_keep after d_levels"""
+        resize = stem == "forest_ragged_resize_device_into"
+        keep = (_dev_ptr(self, f, "d_keep", d_keep, n_trees_new * 8, elem=8, null_ok=True),) if resize else ()
         none = n_trees == 0  # no old forest
         leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 0, null_ok=none)
         n_leaves = _n_scalars(d_leaves) if d_leaves is not None else 0
@@ -552,10 +576,10 @@ class Context:
         leaves_new = _dev_ptr(self, f, "d_leaves_new", d_leaves_new, (n_leaves + n_add) * 32, null_ok=n_leaves + n_add == 0)
         levels_need = a.forest_levels_bytes(n_leaves + n_add, n_trees_new, depth_new)
         levels_new = _dev_ptr(self, f, "d_levels_new", d_levels_new, levels_need, null_ok=depth_new == 0)
-        self._check(a.fn("forest_ragged_append_device_into")(
+        self._check(a.fn(stem)(
             self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8, null_ok=none), n_trees,
             max_leaves, _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            add, n_add, _dev_ptr(self, f, "d_add_offsets", d_add_offsets, (n_trees_new + 1) * 8, elem=8), n_trees_new, max_leaves_new,
+            *keep, add, n_add, _dev_ptr(self, f, "d_add_offsets", d_add_offsets, (n_trees_new + 1) * 8, elem=8), n_trees_new, max_leaves_new,
             leaves_new, _n_scalars(d_leaves_new) if d_leaves_new is not None else 0,
             _dev_ptr(self, f, "d_offsets_new", d_offsets_new, (n_trees_new + 1) * 8, elem=8),
             levels_new, _n_scalars(d_levels_new) if d_levels_new is not None else levels_need // 32,  # (no level: nothing is written)

@@ -154,6 +154,42 @@ def forest_ragged_append(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_l
     return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
 
 
+def forest_ragged_resize(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep=None, d_add=None, d_add_offsets=None,
+                         n_trees_new=None, max_leaves_new=None, arity=4):
+    """A built forest rolled back and forward in one call (Context.merkle{4,2}_forest_ragged_resize_device): tree t keeps its first
+    min(d_keep[t], n_t) leaves (d_keep: int64/uint64 on the device, -1 or any value >= n_t keeps the tree whole; None: every tree) and
+    then receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (both None: a pure rollback).  n_trees_new defaults to the trees
+    d_add_offsets names, else d_keep, else n_trees; smaller than n_trees it drops the trailing trees.  max_leaves_new defaults as in
+    forest_ragged_append.  Sizes and allocates the new forest as forest_ragged_append does and returns the same tuple (d_leaves_new,
+    d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed), all on the device.  No synchronisation."""
+    import torch
+    a = _arity("forest_ragged_resize", arity)
+    ctx = ctx or Context.default()
+    if n_trees_new is None:
+        named = d_add_offsets.numel() - 1 if d_add_offsets is not None else d_keep.numel() if d_keep is not None else n_trees
+        n_trees_new = named
+    dev = next(t for t in (d_add_offsets, d_keep, d_offsets, d_add) if t is not None).device
+    if d_add_offsets is None:  # nothing appended
+        if d_add is not None:
+            raise ValueError("forest_ragged_resize: d_add needs d_add_offsets")
+        d_add_offsets = torch.zeros(n_trees_new + 1, dtype=torch.int64, device=dev)
+    n_add = _n_scalars(d_add) if d_add is not None else 0
+    n_leaves = _n_scalars(d_leaves) if d_leaves is not None else 0
+    if max_leaves_new is None:
+        max_leaves_new = max(max_leaves + n_add, 1)
+    total = n_leaves + n_add
+    leaves_new = torch.empty((total, 4), dtype=torch.int64, device=dev)
+    offsets_new = torch.empty(n_trees_new + 1, dtype=torch.int64, device=dev)
+    levels_new = torch.empty((a.forest_levels_bytes(total, n_trees_new, a.depth(max_leaves_new)) // 32, 4), dtype=torch.int64, device=dev)
+    roots = torch.empty((n_trees_new, 4), dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
+    call = ctx.merkle4_forest_ragged_resize_device if arity == 4 else ctx.merkle2_forest_ragged_resize_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+         n_trees_new, max_leaves_new, leaves_new if total else None, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad, n_hashed)
+    return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
+
+
 def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
     as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are
