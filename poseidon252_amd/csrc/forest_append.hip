@@ -136,7 +136,8 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_tile_sums(FaTrees T, uint64_t* 
     if (threadIdx.x == 0) tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
-// one block per row: the tile sums of the row -> their exclusive scan, in place
+// one block per row (SUM, OFFS, one DIRTY row per level): the tile sums of the row -> their exclusive scan, in place.  FA_BLOCK tiles a
+// trip of the loop, `carry` from trip to trip: the second trip starts past FA_BLOCK * FOREST_APPEND_SCAN_TILE = 524,288 new trees
 __global__ void __launch_bounds__(FA_BLOCK) k_fa_scan_tiles(uint64_t* __restrict__ tsum, size_t tiles) {
     uint64_t* row = tsum + (size_t)blockIdx.x * tiles;
     uint64_t carry = 0;

@@ -191,7 +191,9 @@ __global__ void __launch_bounds__(FM_BLOCK) k_fm_tile_sums(FmLevel L, const u64*
     if (threadIdx.x == 0) tsum[blockIdx.x] = total;
 }
 
-// one block: the tile sums -> toff[tile] = (heads before the tile, missing siblings of the tree that runs into the tile); |S_{l+1}|
+// one block: the tile sums -> toff[tile] = (heads before the tile, missing siblings of the tree that runs into the tile); |S_{l+1}|.
+// FM_BLOCK tiles a trip of the loop: the second trip starts where a level's list is longer than FM_BLOCK * FM_BLOCK = 65,536 elements.
+// `heads` adds up from trip to trip; `carry` (the missing siblings of the tree that runs out of the trip) restarts where a tree starts
 __global__ void __launch_bounds__(FM_BLOCK) k_fm_scan_tiles(const uint32_t* __restrict__ tsum, size_t tiles, u64* __restrict__ toff,
                                                             u64* __restrict__ ctr, unsigned l) {
     if (ctr[FM_BAD]) return;
@@ -329,6 +331,8 @@ __global__ void __launch_bounds__(FM_BLOCK) k_fm_tree_sums(const u64* __restrict
     if (threadIdx.x == 0) ttile[blockIdx.x] = all;
 }
 
+// one block: the tree tiles' sums -> their exclusive scan, in place.  FM_BLOCK tiles a trip of the loop, `carry` from trip to trip: the
+// second trip starts past FM_BLOCK * FM_TREE_TILE = 524,288 trees
 __global__ void __launch_bounds__(FM_BLOCK) k_fm_tree_scan(u64* __restrict__ ttile, size_t tiles) {
     u64 carry = 0;
 #pragma unroll 1

@@ -101,7 +101,8 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_tile_sums(const uint64_t* __res
     if (threadIdx.x == 0) tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
-// one block per row: the tile sums of the row -> their exclusive scan, in place
+// one block per row: the tile sums of the row -> their exclusive scan, in place.  FR_BLOCK tiles a trip of the loop, `carry` from trip
+// to trip: the second trip starts past FR_BLOCK * FR_TILE = 524,288 trees
 __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_tiles(uint64_t* __restrict__ tsum, size_t tiles) {
     uint64_t* row = tsum + (size_t)blockIdx.x * tiles;
     uint64_t carry = 0;

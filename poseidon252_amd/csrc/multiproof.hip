@@ -129,7 +129,9 @@ __global__ void __launch_bounds__(MP_BLOCK) k_mp_tile_sums(MpLevel L, const u64*
     if (threadIdx.x == 0) tsum[blockIdx.x] = total;
 }
 
-// one block: the tile sums -> toff[tile] = (heads before the tile, proof offset of the tile); the level's totals to the counters
+// one block: the tile sums -> toff[tile] = (heads before the tile, proof offset of the tile); the level's totals to the counters.
+// MP_BLOCK tiles a trip of the loop, `heads` and `base` carried from trip to trip: the second trip starts where a level's list is
+// longer than MP_BLOCK * MP_BLOCK = 65,536 elements
 __global__ void __launch_bounds__(MP_BLOCK) k_mp_scan_tiles(const uint32_t* __restrict__ tsum, size_t tiles, u64* __restrict__ toff,
                                                             u64* __restrict__ ctr, unsigned l) {
     u64 heads = 0, base = ctr[MP_BASE];
