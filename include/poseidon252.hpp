@@ -18,6 +18,8 @@
 //   —                                               merkle_forest_ragged_openings_device / merkle_path_ragged_device /
 //                                                   merkle_forest_ragged_verify_device: openings out of such a forest
 //   —                                               merkle_forest_ragged_update_device: leaf updates anywhere in such a forest
+//   —                                               merkle_forest_ragged_update_journaled_device / merkle_forest_ragged_journal_swap_device /
+//                                                   merkle_forest_ragged_journal_bound: such updates undone and redone, no hashing
 //   —                                               merkle_forest_ragged_append_device: leaves appended to its trees, into a new forest
 //   —                                               merkle_forest_ragged_resize_device: its trees cut, then appended to; trailing trees dropped
 //   —                                               merkle_multiproof_device / merkle_multiproof_verify_device /
@@ -431,7 +433,8 @@ namespace detail {
 #define P252_MERKLE_FNS(X, N)                                                                                                                \
     X(N, levels_len) X(N, depth) X(N, forest_ragged) X(N, forest_ragged_device) X(N, forest_ragged_openings_device) X(N, path_ragged_device) \
     X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, forest_ragged_append_device_into) X(N, multiproof_bound)        \
-    X(N, forest_ragged_resize_device_into)                                                                                                    \
+    X(N, forest_ragged_resize_device_into) X(N, forest_ragged_journal_bound) X(N, forest_ragged_update_journaled_device_into)                    \
+    X(N, forest_ragged_journal_swap_device_into)                                                                                             \
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
     X(N, forest_ragged_multiproof_verify_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
@@ -547,6 +550,43 @@ inline void merkle_forest_ragged_update_device(void* d_leaves, std::size_t n_lea
     detail::check(m.forest_ragged_update_device(ctx.get(), m.tag().data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
                                                 d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_update_device");
+}
+
+// The same update keeping a journal of every leaf and node it overwrites (p252_merkle{4,2}_forest_ragged_update_journaled_device_into), and the
+// swap that plays the journal back (p252_merkle{4,2}_forest_ragged_journal_swap_device_into): one swap undoes the update byte for byte, a
+// second one redoes it, and nothing is hashed.  The journal is the caller's: ids (16 bytes per entry) and values (32 bytes per entry)
+// for `cap` entries, cap >= merkle_forest_ragged_journal_bound(..), and a device uint64 length that the update sets.  Of a (tree, leaf)
+// pair given several times one update is applied, whole.  A journal is only meaningful for the forest shape it was taken on.
+struct ForestJournal {
+    void* d_ids;
+    void* d_values;
+    std::size_t cap;
+    void* d_len;
+};
+inline std::size_t merkle_forest_ragged_journal_bound(std::size_t n_leaves, std::size_t n_trees, std::size_t max_leaves, std::size_t k,
+                                                      unsigned arity = 4) {
+    return detail::merkle_abi("merkle_forest_ragged_journal_bound", arity).forest_ragged_journal_bound(n_leaves, n_trees, max_leaves, k);
+}
+inline void merkle_forest_ragged_update_journaled_device(void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
+                                                         std::size_t max_leaves, void* d_levels, const void* d_tree_ids, const void* d_leaf_ids,
+                                                         const void* d_new_leaves, std::size_t k, const ForestJournal& journal, unsigned arity = 4,
+                                                         Context& ctx = Context::default_context(), void* d_roots = nullptr,
+                                                         void* d_n_bad = nullptr, void* d_n_hashed = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_update_journaled_device", arity);
+    detail::check(m.forest_ragged_update_journaled_device_into(ctx.get(), m.tag().data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels,
+                                                          d_tree_ids, d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, journal.d_ids,
+                                                          journal.d_values, journal.cap, journal.d_len, stream),
+                  ctx.get(), "merkle_forest_ragged_update_journaled_device");
+}
+// An entry that names no node of this forest writes nothing and is counted in *d_n_bad (device uint32, zeroed by the caller).
+inline void merkle_forest_ragged_journal_swap_device(void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
+                                                     std::size_t max_leaves, void* d_levels, const ForestJournal& journal, unsigned arity = 4,
+                                                     Context& ctx = Context::default_context(), void* d_roots = nullptr, void* d_n_bad = nullptr,
+                                                     void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_journal_swap_device", arity);
+    detail::check(m.forest_ragged_journal_swap_device_into(ctx.get(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, journal.d_ids,
+                                                      journal.d_values, journal.cap, journal.d_len, d_roots, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_journal_swap_device");
 }
 
 // Leaves appended to the trees of such a forest, written INTO a new compact forest (p252_merkle{4,2}_forest_ragged_append_device_into):

@@ -103,6 +103,9 @@ extern "C" {
  *      p252_merkle{4,2}_forest_ragged_verify_device (additive, same version): openings out of such a forest in one call;
  *      + p252_merkle{4,2}_forest_ragged_update_device (additive, same version): leaf updates anywhere in such a forest in one
  *      call, each dirty node hashed once;
+ *      + p252_merkle{4,2}_forest_ragged_journal_bound, _update_journaled_device_into, _journal_swap_device_into (additive, same
+ *      version; `_into`: the journal is the caller's buffer): the same update keeping a journal of what it overwrites, and the swap
+ *      that undoes and redoes it with no digest;
  *      + p252_merkle{4,2}_multiproof_bound, p252_merkle{4,2}_multiproof_device, p252_merkle{4,2}_multiproof_verify_device
  *      (additive, same version): many leaves of one tree behind one shared proof, each ancestor hashed once;
  *      + p252_merkle{4,2}_forest_ragged_append_device_into (additive, same version): leaves appended to the trees of such a
@@ -478,6 +481,67 @@ int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
                                              size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
                                              const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
                                              void* d_n_hashed, void* hip_stream);
+
+/* The same update with a JOURNAL, and the swap that plays the journal back: leaving an update again (an orphaned block) and entering
+ * it again, without the old leaves and without one digest.  p252_merkle{4,2}_forest_ragged_journal_bound (host, no context): the most
+ * journal entries one call with k updates writes, k + the sum over l = 1 .. depth of min(k, n_leaves / arity^l + n_trees), depth =
+ * that of a tree of min(max_leaves, n_leaves) leaves; 0 when any of the four sizes is 0, SIZE_MAX when the sum overflows. */
+size_t p252_merkle4_forest_ragged_journal_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
+size_t p252_merkle2_forest_ragged_journal_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
+/* The journaled update: every argument up to d_n_hashed is the plain update's, in its order and with its meaning, with ONE tightening:
+ * the (tree, leaf) pairs go through a claim table at level 0 as the dirty nodes of every upper level do, keyed by the leaf's slot in
+ * d_leaves.  Of a pair given several times exactly one update is applied, as a whole scalar, never a mix of halves; the others are
+ * dropped and NOT counted in *d_n_bad (which counts what the plain update counts).  (Two good trees whose ranges overlap share
+ * slots: of two updates of one slot one is applied, and its tree alone is re-hashed.)  *d_n_hashed means what it means there.
+ * The journal, owned by the caller: d_journal_ids (device, 16 bytes per entry, 16-byte aligned), d_journal_values (device, 32 bytes
+ * per entry, 16-byte aligned), journal_cap = their capacity in entries, d_journal_len (device uint64, 8-byte aligned, REQUIRED; the
+ * call sets it, the caller need not zero it).  journal_cap < p252_merkle{4,2}_forest_ragged_journal_bound(n_leaves, n_trees,
+ * max_leaves, k) -> P252_ERR_INVALID_ARGUMENT, nothing enqueued: the device can never run past the journal.  An entry is written
+ * for the old 32 bytes of every leaf and every node the call overwrites, BEFORE the overwrite: id = four uint32 {tree id, level + 1,
+ * node index low, node index high} (level 0 = the leaves; an all-zero id is void), value = the raw bytes that were stored (a leaf
+ * keeps its bytes unreduced, as the build leaves it).  Entries are compact, 0 .. *d_journal_len - 1, the leaves first, then level
+ * by level; the order within a level is unspecified; entries past the length are not written.  Entries name DISTINCT nodes, and
+ * *d_journal_len = the distinct valid pairs + what *d_n_hashed grows by.  Roots are not journalled: a tree's top node (the leaf of
+ * a one-leaf tree) stands for its root.  k == 0 -> P252_OK, *d_journal_len = 0.  As the plain update: asynchronous on hip_stream,
+ * no host synchronisation, no allocation once the scratch is warm (the plain update's scratch, in the pair of THIS stream),
+ * capturable on one stream (it holds memset nodes), at most three graph nodes per level plus the leaf stage.
+ * Measured: profiles/forest_journal.txt. */
+int p252_merkle4_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                       const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                       const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
+                                                       void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids,
+                                                       void* d_journal_values, size_t journal_cap, void* d_journal_len, void* hip_stream);
+/* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag) */
+int p252_merkle2_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                       const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                       const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
+                                                       void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids,
+                                                       void* d_journal_values, size_t journal_cap, void* d_journal_len, void* hip_stream);
+/* The swap.  There is no tag: nothing is hashed, the arity only selects the level layout.  For every entry g < min(*d_journal_len,
+ * journal_cap) the entry's 32 bytes and the 32 bytes of the node it names change places: the forest gets the journal's value, the
+ * journal the forest's.  d_roots (device, n_trees scalars, may be NULL): an entry that is its tree's top also rewrites d_roots[t] —
+ * the node's bytes, or for a one-leaf tree the restored leaf reduced, as the update writes it.  After one swap d_leaves, the used
+ * part of d_levels and the roots of the touched trees are byte for byte what they were before the journaled update; after a second
+ * swap, what they were after it.  The ids and the length never change.  Journals STACK: updates A then B are undone by swap(B),
+ * swap(A) and redone by swap(A), swap(B); any other order is the caller's error, and still writes only inside the forest.
+ * A JOURNAL IS ONLY MEANINGFUL FOR THE FOREST SHAPE (d_offsets) IT WAS TAKEN ON: the append and resize calls produce a new forest
+ * and void every older journal.  The ids are the caller's data, so each is checked against the forest's own index (recomputed as the
+ * update recomputes it): an entry writes nothing and is counted once in *d_n_bad (device uint32 the caller has zeroed; may be NULL)
+ * when its id is void, its tree id >= n_trees, its tree is a bad tree, its level is above the tree's depth, or its node index is at
+ * or past the level's node count.  Ids that name one node twice (no journal of the update does) race with each other inside that
+ * node.  The launch is sized by journal_cap and leaves on the device-side length: an all-void or zero-length journal is P252_OK, and
+ * journal_cap == 0 enqueues nothing.  d_journal_len is required and read only.  Asynchronous on hip_stream, no host synchronisation,
+ * no allocation once the scratch (the forest's index, 16 bytes per tree) is warm, no memset node.  Measured:
+ * profiles/forest_journal.txt.  There is no host-buffer twin: both calls act on a forest that lives on the device. */
+int p252_merkle4_forest_ragged_journal_swap_device_into(p252_ctx* ctx, void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                   size_t max_leaves, void* d_levels, void* d_journal_ids, void* d_journal_values,
+                                                   size_t journal_cap, const void* d_journal_len, void* d_roots, void* d_n_bad,
+                                                   void* hip_stream);
+/* the same for arity 2 */
+int p252_merkle2_forest_ragged_journal_swap_device_into(p252_ctx* ctx, void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                   size_t max_leaves, void* d_levels, void* d_journal_ids, void* d_journal_values,
+                                                   size_t journal_cap, const void* d_journal_len, void* d_roots, void* d_n_bad,
+                                                   void* hip_stream);
 
 /* Leaves appended to the trees of such a forest, written INTO a new compact forest.  A tree's size fixes its level layout, so a
  * forest cannot grow in place; but of a tree of n leaves that receives m > 0 more, node j of level l is unchanged iff

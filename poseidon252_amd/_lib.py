@@ -98,6 +98,12 @@ PROTOTYPES = {
     "p252_merkle2_forest_ragged_verify_device": _f(_vp, _u64p, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp),
     "p252_merkle4_forest_ragged_update_device": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
     "p252_merkle2_forest_ragged_update_device": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
+    "p252_merkle4_forest_ragged_journal_bound": _f(_sz, _sz, _sz, _sz, ret=_sz),
+    "p252_merkle2_forest_ragged_journal_bound": _f(_sz, _sz, _sz, _sz, ret=_sz),
+    "p252_merkle4_forest_ragged_update_journaled_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp),
+    "p252_merkle2_forest_ragged_update_journaled_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp),
+    "p252_merkle4_forest_ragged_journal_swap_device_into": _f(_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
+    "p252_merkle2_forest_ragged_journal_swap_device_into": _f(_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
     "p252_merkle4_forest_ragged_append_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
     "p252_merkle2_forest_ragged_append_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
     "p252_merkle4_forest_ragged_resize_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp),

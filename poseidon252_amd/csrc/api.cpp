@@ -15,6 +15,7 @@
 #include "blake2b.hpp"
 #include "ctx.hpp"
 #include "forest_append.h"
+#include "forest_journal.h"
 #include "forest_openings.h"
 #include "forest_ragged.h"
 #include "forest_update.h"
@@ -854,6 +855,141 @@ int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
                                              void* d_n_hashed, void* hip_stream) {
     return forest_ragged_update_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
                                        d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, hip_stream);
+}
+
+// ---- the same update with a journal of every leaf and node it overwrites, and the swap that plays the journal back: undo, then
+// redo, with no digest (forest_journal.hip).  The update's scratch is the plain update's, its claim table also serving level 0; the
+// swap's is the forest's index alone.  The journal is the caller's ----
+size_t p252_merkle4_forest_ragged_journal_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
+    return forest_journal_bound(4, n_leaves, n_trees, max_leaves, k);
+}
+size_t p252_merkle2_forest_ragged_journal_bound(size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
+    return forest_journal_bound(2, n_leaves, n_trees, max_leaves, k);
+}
+
+// what both calls ask of the journal's three buffers
+static int journal_check(p252_ctx* ctx, const char* who, const void* d_journal_ids, const void* d_journal_values, size_t journal_cap,
+                         const void* d_journal_len) {
+    if (!d_journal_len || (journal_cap && (!d_journal_ids || !d_journal_values)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_journal_ids) || misaligned(d_journal_values)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_journal_len, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_journal_len must be 8-byte aligned");
+    if (journal_cap > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    return P252_OK;
+}
+
+static int forest_ragged_update_journaled_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                 const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                 const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
+                                                 void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids, void* d_journal_values,
+                                                 size_t journal_cap, void* d_journal_len, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const char* who = "merkle_forest_ragged_update_journaled";
+    if (int rc = journal_check(ctx, who, d_journal_ids, d_journal_values, journal_cap, d_journal_len)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (k == 0) {  // no update, an empty journal: the length is the one thing the call always sets
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemsetAsync(d_journal_len, 0, 8, st));
+        return P252_OK;
+    }
+    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
+    const size_t depth = forest_ragged_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
+    if (!tag || !d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_new_leaves || (depth && !d_levels))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_new_leaves) || misaligned(d_roots))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets, d_leaf_ids and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    if (k > SIZE_MAX / 128) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    const ForestJournalPlan plan = forest_journal_plan(arity, n_leaves, n_trees, max_leaves, k);
+    if (journal_cap < plan.bound)  // (nothing is enqueued: the device can never run past the journal)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": journal_cap " + std::to_string(journal_cap) +
+                                                        " is below the call's bound of " + std::to_string(plan.bound) + " entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t index_bytes = forest_ragged_index_bytes(n_trees);
+    ForestJournal j;
+    j.ids = d_journal_ids;
+    j.values = d_journal_values;
+    j.cap = journal_cap;
+    j.len = d_journal_len;
+    return with_stream_scratch(ctx, who, st, index_bytes + plan.up.ids_bytes(), plan.table_bytes, [&](p252_ctx::LevelSet& set) {
+        char* meta = static_cast<char*>(set.buf[0]);
+        const uint64_t *ntree = nullptr, *lo = nullptr;
+        const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
+        if (e != hipSuccess) return e;
+        return launch_forest_update_journaled(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids,
+                                              d_new_leaves, d_roots, d_n_bad, d_n_hashed, j, meta + index_bytes, set.buf[1], st);
+    });
+}
+
+int p252_merkle4_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                       const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                       const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
+                                                       void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids,
+                                                       void* d_journal_values, size_t journal_cap, void* d_journal_len, void* hip_stream) {
+    return forest_ragged_update_journaled_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
+                                                 d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, d_journal_ids, d_journal_values,
+                                                 journal_cap, d_journal_len, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                       const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                       const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
+                                                       void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids,
+                                                       void* d_journal_values, size_t journal_cap, void* d_journal_len, void* hip_stream) {
+    return forest_ragged_update_journaled_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
+                                                 d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, d_journal_ids, d_journal_values,
+                                                 journal_cap, d_journal_len, hip_stream);
+}
+
+static int forest_ragged_journal_swap_device(p252_ctx* ctx, unsigned arity, void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                             size_t n_trees, size_t max_leaves, void* d_levels, void* d_journal_ids, void* d_journal_values,
+                                             size_t journal_cap, const void* d_journal_len, void* d_roots, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (journal_cap == 0) return P252_OK;
+    const char* who = "merkle_forest_ragged_journal_swap";
+    if (int rc = journal_check(ctx, who, d_journal_ids, d_journal_values, journal_cap, d_journal_len)) return rc;
+    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
+    const size_t depth = forest_ragged_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
+    if (!d_leaves || !d_offsets || (depth && !d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_roots)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    ForestJournal j;
+    j.ids = d_journal_ids;
+    j.values = d_journal_values;
+    j.cap = journal_cap;
+    j.len = const_cast<void*>(d_journal_len);  // (read only: k_fj_swap never writes the length)
+    return with_stream_scratch(ctx, who, st, forest_ragged_index_bytes(n_trees), 0, [&](p252_ctx::LevelSet& set) {
+        const uint64_t *ntree = nullptr, *lo = nullptr;
+        const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, set.buf[0], &ntree, &lo, st);
+        if (e != hipSuccess) return e;
+        return launch_forest_journal_swap(arity, d_leaves, d_offsets, ntree, lo, n_trees, d_levels, j, d_roots, d_n_bad, st);
+    });
+}
+
+int p252_merkle4_forest_ragged_journal_swap_device_into(p252_ctx* ctx, void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                   size_t max_leaves, void* d_levels, void* d_journal_ids, void* d_journal_values,
+                                                   size_t journal_cap, const void* d_journal_len, void* d_roots, void* d_n_bad,
+                                                   void* hip_stream) {
+    return forest_ragged_journal_swap_device(ctx, 4, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids,
+                                             d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_journal_swap_device_into(p252_ctx* ctx, void* d_leaves, size_t n_leaves, const void* d_offsets, size_t n_trees,
+                                                   size_t max_leaves, void* d_levels, void* d_journal_ids, void* d_journal_values,
+                                                   size_t journal_cap, const void* d_journal_len, void* d_roots, void* d_n_bad,
+                                                   void* hip_stream) {
+    return forest_ragged_journal_swap_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids,
+                                             d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad, hip_stream);
 }
 
 // ---- leaves appended to the trees of such a forest, written as a new compact forest: clean nodes moved, dirty ones hashed once

@@ -520,6 +520,84 @@ class Context:
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
+    # ---- the update with a journal, and the swap that undoes and redoes it (p252_merkle{4,2}_forest_ragged_journal_*, _update_journaled_device_into;
+    # csrc/forest_journal.hip) ----
+    def merkle4_forest_ragged_journal_bound(self, n_leaves, n_trees, max_leaves, k):
+        """the most journal entries one journaled update of k leaves writes (p252_merkle4_forest_ragged_journal_bound): the capacity
+        merkle4_forest_ragged_update_journaled_device asks of its journal"""
+        return int(_ARITIES[4].fn("forest_ragged_journal_bound")(n_leaves, n_trees, max_leaves, k))
+
+    def merkle2_forest_ragged_journal_bound(self, n_leaves, n_trees, max_leaves, k):
+        """the same for arity 2"""
+        return int(_ARITIES[2].fn("forest_ragged_journal_bound")(n_leaves, n_trees, max_leaves, k))
+
+    def merkle4_forest_ragged_update_journaled_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                                      d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len,
+                                                      d_roots=None, d_n_bad=None, d_n_hashed=None):
+        """merkle_forest_ragged_update_device keeping a journal of every leaf and node it overwrites
+        (p252_merkle4_forest_ragged_update_journaled_device_into): the update's arguments with its meaning, except that of a (tree, leaf) pair
+        given several times exactly one update is applied, whole, and the others are dropped without a count.  The journal is the
+        caller's: d_journal_ids (journal_cap x 4 int32/uint32), d_journal_values (journal_cap scalars), d_journal_len (one device
+        int64/uint64, set by the call); journal_cap >= merkle4_forest_ragged_journal_bound(..), else the library refuses the call.
+        merkle4_forest_ragged_journal_swap_device plays it back."""
+        self._forest_ragged_update_journaled_device("merkle4_forest_ragged_update_journaled_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees,
+                                                    max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves, k, d_journal_ids, d_journal_values,
+                                                    journal_cap, d_journal_len, d_roots, d_n_bad, d_n_hashed)
+
+    def merkle2_forest_ragged_update_journaled_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                                      d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len,
+                                                      d_roots=None, d_n_bad=None, d_n_hashed=None):
+        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
+        self._forest_ragged_update_journaled_device("merkle2_forest_ragged_update_journaled_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees,
+                                                    max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves, k, d_journal_ids, d_journal_values,
+                                                    journal_cap, d_journal_len, d_roots, d_n_bad, d_n_hashed)
+
+    def _forest_ragged_update_journaled_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                               d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad,
+                                               d_n_hashed):
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        self._check(a.fn("forest_ragged_update_journaled_device_into")(
+            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
+            _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32), k, _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
+            _dev_ptr(self, f, "d_journal_ids", d_journal_ids, journal_cap * 16, elem=4, null_ok=journal_cap == 0),
+            _dev_ptr(self, f, "d_journal_values", d_journal_values, journal_cap * 32, null_ok=journal_cap == 0), journal_cap,
+            _dev_ptr(self, f, "d_journal_len", d_journal_len, 8, elem=8), _stream(self)))
+
+    def merkle4_forest_ragged_journal_swap_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
+                                                  journal_cap, d_journal_len, d_roots=None, d_n_bad=None):
+        """the journal of merkle4_forest_ragged_update_journaled_device played back (p252_merkle4_forest_ragged_journal_swap_device_into; no
+        tag, nothing is hashed): each of the first min(d_journal_len, journal_cap) entries changes places with the node it names, so
+        one call undoes the update byte for byte and a second one redoes it; d_roots (n_trees, 4; optional) follows for the touched
+        trees.  The forest arguments exactly as the update took them — a journal is void on any other shape.  An entry that names no
+        node of this forest writes nothing and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
+        self._forest_ragged_journal_swap_device("merkle4_forest_ragged_journal_swap_device", _ARITIES[4], d_leaves, d_offsets, n_trees, max_leaves,
+                                                d_levels, d_journal_ids, d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad)
+
+    def merkle2_forest_ragged_journal_swap_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
+                                                  journal_cap, d_journal_len, d_roots=None, d_n_bad=None):
+        """the same for arity 2"""
+        self._forest_ragged_journal_swap_device("merkle2_forest_ragged_journal_swap_device", _ARITIES[2], d_leaves, d_offsets, n_trees, max_leaves,
+                                                d_levels, d_journal_ids, d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad)
+
+    def _forest_ragged_journal_swap_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
+                                           journal_cap, d_journal_len, d_roots, d_n_bad):
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        self._check(a.fn("forest_ragged_journal_swap_device_into")(
+            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_journal_ids", d_journal_ids, journal_cap * 16, elem=4, null_ok=journal_cap == 0),
+            _dev_ptr(self, f, "d_journal_values", d_journal_values, journal_cap * 32, null_ok=journal_cap == 0), journal_cap,
+            _dev_ptr(self, f, "d_journal_len", d_journal_len, 8, elem=8), _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
     def merkle4_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
                                             max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None):
         """leaves appended to the trees of a forest merkle_forest_ragged_device built with d_levels, written INTO a new compact forest

@@ -190,6 +190,64 @@ def forest_ragged_resize(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_l
     return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
 
 
+class ForestJournal:
+    """what one journaled update overwrote (forest_ragged_update_journaled), on the device: ids (cap, 4) int32 {tree id, level + 1, node
+    index low, high}, values (cap, 4) int64, len (1,) int64 = the entries in use; n_bad (1,) int32 and n_hashed (1,) int64 are the
+    update's counters.  forest_ragged_journal_swap takes it, any number of times."""
+
+    def __init__(self, ids, values, len, n_bad, n_hashed):  # noqa: A002 (the journal's length, as the C call names it)
+        self.ids, self.values, self.len, self.n_bad, self.n_hashed = ids, values, len, n_bad, n_hashed
+
+    @property
+    def cap(self):
+        return self.ids.shape[0]
+
+
+def forest_ragged_update_journaled(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, leaf_ids, new_leaves, d_roots=None,
+                                   arity=4):
+    """Leaf updates of a built forest that can be undone (Context.merkle{4,2}_forest_ragged_update_journaled_device): the forest = torch
+    CUDA tensors as Context.merkle_forest_ragged_device took and filled them, updated in place; (tree_ids[i], leaf_ids[i]) receives
+    new_leaves[i] (sequences, numpy or torch).  Allocates the journal at its bound and returns it as a ForestJournal; its counters are
+    on the device.  No synchronisation."""
+    import torch
+    f = "forest_ragged_update_journaled"
+    a = _arity(f, arity)
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    t = torch.as_tensor(tree_ids, device=dev).to(torch.int64).reshape(-1)
+    l = torch.as_tensor(leaf_ids, device=dev).to(torch.int64).reshape(-1)
+    new = new_leaves if _is_torch(new_leaves) else torch.from_numpy(np.ascontiguousarray(_as_scalars(new_leaves)).view(np.int64))
+    new = new.to(dev).contiguous()
+    k = t.numel()
+    if l.numel() != k or _n_scalars(new) != k:
+        raise ValueError("%s: %d tree ids, %d leaf ids, %d new leaves" % (f, k, l.numel(), _n_scalars(new)))
+    four = arity == 4
+    cap = (ctx.merkle4_forest_ragged_journal_bound if four else ctx.merkle2_forest_ragged_journal_bound)(_n_scalars(d_leaves), n_trees, max_leaves, k)
+    j = ForestJournal(torch.empty((cap, 4), dtype=torch.int32, device=dev), torch.empty((cap, 4), dtype=torch.int64, device=dev),
+                      torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                      torch.zeros(1, dtype=torch.int64, device=dev))
+    call = ctx.merkle4_forest_ragged_update_journaled_device if four else ctx.merkle2_forest_ragged_update_journaled_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None,
+         (t & 0xFFFFFFFF).to(torch.int32), l, new, k, j.ids if cap else None, j.values if cap else None, cap, j.len, d_roots, j.n_bad, j.n_hashed)
+    return j
+
+
+def forest_ragged_journal_swap(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, journal, d_roots=None, arity=4):
+    """The update behind `journal` (a ForestJournal) undone — or, after an undo, redone — with no hashing
+    (Context.merkle{4,2}_forest_ragged_journal_swap_device): the forest exactly as the update took it, changed in place; d_roots follows for
+    the touched trees.  Journals stack: undo the latest first, redo the earliest first.  Returns the entries that named no node of this
+    forest as a (1,) int32 device tensor: 0 for a journal used on its own forest.  No synchronisation."""
+    import torch
+    a = _arity("forest_ragged_journal_swap", arity)
+    ctx = ctx or Context.default()
+    n_bad = torch.zeros(1, dtype=torch.int32, device=d_leaves.device)
+    call = ctx.merkle4_forest_ragged_journal_swap_device if arity == 4 else ctx.merkle2_forest_ragged_journal_swap_device
+    cap = journal.cap
+    call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None, journal.ids if cap else None,
+         journal.values if cap else None, cap, journal.len, d_roots, n_bad)
+    return n_bad
+
+
 def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
     as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are
