@@ -2,9 +2,12 @@
 """Calls the ten ragged-forest entry points once each per shape, for a kernel trace: p252_merkle{4,2}_forest_ragged_device with and
 without d_levels, ..._forest_ragged_openings_device, ..._path_ragged_device, ..._forest_ragged_verify_device and
 ..._forest_ragged_update_device, on a small forest (every level on the 8-lane-group digests) and a large one (the low levels on
-the one-lane digests, the narrow top levels on the groups), with few and with many updates.  Then the other calls that work in the
-context's per-stream scratch, at one small and one chip-filling shape each: p252_hash_ragged_device, root-only
-p252_merkle{4,2}_tree_device and p252_merkle{4,2}_forest_device, p252_merkle{4,2}_verify_batch_device and
+the one-lane digests, the narrow top levels on the groups), with few and with many updates.  Then the calls that change or prove a
+built forest, on the same two forests (the large one has more trees than one scan tile of 2,048, and its pairs fill more than one
+256-element tile of the shared proof's list scan): ..._forest_ragged_update_journaled_device_into, ..._journal_swap_device_into (undo,
+redo), ..._forest_ragged_multiproof_device and its _verify_, ..._forest_ragged_append_device_into and ..._resize_device_into.  Then the
+other calls that work in the context's per-stream scratch, at one small and one chip-filling shape each: p252_hash_ragged_device,
+root-only p252_merkle{4,2}_tree_device and p252_merkle{4,2}_forest_device, p252_merkle{4,2}_verify_batch_device and
 p252_merkle{4,2}_multiproof[_verify]_device.
 
   rocprofv3 --kernel-trace -d DIR -o NAME --output-format csv -- python bench_tools/forest_dispatch_driver.py
@@ -12,7 +15,8 @@ p252_merkle{4,2}_multiproof[_verify]_device.
 
 Two builds of the library launch the same kernels in the same order with the same grids exactly when the lists are equal
 (P252_LIB_PATH selects the library; P252_RAGGED_SORT=0, read once per process, the unsorted re-hash).  Every verify call must
-accept every opening, before and after the updates: the driver exits non-zero otherwise."""
+accept every opening and every shared proof, before and after the updates, and every changed forest must have the roots of a fresh
+build of its leaves: the driver exits non-zero otherwise."""
 import argparse
 import csv
 import os
@@ -93,6 +97,78 @@ def run(ctx, arity, sizes, ks, seed):
     print("arity %d, %d trees, %d leaves, depth %d, k = %s: ok" % (arity, n_trees, n_leaves, D, list(ks)))
 
 
+def run_changes(ctx, arity, sizes, k, seed):
+    """a journaled update with its undo and redo, a shared proof of the updated pairs, an append and a resize: each result against a fresh
+    build of the forest it should equal"""
+    import torch
+    from poseidon252_amd import merkle as M
+    rng = np.random.default_rng(seed)
+    tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
+    sizes = np.asarray(sizes, np.int64)
+    n_trees, max_leaves = len(sizes), int(sizes.max())
+    off = np.zeros(n_trees + 1, np.uint64)
+    np.cumsum(sizes.astype(np.uint64), out=off[1:])
+    n_leaves, D = int(off[-1]), _depth(max_leaves, arity)
+    dev = torch.device("cuda:0")
+    d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
+    d_off = _dev(off)
+    roots = torch.empty((n_trees, 4), dtype=torch.int64, device=dev)
+    d_lv = torch.empty((n_leaves // (arity - 1) + n_trees * D + 1, 4), dtype=torch.int64, device=dev)
+    ctx.merkle_forest_ragged_device(tag, d, d_off, n_trees, max_leaves, roots, d_lv, arity=arity)
+
+    def fresh_roots(leaves, offsets, trees, top, levels_like):
+        out = torch.empty((trees, 4), dtype=torch.int64, device=dev)
+        ctx.merkle_forest_ragged_device(tag, leaves, offsets, trees, top, out, torch.empty_like(levels_like), arity=arity)
+        torch.cuda.synchronize()
+        return out
+
+    tid = rng.integers(0, n_trees, k)
+    lid = (rng.random(k) * sizes[tid]).astype(np.int64)
+    pairs = np.unique(tid.astype(np.int64) << 32 | lid)  # (distinct pairs: as in run)
+    tid, lid, k = pairs >> 32, pairs & 0xffffffff, pairs.size
+    d0, roots0 = d.clone(), roots.clone()
+    new = torch.randint(0, 1 << 60, (k, 4), dtype=torch.int64, device=dev)
+    journal = M.forest_ragged_update_journaled(ctx, tag, d, d_off, n_trees, max_leaves, d_lv, tid, lid, new, d_roots=roots, arity=arity)
+    roots1 = roots.clone()
+    assert torch.equal(roots1, fresh_roots(d, d_off, n_trees, max_leaves, d_lv)), "journaled update: not the roots of a fresh build"
+    assert int(journal.n_bad) == 0 and not torch.equal(roots1, roots0)
+    bad = M.forest_ragged_journal_swap(ctx, d, d_off, n_trees, max_leaves, d_lv, journal, d_roots=roots, arity=arity)
+    torch.cuda.synchronize()
+    assert int(bad) == 0 and torch.equal(d, d0) and torch.equal(roots, roots0), "undo: not the forest before the update"
+    bad = M.forest_ragged_journal_swap(ctx, d, d_off, n_trees, max_leaves, d_lv, journal, d_roots=roots, arity=arity)
+    torch.cuda.synchronize()
+    assert int(bad) == 0 and torch.equal(roots, roots1), "redo: not the updated forest"
+
+    def prove(what, leaves, offsets, trees, top, levels, rts, t_ids, l_ids):
+        proof = M.forest_ragged_multiproof(ctx, leaves, offsets, trees, top, levels, t_ids, l_ids, arity=arity)
+        ok = M.forest_ragged_multiproof_verify(ctx, offsets, leaves.shape[0], trees, top, *proof, rts, arity=arity, tag=tag)
+        named = torch.zeros(trees, dtype=torch.bool)
+        named[torch.as_tensor(np.unique(t_ids))] = True
+        assert torch.equal(ok, named), "%s: %d of %d trees' shared proofs verify" % (what, int(ok.sum()), int(named.sum()))
+
+    prove("updated", d, d_off, n_trees, max_leaves, d_lv, roots, tid, lid)
+
+    # an append to every third tree and two new trees, then a resize that cuts every fifth tree, drops the last two and appends again
+    m = np.where(np.arange(n_trees + 2) % 3 == 0, rng.integers(1, 2 * arity + 2, n_trees + 2), 0)
+    m[n_trees:] = (1, arity + 1)
+    a_off = np.zeros(n_trees + 3, np.uint64)
+    np.cumsum(m.astype(np.uint64), out=a_off[1:])
+    d_add = torch.randint(0, 1 << 60, (int(a_off[-1]), 4), dtype=torch.int64, device=dev)
+    top = max_leaves + 2 * (2 * arity + 1)  # (room for both appends: none is refused)
+    l2, o2, v2, r2, bad2, _ = M.forest_ragged_append(ctx, tag, d, d_off, n_trees, max_leaves, d_lv, d_add, _dev(a_off), max_leaves_new=top, arity=arity)
+    assert int(bad2) == 0 and torch.equal(r2, fresh_roots(l2, o2, n_trees + 2, top, v2)), "append: not the roots of a fresh build"
+    sizes2 = np.concatenate([sizes, [0, 0]]) + m
+    prove("appended", l2, o2, n_trees + 2, top, v2, r2, tid, lid)
+    keep = np.where(np.arange(n_trees) % 5 == 0, (sizes2[:n_trees] + 1) // 2, -1)
+    m3 = m[:n_trees] * (np.arange(n_trees) % 2)
+    a3 = np.zeros(n_trees + 1, np.uint64)
+    np.cumsum(m3.astype(np.uint64), out=a3[1:])
+    l3, o3, v3, r3, bad3, _ = M.forest_ragged_resize(ctx, tag, l2, o2, n_trees + 2, top, v2, _dev(keep.astype(np.int64)), d_add[:int(a3[-1])], _dev(a3),
+                                                     max_leaves_new=top, arity=arity)
+    assert int(bad3) == 0 and torch.equal(r3, fresh_roots(l3, o3, n_trees, top, v3)), "resize: not the roots of a fresh build"
+    print("arity %d, %d trees, %d leaves, k = %d: journaled update, undo, redo, shared proofs, append, resize ok" % (arity, n_trees, n_leaves, k))
+
+
 def run_hash_ragged(ctx, n, max_len):
     import torch
     from poseidon252_amd import hash as H
@@ -155,6 +231,9 @@ def main():
     for arity in (4, 2):
         run(ctx, arity, small, (50,), 1)
         run(ctx, arity, large, (50, 40000), 2)
+    for arity in (4, 2):
+        run_changes(ctx, arity, small, 50, 3)
+        run_changes(ctx, arity, large, 5000, 4)
     run_hash_ragged(ctx, 200, 40)
     run_hash_ragged(ctx, 70000, 8)                  # past the chip's 65,536 lanes
     for arity in (4, 2):

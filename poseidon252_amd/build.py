@@ -22,7 +22,7 @@ SOURCES = ["kernels.hip", "openings.hip", "merkle2.hip", "ragged.hip", "forest_r
 # (ROCM_PATH / HIP_PATH name the ROCm prefix when it is not /opt/rocm — ADVICE r4)
 ROCM = os.environ.get("ROCM_PATH") or os.environ.get("HIP_PATH") or "/opt/rocm"
 LINK_FLAGS = ["-ldl"]
-HEADERS = ["fr29.hpp", "fr_host.hpp", "hades29.hpp", "coop29.hpp", "tables.hpp", "kernels.h", "blake2b.hpp", "ctx.hpp", "openings.h", "ragged.h", "forest_ragged.h", "forest_openings.h", "forest_update.h", "forest_journal.h", "forest_append.h", "multiproof.h", "forest_multiproof.h", "forest_node.hpp", "fastdiv.hpp", "rccl_dyn.hpp",
+HEADERS = ["fr29.hpp", "fr_host.hpp", "hades29.hpp", "coop29.hpp", "tables.hpp", "kernels.h", "blake2b.hpp", "ctx.hpp", "openings.h", "ragged.h", "forest_ragged.h", "forest_openings.h", "forest_update.h", "forest_journal.h", "forest_append.h", "multiproof.h", "forest_multiproof.h", "forest_node.hpp", "blockops.hpp", "fastdiv.hpp", "rccl_dyn.hpp",
            os.path.join("..", "..", "include", "poseidon252_hip.h")]
 
 

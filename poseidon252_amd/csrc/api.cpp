@@ -804,16 +804,36 @@ int p252_merkle2_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4
                                        d_ok, k, hip_stream);
 }
 
+// what the journaled update and the journal's swap (both further down) ask of the journal's three buffers
+static int journal_check(p252_ctx* ctx, const char* who, const void* d_journal_ids, const void* d_journal_values, size_t journal_cap,
+                         const void* d_journal_len) {
+    if (!d_journal_len || (journal_cap && (!d_journal_ids || !d_journal_values)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
+    if (misaligned(d_journal_ids) || misaligned(d_journal_values)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_journal_len, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_journal_len must be 8-byte aligned");
+    if (journal_cap > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    return P252_OK;
+}
+
 // ---- leaf updates anywhere in such a forest in one call, every dirty node hashed once (forest_update.hip).  The scratch — the
 // forest's index, two lists of node ids and the per-level counters; the claim table in the second buffer — is the pair of the
 // calling stream; it holds ids only, never a copy of the new leaves ----
+// `j`: the journaled update (forest_journal.hip), which asks its own checks of the journal first and of its capacity last
 static int forest_ragged_update_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
                                        const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels, const void* d_tree_ids,
                                        const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
-                                       void* d_n_hashed, void* hip_stream) {
+                                       void* d_n_hashed, const ForestJournal* j, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const char* who = j ? "merkle_forest_ragged_update_journaled" : "merkle_forest_ragged_update";
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (j) {
+        if (int rc = journal_check(ctx, who, j->ids, j->values, j->cap, j->len)) return rc;
+        if (k == 0) {  // no update, an empty journal: the length is the one thing the call always sets
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipMemsetAsync(j->len, 0, 8, st));
+        }
+    }
     if (k == 0) return P252_OK;
-    const char* who = "merkle_forest_ragged_update";
     if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
     const size_t depth = forest_ragged_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
@@ -827,17 +847,23 @@ static int forest_ragged_update_device(p252_ctx* ctx, unsigned arity, const uint
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
     if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
     if (k > SIZE_MAX / 128) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
+    const ForestJournalPlan plan = forest_journal_plan(arity, n_leaves, n_trees, max_leaves, k);  // (plan.up: the plain update's)
+    if (j && j->cap < plan.bound)  // (nothing is enqueued: the device can never run past the journal)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": journal_cap " + std::to_string(j->cap) +
+                                                        " is below the call's bound of " + std::to_string(plan.bound) + " entries");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)hip_stream;
     const size_t index_bytes = forest_ragged_index_bytes(n_trees);
-    const ForestUpdatePlan plan = forest_update_plan(arity, n_leaves, n_trees, max_leaves, k);
-    return with_stream_scratch(ctx, who, st, index_bytes + plan.ids_bytes(), plan.table_bytes, [&](p252_ctx::LevelSet& set) {
+    const size_t table_bytes = j ? plan.table_bytes : plan.up.table_bytes;  // (the journal's claim table also serves level 0)
+    return with_stream_scratch(ctx, who, st, index_bytes + plan.up.ids_bytes(), table_bytes, [&](p252_ctx::LevelSet& set) {
         char* meta = static_cast<char*>(set.buf[0]);
         const uint64_t *ntree = nullptr, *lo = nullptr;
         const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
         if (e != hipSuccess) return e;
-        return launch_forest_update(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves,
-                                    d_roots, d_n_bad, d_n_hashed, meta + index_bytes, set.buf[1], st);
+        if (j)
+            return launch_forest_update_journaled(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids,
+                                                  d_new_leaves, d_roots, d_n_bad, d_n_hashed, *j, meta + index_bytes, set.buf[1], st);
+        return launch_forest_update(ctx->d_tab, tag_arg(tag), plan.up, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids,
+                                    d_new_leaves, d_roots, d_n_bad, d_n_hashed, meta + index_bytes, set.buf[1], st);
     });
 }
 
@@ -846,7 +872,7 @@ int p252_merkle4_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
                                              const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
                                              void* d_n_hashed, void* hip_stream) {
     return forest_ragged_update_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
-                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, hip_stream);
+                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, nullptr, hip_stream);
 }
 
 int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, const void* d_offsets,
@@ -854,7 +880,7 @@ int p252_merkle2_forest_ragged_update_device(p252_ctx* ctx, const uint64_t tag[4
                                              const void* d_leaf_ids, const void* d_new_leaves, size_t k, void* d_roots, void* d_n_bad,
                                              void* d_n_hashed, void* hip_stream) {
     return forest_ragged_update_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
-                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, hip_stream);
+                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, nullptr, hip_stream);
 }
 
 // ---- the same update with a journal of every leaf and node it overwrites, and the swap that plays the journal back: undo, then
@@ -867,73 +893,14 @@ size_t p252_merkle2_forest_ragged_journal_bound(size_t n_leaves, size_t n_trees,
     return forest_journal_bound(2, n_leaves, n_trees, max_leaves, k);
 }
 
-// what both calls ask of the journal's three buffers
-static int journal_check(p252_ctx* ctx, const char* who, const void* d_journal_ids, const void* d_journal_values, size_t journal_cap,
-                         const void* d_journal_len) {
-    if (!d_journal_len || (journal_cap && (!d_journal_ids || !d_journal_values)))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
-    if (misaligned(d_journal_ids) || misaligned(d_journal_values)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if (misaligned_to(d_journal_len, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_journal_len must be 8-byte aligned");
-    if (journal_cap > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
-    return P252_OK;
-}
-
-static int forest_ragged_update_journaled_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
-                                                 const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
-                                                 const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
-                                                 void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids, void* d_journal_values,
-                                                 size_t journal_cap, void* d_journal_len, void* hip_stream) {
-    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    const char* who = "merkle_forest_ragged_update_journaled";
-    if (int rc = journal_check(ctx, who, d_journal_ids, d_journal_values, journal_cap, d_journal_len)) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (k == 0) {  // no update, an empty journal: the length is the one thing the call always sets
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipMemsetAsync(d_journal_len, 0, 8, st));
-        return P252_OK;
-    }
-    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": n_leaves, n_trees and max_leaves must be > 0");
-    const size_t depth = forest_ragged_depth(max_leaves < n_leaves ? max_leaves : n_leaves, arity);
-    if (!tag || !d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_new_leaves || (depth && !d_levels))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL buffer");
-    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_new_leaves) || misaligned(d_roots))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_n_hashed, 8))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_offsets, d_leaf_ids and d_n_hashed must be 8-byte aligned");
-    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": d_tree_ids and d_n_bad must be 4-byte aligned");
-    if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
-    if (k > SIZE_MAX / 128) return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": size overflow");
-    const ForestJournalPlan plan = forest_journal_plan(arity, n_leaves, n_trees, max_leaves, k);
-    if (journal_cap < plan.bound)  // (nothing is enqueued: the device can never run past the journal)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, std::string(who) + ": journal_cap " + std::to_string(journal_cap) +
-                                                        " is below the call's bound of " + std::to_string(plan.bound) + " entries");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t index_bytes = forest_ragged_index_bytes(n_trees);
-    ForestJournal j;
-    j.ids = d_journal_ids;
-    j.values = d_journal_values;
-    j.cap = journal_cap;
-    j.len = d_journal_len;
-    return with_stream_scratch(ctx, who, st, index_bytes + plan.up.ids_bytes(), plan.table_bytes, [&](p252_ctx::LevelSet& set) {
-        char* meta = static_cast<char*>(set.buf[0]);
-        const uint64_t *ntree = nullptr, *lo = nullptr;
-        const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
-        if (e != hipSuccess) return e;
-        return launch_forest_update_journaled(ctx->d_tab, tag_arg(tag), plan, d_leaves, d_offsets, ntree, lo, d_levels, d_tree_ids, d_leaf_ids,
-                                              d_new_leaves, d_roots, d_n_bad, d_n_hashed, j, meta + index_bytes, set.buf[1], st);
-    });
-}
-
 int p252_merkle4_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
                                                        const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
                                                        const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
                                                        void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids,
                                                        void* d_journal_values, size_t journal_cap, void* d_journal_len, void* hip_stream) {
-    return forest_ragged_update_journaled_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
-                                                 d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, d_journal_ids, d_journal_values,
-                                                 journal_cap, d_journal_len, hip_stream);
+    const ForestJournal j{d_journal_ids, d_journal_values, journal_cap, d_journal_len};
+    return forest_ragged_update_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, &j, hip_stream);
 }
 
 int p252_merkle2_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
@@ -941,9 +908,9 @@ int p252_merkle2_forest_ragged_update_journaled_device_into(p252_ctx* ctx, const
                                                        const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, size_t k,
                                                        void* d_roots, void* d_n_bad, void* d_n_hashed, void* d_journal_ids,
                                                        void* d_journal_values, size_t journal_cap, void* d_journal_len, void* hip_stream) {
-    return forest_ragged_update_journaled_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
-                                                 d_leaf_ids, d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, d_journal_ids, d_journal_values,
-                                                 journal_cap, d_journal_len, hip_stream);
+    const ForestJournal j{d_journal_ids, d_journal_values, journal_cap, d_journal_len};
+    return forest_ragged_update_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                       d_new_leaves, k, d_roots, d_n_bad, d_n_hashed, &j, hip_stream);
 }
 
 static int forest_ragged_journal_swap_device(p252_ctx* ctx, unsigned arity, void* d_leaves, size_t n_leaves, const void* d_offsets,
@@ -963,11 +930,7 @@ static int forest_ragged_journal_swap_device(p252_ctx* ctx, unsigned arity, void
     if (int rc = forest_shape_check(ctx, who, n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    ForestJournal j;
-    j.ids = d_journal_ids;
-    j.values = d_journal_values;
-    j.cap = journal_cap;
-    j.len = const_cast<void*>(d_journal_len);  // (read only: k_fj_swap never writes the length)
+    const ForestJournal j{d_journal_ids, d_journal_values, journal_cap, const_cast<void*>(d_journal_len)};  // (read only: k_fj_swap never writes the length)
     return with_stream_scratch(ctx, who, st, forest_ragged_index_bytes(n_trees), 0, [&](p252_ctx::LevelSet& set) {
         const uint64_t *ntree = nullptr, *lo = nullptr;
         const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, set.buf[0], &ntree, &lo, st);

@@ -32,6 +32,7 @@
 // by an earlier launch.  No kernel here hashes.
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "forest_append.h"
 #include "forest_node.hpp"
 #include "forest_update.h"
@@ -72,37 +73,6 @@ __device__ __forceinline__ uint64_t scan_value(const FaTrees& T, size_t t, unsig
     return dirty_nodes(T.nold[t], T.keep[t], m, l, T.la);
 }
 
-// exclusive scan of one value per thread over the block (the block total in *total)
-__device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* total) {
-    __shared__ uint64_t part[FA_BLOCK];
-    const unsigned t = threadIdx.x;
-    part[t] = v;
-    __syncthreads();
-    for (unsigned off = 1; off < FA_BLOCK; off <<= 1) {
-        const uint64_t o = t >= off ? part[t - off] : 0ull;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    const uint64_t incl = part[t];
-    *total = part[FA_BLOCK - 1];
-    __syncthreads();  // (part is reused by the caller's next call)
-    return incl - v;
-}
-
-// the largest t in [lo, hi] with B[t] <= g (B ascending, B[lo] <= g): of trees that start at the same place, the last — the one that
-// holds g when g is below the total
-__device__ __forceinline__ size_t last_at_or_below(const uint64_t* __restrict__ B, size_t lo, size_t hi, uint64_t g) {
-    while (lo < hi) {
-        const size_t mid = (lo + hi + 1) >> 1;
-        if (B[mid] <= g)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 }  // namespace
 
 // ---- per tree: the old leaf count, the kept count (keep_in null: every tree whole) and the append ----
@@ -132,24 +102,14 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_tile_sums(FaTrees T, uint64_t* 
     for (unsigned k = 0; k < FA_ITEMS; ++k)
         if (t0 + k < T.n_trees) sum += scan_value<MODE>(T, t0 + k, l);
     uint64_t total;
-    (void)block_exclusive(sum, &total);
+    (void)block_exclusive<FA_BLOCK>(sum, &total);
     if (threadIdx.x == 0) tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
-// one block per row (SUM, OFFS, one DIRTY row per level): the tile sums of the row -> their exclusive scan, in place.  FA_BLOCK tiles a
-// trip of the loop, `carry` from trip to trip: the second trip starts past FA_BLOCK * FOREST_APPEND_SCAN_TILE = 524,288 new trees
+// one block per row (SUM, OFFS, one DIRTY row per level): the tile sums of the row -> their exclusive scan, in place (scan_tile_row of
+// blockops.hpp: the second trip of its loop starts past FA_BLOCK * FOREST_APPEND_SCAN_TILE = 524,288 new trees)
 __global__ void __launch_bounds__(FA_BLOCK) k_fa_scan_tiles(uint64_t* __restrict__ tsum, size_t tiles) {
-    uint64_t* row = tsum + (size_t)blockIdx.x * tiles;
-    uint64_t carry = 0;
-#pragma unroll 1
-    for (size_t base = 0; base < tiles; base += FA_BLOCK) {
-        const size_t i = base + threadIdx.x;
-        const uint64_t v = i < tiles ? row[i] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_exclusive(v, &total);
-        if (i < tiles) row[i] = carry + ex;
-        carry += total;
-    }
+    scan_tile_row<FA_BLOCK>(tsum + (size_t)blockIdx.x * tiles, tiles);
 }
 
 // SUM: the sum rule, m_t settled, the bad trees counted and their roots zeroed.  OFFS: out = d_offsets_new (n_trees + 1).
@@ -164,7 +124,7 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_scan_apply(FaTrees T, const uin
     for (unsigned k = 0; k < FA_ITEMS; ++k)
         if (t0 + k < T.n_trees) sum += scan_value<MODE>(T, t0 + k, l);
     uint64_t total;
-    uint64_t run = tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive(sum, &total);
+    uint64_t run = tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive<FA_BLOCK>(sum, &total);
     uint64_t* row = MODE == FA_DIRTY ? out + (size_t)l * (T.n_trees + 1) : out;
 #pragma unroll 1
     for (unsigned k = 0; k < FA_ITEMS; ++k) {
@@ -277,7 +237,7 @@ __global__ void __launch_bounds__(FA_BLOCK) k_fa_expand(const uint64_t* __restri
     if (g >= L.in[l] || g >= row[T.n_trees]) return;
     const size_t t = last_at_or_below(row, 0, T.n_trees - 1, g);
     const uint64_t i = floor_shift(T.keep[t], l * T.la) + (g - row[t]);
-    lists[L.off[l] + g] = make_uint4((unsigned)t, 1u, (unsigned)i, (unsigned)(i >> 32));
+    lists[L.off[l] + g] = record((uint32_t)t, i);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 // swap's lanes touch disjoint bytes of the forest and disjoint bytes of the journal.  Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "forest_journal.h"
 #include "forest_node.hpp"
 #include "forest_update.h"
@@ -27,36 +28,10 @@ namespace p252 {
 namespace {
 
 constexpr unsigned FJ_BLOCK = 256;
-constexpr unsigned long long FJ_EMPTY = ~0ull;  // (the table is cleared to 0xFF bytes; no slot of the forest has this number)
-constexpr size_t FJ_MIN_SLOTS = 64;
 
-// a record of the level lists, as k_fu_claim writes it and k_fu_digest reads it (forest_update.h)
-__device__ __forceinline__ uint4 record(uint32_t t, uint64_t i) { return make_uint4(t, 1u, (unsigned)i, (unsigned)(i >> 32)); }
 // a journal id: level 0 = the leaves
 __device__ __forceinline__ uint4 journal_id(uint32_t t, unsigned level, uint64_t i) {
     return make_uint4(t, level + 1u, (unsigned)i, (unsigned)(i >> 32));
-}
-
-// empty -> key in a table of 2^(64 - shift) slots, at most half full: true for the one lane that installs the key
-__device__ __forceinline__ bool claim(unsigned long long* __restrict__ table, unsigned shift, unsigned long long key) {
-    const size_t mask = ((size_t)1 << (64 - shift)) - 1;
-    size_t h = (size_t)((key * 0x9E3779B97F4A7C15ull) >> shift);
-    for (;;) {  // (an empty slot is met)
-        const unsigned long long seen = atomicCAS(table + h, FJ_EMPTY, key);
-        if (seen == FJ_EMPTY) return true;
-        if (seen == key) return false;
-        h = (h + 1) & mask;
-    }
-}
-
-// the wave's winners take consecutive places behind *count: the place of this lane (valid where won).  The whole wave calls this.
-__device__ __forceinline__ unsigned long long append_place(bool won, unsigned long long winners, unsigned long long* __restrict__ count) {
-    const unsigned lane = threadIdx.x & 63u;
-    const int leader = __ffsll((long long)winners) - 1;
-    unsigned long long base = 0;
-    if ((int)lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(winners));
-    base = __shfl(base, leader);
-    return base + __popcll(winners & ((1ull << lane) - 1));
 }
 
 struct Journal {
@@ -188,18 +163,12 @@ size_t forest_journal_bound(unsigned arity, size_t n_leaves, size_t n_trees, siz
 ForestJournalPlan forest_journal_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k) {
     ForestJournalPlan p;
     p.up = forest_update_plan(arity, n_leaves, n_trees, max_leaves, k);
-    p.slots0 = FJ_MIN_SLOTS;
+    p.slots0 = CLAIM_MIN_SLOTS;
     while (p.slots0 < 2 * k) p.slots0 <<= 1;
     const size_t bytes0 = p.slots0 * sizeof(unsigned long long);
     p.table_bytes = bytes0 > p.up.table_bytes ? bytes0 : p.up.table_bytes;
     p.bound = forest_journal_bound(arity, n_leaves, n_trees, max_leaves, k);
     return p;
-}
-
-static unsigned shift_of(size_t slots) {
-    unsigned shift = 64;
-    for (size_t s = slots; s > 1; s >>= 1) --shift;
-    return shift;
 }
 
 hipError_t launch_forest_update_journaled(const int32_t* tab, const TagArg& tag, const ForestJournalPlan& plan, void* leaves,
@@ -208,9 +177,6 @@ hipError_t launch_forest_update_journaled(const int32_t* tab, const TagArg& tag,
                                           const ForestJournal& j, void* ids, void* table, hipStream_t st) {
     const ForestUpdatePlan& p = plan.up;
     if (p.k == 0) return hipSuccess;
-    char* base = static_cast<char*>(ids);
-    unsigned long long* count = reinterpret_cast<unsigned long long*>(base);
-    uint4* list[2] = {reinterpret_cast<uint4*>(base + p.count_bytes), reinterpret_cast<uint4*>(base + p.count_bytes + p.list_bytes)};
     unsigned long long* tb = static_cast<unsigned long long*>(table);
     const uint64_t* off = static_cast<const uint64_t*>(offsets);
     const Journal J{static_cast<uint4*>(j.ids), static_cast<uint4*>(j.values), (unsigned long long)j.cap,
@@ -221,37 +187,22 @@ hipError_t launch_forest_update_journaled(const int32_t* tab, const TagArg& tag,
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fj_leaves, dim3((unsigned)((p.k + FJ_BLOCK - 1) / FJ_BLOCK)), dim3(FJ_BLOCK), 0, st, off, ntree, p.n_trees,
                        static_cast<const uint32_t*>(tree_ids), static_cast<const uint64_t*>(leaf_ids), static_cast<const uint4*>(new_leaves),
-                       p.k, static_cast<uint4*>(leaves), static_cast<uint4*>(roots), list[0], static_cast<unsigned*>(n_bad), tb,
+                       p.k, static_cast<uint4*>(leaves), static_cast<uint4*>(roots), p.list(ids, 0), static_cast<unsigned*>(n_bad), tb,
                        shift_of(plan.slots0), J);
     e = hipGetLastError();
     if (e != hipSuccess || p.depth == 0) return e;
-    e = hipMemsetAsync(count, 0, p.count_bytes, st);
-    if (e != hipSuccess) return e;
-    for (unsigned l = 1; l <= p.depth; ++l) {
-        e = hipMemsetAsync(tb, 0xFF, p.slots[l] * sizeof(unsigned long long), st);
-        if (e != hipSuccess) return e;
-        const size_t lanes = p.in[l - 1];
-        hipLaunchKernelGGL(k_fj_claim, dim3((unsigned)((lanes + FJ_BLOCK - 1) / FJ_BLOCK)), dim3(FJ_BLOCK), 0, st, list[(l - 1) & 1],
-                           l == 1 ? (const unsigned long long*)nullptr : count + (l - 1), lanes, ntree, lo, l, p.log2a, tb,
-                           shift_of(p.slots[l]), list[l & 1], count + l, static_cast<const uint4*>(levels), J);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ForestDigestList d;
-        d.list = list[l & 1];
-        d.count = count + l;
-        d.bound = p.in[l];
-        d.ntree = ntree;
-        d.lo = lo;
-        d.offsets = offsets;
-        d.leaves = leaves;
-        d.levels = levels;
-        d.roots = roots;
-        d.n_hashed = n_hashed;
-        d.level = l;
-        e = launch_forest_digest_list(tab, tag, p.arity, p.log2a, d, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    ForestDigestList d;
+    d.ntree = ntree;
+    d.lo = lo;
+    d.offsets = offsets;
+    d.leaves = leaves;
+    d.levels = levels;
+    d.roots = roots;
+    d.n_hashed = n_hashed;
+    return launch_forest_update_levels(tab, tag, p, d, ids, table, st, [&](const ForestClaimLevel& c) {
+        hipLaunchKernelGGL(k_fj_claim, dim3((unsigned)((c.lanes + FJ_BLOCK - 1) / FJ_BLOCK)), dim3(FJ_BLOCK), 0, st, c.in, c.in_count, c.lanes,
+                           ntree, lo, c.level, p.log2a, c.table, c.shift, c.out, c.out_count, static_cast<const uint4*>(levels), J);
+    });
 }
 
 hipError_t launch_forest_journal_swap(unsigned arity, void* leaves, const void* offsets, const uint64_t* ntree, const uint64_t* lo,

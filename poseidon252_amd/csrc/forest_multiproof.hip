@@ -25,6 +25,7 @@
 // records): no kernel here runs the permutation.  ceil_shift, level_start, u64_of and the tree lookup are forest_node.hpp's.
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "forest_multiproof.h"
 #include "forest_node.hpp"
 #include "forest_ragged.h"
@@ -70,24 +71,6 @@ __device__ __forceinline__ unsigned block_seg_scan(unsigned v, unsigned* total) 
     const unsigned ex = t > 0 ? part[t - 1] : 0u;
     __syncthreads();  // (part is reused by the caller's next call)
     return ex;
-}
-
-// exclusive scan of one value per thread over the block (returns the block total in *total)
-__device__ __forceinline__ u64 block_exclusive(u64 v, u64* total) {
-    __shared__ u64 part[FM_BLOCK];
-    const unsigned t = threadIdx.x;
-    part[t] = v;
-    __syncthreads();
-    for (unsigned off = 1; off < FM_BLOCK; off <<= 1) {
-        const u64 o = t >= off ? part[t - off] : 0ull;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    const u64 incl = part[t];
-    *total = part[FM_BLOCK - 1];
-    __syncthreads();
-    return incl - v;
 }
 
 }  // namespace
@@ -327,23 +310,14 @@ __global__ void __launch_bounds__(FM_BLOCK) k_fm_tree_sums(const u64* __restrict
     for (unsigned q = 0; q < FM_TREE_ITEMS; ++q)
         if (t0 + q < n_trees) sum += total[t0 + q];
     u64 all;
-    (void)block_exclusive(sum, &all);
+    (void)block_exclusive<FM_BLOCK>(sum, &all);
     if (threadIdx.x == 0) ttile[blockIdx.x] = all;
 }
 
-// one block: the tree tiles' sums -> their exclusive scan, in place.  FM_BLOCK tiles a trip of the loop, `carry` from trip to trip: the
-// second trip starts past FM_BLOCK * FM_TREE_TILE = 524,288 trees
+// one block: the tree tiles' sums -> their exclusive scan, in place (scan_tile_row of blockops.hpp: the second trip of its loop starts
+// past FM_BLOCK * FM_TREE_TILE = 524,288 trees)
 __global__ void __launch_bounds__(FM_BLOCK) k_fm_tree_scan(u64* __restrict__ ttile, size_t tiles) {
-    u64 carry = 0;
-#pragma unroll 1
-    for (size_t at = 0; at < tiles; at += FM_BLOCK) {
-        const size_t i = at + threadIdx.x;
-        const u64 v = i < tiles ? ttile[i] : 0ull;
-        u64 all;
-        const u64 ex = block_exclusive(v, &all);
-        if (i < tiles) ttile[i] = carry + ex;
-        carry += all;
-    }
+    scan_tile_row<FM_BLOCK>(ttile, tiles);
 }
 
 // ttile == nullptr: one tile
@@ -357,7 +331,7 @@ __global__ void __launch_bounds__(FM_BLOCK) k_fm_tree_offsets(const u64* __restr
         sum += v[q];
     }
     u64 all;
-    u64 run = (ttile ? ttile[blockIdx.x] : 0ull) + block_exclusive(sum, &all);
+    u64 run = (ttile ? ttile[blockIdx.x] : 0ull) + block_exclusive<FM_BLOCK>(sum, &all);
 #pragma unroll
     for (unsigned q = 0; q < FM_TREE_ITEMS; ++q) {
         const size_t t = t0 + q;

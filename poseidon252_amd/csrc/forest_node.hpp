@@ -36,6 +36,9 @@ __device__ __forceinline__ uint64_t level_start(uint64_t n, unsigned l, unsigned
     return w;
 }
 __device__ __forceinline__ uint64_t u64_of(unsigned lo, unsigned hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+// a record of the level lists (16 bytes: tree id, valid, node index low and high), as k_fu_claim writes it and k_fu_digest reads it
+// (forest_update.h); a void record is all zero
+__device__ __forceinline__ uint4 record(uint32_t t, uint64_t i) { return make_uint4(t, 1u, (unsigned)i, (unsigned)(i >> 32)); }
 
 // ---- a tree id of a (tree id, leaf id) pair against the forest's index (launch_forest_ragged_index): n_t, or 0 for an unknown
 // (t >= n_trees) or a bad tree.  *ts = t, or 0 for an unknown tree: safe for the per-tree arrays (n_trees >= 1: entry 0 exists) ----

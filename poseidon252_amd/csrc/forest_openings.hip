@@ -26,6 +26,7 @@
 // (openings.hip's) stay written out here: profiles/forest_kernels_refactor.txt has the reasons.
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "fastdiv.hpp"
 #include "forest_node.hpp"
 #include "forest_openings.h"
@@ -38,7 +39,7 @@ namespace {
 
 constexpr unsigned FO_BLOCK = 256;
 constexpr unsigned FO_ITEMS = 8;  // openings per thread of a sort block
-constexpr unsigned FO_TILE = FO_BLOCK * FO_ITEMS;
+constexpr unsigned FO_TILE = FO_BLOCK * FO_ITEMS;  // (the tile of bucket_hist / bucket_scatter, blockops.hpp)
 constexpr unsigned FO_BAD_BIN = FOREST_OPENINGS_BINS - 1;
 
 // a value select, not a pointer select (openings.hip: the pointer-select form parks the zero in scratch); word 0 of `base` exists
@@ -125,17 +126,7 @@ __device__ __forceinline__ unsigned depth_bin(const uint8_t* __restrict__ depths
 
 __global__ void __launch_bounds__(FO_BLOCK) k_fo_depth_hist(const uint8_t* __restrict__ depths, size_t k, unsigned stride,
                                                             unsigned long long* __restrict__ hist) {
-    __shared__ unsigned cnt[FOREST_OPENINGS_BINS];
-    if (threadIdx.x < FOREST_OPENINGS_BINS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t t0 = (size_t)blockIdx.x * FO_TILE + threadIdx.x;
-#pragma unroll
-    for (unsigned q = 0; q < FO_ITEMS; ++q) {
-        const size_t i = t0 + (size_t)q * FO_BLOCK;
-        if (i < k) atomicAdd(&cnt[depth_bin(depths, i, stride)], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < FOREST_OPENINGS_BINS && cnt[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+    bucket_hist<FO_BLOCK, FO_ITEMS, FOREST_OPENINGS_BINS>(k, hist, [=](size_t i) { return depth_bin(depths, i, stride); });
 }
 
 // counts -> the start of each bin in the sorted order: deepest first, the bad ones last; in place
@@ -153,27 +144,7 @@ __global__ void __launch_bounds__(64) k_fo_depth_scan(unsigned long long* __rest
 
 __global__ void __launch_bounds__(FO_BLOCK) k_fo_depth_scatter(const uint8_t* __restrict__ depths, size_t k, unsigned stride,
                                                                unsigned long long* __restrict__ cursor, uint64_t* __restrict__ order) {
-    __shared__ unsigned cnt[FOREST_OPENINGS_BINS];
-    __shared__ unsigned long long base[FOREST_OPENINGS_BINS];
-    if (threadIdx.x < FOREST_OPENINGS_BINS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t t0 = (size_t)blockIdx.x * FO_TILE + threadIdx.x;
-    unsigned bk[FO_ITEMS], rk[FO_ITEMS];
-#pragma unroll
-    for (unsigned q = 0; q < FO_ITEMS; ++q) {
-        const size_t i = t0 + (size_t)q * FO_BLOCK;
-        bk[q] = i < k ? depth_bin(depths, i, stride) : 0u;
-        rk[q] = i < k ? atomicAdd(&cnt[bk[q]], 1u) : 0u;
-    }
-    __syncthreads();
-    if (threadIdx.x < FOREST_OPENINGS_BINS && cnt[threadIdx.x])
-        base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
-    __syncthreads();
-#pragma unroll
-    for (unsigned q = 0; q < FO_ITEMS; ++q) {
-        const size_t i = t0 + (size_t)q * FO_BLOCK;
-        if (i < k) order[base[bk[q]] + rk[q]] = i;  // (the bins partition 0 .. k-1: every slot below k, written once)
-    }
+    bucket_scatter<FO_BLOCK, FO_ITEMS, FOREST_OPENINGS_BINS>(k, cursor, order, [=](size_t i) { return depth_bin(depths, i, stride); });
 }
 
 // ---- the re-hash, one lane per opening: lane j walks opening order[j] (order == null: opening j) for depths[] levels ----

@@ -30,6 +30,7 @@
 // kernels.h) — node_digest_coop of forest_node.hpp, which holds what the three forest files share.
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "forest_node.hpp"
 #include "forest_ragged.h"
 #include "hades29.hpp"
@@ -48,24 +49,6 @@ __device__ __forceinline__ uint64_t row_value(const uint64_t* __restrict__ ntree
     const uint64_t n = ntree[t];
     if (row == FR_ROW_LEAVES) return n;
     return row == 0 ? levels_len_dev(n, la) : level_nodes(n, row, la);
-}
-
-// exclusive scan of one value per thread over the block (returns the block total in *total)
-__device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* total) {
-    __shared__ uint64_t part[FR_BLOCK];
-    const unsigned t = threadIdx.x;
-    part[t] = v;
-    __syncthreads();
-    for (unsigned off = 1; off < FR_BLOCK; off <<= 1) {
-        const uint64_t o = t >= off ? part[t - off] : 0ull;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    const uint64_t incl = part[t];
-    *total = part[FR_BLOCK - 1];
-    __syncthreads();  // (part is reused by the caller's next call)
-    return incl - v;
 }
 
 }  // namespace
@@ -97,24 +80,14 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_tile_sums(const uint64_t* __res
     for (unsigned k = 0; k < FR_ITEMS; ++k)
         if (t0 + k < n_trees) sum += row_value(ntree, t0 + k, row, la);
     uint64_t total;
-    (void)block_exclusive(sum, &total);
+    (void)block_exclusive<FR_BLOCK>(sum, &total);
     if (threadIdx.x == 0) tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 
-// one block per row: the tile sums of the row -> their exclusive scan, in place.  FR_BLOCK tiles a trip of the loop, `carry` from trip
-// to trip: the second trip starts past FR_BLOCK * FR_TILE = 524,288 trees
+// one block per row: the tile sums of the row -> their exclusive scan, in place (scan_tile_row of blockops.hpp: the second trip of its
+// loop starts past FR_BLOCK * FR_TILE = 524,288 trees)
 __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_tiles(uint64_t* __restrict__ tsum, size_t tiles) {
-    uint64_t* row = tsum + (size_t)blockIdx.x * tiles;
-    uint64_t carry = 0;
-#pragma unroll 1
-    for (size_t base = 0; base < tiles; base += FR_BLOCK) {
-        const size_t i = base + threadIdx.x;
-        const uint64_t v = i < tiles ? row[i] : 0ull;
-        uint64_t total;
-        const uint64_t ex = block_exclusive(v, &total);
-        if (i < tiles) row[i] = carry + ex;
-        carry += total;
-    }
+    scan_tile_row<FR_BLOCK>(tsum + (size_t)blockIdx.x * tiles, tiles);
 }
 
 // FIRST (the leaf-count row): the sum rule above, then the roots of bad trees (zero).  Otherwise: C[row][t] for every
@@ -134,7 +107,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_apply(uint64_t* __restrict
         sum += v[k];
     }
     uint64_t total;
-    uint64_t run = tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive(sum, &total);
+    uint64_t run = tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive<FR_BLOCK>(sum, &total);
 #pragma unroll
     for (unsigned k = 0; k < FR_ITEMS; ++k) {
         const size_t t = t0 + k;
@@ -171,15 +144,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_block_first(const uint64_t* __r
     if (b >= fr.len[l]) return;
     const uint64_t* Crow = C + (size_t)l * (n_trees + 1);
     const uint64_t g = (uint64_t)b * 256;
-    size_t lo = 0, hi = n_trees - 1;  // C[0] = 0 <= g
-    while (lo < hi) {
-        const size_t mid = (lo + hi + 1) >> 1;
-        if (Crow[mid] <= g)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    first[fr.off[l] + b] = lo;
+    first[fr.off[l] + b] = last_at_or_below(Crow, 0, n_trees - 1, g);  // (C[0] = 0 <= g)
 }
 
 // ---- the digests of one level ----
@@ -209,15 +174,7 @@ struct FrNode {
 __device__ __forceinline__ bool fr_node(const FrLevel& P, uint64_t g, FrNode& nd) {
     const uint64_t* __restrict__ C = P.C;
     if (g >= C[P.n_trees]) return false;
-    size_t lo = P.first[g >> 8], hi = P.first[(g >> 8) + 1];
-    while (lo < hi) {
-        const size_t mid = (lo + hi + 1) >> 1;
-        if (C[mid] <= g)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    const size_t t = lo;
+    const size_t t = last_at_or_below(C, P.first[g >> 8], P.first[(g >> 8) + 1], g);
     const uint64_t n = P.ntree[t];
     const unsigned l = P.level;
     nd.i = g - C[t];

@@ -22,6 +22,9 @@ struct ForestUpdatePlan {
     size_t slots[FOREST_RAGGED_MAX_DEPTH + 1] = {};  // claim-table slots of level l: a power of two >= 2 in[l - 1]
     size_t list_bytes = 0, count_bytes = 0, table_bytes = 0;
     size_t ids_bytes() const { return 2 * list_bytes + count_bytes; }  // beside the forest's index, in one buffer
+    // inside that buffer: the counters, then the two lists (level l's records are list l & 1)
+    unsigned long long* counts(void* ids) const { return static_cast<unsigned long long*>(ids); }
+    uint4* list(void* ids, unsigned l) const { return reinterpret_cast<uint4*>(static_cast<char*>(ids) + count_bytes + (l & 1) * list_bytes); }
 };
 ForestUpdatePlan forest_update_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, size_t k);
 
@@ -44,6 +47,58 @@ struct ForestDigestList {
 };
 hipError_t launch_forest_digest_list(const int32_t* tab, const TagArg& tag, unsigned arity, unsigned log2a, const ForestDigestList& list,
                                      hipStream_t st);
+
+// a claim table of `slots` slots (a power of two): the shift that takes a key's 64-bit hash to its slot
+inline unsigned shift_of(size_t slots) {
+    unsigned shift = 64;
+    for (size_t s = slots; s > 1; s >>= 1) --shift;
+    return shift;
+}
+
+// what level l's claim kernel is launched with: list l - 1 (in_count null for l == 1: all `lanes` records) -> list l
+struct ForestClaimLevel {
+    unsigned level = 1, shift = 64;
+    const uint4* in = nullptr;
+    const unsigned long long* in_count = nullptr;
+    size_t lanes = 0;
+    unsigned long long* table = nullptr;
+    uint4* out = nullptr;
+    unsigned long long* out_count = nullptr;
+};
+
+// Levels 1 .. plan.depth of an update whose list 0 is written (plan.list(ids, 0)): per level the claim table is cleared to 0xFF bytes,
+// enqueue_claim(ForestClaimLevel) launches the caller's claim kernel, and the level's digests follow.  `d` carries the forest (ntree,
+// lo, offsets, leaves, levels, roots, n_hashed); the list, count, bound and level are filled here.
+template <class EnqueueClaim>
+hipError_t launch_forest_update_levels(const int32_t* tab, const TagArg& tag, const ForestUpdatePlan& p, ForestDigestList d, void* ids,
+                                       void* table, hipStream_t st, EnqueueClaim enqueue_claim) {
+    unsigned long long* count = p.counts(ids);
+    hipError_t e = hipMemsetAsync(count, 0, p.count_bytes, st);
+    if (e != hipSuccess) return e;
+    for (unsigned l = 1; l <= p.depth; ++l) {
+        e = hipMemsetAsync(table, 0xFF, p.slots[l] * sizeof(unsigned long long), st);
+        if (e != hipSuccess) return e;
+        ForestClaimLevel c;
+        c.level = l;
+        c.shift = shift_of(p.slots[l]);
+        c.in = p.list(ids, l - 1);
+        c.in_count = l == 1 ? nullptr : count + (l - 1);
+        c.lanes = p.in[l - 1];
+        c.table = static_cast<unsigned long long*>(table);
+        c.out = p.list(ids, l);
+        c.out_count = count + l;
+        enqueue_claim(c);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        d.list = c.out;
+        d.count = c.out_count;
+        d.bound = p.in[l];
+        d.level = l;
+        e = launch_forest_digest_list(tab, tag, p.arity, p.log2a, d, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 // The whole update on `st`: ntree / lo = the forest's index (launch_forest_ragged_index); ids = plan.ids_bytes() and table =
 // plan.table_bytes of scratch.  roots, n_bad (uint32), n_hashed (uint64) may be null; levels may be null when plan.depth == 0.

@@ -20,6 +20,7 @@
 // coop8 rule of kernels.h on min(k, bound[l])).  The closed forms, u64_of and the tree lookup are forest_node.hpp's too.
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "forest_node.hpp"
 #include "forest_update.h"
 #include "hades29.hpp"
@@ -30,10 +31,6 @@ namespace p252 {
 namespace {
 
 constexpr unsigned FU_BLOCK = 256;
-constexpr unsigned long long FU_EMPTY = ~0ull;  // (the table is cleared to 0xFF bytes; no slot of d_levels has this number)
-constexpr size_t FU_MIN_SLOTS = 64;
-
-__device__ __forceinline__ uint4 record(uint32_t t, uint64_t i) { return make_uint4(t, 1u, (unsigned)i, (unsigned)(i >> 32)); }
 
 }  // namespace
 
@@ -77,26 +74,11 @@ __global__ void __launch_bounds__(FU_BLOCK) k_fu_claim(const uint4* __restrict__
     const uint64_t n = live ? ntree[t] : 0ull;
     live = live && ceil_shift(n, (l - 1) * la) > 1;  // level l - 1 has more than one node: the tree has a level l
     const uint64_t parent = u64_of(r.z, r.w) >> la;
-    bool won = false;
-    if (live) {
-        const unsigned long long key = LO[t] + level_start(n, l, la) + parent;
-        const size_t mask = ((size_t)1 << (64 - shift)) - 1;
-        size_t h = (size_t)((key * 0x9E3779B97F4A7C15ull) >> shift);
-        for (;;) {  // (the table is at most half full: an empty slot is met)
-            const unsigned long long seen = atomicCAS(table + h, FU_EMPTY, key);
-            if (seen == FU_EMPTY) won = true;
-            if (seen == FU_EMPTY || seen == key) break;
-            h = (h + 1) & mask;
-        }
-    }
+    const bool won = live && claim(table, shift, LO[t] + level_start(n, l, la) + parent);
     const unsigned long long winners = __ballot(won);
     if (winners == 0) return;
-    const unsigned lane = threadIdx.x & 63u;
-    const int leader = __ffsll((long long)winners) - 1;
-    unsigned long long base = 0;
-    if ((int)lane == leader) base = atomicAdd(out_count, (unsigned long long)__popcll(winners));
-    base = __shfl(base, leader);
-    if (won) out[base + __popcll(winners & ((1ull << lane) - 1))] = record(t, parent);
+    const unsigned long long place = append_place(won, winners, out_count);
+    if (won) out[place] = record(t, parent);
 }
 
 // ---- the digests of one level ----
@@ -190,7 +172,7 @@ ForestUpdatePlan forest_update_plan(unsigned arity, size_t n_leaves, size_t n_tr
     size_t widest = 0;
     for (unsigned l = 1; l <= p.depth; ++l) {
         p.in[l] = k < fr.bound[l] ? k : fr.bound[l];
-        size_t slots = FU_MIN_SLOTS;
+        size_t slots = CLAIM_MIN_SLOTS;
         while (slots < 2 * p.in[l - 1]) slots <<= 1;
         p.slots[l] = slots;
         if (slots > widest) widest = slots;
@@ -228,45 +210,24 @@ hipError_t launch_forest_update(const int32_t* tab, const TagArg& tag, const For
                                 const uint64_t* ntree, const uint64_t* lo, void* levels, const void* tree_ids, const void* leaf_ids,
                                 const void* new_leaves, void* roots, void* n_bad, void* n_hashed, void* ids, void* table, hipStream_t st) {
     if (p.k == 0) return hipSuccess;
-    char* base = static_cast<char*>(ids);
-    unsigned long long* count = reinterpret_cast<unsigned long long*>(base);
-    uint4* list[2] = {reinterpret_cast<uint4*>(base + p.count_bytes), reinterpret_cast<uint4*>(base + p.count_bytes + p.list_bytes)};
-    unsigned long long* tb = static_cast<unsigned long long*>(table);
     const uint64_t* off = static_cast<const uint64_t*>(offsets);
     hipLaunchKernelGGL(k_fu_scatter, dim3((unsigned)((p.k + FU_BLOCK - 1) / FU_BLOCK)), dim3(FU_BLOCK), 0, st, off, ntree, p.n_trees,
                        static_cast<const uint32_t*>(tree_ids), static_cast<const uint64_t*>(leaf_ids), static_cast<const uint4*>(new_leaves),
-                       p.k, static_cast<uint4*>(leaves), static_cast<uint4*>(roots), list[0], static_cast<unsigned*>(n_bad));
-    hipError_t e = hipGetLastError();
+                       p.k, static_cast<uint4*>(leaves), static_cast<uint4*>(roots), p.list(ids, 0), static_cast<unsigned*>(n_bad));
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.depth == 0) return e;
-    e = hipMemsetAsync(count, 0, p.count_bytes, st);
-    if (e != hipSuccess) return e;
-    for (unsigned l = 1; l <= p.depth; ++l) {
-        e = hipMemsetAsync(tb, 0xFF, p.slots[l] * sizeof(unsigned long long), st);
-        if (e != hipSuccess) return e;
-        unsigned shift = 64;
-        for (size_t s = p.slots[l]; s > 1; s >>= 1) --shift;
-        const size_t lanes = p.in[l - 1];
-        hipLaunchKernelGGL(k_fu_claim, dim3((unsigned)((lanes + FU_BLOCK - 1) / FU_BLOCK)), dim3(FU_BLOCK), 0, st, list[(l - 1) & 1],
-                           l == 1 ? (const unsigned long long*)nullptr : count + (l - 1), lanes, ntree, lo, l, p.log2a, tb, shift,
-                           list[l & 1], count + l);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ForestDigestList d;
-        d.list = list[l & 1];
-        d.count = count + l;
-        d.bound = p.in[l];
-        d.ntree = ntree;
-        d.lo = lo;
-        d.offsets = offsets;
-        d.leaves = leaves;
-        d.levels = levels;
-        d.roots = roots;
-        d.n_hashed = n_hashed;
-        d.level = l;
-        e = launch_forest_digest_list(tab, tag, p.arity, p.log2a, d, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    ForestDigestList d;
+    d.ntree = ntree;
+    d.lo = lo;
+    d.offsets = offsets;
+    d.leaves = leaves;
+    d.levels = levels;
+    d.roots = roots;
+    d.n_hashed = n_hashed;
+    return launch_forest_update_levels(tab, tag, p, d, ids, table, st, [&](const ForestClaimLevel& c) {
+        hipLaunchKernelGGL(k_fu_claim, dim3((unsigned)((c.lanes + FU_BLOCK - 1) / FU_BLOCK)), dim3(FU_BLOCK), 0, st, c.in, c.in_count, c.lanes,
+                           ntree, lo, c.level, p.log2a, c.table, c.shift, c.out, c.out_count);
+    });
 }
 
 }  // namespace p252

@@ -28,6 +28,7 @@
 // read per record (MpDigest::w_node) instead of once per launch (w_below; w_node == null: this file's own calls).
 #include <hip/hip_runtime.h>
 
+#include "blockops.hpp"
 #include "forest_node.hpp"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -45,25 +46,6 @@ constexpr size_t MP_COUNT_BYTES = 512;
 constexpr unsigned MP_MASK_SHIFT = 28;  // a record's last word: proof offset bits 32 .. 59, slot mask above
 
 typedef unsigned long long u64;
-
-// exclusive scan of one value per thread over the block (returns the block total in *total)
-template <class T>
-__device__ __forceinline__ T block_exclusive(T v, T* total) {
-    __shared__ T part[MP_BLOCK];
-    const unsigned t = threadIdx.x;
-    part[t] = v;
-    __syncthreads();
-    for (unsigned off = 1; off < MP_BLOCK; off <<= 1) {
-        const T o = t >= off ? part[t - off] : (T)0;
-        __syncthreads();
-        part[t] += o;
-        __syncthreads();
-    }
-    const T incl = part[t];
-    *total = part[MP_BLOCK - 1];
-    __syncthreads();  // (part is reused by the caller's next call)
-    return incl - v;
-}
 
 }  // namespace
 
@@ -125,7 +107,7 @@ __global__ void __launch_bounds__(MP_BLOCK) k_mp_tile_sums(MpLevel L, const u64*
     unsigned mask;
     const unsigned v = e < L.lanes ? mp_element<ARITY>(L, e, ctr[l], &p, &mask) : 0u;
     unsigned total;
-    (void)block_exclusive(v, &total);
+    (void)block_exclusive<MP_BLOCK>(v, &total);
     if (threadIdx.x == 0) tsum[blockIdx.x] = total;
 }
 
@@ -140,8 +122,8 @@ __global__ void __launch_bounds__(MP_BLOCK) k_mp_scan_tiles(const uint32_t* __re
         const size_t i = at + threadIdx.x;
         const uint32_t v = i < tiles ? tsum[i] : 0u;
         u64 th, tm;
-        const u64 eh = block_exclusive<u64>(v >> 16, &th);
-        const u64 em = block_exclusive<u64>(v & 0xffffu, &tm);
+        const u64 eh = block_exclusive<MP_BLOCK, u64>(v >> 16, &th);
+        const u64 em = block_exclusive<MP_BLOCK, u64>(v & 0xffffu, &tm);
         if (i < tiles) {
             toff[2 * i] = heads + eh;
             toff[2 * i + 1] = base + em;
@@ -167,7 +149,7 @@ __global__ void __launch_bounds__(MP_BLOCK) k_mp_apply(MpLevel L, u64* __restric
     unsigned mask = 0;
     const unsigned v = e < L.lanes ? mp_element<ARITY>(L, e, ctr[l], &p, &mask) : 0u;
     unsigned total;
-    const unsigned ex = block_exclusive(v, &total);
+    const unsigned ex = block_exclusive<MP_BLOCK>(v, &total);
     u64 heads = 0, base;
     if (toff) {
         heads = toff[2 * (size_t)blockIdx.x];

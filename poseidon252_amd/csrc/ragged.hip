@@ -22,6 +22,7 @@
 
 #include <cstdlib>
 
+#include "blockops.hpp"
 #include "coop29.hpp"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -33,7 +34,7 @@ namespace {
 
 constexpr unsigned SORT_BLOCK = 256;
 constexpr unsigned SORT_ITEMS = 8;  // messages per thread of a sort block
-constexpr unsigned SORT_TILE = SORT_BLOCK * SORT_ITEMS;
+constexpr unsigned SORT_TILE = SORT_BLOCK * SORT_ITEMS;  // (the tile of bucket_hist / bucket_scatter, blockops.hpp)
 
 // absorb blocks of a message of L scalars (no overflow for any L)
 __device__ __forceinline__ uint64_t blocks_of(uint64_t L) { return (L >> 2) + ((L & 3u) != 0); }
@@ -54,18 +55,7 @@ __device__ __forceinline__ unsigned bucket_of(const uint64_t* __restrict__ offse
 // ---- the sort ----
 __global__ void __launch_bounds__(SORT_BLOCK) k_ragged_hist(const uint64_t* __restrict__ offsets, size_t n, uint64_t max_len,
                                                             unsigned long long* __restrict__ hist) {
-    __shared__ unsigned cnt[RAGGED_BUCKETS];
-    for (unsigned b = threadIdx.x; b < RAGGED_BUCKETS; b += SORT_BLOCK) cnt[b] = 0;
-    __syncthreads();
-    const size_t t0 = (size_t)blockIdx.x * SORT_TILE + threadIdx.x;
-#pragma unroll
-    for (unsigned k = 0; k < SORT_ITEMS; ++k) {
-        const size_t i = t0 + (size_t)k * SORT_BLOCK;
-        if (i < n) atomicAdd(&cnt[bucket_of(offsets, i, max_len)], 1u);
-    }
-    __syncthreads();
-    for (unsigned b = threadIdx.x; b < RAGGED_BUCKETS; b += SORT_BLOCK)
-        if (cnt[b]) atomicAdd(&hist[b], (unsigned long long)cnt[b]);
+    bucket_hist<SORT_BLOCK, SORT_ITEMS, RAGGED_BUCKETS>(n, hist, [=](size_t i) { return bucket_of(offsets, i, max_len); });
 }
 
 // counts -> start of each bucket in the sorted order, buckets in DESCENDING order (longest messages first), in place
@@ -99,27 +89,7 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_ragged_scan(unsigned long long* 
 
 __global__ void __launch_bounds__(SORT_BLOCK) k_ragged_scatter(const uint64_t* __restrict__ offsets, size_t n, uint64_t max_len,
                                                                unsigned long long* __restrict__ cursor, uint64_t* __restrict__ order) {
-    __shared__ unsigned cnt[RAGGED_BUCKETS];
-    __shared__ unsigned long long base[RAGGED_BUCKETS];
-    for (unsigned b = threadIdx.x; b < RAGGED_BUCKETS; b += SORT_BLOCK) cnt[b] = 0;
-    __syncthreads();
-    const size_t t0 = (size_t)blockIdx.x * SORT_TILE + threadIdx.x;
-    unsigned bk[SORT_ITEMS], rk[SORT_ITEMS];
-#pragma unroll
-    for (unsigned k = 0; k < SORT_ITEMS; ++k) {
-        const size_t i = t0 + (size_t)k * SORT_BLOCK;
-        bk[k] = i < n ? bucket_of(offsets, i, max_len) : 0u;
-        rk[k] = i < n ? atomicAdd(&cnt[bk[k]], 1u) : 0u;
-    }
-    __syncthreads();
-    for (unsigned b = threadIdx.x; b < RAGGED_BUCKETS; b += SORT_BLOCK)
-        if (cnt[b]) base[b] = atomicAdd(&cursor[b], (unsigned long long)cnt[b]);
-    __syncthreads();
-#pragma unroll
-    for (unsigned k = 0; k < SORT_ITEMS; ++k) {
-        const size_t i = t0 + (size_t)k * SORT_BLOCK;
-        if (i < n) order[base[bk[k]] + rk[k]] = i;
-    }
+    bucket_scatter<SORT_BLOCK, SORT_ITEMS, RAGGED_BUCKETS>(n, cursor, order, [=](size_t i) { return bucket_of(offsets, i, max_len); });
 }
 
 // ---- the sponge, one lane per message: lane i hashes message order[i] (order == null: message i) ----

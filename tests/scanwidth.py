@@ -3,7 +3,8 @@ tests/test_scan_width_cpu.py (the shapes' conditions, on the numpy models alone)
 A plain helper module, imported as forestwalk and edgecases are; no torch at module level.
 
 Five kernels scan tile sums in a loop of one block per trip with a carry from trip to trip (k_fr_scan_tiles, k_fa_scan_tiles,
-k_mp_scan_tiles, k_fm_scan_tiles, k_fm_tree_scan).  The tile and block constants are read out of the csrc text, the shapes are derived
+k_mp_scan_tiles, k_fm_scan_tiles, k_fm_tree_scan; the three over trees through one routine, scan_tile_row of csrc/blockops.hpp, with
+each kernel's own block constant).  The tile and block constants are read out of the csrc text, the shapes are derived
 from them, and the CPU test asserts on the models' counts that every shape makes the trips it is here for: a changed constant moves
 the shapes or fails that test.
 

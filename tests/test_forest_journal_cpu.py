@@ -147,8 +147,12 @@ def test_own_translation_unit_and_nothing_is_copied():
     src = open(os.path.join(CSRC, "forest_journal.hip")).read()
     code = re.sub(r"//[^\n]*", "", src)
     assert '#include "forest_node.hpp"' in src and '#include "forest_update.h"' in src
-    # the digests are the update's, the address arithmetic forest_node.hpp's: used here, defined there
-    assert "launch_forest_digest_list(" in code and "hades_permute" not in code and "node_digest_coop" not in code
+    # the digests are the update's — reached through its level loop (forest_update.h), which is handed k_fj_claim's launch — and the address
+    # arithmetic forest_node.hpp's: used here, defined there
+    levels = re.search(r"\blaunch_forest_update_levels\s*\([^;{]*\)\s*\{.*?\n\}", open(os.path.join(CSRC, "forest_update.h")).read(), flags=re.S)
+    assert levels and "launch_forest_digest_list(" in levels.group(0) and "enqueue_claim(" in levels.group(0)
+    assert "launch_forest_update_levels(" in code and not re.search(r"hipError_t\s+launch_forest_update_levels\b", code)
+    assert "hades_permute" not in code and "node_digest_coop" not in code
     for fn in ("level_start", "ceil_shift", "u64_of", "forest_tree_leaves", "level_nodes"):
         assert re.search(r"\b%s\(" % fn, code), fn
         assert not re.search(r"\b%s\s*\([^;{]*\)\s*\{" % fn, code), fn
