@@ -7,137 +7,11 @@
 // check of the library.  One line per case:   symbol <TAB> case <TAB> rc <TAB> p252_last_error
 // (tests/test_api_refusals_cpu.py compares the lines with tests/golden/api_refusals.txt).  No pointer is dereferenced: no case
 // reaches a device.
-#include <cstdint>
-#include <cstdio>
-#include <functional>
-#include <string>
-#include <vector>
+#include "refusal_table.hpp"
 
-#include "../../poseidon252_amd/csrc/ctx.hpp"
+using namespace refusal;
 
 namespace {
-
-alignas(64) unsigned char g_buf[64 * 32];
-uint64_t g_tag[4] = {1, 2, 3, 4};
-
-enum Kind {
-    CTX,   // the context
-    HOST,  // a host pointer the library reads at once (tag, arrays of the multi calls): NULL only
-    P16,   // device scalar array: NULL, +8
-    P8,    // device uint64 array: NULL, +4
-    P4,    // device uint32 array: NULL, +2
-    P1,    // device byte array: NULL
-    CNT,   // size_t count: 0, the common edges, its own edges
-    INT,   // int / unsigned selector: its own edges only
-};
-
-struct Arg {
-    const char* name;
-    Kind kind;
-    uint64_t good;                // CNT / INT: the good value; pointers: filled in (a slot of g_buf)
-    std::vector<uint64_t> edges;  // further values of this argument
-};
-
-struct Combo {  // several arguments at once: overflow products, "NULL is fine when the count is 0"
-    const char* name;
-    std::vector<std::pair<const char*, uint64_t>> set;
-};
-
-using V = const uint64_t*;
-struct Entry {
-    const char* sym;
-    std::vector<Arg> args;
-    std::function<int(V)> call;
-    std::vector<Combo> combos;
-    bool ctx_array = false;  // slot 0 is an array of contexts (the multi calls): the message is the one context's
-};
-
-p252_ctx* g_ctx = nullptr;
-
-p252_ctx* C(uint64_t v) { return reinterpret_cast<p252_ctx*>(v); }
-void* P(uint64_t v) { return reinterpret_cast<void*>(v); }
-const uint64_t* T(uint64_t v) { return reinterpret_cast<const uint64_t*>(v); }
-
-const uint64_t MAXZ = SIZE_MAX;
-const std::vector<uint64_t> COMMON = {MAXZ, 1ull << 32, (1ull << 32) - 1, 0x80000000ull, 0x7fffffffull};
-
-std::string hex(uint64_t v) {
-    char b[32];
-    std::snprintf(b, sizeof b, v < 10 ? "%llu" : "0x%llx", (unsigned long long)v);
-    return b;
-}
-
-void row(const Entry& e, const std::string& what, const std::vector<uint64_t>& v) {
-    g_ctx->err.clear();
-    const int rc = e.call(v.data());
-    std::string msg = p252_last_error(e.ctx_array ? g_ctx : C(v[0]));
-    for (char& c : msg)
-        if (c == '\t' || c == '\n') c = ' ';
-    std::printf("%s\t%s\t%d\t%s\n", e.sym, what.c_str(), rc, msg.c_str());
-}
-
-void run(Entry& e) {
-    std::vector<uint64_t> good;
-    for (size_t i = 0; i < e.args.size(); ++i) {
-        Arg& a = e.args[i];
-        if (a.kind == CTX) a.good = reinterpret_cast<uint64_t>(g_ctx);
-        if (a.kind == HOST && !a.good) a.good = reinterpret_cast<uint64_t>(g_tag);
-        if (a.kind == P16 || a.kind == P8 || a.kind == P4 || a.kind == P1) a.good = reinterpret_cast<uint64_t>(g_buf + 64 * (i + 1));
-        good.push_back(a.good);
-    }
-    row(e, "control", good);
-    for (size_t i = 0; i < e.args.size(); ++i) {
-        const Arg& a = e.args[i];
-        auto vary = [&](const std::string& what, uint64_t val) {
-            std::vector<uint64_t> v = good;
-            v[i] = val;
-            row(e, std::string(a.name) + what, v);
-        };
-        if (a.kind != CNT && a.kind != INT) vary("=NULL", 0);
-        if (a.kind == P16) vary("+8", a.good + 8);
-        if (a.kind == P8) vary("+4", a.good + 4);
-        if (a.kind == P4) vary("+2", a.good + 2);
-        if (a.kind == CNT) {
-            vary("=0", 0);
-            for (uint64_t x : COMMON) vary("=" + hex(x), x);
-        }
-        for (uint64_t x : a.edges) vary("=" + hex(x), x);
-    }
-    for (const Combo& c : e.combos) {
-        std::vector<uint64_t> v = good;
-        for (const auto& s : c.set) {
-            size_t i = 0;
-            while (i < e.args.size() && std::string(e.args[i].name) != s.first) ++i;
-            if (i == e.args.size()) {
-                std::fprintf(stderr, "%s: combo %s names no argument %s\n", e.sym, c.name, s.first);
-                std::exit(2);
-            }
-            v[i] = s.second;
-        }
-        row(e, c.name, v);
-    }
-}
-
-const Arg CTXA = {"ctx", CTX, 0, {}}, TAGA = {"tag", HOST, 0, {}};
-Arg cnt(const char* name, uint64_t good, std::vector<uint64_t> edges = {}) { return {name, CNT, good, edges}; }
-Arg p16(const char* name) { return {name, P16, 0, {}}; }
-Arg p8(const char* name) { return {name, P8, 0, {}}; }
-Arg p4(const char* name) { return {name, P4, 0, {}}; }
-Arg p1(const char* name) { return {name, P1, 0, {}}; }
-
-// limits of the library's size checks (api.cpp): forest_shape_check, the `k > SIZE_MAX / 128 / depth` family, the ragged depths
-const uint64_t FOREST_MAX_DEPTH = 64;  // FOREST_RAGGED_MAX_DEPTH = FOREST_OPENINGS_MAX_DEPTH
-const uint64_t TREES_MAX = MAXZ / 8 / (FOREST_MAX_DEPTH + 2);
-
-std::vector<Combo> forest_shape_combos() {
-    return {{"n_leaves=SIZE_MAX/64", {{"n_leaves", MAXZ / 64}}},
-            {"n_leaves=SIZE_MAX/64+1", {{"n_leaves", MAXZ / 64 + 1}}},
-            {"n_trees=SIZE_MAX/8/66", {{"n_trees", TREES_MAX}}},
-            {"n_trees=SIZE_MAX/8/66+1", {{"n_trees", TREES_MAX + 1}}},
-            {"n_trees*min(max_leaves,n_leaves)=SIZE_MAX/2", {{"n_leaves", 1ull << 40}, {"max_leaves", 1ull << 41}, {"n_trees", (MAXZ / 2) >> 40}}},
-            {"n_trees*min(max_leaves,n_leaves)>SIZE_MAX/2", {{"n_leaves", 1ull << 40}, {"max_leaves", 1ull << 41}, {"n_trees", ((MAXZ / 2) >> 40) + 1}}},
-            {"n_trees*max_leaves>SIZE_MAX/2,max_leaves<n_leaves", {{"n_leaves", 1ull << 50}, {"max_leaves", 1ull << 40}, {"n_trees", ((MAXZ / 2) >> 40) + 1}}}};
-}
 
 std::vector<Entry> entries() {
     std::vector<Entry> es;

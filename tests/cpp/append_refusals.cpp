@@ -4,17 +4,11 @@
 // them with or without a GPU.  The control row must get past validation and fail at hipSetDevice(ctx->device) with P252_ERR_HIP;
 // every other row varies the control one way.  The buffers are addresses 1 MiB apart that nothing dereferences: no row reaches a
 // device.  (tests/test_forest_append_cpu.py compares the lines with tests/golden/append_refusals.txt.)
-#include <cstdint>
-#include <cstdio>
-#include <functional>
-#include <string>
-#include <vector>
+#include "refusal_table.hpp"
 
-#include "../../poseidon252_amd/csrc/ctx.hpp"
+using namespace refusal;
 
 namespace {
-
-uint64_t g_tag[4] = {1, 2, 3, 4};
 
 struct Args {
     p252_ctx* ctx;
@@ -23,9 +17,6 @@ struct Args {
         leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots, d_n_bad, d_n_hashed;
 };
 
-void* P(uint64_t v) { return reinterpret_cast<void*>(v); }
-uint64_t slot(unsigned i) { return 0x100000000ull + 0x100000ull * i; }
-
 int call(unsigned arity, const Args& a) {
     return (arity == 4 ? p252_merkle4_forest_ragged_append_device_into : p252_merkle2_forest_ragged_append_device_into)(
         a.ctx, a.tag, P(a.d_leaves), a.n_leaves, P(a.d_offsets), a.n_trees, a.max_leaves, P(a.d_levels), P(a.d_add), a.n_add, P(a.d_add_offsets),
@@ -33,16 +24,13 @@ int call(unsigned arity, const Args& a) {
         P(a.d_n_bad), P(a.d_n_hashed), nullptr);
 }
 
-struct Case {
-    std::string name;
-    std::function<void(Args&)> vary;
-};
+using Case = CaseOf<Args>;
+using Buf = BufOf<Args>;
 
 }  // namespace
 
 int main() {
     p252_ctx* ctx = new p252_ctx();  // device = -1: never bound
-    const uint64_t MAXZ = SIZE_MAX;
     for (unsigned arity : {4u, 2u}) {
         const char* sym = arity == 4 ? "p252_merkle4_forest_ragged_append_device_into" : "p252_merkle2_forest_ragged_append_device_into";
         // 3 old trees of at most 5 of 12 leaves; 4 new trees of at most 9 of 12 + 6 leaves
@@ -73,29 +61,21 @@ int main() {
             {"max_leaves=max_leaves_new=1,d_levels=d_levels_new=NULL", [](Args& a) { a.max_leaves = a.max_leaves_new = 1, a.d_levels = a.d_levels_new = 0; }},
             {"max_leaves=1,max_leaves_new=2,d_levels=d_levels_new=NULL", [](Args& a) { a.max_leaves = 1, a.max_leaves_new = 2, a.d_levels = a.d_levels_new = 0; }},
             // overflow
-            {"n_leaves=SIZE_MAX/64+1", [MAXZ](Args& a) { a.n_leaves = MAXZ / 64 + 1; }},
-            {"n_add=SIZE_MAX/64+1", [MAXZ](Args& a) { a.n_add = MAXZ / 64 + 1; }},
-            {"n_add=SIZE_MAX", [MAXZ](Args& a) { a.n_add = MAXZ; }},
-            {"leaves_cap=SIZE_MAX/64+1", [MAXZ](Args& a) { a.leaves_cap = MAXZ / 64 + 1; }},
-            {"levels_cap=SIZE_MAX/64+1", [MAXZ](Args& a) { a.levels_cap = MAXZ / 64 + 1; }},
-            {"n_trees_new=SIZE_MAX/8/66+1", [MAXZ](Args& a) { a.n_trees_new = MAXZ / 8 / 66 + 1; }},
+            {"n_leaves=SIZE_MAX/64+1", [](Args& a) { a.n_leaves = MAXZ / 64 + 1; }},
+            {"n_add=SIZE_MAX/64+1", [](Args& a) { a.n_add = MAXZ / 64 + 1; }},
+            {"n_add=SIZE_MAX", [](Args& a) { a.n_add = MAXZ; }},
+            {"leaves_cap=SIZE_MAX/64+1", [](Args& a) { a.leaves_cap = MAXZ / 64 + 1; }},
+            {"levels_cap=SIZE_MAX/64+1", [](Args& a) { a.levels_cap = MAXZ / 64 + 1; }},
+            {"n_trees_new=SIZE_MAX/8/66+1", [](Args& a) { a.n_trees_new = MAXZ / 8 / 66 + 1; }},
             {"n_trees_new*min(max_leaves_new,n_leaves+n_add)>SIZE_MAX/2",
-             [MAXZ](Args& a) { a.n_add = 1ull << 40, a.max_leaves_new = 1ull << 41, a.n_trees_new = ((MAXZ / 2) >> 40) + 1; }},
+             [](Args& a) { a.n_add = 1ull << 40, a.max_leaves_new = 1ull << 41, a.n_trees_new = ((MAXZ / 2) >> 40) + 1; }},
         };
         // every buffer NULL, and off its alignment
-        struct Buf {
-            const char* name;
-            uint64_t Args::*at;
-            unsigned align;
-        };
         const Buf bufs[] = {{"d_leaves", &Args::d_leaves, 16},      {"d_offsets", &Args::d_offsets, 8},         {"d_levels", &Args::d_levels, 16},
                             {"d_add", &Args::d_add, 16},            {"d_add_offsets", &Args::d_add_offsets, 8}, {"d_leaves_new", &Args::d_leaves_new, 16},
                             {"d_offsets_new", &Args::d_offsets_new, 8}, {"d_levels_new", &Args::d_levels_new, 16},  {"d_roots", &Args::d_roots, 16},
                             {"d_n_bad", &Args::d_n_bad, 4},         {"d_n_hashed", &Args::d_n_hashed, 8}};
-        for (const Buf& b : bufs) {
-            cases.push_back({std::string(b.name) + "=NULL", [b](Args& a) { a.*(b.at) = 0; }});
-            cases.push_back({std::string(b.name) + "+" + std::to_string(b.align / 2), [b](Args& a) { a.*(b.at) += b.align / 2; }});
-        }
+        null_and_misaligned(cases, bufs);
         // every output range against every input range: the output starts inside the input's last 16 bytes, and just behind the input
         const struct {
             const char* name;
@@ -118,16 +98,7 @@ int main() {
         cases.push_back({"d_leaves_new=d_leaves-leaves_cap*32+16", [](Args& a) { a.d_leaves_new = a.d_leaves - 18 * 32 + 16; }});
         cases.push_back({"d_leaves_new=d_leaves-leaves_cap*32", [](Args& a) { a.d_leaves_new = a.d_leaves - 18 * 32; }});
         cases.push_back({"n_add=0,d_leaves_new=d_add", [](Args& a) { a.n_add = 0, a.d_leaves_new = a.d_add; }});  // (no byte of d_add is read)
-        for (const Case& c : cases) {
-            Args a = good;
-            c.vary(a);
-            ctx->err.clear();
-            const int rc = call(arity, a);
-            std::string msg = p252_last_error(a.ctx);
-            for (char& ch : msg)
-                if (ch == '\t' || ch == '\n') ch = ' ';
-            std::printf("%s\t%s\t%d\t%s\n", sym, c.name.c_str(), rc, msg.c_str());
-        }
+        run_cases(sym, good, cases, [arity](const Args& a) { return call(arity, a); });
     }
     delete ctx;
     return 0;

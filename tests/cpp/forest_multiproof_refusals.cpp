@@ -5,17 +5,11 @@
 // every other row varies the control one way.  The buffers are addresses 1 MiB apart that nothing dereferences: no row reaches a
 // device.  (tests/test_forest_multiproof_cpu.py compares the lines with tests/golden/forest_multiproof_refusals.txt; api_refusals.cpp
 // tables the entry points whose names end in `_device`, these — `_device_into`, as the append's — have their table here.)
-#include <cstdint>
-#include <cstdio>
-#include <functional>
-#include <string>
-#include <vector>
+#include "refusal_table.hpp"
 
-#include "../../poseidon252_amd/csrc/ctx.hpp"
+using namespace refusal;
 
 namespace {
-
-uint64_t g_tag[4] = {1, 2, 3, 4};
 
 struct Args {
     p252_ctx* ctx;
@@ -23,9 +17,6 @@ struct Args {
     uint64_t d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof, proof_len, d_proof_offsets,
         d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad;
 };
-
-void* P(uint64_t v) { return reinterpret_cast<void*>(v); }
-uint64_t slot(unsigned i) { return 0x100000000ull + 0x100000ull * i; }
 
 int extract(unsigned arity, const Args& a) {
     return (arity == 4 ? p252_merkle4_forest_ragged_multiproof_device_into : p252_merkle2_forest_ragged_multiproof_device_into)(
@@ -38,21 +29,13 @@ int verify(unsigned arity, const Args& a) {
         a.proof_len, P(a.d_proof_offsets), P(a.d_roots), P(a.d_ok), P(a.d_roots_out), P(a.d_n_hashed), P(a.d_n_bad), nullptr);
 }
 
-struct Case {
-    std::string name;
-    std::function<void(Args&)> vary;
-};
-struct Buf {
-    const char* name;
-    uint64_t Args::*at;
-    unsigned align;
-};
+using Case = CaseOf<Args>;
+using Buf = BufOf<Args>;
 
 }  // namespace
 
 int main() {
     p252_ctx* ctx = new p252_ctx();  // device = -1: never bound
-    const uint64_t MAXZ = SIZE_MAX;
     for (unsigned arity : {4u, 2u}) {
         // the bound needs no context: its zero rows and one value
         const char* bsym = arity == 4 ? "p252_merkle4_forest_ragged_multiproof_bound" : "p252_merkle2_forest_ragged_multiproof_bound";
@@ -80,12 +63,12 @@ int main() {
             {"max_leaves=2^32", [](Args& a) { a.max_leaves = 1ull << 32; }},
             {"max_leaves=1,d_levels=NULL", [](Args& a) { a.max_leaves = 1, a.d_levels = 0; }},
             {"proof_len=0,d_proof=NULL", [](Args& a) { a.proof_len = 0, a.d_proof = 0; }},
-            {"proof_len=SIZE_MAX/32", [MAXZ](Args& a) { a.proof_len = MAXZ / 32; }},
-            {"proof_len=SIZE_MAX/32+1", [MAXZ](Args& a) { a.proof_len = MAXZ / 32 + 1; }},
-            {"n_leaves=SIZE_MAX/64+1", [MAXZ](Args& a) { a.n_leaves = MAXZ / 64 + 1; }},
-            {"n_trees=SIZE_MAX/8/66+1", [MAXZ](Args& a) { a.n_trees = MAXZ / 8 / 66 + 1; }},
+            {"proof_len=SIZE_MAX/32", [](Args& a) { a.proof_len = MAXZ / 32; }},
+            {"proof_len=SIZE_MAX/32+1", [](Args& a) { a.proof_len = MAXZ / 32 + 1; }},
+            {"n_leaves=SIZE_MAX/64+1", [](Args& a) { a.n_leaves = MAXZ / 64 + 1; }},
+            {"n_trees=SIZE_MAX/8/66+1", [](Args& a) { a.n_trees = MAXZ / 8 / 66 + 1; }},
             {"n_trees*min(max_leaves,n_leaves)>SIZE_MAX/2",
-             [MAXZ](Args& a) { a.n_leaves = 1ull << 40, a.max_leaves = 1ull << 31, a.n_trees = ((MAXZ / 2) >> 31) + 1; }},
+             [](Args& a) { a.n_leaves = 1ull << 40, a.max_leaves = 1ull << 31, a.n_trees = ((MAXZ / 2) >> 31) + 1; }},
         };
         const Buf ebufs[] = {{"d_leaves", &Args::d_leaves, 16},         {"d_offsets", &Args::d_offsets, 8},   {"d_levels", &Args::d_levels, 16},
                              {"d_tree_ids", &Args::d_tree_ids, 4},      {"d_leaf_ids", &Args::d_leaf_ids, 8}, {"d_leaves_out", &Args::d_leaves_out, 16},
@@ -101,20 +84,8 @@ int main() {
             std::vector<Case> cases = shape;
             if (which) cases.push_back({"tag=NULL", [](Args& a) { a.tag = nullptr; }});
             // every buffer NULL, and off its alignment
-            for (const Buf& b : which ? std::vector<Buf>(vbufs, vbufs + 11) : std::vector<Buf>(ebufs, ebufs + 9)) {
-                cases.push_back({std::string(b.name) + "=NULL", [b](Args& a) { a.*(b.at) = 0; }});
-                if (b.align > 1) cases.push_back({std::string(b.name) + "+" + std::to_string(b.align / 2), [b](Args& a) { a.*(b.at) += b.align / 2; }});
-            }
-            for (const Case& c : cases) {
-                Args a = good;
-                c.vary(a);
-                ctx->err.clear();
-                const int rc = which ? verify(arity, a) : extract(arity, a);
-                std::string msg = p252_last_error(a.ctx);
-                for (char& ch : msg)
-                    if (ch == '\t' || ch == '\n') ch = ' ';
-                std::printf("%s\t%s\t%d\t%s\n", sym.c_str(), c.name.c_str(), rc, msg.c_str());
-            }
+            which ? null_and_misaligned(cases, vbufs) : null_and_misaligned(cases, ebufs);
+            run_cases(sym, good, cases, [arity, which](const Args& a) { return which ? verify(arity, a) : extract(arity, a); });
         }
     }
     delete ctx;

@@ -18,8 +18,7 @@ import sys
 import numpy as np
 
 import edgecases as E
-from test_forest_append_gpu import SENTINEL
-from test_forest_openings_gpu import _depth, _levels_bound
+from helpers.forest import SENTINEL, _depth, _levels_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if os.path.join(ROOT, "bench_tools") not in sys.path:

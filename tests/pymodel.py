@@ -597,3 +597,61 @@ def perm_armaint(x_mont, C=None, M=None, T=None):
         X = [sbox(z) for z in Z]
         Z = [irow(X, i, T["fr_kappa"][k][i]) for i in range(5)]
     return [mm(z, T["F"]) for z in Z]
+
+
+# ---- the cipher: dusk-safe's sponge state machine on Python ints (for tests/test_encryption.py and tests/shapecases.py) ----
+def _io_pattern(variant, ln):
+    """the io-pattern as dusk-safe sees it: list of ('A' | 'S', len) calls"""
+    if variant == 0:
+        return [("A", 2), ("A", 1), ("S", ln), ("A", ln), ("S", 1)]
+    pat = [("A", 2), ("A", 1)]
+    left = ln
+    while left:
+        c = min(4, left)
+        pat += [("S", c), ("A", c)]
+        left -= c
+    return pat + [("S", 1)]
+
+
+class BigIntSponge:
+    """dusk-safe 0.3's Sponge restated on Python ints (mechanics pinned by the reference KAT)"""
+
+    def __init__(self, tag, perm):
+        self.state = [tag, 0, 0, 0, 0]
+        self.pos_absorb = self.pos_squeeze = 0
+        self.perm = perm
+
+    def absorb(self, elems):
+        for e in elems:
+            if self.pos_absorb == 4:
+                self.state = self.perm(self.state)
+                self.pos_absorb = 0
+            self.state[1 + self.pos_absorb] = (self.state[1 + self.pos_absorb] + e) % P
+            self.pos_absorb += 1
+        self.pos_squeeze = 4
+
+    def squeeze(self, n):
+        out = []
+        for _ in range(n):
+            if self.pos_squeeze == 4:
+                self.state = self.perm(self.state)
+                self.pos_squeeze = self.pos_absorb = 0
+            out.append(self.state[1 + self.pos_squeeze])
+            self.pos_squeeze += 1
+        return out
+
+
+def _bigint_encrypt(variant, tag, m, secret, nonce, perm):
+    sp = BigIntSponge(tag, perm)
+    out, masks, consumed, absorbed_msg = [], [], 0, 0
+    calls = _io_pattern(variant, len(m))
+    sp.absorb(secret)
+    sp.absorb([nonce])
+    for kind, c in calls[2:-1]:
+        if kind == "S":
+            masks += sp.squeeze(c)
+        else:
+            sp.absorb(m[absorbed_msg:absorbed_msg + c])
+            absorbed_msg += c
+    mac = sp.squeeze(1)[0]
+    return [(a + b) % P for a, b in zip(m, masks)] + [mac]

@@ -204,8 +204,8 @@ def expected_rows(family, n, part=WHOLE):
 
 # ---------------------------------------------------------------------------------------------- big-integer references
 def bigint_encrypt(variant, tag, message, secret, nonce, perm):
-    """the big-integer state machine of tests/test_encryption.py (its one copy)"""
-    from test_encryption import _bigint_encrypt
+    """the big-integer state machine of tests/pymodel.py (its one copy)"""
+    from pymodel import _bigint_encrypt
     return _bigint_encrypt(variant, tag, message, secret, nonce, perm)
 
 

@@ -5,37 +5,23 @@ entry point, and varied rows the library accepts) by return code and by the part
 first ": " (the rest is the HIP runtime's and differs between machines)."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from helpers.percall import ERR_HIP, assert_rows_equal_golden, refusal_table
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "api_refusals.txt")
-ERR_HIP = -4
 # the one entry point that takes a communicator, which only RCCL ranks can make: no argument set of it gets past validation here
 NO_CONTROL = {"p252_merkle4_tree_sharded_device"}
 
 
-def _rows(text):
-    rows = [line.split("\t") for line in text.splitlines()]
-    assert all(len(r) == 4 for r in rows), [r for r in rows if len(r) != 4][:3]
-    return [(r[0], r[1], int(r[2]), r[3].split(": ")[0] if int(r[2]) == ERR_HIP else r[3]) for r in rows]
-
-
 @pytest.fixture(scope="module")
 def table(tmp_path_factory):
-    from poseidon252_amd import build as B
-    exe = str(tmp_path_factory.mktemp("api_refusals") / "api_refusals")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(B.ROCM, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "api_refusals.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"), "-lposeidon252_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
-    return _rows(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+    return refusal_table("api_refusals", tmp_path_factory.mktemp("api_refusals"))
 
 
 def test_every_row_equals_the_recorded_one(table):
-    golden = _rows(open(GOLDEN).read())
-    assert [r[:2] for r in table] == [r[:2] for r in golden]  # the same cases in the same order
-    assert [r for r, g in zip(table, golden) if r != g] == []
+    assert_rows_equal_golden(table, "api_refusals")
 
 
 def test_every_entry_point_has_a_control_row_that_reaches_the_device(table):

@@ -5,7 +5,6 @@ import ctypes
 import os
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
 
 
 def _c_kind(ctype):
@@ -42,49 +42,6 @@ def test_prototypes_match_the_header():
         for (pname, ctype), t in zip(params, argtypes):
             assert _c_kind(ctype) == _ctypes_kind(t), "%s(%s): %s bound as %s" % (name, pname, ctype, t.__name__)
         assert _c_kind(ret) == _ctypes_kind(restype), "%s returns %s, bound as %s" % (name, ret, restype)
-
-
-# host helpers that take no context and touch no device: the recorder may forward them to the real library
-HOST_HELPERS = {"p252_merkle4_levels_len", "p252_merkle2_levels_len", "p252_merkle4_depth", "p252_merkle2_depth", "p252_tag",
-                "p252_encryption_tag"}
-
-
-class Recorder:
-    """stands in for the library: records every other call and returns P252_OK without forwarding it"""
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in HOST_HELPERS:
-            return getattr(self.real, name)
-
-        def call(*args):
-            self.calls.append(name)
-            return 0
-        return call
-
-
-class OnDevice(torch.Tensor):
-    """a CPU tensor that reports itself to be on cuda:0 — passes the binding's checks; only the recorder ever sees its address"""
-
-    @property
-    def is_cuda(self):
-        return True
-
-    def get_device(self):
-        return 0
-
-
-def dev(dtype=torch.int64, n=64):
-    return torch.zeros(n, dtype=dtype).as_subclass(OnDevice)  # 512 bytes as int64: more than any call below touches, a forest's levels apart
-
-
-def _no_device_context():
-    from poseidon252_amd import Context
-    ctx = Context.__new__(Context)  # no device: nothing below may reach one
-    ctx._h, ctx.device = None, 0
-    return ctx
 
 
 def arity_cases(c):
@@ -192,29 +149,6 @@ def cases():
          lambda a: merkle4_tree_multi_device_resident([c, ctx2], tag, a["d_leaves"], 4, a["d_roots"]),
          dict(d_leaves=[dev(), dev()], d_roots=[dev(), dev()])),
     ]
-
-
-def with_cpu_tensor(args):
-    """every variant of `args` with one device tensor (an argument, or an entry of a list / tuple argument) replaced by a CPU one"""
-    def cpu(t):
-        return torch.zeros_like(t.as_subclass(torch.Tensor))
-    for name, v in args.items():
-        if isinstance(v, OnDevice):
-            yield name, dict(args, **{name: cpu(v)})
-        elif isinstance(v, (list, tuple)):
-            for i in range(len(v)):
-                seq = list(v)
-                seq[i] = cpu(seq[i])
-                yield "%s[%d]" % (name, i), dict(args, **{name: type(v)(seq)})
-
-
-@pytest.fixture
-def recorder(monkeypatch):
-    from poseidon252_amd import _lib
-    rec = Recorder(_lib.lib())
-    monkeypatch.setattr(_lib, "_lib", rec)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=0))
-    return rec
 
 
 # the tensors of cases(): 67 in the rows that take an arity, once per arity, and 73 in the others (the 68 of the round-5 surface and

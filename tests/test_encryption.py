@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import pymodel
+from pymodel import _bigint_encrypt
 
 VARIANTS = [0, 1]  # STREAM, DUPLEX
 LENS = [1, 2, 4, 5, 21, 42]  # tests/encryption.rs:33,49 use 42 and 21; benches/encrypt.rs uses 2
@@ -25,63 +26,6 @@ def _inputs(oracle_mod, n, ln, seed):
     secrets = oracle_mod.fill_random(seed + 1, 2 * n).reshape(n, 2, 4)
     nonces = oracle_mod.fill_random(seed + 2, n)
     return msgs, secrets, nonces
-
-
-def _io_pattern(variant, ln):
-    """the io-pattern as dusk-safe sees it: list of ('A' | 'S', len) calls"""
-    if variant == 0:
-        return [("A", 2), ("A", 1), ("S", ln), ("A", ln), ("S", 1)]
-    pat = [("A", 2), ("A", 1)]
-    left = ln
-    while left:
-        c = min(4, left)
-        pat += [("S", c), ("A", c)]
-        left -= c
-    return pat + [("S", 1)]
-
-
-class BigIntSponge:
-    """dusk-safe 0.3's Sponge restated on Python ints (mechanics pinned by the reference KAT)"""
-
-    def __init__(self, tag, perm):
-        self.state = [tag, 0, 0, 0, 0]
-        self.pos_absorb = self.pos_squeeze = 0
-        self.perm = perm
-
-    def absorb(self, elems):
-        for e in elems:
-            if self.pos_absorb == 4:
-                self.state = self.perm(self.state)
-                self.pos_absorb = 0
-            self.state[1 + self.pos_absorb] = (self.state[1 + self.pos_absorb] + e) % pymodel.P
-            self.pos_absorb += 1
-        self.pos_squeeze = 4
-
-    def squeeze(self, n):
-        out = []
-        for _ in range(n):
-            if self.pos_squeeze == 4:
-                self.state = self.perm(self.state)
-                self.pos_squeeze = self.pos_absorb = 0
-            out.append(self.state[1 + self.pos_squeeze])
-            self.pos_squeeze += 1
-        return out
-
-
-def _bigint_encrypt(variant, tag, m, secret, nonce, perm):
-    sp = BigIntSponge(tag, perm)
-    out, masks, consumed, absorbed_msg = [], [], 0, 0
-    calls = _io_pattern(variant, len(m))
-    sp.absorb(secret)
-    sp.absorb([nonce])
-    for kind, c in calls[2:-1]:
-        if kind == "S":
-            masks += sp.squeeze(c)
-        else:
-            sp.absorb(m[absorbed_msg:absorbed_msg + c])
-            absorbed_msg += c
-    mac = sp.squeeze(1)[0]
-    return [(a + b) % pymodel.P for a, b in zip(m, masks)] + [mac]
 
 
 # ------------------------------------------------------------------ CPU

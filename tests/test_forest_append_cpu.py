@@ -4,10 +4,8 @@ brute-force construction of both trees and with trees hashed by the big-int mode
 declared, exported and mirrored in the Rust FFI under ABI 9, under a name the refusal table of the `_device(` symbols does not catch;
 forest_append.hip compiles for gfx950 within its resource targets and hashes nothing itself; the host refusals, as a table of their
 own; the Python methods validate every buffer before the library is reached and hand the C call the right sizes."""
-import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -18,12 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 from forest_append_bench import forest_append_model, level_widths, model_leaves  # noqa: E402
+from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
 from helpers.kernel_resources import kernel_resources  # noqa: E402
-from test_binding_checks import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
+from helpers.percall import (ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols,  # noqa: E402
+                             refusal_table)
 
 SYMBOLS = ("p252_merkle4_forest_ragged_append_device_into", "p252_merkle2_forest_ragged_append_device_into")
 N_ARGS = 22
-ERR_HIP = -4
 
 
 # ---- the model ----
@@ -130,22 +129,7 @@ def test_model_against_trees_hashed_by_the_big_int_model(oracle_mod, arity, n, m
 
 # ---- the symbols ----
 def test_two_symbols_declared_exported_and_in_sys_rs():
-    from poseidon252_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
-    for name in SYMBOLS:
-        m = re.search(r"\bint %s\s*\((.*?)\);" % name, header, flags=re.S)
-        assert m, name
-        assert m.group(1).count(",") + 1 == N_ARGS, name
-        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
-        assert len(_lib.PROTOTYPES[name][0]) == N_ARGS, name
-        assert rust[name].count(":") == N_ARGS, (name, rust[name])
-    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_rust_sys.py"), "--check"], stdout=subprocess.DEVNULL)
+    _, header = check_abi_symbols(dict.fromkeys(SYMBOLS, N_ARGS))
     # no new name that the refusal table of the `_device(` symbols would have to hold: that table stays as it is
     declared = set(re.findall(r"\b(p252_[a-z0-9_]+_device)\s*\(", header))
     table = {line.split("\t")[0] for line in open(os.path.join(ROOT, "tests", "golden", "api_refusals.txt")).read().splitlines()}
@@ -183,26 +167,13 @@ def test_the_unit_hashes_nothing_itself():
 
 
 # ---- the host refusals ----
-def _rows(text):
-    rows = [line.split("\t") for line in text.splitlines()]
-    assert all(len(r) == 4 for r in rows), [r for r in rows if len(r) != 4][:3]
-    return [(r[0], r[1], int(r[2]), r[3].split(": ")[0] if int(r[2]) == ERR_HIP else r[3]) for r in rows]
-
-
 @pytest.fixture(scope="module")
 def table(tmp_path_factory):
-    from poseidon252_amd import build as B
-    exe = str(tmp_path_factory.mktemp("append_refusals") / "append_refusals")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(B.ROCM, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "append_refusals.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"), "-lposeidon252_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
-    return _rows(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+    return refusal_table("append_refusals", tmp_path_factory.mktemp("append_refusals"))
 
 
 def test_every_refusal_row_equals_the_recorded_one(table):
-    golden = _rows(open(os.path.join(ROOT, "tests", "golden", "append_refusals.txt")).read())
-    assert [r[:2] for r in table] == [r[:2] for r in golden]
-    assert [r for r, g in zip(table, golden) if r != g] == []
+    assert_rows_equal_golden(table, "append_refusals")
 
 
 def test_refusal_table_has_a_control_row_and_every_host_refusal(table):
@@ -295,14 +266,8 @@ def test_python_methods_refuse_cpu_tensors_and_pass_the_sizes(recorder, monkeypa
 
 
 def test_cpp_mirror_test_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_forest_append_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_append_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_forest_append_api", tmp_path)
 
 
 def test_bench_tool_parses():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_append_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--quick" in r.stdout, r.stderr
+    bench_tool_parses("forest_append_bench")

@@ -5,13 +5,13 @@ the append itself: offsets, leaves, levels, roots, the digest count and the bad 
 appends; both digest kernels and more trees than one scan tile; two appends in a row, openings and updates of the grown forest; two
 streams, graph capture, the C++ mirror."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from test_forest_openings_gpu import _levels_bound, _np, _offsets, _open, _tag, _torch, _verify
+from helpers.forest import SENTINEL, Grown, Old, _append, _fresh, _np, _offsets, _open, _outputs, _tag, _torch, _tree, _verify
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
@@ -19,49 +19,7 @@ from forest_append_bench import forest_append_model, level_widths, model_leaves 
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -0x0123456789ABCDEF  # no scalar and no root has these limbs (the top limb is above the modulus')
 SCAN_TILE = 2048                # FOREST_APPEND_SCAN_TILE of csrc/forest_append.h
-
-
-def _tree(oracle_mod, arity):
-    return oracle_mod.merkle4_tree if arity == 4 else oracle_mod.merkle2_tree
-
-
-class Old:
-    """a forest built on the device with its tree-major levels"""
-
-    def __init__(self, ctx, arity, flat, off, max_leaves):
-        import torch
-        self.arity, self.flat, self.off, self.max_leaves, self.n_trees = arity, flat, np.asarray(off, np.uint64), max_leaves, len(off) - 1
-        self.d, self.d_off = _torch(flat), _torch(self.off)
-        self.roots = torch.full((self.n_trees, 4), SENTINEL, dtype=torch.int64, device=self.d.device)
-        self.d_lv = torch.full((_levels_bound(flat.shape[0], self.n_trees, max_leaves, arity) + 3, 4), SENTINEL, dtype=torch.int64, device=self.d.device)
-        ctx.merkle_forest_ragged_device(_tag(arity), self.d, self.d_off, self.n_trees, max_leaves, self.roots, self.d_lv, None, arity=arity)
-
-
-def _outputs(arity, total, n_trees_new, max_new, tail=7):
-    """sentinel-filled output buffers with `tail` scalars past what the call may use -> (leaves, offsets, levels, roots)"""
-    import torch
-    full = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.int64, device="cuda:0")  # noqa: E731
-    return full(total + tail, 4), full(n_trees_new + 1 + tail), full(_levels_bound(total, n_trees_new, max_new, arity) + tail, 4), full(n_trees_new + tail, 4)
-
-
-def _append(ctx, old, d_add, d_aoff, n_trees_new, max_new, out, bad=None, hashed=None):
-    call = ctx.merkle4_forest_ragged_append_device if old.arity == 4 else ctx.merkle2_forest_ragged_append_device
-    call(_tag(old.arity), old.d, old.d_off, old.n_trees, old.max_leaves, old.d_lv, d_add, d_aoff, n_trees_new, max_new, out[0], out[1][:n_trees_new + 1],
-         out[2], out[3][:n_trees_new], bad, hashed)
-
-
-def _fresh(ctx, arity, M, old_flat, add, n_trees_new, max_new, like):
-    """the reference: the model's new forest (leaves padded with the sentinel to the capacity of `like`), built afresh into
-    sentinel-filled buffers of the same sizes -> (leaves, offsets, levels, roots)"""
-    import torch
-    leaves, offsets, levels, roots = (torch.full_like(t, SENTINEL) for t in like)
-    want = model_leaves(M, old_flat, add)
-    leaves[:want.shape[0]] = _torch(want)
-    offsets[:n_trees_new + 1] = _torch(M["offsets_new"].astype(np.uint64))
-    ctx.merkle_forest_ragged_device(_tag(arity), leaves, offsets[:n_trees_new + 1], n_trees_new, max_new, roots[:n_trees_new], levels, None, arity=arity)
-    return leaves, offsets, levels, roots
 
 
 def _run(ctx, oracle_mod, arity, flat, off, max_leaves, add, aoff, max_new, oracle_up_to=70):
@@ -213,14 +171,6 @@ def test_more_trees_than_one_scan_tile(gpu_ctx, oracle_mod, arity):
 
 
 # ---- 5. composition ----
-class Grown(Old):
-    """the outputs of an append, as the forest the next call reads"""
-
-    def __init__(self, arity, out, n_trees, max_leaves):
-        self.arity, self.n_trees, self.max_leaves = arity, n_trees, max_leaves
-        self.d, self.d_off, self.d_lv, self.roots = out[0], out[1][:n_trees + 1], out[2], out[3][:n_trees]
-
-
 @pytest.mark.parametrize("arity", [4, 2])
 def test_two_appends_equal_one_and_the_grown_forest_is_an_ordinary_forest(gpu_ctx, oracle_mod, arity):
     import torch
@@ -361,10 +311,4 @@ def test_graph_capture_replays_on_new_leaves(gpu_ctx, oracle_mod, arity):
 
 # ---- 7. the C++ mirror ----
 def test_cpp_mirror_on_gpu(gpu_ctx, oracle_mod, tmp_path):
-    exe = str(tmp_path / "test_forest_append_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_append_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0, out.stdout.decode() + out.stderr.decode()
+    run_cpp_mirror(build_cpp_mirror("test_forest_append_api", tmp_path))

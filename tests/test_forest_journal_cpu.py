@@ -4,13 +4,9 @@ mirrored in the Rust FFI under ABI 9; the host bound is the documented formula, 
 where no two updates share an ancestor; forest_journal.hip compiles for gfx950 to its three bookkeeping kernels within their
 resource targets and brings no digest of its own; the Python mirror refuses a CPU tensor before the library is reached and adds no
 arity= parameter; the argument refusals of the two device entry points equal a recorded table; the C++ mirror test compiles."""
-import ctypes
 import inspect
 import os
 import re
-import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -20,10 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 
 import forestjournal as FJ  # noqa: E402
+from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
+from helpers.forest import _mix, dirty_count  # noqa: E402
 from helpers.kernel_resources import kernel_resources  # noqa: E402
-from test_binding_checks import Recorder, _no_device_context, dev, with_cpu_tensor  # noqa: E402
-from test_forest_openings_gpu import _mix  # noqa: E402
-from test_forest_update_cpu import dirty_count  # noqa: E402
+from helpers.percall import (ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols,  # noqa: E402
+                             refusal_table)
 
 ARGS = {"p252_merkle%d_forest_ragged_%s" % (a, stem): n for a in (4, 2)
         for stem, n in (("journal_bound", 4), ("update_journaled_device_into", 20), ("journal_swap_device_into", 14))}
@@ -31,22 +28,8 @@ STEMS = ("journal_bound", "update_journaled_device", "journal_swap_device")
 
 
 def test_six_symbols_declared_exported_and_in_sys_rs():
-    from poseidon252_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
     assert len(ARGS) == 6
-    for name, n_args in ARGS.items():
-        m = re.search(r"\b(?:int|size_t) %s\s*\((.*?)\);" % name, header, flags=re.S)
-        assert m, name
-        assert m.group(1).count(",") + 1 == n_args, name
-        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
-        assert len(_lib.PROTOTYPES[name][0]) == n_args, name
-        assert rust[name].count(":") == n_args, (name, rust[name])
-    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
+    raw, header = check_abi_symbols(ARGS)
     # the update's arguments first, in its order, then the journal's four, then the stream
     plain = re.search(r"\bint p252_merkle4_forest_ragged_update_device\s*\((.*?)\);", header, flags=re.S).group(1)
     journaled = re.search(r"\bint p252_merkle4_forest_ragged_update_journaled_device_into\s*\((.*?)\);", header, flags=re.S).group(1)
@@ -163,15 +146,6 @@ def test_own_translation_unit_and_nothing_is_copied():
         assert "forest_journal" not in open(os.path.join(CSRC, other)).read(), other
 
 
-@pytest.fixture
-def recorder(monkeypatch):
-    from poseidon252_amd import _lib
-    rec = Recorder(_lib.lib())
-    monkeypatch.setattr(_lib, "_lib", rec)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=0))
-    return rec
-
-
 def _cases(c):
     """(the C entry point, the call, its arguments) for the four methods that hand device pointers to the library.  d_leaves is 16
     scalars long, which sets the bound of d_levels; the journal holds 8 entries."""
@@ -226,37 +200,22 @@ def test_the_journal_is_sized_by_its_capacity(recorder):
 
 
 # ---- the refusals of the two device entry points, as a table that needs no GPU (tests/cpp/journal_refusals.cpp) ----
-ERR_HIP = -4
 DEVICE_SYMBOLS = [n for n in ARGS if n.endswith("_device_into")]
 
 
-def _rows(text):
-    rows = [line.split("\t") for line in text.splitlines()]
-    assert all(len(r) == 4 for r in rows), [r for r in rows if len(r) != 4][:3]
-    # (what follows the library's own part of a HIP failure is the runtime's text and differs between machines)
-    return [(r[0], r[1], int(r[2]), r[3].split(": ")[0] if int(r[2]) == ERR_HIP else r[3]) for r in rows]
-
-
 @pytest.fixture(scope="module")
-def refusal_table(tmp_path_factory):
-    from poseidon252_amd import build as B
-    exe = str(tmp_path_factory.mktemp("journal_refusals") / "journal_refusals")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(B.ROCM, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "journal_refusals.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"), "-lposeidon252_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
-    return _rows(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+def table(tmp_path_factory):
+    return refusal_table("journal_refusals", tmp_path_factory.mktemp("journal_refusals"))
 
 
-def test_every_refusal_row_equals_the_recorded_one(refusal_table):
-    golden = _rows(open(os.path.join(ROOT, "tests", "golden", "journal_refusals.txt")).read())
-    assert [r[:2] for r in refusal_table] == [r[:2] for r in golden]  # the same cases in the same order
-    assert [r for r, g in zip(refusal_table, golden) if r != g] == []
+def test_every_refusal_row_equals_the_recorded_one(table):
+    assert_rows_equal_golden(table, "journal_refusals")
 
 
-def test_refusal_table_has_a_control_row_and_every_host_refusal(refusal_table):
-    assert sorted({r[0] for r in refusal_table}) == sorted(DEVICE_SYMBOLS) and len(DEVICE_SYMBOLS) == 4
+def test_refusal_table_has_a_control_row_and_every_host_refusal(table):
+    assert sorted({r[0] for r in table}) == sorted(DEVICE_SYMBOLS) and len(DEVICE_SYMBOLS) == 4
     for sym in DEVICE_SYMBOLS:
-        by = {r[1]: r[2:] for r in refusal_table if r[0] == sym}
+        by = {r[1]: r[2:] for r in table if r[0] == sym}
         arity, update = int(sym[len("p252_merkle")]), "update_journaled" in sym
         assert by["control"] == (ERR_HIP, "hipSetDevice(ctx->device)")  # past validation: without this the other rows prove nothing
         refused = lambda case, word: by[case][0] == -3 and word in by[case][1]  # noqa: E731
@@ -316,13 +275,8 @@ def test_bound_method_reaches_the_host_function():
 
 
 def test_cpp_mirror_test_compiles(tmp_path):
-    exe = str(tmp_path / "test_forest_journal_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_journal_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_forest_journal_api", tmp_path, oracle=False)
 
 
 def test_bench_tool_parses():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_journal_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--quick" in r.stdout, r.stderr
+    bench_tool_parses("forest_journal_bench")

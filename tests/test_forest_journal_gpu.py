@@ -4,16 +4,15 @@ oracle, the journal against the numpy model (tests/forestjournal.py) and the byt
 byte, stacked journals, duplicates and bad updates, edge sizes, a journal swapped into a forest it was not taken on, streams, graph
 capture, the C++ mirror, and the swap against the re-update it replaces."""
 import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
 import forestjournal as FJ
-from test_forest_openings_gpu import _mix, _np, _offsets, _open, _tag, _torch, _verify
-from test_forest_update_cpu import dirty_count
-from test_forest_update_gpu import SENTINEL, _check_against_fresh_build, _distinct_pairs, _forest
+from helpers.forest import (SENTINEL, _check_against_fresh_build, _distinct_pairs, _forest, _mix, _np, _offsets, _open, _tag, _torch, _verify,
+                            dirty_count)
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 pytestmark = pytest.mark.gpu
 
@@ -467,12 +466,7 @@ def test_merkle_conveniences_round_trip(gpu_ctx, oracle_mod, arity):
 
 
 def test_cpp_mirror_on_gpu(gpu_ctx, tmp_path):
-    exe = str(tmp_path / "test_forest_journal_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_journal_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0, out.stdout.decode() + out.stderr.decode()
+    run_cpp_mirror(build_cpp_mirror("test_forest_journal_api", tmp_path, oracle=False))
 
 
 # ---- 9. the swap against what it replaces ----

@@ -4,10 +4,8 @@ FFI under ABI 9; forest_multiproof.hip is its own translation unit, compiles for
 hashing kernel; the model the GPU tests compare the device's bytes with (a composition of the single-tree model) agrees with a
 brute-force set construction and, with the oracle's digest, reproduces the oracle's roots; the bound holds and is reached; the Python
 mirror validates every buffer before it reaches the library; every host refusal is the recorded one; the C++ mirror test compiles."""
-import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -19,36 +17,20 @@ CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 from forest_multiproof_bench import (forest_multiproof_bound, forest_multiproof_counts, forest_multiproof_extract,  # noqa: E402
                                      forest_multiproof_roots)
+from helpers.binding import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
 from helpers.kernel_resources import kernel_resources  # noqa: E402
-from test_forest_openings_cpu import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
+from helpers.percall import (ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols,  # noqa: E402
+                             refusal_table)
 import edgecases as E  # noqa: E402
 
 ARGS = {"p252_merkle4_forest_ragged_multiproof_bound": 4, "p252_merkle2_forest_ragged_multiproof_bound": 4,
         "p252_merkle4_forest_ragged_multiproof_device_into": 16, "p252_merkle2_forest_ragged_multiproof_device_into": 16,
         "p252_merkle4_forest_ragged_multiproof_verify_device_into": 19, "p252_merkle2_forest_ragged_multiproof_verify_device_into": 19}
-ERR_HIP = -4
 SIZES = (0, 1, 2, 3, 4, 5, 16, 17, 21, 64, 65)
 
 
 def test_six_symbols_declared_exported_and_in_sys_rs():
-    from poseidon252_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
-    for name, n_args in ARGS.items():
-        m = re.search(r"\b(int|size_t) %s\s*\((.*?)\);" % name, header, flags=re.S)
-        assert m, name
-        assert (m.group(1) == "size_t") == name.endswith("_bound"), name
-        assert m.group(2).count(",") + 1 == n_args, name
-        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
-        assert len(_lib.PROTOTYPES[name][0]) == n_args, name
-        assert rust[name].count(":") == n_args, (name, rust[name])
-    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_rust_sys.py"), "--check"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    check_abi_symbols(ARGS)
 
 
 def test_own_translation_unit_without_a_hashing_kernel():
@@ -269,26 +251,13 @@ def test_conveniences_are_exported_and_refuse_an_outside_pair_before_any_call():
 
 
 # ---- the host refusals ----
-def _rows(text):
-    rows = [line.split("\t") for line in text.splitlines()]
-    assert all(len(r) == 4 for r in rows), [r for r in rows if len(r) != 4][:3]
-    return [(r[0], r[1], int(r[2]), r[3].split(": ")[0] if int(r[2]) == ERR_HIP else r[3]) for r in rows]
-
-
 @pytest.fixture(scope="module")
 def table(tmp_path_factory):
-    from poseidon252_amd import build as B
-    exe = str(tmp_path_factory.mktemp("forest_multiproof_refusals") / "forest_multiproof_refusals")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(B.ROCM, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "forest_multiproof_refusals.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-o", exe])
-    return _rows(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+    return refusal_table("forest_multiproof_refusals", tmp_path_factory.mktemp("forest_multiproof_refusals"))
 
 
 def test_every_refusal_row_equals_the_recorded_one(table):
-    golden = _rows(open(os.path.join(ROOT, "tests", "golden", "forest_multiproof_refusals.txt")).read())
-    assert [r[:2] for r in table] == [r[:2] for r in golden]
-    assert [r for r, g in zip(table, golden) if r != g] == []
+    assert_rows_equal_golden(table, "forest_multiproof_refusals")
 
 
 def test_refusal_table_has_a_control_row_and_every_host_refusal(table):
@@ -324,14 +293,8 @@ def test_refusal_table_has_a_control_row_and_every_host_refusal(table):
 
 
 def test_cpp_mirror_test_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_forest_multiproof_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_multiproof_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_forest_multiproof_api", tmp_path)
 
 
 def test_bench_tool_parses():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_multiproof_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--quick" in r.stdout, r.stderr
+    bench_tool_parses("forest_multiproof_bench")

@@ -5,15 +5,14 @@ existing single-tree call, the roots against the oracle; forests whose tree bord
 that reach both digest kernels; rejection per tree, bad pairs, a short proof buffer, edge values, streams, p252_trim, the conveniences,
 the C++ mirror, and the time against the per-tree loop of the single-tree calls."""
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 import pytest
 
-from test_forest_openings_gpu import _np, _offsets, _tag, _torch
-from test_multiproof_gpu import _extract as _single_extract, _verify as _single_verify
+from helpers.forest import SENTINEL, _np, _offsets, _single_extract, _single_verify, _tag, _torch
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
@@ -22,7 +21,6 @@ import edgecases as E  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -0x0123456789ABCDEF  # no scalar and no root has these limbs (the top limb is above the modulus')
 SENT64 = np.uint64(SENTINEL & (2 ** 64 - 1))
 SIZES = [5, 300, 1, 17, 66, 0, 64, 1000, 2, 16]  # (arity 4: 64 and 16 are complete trees; 0 is an empty tree, bad only if named)
 _FORESTS = {}
@@ -349,13 +347,7 @@ def test_conveniences_sort_deduplicate_and_raise_on_an_outside_pair(gpu_ctx, ari
 
 
 def test_cpp_mirror_program_runs(gpu_ctx, oracle_mod, tmp_path):
-    exe = str(tmp_path / "test_forest_multiproof_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_multiproof_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    assert run_cpp_mirror(build_cpp_mirror("test_forest_multiproof_api", tmp_path), timeout=120).strip().endswith("ok")
 
 
 # ---- 9. relative time, same run ----

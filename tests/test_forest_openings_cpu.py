@@ -3,18 +3,16 @@ p252_merkle{4,2}_forest_ragged_verify_device; csrc/forest_openings.hip) — what
 declared, exported and mirrored in the Rust FFI under ABI 9; forest_openings.hip compiles for gfx950 within its resource targets and
 includes the library's permutation instead of copying it; the Python mirror validates every buffer before it reaches the library; a
 stale ABI-9 build is reported by name; the C++ mirror test compiles."""
-import ctypes
 import os
-import re
 import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
+from helpers.binding import _dev, recorder  # noqa: F401
 from helpers.kernel_resources import kernel_resources
+from helpers.percall import bench_tool_parses, build_cpp_mirror, check_abi_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
@@ -24,21 +22,7 @@ ARGS = {"p252_merkle4_forest_ragged_openings_device": 16, "p252_merkle2_forest_r
 
 
 def test_six_symbols_declared_exported_and_in_sys_rs():
-    from poseidon252_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
-    for name, n_args in ARGS.items():
-        m = re.search(r"\bint %s\s*\((.*?)\);" % name, header, flags=re.S)
-        assert m, name
-        assert m.group(1).count(",") + 1 == n_args, name
-        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
-        assert len(_lib.PROTOTYPES[name][0]) == n_args, name
-        assert rust[name].count(":") == n_args, (name, rust[name])
-    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
+    check_abi_symbols(ARGS)
 
 
 @pytest.fixture(scope="module")
@@ -72,47 +56,6 @@ def test_own_translation_unit_and_the_permutation_is_included():
     assert "forest_openings" not in open(os.path.join(CSRC, "kernels.h")).read()
     # the forest's index comes from the build's own kernels, not from a copy of them
     assert "k_fr_prep" not in src and "launch_forest_ragged_index" in open(os.path.join(CSRC, "forest_ragged.hip")).read()
-
-
-class _Recorder:
-    """stands in for the library: host helpers go to the real one, every other call is recorded and returns P252_OK"""
-    HOST = {"p252_merkle4_depth", "p252_merkle2_depth"}
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in self.HOST:
-            return getattr(self.real, name)
-
-        def call(*args):
-            self.calls.append(name)
-            return 0
-        return call
-
-
-class _OnDevice(torch.Tensor):
-    """a CPU tensor that reports itself to be on cuda:0: passes the binding's checks, only the recorder sees its address"""
-
-    @property
-    def is_cuda(self):
-        return True
-
-    def get_device(self):
-        return 0
-
-
-def _dev(n, dtype=torch.int64):
-    return torch.zeros(n, dtype=dtype).as_subclass(_OnDevice)
-
-
-@pytest.fixture
-def recorder(monkeypatch):
-    from poseidon252_amd import _lib
-    rec = _Recorder(_lib.lib())
-    monkeypatch.setattr(_lib, "_lib", rec)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: types.SimpleNamespace(cuda_stream=0))
-    return rec
 
 
 @pytest.mark.parametrize("arity", [4, 2])
@@ -207,14 +150,8 @@ def test_stale_abi9_build_is_reported_by_name(tmp_path, monkeypatch):
 
 
 def test_cpp_mirror_test_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_forest_openings_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_openings_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_forest_openings_api", tmp_path)
 
 
 def test_bench_tool_parses():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_openings_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--openings" in r.stdout, r.stderr
+    bench_tool_parses("forest_openings_bench", options=("--openings",))

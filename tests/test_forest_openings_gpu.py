@@ -5,90 +5,17 @@ and fixed-depth calls, bad openings, edge sizes, streams, graph capture, a leaf 
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 import pytest
+
+from helpers.forest import _build, _depth, _levels_bound, _median_ms, _mix, _np, _offsets, _open, _tag, _torch, _v2_rate, _verify
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD = 0xFF
-
-
-def _mix(arity):  # the sizes of test_forest_ragged_gpu.py
-    a = arity
-    return [1, 2, 3, a, a + 1, a * a - 1, a * a, a * a + 1, 63, 65, (4 ** 5 + 1) if a == 4 else (2 ** 10 + 1)]
-
-
-def _offsets(sizes, start=0):
-    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
-    return off + np.uint64(start)
-
-
-def _tag(arity):
-    from poseidon252_amd import merkle as M
-    return M.merkle4_tag() if arity == 4 else M.merkle2_tag()
-
-
-def _torch(a, dev="cuda:0"):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.view(np.int64)
-    elif a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).to(dev)
-
-
-def _np(t):
-    a = t.cpu().numpy()
-    return a.view(np.uint64) if a.dtype == np.int64 else a
-
-
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def _levels_bound(n_leaves, n_trees, max_leaves, arity):
-    return n_leaves // (arity - 1) + n_trees * _depth(max_leaves, arity)
-
-
-def _build(ctx, arity, d_leaves, d_off, n_trees, max_leaves):
-    """the forest with its tree-major levels -> (roots, levels)"""
-    import torch
-    n_leaves = d_leaves.numel() // 4
-    roots = torch.full((n_trees, 4), -1, dtype=torch.int64, device=d_leaves.device)
-    d_lv = torch.zeros((max(_levels_bound(n_leaves, n_trees, max_leaves, arity), 1), 4), dtype=torch.int64, device=d_leaves.device)
-    ctx.merkle_forest_ragged_device(_tag(arity), d_leaves, d_off, n_trees, max_leaves, roots, d_lv, None, arity=arity)
-    return roots, d_lv
-
-
-def _open(ctx, arity, d_leaves, d_off, n_trees, max_leaves, d_lv, tree_ids, leaf_ids):
-    """openings, re-hash and verify of (tree_ids, leaf_ids) (numpy) -> dict of numpy results"""
-    import torch
-    k = len(tree_ids)
-    d_tid, d_lid = _torch(np.asarray(tree_ids, np.uint32)), _torch(np.asarray(leaf_ids, np.uint64))
-    bad = torch.zeros(2, dtype=torch.int32, device=d_leaves.device)
-    lv, sib, pos, dep, D = ctx.merkle_forest_ragged_openings_device(d_leaves, d_off, n_trees, max_leaves, d_lv, d_tid, d_lid, k,
-                                                                    d_n_bad=bad[:1], arity=arity)
-    back = torch.full((k, 4), -1, dtype=torch.int64, device=d_leaves.device)
-    ctx.merkle_path_ragged_device(_tag(arity), lv, sib, pos, dep, D, back, k, d_n_bad=bad[1:], arity=arity)
-    return dict(leaves=lv, sib=sib, pos=pos, dep=dep, D=D, back=back, bad=bad, d_tid=d_tid, d_lid=d_lid)
-
-
-def _verify(ctx, arity, o, d_roots, n_trees):
-    import torch
-    k = o["dep"].numel()
-    ok = torch.full((k,), 7, dtype=torch.uint8, device=o["dep"].device)
-    ctx.merkle_forest_ragged_verify_device(_tag(arity), o["leaves"], o["sib"], o["pos"], o["dep"], o["D"], o["d_tid"], d_roots, n_trees, ok, k,
-                                           arity=arity)
-    return ok
 
 
 def _merkle2_openings(leaves, levels, indices):
@@ -153,7 +80,7 @@ _CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
 import poseidon252_amd as P
-import test_forest_openings_gpu as T
+from helpers import forest as T
 z = np.load(%(inp)r)
 arity, sizes = int(z["arity"]), z["sizes"].tolist()
 ctx = P.Context(0)
@@ -477,18 +404,6 @@ def test_trim_gives_the_scratch_back(oracle_mod):
         ctx.close()
 
 
-def _median_ms(fn, reps):
-    import torch
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
-
-
 # V1 floor: 0.9 x the ratio measured on an MI355X (profiles/forest_openings.txt: 1.004 for arity 4, 0.997 for arity 2), rounded down
 # to two digits — the margin is for box-to-box clock spread, which a same-process ratio mostly cancels
 V1_FLOOR = {4: 0.90, 2: 0.89}
@@ -497,33 +412,9 @@ _V2_CHILD = r"""
 import sys, json, numpy as np, torch
 sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
 import poseidon252_amd as P
-import test_forest_openings_gpu as T
+from helpers import forest as T
 print(json.dumps(T._v2_rate(P.Context(0))))
 """
-
-
-def _v2_rate(ctx, reps=7):
-    """sum of depths / time of path_ragged on a mixed forest (2,000 trees log-uniform in [1, 4^6], 2^19 openings, the tree drawn
-    uniformly), in levels per second"""
-    import torch
-    rng = np.random.default_rng(2)
-    top = 4 ** 6
-    sizes = np.floor(np.exp(rng.uniform(0, np.log(top + 1), 2000))).astype(np.int64).clip(1, top)
-    off = _offsets(sizes)
-    d = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device="cuda:0")
-    d_off = _torch(off)
-    roots, d_lv = _build(ctx, 4, d, d_off, len(sizes), top)
-    k = 1 << 19
-    tid = rng.integers(0, len(sizes), k)
-    lid = (rng.random(k) * sizes[tid]).astype(np.int64)
-    o = _open(ctx, 4, d, d_off, len(sizes), top, d_lv, tid, lid)
-    torch.cuda.synchronize()
-    assert torch.equal(o["back"], roots[_torch(tid.astype(np.int64))])
-    run = lambda: ctx.merkle_path_ragged_device(_tag(4), o["leaves"], o["sib"], o["pos"], o["dep"], o["D"], o["back"], k)  # noqa: E731
-    run()
-    ms = _median_ms(run, reps)
-    levels = int(o["dep"].to(torch.int64).sum())
-    return {"ms": ms, "levels_per_s": levels / ms * 1e3}
 
 
 @pytest.mark.parametrize("arity,per", [(4, 4 ** 6), (2, 2 ** 12)])
@@ -569,10 +460,4 @@ def test_v2_sorted_is_not_slower_than_unsorted(gpu_ctx):
 
 
 def test_cpp_mirror_on_gpu(gpu_ctx, oracle_mod, tmp_path):
-    exe = str(tmp_path / "test_forest_openings_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_openings_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0, out.stdout.decode() + out.stderr.decode()
+    run_cpp_mirror(build_cpp_mirror("test_forest_openings_api", tmp_path))

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from helpers.kernel_resources import kernel_resources
+from helpers.percall import bench_tool_parses, build_cpp_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
@@ -144,15 +145,8 @@ def test_stale_abi9_build_is_reported_by_name(tmp_path, monkeypatch):
 
 
 def test_cpp_mirror_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_forest_ragged_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_ragged_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_forest_ragged_api", tmp_path)
 
 
 def test_forest_ragged_bench_tool_parses():
-    import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_ragged_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--w2-trees" in r.stdout, r.stderr
+    bench_tool_parses("forest_ragged_bench", options=("--w2-trees",))

@@ -4,46 +4,15 @@ bad trees, streams, graph capture, openings of a tree's block, offsets past 4 Gi
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 import pytest
 
+from helpers.forest import _levels_bound, _median_ms, _mix, _np, _offsets, _tag, _torch
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _mix(arity):
-    a = arity
-    return [1, 2, 3, a, a + 1, a * a - 1, a * a, a * a + 1, 63, 65, (4 ** 5 + 1) if a == 4 else (2 ** 10 + 1)]
-
-
-def _offsets(sizes, start=0):
-    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
-    return off + np.uint64(start)
-
-
-def _tag(P, arity):
-    from poseidon252_amd import merkle as M
-    return M.merkle4_tag() if arity == 4 else M.merkle2_tag()
-
-
-def _torch(a, dev="cuda:0"):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)
-
-
-def _np(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def _levels_bound(n_leaves, n_trees, max_leaves, arity):
-    from poseidon252_amd import _lib
-    L = _lib.lib()
-    depth = (L.p252_merkle4_depth if arity == 4 else L.p252_merkle2_depth)(max_leaves)
-    return n_leaves // (arity - 1) + n_trees * depth
 
 
 def _device_forest(ctx, arity, d_leaves, d_off, n_trees, max_leaves, levels=False, bad=False, stream=None):
@@ -53,7 +22,7 @@ def _device_forest(ctx, arity, d_leaves, d_off, n_trees, max_leaves, levels=Fals
     d_lv = torch.zeros((max(_levels_bound(n_leaves, n_trees, max_leaves, arity), 1), 4), dtype=torch.int64,
                        device=d_leaves.device) if levels else None
     d_bad = torch.zeros(1, dtype=torch.int32, device=d_leaves.device) if bad else None
-    ctx.merkle_forest_ragged_device(_tag(None, arity), d_leaves, d_off, n_trees, max_leaves, roots, d_lv, d_bad, arity=arity)
+    ctx.merkle_forest_ragged_device(_tag(arity), d_leaves, d_off, n_trees, max_leaves, roots, d_lv, d_bad, arity=arity)
     return roots, d_lv, d_bad
 
 
@@ -69,7 +38,7 @@ def _single_tree_device(ctx, arity, d_leaves, lo, hi, levels=False):
     ll = (L.p252_merkle4_levels_len if arity == 4 else L.p252_merkle2_levels_len)(n)
     lv = torch.empty((max(ll, 1), 4), dtype=torch.int64, device=d_leaves.device) if levels else None
     fn = L.p252_merkle4_tree_device if arity == 4 else L.p252_merkle2_tree_device
-    tag = np.ascontiguousarray(_tag(None, arity), dtype=np.uint64)
+    tag = np.ascontiguousarray(_tag(arity), dtype=np.uint64)
     rc = fn(ctx._h, tag.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), d_leaves.data_ptr() + lo * 32, n, root.data_ptr(),
             lv.data_ptr() if levels else None, _stream(ctx))
     assert rc == 0, L.p252_last_error(ctx._h)
@@ -83,7 +52,7 @@ def test_oracle_parity_roots_and_levels(gpu_ctx, oracle_mod, arity):
     np.random.default_rng(arity).shuffle(sizes)
     off = _offsets(sizes)
     flat = oracle_mod.fill_random(0xF0 + arity, int(off[-1]))
-    tag = _tag(P, arity)
+    tag = _tag(arity)
     tree = oracle_mod.merkle4_tree if arity == 4 else oracle_mod.merkle2_tree
     roots, levels, lo = P.merkle_forest_ragged((flat, off), arity=arity, ctx=gpu_ctx, want_levels=True)
     assert roots.shape == (len(sizes), 4) and lo.shape == (len(sizes) + 1,) and levels.shape == (int(lo[-1]), 4)
@@ -165,7 +134,7 @@ def test_equal_sizes_equal_the_forest(gpu_ctx, oracle_mod, arity, k):
     flat = oracle_mod.fill_random(0xE0 + arity, per * n_trees)
     d = _torch(flat)
     exp = torch.empty((n_trees, 4), dtype=torch.int64, device=d.device)
-    gpu_ctx.merkle4_forest_device(_tag(None, arity), d, n_trees, per, exp, arity=arity)
+    gpu_ctx.merkle4_forest_device(_tag(arity), d, n_trees, per, exp, arity=arity)
     got, _, _ = _device_forest(gpu_ctx, arity, d, _torch(_offsets([per] * n_trees)), n_trees, per)
     assert torch.equal(got, exp)
 
@@ -185,7 +154,7 @@ def test_modes_agree_and_edge_calls(gpu_ctx, oracle_mod):
     assert np.array_equal(_np(d_lv)[:int(lo[-1])], host_lv)
     # n_trees = 0: nothing enqueued, the roots untouched
     keep = torch.full((1, 4), 7, dtype=torch.int64, device=d.device)
-    gpu_ctx.merkle_forest_ragged_device(_tag(None, 4), d, d_off, 0, 300, keep)
+    gpu_ctx.merkle_forest_ragged_device(_tag(4), d, d_off, 0, 300, keep)
     assert int(keep.sum()) == 28
     assert P.merkle_forest_ragged([], ctx=gpu_ctx).shape == (0, 4)
     # one tree equals the single-tree call
@@ -206,7 +175,7 @@ def test_bad_trees_on_the_device_and_the_host(gpu_ctx, oracle_mod):
     assert int(d_bad.item()) == 4
     for t in (1, 3, 5, 9):
         assert not roots[t].any(), t
-    tag = _tag(P, 4)
+    tag = _tag(4)
     lv_all = _np(d_lv)
     at = 0
     for t in sorted(good):
@@ -286,7 +255,7 @@ def test_graph_capture_replays_on_new_leaves(gpu_ctx, oracle_mod):
     d = _torch(oracle_mod.fill_random(0x61, n))
     d_off = _torch(off)
     roots = torch.zeros((len(sizes), 4), dtype=torch.int64, device=d.device)
-    tag = _tag(P, 4)
+    tag = _tag(4)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
         gpu_ctx.merkle_forest_ragged_device(tag, d, d_off, len(sizes), 1000, roots)  # warm-up: the stream's scratch
@@ -319,7 +288,7 @@ def test_tree_block_feeds_openings_and_verify(gpu_ctx, oracle_mod, arity):
         idx = torch.arange(n, dtype=torch.int32, device=d.device)
         out, sib, pos, depth = gpu_ctx.merkle4_openings_device(leaves_t, n, d_lv[int(lo[t]):int(lo[t + 1])], idx, n, check=True, arity=arity)
         ok = torch.zeros(n, dtype=torch.uint8, device=d.device)
-        gpu_ctx.merkle_verify_batch_device(_tag(None, arity), out, sib, pos, depth, roots[t], ok, n, arity=arity)
+        gpu_ctx.merkle_verify_batch_device(_tag(arity), out, sib, pos, depth, roots[t], ok, n, arity=arity)
         torch.cuda.synchronize()
         assert int(ok.sum()) == n, (arity, t)
 
@@ -339,21 +308,9 @@ def test_offsets_past_4_gib(gpu_ctx, oracle_mod):
     torch.cuda.empty_cache()
 
 
-def _median_ms(fn, reps):
-    import torch
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
-
-
 def test_relative_speed_floors(gpu_ctx):
     import torch
-    tag = _tag(None, 4)
+    tag = _tag(4)
     # W1: equal sizes, the ragged call against the equal-size forest, alternated in one process
     n_trees, per = 1024, 4 ** 6
     d = torch.randint(0, 1 << 60, (n_trees * per, 4), dtype=torch.int64, device="cuda:0")

@@ -6,14 +6,13 @@ byte, the digest count and the bad count; a pure rollback; clean nodes moved and
 a dirty list too wide for the lane groups across the scan tiles; composition with the append; openings of the result; graph capture;
 the C++ mirror."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from test_forest_append_gpu import SENTINEL, Grown, Old, _append, _fresh, _outputs, _tree
-from test_forest_openings_gpu import _depth, _np, _offsets, _open, _tag, _torch, _verify
+from helpers.forest import SENTINEL, Grown, Old, _append, _depth, _fresh, _np, _offsets, _open, _outputs, _tag, _torch, _tree, _verify
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
@@ -317,10 +316,4 @@ def test_graph_capture_replays_on_new_leaves_and_new_kept_counts(gpu_ctx, oracle
 
 # ---- 9. the C++ mirror ----
 def test_cpp_mirror_on_gpu(gpu_ctx, oracle_mod, tmp_path):
-    exe = str(tmp_path / "test_forest_resize_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_resize_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0, out.stdout.decode() + out.stderr.decode()
+    run_cpp_mirror(build_cpp_mirror("test_forest_resize_api", tmp_path))

@@ -3,11 +3,8 @@
 forest_update.hip compiles for gfx950 within its resource targets and includes the library's permutation instead of copying it;
 the Python mirror validates every buffer before it reaches the library; the numpy model of the dirty-node count that the GPU tests
 compare d_n_hashed with agrees with a brute-force set; the C++ mirror test compiles."""
-import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,30 +12,16 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_update_bench import dirty_nodes as dirty_count  # noqa: E402  (the numpy model of what one call may hash; checked below)
-from helpers.kernel_resources import kernel_resources  # noqa: E402
-from test_forest_openings_cpu import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
+from helpers.binding import _dev, recorder  # noqa: F401  (the stub library and the tensors that pass for device ones)
+from helpers.forest import dirty_count  # (the numpy model of what one call may hash; checked below)
+from helpers.kernel_resources import kernel_resources
+from helpers.percall import bench_tool_parses, build_cpp_mirror, check_abi_symbols
 
 ARGS = {"p252_merkle4_forest_ragged_update_device": 16, "p252_merkle2_forest_ragged_update_device": 16}
 
 
 def test_two_symbols_declared_exported_and_in_sys_rs():
-    from poseidon252_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
-    for name, n_args in ARGS.items():
-        m = re.search(r"\bint %s\s*\((.*?)\);" % name, header, flags=re.S)
-        assert m, name
-        assert m.group(1).count(",") + 1 == n_args, name
-        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
-        assert len(_lib.PROTOTYPES[name][0]) == n_args, name
-        assert rust[name].count(":") == n_args, (name, rust[name])
-    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
+    raw, _ = check_abi_symbols(ARGS)
     assert "no host-buffer twin" in raw  # the call acts on a forest that lives on the device, and the header says so
 
 
@@ -157,14 +140,8 @@ def test_dirty_count_model_agrees_with_a_brute_force_set():
 
 
 def test_cpp_mirror_test_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_forest_update_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_update_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_forest_update_api", tmp_path)
 
 
 def test_bench_tool_parses():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "forest_update_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--quick" in r.stdout, r.stderr
+    bench_tool_parses("forest_update_bench")

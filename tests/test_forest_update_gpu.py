@@ -5,85 +5,22 @@ of the changed leaves, streams, graph capture, p252_trim, a leaf buffer past 4 G
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 import pytest
 
-from test_forest_openings_gpu import _build, _depth, _levels_bound, _mix, _np, _offsets, _open, _tag, _torch, _verify
-from test_forest_update_cpu import dirty_count
+from helpers.forest import (SENTINEL, _build, _check_against_fresh_build, _depth, _distinct_pairs, _forest, _levels_bound, _median_ms, _mix, _np,
+                            _offsets, _open, _tag, _torch, _tree, _update, _verify, dirty_count)
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = -0x0123456789ABCDEF  # no scalar and no root has these limbs (the top limb is above the modulus')
 
 
 def _used(sizes, arity):
     from poseidon252_amd import levels_len
     return sum(levels_len(int(n), arity) for n in sizes if n > 0)
-
-
-def _tree(oracle_mod, arity):
-    return oracle_mod.merkle4_tree if arity == 4 else oracle_mod.merkle2_tree
-
-
-def _forest(ctx, arity, flat, off, max_leaves=None, tail=9):
-    """the forest on the device, built into a sentinel-filled d_levels with `tail` scalars past the bound -> (d, d_off, roots, d_lv)"""
-    import torch
-    sizes = np.diff(off.astype(np.int64))
-    n_trees = len(sizes)
-    max_leaves = max_leaves or int(sizes.max())
-    d, d_off = _torch(flat), _torch(off)
-    roots = torch.full((n_trees, 4), SENTINEL, dtype=torch.int64, device=d.device)
-    d_lv = torch.full((_levels_bound(flat.shape[0], n_trees, max_leaves, arity) + tail, 4), SENTINEL, dtype=torch.int64, device=d.device)
-    ctx.merkle_forest_ragged_device(_tag(arity), d, d_off, n_trees, max_leaves, roots, d_lv, None, arity=arity)
-    return d, d_off, roots, d_lv
-
-
-def _update(ctx, arity, d, d_off, n_trees, max_leaves, d_lv, tid, lid, new, d_roots=None):
-    """one update call -> (n_bad, n_hashed) as device tensors"""
-    import torch
-    k = len(tid)
-    bad = torch.zeros(1, dtype=torch.int32, device=d.device)
-    hashed = torch.zeros(1, dtype=torch.int64, device=d.device)
-    ctx.merkle_forest_ragged_update_device(_tag(arity), d, d_off, n_trees, max_leaves, d_lv, _torch(np.asarray(tid, np.uint32)),
-                                           _torch(np.asarray(lid, np.uint64)), _torch(new), k, d_roots=d_roots, d_n_bad=bad,
-                                           d_n_hashed=hashed, arity=arity)
-    return bad, hashed
-
-
-def _distinct_pairs(sizes, rng, k, trees=None):
-    """k distinct (tree, leaf) pairs of the trees `trees` (default: all), in random order"""
-    trees = np.arange(len(sizes)) if trees is None else np.asarray(trees)
-    tid = np.repeat(trees, np.asarray(sizes)[trees])
-    lid = np.concatenate([np.arange(sizes[t]) for t in trees])
-    pick = rng.choice(tid.size, size=min(k, tid.size), replace=False)
-    return tid[pick], lid[pick]
-
-
-def _check_against_fresh_build(ctx, oracle_mod, arity, flat, off, tid, lid, new, d, d_lv, d_roots, max_leaves=None):
-    """after an update of the valid (tid, lid) with `new`: leaves, the whole d_levels (sentinel tail included) and the roots of the
-    touched trees equal a fresh build of the modified leaves; every root equals the oracle's; untouched roots keep the sentinel"""
-    import torch
-    sizes = np.diff(off.astype(np.int64))
-    want = flat.copy()
-    want[off[tid].astype(np.int64) + np.asarray(lid, np.int64)] = new
-    assert np.array_equal(_np(d), want)
-    _, _, f_roots, f_lv = _forest(ctx, arity, want, off, max_leaves, tail=d_lv.shape[0] - _levels_bound(flat.shape[0], len(sizes),
-                                                                                                      max_leaves or int(sizes.max()), arity))
-    torch.cuda.synchronize()
-    assert torch.equal(d_lv, f_lv)
-    touched = np.zeros(len(sizes), bool)
-    touched[np.asarray(tid)] = True
-    got, fresh = _np(d_roots), _np(f_roots)
-    assert np.array_equal(got[touched], fresh[touched])
-    assert (got[~touched] == np.uint64(SENTINEL & (2 ** 64 - 1))).all()
-    tree = _tree(oracle_mod, arity)
-    for t in range(len(sizes)):
-        if sizes[t] > 0:
-            assert np.array_equal(fresh[t], tree(_tag(arity), want[int(off[t]):int(off[t + 1])])[0]), t
-    return want, fresh
 
 
 # ---- 1. parity ----
@@ -267,7 +204,7 @@ _CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
 import poseidon252_amd as P
-import test_forest_update_gpu as T
+from helpers import forest as T
 z = np.load(%(inp)r)
 arity = int(z["arity"])
 ctx = P.Context(0)
@@ -488,28 +425,10 @@ def test_leaf_buffer_past_4_gib(gpu_ctx, oracle_mod, arity):
 
 # ---- 9. the C++ mirror ----
 def test_cpp_mirror_on_gpu(gpu_ctx, oracle_mod, tmp_path):
-    exe = str(tmp_path / "test_forest_update_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_forest_update_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0, out.stdout.decode() + out.stderr.decode()
+    run_cpp_mirror(build_cpp_mirror("test_forest_update_api", tmp_path))
 
 
 # ---- 10. the speed floor ----
-def _median_ms(fn, reps):
-    import torch
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
-
-
 # U1 floor: 0.9 x the ratio measured on an MI355X for this size (profiles/forest_update.txt, "U1 4^11 leaves, k = 2^18": 2.590), rounded
 # down to two digits — the margin is for box-to-box clock spread, which a same-process alternated ratio mostly cancels.  Never
 # below 1.0: de-duplication that does not pay for its claim passes is not done.

@@ -4,10 +4,8 @@ under ABI 9; multiproof.hip compiles for gfx950 within its resource targets and 
 copying it; the numpy model of the format that the GPU tests compare the device's bytes with agrees with a brute-force set
 construction and, with the oracle's digest, reproduces the oracle's roots; the bound holds and is tight for one leaf; the Python
 mirror validates every buffer before it reaches the library; the C++ mirror test compiles."""
-import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -18,8 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 from multiproof_bench import multiproof_bound, multiproof_counts, multiproof_extract, multiproof_model, multiproof_root  # noqa: E402
+from helpers.binding import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
 from helpers.kernel_resources import kernel_resources  # noqa: E402
-from test_forest_openings_cpu import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
+from helpers.percall import bench_tool_parses, build_cpp_mirror, check_abi_symbols  # noqa: E402
 
 ARGS = {"p252_merkle4_multiproof_bound": 2, "p252_merkle2_multiproof_bound": 2,
         "p252_merkle4_multiproof_device": 12, "p252_merkle2_multiproof_device": 12,
@@ -28,24 +27,7 @@ SHAPES = [(4, n) for n in (1, 2, 4, 5, 16, 17, 21, 64, 1000)] + [(2, n) for n in
 
 
 def test_six_symbols_declared_exported_and_in_sys_rs():
-    from poseidon252_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "poseidon252_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"#define P252_ABI_VERSION 9\b", raw)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    rust = {m.group(1): m.group(2) for m in re.finditer(r"pub fn (p252_\w+)\((.*?)\)", sysrs)}
-    for name, n_args in ARGS.items():
-        m = re.search(r"\b(int|size_t) %s\s*\((.*?)\);" % name, header, flags=re.S)
-        assert m, name
-        assert (m.group(1) == "size_t") == name.endswith("_bound"), name
-        assert m.group(2).count(",") + 1 == n_args, name
-        assert hasattr(L, name) and name in _lib.ABI_SYMBOLS, name
-        assert len(_lib.PROTOTYPES[name][0]) == n_args, name
-        assert rust[name].count(":") == n_args, (name, rust[name])
-    assert _lib.lib().p252_abi_version() == 9 and _lib.ABI_VERSION == 9
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_rust_sys.py"), "--check"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    check_abi_symbols(ARGS)
 
 
 @pytest.fixture(scope="module")
@@ -217,14 +199,8 @@ def test_python_methods_validate_before_any_device_call(recorder, arity):
 
 
 def test_cpp_mirror_test_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_multiproof_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_multiproof_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_multiproof_api", tmp_path)
 
 
 def test_bench_tool_parses():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench_tools", "multiproof_bench.py"), "--help"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--quick" in r.stdout, r.stderr
+    bench_tool_parses("multiproof_bench")

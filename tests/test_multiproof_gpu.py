@@ -8,7 +8,8 @@ import sys
 import numpy as np
 import pytest
 
-from test_forest_openings_gpu import _np, _offsets, _tag, _torch
+from helpers.forest import SENTINEL, _build, _np, _offsets, _single_extract as _extract, _single_verify as _verify, _tag, _torch
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
@@ -16,7 +17,6 @@ from multiproof_bench import multiproof_counts, multiproof_extract, tree_device 
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -0x0123456789ABCDEF  # no scalar and no root has these limbs (the top limb is above the modulus')
 _TREES = {}
 
 
@@ -38,40 +38,6 @@ def _tree(ctx, arity, n):
         torch.cuda.synchronize()
         _TREES[(arity, n)] = (leaves, _np(d_lv)[:levels_len(n, arity)], _np(d_root), d, d_lv, d_root)
     return _TREES[(arity, n)]
-
-
-def _extract(ctx, arity, n, d, d_lv, pos, cap=None, pad=0):
-    """one extraction -> (leaves_out (k + pad, 4) numpy, the whole proof buffer (bound + pad, 4) numpy, proof_len, n_bad); the call
-    sees the first k rows / the first `cap` (default: bound) rows only, the rest holds the sentinel"""
-    import torch
-    k = len(pos)
-    bound = ctx.merkle_multiproof_bound(n, k, arity)
-    cap = bound if cap is None else cap
-    out = torch.full((k + pad, 4), SENTINEL, dtype=torch.int64, device=d.device)
-    proof = torch.full((bound + pad, 4), SENTINEL, dtype=torch.int64, device=d.device)
-    plen = torch.full((1,), -1, dtype=torch.int64, device=d.device)
-    bad = torch.zeros(1, dtype=torch.int32, device=d.device)
-    ctx.merkle_multiproof_device(d, n, d_lv if n > 1 else None, _torch(np.asarray(pos, np.uint32)), k, out[:k], proof[:cap] if cap else None,
-                                 plen, d_n_bad=bad, arity=arity)
-    ctx.sync()
-    return _np(out), _np(proof), int(plen), int(bad)
-
-
-def _verify(ctx, arity, n, pos, leaves, proof, proof_len, root):
-    """one verification of numpy inputs -> (ok, root_out numpy or None when untouched, n_hashed, n_bad)"""
-    import torch
-    dev = "cuda:0"
-    ok = torch.full((1,), 7, dtype=torch.uint8, device=dev)
-    root_out = torch.full((4,), SENTINEL, dtype=torch.int64, device=dev)
-    hashed = torch.full((1,), -1, dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    d_proof = _torch(np.ascontiguousarray(proof, dtype=np.uint64)) if len(proof) else None
-    ctx.merkle_multiproof_verify_device(_tag(arity), n, _torch(np.asarray(pos, np.uint32)), _torch(np.ascontiguousarray(leaves, dtype=np.uint64)),
-                                        len(pos), d_proof, proof_len, _torch(np.ascontiguousarray(root, dtype=np.uint64)), ok,
-                                        d_root_out=root_out, d_n_hashed=hashed, d_n_bad=bad, arity=arity)
-    ctx.sync()
-    r = _np(root_out)
-    return int(ok), (None if (r == np.uint64(SENTINEL & (2 ** 64 - 1))).all() else r), int(hashed), int(bad)
 
 
 def _round_trip(ctx, arity, n, pos):
@@ -259,7 +225,6 @@ def test_another_stream_and_a_trimmed_context_give_the_same(gpu_ctx, arity):
 def test_a_tree_block_of_a_ragged_forest_is_a_single_tree(gpu_ctx, oracle_mod, arity):
     import torch
     from poseidon252_amd import levels_len
-    from test_forest_openings_gpu import _build
     sizes = [5, 300, 1, 17, 66]
     off = _offsets(sizes).astype(np.int64)
     lo = np.concatenate([[0], np.cumsum([levels_len(s, arity) for s in sizes])])
@@ -295,11 +260,4 @@ def test_the_convenience_calls_sort_and_de_duplicate(gpu_ctx, arity):
 
 
 def test_cpp_mirror_on_gpu(gpu_ctx, oracle_mod, tmp_path):
-    import subprocess
-    exe = str(tmp_path / "test_multiproof_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_multiproof_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0, out.stdout.decode() + out.stderr.decode()
+    run_cpp_mirror(build_cpp_mirror("test_multiproof_api", tmp_path))

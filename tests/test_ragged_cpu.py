@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers.percall import build_cpp_mirror
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
 RAGGED = ("p252_hash_ragged", "p252_hash_ragged_truncated", "p252_hash_ragged_device", "p252_hash_ragged_truncated_device")
@@ -118,12 +120,7 @@ def test_ragged_call_without_gpu_raises_device_error():
 
 
 def test_cpp_mirror_compiles(tmp_path, oracle_mod):
-    exe = str(tmp_path / "test_ragged_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_ragged_api.cpp"), "-L", os.path.join(ROOT, "poseidon252_amd"),
-                           "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle", "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"),
-                           "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    assert os.path.exists(exe)
+    build_cpp_mirror("test_ragged_api", tmp_path)
 
 
 def test_ragged_bench_tool_parses():

@@ -8,6 +8,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers.percall import build_cpp_mirror, run_cpp_mirror
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -275,9 +277,4 @@ def test_sorted_schedule_pays(gpu_ctx):
 
 
 def test_cpp_mirror_on_gpu(tmp_path, oracle_mod, gpu_ctx):
-    exe = str(tmp_path / "test_ragged_api")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_ragged_api.cpp"),
-                           "-L", os.path.join(ROOT, "poseidon252_amd"), "-lposeidon252_hip", "-L", os.path.join(ROOT, "oracle"), "-lp252_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "poseidon252_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, timeout=600)
-    assert out.returncode == 0 and b"ALL PASSED" in out.stdout, out.stdout.decode() + out.stderr.decode()
+    assert "ALL PASSED" in run_cpp_mirror(build_cpp_mirror("test_ragged_api", tmp_path, flags=()))

@@ -11,17 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+from helpers.forest import _np as _host, _torch as _dev
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).to("cuda:0")
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 # ---------------------------------------------------------------------------------------------- item 2: streams of ONE context

@@ -1,7 +1,7 @@
 """The shape lists of tests/shapecases.py, without a GPU: that they reach every class of the kernels' shape-dependent branching (proved
 against the dispatch model, as EQUALITIES with the class sets written out here: a list that shrinks fails), that the model's
 cipher walk is the state machine the big-integer sponge runs, and that the oracle is right at every shape the sweep compares the
-kernels with (against the big-integer restatements of tests/pymodel.py and tests/test_encryption.py)."""
+kernels with (against the big-integer restatements of tests/pymodel.py)."""
 import itertools
 import os
 
@@ -127,7 +127,7 @@ def test_cipher_classes_are_all_reached():
 
 
 def test_cipher_program_is_the_io_pattern_of_the_bigint_machine():
-    import test_encryption as T
+    import pymodel as T
     for v, ln in S.CRYPT_CASES:
         assert [("A" if k in (0, 1, 3) else "S", c) for k, c in S.crypt_program(v, ln)] == T._io_pattern(v, ln)
 
@@ -196,7 +196,7 @@ def test_oracle_sponge_matches_the_bigint_sponge_at_every_shape(oracle_mod, perm
 
 
 def test_oracle_encryption_matches_the_bigint_machine_at_every_case(oracle_mod, perm):
-    """every (variant, len) of the sweep: the oracle's encrypt against the big-integer state machine of tests/test_encryption.py, whose
+    """every (variant, len) of the sweep: the oracle's encrypt against the big-integer state machine of tests/pymodel.py, whose
     count of permutations is the dispatch model's"""
     f = oracle_mod.int_from_mont
     for variant, ln in S.CRYPT_CASES:

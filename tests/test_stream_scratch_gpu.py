@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_forest_openings_gpu import _depth, _offsets, _tag, _torch
+from helpers.forest import _depth, _offsets, _tag, _torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
