@@ -22,6 +22,7 @@
 //                                                   merkle_forest_ragged_journal_bound: such updates undone and redone, no hashing
 //   —                                               merkle_forest_ragged_append_device: leaves appended to its trees, into a new forest
 //   —                                               merkle_forest_ragged_resize_device: its trees cut, then appended to; trailing trees dropped
+//   —                                               merkle_forest_ragged_select_device: any of its trees (and another forest's) gathered into a new forest
 //   —                                               merkle_multiproof_device / merkle_multiproof_verify_device /
 //                                                   merkle_multiproof_bound: many leaves of one tree, one shared proof
 //   —                                               merkle_forest_ragged_multiproof_device / _verify_device / _bound: leaves of many
@@ -434,7 +435,7 @@ namespace detail {
     X(N, levels_len) X(N, depth) X(N, forest_ragged) X(N, forest_ragged_device) X(N, forest_ragged_openings_device) X(N, path_ragged_device) \
     X(N, forest_ragged_verify_device) X(N, forest_ragged_update_device) X(N, forest_ragged_append_device_into) X(N, multiproof_bound)        \
     X(N, forest_ragged_resize_device_into) X(N, forest_ragged_journal_bound) X(N, forest_ragged_update_journaled_device_into)                    \
-    X(N, forest_ragged_journal_swap_device_into)                                                                                             \
+    X(N, forest_ragged_journal_swap_device_into) X(N, forest_ragged_select_device_into)                                                      \
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
     X(N, forest_ragged_multiproof_verify_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
@@ -641,6 +642,30 @@ inline void merkle_forest_ragged_resize_device(const ForestView& old_forest, con
                                                      resized.d_offsets, resized.d_levels, resized.levels_cap, resized.d_roots, d_n_bad, d_n_hashed,
                                                      stream),
                   ctx.get(), "merkle_forest_ragged_resize_device");
+}
+
+// Any trees of one or two such forests gathered INTO a new compact forest, with no digest (p252_merkle{4,2}_forest_ragged_select_device_into):
+// `a` and `b` exactly as their builds took and filled them, with their n_trees roots (read-only; b may be nullptr).  d_pick = n_pick
+// device uint64: below a.n_trees a tree of a, then a tree of b; any order, repeats allowed.  `picked` names the caller's output buffers
+// and their capacities in scalars (levels_cap >= forest_append_levels_cap(leaves_cap, n_pick, max of the two max_leaves)): afterwards
+// they hold byte for byte a fresh build of the new forest.  A pick out of range, of a bad tree, or past leaves_cap (and every non-empty
+// one behind it) becomes an empty tree — a zero root, no storage — and is counted in *d_n_bad (device uint32, zeroed by the caller).
+struct ForestSource {
+    ForestView forest;
+    const void* d_roots;
+};
+inline void merkle_forest_ragged_select_device(const ForestSource& a, const ForestSource* b, const void* d_pick, std::size_t n_pick,
+                                               const ForestOut& picked, unsigned arity = 4, Context& ctx = Context::default_context(),
+                                               void* d_n_bad = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_select_device", arity);
+    const ForestSource none{{nullptr, 0, nullptr, 0, 0, nullptr}, nullptr};
+    const ForestSource& s = b ? *b : none;
+    detail::check(m.forest_ragged_select_device_into(ctx.get(), a.forest.d_leaves, a.forest.n_leaves, a.forest.d_offsets, a.forest.n_trees,
+                                                     a.forest.max_leaves, a.forest.d_levels, a.d_roots, s.forest.d_leaves, s.forest.n_leaves,
+                                                     s.forest.d_offsets, s.forest.n_trees, s.forest.max_leaves, s.forest.d_levels, s.d_roots, d_pick,
+                                                     n_pick, picked.d_leaves, picked.leaves_cap, picked.d_offsets, picked.d_levels,
+                                                     picked.levels_cap, picked.d_roots, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_select_device");
 }
 
 // Many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_*; the format is in poseidon252_hip.h).

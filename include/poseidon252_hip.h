@@ -112,6 +112,8 @@ extern "C" {
  *      forest, written as a new compact forest; unchanged nodes are moved, not hashed again;
  *      + p252_merkle{4,2}_forest_ragged_resize_device_into (additive, same version): the same after each tree was cut to its
  *      first k_t leaves, trailing trees dropped: a rollback, a reorg or a prune without a rebuild;
+ *      + p252_merkle{4,2}_forest_ragged_select_device_into (additive, same version): any trees of one or two such forests
+ *      gathered into a new compact forest, in any order, with no digest: a prune in the middle, a merge, a split, a reorder;
  *      + p252_merkle{4,2}_forest_ragged_multiproof_bound, _multiproof_device_into, _multiproof_verify_device_into (additive, same
  *      version; `_into` as the append: every result goes into buffers the caller owns):
  *      leaves of many trees of such a forest behind one tree-major shared proof, each ancestor hashed once */
@@ -629,6 +631,52 @@ int p252_merkle2_forest_ragged_resize_device_into(p252_ctx* ctx, const uint64_t 
                                                   size_t n_trees_new, size_t max_leaves_new, void* d_leaves_new, size_t leaves_cap,
                                                   void* d_offsets_new, void* d_levels_new, size_t levels_cap, void* d_roots, void* d_n_bad,
                                                   void* d_n_hashed, void* hip_stream);
+
+/* Any trees of one or two BUILT forests gathered into a new compact forest, in any order: a tree pruned in the middle (the trees
+ * behind it renumbered), a freshly built batch merged into the stored forest, a forest split into shards or reordered.  A tree's
+ * tree-major block depends on its own leaves only — it holds byte for byte what p252_merkle{4,2}_tree writes for it alone — so NOTHING
+ * IS HASHED and there is no tag: leaves, level blocks and roots are relocated at memory speed; the arity only selects the layout
+ * (p252_merkle{4,2}_levels_len).
+ * Sources A and B (read-only): each exactly what p252_merkle{4,2}_forest_ragged_device was given and filled — d_leaves, n_leaves,
+ * d_offsets, n_trees, max_leaves, the tree-major d_levels and the n_trees d_roots.  Each source's leaf counts and block starts are
+ * recomputed with the build's own validation, so a bad tree means here what it means there.  B is optional: with n_trees_b == 0 its
+ * other six arguments may be 0 / NULL.  d_levels_x may be NULL when max_leaves_x <= 1.
+ * d_pick = n_pick uint64 (device, 8-byte aligned): new tree j is tree d_pick[j] of A when the id is below n_trees_a, tree d_pick[j] -
+ * n_trees_a of B when it is below n_trees_a + n_trees_b; any order, any tree any number of times.  A pick is REFUSED when its id is
+ * >= n_trees_a + n_trees_b, when it names a tree its source's build calls bad, or when — with s_j the leaf count of pick j, 0 for
+ * those two — s_0 + .. + s_j exceeds leaves_cap: once the running sum passes the cap every later non-empty pick is refused as well
+ * (one scan decides it, and the device stays inside leaves_cap whatever the list holds).  A refused pick is an empty tree of the new
+ * forest — a zero root, no storage, its position j kept — and counts once in *d_n_bad (device uint32 the caller has zeroed; may be
+ * NULL).
+ * Outputs (device): d_offsets_new[0] = 0, d_offsets_new[j + 1] = d_offsets_new[j] + n_j (n_pick + 1 uint64); d_leaves_new, the used
+ * part of d_levels_new and d_roots_new[n_pick] are the picked trees' leaves, level blocks and roots byte for byte, hence byte for
+ * byte what a fresh p252_merkle{4,2}_forest_ragged_device(d_leaves_new, leaves_cap, d_offsets_new, n_pick, max(max_leaves_a,
+ * max_leaves_b), ..) writes: an ordinary forest that every other call takes unchanged.  Nothing at or past the used lengths is
+ * written.  P252_ERR_INVALID_ARGUMENT, nothing enqueued: n_trees_a == 0, leaves_cap == 0, levels_cap < leaves_cap / (A - 1) + n_pick *
+ * depth(max(max_leaves_a, max_leaves_b)), a NULL or misaligned buffer (scalars 16 bytes, offsets and picks 8, d_n_bad 4; d_levels_new
+ * may be NULL when both max_leaves are <= 1), size overflow, or any output range that overlaps an input range or another output
+ * range (all sizes are known on the host).  n_pick == 0 -> P252_OK, nothing enqueued.  Asynchronous on hip_stream: no host
+ * synchronisation, no allocation once the scratch is warm, no memset node — it can be captured into a hipGraph.  Scratch, in the
+ * context's pair of THIS stream (p252_trim / p252_wipe cover it), ids and counts only: 16 bytes per tree of A, of B and of the new
+ * forest for the indices, 8 bytes per pick, 8 bytes per 512 scalars of the two capacities.  Cost: about 30 small launches and two
+ * relocation launches that are balanced over 512-scalar tiles of the NEW arrays, not over trees.  Measured
+ * (profiles/forest_select.txt) against a fresh build of the same new forest and a hipMemcpyDtoDAsync of the same bytes in the same
+ * run: 20,000 mixed trees (34 M leaves) kept, 1 % dropped, permuted or merged from two halves in 0.65-0.71 ms, 34-37x ahead of the
+ * build, 4.1-4.4 TB/s read + written, 0.78-0.84 of the copy's rate; one 4^12-leaf tree 0.34 ms, 38x (arity 2, 2^24 leaves: 0.46 ms,
+ * 80x).  There is no host-buffer twin. */
+int p252_merkle4_forest_ragged_select_device_into(p252_ctx* ctx, const void* d_leaves_a, size_t n_leaves_a, const void* d_offsets_a,
+                                                  size_t n_trees_a, size_t max_leaves_a, const void* d_levels_a, const void* d_roots_a,
+                                                  const void* d_leaves_b, size_t n_leaves_b, const void* d_offsets_b, size_t n_trees_b,
+                                                  size_t max_leaves_b, const void* d_levels_b, const void* d_roots_b, const void* d_pick,
+                                                  size_t n_pick, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                                  void* d_levels_new, size_t levels_cap, void* d_roots_new, void* d_n_bad, void* hip_stream);
+/* the same for arity 2 (the level layout of p252_merkle2_levels_len) */
+int p252_merkle2_forest_ragged_select_device_into(p252_ctx* ctx, const void* d_leaves_a, size_t n_leaves_a, const void* d_offsets_a,
+                                                  size_t n_trees_a, size_t max_leaves_a, const void* d_levels_a, const void* d_roots_a,
+                                                  const void* d_leaves_b, size_t n_leaves_b, const void* d_offsets_b, size_t n_trees_b,
+                                                  size_t max_leaves_b, const void* d_levels_b, const void* d_roots_b, const void* d_pick,
+                                                  size_t n_pick, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                                  void* d_levels_new, size_t levels_cap, void* d_roots_new, void* d_n_bad, void* hip_stream);
 
 /* ---- many leaves of ONE tree behind one shared proof.  The tree is what p252_merkle{4,2}_tree_device stored (d_leaves + d_levels;
  * one tree block of a ragged forest is the same layout); only the proof object is new.  The per-leaf openings above write

@@ -108,6 +108,8 @@ PROTOTYPES = {
     "p252_merkle2_forest_ragged_append_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
     "p252_merkle4_forest_ragged_resize_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
     "p252_merkle2_forest_ragged_resize_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp),
+    "p252_merkle4_forest_ragged_select_device_into": _f(_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp),
+    "p252_merkle2_forest_ragged_select_device_into": _f(_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp),
     "p252_merkle4_multiproof_bound": _f(_sz, _sz, ret=_sz),
     "p252_merkle2_multiproof_bound": _f(_sz, _sz, ret=_sz),
     "p252_merkle4_multiproof_device": _f(_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp),

@@ -1075,6 +1075,102 @@ int p252_merkle2_forest_ragged_resize_device_into(p252_ctx* ctx, const uint64_t 
                                             levels_cap, d_roots, d_n_bad, d_n_hashed, hip_stream);
 }
 
+// ---- any trees of one or two built forests gathered into a new compact forest (the select of forest_ragged.hip): a prune in the
+// middle, a merge, a split, a reorder.  Nothing is hashed, so there is no tag.  The scratch — the indices of A, B and the new forest,
+// one count per pick, the first-tree rows of the relocation tiles — is the pair of the calling stream; there is no host-buffer twin ----
+static int forest_ragged_select_device_into(p252_ctx* ctx, unsigned arity, const void* d_leaves_a, size_t n_leaves_a, const void* d_offsets_a,
+                                            size_t n_trees_a, size_t max_leaves_a, const void* d_levels_a, const void* d_roots_a,
+                                            const void* d_leaves_b, size_t n_leaves_b, const void* d_offsets_b, size_t n_trees_b,
+                                            size_t max_leaves_b, const void* d_levels_b, const void* d_roots_b, const void* d_pick,
+                                            size_t n_pick, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new, void* d_levels_new,
+                                            size_t levels_cap, void* d_roots_new, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = "merkle_forest_ragged_select";
+    if (n_trees_a == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_trees_a must be > 0");
+    if (n_pick == 0) return P252_OK;
+    if (n_trees_b == 0) {  // B absent: nothing of it is read
+        d_leaves_b = d_offsets_b = d_levels_b = d_roots_b = nullptr;
+        n_leaves_b = max_leaves_b = 0;
+    }
+    if (n_leaves_a == 0 || max_leaves_a == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves_a and max_leaves_a must be > 0");
+    if (n_trees_b && (n_leaves_b == 0 || max_leaves_b == 0))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves_b and max_leaves_b must be > 0");
+    if (leaves_cap == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": leaves_cap must be > 0");
+    const size_t max_leaves = max_leaves_a > max_leaves_b ? max_leaves_a : max_leaves_b;
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves_a, n_trees_a, max_leaves_a)) return rc;  // (the build's own limits, all three)
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves_b, n_trees_b, max_leaves_b)) return rc;
+    if (int rc = forest_shape_check(ctx, who.c_str(), leaves_cap, n_pick, max_leaves)) return rc;
+    // the picks' counts, summed on the device before the cap rule cuts them, stay below 2^63
+    const size_t eff_a = max_leaves_a < n_leaves_a ? max_leaves_a : n_leaves_a, eff_b = max_leaves_b < n_leaves_b ? max_leaves_b : n_leaves_b;
+    if (n_trees_a > SIZE_MAX - n_trees_b || n_pick > (SIZE_MAX / 2) / (eff_a > eff_b ? eff_a : eff_b) || levels_cap > SIZE_MAX / 64)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const size_t levels_need = leaves_cap / (arity - 1) + n_pick * forest_ragged_depth(max_leaves, arity);
+    if (levels_cap < levels_need)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": levels_cap must be >= leaves_cap / (arity - 1) + n_pick * depth(max_leaves)");
+    if (!d_leaves_a || !d_offsets_a || !d_roots_a || (max_leaves_a > 1 && !d_levels_a))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer of forest A");
+    if (n_trees_b && (!d_leaves_b || !d_offsets_b || !d_roots_b || (max_leaves_b > 1 && !d_levels_b)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer of forest B");
+    if (!d_pick) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL d_pick");
+    if (!d_leaves_new || !d_offsets_new || !d_roots_new || (max_leaves > 1 && !d_levels_new))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL output buffer");
+    if (misaligned(d_leaves_a) || misaligned(d_levels_a) || misaligned(d_roots_a) || misaligned(d_leaves_b) || misaligned(d_levels_b) ||
+        misaligned(d_roots_b) || misaligned(d_leaves_new) || misaligned(d_levels_new) || misaligned(d_roots_new))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets_a, 8) || misaligned_to(d_offsets_b, 8) || misaligned_to(d_pick, 8) || misaligned_to(d_offsets_new, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets_a, d_offsets_b, d_pick and d_offsets_new must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
+    const size_t levels_a = n_leaves_a / (arity - 1) + n_trees_a * forest_ragged_depth(max_leaves_a, arity);
+    const size_t levels_b = n_leaves_b / (arity - 1) + n_trees_b * forest_ragged_depth(max_leaves_b, arity);
+    const ByteRange in[] = {{d_leaves_a, n_leaves_a * 32, "d_leaves_a"}, {d_offsets_a, (n_trees_a + 1) * 8, "d_offsets_a"},
+                            {d_levels_a, levels_a * 32, "d_levels_a"},   {d_roots_a, n_trees_a * 32, "d_roots_a"},
+                            {d_leaves_b, n_leaves_b * 32, "d_leaves_b"}, {d_offsets_b, n_trees_b ? (n_trees_b + 1) * 8 : 0, "d_offsets_b"},
+                            {d_levels_b, levels_b * 32, "d_levels_b"},   {d_roots_b, n_trees_b * 32, "d_roots_b"},
+                            {d_pick, n_pick * 8, "d_pick"}};
+    const ByteRange out[] = {{d_leaves_new, leaves_cap * 32, "d_leaves_new"}, {d_offsets_new, (n_pick + 1) * 8, "d_offsets_new"},
+                             {d_levels_new, levels_cap * 32, "d_levels_new"}, {d_roots_new, n_pick * 32, "d_roots_new"},
+                             {d_n_bad, 4, "d_n_bad"}};
+    for (size_t o = 0; o < sizeof(out) / sizeof(out[0]); ++o) {
+        for (const ByteRange& i : in)
+            if (ranges_overlap(out[o], i)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + out[o].name + " overlaps " + i.name);
+        for (size_t q = 0; q < o; ++q)
+            if (ranges_overlap(out[o], out[q])) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + out[o].name + " overlaps " + out[q].name);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    ForestSelectSource A, B;
+    A.leaves = d_leaves_a, A.offsets = d_offsets_a, A.levels = d_levels_a, A.roots = d_roots_a;
+    A.n_leaves = n_leaves_a, A.n_trees = n_trees_a, A.max_leaves = max_leaves_a;
+    B.leaves = d_leaves_b, B.offsets = d_offsets_b, B.levels = d_levels_b, B.roots = d_roots_b;
+    B.n_leaves = n_leaves_b, B.n_trees = n_trees_b, B.max_leaves = max_leaves_b;
+    const ForestSelectPlan plan = forest_select_plan(arity, n_trees_a, n_trees_b, max_leaves, n_pick, leaves_cap);
+    return with_stream_scratch(ctx, who, st, plan.meta_bytes(), 0, [&](p252_ctx::LevelSet& set) {
+        return launch_forest_select(plan, A, B, d_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new, d_n_bad, set.buf[0], st);
+    });
+}
+
+int p252_merkle4_forest_ragged_select_device_into(p252_ctx* ctx, const void* d_leaves_a, size_t n_leaves_a, const void* d_offsets_a,
+                                                  size_t n_trees_a, size_t max_leaves_a, const void* d_levels_a, const void* d_roots_a,
+                                                  const void* d_leaves_b, size_t n_leaves_b, const void* d_offsets_b, size_t n_trees_b,
+                                                  size_t max_leaves_b, const void* d_levels_b, const void* d_roots_b, const void* d_pick,
+                                                  size_t n_pick, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                                  void* d_levels_new, size_t levels_cap, void* d_roots_new, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_select_device_into(ctx, 4, d_leaves_a, n_leaves_a, d_offsets_a, n_trees_a, max_leaves_a, d_levels_a, d_roots_a, d_leaves_b,
+                                            n_leaves_b, d_offsets_b, n_trees_b, max_leaves_b, d_levels_b, d_roots_b, d_pick, n_pick, d_leaves_new,
+                                            leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots_new, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_select_device_into(p252_ctx* ctx, const void* d_leaves_a, size_t n_leaves_a, const void* d_offsets_a,
+                                                  size_t n_trees_a, size_t max_leaves_a, const void* d_levels_a, const void* d_roots_a,
+                                                  const void* d_leaves_b, size_t n_leaves_b, const void* d_offsets_b, size_t n_trees_b,
+                                                  size_t max_leaves_b, const void* d_levels_b, const void* d_roots_b, const void* d_pick,
+                                                  size_t n_pick, void* d_leaves_new, size_t leaves_cap, void* d_offsets_new,
+                                                  void* d_levels_new, size_t levels_cap, void* d_roots_new, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_select_device_into(ctx, 2, d_leaves_a, n_leaves_a, d_offsets_a, n_trees_a, max_leaves_a, d_levels_a, d_roots_a, d_leaves_b,
+                                            n_leaves_b, d_offsets_b, n_trees_b, max_leaves_b, d_levels_b, d_roots_b, d_pick, n_pick, d_leaves_new,
+                                            leaves_cap, d_offsets_new, d_levels_new, levels_cap, d_roots_new, d_n_bad, hip_stream);
+}
+
 // (the host-buffer entry points — caller memory in, results back, synchronous — are in host_io.cpp)
 
 // page-locked host memory for callers that want the host-buffer entry points at PCIe speed

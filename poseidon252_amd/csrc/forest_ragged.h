@@ -1,6 +1,7 @@
 // forest_ragged.h — launch interface between api.cpp and forest_ragged.hip: a forest of Merkle trees of DIFFERENT sizes in one
 // call (p252_merkle{4,2}_forest_ragged*).  Tree t = leaves[offsets[t] .. offsets[t+1]); each tree is exactly what
 // p252_merkle{4,2}_tree builds (levels zero-padded to a multiple of the arity, a single leaf is its own root).
+// Also the select of such forests (p252_merkle{4,2}_forest_ragged_select_device_into): trees gathered into a new forest, nothing hashed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,5 +44,36 @@ hipError_t launch_forest_ragged(const int32_t* tab, const TagArg& tag, const For
 size_t forest_ragged_index_bytes(size_t n_trees);
 hipError_t launch_forest_ragged_index(unsigned arity, const void* offsets, size_t n_trees, size_t n_leaves, size_t max_leaves, void* meta,
                                       const uint64_t** ntree, const uint64_t** lo, hipStream_t st);
+
+// Trees of one or two BUILT forests gathered into a new compact forest (p252_merkle{4,2}_forest_ragged_select_device_into): nothing is
+// hashed, leaves, level blocks and roots move.  The relocation is balanced over tiles of FOREST_SELECT_MOVE_TILE scalars of the new
+// arrays, not over trees.
+constexpr unsigned FOREST_SELECT_MOVE_TILE = 512;
+
+// one source forest, as its build was given and filled it (n_trees == 0: absent, nothing of it is read)
+struct ForestSelectSource {
+    const void* leaves = nullptr;
+    const void* offsets = nullptr;
+    const void* levels = nullptr;
+    const void* roots = nullptr;
+    size_t n_leaves = 0, n_trees = 0, max_leaves = 0;
+};
+
+struct ForestSelectPlan {
+    unsigned arity = 4, depth = 0;  // depth of a tree of max_leaves leaves
+    size_t n_pick = 0, leaves_cap = 0, max_leaves = 0;  // max_leaves: the larger of the two sources'
+    size_t nodes = 0;  // the bound on the new levels: leaves_cap / (arity - 1) + n_pick * depth
+    size_t tiles = 0, leaf_tiles = 0, node_tiles = 0;
+    size_t index_a_bytes = 0, index_b_bytes = 0, index_new_bytes = 0, work_bytes = 0;
+    size_t meta_bytes() const { return index_a_bytes + index_b_bytes + index_new_bytes + work_bytes; }
+};
+ForestSelectPlan forest_select_plan(unsigned arity, size_t n_trees_a, size_t n_trees_b, size_t max_leaves, size_t n_pick, size_t leaves_cap);
+
+// The whole select on `st`: the indices of A, B and the new forest, the two scans over the picks (the cap rule, d_offsets_new), the
+// relocation, the roots.  pick = n_pick uint64 ids (below A.n_trees: of A; then of B); meta = plan.meta_bytes() of scratch, ids and
+// counts only.  n_bad (device uint32, may be null) is incremented once per refused pick, whose root is written as zero.
+hipError_t launch_forest_select(const ForestSelectPlan& plan, const ForestSelectSource& A, const ForestSelectSource& B, const void* pick,
+                                void* leaves_new, void* offsets_new, void* levels_new, void* roots_new, void* n_bad, void* meta,
+                                hipStream_t st);
 
 }  // namespace p252

@@ -28,6 +28,8 @@
 // written out in k_fr_digest and again in k_fu_digest (through a shared function both come out with other instruction streams:
 // profiles/forest_kernels_refactor.txt), and hades_permute_coop<8> for levels that cannot fill the chip (the coop8 rule of
 // kernels.h) — node_digest_coop of forest_node.hpp, which holds what the three forest files share.
+// The unit also holds the SELECT (p252_merkle{4,2}_forest_ragged_select_device_into): trees of built forests gathered into a new forest
+// with no digest — k_fr_sel_*, data movement and bookkeeping only, described above its kernels below.
 #include <hip/hip_runtime.h>
 
 #include "blockops.hpp"
@@ -238,6 +240,111 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_roots_from_levels(const uint64_
 }
 
 // ---------------------------------------------------------------------------------------------
+// the select: trees of one or two BUILT forests gathered into a new compact forest (p252_merkle{4,2}_forest_ragged_select_device_into).
+// A tree's tree-major block holds what its own leaves give and nothing else, so nothing is hashed: leaves, level blocks and roots move.
+//   k_fr_sel_sizes       per pick j: the leaf count s_j of the tree it names in A or B (0: an id out of range, a bad tree)
+//   (k_fr_tile_sums / k_fr_scan_tiles / k_fr_scan_apply<true> over s_j with n_leaves = leaves_cap: the build's sum rule IS the cap
+//    rule — a pick whose running sum passes leaves_cap is refused, and so is every later non-empty one)
+//   k_fr_sel_offsets     the scan of the accepted counts: d_offsets_new
+//   (launch_forest_ragged_index on d_offsets_new: the new forest's leaf counts and block starts are the build's own)
+//   k_fr_sel_tile_first  per 512-scalar tile of the new leaves / of the new levels: the tree that holds its first scalar
+//   k_fr_sel_move        one lane per 16-byte half of four scalars of the new array (leaves, then levels): its tree between the first
+//                        trees of its tile and of the next, then the same place of the picked tree's block in its source
+//   k_fr_sel_roots       the picked trees' roots; zero, and one count in *n_bad, for a refused pick
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr unsigned FRS_MOVE = 2 * FOREST_SELECT_MOVE_TILE / FR_BLOCK;  // 16-byte halves per lane of a relocation block
+
+// the picked trees' starts (of their leaves, or of their level blocks) and the array they index, in either source
+struct FrSelSrc {
+    const uint64_t* start_a;
+    const uint64_t* start_b;
+    const uint4* data_a;
+    const uint4* data_b;
+    uint64_t n_trees_a;
+};
+}  // namespace
+
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_sel_sizes(const uint64_t* __restrict__ pick, size_t n_pick, const uint64_t* __restrict__ ntree_a,
+                                                           uint64_t n_trees_a, const uint64_t* __restrict__ ntree_b, uint64_t n_trees_b,
+                                                           uint64_t* __restrict__ count) {
+    const size_t j = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
+    if (j >= n_pick) return;
+    const uint64_t id = pick[j];
+    uint64_t n = 0;
+    if (id < n_trees_a)
+        n = ntree_a[id];
+    else if (id - n_trees_a < n_trees_b)
+        n = ntree_b[id - n_trees_a];
+    count[j] = n;
+}
+
+// out[j] = the accepted counts before pick j, out[n_pick] = their total (tsum: the tile sums of `count`, scanned)
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_sel_offsets(const uint64_t* __restrict__ count, size_t n_pick, const uint64_t* __restrict__ tsum,
+                                                             uint64_t* __restrict__ out) {
+    const size_t t0 = (size_t)blockIdx.x * FR_TILE + (size_t)threadIdx.x * FR_ITEMS;
+    uint64_t v[FR_ITEMS], sum = 0;
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k) {
+        v[k] = t0 + k < n_pick ? count[t0 + k] : 0ull;
+        sum += v[k];
+    }
+    uint64_t total;
+    uint64_t run = tsum[blockIdx.x] + block_exclusive<FR_BLOCK>(sum, &total);
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k) {
+        const size_t t = t0 + k;
+        if (t >= n_pick) break;
+        out[t] = run;
+        run += v[k];
+        if (t == n_pick - 1) out[n_pick] = run;
+    }
+}
+
+// the tree that holds scalar FOREST_SELECT_MOVE_TILE * b of B (n_trees + 1 starts): the largest t < n_trees with B[t] <= it
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_sel_tile_first(const uint64_t* __restrict__ B, size_t n_trees, size_t entries,
+                                                                uint64_t* __restrict__ first) {
+    const size_t b = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
+    if (b >= entries) return;
+    first[b] = last_at_or_below(B, 0, n_trees - 1, (uint64_t)b * FOREST_SELECT_MOVE_TILE);  // (B[0] = 0)
+}
+
+// scalar s of the new array lies in new tree t (a pick that was accepted: only those have scalars), at s - B[t] of its block
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_sel_move(const uint64_t* __restrict__ B, size_t n_pick, const uint64_t* __restrict__ first,
+                                                          const uint64_t* __restrict__ pick, FrSelSrc S, uint4* __restrict__ out) {
+    const uint64_t total = B[n_pick];
+    const size_t lo = first[blockIdx.x], hi = first[blockIdx.x + 1];
+#pragma unroll
+    for (unsigned u = 0; u < FRS_MOVE; ++u) {
+        const uint64_t h = ((uint64_t)blockIdx.x * FRS_MOVE + u) * FR_BLOCK + threadIdx.x;  // the 16-byte half
+        const uint64_t s = h >> 1;
+        if (s >= total) return;
+        const size_t t = last_at_or_below(B, lo, hi, s);
+        const uint64_t id = pick[t];
+        const bool from_b = id >= S.n_trees_a;
+        const uint64_t from = (from_b ? S.start_b[id - S.n_trees_a] : S.start_a[id]) + (s - B[t]);
+        out[h] = (from_b ? S.data_b : S.data_a)[2 * from + (h & 1)];
+    }
+}
+
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_sel_roots(const uint64_t* __restrict__ ntree_new, size_t n_pick, const uint64_t* __restrict__ pick,
+                                                           uint64_t n_trees_a, const uint4* __restrict__ roots_a, const uint4* __restrict__ roots_b,
+                                                           Scalar32* __restrict__ roots, unsigned* __restrict__ n_bad) {
+    const size_t j = (size_t)blockIdx.x * FR_BLOCK + threadIdx.x;
+    if (j >= n_pick) return;
+    if (ntree_new[j] == 0) {  // refused: a good tree has a leaf
+        store_zero(roots + j);
+        if (n_bad) atomicAdd(n_bad, 1u);
+        return;
+    }
+    const uint64_t id = pick[j];
+    const uint4* src = id >= n_trees_a ? roots_b + 2 * (id - n_trees_a) : roots_a + 2 * id;
+    uint4* dst = reinterpret_cast<uint4*>(roots + j);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
+// ---------------------------------------------------------------------------------------------
 // launcher (C++ linkage, called from api.cpp)
 // ---------------------------------------------------------------------------------------------
 unsigned forest_ragged_depth(size_t n, unsigned arity) {
@@ -362,6 +469,82 @@ hipError_t launch_forest_ragged(const int32_t* tab, const TagArg& tag, const For
     }
     if (p.levels)
         hipLaunchKernelGGL(k_fr_roots_from_levels, dim3(grid_for(n)), blk, 0, st, ntree, C, n, la, static_cast<const Scalar32*>(levels), rt);
+    return hipGetLastError();
+}
+
+ForestSelectPlan forest_select_plan(unsigned arity, size_t n_trees_a, size_t n_trees_b, size_t max_leaves, size_t n_pick, size_t leaves_cap) {
+    ForestSelectPlan p;
+    p.arity = arity;
+    p.depth = forest_ragged_depth(max_leaves, arity);
+    p.n_pick = n_pick;
+    p.leaves_cap = leaves_cap;
+    p.max_leaves = max_leaves;
+    p.nodes = leaves_cap / (arity - 1) + n_pick * p.depth;
+    p.tiles = (n_pick + FR_TILE - 1) / FR_TILE;
+    p.leaf_tiles = (leaves_cap + FOREST_SELECT_MOVE_TILE - 1) / FOREST_SELECT_MOVE_TILE;
+    p.node_tiles = (p.nodes + FOREST_SELECT_MOVE_TILE - 1) / FOREST_SELECT_MOVE_TILE;
+    p.index_a_bytes = forest_ragged_index_bytes(n_trees_a);
+    p.index_b_bytes = forest_ragged_index_bytes(n_trees_b);
+    p.index_new_bytes = forest_ragged_index_bytes(n_pick);
+    // one count per pick, the scans' tile sums, the two first-tree rows
+    const size_t words = n_pick + p.tiles + p.leaf_tiles + 1 + p.node_tiles + 1;
+    p.work_bytes = (words * 8 + 255) & ~(size_t)255;
+    return p;
+}
+
+hipError_t launch_forest_select(const ForestSelectPlan& p, const ForestSelectSource& A, const ForestSelectSource& B, const void* pick,
+                                void* leaves_new, void* offsets_new, void* levels_new, void* roots_new, void* n_bad, void* meta,
+                                hipStream_t st) {
+    const size_t n = p.n_pick;
+    if (n == 0) return hipSuccess;
+    char* base = static_cast<char*>(meta);
+    const uint64_t *ntree_a = nullptr, *lo_a = nullptr, *ntree_b = nullptr, *lo_b = nullptr, *ntree_new = nullptr, *lo_new = nullptr;
+    hipError_t e = launch_forest_ragged_index(p.arity, A.offsets, A.n_trees, A.n_leaves, A.max_leaves, base, &ntree_a, &lo_a, st);
+    if (e != hipSuccess) return e;
+    e = launch_forest_ragged_index(p.arity, B.offsets, B.n_trees, B.n_leaves, B.max_leaves, base + p.index_a_bytes, &ntree_b, &lo_b, st);
+    if (e != hipSuccess) return e;
+    uint64_t* count = reinterpret_cast<uint64_t*>(base + p.index_a_bytes + p.index_b_bytes + p.index_new_bytes);
+    uint64_t* tsum = count + n;
+    uint64_t* first_leaf = tsum + p.tiles;
+    uint64_t* first_node = first_leaf + p.leaf_tiles + 1;
+    const uint64_t* pk = static_cast<const uint64_t*>(pick);
+    uint64_t* off_new = static_cast<uint64_t*>(offsets_new);
+    const unsigned la = p.arity == 4 ? 2 : 1;
+    const dim3 blk(FR_BLOCK), per_pick(grid_for(n)), tiles((unsigned)p.tiles, 1);
+
+    hipLaunchKernelGGL(k_fr_sel_sizes, per_pick, blk, 0, st, pk, n, ntree_a, (uint64_t)A.n_trees, ntree_b, (uint64_t)B.n_trees, count);
+    // the cap rule: the build's sum rule over the picks' counts, with leaves_cap for n_leaves (no roots, nothing counted)
+    hipLaunchKernelGGL(k_fr_tile_sums, tiles, blk, 0, st, count, n, FR_ROW_LEAVES, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, p.tiles);
+    hipLaunchKernelGGL(k_fr_scan_apply<true>, tiles, blk, 0, st, count, n, FR_ROW_LEAVES, la, tsum, (uint64_t*)nullptr, (uint64_t)p.leaves_cap,
+                       (const uint64_t*)nullptr, (const Scalar32*)nullptr, (Scalar32*)nullptr, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k_fr_tile_sums, tiles, blk, 0, st, count, n, FR_ROW_LEAVES, la, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, p.tiles);
+    hipLaunchKernelGGL(k_fr_sel_offsets, tiles, blk, 0, st, count, n, tsum, off_new);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the new forest's index: the build's own validation and block starts, on the offsets just written
+    e = launch_forest_ragged_index(p.arity, off_new, n, p.leaves_cap, p.max_leaves, base + p.index_a_bytes + p.index_b_bytes, &ntree_new, &lo_new, st);
+    if (e != hipSuccess) return e;
+
+    FrSelSrc S;
+    S.n_trees_a = A.n_trees;
+    S.start_a = static_cast<const uint64_t*>(A.offsets);
+    S.start_b = static_cast<const uint64_t*>(B.offsets);
+    S.data_a = static_cast<const uint4*>(A.leaves);
+    S.data_b = static_cast<const uint4*>(B.leaves);
+    hipLaunchKernelGGL(k_fr_sel_tile_first, dim3(grid_for(p.leaf_tiles + 1)), blk, 0, st, off_new, n, p.leaf_tiles + 1, first_leaf);
+    hipLaunchKernelGGL(k_fr_sel_move, dim3((unsigned)p.leaf_tiles), blk, 0, st, off_new, n, first_leaf, pk, S, static_cast<uint4*>(leaves_new));
+    if (p.depth && p.nodes) {
+        S.start_a = lo_a;
+        S.start_b = lo_b;
+        S.data_a = static_cast<const uint4*>(A.levels);
+        S.data_b = static_cast<const uint4*>(B.levels);
+        hipLaunchKernelGGL(k_fr_sel_tile_first, dim3(grid_for(p.node_tiles + 1)), blk, 0, st, lo_new, n, p.node_tiles + 1, first_node);
+        hipLaunchKernelGGL(k_fr_sel_move, dim3((unsigned)p.node_tiles), blk, 0, st, lo_new, n, first_node, pk, S, static_cast<uint4*>(levels_new));
+    }
+    hipLaunchKernelGGL(k_fr_sel_roots, per_pick, blk, 0, st, ntree_new, n, pk, (uint64_t)A.n_trees, static_cast<const uint4*>(A.roots),
+                       static_cast<const uint4*>(B.roots), static_cast<Scalar32*>(roots_new), static_cast<unsigned*>(n_bad));
     return hipGetLastError();
 }
 

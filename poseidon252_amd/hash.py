@@ -664,6 +664,74 @@ class Context:
             _dev_ptr(self, f, "d_roots", d_roots, n_trees_new * 32), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
+    def merkle4_forest_ragged_select_device(self, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
+                                            d_n_bad=None):
+        """any trees of one or two built forests gathered INTO a new compact forest, with no digest
+        (p252_merkle4_forest_ragged_select_device_into).  forest_a, forest_b = (d_leaves, d_offsets, n_trees, max_leaves, d_levels,
+        d_roots), each exactly what merkle_forest_ragged_device took and filled (read-only); forest_b may be None.  d_pick = n_pick
+        int64/uint64 ids on the device: below n_trees_a a tree of A, then a tree of B; any order, repeats allowed.  Written:
+        d_leaves_new (its length is leaves_cap), d_offsets_new (n_pick + 1), d_levels_new (at least the bound of
+        merkle_forest_ragged_device for leaves_cap leaves, n_pick trees and the larger max_leaves), d_roots_new (n_pick, 4) — byte
+        for byte a fresh build of the new forest.  A pick out of range, of a bad tree, or past leaves_cap (and every non-empty one
+        after it) becomes an empty tree and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
+        self._forest_ragged_select_device("merkle4_forest_ragged_select_device", _ARITIES[4], forest_a, forest_b, d_pick, n_pick, d_leaves_new,
+                                          d_offsets_new, d_levels_new, d_roots_new, d_n_bad)
+
+    def merkle2_forest_ragged_select_device(self, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
+                                            d_n_bad=None):
+        """the same for arity 2 (the level layout of merkle2 trees)"""
+        self._forest_ragged_select_device("merkle2_forest_ragged_select_device", _ARITIES[2], forest_a, forest_b, d_pick, n_pick, d_leaves_new,
+                                          d_offsets_new, d_levels_new, d_roots_new, d_n_bad)
+
+    def _forest_ragged_select_device(self, f, a, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
+                                     d_n_bad):
+        def source(which, forest):
+            """the seven C arguments of one source forest, and its byte ranges"""
+            if forest is None:
+                return (None, 0, None, 0, 0, None, None), 0, []
+            if len(forest) != 6:
+                raise ValueError("%s: forest_%s must be (d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots)" % (f, which))
+            d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots = forest
+            if n_trees <= 0 or max_leaves <= 0:
+                raise ValueError("%s: forest_%s needs n_trees and max_leaves > 0" % (f, which))
+            leaves = _dev_ptr(self, f, "d_leaves_" + which, d_leaves, 32)
+            n_leaves = _n_scalars(d_leaves)
+            depth = a.depth(max_leaves)
+            sizes = ((n_trees + 1) * 8, a.forest_levels_bytes(n_leaves, n_trees, depth), n_trees * 32)
+            ptrs = (leaves, n_leaves, _dev_ptr(self, f, "d_offsets_" + which, d_offsets, sizes[0], elem=8), n_trees, max_leaves,
+                    _dev_ptr(self, f, "d_levels_" + which, d_levels, sizes[1], null_ok=depth == 0),
+                    _dev_ptr(self, f, "d_roots_" + which, d_roots, sizes[2]))
+            ranges = [("d_leaves_" + which, leaves, n_leaves * 32), ("d_offsets_" + which, ptrs[2], sizes[0]),
+                      ("d_levels_" + which, ptrs[5], sizes[1]), ("d_roots_" + which, ptrs[6], sizes[2])]
+            return ptrs, max_leaves, ranges
+
+        if forest_a is None:
+            raise ValueError("%s: forest_a is required" % f)
+        args_a, max_a, in_a = source("a", forest_a)
+        args_b, max_b, in_b = source("b", forest_b)
+        if n_pick < 0:
+            raise ValueError("%s: n_pick must be >= 0" % f)
+        pick = _dev_ptr(self, f, "d_pick", d_pick, n_pick * 8, elem=8, null_ok=n_pick == 0)
+        depth = a.depth(max(max_a, max_b))
+        leaves_new = _dev_ptr(self, f, "d_leaves_new", d_leaves_new, 32)
+        leaves_cap = _n_scalars(d_leaves_new)
+        levels_need = a.forest_levels_bytes(leaves_cap, n_pick, depth)
+        levels_new = _dev_ptr(self, f, "d_levels_new", d_levels_new, levels_need, null_ok=depth == 0)
+        levels_cap = _n_scalars(d_levels_new) if d_levels_new is not None else levels_need // 32  # (no level: nothing is written)
+        offsets_new = _dev_ptr(self, f, "d_offsets_new", d_offsets_new, (n_pick + 1) * 8, elem=8)
+        roots_new = _dev_ptr(self, f, "d_roots_new", d_roots_new, n_pick * 32)
+        n_bad = _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True)
+        # no output may overlap an input or another output (the library refuses it too: all sizes are known here)
+        outs = [("d_leaves_new", leaves_new, leaves_cap * 32), ("d_offsets_new", offsets_new, (n_pick + 1) * 8),
+                ("d_levels_new", levels_new, levels_cap * 32), ("d_roots_new", roots_new, n_pick * 32), ("d_n_bad", n_bad, 4)]
+        ins = in_a + in_b + [("d_pick", pick, n_pick * 8)]
+        for i, (name, p, size) in enumerate(outs):
+            for other, q, size_q in ins + outs[:i]:
+                if p and q and size and size_q and p < q + size_q and q < p + size:
+                    raise ValueError("%s: %s overlaps %s" % (f, name, other))
+        self._check(a.fn("forest_ragged_select_device_into")(self._h, *args_a, *args_b, pick, n_pick, leaves_new, leaves_cap, offsets_new,
+                                                             levels_new, levels_cap, roots_new, n_bad, _stream(self)))
+
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
         f = "truncate250_device"

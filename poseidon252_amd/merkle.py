@@ -190,6 +190,42 @@ def forest_ragged_resize(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_l
     return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
 
 
+def forest_ragged_select(ctx, forest_a, pick, forest_b=None, arity=4, leaves_cap=None):
+    """Any trees of one or two built forests gathered into a new compact forest, with no digest
+    (Context.merkle{4,2}_forest_ragged_select_device): forest_a, forest_b = (d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots),
+    torch CUDA tensors as Context.merkle_forest_ragged_device took and filled them; pick = the ids of the new forest's trees in order
+    (a device int64 tensor, or anything numpy takes): below n_trees_a a tree of A, then a tree of B.  leaves_cap defaults to the leaves
+    of both sources, enough when no tree is named twice; a pick past it is refused and counted, never written.  Sizes and allocates
+    the new forest and returns (d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad (1,) int32), all on the device: what
+    forest_ragged_append returns for a new forest, less the digest count (there is none).  d_levels_new holds the bound of the new
+    shape; max_leaves of the new forest is the larger of the two sources'.  No synchronisation."""
+    import torch
+    a = _arity("forest_ragged_select", arity)
+    ctx = ctx or Context.default()
+    dev = forest_a[0].device
+    if not isinstance(pick, torch.Tensor):
+        ids = np.ascontiguousarray(pick)
+        if ids.dtype.kind not in "iu":
+            raise ValueError("forest_ragged_select: pick must hold integers, not %s" % ids.dtype)
+        pick = torch.from_numpy(ids.astype(np.uint64).view(np.int64).reshape(-1)).to(dev)
+    n_pick = pick.numel()
+    if leaves_cap is None:
+        leaves_cap = _n_scalars(forest_a[0]) + (_n_scalars(forest_b[0]) if forest_b is not None else 0)
+    if leaves_cap <= 0:
+        raise ValueError("forest_ragged_select: leaves_cap must be > 0")
+    max_leaves = max(forest_a[3], forest_b[3] if forest_b is not None else 0)
+    leaves_new = torch.empty((leaves_cap, 4), dtype=torch.int64, device=dev)
+    offsets_new = torch.empty(n_pick + 1, dtype=torch.int64, device=dev)
+    levels_new = torch.empty((a.forest_levels_bytes(leaves_cap, n_pick, a.depth(max_leaves)) // 32, 4), dtype=torch.int64, device=dev)
+    roots = torch.empty((n_pick, 4), dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_pick == 0:  # (the library enqueues nothing: the one offset is written here)
+        offsets_new.zero_()
+    call = ctx.merkle4_forest_ragged_select_device if arity == 4 else ctx.merkle2_forest_ragged_select_device
+    call(forest_a, forest_b, pick, n_pick, leaves_new, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad)
+    return leaves_new, offsets_new, levels_new, roots, n_bad
+
+
 class ForestJournal:
     """what one journaled update overwrote (forest_ragged_update_journaled), on the device: ids (cap, 4) int32 {tree id, level + 1, node
     index low, high}, values (cap, 4) int64, len (1,) int64 = the entries in use; n_bad (1,) int32 and n_hashed (1,) int64 are the
