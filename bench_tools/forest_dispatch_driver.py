@@ -19,15 +19,13 @@ accept every opening and every shared proof, before and after the updates, and e
 build of its leaves: the driver exits non-zero otherwise."""
 import argparse
 import csv
-import os
 import re
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
+import _common as C
+from testsupport import treeshape as TS
 
 
 def dispatches(path):
@@ -38,20 +36,6 @@ def dispatches(path):
         print(base, r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"], r["Workgroup_Size_X"], r["Workgroup_Size_Y"], r["Workgroup_Size_Z"])
 
 
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
-    return torch.from_numpy(a).to("cuda:0")
-
-
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n, d = (n + arity - 1) // arity, d + 1
-    return d
-
-
 def run(ctx, arity, sizes, ks, seed):
     import torch
     from poseidon252_amd import merkle as M
@@ -59,14 +43,13 @@ def run(ctx, arity, sizes, ks, seed):
     tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
     sizes = np.asarray(sizes, np.int64)
     n_trees, max_leaves = len(sizes), int(sizes.max())
-    off = np.zeros(n_trees + 1, np.uint64)
-    np.cumsum(sizes.astype(np.uint64), out=off[1:])
-    n_leaves, D = int(off[-1]), _depth(max_leaves, arity)
+    off = TS.offsets(sizes)
+    n_leaves, D = int(off[-1]), TS.depth(max_leaves, arity)
     dev = torch.device("cuda:0")
     d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
-    d_off = _dev(off)
+    d_off = C.dev(off)
     roots, roots2 = (torch.empty((n_trees, 4), dtype=torch.int64, device=dev) for _ in range(2))
-    d_lv = torch.empty((n_leaves // (arity - 1) + n_trees * D + 1, 4), dtype=torch.int64, device=dev)
+    d_lv = torch.empty((TS.levels_bound(n_leaves, n_trees, max_leaves, arity) + 1, 4), dtype=torch.int64, device=dev)
     ctx.merkle_forest_ragged_device(tag, d, d_off, n_trees, max_leaves, roots, None, arity=arity)   # level-major scratch
     ctx.merkle_forest_ragged_device(tag, d, d_off, n_trees, max_leaves, roots2, d_lv, arity=arity)  # tree-major d_levels
     torch.cuda.synchronize()
@@ -76,7 +59,7 @@ def run(ctx, arity, sizes, ks, seed):
         lid = (rng.random(k) * sizes[tid]).astype(np.int64)
         pairs = np.unique(tid.astype(np.int64) << 32 | lid)  # the update call wants distinct (tree, leaf) pairs: a pair drawn twice
         tid, lid, k = pairs >> 32, pairs & 0xffffffff, pairs.size  # with two values leaves whichever landed, and its opening may not verify
-        d_tid, d_lid = _dev(tid.astype(np.uint32)), _dev(lid.astype(np.uint64))
+        d_tid, d_lid = C.dev(tid.astype(np.uint32)), C.dev(lid.astype(np.uint64))
         out = (torch.empty((k, 4), dtype=torch.int64, device=dev), torch.empty((k, D, arity - 1, 4), dtype=torch.int64, device=dev),
                torch.empty((k, D), dtype=torch.uint8, device=dev), torch.empty((k,), dtype=torch.uint8, device=dev))
         back = torch.empty((k, 4), dtype=torch.int64, device=dev)
@@ -106,14 +89,13 @@ def run_changes(ctx, arity, sizes, k, seed):
     tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
     sizes = np.asarray(sizes, np.int64)
     n_trees, max_leaves = len(sizes), int(sizes.max())
-    off = np.zeros(n_trees + 1, np.uint64)
-    np.cumsum(sizes.astype(np.uint64), out=off[1:])
-    n_leaves, D = int(off[-1]), _depth(max_leaves, arity)
+    off = TS.offsets(sizes)
+    n_leaves, D = int(off[-1]), TS.depth(max_leaves, arity)
     dev = torch.device("cuda:0")
     d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
-    d_off = _dev(off)
+    d_off = C.dev(off)
     roots = torch.empty((n_trees, 4), dtype=torch.int64, device=dev)
-    d_lv = torch.empty((n_leaves // (arity - 1) + n_trees * D + 1, 4), dtype=torch.int64, device=dev)
+    d_lv = torch.empty((TS.levels_bound(n_leaves, n_trees, max_leaves, arity) + 1, 4), dtype=torch.int64, device=dev)
     ctx.merkle_forest_ragged_device(tag, d, d_off, n_trees, max_leaves, roots, d_lv, arity=arity)
 
     def fresh_roots(leaves, offsets, trees, top, levels_like):
@@ -151,19 +133,17 @@ def run_changes(ctx, arity, sizes, k, seed):
     # an append to every third tree and two new trees, then a resize that cuts every fifth tree, drops the last two and appends again
     m = np.where(np.arange(n_trees + 2) % 3 == 0, rng.integers(1, 2 * arity + 2, n_trees + 2), 0)
     m[n_trees:] = (1, arity + 1)
-    a_off = np.zeros(n_trees + 3, np.uint64)
-    np.cumsum(m.astype(np.uint64), out=a_off[1:])
+    a_off = TS.offsets(m)
     d_add = torch.randint(0, 1 << 60, (int(a_off[-1]), 4), dtype=torch.int64, device=dev)
     top = max_leaves + 2 * (2 * arity + 1)  # (room for both appends: none is refused)
-    l2, o2, v2, r2, bad2, _ = M.forest_ragged_append(ctx, tag, d, d_off, n_trees, max_leaves, d_lv, d_add, _dev(a_off), max_leaves_new=top, arity=arity)
+    l2, o2, v2, r2, bad2, _ = M.forest_ragged_append(ctx, tag, d, d_off, n_trees, max_leaves, d_lv, d_add, C.dev(a_off), max_leaves_new=top, arity=arity)
     assert int(bad2) == 0 and torch.equal(r2, fresh_roots(l2, o2, n_trees + 2, top, v2)), "append: not the roots of a fresh build"
     sizes2 = np.concatenate([sizes, [0, 0]]) + m
     prove("appended", l2, o2, n_trees + 2, top, v2, r2, tid, lid)
     keep = np.where(np.arange(n_trees) % 5 == 0, (sizes2[:n_trees] + 1) // 2, -1)
     m3 = m[:n_trees] * (np.arange(n_trees) % 2)
-    a3 = np.zeros(n_trees + 1, np.uint64)
-    np.cumsum(m3.astype(np.uint64), out=a3[1:])
-    l3, o3, v3, r3, bad3, _ = M.forest_ragged_resize(ctx, tag, l2, o2, n_trees + 2, top, v2, _dev(keep.astype(np.int64)), d_add[:int(a3[-1])], _dev(a3),
+    a3 = TS.offsets(m3)
+    l3, o3, v3, r3, bad3, _ = M.forest_ragged_resize(ctx, tag, l2, o2, n_trees + 2, top, v2, C.dev(keep.astype(np.int64)), d_add[:int(a3[-1])], C.dev(a3),
                                                      max_leaves_new=top, arity=arity)
     assert int(bad3) == 0 and torch.equal(r3, fresh_roots(l3, o3, n_trees, top, v3)), "resize: not the roots of a fresh build"
     print("arity %d, %d trees, %d leaves, k = %d: journaled update, undo, redo, shared proofs, append, resize ok" % (arity, n_trees, n_leaves, k))
@@ -173,12 +153,11 @@ def run_hash_ragged(ctx, n, max_len):
     import torch
     from poseidon252_amd import hash as H
     lens = 1 + np.arange(n) % max_len
-    off = np.zeros(n + 1, np.uint64)
-    np.cumsum(lens.astype(np.uint64), out=off[1:])
+    off = TS.offsets(lens)
     d_in = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device="cuda:0")
     out = torch.empty((n, 1, 4), dtype=torch.int64, device="cuda:0")
     bad = torch.zeros(1, dtype=torch.int32, device="cuda:0")
-    ctx.hash_ragged_device(_dev(H.ragged_tags(H.Domain.Other, 1, max_len)), max_len, d_in, _dev(off), 1, out, n, d_n_bad=bad)
+    ctx.hash_ragged_device(C.dev(H.ragged_tags(H.Domain.Other, 1, max_len)), max_len, d_in, C.dev(off), 1, out, n, d_n_bad=bad)
     torch.cuda.synchronize()
     assert int(bad) == 0
     print("hash_ragged, %d messages of 1 .. %d scalars: ok" % (n, max_len))
@@ -187,7 +166,7 @@ def run_hash_ragged(ctx, n, max_len):
 def run_tree_families(ctx, arity, n_leaves, k, n_trees, per):
     """root-only tree and equal-size forest; k openings of the stored tree verified in bulk; a shared proof of k leaves, verified"""
     import torch
-    from multiproof_bench import tree_device
+    from testsupport.device import tree_device
     from poseidon252_amd import levels_len
     from poseidon252_amd import merkle as M
     dev = torch.device("cuda:0")
@@ -201,7 +180,7 @@ def run_tree_families(ctx, arity, n_leaves, k, n_trees, per):
     f_roots = torch.empty((n_trees, 4), dtype=torch.int64, device=dev)
     ctx.merkle4_forest_device(tag, f_leaves, n_trees, per, f_roots, arity=arity)
     idx = np.sort(np.random.default_rng(7).permutation(n_leaves)[:k]).astype(np.uint32)
-    d_idx = _dev(idx)
+    d_idx = C.dev(idx)
     o_l, o_s, o_p, depth = ctx.merkle4_openings_device(d, n_leaves, d_lv, d_idx, k, arity=arity)
     ok = torch.zeros(k, dtype=torch.uint8, device=dev)
     ctx.merkle_verify_batch_device(tag, o_l, o_s, o_p, depth, root2, ok, k, arity=arity)

@@ -20,22 +20,21 @@ leaves).  Prints one line per case, writes them to --out, and prints a JSON summ
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from forest_update_bench import Forest, _alternate, _clock_mhz, _depth, _dev, dirty_nodes  # noqa: E402
+import _common as C
+from _common import ROOT, Forest
+from testsupport import treeshape as TS
+from testsupport.forestupdate import dirty_nodes
 
 
 def _case(ctx, name, f, tid, lid, reps, say):
     """one forest, one update list -> the row of results"""
     import torch
     a, k = f.arity, len(tid)
-    d_tid, d_lid = _dev(np.asarray(tid, np.uint32)), _dev(np.asarray(lid, np.uint64))
-    slot = _dev(f.off[np.asarray(tid)].astype(np.int64) + np.asarray(lid, np.int64))
+    d_tid, d_lid = C.dev(np.asarray(tid, np.uint32)), C.dev(np.asarray(lid, np.uint64))
+    slot = C.dev(f.off[np.asarray(tid)].astype(np.int64) + np.asarray(lid, np.int64))
     d_old = f.d[slot].clone()  # what a caller without a journal must have saved
     d_new = torch.randint(0, 1 << 60, (k, 4), dtype=torch.int64, device="cuda:0", generator=torch.Generator(device="cuda:0").manual_seed(3))
     n_leaves = f.d.shape[0]
@@ -70,16 +69,16 @@ def _case(ctx, name, f, tid, lid, reps, say):
     n_entries, n_hashed = int(jlen), int(hashed)
     # (a)
     plain(), journaled()
-    t_plain, t_journaled = _alternate([plain, journaled], reps)
+    t_plain, t_journaled = C.alternate([plain, journaled], reps, C.once_ms)
     # (b)
     journaled(), swap(), reupdate()
-    t_swap, t_re = _alternate([swap, reupdate], reps)
+    t_swap, t_re = C.alternate([swap, reupdate], reps, C.once_ms)
     # the swap's bytes against a copy of the same bytes
     src = torch.empty(max(n_entries, 1) * 64, dtype=torch.uint8, device="cuda:0")
     dst = torch.empty_like(src)
     copy = lambda: dst.copy_(src)  # noqa: E731
     copy()
-    t_swap2, t_copy = _alternate([swap, copy], reps)
+    t_swap2, t_copy = C.alternate([swap, copy], reps, C.once_ms)
     moved = n_entries * 128
     row = {"case": name, "arity": a, "k": k, "journal_entries": n_entries, "journal_bound": cap, "digests": n_hashed,
            "digests_numpy": dirty_nodes(f.sizes, tid, lid, a), "plain_update_ms": t_plain, "journaled_update_ms": t_journaled,
@@ -111,14 +110,14 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx), "rows": []}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx), "rows": []}
     say("python bench_tools/forest_journal_bench.py --reps %d%s   shader clock before: %s MHz" % (a.reps, " --quick" if a.quick else "", res["clock_mhz_before"]))
     ks = [1, 1 << 6, 1 << 12] if a.quick else [1, 1 << 10, 1 << 16, 1 << 20]
     for arity, n in ((4, 4 ** 8 if a.quick else 4 ** 12), (2, 2 ** 16 if a.quick else 2 ** 24)):
         f = Forest(ctx, arity, [n], n)
         for k in ks:
             lid = np.random.default_rng(1).choice(n, k, replace=False)
-            res["rows"].append(_case(ctx, "arity %d, one tree of %d^%d leaves" % (arity, arity, _depth(n, arity)), f, np.zeros(k, np.int64), lid, a.reps, say))
+            res["rows"].append(_case(ctx, "arity %d, one tree of %d^%d leaves" % (arity, arity, TS.depth(n, arity)), f, np.zeros(k, np.int64), lid, a.reps, say))
         del f
         torch.cuda.empty_cache()
     rng = np.random.default_rng(a.seed)
@@ -130,7 +129,7 @@ def main():
     f = Forest(ctx, 4, sizes, top)
     res["rows"].append(_case(ctx, "arity 4, %d mixed trees (log-uniform 1..4^7, %d leaves), 1-16 updates each" % (n_trees, int(sizes.sum())), f, tid, lid,
                              a.reps, say))
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     say("shader clock after: %s MHz" % res["clock_mhz_after"])
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:

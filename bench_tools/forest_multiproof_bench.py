@@ -11,99 +11,20 @@ tree-major proof, one call each) against the calls that served a forest before i
     digests and time, and the same with ONE pair per tree (where the per-leaf openings have nothing to share).
 Every shape is warmed up; times are medians of --reps host wall clocks around calls that end in a device synchronise; the two sides of a
 ratio alternate in the one process (the per-tree loop of (a), thousands of calls a repetition, runs max(3, reps / 4) of them); every forest proof is verified (d_ok = 1 on the trees with pairs, roots = the build's) and its
-offsets and digest count are compared with the model below before it is timed; the shader clock is probed before and after.
-Prints one line per workload, writes them to --out, and prints a JSON summary last.
-
-The model of the forest proof is here too, for the tests to compare the device's bytes and counts with: a composition of the
-single-tree model of multiproof_bench.py — P_t = multiproof_extract(tree t's leaves, tree t's levels, tree t's positions)."""
+offsets and digest count are compared with the model (testsupport/multiproofmodel.py) before it is timed; the shader clock is probed before and after.
+Prints one line per workload, writes them to --out, and prints a JSON summary last."""
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from multiproof_bench import _alternate, _clock_mhz, multiproof_counts, multiproof_extract, multiproof_root  # noqa: E402
-
-
-def _levels_len(n, arity):
-    total = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        total += n
-    return total
-
-
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n, d = (n + arity - 1) // arity, d + 1
-    return d
-
-
-def forest_pairs_by_tree(n_trees, tree_ids, leaf_ids):
-    """{t: the ascending positions asked of tree t} for strictly ascending pairs (trees without pairs are absent)"""
-    tid, lid = np.asarray(tree_ids, dtype=np.int64).reshape(-1), np.asarray(leaf_ids, dtype=np.int64).reshape(-1)
-    assert tid.size == lid.size and tid.size and int(tid.min()) >= 0 and int(tid.max()) < n_trees
-    key = tid * (1 << 40) + lid
-    assert bool(np.all(np.diff(key) > 0)), "pairs must be strictly ascending in (tree, leaf)"
-    trees, first = np.unique(tid, return_index=True)
-    return {int(t): part for t, part in zip(trees, np.split(lid, first[1:]))}
-
-
-def forest_multiproof_counts(sizes, tree_ids, leaf_ids, arity):
-    """(proof_offsets (n_trees + 1,) uint64, digests a verifier computes) of the forest proof of the pairs in trees of `sizes` leaves"""
-    per_tree = forest_pairs_by_tree(len(sizes), tree_ids, leaf_ids)
-    lens, hashed = np.zeros(len(sizes) + 1, dtype=np.uint64), 0
-    for t, pos in per_tree.items():
-        length, digests = multiproof_counts(int(sizes[t]), pos, arity)
-        lens[t + 1] = length
-        hashed += digests
-    return np.cumsum(lens, dtype=np.uint64), hashed
-
-
-def forest_multiproof_extract(leaves, offsets, levels, tree_ids, leaf_ids, arity):
-    """(leaves_out (k, 4), proof (len, 4), proof_offsets (n_trees + 1,)) out of a built forest: leaves (n, 4), offsets (n_trees + 1,),
-    levels = the tree-major upper levels (tree t's block after the blocks of the trees before it)"""
-    leaves, levels = np.asarray(leaves).reshape(-1, 4), np.asarray(levels).reshape(-1, 4)
-    off = np.asarray(offsets, dtype=np.int64)
-    sizes = np.diff(off)
-    lo = np.concatenate([[0], np.cumsum([_levels_len(int(n), arity) for n in sizes])]).astype(np.int64)
-    per_tree = forest_pairs_by_tree(len(sizes), tree_ids, leaf_ids)
-    parts, lens = [], np.zeros(len(sizes) + 1, dtype=np.uint64)
-    for t in sorted(per_tree):
-        p = multiproof_extract(leaves[off[t]:off[t + 1]], levels[lo[t]:lo[t + 1]], per_tree[t], arity)
-        parts.append(p)
-        lens[t + 1] = p.shape[0]
-    proof = np.concatenate(parts) if parts else np.zeros((0, 4), dtype=leaves.dtype)
-    tid, lid = np.asarray(tree_ids, dtype=np.int64).reshape(-1), np.asarray(leaf_ids, dtype=np.int64).reshape(-1)
-    return leaves[off[tid] + lid], proof, np.cumsum(lens, dtype=np.uint64)
-
-
-def forest_multiproof_roots(sizes, tree_ids, leaf_ids, leaf_values, proof, proof_offsets, arity, digest, reduce=None):
-    """{t: the root tree t's part re-hashes to, or None when its structure does not consume exactly its part}; a one-leaf tree's root is
-    reduce(its leaf) (the forest's convention: the leaf mod p)"""
-    per_tree = forest_pairs_by_tree(len(sizes), tree_ids, leaf_ids)
-    tid = np.asarray(tree_ids, dtype=np.int64).reshape(-1)
-    vals, proof, po = np.asarray(leaf_values).reshape(-1, 4), np.asarray(proof).reshape(-1, 4), np.asarray(proof_offsets, dtype=np.int64)
-    out = {}
-    for t, pos in per_tree.items():
-        root = multiproof_root(int(sizes[t]), pos, vals[tid == t], proof[po[t]:po[t + 1]], arity, digest)
-        if root is not None and int(sizes[t]) == 1 and reduce is not None:
-            root = np.asarray(reduce(np.asarray(root).reshape(1, 4))).reshape(4)
-        out[t] = root
-    return out
-
-
-def forest_multiproof_bound(n_leaves, n_trees, max_leaves, k, arity):
-    """p252_merkle{4,2}_forest_ragged_multiproof_bound"""
-    if not (k and n_leaves and n_trees):
-        return 0
-    d = _depth(max_leaves, arity)
-    return min(k * d * (arity - 1), n_leaves + n_leaves // (arity - 1) + n_trees * d)
+import _common as C
+from _common import ROOT
+from testsupport import treeshape as TS
+# (the numpy model lived in this module once: all of its names stay importable from here)
+from testsupport.multiproofmodel import (forest_multiproof_bound, forest_multiproof_counts, forest_multiproof_extract,  # noqa: F401
+                                         forest_multiproof_roots, forest_pairs_by_tree)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -113,20 +34,16 @@ class Forest:
     def __init__(self, ctx, arity, sizes, tid, lid, seed=5):
         import torch
         from poseidon252_amd import merkle as M
-        from poseidon252_amd.hash import _ARITIES
         self.ctx, self.arity, self.sizes = ctx, arity, np.asarray(sizes, dtype=np.int64)
         self.dev = dev = torch.device("cuda:0")
         self.tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
         self.T, self.n, self.top = len(sizes), int(self.sizes.sum()), int(self.sizes.max())
-        off = np.zeros(self.T + 1, dtype=np.int64)
-        np.cumsum(self.sizes, out=off[1:])
-        self.off = off
-        self.lo = np.concatenate([[0], np.cumsum([_levels_len(int(n), arity) for n in sizes])]).astype(np.int64)
+        self.off = off = TS.offsets(self.sizes, dtype=np.int64)
+        self.lo = TS.offsets(TS.levels_len(self.sizes, arity), dtype=np.int64)
         g = torch.Generator(device="cpu").manual_seed(seed)
         self.leaves = torch.randint(0, 1 << 60, (self.n, 4), dtype=torch.int64, generator=g).to(dev)
         self.offsets = torch.from_numpy(off).to(dev)
-        depth = _ARITIES[arity].depth(self.top)
-        self.levels = torch.zeros((max(self.n // (arity - 1) + self.T * depth, 1), 4), dtype=torch.int64, device=dev)
+        self.levels = torch.zeros((max(TS.levels_bound(self.n, self.T, self.top, arity), 1), 4), dtype=torch.int64, device=dev)
         self.roots = torch.zeros((self.T, 4), dtype=torch.int64, device=dev)
         ctx.merkle_forest_ragged_device(self.tag, self.leaves, self.offsets, self.T, self.top, self.roots, d_levels=self.levels, arity=arity)
         self.set_pairs(tid, lid)
@@ -224,7 +141,7 @@ def _openings_side(f):
     verify = lambda: ctx.merkle_forest_ragged_verify_device(f.tag, lv, sib, pos, dep, D, f.tid, f.roots, f.T, oks, k, arity=f.arity)  # noqa: E731
     verify()
     torch.cuda.synchronize()
-    depths = np.array([_depth(int(n), f.arity) for n in f.sizes])[f.tid_h]
+    depths = TS.depth(f.sizes, f.arity)[f.tid_h]
     return extract, verify, int(depths.sum()) * (f.arity - 1) * 32, int(depths.sum()), int(oks.sum()) == k
 
 
@@ -243,7 +160,7 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx)}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx)}
     say("python bench_tools/forest_multiproof_bench.py --reps %d%s   shader clock before: %s MHz" % (a.reps, " --quick" if a.quick else "", res["clock_mhz_before"]))
     n_trees = 500 if a.quick else a.trees
     loop_reps = max(3, a.reps // 4)  # (the loop is thousands of launch-bound calls a repetition)
@@ -254,8 +171,8 @@ def main():
     good = f.check()
     loop_extract, loop_verify = f.per_tree_loop()
     loop_extract(), loop_verify()
-    t_loop_e, t_e = _alternate([loop_extract, f.extract], loop_reps)
-    t_loop_v, t_v = _alternate([loop_verify, f.verify], loop_reps)
+    t_loop_e, t_e = C.alternate([loop_extract, f.extract], loop_reps, C.once_ms)
+    t_loop_v, t_v = C.alternate([loop_verify, f.verify], loop_reps, C.once_ms)
     res["a"] = {"trees": n_trees, "leaves": f.n, "pairs": f.k, "loop_extract_ms": t_loop_e, "forest_extract_ms": t_e, "extract_ratio": t_loop_e / t_e,
                 "loop_verify_ms": t_loop_v, "forest_verify_ms": t_v, "verify_ratio": t_loop_v / t_v, "agrees_with_model": good}
     say("(a) %d mixed trees, %d leaves, %d pairs (1 .. 16 a tree): extract per-tree loop %.2f ms  one call %.3f ms  ratio %.1f  |  verify "
@@ -266,8 +183,8 @@ def main():
         f.set_pairs(tid_c, lid_c)
         good = f.check()
         o_e, o_v, o_bytes, o_digests, o_ok = _openings_side(f)
-        t_oe, t_me = _alternate([o_e, f.extract], a.reps)
-        t_ov, t_mv = _alternate([o_v, f.verify], a.reps)
+        t_oe, t_me = C.alternate([o_e, f.extract], a.reps, C.once_ms)
+        t_ov, t_mv = C.alternate([o_v, f.verify], a.reps, C.once_ms)
         row = {"pairs_per_tree": label, "pairs": f.k, "openings_ms": t_oe, "multiproof_ms": t_me, "extract_ratio": t_oe / t_me, "verify_ms": t_ov,
                "multiproof_verify_ms": t_mv, "verify_ratio": t_ov / t_mv, "siblings_bytes": o_bytes, "proof_bytes": f.length * 32,
                "digests_per_leaf": o_digests, "digests_once": int(f.hashed), "agrees_with_model": good and o_ok}
@@ -296,8 +213,8 @@ def main():
         single_v()
         torch.cuda.synchronize()
         good = good and length == f.length and int(ok1) == 1 and bool(torch.equal(proof1[:length], f.proof[:length]))
-        t_se, t_fe = _alternate([single_e, f.extract], a.reps)
-        t_sv, t_fv = _alternate([single_v, f.verify], a.reps)
+        t_se, t_fe = C.alternate([single_e, f.extract], a.reps, C.once_ms)
+        t_sv, t_fv = C.alternate([single_v, f.verify], a.reps, C.once_ms)
         res["b"].append({"arity": arity, "leaves": n, "k": k, "single_extract_ms": t_se, "forest_extract_ms": t_fe, "extract_ratio": t_se / t_fe,
                          "single_verify_ms": t_sv, "forest_verify_ms": t_fv, "verify_ratio": t_sv / t_fv, "agrees": good})
         say("(b) arity %d, one tree of %d leaves alone in a forest, k = 2^%d: extract single-tree %.3f ms  forest %.3f ms  ratio %.2f  |  verify "
@@ -305,7 +222,7 @@ def main():
             % (arity, n, int(np.log2(k)), t_se, t_fe, t_se / t_fe, t_sv, t_fv, t_sv / t_fv, good))
         del f, out1, proof1
         torch.cuda.empty_cache()
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     say("shader clock after: %s MHz" % res["clock_mhz_after"])
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:

@@ -21,56 +21,11 @@ import json
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _median_ms(fn, reps):
-    import torch
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
-
-
-def _offsets(sizes):
-    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
-    return off
-
-
-def _clock_mhz(ctx):
-    """shader clock of one probe wave (MHz), or None"""
-    import torch
-    try:
-        t = ctx.clock_probe(spin_us=1000)
-        torch.cuda.synchronize()
-        return round(ctx.clock_probe_result(t)["shader_ghz"] * 1e3, 1)
-    except Exception:  # (a measurement aid only)
-        return None
-
-
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
-    return torch.from_numpy(a).to("cuda:0")
+import _common as C
+from testsupport import treeshape as TS
 
 
 class Forest:
@@ -81,17 +36,17 @@ class Forest:
         from poseidon252_amd import merkle as M
         self.ctx, self.arity, self.n_trees, self.max_leaves, self.k = ctx, arity, len(sizes), max_leaves, len(tid)
         self.tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         n_leaves = int(off[-1])
         dev = torch.device("cuda:0")
         self.d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
-        self.d_off = _dev(off)
-        self.D = D = _depth(max_leaves, arity)
+        self.d_off = C.dev(off)
+        self.D = D = TS.depth(max_leaves, arity)
         self.roots = torch.empty((self.n_trees, 4), dtype=torch.int64, device=dev)
-        self.d_lv = torch.empty((n_leaves // (arity - 1) + self.n_trees * D + 1, 4), dtype=torch.int64, device=dev)
+        self.d_lv = torch.empty((TS.levels_bound(n_leaves, self.n_trees, max_leaves, arity) + 1, 4), dtype=torch.int64, device=dev)
         ctx.merkle_forest_ragged_device(self.tag, self.d, self.d_off, self.n_trees, max_leaves, self.roots, self.d_lv, arity=arity)
         k = self.k
-        self.d_tid, self.d_lid = _dev(np.asarray(tid, np.uint32)), _dev(np.asarray(lid, np.uint64))
+        self.d_tid, self.d_lid = C.dev(np.asarray(tid, np.uint32)), C.dev(np.asarray(lid, np.uint64))
         self.out = (torch.empty((k, 4), dtype=torch.int64, device=dev), torch.empty((k, D, arity - 1, 4), dtype=torch.int64, device=dev),
                     torch.empty((k, D), dtype=torch.uint8, device=dev), torch.empty((k,), dtype=torch.uint8, device=dev))
         self.back = torch.empty((k, 4), dtype=torch.int64, device=dev)
@@ -127,9 +82,9 @@ def _v2(ctx, a):
     f = Forest(ctx, 4, sizes, top, tid, lid)
     f.extract(), f.rehash(), f.verify()
     torch.cuda.synchronize()
-    same = bool(torch.equal(f.back, f.roots[_dev(tid.astype(np.int64))])) and int(f.ok.sum()) == f.k
-    ms = _median_ms(f.rehash, a.reps)
-    depths = np.array([_depth(int(n), 4) for n in sizes])[tid]
+    same = bool(torch.equal(f.back, f.roots[C.dev(tid.astype(np.int64))])) and int(f.ok.sum()) == f.k
+    ms = C.median_ms(f.rehash, a.reps)
+    depths = TS.depth(sizes, 4)[tid]
     waves = depths[:depths.size // 64 * 64].reshape(-1, 64)
     return f, {"trees": len(sizes), "openings": f.k, "levels": int(depths.sum()), "mean_depth": float(depths.mean()),
                "rehash_ms": ms, "levels_per_s": float(depths.sum()) / ms * 1e3, "roots_match_the_build": same,
@@ -155,7 +110,7 @@ def main():
     if a.v2_only:
         print(json.dumps(_v2(ctx, a)[1]))
         return
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx)}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx)}
 
     # ---- V1: equal depths ----
     for arity, per in ((4, 4 ** 6), (2, 2 ** 12)):
@@ -169,12 +124,12 @@ def main():
         f.extract(), f.rehash(), fixed(), f.verify()
         tf, tr = [], []
         for _ in range(a.reps):  # alternated
-            tf.append(_median_ms(fixed, 1))
-            tr.append(_median_ms(f.rehash, 1))
+            tf.append(C.median_ms(fixed, 1))
+            tr.append(C.median_ms(f.rehash, 1))
         same = bool(torch.equal(exp, f.back)) and int(f.ok.sum()) == k
-        t_ext, t_ver = _median_ms(f.extract, a.reps), _median_ms(f.verify, a.reps)
+        t_ext, t_ver = C.median_ms(f.extract, a.reps), C.median_ms(f.verify, a.reps)
         small = min(1000, k)
-        t_ext_small = _median_ms(lambda: f.extract(small), a.reps)
+        t_ext_small = C.median_ms(lambda: f.extract(small), a.reps)
         mf, mr = float(np.median(tf)), float(np.median(tr))
         per_level = (96 + 96 + 1) if arity == 4 else (32 + 32 + 1)
         ext_bytes = k * (D * per_level + 64)
@@ -215,16 +170,16 @@ def main():
     from poseidon252_amd import levels_len
     lo = np.zeros(sub + 1, dtype=np.int64)
     np.cumsum([levels_len(int(n), 4) for n in sizes[:sub]], out=lo[1:])
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     import ctypes
     tp = np.ascontiguousarray(f.tag, dtype=np.uint64).ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
     st = _stream(ctx)
-    idx32 = _dev(lid[:sub].astype(np.uint32))
+    idx32 = C.dev(lid[:sub].astype(np.uint32))
     one_out = torch.zeros((sub, 4), dtype=torch.int64, device="cuda:0")
     one_sib = torch.zeros((sub, f.D, 3, 4), dtype=torch.int64, device="cuda:0")
     one_pos = torch.zeros((sub, f.D), dtype=torch.uint8, device="cuda:0")
     one_ok = torch.zeros(sub, dtype=torch.uint8, device="cuda:0")
-    deps = [_depth(int(n), 4) for n in sizes[:sub]]
+    deps = [TS.depth(int(n), 4) for n in sizes[:sub]]
 
     def each():
         for t in range(sub):
@@ -243,13 +198,13 @@ def main():
         f.extract(sub)
         f.verify(sub)
     each(), one()
-    t_each, t_one = _median_ms(each, max(1, min(a.reps, 3))), _median_ms(one, a.reps)
+    t_each, t_one = C.median_ms(each, max(1, min(a.reps, 3))), C.median_ms(one, a.reps)
     same = int(one_ok.sum()) == sub and int(f.ok[:sub].sum()) == sub and bool(torch.equal(one_out, f.out[0][:sub]))
     res["per_tree"] = {"subset": sub, "single_calls_ms": t_each, "forest_calls_ms": t_one, "ms_per_tree_single_calls": t_each / sub,
                        "ms_per_tree_forest_calls": t_one / sub, "speedup": t_each / t_one, "identical": same}
     print("per tree (first %d trees of V2, a subset, one opening each): %.3f ms in %d + %d single-tree calls, %.3f ms in one openings + one "
           "verify call: %.1fx  identical %s" % (sub, t_each, sub, sub, t_one, t_each / t_one, same), flush=True)
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     print(json.dumps(res))
 
 

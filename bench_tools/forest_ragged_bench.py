@@ -12,44 +12,11 @@ perm/s = sum of levels_len(n_t) / time, against one p252_merkle4_tree_device cal
 import argparse
 import ctypes
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _median_ms(fn, reps):
-    import torch
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
-
-
-def _offsets(sizes):
-    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
-    return off
-
-
-def _clock_mhz(ctx):
-    """shader clock of one probe wave (MHz), or None"""
-    import torch
-    try:
-        t = ctx.clock_probe(spin_us=1000)
-        torch.cuda.synchronize()
-        r = ctx.clock_probe_result(t)
-        return round(r["shader_ghz"] * 1e3, 1)
-    except Exception:  # (a measurement aid only)
-        return None
+import _common as C
+from testsupport import treeshape as TS
 
 
 def main():
@@ -68,14 +35,14 @@ def main():
     ctx = P.Context(0)
     L = _lib.lib()
     dev = torch.device("cuda:0")
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx)}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx)}
 
     # ---- W1: equal sizes ----
     for arity, per in ((4, 4 ** 6), (2, 2 ** 12)):
         tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
         n_trees = a.w1_trees
         d = torch.randint(0, 1 << 60, (n_trees * per, 4), dtype=torch.int64, device=dev)
-        d_off = torch.from_numpy(_offsets([per] * n_trees).view(np.int64)).to(dev)
+        d_off = torch.from_numpy(TS.offsets([per] * n_trees).view(np.int64)).to(dev)
         ra = torch.empty((n_trees, 4), dtype=torch.int64, device=dev)
         rb = torch.empty_like(ra)
         forest = lambda: ctx.merkle4_forest_device(tag, d, n_trees, per, ra, arity=arity)  # noqa: E731
@@ -83,8 +50,8 @@ def main():
         forest(), ragged()
         tf, tr = [], []
         for _ in range(a.reps):  # alternated
-            tf.append(_median_ms(forest, 1))
-            tr.append(_median_ms(ragged, 1))
+            tf.append(C.median_ms(forest, 1))
+            tr.append(C.median_ms(ragged, 1))
         same = bool(torch.equal(ra, rb))
         perms = n_trees * levels_len(per, arity)
         mf, mr = float(np.median(tf)), float(np.median(tr))
@@ -100,14 +67,14 @@ def main():
     rng = np.random.default_rng(a.seed)
     top = 4 ** 7
     sizes = np.floor(np.exp(rng.uniform(0, np.log(top + 1), a.w2_trees))).astype(np.int64).clip(1, top)
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     tag = M.merkle4_tag()
     d = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device=dev)
     d_off = torch.from_numpy(off.view(np.int64)).to(dev)
     roots = torch.empty((len(sizes), 4), dtype=torch.int64, device=dev)
     one = lambda: ctx.merkle_forest_ragged_device(tag, d, d_off, len(sizes), top, roots)  # noqa: E731
     one()
-    t_one = _median_ms(one, a.reps)
+    t_one = C.median_ms(one, a.reps)
     perms = int(sum(levels_len(int(n), 4) for n in sizes))
     sub = min(a.per_tree, len(sizes))
     sub_roots = torch.empty((sub, 4), dtype=torch.int64, device=dev)
@@ -121,7 +88,7 @@ def main():
             rc = L.p252_merkle4_tree_device(ctx._h, tp, base + int(off[t]) * 32, int(sizes[t]), sub_roots[t].data_ptr(), None, st)
             assert rc == 0
     each()
-    t_each = _median_ms(each, max(1, min(a.reps, 3)))
+    t_each = C.median_ms(each, max(1, min(a.reps, 3)))
     same = bool(torch.equal(sub_roots, roots[:sub]))
     w1 = res["w1_arity4"]["forest_perm_s"]
     w = {"trees": len(sizes), "leaves": int(off[-1]), "useful_perms": perms, "ragged_ms": t_one, "ragged_perm_s": perms / t_one * 1e3,
@@ -133,7 +100,7 @@ def main():
           "per-tree calls on the first %d (subset): %.3f ms = %.4f ms/tree vs %.5f ms/tree  speedup %.1fx  identical %s"
           % (len(sizes), int(off[-1]), t_one, w["ragged_perm_s"], w["of_w1_forest_rate"], sub, t_each, t_each / sub, t_one / len(sizes),
              w["per_tree_speedup"], same), flush=True)
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     print(json.dumps(res))
 
 

@@ -20,98 +20,27 @@ is what its one-node digest launches, one per level, cost: the fixed cost of a r
 P, the append path with the library named by P252_LIB_PATH: forest_append_bench.py's two headline cases (one 4^12-leaf tree + 2^16
 leaves; 20,000 mixed trees, leaves appended to every tree), append time only.  bench_tools/ab_variants.sh style: run this tool with
 --append-only --label NAME once per library, alternating, and compare the medians with the spread one library shows against itself.
-Prints one line per workload, writes them to --out, and prints a JSON summary last.
-
-The module also holds forest_resize_model, the numpy model of the call that the tests compare it with."""
+Prints one line per workload, writes them to --out, and prints a JSON summary last."""
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from forest_append_bench import Case, _alternate, _clock_mhz, _depth, _dev, good_leaf_counts, level_widths, model_leaves  # noqa: E402,F401
-
-KEEP_ALL = (1 << 64) - 1
-
-
-def forest_resize_model(offsets, n_leaves, max_leaves, keep, add_offsets, n_add, max_leaves_new, arity):
-    """What p252_merkle{4,2}_forest_ragged_resize_device_into does to a forest (offsets: n_trees + 1, or empty for no old forest) given
-    keep (n_trees_new values, or None: every tree whole) and add_offsets (n_trees_new + 1).  Returns forest_append_model's dict — with
-    keep None and no tree dropped, the same values — plus
-      k                   per tree of the new forest: the old leaves it keeps, min(keep[t], n_old[t])
-    leaf_src / node_src name slots of the OLD forest's leaves / levels, or -1 - (index in d_add) / -1 (dirty: hashed).  A node of the
-    new tree is clean iff its index is below floor(k / arity^level) — or the tree is unchanged (k == n_old, m == 0), whose last,
-    partly filled parents are clean as well."""
-    off = [int(x) for x in np.asarray(offsets).reshape(-1)]
-    aoff = [int(x) for x in np.asarray(add_offsets).reshape(-1)]
-    T = len(aoff) - 1
-    old = good_leaf_counts(off, n_leaves, max_leaves) if len(off) > 1 else []
-    n_old = [old[t] if t < len(old) else 0 for t in range(T)]
-    if keep is not None:  # (as uint64, one by one: a list that mixes 2^64 - 1 with small values would become floats in numpy)
-        keep = [int(x) & KEEP_ALL for x in (keep.reshape(-1).tolist() if isinstance(keep, np.ndarray) else keep)]
-        assert len(keep) == T
-    k = list(n_old) if keep is None else [min(x, n) for x, n in zip(keep, n_old)]
-    m, refused, run = [], [], 0
-    for t in range(T):
-        lo, hi = aoff[t], aoff[t + 1]
-        mt = hi - lo
-        ok = hi >= lo and hi <= n_add and k[t] + mt <= max_leaves_new
-        mt = mt if ok else 0
-        if ok and mt and (run > n_add or mt > n_add - run):  # the sum rule: overlapping ranges behind decreasing offsets
-            ok = False
-        run += mt
-        m.append(mt if ok else 0)
-        refused.append(not ok)
-    n_new = [a + b for a, b in zip(k, m)]
-    offsets_new = np.zeros(T + 1, dtype=np.int64)
-    np.cumsum(n_new, out=offsets_new[1:])
-    leaf_src = np.empty(int(offsets_new[-1]), dtype=np.int64)
-    for t in range(T):
-        at = int(offsets_new[t])
-        if k[t]:
-            leaf_src[at:at + k[t]] = off[t] + np.arange(k[t])
-        if m[t]:
-            leaf_src[at + k[t]:at + n_new[t]] = -1 - (aoff[t] + np.arange(m[t]))
-    lo_old = np.zeros(len(old) + 1, dtype=np.int64)
-    np.cumsum([sum(level_widths(n, arity)) for n in old], out=lo_old[1:])
-    lo_new = np.zeros(T + 1, dtype=np.int64)
-    np.cumsum([sum(level_widths(n, arity)) for n in n_new], out=lo_new[1:])
-    node_src = np.full(int(lo_new[-1]), -1, dtype=np.int64)
-    node_id = []
-    dirty, n_hashed = {}, 0
-    for t in range(T):
-        w_new, w_old = level_widths(n_new[t], arity), level_widths(n_old[t], arity)
-        start_new, start_old = int(lo_new[t]), int(lo_old[t]) if t < len(old) else 0
-        unchanged = m[t] == 0 and k[t] == n_old[t]
-        for l, w in enumerate(w_new, 1):
-            clean = w if unchanged else k[t] // arity ** l
-            node_src[start_new:start_new + clean] = start_old + np.arange(clean)
-            node_id += [(t, l, j) for j in range(w)]
-            if w > clean:
-                dirty.setdefault(l, []).extend((t, j) for j in range(clean, w))
-                n_hashed += w - clean
-            start_new += w
-            if l <= len(w_old):
-                start_old += w_old[l - 1]
-    n_bad = sum(1 for t in range(T) if refused[t] or n_new[t] == 0)
-    return {"n_old": n_old, "k": k, "m": m, "refused": refused, "n_new": n_new, "offsets_new": offsets_new, "leaf_src": leaf_src, "lo_new": lo_new,
-            "lo_old": lo_old, "node_src": node_src, "node_id": node_id, "dirty": dirty, "n_hashed": n_hashed, "n_bad": n_bad}
+import _common as C
+from _common import ROOT, Case
+from testsupport import treeshape as TS
+# (the numpy model of the call lived in this module once: its names stay importable from here)
+from testsupport.forestappend import KEEP_ALL, forest_resize_model  # noqa: F401
 
 
-# ---------------------------------------------------------------------------------------------
-# the measurement
-# ---------------------------------------------------------------------------------------------
 class ResizeCase(Case):
-    """forest_append_bench.Case with a kept count per tree: the resize, and the fresh build of its result"""
+    """_common.Case with a kept count per tree: the resize, and the fresh build of its result"""
 
     def __init__(self, ctx, arity, sizes, cuts, adds):
         Case.__init__(self, ctx, arity, sizes, adds)
         sizes, cuts = np.asarray(sizes, dtype=np.int64), np.asarray(cuts, dtype=np.int64)
-        self.d_keep = _dev(sizes - cuts)
+        self.d_keep = C.dev(sizes - cuts)
         self.resize_call = ctx.merkle4_forest_ragged_resize_device if arity == 4 else ctx.merkle2_forest_ragged_resize_device
 
     def append(self, count=False):  # (Case's name for the call under test: _measure and rebuild use it)
@@ -122,7 +51,7 @@ class ResizeCase(Case):
         """roots, and the used part of the levels (the buffers are sized for the uncut forest)"""
         import torch
         torch.cuda.synchronize()
-        used = int(sum(sum(level_widths(int(n), self.arity)) for n in np.diff(self.a_off.cpu().numpy())))
+        used = int(TS.levels_len(np.diff(self.a_off.cpu().numpy()), self.arity).sum())
         return bool(torch.equal(self.a_roots, self.b_roots)) and bool(torch.equal(self.a_lv[:used], self.b_lv[:used]))
 
 
@@ -133,7 +62,7 @@ def _measure(case, reps):
     case.rebuild()
     same = case.identical()
     hashed = int(case.hashed)
-    t_call, t_build = _alternate([case.append, case.rebuild], reps)
+    t_call, t_build = C.alternate([case.append, case.rebuild], reps, C.event_ms)
     torch.cuda.synchronize()
     return {"resize_ms": t_call, "rebuild_ms": t_build, "ratio": t_build / t_call, "digests": hashed, "identical": same}
 
@@ -156,7 +85,7 @@ def _append_only(ctx, a, say):
                        ("mixed", lambda: Case(ctx, 4, sizes, every))):
         c = case()
         c.append()
-        (t,) = _alternate([c.append], a.reps)
+        (t,) = C.alternate([c.append], a.reps, C.event_ms)
         out[name] = t
         del c
         torch.cuda.empty_cache()
@@ -189,7 +118,7 @@ def main():
             fh.write("\n".join(lines) + "\n")
         print(json.dumps(res))
         return
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx), "a": [], "r": []}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx), "a": [], "r": []}
     say("python bench_tools/forest_resize_bench.py --reps %d%s   shader clock before: %s MHz" % (a.reps, " --quick" if a.quick else "", res["clock_mhz_before"]))
 
     # ---- A: one tree rolled back; R: the relocation of its one-leaf rollback ----
@@ -207,7 +136,7 @@ def main():
         src = torch.empty(moved // 2, dtype=torch.uint8, device="cuda:0")
         dst = torch.empty_like(src)
         c.append(count=True), dst.copy_(src)
-        t_move, t_copy = _alternate([c.append, lambda: dst.copy_(src)], a.reps)
+        t_move, t_copy = C.alternate([c.append, lambda: dst.copy_(src)], a.reps, C.event_ms)
         one_leaf = [x for x in res["a"] if x["arity"] == arity and x["removed"] == 1][0]["resize_ms"]
         rr = {"arity": arity, "leaves": n, "bytes": moved, "relocation_ms": t_move, "copy_ms": t_copy, "relocation_tbs": moved / t_move / 1e9,
               "copy_tbs": moved / t_copy / 1e9, "digests": int(c.hashed), "one_leaf_rollback_ms": one_leaf, "one_leaf_digest_launches_ms": one_leaf - t_move}
@@ -215,7 +144,7 @@ def main():
         say("R arity %d, %d leaves, every kept count = the size: %.3f ms (%d digests) for %d bytes read + written = %.2f TB/s (every launch of the call "
             "included)  device-to-device copy of the same bytes %.3f ms = %.2f TB/s  copy/relocation %.2f  the one-leaf rollback above less this: "
             "%.3f ms in %d one-node digest launches" % (arity, n, t_move, rr["digests"], moved, rr["relocation_tbs"], t_copy, rr["copy_tbs"], t_copy / t_move,
-                                                       rr["one_leaf_digest_launches_ms"], _depth(n - 1, arity)))
+                                                       rr["one_leaf_digest_launches_ms"], TS.depth(n - 1, arity)))
         del c, src, dst
         torch.cuda.empty_cache()
 
@@ -249,7 +178,7 @@ def main():
     two_calls()
     torch.cuda.synchronize()
     same = bool(torch.equal(two_roots, one.a_roots)) and bool(torch.equal(two_off, one.a_off))
-    t_one, t_two = _alternate([one.append, two_calls], a.reps)
+    t_one, t_two = C.alternate([one.append, two_calls], a.reps, C.event_ms)
     res["g"] = dict(row, trees=n_trees, swapped=int(cuts.sum()), one_call_ms=t_one, two_calls_ms=t_two, two_equal_one=same)
     say("G reorg: %d trees, %d leaves off and %d on: one call %.3f ms (%d digests)  resize then append %.3f ms  two/one %.2f  fresh build %.3f ms  "
         "build/one %.2f  identical %s, two calls equal one %s" % (n_trees, int(cuts.sum()), int(cuts.sum()), t_one, row["digests"], t_two, t_two / t_one,
@@ -260,7 +189,7 @@ def main():
         rows = [r for r in res["a"] if r["arity"] == arity]
         lose = [r for r in rows if r["ratio"] < 1.0]
         say("arity %d: a fresh build is as quick from %s removed leaves of %d" % (arity, ("%d (1/%d of the tree)" % (lose[0]["removed"], rows[0]["leaves"] // lose[0]["removed"])) if lose else "none of the sweep", rows[0]["leaves"]))
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     say("shader clock after: %s MHz" % res["clock_mhz_after"])
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:

@@ -20,67 +20,12 @@ import argparse
 import ctypes
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def levels_len(sizes, arity):
-    """levels_len of every tree of `sizes` (numpy int64): the nodes above the leaves"""
-    cur = np.asarray(sizes, dtype=np.int64).copy()
-    total = np.zeros_like(cur)
-    while (cur > 1).any():
-        nxt = np.where(cur > 1, (cur + arity - 1) // arity, cur)
-        total += np.where(cur > 1, nxt, 0)
-        cur = nxt
-    return total
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = a.view(np.int64) if a.dtype == np.uint64 else a
-    return torch.from_numpy(a).to("cuda:0")
-
-
-def _event_ms(fn):
-    """one launch of fn between two device events on the current stream"""
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def _alternate(fns, reps):
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            ts[i].append(_event_ms(fn))
-    return [float(np.median(t)) for t in ts]
-
-
-def _clock_mhz(ctx):
-    import torch
-    try:
-        t = ctx.clock_probe(spin_us=1000)
-        torch.cuda.synchronize()
-        return round(ctx.clock_probe_result(t)["shader_ghz"] * 1e3, 1)
-    except Exception:  # (a measurement aid only)
-        return None
+import _common as C
+from _common import ROOT
+from testsupport import treeshape as TS
 
 
 def _hip_runtime():
@@ -101,11 +46,9 @@ class Forest:
         from poseidon252_amd import merkle as M
         sizes = np.asarray(sizes, dtype=np.int64)
         self.sizes, self.T, self.n_leaves, self.max_leaves = sizes, len(sizes), int(sizes.sum()), int(sizes.max())
-        off = np.zeros(self.T + 1, dtype=np.int64)
-        np.cumsum(sizes, out=off[1:])
-        self.d_off = _dev(off)
+        self.d_off = C.dev(TS.offsets(sizes, dtype=np.int64))
         self.d = torch.randint(0, 1 << 60, (self.n_leaves, 4), dtype=torch.int64, device="cuda:0")
-        self.lv = torch.empty((self.n_leaves // (arity - 1) + self.T * _depth(self.max_leaves, arity), 4), dtype=torch.int64, device="cuda:0")
+        self.lv = torch.empty((TS.levels_bound(self.n_leaves, self.T, self.max_leaves, arity), 4), dtype=torch.int64, device="cuda:0")
         self.roots = torch.empty((self.T, 4), dtype=torch.int64, device="cuda:0")
         ctx.merkle_forest_ragged_device(M.merkle4_tag() if arity == 4 else M.merkle2_tag(), self.d, self.d_off, self.T, self.max_leaves, self.roots,
                                         self.lv, arity=arity)
@@ -126,10 +69,10 @@ class Pick:
         sizes = np.concatenate([a.sizes, b.sizes]) if b is not None else a.sizes
         new = sizes[pick]
         self.n_pick, self.leaves, self.max_leaves = len(pick), int(new.sum()), max(a.max_leaves, b.max_leaves if b is not None else 0)
-        self.levels_used = int(levels_len(new, arity).sum())
+        self.levels_used = int(TS.levels_len(new, arity).sum())
         self.bytes = 32 * (self.leaves + self.levels_used + self.n_pick)
-        self.d_pick = _dev(pick)
-        cap = self.leaves // (arity - 1) + self.n_pick * _depth(self.max_leaves, arity)
+        self.d_pick = C.dev(pick)
+        cap = TS.levels_bound(self.leaves, self.n_pick, self.max_leaves, arity)
         new3 = lambda: (torch.zeros((self.leaves, 4), dtype=torch.int64, device="cuda:0"),  # noqa: E731
                         torch.zeros((max(cap, 1), 4), dtype=torch.int64, device="cuda:0"),
                         torch.zeros((self.n_pick, 4), dtype=torch.int64, device="cuda:0"))
@@ -168,7 +111,7 @@ def _measure(p, reps):
     p.rebuild()
     p.copy()
     same = p.outputs_equal()
-    t_sel, t_build, t_copy = _alternate([p.select, p.rebuild, p.copy], reps)
+    t_sel, t_build, t_copy = C.alternate([p.select, p.rebuild, p.copy], reps, C.event_ms)
     torch.cuda.synchronize()
     return {"trees": p.n_pick, "leaves": p.leaves, "bytes": p.bytes, "select_ms": t_sel, "rebuild_ms": t_build, "copy_ms": t_copy,
             "rebuild_over_select": t_build / t_sel, "select_gbs": 2 * p.bytes / t_sel / 1e6, "copy_gbs": 2 * p.bytes / t_copy / 1e6,
@@ -194,7 +137,7 @@ def main():
         print(s, flush=True)
         lines.append(s)
     cases = [c for c in a.cases.split(",") if c]
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx), "cases": {}}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx), "cases": {}}
     say("python bench_tools/forest_select_bench.py --reps %d --cases %s%s   shader clock before: %s MHz"
         % (a.reps, a.cases, " --quick" if a.quick else "", res["clock_mhz_before"]))
 
@@ -236,7 +179,7 @@ def main():
         run(case, "merge of two halves", arity, fa, fb, [0, 1])
         del fa, fb
         torch.cuda.empty_cache()
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     say("shader clock after: %s MHz" % res["clock_mhz_after"])
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:

@@ -19,111 +19,21 @@ Prints one line per workload, writes them to --out, and prints a JSON summary la
 import argparse
 import json
 import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _common as C
+from _common import ROOT
+from testsupport import treeshape as TS
+from testsupport.forestupdate import dirty_nodes
 
 
-def _once_ms(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def _alternate(fns, reps):
-    """medians (ms) of the callables, run in turn `reps` times"""
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            ts[i].append(_once_ms(fn))
-    return [float(np.median(t)) for t in ts]
-
-
-def _offsets(sizes):
-    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
-    return off
-
-
-def _clock_mhz(ctx):
-    """shader clock of one probe wave (MHz), or None"""
-    import torch
-    try:
-        t = ctx.clock_probe(spin_us=1000)
-        torch.cuda.synchronize()
-        return round(ctx.clock_probe_result(t)["shader_ghz"] * 1e3, 1)
-    except Exception:  # (a measurement aid only)
-        return None
-
-
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
-    return torch.from_numpy(a).to("cuda:0")
-
-
-def dirty_nodes(sizes, tree_ids, leaf_ids, arity):
-    """the number of DISTINCT nodes above the leaves (tree_ids[i], leaf_ids[i]) of a forest of trees of `sizes` leaves: what one call
-    may hash.  Bad updates (tree id outside the forest, an empty tree, leaf id outside the tree) dirty nothing."""
-    sizes = np.asarray(sizes, dtype=np.int64)
-    tid, lid = np.asarray(tree_ids, dtype=np.int64), np.asarray(leaf_ids, dtype=np.int64)
-    good = (tid >= 0) & (tid < sizes.size)
-    tid, lid = tid[good], lid[good]
-    good = (lid >= 0) & (lid < sizes[tid])
-    tid, lid = tid[good], lid[good]
-    depth_of = np.array([_depth(int(n), arity) for n in sizes], dtype=np.int64)
-    assert sizes.size < 1 << 23 and (sizes.size == 0 or int(sizes.max()) <= 1 << 40)  # (tree, node) packs into one int64
-    total, level = 0, 0
-    while tid.size:
-        level += 1
-        alive = depth_of[tid] >= level  # the tree has a level `level`
-        nodes = np.unique((tid[alive] << 40) | (lid[alive] // arity))
-        total += nodes.size
-        tid, lid = nodes >> 40, nodes & ((1 << 40) - 1)
-    return total
-
-
-class Forest:
-    """a built forest (tree-major levels) on the device"""
-
-    def __init__(self, ctx, arity, sizes, max_leaves):
-        import torch
-        from poseidon252_amd import merkle as M
-        self.ctx, self.arity, self.sizes, self.n_trees, self.max_leaves = ctx, arity, np.asarray(sizes, dtype=np.int64), len(sizes), max_leaves
-        self.tag = M.merkle4_tag() if arity == 4 else M.merkle2_tag()
-        self.off = _offsets(sizes)
-        n_leaves = int(self.off[-1])
-        dev = torch.device("cuda:0")
-        self.d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device=dev)
-        self.d_off = _dev(self.off)
-        self.roots = torch.empty((self.n_trees, 4), dtype=torch.int64, device=dev)
-        self.d_lv = torch.empty((n_leaves // (arity - 1) + self.n_trees * _depth(max_leaves, arity) + 1, 4), dtype=torch.int64, device=dev)
-        self.build()
-
-    def build(self):
-        self.ctx.merkle_forest_ragged_device(self.tag, self.d, self.d_off, self.n_trees, self.max_leaves, self.roots, self.d_lv, arity=self.arity)
-
+class Forest(C.Forest):
     def updater(self, tid, lid, seed=3):
         """the forest call on (tid, lid) with random new leaves -> (callable, the new leaves, d_n_hashed)"""
         import torch
         k = len(tid)
-        d_tid, d_lid = _dev(np.asarray(tid, np.uint32)), _dev(np.asarray(lid, np.uint64))
+        d_tid, d_lid = C.dev(np.asarray(tid, np.uint32)), C.dev(np.asarray(lid, np.uint64))
         g = torch.Generator(device="cuda:0").manual_seed(seed)
         d_new = torch.randint(0, 1 << 60, (k, 4), dtype=torch.int64, device="cuda:0", generator=g)
         hashed = torch.zeros(1, dtype=torch.int64, device="cuda:0")
@@ -143,18 +53,18 @@ def _u1(ctx, n, ks, reps, say):
     for k in ks:
         lid = np.random.default_rng(1).choice(n, k, replace=False)
         new, d_new, hashed = f.updater(np.zeros(k, np.int64), lid)
-        d_idx = _dev(lid.astype(np.uint32))
+        d_idx = C.dev(lid.astype(np.uint32))
         old = lambda: ctx.merkle4_update_device(f.tag, d_b, n, lv_b, d_idx, d_new, k, d_root=root_b)  # noqa: E731
         new(count=True), old()
         torch.cuda.synchronize()
         same = bool(torch.equal(f.d, d_b)) and bool(torch.equal(f.d_lv[:lv_b.shape[0]], lv_b)) and bool(torch.equal(f.roots, root_b))
-        t_old, t_new = _alternate([old, new], reps)
-        dirty, per_level = dirty_nodes([n], np.zeros(k, np.int64), lid, 4), k * _depth(n, 4)
+        t_old, t_new = C.alternate([old, new], reps, C.once_ms)
+        dirty, per_level = dirty_nodes([n], np.zeros(k, np.int64), lid, 4), k * TS.depth(n, 4)
         rows.append({"leaves": n, "k": k, "per_level_ms": t_old, "once_ms": t_new, "ratio": t_old / t_new, "digests_per_level_call": per_level,
                      "digests_once": dirty, "digests_counted_on_device": int(hashed), "count_ratio": per_level / dirty, "identical": same})
         say("U1 4^%d leaves, k = 2^%d: p252_merkle4_update_device %.3f ms (%d digests)  forest update %.3f ms (%d digests, %d counted on the "
             "device)  ratio %.3f (digest counts %.2f)  identical %s"
-            % (_depth(n, 4), int(np.log2(k)), t_old, per_level, t_new, dirty, int(hashed), t_old / t_new, per_level / dirty, same))
+            % (TS.depth(n, 4), int(np.log2(k)), t_old, per_level, t_new, dirty, int(hashed), t_old / t_new, per_level / dirty, same))
     return f, rows
 
 
@@ -178,7 +88,7 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx)}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx)}
     say("python bench_tools/forest_update_bench.py --reps %d%s   shader clock before: %s MHz" % (a.reps, " --quick" if a.quick else "", res["clock_mhz_before"]))
 
     # ---- U1: de-duplication ----
@@ -193,10 +103,10 @@ def main():
         lid = np.random.default_rng(1).choice(n1, k, replace=False)
         new, _, _ = f.updater(np.zeros(k, np.int64), lid)
         new(), f.build()
-        t_new, t_build = _alternate([new, f.build], a.reps)
+        t_new, t_build = C.alternate([new, f.build], a.reps, C.once_ms)
         res["u3"].append({"k": k, "update_ms": t_new, "rebuild_ms": t_build, "ratio": t_build / t_new})
         say("U3 4^%d leaves, k = 4^%d (N/%d): forest update %.3f ms  full rebuild %.3f ms  rebuild/update %.3f"
-            % (_depth(n1, 4), _depth(k, 4), n1 // k, t_new, t_build, t_build / t_new))
+            % (TS.depth(n1, 4), TS.depth(k, 4), n1 // k, t_new, t_build, t_build / t_new))
         k *= 4
     wins = [r["k"] for r in res["u3"] if r["ratio"] < 1.0]
     res["u3_rebuild_wins_from_k"] = wins[0] if wins else None
@@ -225,7 +135,7 @@ def main():
     tp = np.ascontiguousarray(f.tag, dtype=np.uint64).ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
     st = _stream(ctx)
     d_b, lv_b, roots_b = f.d.clone(), f.d_lv.clone(), f.roots.clone()
-    idx32 = _dev(lid.astype(np.uint32))
+    idx32 = C.dev(lid.astype(np.uint32))
 
     def each():
         for t in range(sub):
@@ -237,8 +147,8 @@ def main():
     torch.cuda.synchronize()
     same = (bool(torch.equal(f.roots[:sub], roots_b[:sub])) and bool(torch.equal(f.d_lv[:int(lo[sub])], lv_b[:int(lo[sub])]))
             and bool(torch.equal(f.d[:int(f.off[sub])], d_b[:int(f.off[sub])])))
-    t_new, t_build = _alternate([new, f.build], a.reps)
-    t_each = float(np.median([_once_ms(each) for _ in range(max(1, min(a.reps, 3)))]))
+    t_new, t_build = C.alternate([new, f.build], a.reps, C.once_ms)
+    t_each = float(np.median([C.once_ms(each) for _ in range(max(1, min(a.reps, 3)))]))
     dirty, all_nodes = dirty_nodes(sizes, tid, lid, 4), int(sum(levels_len(int(n), 4) for n in sizes))
     res["u2"] = {"trees": n_trees, "leaves": int(sizes.sum()), "updates": n_trees, "update_ms": t_new, "rebuild_ms": t_build,
                  "per_tree_subset": sub, "per_tree_subset_ms": t_each, "ms_per_tree_single_calls": t_each / sub, "ms_per_tree_forest_call": t_new / n_trees,
@@ -264,14 +174,14 @@ def main():
         f.build()
         torch.cuda.synchronize()
         same = bool(torch.equal(f.roots, fresh_roots)) and bool(torch.equal(f.d_lv[:n2 - 1], fresh_lv[:n2 - 1]))
-        t_new, t_build = _alternate([new, f.build], a.reps)
+        t_new, t_build = C.alternate([new, f.build], a.reps, C.once_ms)
         dirty = dirty_nodes([n2], np.zeros(k, np.int64), lid, 2)
         res["arity2"].append({"leaves": n2, "k": k, "update_ms": t_new, "rebuild_ms": t_build, "ratio": t_build / t_new, "digests_once": dirty,
                               "digests_counted_on_device": int(hashed), "digests_rebuild": n2 - 1, "identical": same})
         say("arity 2, 2^%d leaves, k = 2^%d: forest update %.3f ms (%d digests, %d counted on the device; k per level would be %d)  "
             "full rebuild %.3f ms (%d digests)  rebuild/update %.3f  identical %s"
-            % (_depth(n2, 2), int(np.log2(k)), t_new, dirty, int(hashed), k * _depth(n2, 2), t_build, n2 - 1, t_build / t_new, same))
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+            % (TS.depth(n2, 2), int(np.log2(k)), t_new, dirty, int(hashed), k * TS.depth(n2, 2), t_build, n2 - 1, t_build / t_new, same))
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     say("shader clock after: %s MHz" % res["clock_mhz_after"])
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:

@@ -7,131 +7,19 @@ against the per-leaf calls (p252_merkle{4,2}_openings_device, p252_merkle{4,2}_v
 One arity-4 tree of 4^12 leaves and one arity-2 tree of 2^24 leaves; k = 2^10, 2^14, 2^17, 2^20 random distinct positions (seed 1),
 sorted.  Every shape is warmed up; times are medians of --reps host wall clocks around calls that end in a device synchronise; the
 two sides of a ratio alternate in the one process; every multiproof is verified (ok = 1, root = the tree's) and its length and digest
-count are compared with the numpy model below before it is timed; the shader clock is probed before and after.
-Prints one line per workload, writes them to --out, and prints a JSON summary last.
-
-The numpy model of the proof format (include/poseidon252_hip.h) is here too — multiproof_model, multiproof_extract, multiproof_root —
-for the tests to compare the device's bytes and counts with."""
+count are compared with the numpy model (testsupport/multiproofmodel.py) before it is timed; the shader clock is probed before and after.
+Prints one line per workload, writes them to --out, and prints a JSON summary last."""
 import argparse
 import json
 import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def multiproof_model(n_leaves, positions, arity):
-    """the structure of the shared proof of the strictly ascending `positions` of a tree of n_leaves: (proof_nodes, S, w) with
-    w[l] = nodes of level l, S[l] = the sorted nodes of level l that the verifier knows or computes (S[0] = the positions), and
-    proof_nodes[l] = the nodes of level l the proof holds, in proof order (l = 0 .. depth - 1)"""
-    s = np.asarray(positions, dtype=np.int64).reshape(-1)
-    assert s.size and n_leaves >= 1 and int(s[0]) >= 0 and int(s[-1]) < n_leaves and bool(np.all(np.diff(s) > 0))
-    S, w, proof_nodes = [s], [int(n_leaves)], []
-    while w[-1] > 1:
-        parents = np.unique(S[-1] // arity)
-        slots = (parents[:, None] * arity + np.arange(arity)).reshape(-1)  # parent by parent, slot by slot: the visiting order
-        proof_nodes.append(slots[(slots < w[-1]) & ~np.isin(slots, S[-1])])
-        S.append(parents)
-        w.append((w[-1] + arity - 1) // arity)
-    return proof_nodes, S, w
-
-
-def multiproof_counts(n_leaves, positions, arity):
-    """(proof scalars, digests a verifier computes)"""
-    proof_nodes, S, _ = multiproof_model(n_leaves, positions, arity)
-    return int(sum(p.size for p in proof_nodes)), int(sum(s.size for s in S[1:]))
-
-
-def multiproof_bound(n_leaves, k, arity):
-    """p252_merkle{4,2}_multiproof_bound"""
-    total, w = 0, n_leaves
-    while w > 1:
-        up = (w + arity - 1) // arity
-        total += min((arity - 1) * min(k, up), w - min(k, w))
-        w = up
-    return total
-
-
-def _split_levels(leaves, levels, arity):
-    leaves, levels = np.asarray(leaves).reshape(-1, 4), np.asarray(levels).reshape(-1, 4)
-    per_level, cnt, off = [leaves], leaves.shape[0], 0
-    while cnt > 1:
-        cnt = (cnt + arity - 1) // arity
-        per_level.append(levels[off:off + cnt])
-        off += cnt
-    return per_level
-
-
-def multiproof_extract(leaves, levels, positions, arity):
-    """the proof (len, 4) of `positions` out of a stored tree: leaves (n, 4), levels = the upper levels bottom-up"""
-    per_level = _split_levels(leaves, levels, arity)
-    proof_nodes, _, _ = multiproof_model(per_level[0].shape[0], positions, arity)
-    parts = [per_level[l][nodes] for l, nodes in enumerate(proof_nodes)]
-    return np.concatenate(parts) if parts else np.zeros((0, 4), dtype=per_level[0].dtype)
-
-
-def multiproof_root(n_leaves, positions, leaf_values, proof, arity, digest):
-    """the verifier: the root that (positions, leaf_values (k, 4), proof (len, 4)) re-hash to with digest((m, arity, 4)) -> (m, 4),
-    or None when the structure does not consume exactly len(proof) scalars"""
-    proof_nodes, S, w = multiproof_model(n_leaves, positions, arity)
-    proof = np.asarray(proof, dtype=np.uint64).reshape(-1, 4)
-    if proof.shape[0] != sum(p.size for p in proof_nodes):
-        return None
-    vals, at = np.asarray(leaf_values, dtype=np.uint64).reshape(-1, 4), 0
-    for l, nodes in enumerate(proof_nodes):
-        parents = S[l + 1]
-        children = np.zeros((parents.size * arity, 4), dtype=np.uint64)  # (slots at or past w[l] stay zero)
-        first = parents * arity
-        place = lambda c: np.searchsorted(first, c - c % arity) * arity + c % arity  # noqa: E731
-        children[place(S[l])] = vals
-        children[place(nodes)] = proof[at:at + nodes.size]
-        at += nodes.size
-        vals = np.asarray(digest(children.reshape(parents.size, arity, 4))).reshape(-1, 4)
-    return vals[0]
-
-
-def tree_device(ctx, arity, tag, d_leaves, n, d_root, d_levels):
-    """p252_merkle{4,2}_tree_device on torch's current stream (the Python mirror has the arity-4 call only)"""
-    import ctypes
-    from poseidon252_amd import _lib
-    from poseidon252_amd.hash import _stream
-    L = _lib.lib()
-    fn = L.p252_merkle4_tree_device if arity == 4 else L.p252_merkle2_tree_device
-    tp = np.ascontiguousarray(tag, dtype=np.uint64).ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-    ctx._check(fn(ctx._h, tp, d_leaves.data_ptr(), n, d_root.data_ptr(), d_levels.data_ptr() if d_levels is not None else None, _stream(ctx)))
-
-
-def _once_ms(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def _alternate(fns, reps):
-    """medians (ms) of the callables, run in turn `reps` times"""
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            ts[i].append(_once_ms(fn))
-    return [float(np.median(t)) for t in ts]
-
-
-def _clock_mhz(ctx):
-    """shader clock of one probe wave (MHz), or None"""
-    import torch
-    try:
-        t = ctx.clock_probe(spin_us=1000)
-        torch.cuda.synchronize()
-        return round(ctx.clock_probe_result(t)["shader_ghz"] * 1e3, 1)
-    except Exception:  # (a measurement aid only)
-        return None
+import _common as C
+from _common import ROOT
+from testsupport.device import tree_device
+# (the numpy model lived in this module once: all of its names stay importable from here)
+from testsupport.multiproofmodel import multiproof_bound, multiproof_counts, multiproof_extract, multiproof_model, multiproof_root  # noqa: F401
 
 
 def _tree(ctx, arity, n, say, reps, ks):
@@ -170,8 +58,8 @@ def _tree(ctx, arity, n, say, reps, ks):
         batch()
         torch.cuda.synchronize()
         good = good and int(oks.sum()) == k
-        t_open, t_extract = _alternate([openings, extract], reps)
-        t_batch, t_verify = _alternate([batch, verify], reps)
+        t_open, t_extract = C.alternate([openings, extract], reps, C.once_ms)
+        t_batch, t_verify = C.alternate([batch, verify], reps, C.once_ms)
         per_leaf_scalars, per_leaf_digests = k * depth * (arity - 1), k * depth
         rows.append({"arity": arity, "leaves": n, "k": k, "openings_ms": t_open, "multiproof_ms": t_extract, "extract_ratio": t_open / t_extract,
                      "verify_batch_ms": t_batch, "multiproof_verify_ms": t_verify, "verify_ratio": t_batch / t_verify,
@@ -202,7 +90,7 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    res = {"reps": a.reps, "clock_mhz_before": _clock_mhz(ctx)}
+    res = {"reps": a.reps, "clock_mhz_before": C.clock_mhz(ctx)}
     say("python bench_tools/multiproof_bench.py --reps %d%s   shader clock before: %s MHz" % (a.reps, " --quick" if a.quick else "", res["clock_mhz_before"]))
     ks = [1 << 6, 1 << 10, 1 << 14] if a.quick else [1 << 10, 1 << 14, 1 << 17, 1 << 20]
     if a.only:
@@ -210,7 +98,7 @@ def main():
     else:
         res["rows"] = _tree(ctx, 4, 4 ** 8 if a.quick else 4 ** 12, say, a.reps, ks)
         res["rows"] += _tree(ctx, 2, 2 ** 16 if a.quick else 2 ** 24, say, a.reps, ks)
-    res["clock_mhz_after"] = _clock_mhz(ctx)
+    res["clock_mhz_after"] = C.clock_mhz(ctx)
     say("shader clock after: %s MHz" % res["clock_mhz_after"])
     if not a.only:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

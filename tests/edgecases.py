@@ -12,7 +12,6 @@ A row is data: its name, the callable that makes the GPU calls (and, when asked,
 of the kernels its sizes select under the default environment (launch_merkle4, coop8 and the launchers in csrc/*.hip decide)."""
 import os
 import re
-import sys
 import time
 
 import numpy as np
@@ -20,8 +19,6 @@ import numpy as np
 import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if os.path.join(ROOT, "bench_tools") not in sys.path:
-    sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
 
 P = oracle.P
 R = oracle.R
@@ -239,7 +236,7 @@ def _truncated(x):
 
 
 def _tree_device(ctx, arity, tag, d_leaves, n, d_root, d_levels):
-    from multiproof_bench import tree_device  # p252_merkle{4,2}_tree_device on the current stream
+    from testsupport.device import tree_device  # p252_merkle{4,2}_tree_device on the current stream
     tree_device(ctx, arity, tag, d_leaves, n, d_root, d_levels)
 
 
@@ -642,10 +639,10 @@ def tree_update(run, k, n=4 ** 8, seed=0xA000):
 
 
 def multiproof(run, arity, n, k, seed=0xB000):
-    """one shared proof of k sorted leaves of a tree over edge leaves: the proof is the numpy model's (multiproof_bench.py), it
+    """one shared proof of k sorted leaves of a tree over edge leaves: the proof is the numpy model's (multiproofmodel.py), it
     verifies, still does with its leaves and nodes as unreduced twins, and does not against root + p"""
     import torch
-    from multiproof_bench import multiproof_extract
+    from testsupport.multiproofmodel import multiproof_extract
     raw, red, _ = edge_draw(seed + arity, (n,))
     d, tag = _dev(raw), _mtag(arity)
     root, lv = _empty(4), _empty(_levels_len(n, arity), 4)

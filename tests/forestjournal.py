@@ -3,23 +3,9 @@ level, node) one call must journal, the host bound of their number, and a host r
 level arrays).  Plain Python sets and loops: nothing here shares code with the library."""
 import numpy as np
 
+from testsupport.treeshape import depth, level_starts, level_widths, levels_len
+
 SIZE_MAX = 2 ** 64 - 1
-
-
-def depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def level_counts(n, arity):
-    """nodes of level 0 (the leaves), 1, .. of a tree of n leaves: the last one is 1"""
-    out = [n]
-    while out[-1] > 1:
-        out.append((out[-1] + arity - 1) // arity)
-    return out
 
 
 def journal_entries(sizes, arity, tid, lid):
@@ -57,7 +43,7 @@ def split_levels(levels, sizes, arity):
     """the tree-major d_levels (used part) -> one writable (levels_len(n_t), 4) array per tree"""
     out, at = [], 0
     for n in sizes:
-        ln = sum(level_counts(n, arity)[1:]) if n > 0 else 0
+        ln = levels_len(n, arity)
         out.append(levels[at:at + ln].copy())
         at += ln
     return out
@@ -72,14 +58,14 @@ def swap_host(leaves, off, sizes, levels_per_tree, ids, values, n, arity, roots=
         if level < 0 or t >= len(sizes) or sizes[t] == 0:
             bad += 1
             continue
-        counts = level_counts(int(sizes[t]), arity)
+        counts = [int(sizes[t])] + level_widths(sizes[t], arity)  # nodes of level 0 (the leaves), 1, ..: the last one is 1
         if level >= len(counts) or i >= counts[level]:
             bad += 1
             continue
         if level == 0:
             row = leaves[int(off[t]) + i]
         else:
-            row = levels_per_tree[t][sum(counts[1:level]) + i]
+            row = levels_per_tree[t][level_starts(sizes[t], arity)[level - 1] + i]
         mine = values[g].copy()
         values[g] = row
         row[...] = mine

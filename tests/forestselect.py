@@ -3,26 +3,7 @@ picks are refused, where every picked tree lands, and the numpy gather that turn
 levels and roots.  No torch here: the CPU tests import it too."""
 import numpy as np
 
-
-def levels_len(n, arity):
-    """the nodes above the leaves of a tree of n leaves (p252_merkle{4,2}_levels_len)"""
-    total = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        total += n
-    return total
-
-
-def depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def levels_bound(n_leaves, n_trees, max_leaves, arity):
-    return n_leaves // (arity - 1) + n_trees * depth(max_leaves, arity)
+from testsupport.treeshape import block_starts, levels_len
 
 
 def select_model(arity, sizes_a, bad_a, sizes_b, bad_b, pick, leaves_cap):
@@ -46,7 +27,7 @@ def select_model(arity, sizes_a, bad_a, sizes_b, bad_b, pick, leaves_cap):
         ok = s > 0 and run <= leaves_cap
         source.append(src), tree.append(t), n.append(s if ok else 0), refused.append(not ok)
     offsets_new = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
-    level_starts = np.concatenate([[0], np.cumsum([levels_len(k, arity) for k in n])]).astype(np.uint64)
+    level_starts = block_starts(n, arity, dtype=np.uint64)
     return dict(source=source, tree=tree, n=n, refused=refused, offsets_new=offsets_new, level_starts=level_starts, n_bad=sum(refused))
 
 
@@ -71,4 +52,4 @@ def gather(model, arity, forest_a, forest_b=None):
 def level_starts_of(sizes, bad, arity):
     """the block starts of a source forest's tree-major levels: the prefix sums of levels_len over its trees, bad ones counting 0"""
     bad = set(bad)
-    return np.concatenate([[0], np.cumsum([0 if (t in bad or s <= 0) else levels_len(int(s), arity) for t, s in enumerate(sizes)])]).astype(np.uint64)
+    return block_starts([0 if t in bad else s for t, s in enumerate(sizes)], arity, dtype=np.uint64)

@@ -5,28 +5,21 @@ helper module, imported as edgecases, pymodel and primcases are; no torch at mod
 The forest is built ONCE and never rebuilt: every update, append and resize reads what the call before it wrote (leaves, offsets,
 levels, roots), and after every one of them openings and forest multiproofs are extracted and verified.  What is expected comes from
 the oracle's single-tree builds over the host model's leaves (per tree, cached: a step re-hashes the trees it changed) and from the
-numpy models of bench_tools (forest_resize_model — with keep None the append's — for offsets and counters, dirty_nodes for an update's digests,
+numpy models of testsupport (forest_resize_model — with keep None the append's — for offsets and counters, dirty_nodes for an update's digests,
 forest_multiproof_extract / forest_multiproof_counts for the shared proof) — never from the code under test.
 
   HostForest            arity, max_leaves and one (n_t, 4) uint64 array per tree: the bytes as handed in; update / resize in numpy
   plan(profile, arity)  the deterministic step list (made against the host forest alone) with the facts the conditions are checked on
   Walk / run            carries (d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots) from each call's outputs into the next
                         call's inputs on a backend with Context's methods, and compares after every step"""
-import os
-import sys
-
 import numpy as np
 
 import edgecases as E
-from helpers.forest import SENTINEL, _depth, _levels_bound
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if os.path.join(ROOT, "bench_tools") not in sys.path:
-    sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_append_bench import level_widths  # noqa: E402
-from forest_multiproof_bench import forest_multiproof_counts, forest_multiproof_extract  # noqa: E402
-from forest_resize_bench import KEEP_ALL, forest_resize_model  # noqa: E402
-from forest_update_bench import dirty_nodes  # noqa: E402
+from testsupport.forestappend import KEEP_ALL, forest_resize_model
+from testsupport.forestupdate import dirty_nodes
+from helpers.forest import SENTINEL
+from testsupport.multiproofmodel import forest_multiproof_counts, forest_multiproof_extract
+from testsupport import treeshape as TS
 
 SENT64 = np.uint64(SENTINEL & E.M64)
 TAIL = 5            # rows of sentinel past what a call may use, in every output buffer
@@ -51,15 +44,6 @@ T_ONE, T_ZERO, T_POWER, T_LEFT, T_SAME, T_RIGHT, T_DEEP, T_LEAF, T_EMPTY = 3, 5,
 
 def _empty():
     return np.zeros((0, 4), dtype=np.uint64)
-
-
-def _lo(sizes, arity):
-    """block starts of the tree-major levels: n_trees + 1"""
-    return np.concatenate([[0], np.cumsum([sum(level_widths(int(n), arity)) for n in sizes])]).astype(np.int64)
-
-
-def _offs(sizes, start=0):
-    return (np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]) + start).astype(np.uint64)
 
 
 def _unreduced(i):
@@ -181,7 +165,7 @@ class _Planner:
         for t in borders(T):
             sizes[t] = max(int(sizes[t]), 3)
         flat = self.draw(int(sizes.sum()))
-        off = _offs(sizes).astype(np.int64)
+        off = TS.offsets(sizes).astype(np.int64)
         trees = [flat[off[t]:off[t + 1]] for t in range(T)]
         self.H = HostForest(arity, cfg["max_leaves"], trees)
         self.P = Plan(profile, arity, [t.copy() for t in trees], cfg["max_leaves"])
@@ -196,11 +180,11 @@ class _Planner:
     def _common(self, kind, whole, wrapper):
         H = self.H
         return dict(kind=kind, whole=whole, wrapper=wrapper, T_before=H.n_trees, sizes_before=H.sizes(), maxl_before=H.max_leaves,
-                    D_before=_depth(H.max_leaves, self.a), n_view=self.rows if whole else self.end, dead_rows=self.rows - self.end)
+                    D_before=TS.depth(H.max_leaves, self.a), n_view=self.rows if whole else self.end, dead_rows=self.rows - self.end)
 
     def _done(self, s, changed, pairs):
         H, a = self.H, self.a
-        s.update(T_after=H.n_trees, sizes_after=H.sizes(), maxl_after=H.max_leaves, D_after=_depth(H.max_leaves, a), changed=sorted(changed))
+        s.update(T_after=H.n_trees, sizes_after=H.sizes(), maxl_after=H.max_leaves, D_after=TS.depth(H.max_leaves, a), changed=sorted(changed))
         # what the oracle covers: every tree in `small`; in `wide` the changed trees with the lowest ids and the trees at the tile borders
         if self.wide:
             cover = sorted(set(s["changed"][:ORACLE_CAP]) | {t for t in borders(H.n_trees)})
@@ -263,7 +247,7 @@ class _Planner:
         s = self._common(kind, False, wrapper)
         n_new = len(m)
         max_new = H.max_leaves if max_new is None else max_new
-        aoff = _offs(m)
+        aoff = TS.offsets(m)
         add = self.draw(int(aoff[-1]))
         for j, t in enumerate(one_leaf_new):  # a brand-new tree of exactly one leaf, its limbs >= p
             assert t >= H.n_trees and m[t] == 1
@@ -280,7 +264,7 @@ class _Planner:
         assert not pure or s["n_add"] == 0
         N, T = s["n_view"] + s["n_add"], n_new
         s["dirty_bound_1"] = (s["n_add"] >> self.la) + 2 * T
-        s["bounds"] = [min((s["n_add"] >> (l * self.la)) + 2 * T, (N >> (l * self.la)) + T) for l in range(1, _depth(min(max_new, max(N, 1)), a) + 1)]
+        s["bounds"] = [min((s["n_add"] >> (l * self.la)) + 2 * T, (N >> (l * self.la)) + T) for l in range(1, TS.depth(min(max_new, max(N, 1)), a) + 1)]
         changed = H.resize(s["keep"], add, aoff, n_new, max_new)
         self.end = int(sum(H.sizes()))
         self.rows = N + (0 if wrapper else TAIL)
@@ -312,10 +296,10 @@ def plan(profile, arity, seed=None):
     # 3: a pure rollback through the sizing wrapper: to one leaf, to nothing, to a whole power of the arity (nothing appended), every
     #    deepest tree to a shallower one, one tree unchanged between two changed ones
     sizes = H.sizes()
-    deepest = max(_depth(n, a) for n in sizes)
+    deepest = max(TS.depth(n, a) for n in sizes)
     keep = p.cuts(0.5, spare=(T_SAME,))
     top = a ** (deepest - 1)  # (the largest tree one level shallower)
-    keep.update({t: int(rng.integers(top - 3 if p.wide else 1, top + 1)) for t, n in enumerate(sizes) if _depth(n, a) == deepest})
+    keep.update({t: int(rng.integers(top - 3 if p.wide else 1, top + 1)) for t, n in enumerate(sizes) if TS.depth(n, a) == deepest})
     keep.update({T_ONE: 1, T_ZERO: 0, T_POWER: cfg["sp_keep"], T_LEFT: 5, T_RIGHT: sizes[T_RIGHT] - 1})
     keep.pop(T_SAME, None)
     p.resize("rollback", keep, [0] * H.n_trees, wrapper=True, pure=True)
@@ -399,14 +383,14 @@ class Walk:
     def build(self):
         H, a, B = self.H, self.a, self.B
         sizes = H.sizes()
-        self.off = _offs(sizes, START)
+        self.off = TS.offsets(sizes, START)
         self.end = int(self.off[-1])
         buf = np.full((self.end + TAIL, 4), SENT64, dtype=np.uint64)
         buf[START:self.end] = H.flat()
         self.T, self.maxl, self.sentinel = H.n_trees, H.max_leaves, True
         self.d_leaves, self.d_off = B.dev(buf), B.dev(self.off)
         self.off_buf = self.d_off
-        self.d_levels = self._full(_levels_bound(buf.shape[0], self.T, self.maxl, a) + TAIL, 4)
+        self.d_levels = self._full(TS.levels_bound(buf.shape[0], self.T, self.maxl, a) + TAIL, 4)
         self.roots_buf = self._full(self.T + TAIL, 4)
         self.d_roots = self.roots_buf[:self.T]
         bad = self._zero(np.int32)
@@ -441,7 +425,7 @@ class Walk:
             c["aoff"] = None if s["pure"] else B.dev(s["add_offsets"])
             if not s["wrapper"]:
                 total = c["n_view"] + n_add
-                c["out"] = (self._full(total + TAIL, 4), self._full(T2 + 1 + TAIL), self._full(_levels_bound(total, T2, s["max_leaves_new"], a) + TAIL, 4),
+                c["out"] = (self._full(total + TAIL, 4), self._full(T2 + 1 + TAIL), self._full(TS.levels_bound(total, T2, s["max_leaves_new"], a) + TAIL, 4),
                             self._full(T2 + TAIL, 4))
             aoff = np.zeros(T2 + 1, dtype=np.uint64) if s["pure"] else s["add_offsets"]
             c["changed"] = H.resize(s["keep"], s["add"] if n_add else _empty(), aoff, T2, s["max_leaves_new"])
@@ -495,7 +479,7 @@ class Walk:
             self.d_roots = self.roots_buf[:T2]
             self.sentinel = not s["wrapper"]
             self.T, self.maxl = T2, max_new
-            self.off = _offs(self.H.sizes())
+            self.off = TS.offsets(self.H.sizes())
             self.end = int(self.off[-1])
             c["old_pad"][:m] = old_roots[:m]
         # ---- the read phase, on the view the step's call had (an append / resize: the sliced view of its output) ----
@@ -538,7 +522,7 @@ class Walk:
             at = int(np.nonzero((leaves[lo_:hi_] != H.flat()).any(axis=1))[0][0])
             t = int(np.searchsorted(self.off.astype(np.int64) - lo_, at, side="right") - 1)
             raise AssertionError("the leaves are not the bytes handed in, first at tree %d leaf %d" % (t, at - int(self.off[t]) + lo_))
-        lo = _lo(sizes, a)
+        lo = TS.block_starts(sizes, a)
         used = int(lo[-1])
         H.ensure(cover)
         want_roots = np.stack([H.root(t) for t in cover]) if cover else np.zeros((0, 4), dtype=np.uint64)
@@ -551,7 +535,7 @@ class Walk:
             slot = int(idx[j])
             t = int(np.searchsorted(lo, slot, side="right") - 1)
             p, l = slot - int(lo[t]), 1
-            for w in level_widths(sizes[t], a):
+            for w in TS.level_widths(sizes[t], a):
                 if p < w:
                     break
                 p, l = p - w, l + 1
@@ -560,7 +544,7 @@ class Walk:
         got_roots = roots[:T][cover]
         if not np.array_equal(got_roots, want_roots):
             t = cover[int(np.nonzero((got_roots != want_roots).any(axis=1))[0][0])]
-            raise AssertionError("the roots differ from the oracle, first at (tree %d, level %d, node 0)" % (t, _depth(sizes[t], a)))
+            raise AssertionError("the roots differ from the oracle, first at (tree %d, level %d, node 0)" % (t, TS.depth(sizes[t], a)))
         self.run_same(got_roots, want_roots, "roots")
         # everything at or past the used lengths: still the sentinel behind an append / resize into sentinel buffers; as it was before
         # behind an in-place update
@@ -617,9 +601,9 @@ class Walk:
         raw = np.stack([H.trees[int(t)][int(l)] for t, l in zip(tid, lid)])
         # openings: the leaves' bytes, the depths, the re-hash by the library and by the oracle, the two verdicts
         o_l, o_s, o_p, o_d, D = c["open"]
-        assert D == _depth(self.maxl, a) and B.host(c["o_bad"]).tolist() == [0, 0], "openings: the stride, or a bad opening"
+        assert D == TS.depth(self.maxl, a) and B.host(c["o_bad"]).tolist() == [0, 0], "openings: the stride, or a bad opening"
         assert np.array_equal(B.host(o_l), raw), "openings: the leaves are not the bytes handed in"
-        depths = np.array([_depth(sizes[int(t)], a) for t in tid], dtype=np.int64)
+        depths = np.array([TS.depth(sizes[int(t)], a) for t in tid], dtype=np.int64)
         assert np.array_equal(B.host(o_d).astype(np.int64), depths), "openings: the depths are not depth(n_t)"
         self.run_same(B.host(c["back"]), want_roots, "openings re-hashed")
         sib, pos = B.host(o_s).reshape(k, D, a - 1, 4), B.host(o_p).reshape(k, D)
@@ -632,11 +616,11 @@ class Walk:
                 assert int(ok[1][j]) == int(same), "opening %d of tree %d against the roots before the step: verdict %d, roots %s" % (
                     j, t, int(ok[1][j]), "equal" if same else "differ")
         # the shared proof: bytes, offsets, verdicts, recomputed roots, digests
-        lo = _lo(sizes, a)
+        lo = TS.block_starts(sizes, a)
         model_lv = np.zeros((int(lo[-1]), 4), dtype=np.uint64)
         for t in set(tid.tolist()):
             model_lv[lo[t]:lo[t + 1]] = H.levels(t)
-        want_out, want_proof, want_po = forest_multiproof_extract(H.flat(), _offs(sizes).astype(np.int64), model_lv, tid, lid, a)
+        want_out, want_proof, want_po = forest_multiproof_extract(H.flat(), TS.offsets(sizes).astype(np.int64), model_lv, tid, lid, a)
         assert np.array_equal(want_po, c["po_want"])
         length = int(want_po[-1])
         po, proof, out = B.host(c["mp_po"]), B.host(c["mp_proof"]), B.host(c["mp_out"])

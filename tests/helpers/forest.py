@@ -1,16 +1,13 @@
 """The device helpers of the ragged-forest tests (build, openings, update, append, resize, journal, multiproof, the forest walk):
 one definition of each, on the GPU through the Python binding.  The child processes that the GPU tests start import this module too."""
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_append_bench import model_leaves  # noqa: E402
+from testsupport import treeshape as TS
+from testsupport.forestappend import model_leaves
 # (the numpy model of what one update may hash; tests/test_forest_update_cpu.py checks it)
-from forest_update_bench import dirty_nodes as dirty_count  # noqa: E402,F401
+from testsupport.forestupdate import dirty_nodes as dirty_count  # noqa: F401
 
 SENTINEL = -0x0123456789ABCDEF  # no scalar and no root has these limbs (the top limb is above the modulus')
 
@@ -18,12 +15,6 @@ SENTINEL = -0x0123456789ABCDEF  # no scalar and no root has these limbs (the top
 def _mix(arity):  # tree sizes around every power of the arity that matters, and one tree a level deeper than the rest
     a = arity
     return [1, 2, 3, a, a + 1, a * a - 1, a * a, a * a + 1, 63, 65, (4 ** 5 + 1) if a == 4 else (2 ** 10 + 1)]
-
-
-def _offsets(sizes, start=0):
-    off = np.zeros(len(sizes) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray(sizes, dtype=np.uint64), out=off[1:])
-    return off + np.uint64(start)
 
 
 def _tag(arity):
@@ -46,24 +37,12 @@ def _np(t):
     return a.view(np.uint64) if a.dtype == np.int64 else a
 
 
-def _depth(n, arity):
-    d = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        d += 1
-    return d
-
-
-def _levels_bound(n_leaves, n_trees, max_leaves, arity):
-    return n_leaves // (arity - 1) + n_trees * _depth(max_leaves, arity)
-
-
 def _build(ctx, arity, d_leaves, d_off, n_trees, max_leaves):
     """the forest with its tree-major levels -> (roots, levels)"""
     import torch
     n_leaves = d_leaves.numel() // 4
     roots = torch.full((n_trees, 4), -1, dtype=torch.int64, device=d_leaves.device)
-    d_lv = torch.zeros((max(_levels_bound(n_leaves, n_trees, max_leaves, arity), 1), 4), dtype=torch.int64, device=d_leaves.device)
+    d_lv = torch.zeros((max(TS.levels_bound(n_leaves, n_trees, max_leaves, arity), 1), 4), dtype=torch.int64, device=d_leaves.device)
     ctx.merkle_forest_ragged_device(_tag(arity), d_leaves, d_off, n_trees, max_leaves, roots, d_lv, None, arity=arity)
     return roots, d_lv
 
@@ -102,7 +81,7 @@ def _forest(ctx, arity, flat, off, max_leaves=None, tail=9):
     max_leaves = max_leaves or int(sizes.max())
     d, d_off = _torch(flat), _torch(off)
     roots = torch.full((n_trees, 4), SENTINEL, dtype=torch.int64, device=d.device)
-    d_lv = torch.full((_levels_bound(flat.shape[0], n_trees, max_leaves, arity) + tail, 4), SENTINEL, dtype=torch.int64, device=d.device)
+    d_lv = torch.full((TS.levels_bound(flat.shape[0], n_trees, max_leaves, arity) + tail, 4), SENTINEL, dtype=torch.int64, device=d.device)
     ctx.merkle_forest_ragged_device(_tag(arity), d, d_off, n_trees, max_leaves, roots, d_lv, None, arity=arity)
     return d, d_off, roots, d_lv
 
@@ -136,8 +115,8 @@ def _check_against_fresh_build(ctx, oracle_mod, arity, flat, off, tid, lid, new,
     want = flat.copy()
     want[off[tid].astype(np.int64) + np.asarray(lid, np.int64)] = new
     assert np.array_equal(_np(d), want)
-    _, _, f_roots, f_lv = _forest(ctx, arity, want, off, max_leaves, tail=d_lv.shape[0] - _levels_bound(flat.shape[0], len(sizes),
-                                                                                                      max_leaves or int(sizes.max()), arity))
+    bound = TS.levels_bound(flat.shape[0], len(sizes), max_leaves or int(sizes.max()), arity)
+    _, _, f_roots, f_lv = _forest(ctx, arity, want, off, max_leaves, tail=d_lv.shape[0] - bound)
     torch.cuda.synchronize()
     assert torch.equal(d_lv, f_lv)
     touched = np.zeros(len(sizes), bool)
@@ -160,7 +139,7 @@ class Old:
         self.arity, self.flat, self.off, self.max_leaves, self.n_trees = arity, flat, np.asarray(off, np.uint64), max_leaves, len(off) - 1
         self.d, self.d_off = _torch(flat), _torch(self.off)
         self.roots = torch.full((self.n_trees, 4), SENTINEL, dtype=torch.int64, device=self.d.device)
-        self.d_lv = torch.full((_levels_bound(flat.shape[0], self.n_trees, max_leaves, arity) + 3, 4), SENTINEL, dtype=torch.int64, device=self.d.device)
+        self.d_lv = torch.full((TS.levels_bound(flat.shape[0], self.n_trees, max_leaves, arity) + 3, 4), SENTINEL, dtype=torch.int64, device=self.d.device)
         ctx.merkle_forest_ragged_device(_tag(arity), self.d, self.d_off, self.n_trees, max_leaves, self.roots, self.d_lv, None, arity=arity)
 
 
@@ -168,7 +147,7 @@ def _outputs(arity, total, n_trees_new, max_new, tail=7):
     """sentinel-filled output buffers with `tail` scalars past what the call may use -> (leaves, offsets, levels, roots)"""
     import torch
     full = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.int64, device="cuda:0")  # noqa: E731
-    return full(total + tail, 4), full(n_trees_new + 1 + tail), full(_levels_bound(total, n_trees_new, max_new, arity) + tail, 4), full(n_trees_new + tail, 4)
+    return full(total + tail, 4), full(n_trees_new + 1 + tail), full(TS.levels_bound(total, n_trees_new, max_new, arity) + tail, 4), full(n_trees_new + tail, 4)
 
 
 def _append(ctx, old, d_add, d_aoff, n_trees_new, max_new, out, bad=None, hashed=None):
@@ -250,7 +229,7 @@ def _v2_rate(ctx, reps=7):
     rng = np.random.default_rng(2)
     top = 4 ** 6
     sizes = np.floor(np.exp(rng.uniform(0, np.log(top + 1), 2000))).astype(np.int64).clip(1, top)
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     d = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device="cuda:0")
     d_off = _torch(off)
     roots, d_lv = _build(ctx, 4, d, d_off, len(sizes), top)

@@ -24,11 +24,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
-for _p in (ROOT, os.path.join(ROOT, "bench_tools")):  # (a child process starts from this file alone)
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+if ROOT not in sys.path:  # (a child process starts from this file alone: tests/ is its path already)
+    sys.path.insert(0, ROOT)
 
 import edgecases as E  # noqa: E402
+from testsupport import treeshape as TS  # noqa: E402
 
 NAMES = ("FR_BLOCK", "FR_ITEMS", "FOREST_APPEND_SCAN_TILE", "FA_BLOCK", "MP_BLOCK", "FM_BLOCK", "FM_TREE_ITEMS", "RAGGED_EXACT_BLOCKS")
 ARITIES = (4, 2)
@@ -89,34 +89,6 @@ LIST_CHUNK = max(chunk("k_mp_scan_tiles"), chunk("k_fm_scan_tiles"))
 WIDE_TREES = 2 * TREE_CHUNK + 3 * TREE_TILE + 5
 
 
-def depth(n, arity):
-    d = 0
-    while n > 1:
-        n, d = (n + arity - 1) // arity, d + 1
-    return d
-
-
-def widths(n, arity):
-    """nodes of levels 1, 2, .. of a tree of n leaves, n an array -> a list of arrays (0 where the tree has no such level)"""
-    n = np.asarray(n, dtype=np.int64)
-    out, w = [], n.copy()
-    while int(w.max(initial=0)) > 1:
-        w = np.where(w > 1, (w + arity - 1) // arity, 0)
-        out.append(w)
-    return out
-
-
-def levels_len(n, arity):
-    n = np.asarray(n, dtype=np.int64)
-    return sum(widths(n, arity), np.zeros_like(n))
-
-
-def offsets(sizes):
-    off = np.zeros(len(sizes) + 1, dtype=np.int64)
-    np.cumsum(np.asarray(sizes, dtype=np.int64), out=off[1:])
-    return off
-
-
 def leaves(n, seed):
     """n scalars below 2^252 (every limb below 2^60)"""
     return np.random.default_rng(seed).integers(0, 1 << 60, size=(int(n), 4), dtype=np.uint64)
@@ -159,7 +131,7 @@ def wide_forest(arity, n_trees=None):
             j = int(np.searchsorted(ones, c))
             picks |= {int(ones[j - 1]), int(ones[min(j, ones.size - 1)])}
         f.unreduced = sorted(picks - border)
-        f.arity, f.sizes, f.off, f.max_leaves = arity, sizes, offsets(sizes), top
+        f.arity, f.sizes, f.off, f.max_leaves = arity, sizes, TS.offsets(sizes, dtype=np.int64), top
         f.flat = leaves(f.off[-1], 0xF0 + arity)
         for i, t in enumerate(f.unreduced):
             f.flat[f.off[t]] = E._PAT_RAW[E._BIG[i % len(E._BIG)]]
@@ -180,7 +152,7 @@ def expected_forest(sizes, off, flat, arity, digest):
     numpy and zero-padded, digested level by level with digest((m, arity, 4)) -> (m, 4).  A one-leaf tree's root is its leaf mod p, an
     empty tree's is zero."""
     sizes, off = np.asarray(sizes, dtype=np.int64), np.asarray(off, dtype=np.int64)
-    lo = offsets(levels_len(sizes, arity))
+    lo = TS.block_starts(sizes, arity)
     roots = np.zeros((sizes.size, 4), dtype=np.uint64)
     levels = np.zeros((int(lo[-1]), 4), dtype=np.uint64)
     for n in np.unique(sizes):
@@ -266,7 +238,7 @@ def resize_counts(sizes_old, keep, m, arity):
     n_new = k + m
     unchanged = (m == 0) & (k == n_old)
     hashed = 0
-    for l, w in enumerate(widths(n_new, arity), 1):
+    for l, w in enumerate(TS.level_widths(n_new, arity), 1):
         clean = np.where(unchanged, w, np.minimum(k // arity ** l, w))
         hashed += int((w - clean).sum())
     return n_new, hashed, int((n_new == 0).sum())
@@ -276,7 +248,7 @@ def resize_leaves(off_old, flat, keep_counts, add_off, add):
     """the new forest's leaves: tree t's first keep_counts[t] old leaves, then add[add_off[t]:add_off[t + 1]]"""
     k, m = np.asarray(keep_counts, dtype=np.int64), np.diff(np.asarray(add_off, dtype=np.int64))
     n_new = k + m
-    new_off = offsets(n_new)
+    new_off = TS.offsets(n_new, dtype=np.int64)
     out = np.empty((int(new_off[-1]), 4), dtype=np.uint64)
     T, T_old = k.size, len(off_old) - 1
     old_start = np.zeros(T, dtype=np.int64)
@@ -300,7 +272,7 @@ def wide_append(arity, n_trees=None):
         m[:T] = np.where(rng.random(T) < 0.25, rng.integers(0, 4, T), 0)
         m[trip_borders(T)] = rng.integers(1, 4, len(trip_borders(T)))
         m[T:] = rng.integers(1, f.max_leaves + 1, T_new - T)
-        add_off = offsets(m)
+        add_off = TS.offsets(m, dtype=np.int64)
         return dict(m=m, add_off=add_off, add=leaves(add_off[-1], 0xAD + arity), T_new=T_new, max_new=f.max_leaves + 3, keep=None)
     return _cached(("append", arity, n_trees), make)
 
@@ -325,7 +297,7 @@ def wide_resize(arity, sizes):
         to_zero = np.setdiff1d(rng.choice(T_new, 6, replace=False), b)  # cut to nothing, nothing appended: empty trees, counted bad
         to_zero = np.union1d(to_zero, [T_new - 2])
         keep[to_zero], m[to_zero] = 0, 0
-        add_off = offsets(m)
+        add_off = TS.offsets(m, dtype=np.int64)
         return dict(m=m, add_off=add_off, add=leaves(add_off[-1], 0x2E + arity), T_new=T_new, max_new=int(sizes_.max()) + 2, keep=keep,
                     to_one=to_one, to_zero=to_zero)
     return _cached(("resize", arity, len(sizes)), make)
@@ -357,7 +329,7 @@ def single_positions(arity, case):
 
 # ---------------------------------------------------------------------------------------------- forest multiproofs
 def forest_multiproof_fast(sizes, tid, lid, arity, off=None, flat=None, lo=None, levels=None):
-    """forest_multiproof_counts and forest_multiproof_extract of bench_tools, vectorised over all trees at once -> dict(po (T + 1,)
+    """forest_multiproof_counts and forest_multiproof_extract of multiproofmodel, vectorised over all trees at once -> dict(po (T + 1,)
     uint64, hashed, counts [|S_0|, |S_1|, ..] (the lists the device walks), and with the forest given: out (k, 4), proof (len, 4))"""
     sizes = np.asarray(sizes, dtype=np.int64)
     t, node = np.asarray(tid, dtype=np.int64).reshape(-1), np.asarray(lid, dtype=np.int64).reshape(-1)
@@ -411,7 +383,7 @@ class FmCase:
 
 def _case(arity, sizes, tid, lid, victim, big=None, seed=0):
     c = FmCase()
-    c.arity, c.sizes, c.off, c.max_leaves = arity, np.asarray(sizes, dtype=np.int64), offsets(sizes), int(np.max(sizes))
+    c.arity, c.sizes, c.off, c.max_leaves = arity, np.asarray(sizes, dtype=np.int64), TS.offsets(sizes, dtype=np.int64), int(np.max(sizes))
     c.tid, c.lid, c.victim, c.big, c.seed = np.asarray(tid, dtype=np.int64), np.asarray(lid, dtype=np.int64), int(victim), big, seed
     return c
 
@@ -498,7 +470,7 @@ def ragged_batch(n, seed=0):
     lens = rng.integers(1, 43, n)
     at = np.sort(rng.choice(n, len(RAGGED_LONG), replace=False))
     lens[at] = RAGGED_LONG
-    off = offsets(lens).astype(np.uint64)
+    off = TS.offsets(lens)
     return leaves(int(off[-1]), 0x7A + n), off, lens
 
 
@@ -526,10 +498,6 @@ def _call(ctx, arity, stem):
     return getattr(ctx, "merkle%d_forest_ragged_%s" % (arity, stem))
 
 
-def levels_bound(n_leaves, n_trees, max_leaves, arity):
-    return max(n_leaves // (arity - 1) + n_trees * depth(max_leaves, arity), 1)
-
-
 def run_build(ctx, arity, flat, off, max_leaves, want_levels=True, d=None):
     """one build into sentinel buffers -> (d_leaves, d_off, d_roots, d_levels or None, n_bad)"""
     import torch
@@ -537,7 +505,7 @@ def run_build(ctx, arity, flat, off, max_leaves, want_levels=True, d=None):
     d = E._dev(flat) if d is None else d
     d_off = E._dev(np.asarray(off, dtype=np.uint64))
     roots = torch.full((T, 4), SENTINEL, dtype=torch.int64, device=d.device)
-    lv = torch.full((levels_bound(flat.shape[0], T, max_leaves, arity), 4), SENTINEL, dtype=torch.int64, device=d.device) if want_levels else None
+    lv = torch.full((max(TS.levels_bound(flat.shape[0], T, max_leaves, arity), 1), 4), SENTINEL, dtype=torch.int64, device=d.device) if want_levels else None
     bad = torch.zeros(1, dtype=torch.int32, device=d.device)
     ctx.merkle_forest_ragged_device(E._mtag(arity), d, d_off, T, max_leaves, roots, lv, bad, arity=arity)
     torch.cuda.synchronize()
@@ -552,7 +520,7 @@ def run_resize(ctx, arity, old, step, n_leaves_old):
     T2, max_new, n_add = step["T_new"], step["max_new"], int(step["add_off"][-1])
     total = n_leaves_old + n_add
     full = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.int64, device=d.device)  # noqa: E731
-    o_leaves, o_off, o_lv, o_roots = full(total, 4), full(T2 + 1), full(levels_bound(total, T2, max_new, arity), 4), full(T2, 4)
+    o_leaves, o_off, o_lv, o_roots = full(total, 4), full(T2 + 1), full(max(TS.levels_bound(total, T2, max_new, arity), 1), 4), full(T2, 4)
     bad, hashed = torch.zeros(1, dtype=torch.int32, device=d.device), torch.zeros(1, dtype=torch.int64, device=d.device)
     args = (E._mtag(arity), d, d_off, T, maxl, d_lv)
     keep = () if step["keep"] is None else (E._dev(step["keep"]),)
@@ -624,7 +592,7 @@ def child(what, arity, out_dir):
     if what == "build":
         f = wide_forest(arity)
         _, _, roots, lv, bad = run_build(ctx, arity, f.flat, f.off, f.max_leaves)
-        used = int(levels_len(f.sizes, arity).sum())
+        used = int(TS.levels_len(f.sizes, arity).sum())
         np.savez(os.path.join(out_dir, "build.npz"), roots=E._host(roots), levels_sha256=_digest_of(E._host(lv)[:used]), bad=bad)
     elif what.startswith("fm:"):
         name = what[3:]

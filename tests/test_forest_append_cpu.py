@@ -6,7 +6,6 @@ forest_append.hip compiles for gfx950 within its resource targets and hashes not
 own; the Python methods validate every buffer before the library is reached and hand the C call the right sizes."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -14,12 +13,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_append_bench import forest_append_model, level_widths, model_leaves  # noqa: E402
+from testsupport.forestappend import forest_append_model, model_leaves  # noqa: E402
 from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
 from helpers.kernel_resources import kernel_resources  # noqa: E402
 from helpers.percall import (ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols,  # noqa: E402
                              refusal_table)
+from testsupport.treeshape import level_widths  # noqa: E402
 
 SYMBOLS = ("p252_merkle4_forest_ragged_append_device_into", "p252_merkle2_forest_ragged_append_device_into")
 N_ARGS = 22

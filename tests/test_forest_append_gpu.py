@@ -1,21 +1,16 @@
 """Leaves appended to the trees of a forest of trees of different sizes (p252_merkle{4,2}_forest_ragged_append_device_into;
 csrc/forest_append.hip) on the GPU.  The reference of every comparison is a fresh merkle_forest_ragged_device build of the new forest
-as the numpy model (bench_tools/forest_append_bench.py, checked without a GPU) lays it out, plus the oracle on the small trees — never
+as the numpy model (testsupport/forestappend.py, checked without a GPU) lays it out, plus the oracle on the small trees — never
 the append itself: offsets, leaves, levels, roots, the digest count and the bad count; clean nodes moved and not hashed again; refused
 appends; both digest kernels and more trees than one scan tile; two appends in a row, openings and updates of the grown forest; two
 streams, graph capture, the C++ mirror."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-from helpers.forest import SENTINEL, Grown, Old, _append, _fresh, _np, _offsets, _open, _outputs, _tag, _torch, _tree, _verify
+from testsupport.forestappend import forest_append_model, model_leaves
+from helpers.forest import SENTINEL, Grown, Old, _append, _fresh, _np, _open, _outputs, _tag, _torch, _tree, _verify
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_append_bench import forest_append_model, level_widths, model_leaves  # noqa: E402
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -65,9 +60,9 @@ def _mixed(arity):
 @pytest.mark.parametrize("arity", [4, 2])
 def test_mixed_forest_equals_a_fresh_build(gpu_ctx, oracle_mod, arity):
     sizes, adds = _mixed(arity)
-    off = _offsets(sizes, start=5)  # offsets[0] != 0
+    off = TS.offsets(sizes, start=5)  # offsets[0] != 0
     flat = oracle_mod.fill_random(0xA00 + arity, int(off[-1]) + 3)
-    aoff = _offsets(adds)
+    aoff = TS.offsets(adds)
     add = oracle_mod.fill_random(0xA10 + arity, int(aoff[-1]))
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 64, add, aoff, 264)
     assert len(adds) == len(sizes) + 3 and M["n_bad"] == 1 and not any(M["refused"])  # (the tree that stays empty)
@@ -84,11 +79,11 @@ def test_mixed_forest_equals_a_fresh_build(gpu_ctx, oracle_mod, arity):
 def test_clean_nodes_are_moved_and_dirty_ones_hashed_from_what_lies_below(gpu_ctx, oracle_mod, arity):
     import torch
     sizes, adds = _mixed(arity)
-    off, aoff = _offsets(sizes, start=2), _offsets(adds)
+    off, aoff = TS.offsets(sizes, start=2), TS.offsets(adds)
     flat = oracle_mod.fill_random(0xA20 + arity, int(off[-1]))
     add = oracle_mod.fill_random(0xA30 + arity, int(aoff[-1]))
     old = Old(gpu_ctx, arity, flat, off, 64)
-    used_old = sum(sum(level_widths(n, arity)) for n in sizes)
+    used_old = sum(sum(TS.level_widths(n, arity)) for n in sizes)
     # junk that no digest equals, one value per slot, each a valid scalar (the top limb is below the modulus')
     junk = np.zeros((old.d_lv.shape[0], 4), dtype=np.uint64)
     junk[:, 0], junk[:, 1], junk[:, 3] = np.arange(1, junk.shape[0] + 1), 0x1111, 0x0123456789ABCDEF
@@ -105,7 +100,7 @@ def test_clean_nodes_are_moved_and_dirty_ones_hashed_from_what_lies_below(gpu_ct
     n_clean = 0
     for t, n in enumerate(M["n_new"]):
         below, at = leaves[int(M["offsets_new"][t]):int(M["offsets_new"][t]) + n], int(M["lo_new"][t])
-        for w in level_widths(n, arity):
+        for w in TS.level_widths(n, arity):
             kids = np.zeros((w * arity, 4), dtype=np.uint64)
             kids[:below.shape[0]] = below
             digests = oracle_mod.hash_batch(_tag(arity), kids.reshape(w, arity, 4), arity, 1).reshape(w, 4)
@@ -123,7 +118,7 @@ def test_clean_nodes_are_moved_and_dirty_ones_hashed_from_what_lies_below(gpu_ct
 @pytest.mark.parametrize("arity", [4, 2])
 def test_refused_appends_keep_the_tree_and_are_counted_once(gpu_ctx, oracle_mod, arity):
     sizes = [10, 20, 5, 30, 8]
-    off = _offsets(sizes, start=1)
+    off = TS.offsets(sizes, start=1)
     flat = oracle_mod.fill_random(0xA40 + arity, int(off[-1]) + 2)
     # tree 1: decreasing offsets; tree 2: accepted (its range overlaps tree 0's); tree 3: 30 + 6 > max_leaves_new; tree 4: past n_add;
     # tree 5 (new): decreasing, and empty as well — counted once
@@ -151,8 +146,8 @@ def test_a_level_too_wide_for_the_lane_groups(gpu_ctx, oracle_mod, arity):
     n, m = (1 << 15) + 7, 1 << 15
     assert (m >> (2 if arity == 4 else 1)) + 2 > 8192
     flat, add = oracle_mod.fill_random(0xA60 + arity, n), oracle_mod.fill_random(0xA70 + arity, m)
-    old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, _offsets([n]), n, add, _offsets([m]), n + m, oracle_up_to=1 << 17)
-    assert M["n_hashed"] == sum(-(-(n + m) // arity ** l) - n // arity ** l for l in range(1, len(level_widths(n + m, arity)) + 1))
+    old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, TS.offsets([n]), n, add, TS.offsets([m]), n + m, oracle_up_to=1 << 17)
+    assert M["n_hashed"] == sum(-(-(n + m) // arity ** l) - n // arity ** l for l in range(1, len(TS.level_widths(n + m, arity)) + 1))
 
 
 @pytest.mark.parametrize("arity", [4, 2])
@@ -161,7 +156,7 @@ def test_more_trees_than_one_scan_tile(gpu_ctx, oracle_mod, arity):
     T = SCAN_TILE + 1
     sizes, adds = rng.integers(1, 6, T).tolist(), rng.integers(0, 4, T).tolist()
     sizes[SCAN_TILE - 1], sizes[SCAN_TILE], adds[SCAN_TILE - 1], adds[SCAN_TILE] = 5, 3, 2, 3  # both sides of the tile's edge grow
-    off, aoff = _offsets(sizes), _offsets(adds)
+    off, aoff = TS.offsets(sizes), TS.offsets(adds)
     flat, add = oracle_mod.fill_random(0xA80 + arity, int(off[-1])), oracle_mod.fill_random(0xA90 + arity, int(aoff[-1]))
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 5, add, aoff, 8, oracle_up_to=0)
     tree, roots, leaves = _tree(oracle_mod, arity), _np(out[3]), _np(out[0])
@@ -177,7 +172,7 @@ def test_two_appends_equal_one_and_the_grown_forest_is_an_ordinary_forest(gpu_ct
     sizes = [1, 4, 5, 16, 0, 33, 64, 2]
     x, y = [3, 0, 1, 5, 2, 0, 1, 9, 4], [1, 7, 0, 4, 0, 0, 64, 1, 0, 6]  # the first call adds one tree, the second another
     T1, T2 = len(x), len(y)
-    off, xoff, yoff = _offsets(sizes, start=3), _offsets(x), _offsets(y)
+    off, xoff, yoff = TS.offsets(sizes, start=3), TS.offsets(x), TS.offsets(y)
     flat = oracle_mod.fill_random(0xAA0 + arity, int(off[-1]))
     ax, ay = oracle_mod.fill_random(0xAB0 + arity, int(xoff[-1])), oracle_mod.fill_random(0xAC0 + arity, int(yoff[-1]))
     old = Old(gpu_ctx, arity, flat, off, 64)
@@ -189,7 +184,7 @@ def test_two_appends_equal_one_and_the_grown_forest_is_an_ordinary_forest(gpu_ct
     _append(gpu_ctx, g1, _torch(ay), _torch(yoff), T2, 160, out2, None, hashed)
     # the concatenation in one call
     both = [(x[t] if t < T1 else 0) + y[t] for t in range(T2)]
-    boff = _offsets(both)
+    boff = TS.offsets(both)
     ab = np.concatenate([np.concatenate([ax[int(xoff[t]):int(xoff[t + 1])] if t < T1 else ax[:0], ay[int(yoff[t]):int(yoff[t + 1])]]) for t in range(T2)])
     M = forest_append_model(off, flat.shape[0], 64, boff, ab.shape[0], 160, arity)
     out12 = _outputs(arity, flat.shape[0] + ab.shape[0], T2, 160)
@@ -225,7 +220,7 @@ def test_merkle_forest_ragged_append_sizes_and_returns_the_new_forest(gpu_ctx, o
     import torch
     from poseidon252_amd import merkle
     sizes, adds = [3, 1, 17], [2, 0, 5, 4]
-    off, aoff = _offsets(sizes), _offsets(adds)
+    off, aoff = TS.offsets(sizes), TS.offsets(adds)
     flat, add = oracle_mod.fill_random(0xAE0, int(off[-1])), oracle_mod.fill_random(0xAE1, int(aoff[-1]))
     for arity in (4, 2):
         old = Old(gpu_ctx, arity, flat, off, 17)
@@ -251,7 +246,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
     for j, (arity, sizes) in enumerate(((4, [3000, 7, 900, 1] * 10), (2, [65, 1024, 2, 300] * 10))):
         rng = np.random.default_rng(j)
         adds = rng.integers(0, 400, len(sizes) + 2).tolist()
-        off, aoff = _offsets(sizes), _offsets(adds)
+        off, aoff = TS.offsets(sizes), TS.offsets(adds)
         flat, add = oracle_mod.fill_random(0xAF0 + j, int(off[-1])), oracle_mod.fill_random(0xAF8 + j, int(aoff[-1]))
         old = Old(gpu_ctx, arity, flat, off, max(sizes))
         T, max_new = len(adds), max(sizes) + 400
@@ -279,7 +274,7 @@ def test_graph_capture_replays_on_new_leaves(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = [1, 5, 17, 256, 1000, 3, 64, 0] * 10
     adds = np.random.default_rng(arity).integers(0, 40, len(sizes) + 1).tolist()
-    off, aoff = _offsets(sizes), _offsets(adds)
+    off, aoff = TS.offsets(sizes), TS.offsets(adds)
     flat, add = oracle_mod.fill_random(0xB00 + arity, int(off[-1])), oracle_mod.fill_random(0xB10 + arity, int(aoff[-1]))
     old = Old(gpu_ctx, arity, flat, off, 1000)
     T, max_new = len(adds), 1040

@@ -21,6 +21,7 @@ from helpers.forest import _mix, dirty_count  # noqa: E402
 from helpers.kernel_resources import kernel_resources  # noqa: E402
 from helpers.percall import (ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols,  # noqa: E402
                              refusal_table)
+from testsupport import treeshape as TS  # noqa: E402
 
 ARGS = {"p252_merkle%d_forest_ragged_%s" % (a, stem): n for a in (4, 2)
         for stem, n in (("journal_bound", 4), ("update_journaled_device_into", 20), ("journal_swap_device_into", 14))}
@@ -95,7 +96,7 @@ def test_host_swap_model_is_an_involution():
     off = np.concatenate([[2], 2 + np.cumsum(sizes)]).astype(np.uint64)
     rng = np.random.default_rng(3)
     leaves = rng.integers(0, 1 << 62, (int(off[-1]) + 1, 4)).astype(np.uint64)
-    levels = [rng.integers(0, 1 << 62, (sum(FJ.level_counts(n, arity)[1:]) if n else 0, 4)).astype(np.uint64) for n in sizes]
+    levels = [rng.integers(0, 1 << 62, (TS.levels_len(n, arity), 4)).astype(np.uint64) for n in sizes]
     want = sorted(FJ.journal_entries(sizes, arity, [0, 2, 2, 4, 4, 9, 3], [0, 16, 3, 63, 0, 0, 0]), key=lambda e: (e[1], e[0], e[2]))
     ids = np.array([[t, lv + 1, i & 0xFFFFFFFF, i >> 32] for t, lv, i in want] + [[0, 0, 0, 0], [1, 4, 0, 0], [2, 1, 17, 0], [3, 1, 0, 0]], np.uint32)
     values = rng.integers(0, 1 << 62, (len(ids), 4)).astype(np.uint64)

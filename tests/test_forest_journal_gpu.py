@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 import forestjournal as FJ
-from helpers.forest import (SENTINEL, _check_against_fresh_build, _distinct_pairs, _forest, _mix, _np, _offsets, _open, _tag, _torch, _verify,
-                            dirty_count)
+from helpers.forest import SENTINEL, _check_against_fresh_build, _distinct_pairs, _forest, _mix, _np, _open, _tag, _torch, _verify, dirty_count
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +59,7 @@ def _node_rows(entries, sizes, off, arity):
     lo = _lo(sizes, arity)
     rows = []
     for t, level, i in entries:
-        counts = FJ.level_counts(int(sizes[t]), arity)
+        counts = [int(sizes[t])] + TS.level_widths(sizes[t], arity)
         rows.append((level == 0, int(off[t]) + i if level == 0 else int(lo[t]) + sum(counts[1:level]) + i))
     return rows
 
@@ -68,7 +68,7 @@ def _mixed(gpu_ctx, oracle_mod, arity, seed):
     """the forest of the issue: _mix(arity) * 2 shuffled, offsets[0] != 0, sentinel-filled levels with a tail"""
     sizes = _mix(arity) * 2
     np.random.default_rng(arity).shuffle(sizes)
-    off = _offsets(sizes, start=5)
+    off = TS.offsets(sizes, start=5)
     flat = oracle_mod.fill_random(seed + arity, int(off[-1]) + 3)
     return sizes, off, flat, _forest(gpu_ctx, arity, flat, off)
 
@@ -231,7 +231,7 @@ def test_a_forest_of_one_leaf_trees(gpu_ctx, oracle_mod, arity):
     n_trees = 50
     flat = oracle_mod.fill_random(0x1E00 + arity, n_trees)
     flat[3] = P_LIMBS + np.array([7, 0, 0, 0], dtype=np.uint64)  # limbs >= p
-    d, d_off = _torch(flat), _torch(_offsets([1] * n_trees))
+    d, d_off = _torch(flat), _torch(TS.offsets([1] * n_trees))
     built = _sentinel_roots(n_trees, d.device)
     gpu_ctx.merkle_forest_ragged_device(_tag(arity), d, d_off, n_trees, 1, built, None, None, arity=arity)
     tid, lid = np.array([3, 49, 0, 50, 11]), np.array([0, 0, 0, 0, 1])  # (two bad ones)
@@ -268,7 +268,7 @@ def test_one_update_a_short_journal_and_a_long_one(gpu_ctx, oracle_mod, arity):
     pre = _state(d, d_lv, d_roots)
     new = oracle_mod.fill_random(0x1E30 + arity, 1)
     bound = _bound(gpu_ctx, arity, d.shape[0], n_trees, max_leaves, 1)
-    assert bound == 1 + FJ.depth(max_leaves, arity)
+    assert bound == 1 + TS.depth(max_leaves, arity)
     # one entry short: refused, nothing enqueued, nothing changes
     with pytest.raises(ValueError, match="journal_cap %d is below the call's bound of %d" % (bound - 1, bound)):
         _journaled(gpu_ctx, arity, d, d_off, n_trees, max_leaves, d_lv, [big], [sizes[big] - 1], new, d_roots, cap=bound - 1)
@@ -292,7 +292,7 @@ def test_one_wide_tree_both_digest_kernels_and_multi_block_appends(gpu_ctx, orac
     """k = 20,000 distinct leaves of one tree: the level lists pass 8,192 and 16,384 records"""
     import torch
     n = 4 ** 8 if arity == 4 else 2 ** 16
-    off = _offsets([n], start=1)
+    off = TS.offsets([n], start=1)
     flat = oracle_mod.fill_random(0x1E40 + arity, n + 1)
     d, d_off, roots, d_lv = _forest(gpu_ctx, arity, flat, off)
     lid = np.random.default_rng(81 + arity).choice(n, 20000, replace=False)
@@ -328,14 +328,14 @@ def test_a_foreign_journal_writes_only_what_names_a_node_of_the_forest(gpu_ctx, 
     J = _journaled(gpu_ctx, arity, d, d_off, len(sizes), max(sizes), d_lv, tid, lid, oracle_mod.fill_random(0x1F10 + arity, tid.size))
     # the first three trees alone, with their own max_leaves
     small = sizes[:3]
-    s_off = _offsets(small, start=5)
+    s_off = TS.offsets(small, start=5)
     s_flat = flat[:int(s_off[-1]) + 3].copy()
     sd, sd_off, s_roots, sd_lv = _forest(gpu_ctx, arity, s_flat, s_off)
     torch.cuda.synchronize()
     n = int(J["len"])
     # two hand-made ids in the journal's unused tail: level = depth + 2 of tree 0, and node index = the count of tree 2's level 1
-    t2 = FJ.level_counts(small[2], arity)
-    hand = np.array([[0, FJ.depth(small[0], arity) + 2 + 1, 0, 0], [2, 1 + 1 if len(t2) > 1 else 1, t2[1] if len(t2) > 1 else t2[0], 0]], np.uint32)
+    t2 = [small[2]] + TS.level_widths(small[2], arity)
+    hand = np.array([[0, TS.depth(small[0], arity) + 2 + 1, 0, 0], [2, 1 + 1 if len(t2) > 1 else 1, t2[1] if len(t2) > 1 else t2[0], 0]], np.uint32)
     assert n + 2 <= J["cap"]
     J["ids"][n:n + 2] = _torch(hand)
     J["len"] += 2
@@ -361,7 +361,7 @@ def test_a_foreign_journal_writes_only_what_names_a_node_of_the_forest(gpu_ctx, 
 def test_update_and_swap_captured_on_one_stream(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = [1, 5, 17, 256, 1000, 3, 64] * 20
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0x2000 + arity, int(off[-1]))
     d, d_off, roots, d_lv = _forest(gpu_ctx, arity, flat, off)
     n_trees, max_leaves, k = len(sizes), 1000, 3000
@@ -413,7 +413,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
     dev = torch.device("cuda:0")
     jobs = []
     for j, (arity, sizes) in enumerate(((4, [3000, 7, 900, 1] * 10), (2, [65, 1024, 2, 300] * 10))):
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         flat = oracle_mod.fill_random(0x2100 + j, int(off[-1]))
         tid, lid = _distinct_pairs(sizes, np.random.default_rng(j), 6000)
         new = oracle_mod.fill_random(0x2110 + j, tid.size)
@@ -489,7 +489,7 @@ def test_the_swap_is_faster_than_the_re_update_with_the_old_leaves(gpu_ctx):
     import torch
     n, k = 4 ** 8, 1 << 14
     d = torch.randint(0, 1 << 60, (n, 4), dtype=torch.int64, device="cuda:0")
-    d_off = _torch(_offsets([n]))
+    d_off = _torch(TS.offsets([n]))
     roots = torch.zeros((1, 4), dtype=torch.int64, device="cuda:0")
     d_lv = torch.zeros((n // 3 + 8 + 1, 4), dtype=torch.int64, device="cuda:0")
     tag = _tag(4)

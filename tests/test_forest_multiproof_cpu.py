@@ -6,7 +6,6 @@ brute-force set construction and, with the oracle's digest, reproduces the oracl
 mirror validates every buffer before it reaches the library; every host refusal is the recorded one; the C++ mirror test compiles."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -14,13 +13,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_multiproof_bench import (forest_multiproof_bound, forest_multiproof_counts, forest_multiproof_extract,  # noqa: E402
-                                     forest_multiproof_roots)
 from helpers.binding import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
 from helpers.kernel_resources import kernel_resources  # noqa: E402
 from helpers.percall import (ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols,  # noqa: E402
                              refusal_table)
+from testsupport.multiproofmodel import (forest_multiproof_bound, forest_multiproof_counts, forest_multiproof_extract,  # noqa: E402
+                             forest_multiproof_roots)
 import edgecases as E  # noqa: E402
 
 ARGS = {"p252_merkle4_forest_ragged_multiproof_bound": 4, "p252_merkle2_forest_ragged_multiproof_bound": 4,

@@ -1,23 +1,19 @@
 """The shared proof across a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_device_into / _verify_device;
 csrc/forest_multiproof.hip) on the GPU: the proof offsets, the proof's bytes, the leaves, the recomputed roots and the digest count
-against the model (bench_tools/forest_multiproof_bench.py: a composition of the single-tree model), every tree's part against the
+against the model (testsupport/multiproofmodel.py: a composition of the single-tree model), every tree's part against the
 existing single-tree call, the roots against the oracle; forests whose tree borders fall inside and on the edges of the scan tiles and
 that reach both digest kernels; rejection per tree, bad pairs, a short proof buffer, edge values, streams, p252_trim, the conveniences,
 the C++ mirror, and the time against the per-tree loop of the single-tree calls."""
-import os
-import sys
 import time
 
 import numpy as np
 import pytest
 
-from helpers.forest import SENTINEL, _np, _offsets, _single_extract, _single_verify, _tag, _torch
+import edgecases as E
+from helpers.forest import SENTINEL, _np, _single_extract, _single_verify, _tag, _torch
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_multiproof_bench import forest_multiproof_counts, forest_multiproof_extract, forest_pairs_by_tree  # noqa: E402
-import edgecases as E  # noqa: E402
+from testsupport.multiproofmodel import forest_multiproof_counts, forest_multiproof_extract, forest_pairs_by_tree
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -26,27 +22,17 @@ SIZES = [5, 300, 1, 17, 66, 0, 64, 1000, 2, 16]  # (arity 4: 64 and 16 are compl
 _FORESTS = {}
 
 
-def _levels_len(n, arity):
-    total = 0
-    while n > 1:
-        n = (n + arity - 1) // arity
-        total += n
-    return total
-
-
 class Forest:
     """a forest built once with its levels: host copies (leaves, compact tree-major levels, roots) and the device tensors"""
 
     def __init__(self, ctx, arity, sizes, leaves):
         import torch
-        from poseidon252_amd.hash import _ARITIES
         self.arity, self.sizes, self.T, self.top = arity, np.asarray(sizes, dtype=np.int64), len(sizes), int(max(sizes))
-        self.off = _offsets(sizes).astype(np.int64)
+        self.off = TS.offsets(sizes, dtype=np.int64)
         self.n, self.leaves = int(self.off[-1]), leaves
-        self.lo = np.concatenate([[0], np.cumsum([_levels_len(int(n), arity) for n in sizes])]).astype(np.int64)
+        self.lo = TS.offsets(TS.levels_len(sizes, arity), dtype=np.int64)
         self.d, self.d_off = _torch(leaves), _torch(self.off.astype(np.uint64))
-        depth = _ARITIES[arity].depth(self.top)
-        self.d_lv = torch.zeros((max(self.n // (arity - 1) + self.T * depth, 1), 4), dtype=torch.int64, device=self.d.device)
+        self.d_lv = torch.zeros((max(TS.levels_bound(self.n, self.T, self.top, arity), 1), 4), dtype=torch.int64, device=self.d.device)
         self.d_roots = torch.zeros((self.T, 4), dtype=torch.int64, device=self.d.device)
         ctx.merkle_forest_ragged_device(_tag(arity), self.d, self.d_off, self.T, self.top, self.d_roots, d_levels=self.d_lv, arity=arity)
         torch.cuda.synchronize()

@@ -9,8 +9,9 @@ import sys
 import numpy as np
 import pytest
 
-from helpers.forest import _build, _depth, _levels_bound, _median_ms, _mix, _np, _offsets, _open, _tag, _torch, _v2_rate, _verify
+from helpers.forest import _build, _median_ms, _mix, _np, _open, _tag, _torch, _v2_rate, _verify
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +61,7 @@ def _expected(oracle_mod, arity, flat, off, sizes, tree_ids, leaf_ids, D):
         if not sel.size:
             continue
         s, p = (M.merkle4_openings(lv_t, lv, leaf_ids[sel]) if arity == 4 else _merkle2_openings(lv_t, lv, leaf_ids[sel]))
-        d = _depth(n, arity)
+        d = TS.depth(n, arity)
         assert s.shape[1] == d
         e_leaf[sel] = lv_t[leaf_ids[sel]]
         e_sib[sel, :d] = s.reshape(sel.size, d, arity - 1, 4)
@@ -98,7 +99,7 @@ def test_oracle_parity_every_leaf_of_every_tree(gpu_ctx, oracle_mod, tmp_path, a
     import torch
     sizes = _mix(arity) * 2
     np.random.default_rng(arity).shuffle(sizes)
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0x0F0 + arity, int(off[-1]))
     d, d_off = _torch(flat), _torch(off)
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, len(sizes), max(sizes))
@@ -107,7 +108,7 @@ def test_oracle_parity_every_leaf_of_every_tree(gpu_ctx, oracle_mod, tmp_path, a
     ok = _verify(gpu_ctx, arity, o, roots, len(sizes))
     torch.cuda.synchronize()
     D = o["D"]
-    assert D == _depth(max(sizes), arity)
+    assert D == TS.depth(max(sizes), arity)
     e_leaf, e_sib, e_pos, e_dep, e_roots = _expected(oracle_mod, arity, flat, off, sizes, tid, lid, D)
     assert np.array_equal(_np(roots), e_roots)
     assert np.array_equal(_np(o["leaves"]), e_leaf)
@@ -134,7 +135,7 @@ def test_rows_equal_the_single_tree_openings_call(gpu_ctx, oracle_mod, arity):
     import torch
     from poseidon252_amd import levels_len
     sizes = _mix(arity)
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0x51 + arity, int(off[-1]))
     d, d_off = _torch(flat), _torch(off)
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, len(sizes), max(sizes))
@@ -148,7 +149,7 @@ def test_rows_equal_the_single_tree_openings_call(gpu_ctx, oracle_mod, arity):
         idx = torch.arange(n, dtype=torch.int32, device=d.device)
         lv_t = d_lv[int(lo[t]):int(lo[t + 1])] if n > 1 else None
         out, sib, pos, depth = gpu_ctx.merkle4_openings_device(d[a:b], n, lv_t, idx, n, check=True, arity=arity)
-        assert depth == _depth(n, arity) and bool((o["dep"][a:b] == depth).all())
+        assert depth == TS.depth(n, arity) and bool((o["dep"][a:b] == depth).all())
         assert torch.equal(o["leaves"][a:b], out)
         assert torch.equal(o["sib"][a:b, :depth], sib) and torch.equal(o["pos"][a:b, :depth], pos)
         assert not bool(o["sib"][a:b, depth:].any()) and not bool(o["pos"][a:b, depth:].any())
@@ -159,7 +160,7 @@ def test_equal_depths_equal_path_batch_device(gpu_ctx, oracle_mod, arity, per):
     import torch
     n_trees, k = 300, 20000
     flat = oracle_mod.fill_random(0xE7 + arity, per * n_trees)
-    d, d_off = _torch(flat), _torch(_offsets([per] * n_trees))
+    d, d_off = _torch(flat), _torch(TS.offsets([per] * n_trees))
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, n_trees, per)
     rng = np.random.default_rng(5)
     tid, lid = rng.integers(0, n_trees, k), rng.integers(0, per, k)
@@ -200,7 +201,7 @@ def test_negatives(gpu_ctx, oracle_mod, arity):
     torch.cuda.synchronize()
     assert _np(o["bad"]).tolist() == [nb, nb]  # counted once by the extraction, and once by the re-hash
     dep = _np(o["dep"])
-    assert dep[ng:].tolist() == [BAD] * nb and dep[:ng].tolist() == [_depth(good[t][1] - good[t][0], arity) for t in g_tid]
+    assert dep[ng:].tolist() == [BAD] * nb and dep[:ng].tolist() == [TS.depth(good[t][1] - good[t][0], arity) for t in g_tid]
     for key in ("leaves", "sib", "pos", "back"):
         assert not _np(o[key])[ng:].any(), key
     assert _np(ok).tolist() == [1] * ng + [0] * nb
@@ -228,7 +229,7 @@ def test_edge_sizes(gpu_ctx, oracle_mod, arity):
     # D == 0: every tree a single leaf, no levels at all
     n_trees = 50
     flat = oracle_mod.fill_random(0xD0 + arity, n_trees)
-    d, d_off = _torch(flat), _torch(_offsets([1] * n_trees))
+    d, d_off = _torch(flat), _torch(TS.offsets([1] * n_trees))
     roots = torch.zeros((n_trees, 4), dtype=torch.int64, device=d.device)
     gpu_ctx.merkle_forest_ragged_device(_tag(arity), d, d_off, n_trees, 1, roots, None, None, arity=arity)
     tid = np.array([3, 49, 0, 50, 3])
@@ -241,7 +242,7 @@ def test_edge_sizes(gpu_ctx, oracle_mod, arity):
     assert _np(ok).tolist() == [1, 1, 1, 0, 0]
     # a mixed forest: k = 0 (nothing enqueued, the C call takes NULL buffers), k = 1, k = 70,000 (several sort tiles)
     sizes = _mix(arity) * 2
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0xD1 + arity, int(off[-1]))
     d, d_off = _torch(flat), _torch(off)
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, len(sizes), max(sizes))
@@ -269,7 +270,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
     dev = torch.device("cuda:0")
     jobs = []
     for j, (arity, sizes) in enumerate(((4, [3000, 7, 900, 1] * 10), (2, [65, 1024, 2, 300] * 10))):
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         flat = oracle_mod.fill_random(0x5E0 + j, int(off[-1]))
         d, d_off = _torch(flat), _torch(off)
         roots, d_lv = _build(gpu_ctx, arity, d, d_off, len(sizes), max(sizes))
@@ -297,7 +298,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
 def test_graph_capture_of_openings_and_verify_replays_on_new_leaf_ids(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = [1, 5, 17, 256, 1000, 3, 64] * 20
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     d, d_off = _torch(oracle_mod.fill_random(0x61 + arity, int(off[-1]))), _torch(off)
     n_trees, max_leaves, k = len(sizes), 1000, 5000
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, n_trees, max_leaves)
@@ -308,7 +309,7 @@ def test_graph_capture_of_openings_and_verify_replays_on_new_leaf_ids(gpu_ctx, o
         return tid, (rng.random(k) * np.asarray(sizes)[tid]).astype(np.int64)
     tid, lid = draw()
     d_tid, d_lid = _torch(tid.astype(np.uint32)), _torch(lid.astype(np.uint64))
-    D = _depth(max_leaves, arity)
+    D = TS.depth(max_leaves, arity)
     out = (torch.empty((k, 4), dtype=torch.int64, device=d.device), torch.empty((k, D, arity - 1, 4), dtype=torch.int64, device=d.device),
            torch.empty((k, D), dtype=torch.uint8, device=d.device), torch.empty((k,), dtype=torch.uint8, device=d.device))
     ok = torch.zeros(k, dtype=torch.uint8, device=d.device)
@@ -342,9 +343,9 @@ def test_leaf_buffer_past_4_gib(gpu_ctx, oracle_mod, arity):
     import torch
     start = (1 << 27) + 3  # more than 2^27 leaves (4 GiB) before the first tree
     sizes = [1, 9, 1000, 64, 4097]
-    off = _offsets(sizes, start=start)
+    off = TS.offsets(sizes, start=start)
     n_leaves = int(off[-1]) + 5
-    need = n_leaves * 32 + _levels_bound(n_leaves, len(sizes), 4097, arity) * 32 + (1 << 30)
+    need = n_leaves * 32 + TS.levels_bound(n_leaves, len(sizes), 4097, arity) * 32 + (1 << 30)
     free, _ = torch.cuda.mem_get_info()
     if free < need:
         pytest.skip("needs %d GiB of free HBM" % (need >> 30))
@@ -376,7 +377,7 @@ def test_trim_gives_the_scratch_back(oracle_mod):
     ctx = P.Context(0)
     try:
         arity, sizes = 4, [4 ** 5] * 64
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         d, d_off = _torch(oracle_mod.fill_random(0x77, int(off[-1]))), _torch(off)
         roots, d_lv = _build(ctx, arity, d, d_off, len(sizes), max(sizes))
         k = 1 << 21
@@ -424,7 +425,7 @@ def test_v1_equal_depths_keep_the_fixed_depth_rate(gpu_ctx, arity, per):
     import torch
     n_trees, k = 1024, 1 << 18
     d = torch.randint(0, 1 << 60, (n_trees * per, 4), dtype=torch.int64, device="cuda:0")
-    d_off = _torch(_offsets([per] * n_trees))
+    d_off = _torch(TS.offsets([per] * n_trees))
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, n_trees, per)
     rng = np.random.default_rng(1)
     o = _open(gpu_ctx, arity, d, d_off, n_trees, per, d_lv, rng.integers(0, n_trees, k), rng.integers(0, per, k))

@@ -8,7 +8,8 @@ import sys
 import numpy as np
 import pytest
 
-from helpers.forest import _levels_bound, _median_ms, _mix, _np, _offsets, _tag, _torch
+from helpers.forest import _median_ms, _mix, _np, _tag, _torch
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +20,7 @@ def _device_forest(ctx, arity, d_leaves, d_off, n_trees, max_leaves, levels=Fals
     import torch
     n_leaves = d_leaves.numel() // 4
     roots = torch.full((n_trees, 4), -1, dtype=torch.int64, device=d_leaves.device)
-    d_lv = torch.zeros((max(_levels_bound(n_leaves, n_trees, max_leaves, arity), 1), 4), dtype=torch.int64,
+    d_lv = torch.zeros((max(TS.levels_bound(n_leaves, n_trees, max_leaves, arity), 1), 4), dtype=torch.int64,
                        device=d_leaves.device) if levels else None
     d_bad = torch.zeros(1, dtype=torch.int32, device=d_leaves.device) if bad else None
     ctx.merkle_forest_ragged_device(_tag(arity), d_leaves, d_off, n_trees, max_leaves, roots, d_lv, d_bad, arity=arity)
@@ -50,7 +51,7 @@ def test_oracle_parity_roots_and_levels(gpu_ctx, oracle_mod, arity):
     import poseidon252_amd as P
     sizes = _mix(arity) * 2
     np.random.default_rng(arity).shuffle(sizes)
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0xF0 + arity, int(off[-1]))
     tag = _tag(arity)
     tree = oracle_mod.merkle4_tree if arity == 4 else oracle_mod.merkle2_tree
@@ -100,7 +101,7 @@ np.save(%(out)r, roots.cpu().numpy())
 def test_both_kernel_families_equal_single_tree_calls(gpu_ctx, oracle_mod, tmp_path, arity, min_level1):
     import torch
     sizes = _big_mix(arity, min_level1, seed=min_level1 + arity)
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0xB1 + arity, int(off[-1]))
     d, d_off = _torch(flat), _torch(off)
     roots, d_lv, _ = _device_forest(gpu_ctx, arity, d, d_off, len(sizes), max(sizes), levels=True)
@@ -135,7 +136,7 @@ def test_equal_sizes_equal_the_forest(gpu_ctx, oracle_mod, arity, k):
     d = _torch(flat)
     exp = torch.empty((n_trees, 4), dtype=torch.int64, device=d.device)
     gpu_ctx.merkle4_forest_device(_tag(arity), d, n_trees, per, exp, arity=arity)
-    got, _, _ = _device_forest(gpu_ctx, arity, d, _torch(_offsets([per] * n_trees)), n_trees, per)
+    got, _, _ = _device_forest(gpu_ctx, arity, d, _torch(TS.offsets([per] * n_trees)), n_trees, per)
     assert torch.equal(got, exp)
 
 
@@ -143,7 +144,7 @@ def test_modes_agree_and_edge_calls(gpu_ctx, oracle_mod):
     import torch
     import poseidon252_amd as P
     sizes = [5, 1, 17, 64, 300, 2]
-    off = _offsets(sizes, start=3)  # offsets[0] need not be 0
+    off = TS.offsets(sizes, start=3)  # offsets[0] need not be 0
     flat = oracle_mod.fill_random(0xA4, int(off[-1]) + 2)
     host_roots, host_lv, lo = P.merkle_forest_ragged((flat, off), ctx=gpu_ctx, want_levels=True)
     assert np.array_equal(P.merkle_forest_ragged((flat, off), ctx=gpu_ctx), host_roots)
@@ -232,7 +233,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
     dev = torch.device("cuda:0")
     jobs = []
     for k, sizes in enumerate(([3000, 7, 900, 1] * 40, [65, 4096, 2, 300] * 30)):
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         flat = oracle_mod.fill_random(0x5E + k, int(off[-1]))
         jobs.append((sizes, off, flat, _torch(flat), _torch(off)))
     torch.cuda.synchronize()
@@ -250,7 +251,7 @@ def test_graph_capture_replays_on_new_leaves(gpu_ctx, oracle_mod):
     import torch
     import poseidon252_amd as P
     sizes = [1, 5, 17, 256, 1000, 3, 64] * 20
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     n = int(off[-1])
     d = _torch(oracle_mod.fill_random(0x61, n))
     d_off = _torch(off)
@@ -274,7 +275,7 @@ def test_graph_capture_replays_on_new_leaves(gpu_ctx, oracle_mod):
 def test_tree_block_feeds_openings_and_verify(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = [70, 1, 300, 16, 5]
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0x0B + arity, int(off[-1]))
     d, d_off = _torch(flat), _torch(off)
     roots, d_lv, _ = _device_forest(gpu_ctx, arity, d, d_off, len(sizes), 300, levels=True)
@@ -297,7 +298,7 @@ def test_offsets_past_4_gib(gpu_ctx, oracle_mod):
     import torch
     start = (1 << 27) + 3  # more than 2^27 leaves (4 GiB) before the first tree
     sizes = [1, 9, 1000, 64, 4097]
-    off = _offsets(sizes, start=start)
+    off = TS.offsets(sizes, start=start)
     d = torch.zeros((int(off[-1]) + 5, 4), dtype=torch.int64, device="cuda:0")
     d[start:int(off[-1])] = _torch(oracle_mod.fill_random(0x64, int(off[-1]) - start))
     roots, _, _ = _device_forest(gpu_ctx, 4, d, _torch(off), len(sizes), 4097)
@@ -314,7 +315,7 @@ def test_relative_speed_floors(gpu_ctx):
     # W1: equal sizes, the ragged call against the equal-size forest, alternated in one process
     n_trees, per = 1024, 4 ** 6
     d = torch.randint(0, 1 << 60, (n_trees * per, 4), dtype=torch.int64, device="cuda:0")
-    d_off = _torch(_offsets([per] * n_trees))
+    d_off = _torch(TS.offsets([per] * n_trees))
     roots_a = torch.empty((n_trees, 4), dtype=torch.int64, device=d.device)
     roots_b = torch.empty_like(roots_a)
     forest = lambda: gpu_ctx.merkle4_forest_device(tag, d, n_trees, per, roots_a)  # noqa: E731
@@ -330,7 +331,7 @@ def test_relative_speed_floors(gpu_ctx):
     # mixed sizes: one call against one tree call per tree (per tree)
     rng = np.random.default_rng(2)
     sizes = np.exp(rng.uniform(0, np.log(4 ** 5), 2000)).astype(np.int64).clip(1, 4 ** 5).tolist()
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     dm = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device="cuda:0")
     dm_off = _torch(off)
     roots_m = torch.empty((len(sizes), 4), dtype=torch.int64, device=dm.device)

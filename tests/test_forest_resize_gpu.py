@@ -1,23 +1,17 @@
 """A forest of trees of different sizes rolled back, and forward again, in one call
 (p252_merkle{4,2}_forest_ragged_resize_device_into; csrc/forest_append.hip) on the GPU.  The reference of every comparison is a fresh
-merkle_forest_ragged_device build of the new forest as the numpy model (bench_tools/forest_resize_bench.py, checked without a GPU)
+merkle_forest_ragged_device build of the new forest as the numpy model (testsupport/forestappend.py, checked without a GPU)
 lays it out, plus the oracle on the small trees — never the resize itself: leaves, offsets, the used levels and the roots byte for
 byte, the digest count and the bad count; a pure rollback; clean nodes moved and dirty ones hashed from below; trailing trees dropped;
 a dirty list too wide for the lane groups across the scan tiles; composition with the append; openings of the result; graph capture;
 the C++ mirror."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-from helpers.forest import SENTINEL, Grown, Old, _append, _depth, _fresh, _np, _offsets, _open, _outputs, _tag, _torch, _tree, _verify
+from testsupport.forestappend import KEEP_ALL, forest_append_model, forest_resize_model
+from helpers.forest import SENTINEL, Grown, Old, _append, _fresh, _np, _open, _outputs, _tag, _torch, _tree, _verify
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_append_bench import forest_append_model, level_widths  # noqa: E402
-from forest_resize_bench import KEEP_ALL, forest_resize_model  # noqa: E402
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -89,9 +83,9 @@ def _mixed(arity):
 @pytest.mark.parametrize("arity", [4, 2])
 def test_mixed_forest_equals_a_fresh_build(gpu_ctx, oracle_mod, arity):
     sizes, keep, adds = _mixed(arity)
-    off = _offsets(sizes, start=5)  # offsets[0] != 0
+    off = TS.offsets(sizes, start=5)  # offsets[0] != 0
     flat = oracle_mod.fill_random(0xC00 + arity, int(off[-1]) + 3)
-    aoff = _offsets(adds)
+    aoff = TS.offsets(adds)
     add = oracle_mod.fill_random(0xC10 + arity, int(aoff[-1]))
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 257, keep, add, aoff, 262)
     assert len(sizes) == 39 and M["n_old"] == sizes + [0] and M["m"] == adds and not any(M["refused"])
@@ -116,11 +110,11 @@ def test_pure_rollback_hashes_at_most_one_node_per_tree_and_level(gpu_ctx, oracl
     """n_add == 0 and d_add == NULL: the case an append launcher returns early on"""
     sizes = [300, 17, 64, 5, 1, 16, 2, 1000, 33]
     keep = [299, 16, 64, 1, 1, 4, 0, 257, KEEP_ALL]  # (16 of 17, 4 of 16: the root of the cut tree is a clean node for arity 4 and 2)
-    off = _offsets(sizes, start=1)
+    off = TS.offsets(sizes, start=1)
     flat = oracle_mod.fill_random(0xC20 + arity, int(off[-1]))
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 1000, keep, flat[:0], np.zeros(len(sizes) + 1, np.uint64), 1000, oracle_up_to=300)
     assert M["m"] == [0] * 9 and M["k"] == [299, 16, 64, 1, 1, 4, 0, 257, 33] and M["n_bad"] == 1
-    assert 0 < M["n_hashed"] <= sum(_depth(n, arity) for n in M["n_new"])
+    assert 0 < M["n_hashed"] <= sum(TS.depth(n, arity) for n in M["n_new"])
     assert all(len({t for t, _ in nodes}) == len(nodes) for nodes in M["dirty"].values())  # one node per tree and level at the most
     for t in (2, 4, 8):  # the trees kept whole keep their roots
         assert np.array_equal(_np(out[3])[t], _np(old.roots)[t]), t
@@ -133,7 +127,7 @@ def test_clean_nodes_are_moved_and_dirty_ones_hashed_from_what_lies_below(gpu_ct
     that changes — is overwritten before the call; the result still equals the fresh build"""
     import torch
     sizes, keep, adds = _mixed(arity)
-    off, aoff = _offsets(sizes, start=2), _offsets(adds)
+    off, aoff = TS.offsets(sizes, start=2), TS.offsets(adds)
     flat = oracle_mod.fill_random(0xC30 + arity, int(off[-1]))
     add = oracle_mod.fill_random(0xC40 + arity, int(aoff[-1]))
     old = Old(gpu_ctx, arity, flat, off, 257)
@@ -151,7 +145,7 @@ def test_clean_nodes_are_moved_and_dirty_ones_hashed_from_what_lies_below(gpu_ct
         lo = int(off[t])
         leaves[lo + k:lo + n] = junk_leaves[lo + k:lo + n]
         at = int(M["lo_old"][t])
-        for l, w in enumerate(level_widths(n, arity), 1):
+        for l, w in enumerate(TS.level_widths(n, arity), 1):
             first = k // arity ** l
             levels[at + first:at + w] = junk_levels[at + first:at + w]
             n_dead += w - first
@@ -179,7 +173,7 @@ def test_clean_nodes_are_moved_and_dirty_ones_hashed_from_what_lies_below(gpu_ct
 @pytest.mark.parametrize("arity", [4, 2])
 def test_trailing_trees_are_dropped(gpu_ctx, oracle_mod, arity):
     sizes = [5, 64, 1, 17, 300, 2, 40]
-    off = _offsets(sizes, start=3)
+    off = TS.offsets(sizes, start=3)
     flat = oracle_mod.fill_random(0xC50 + arity, int(off[-1]))
     # nothing else: the survivors unchanged, no digest
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 300, None, flat[:0], np.zeros(5, np.uint64), 300)
@@ -187,7 +181,7 @@ def test_trailing_trees_are_dropped(gpu_ctx, oracle_mod, arity):
     assert np.array_equal(_np(out[3])[:4], _np(old.roots)[:4])
     # dropped while new leaves go to the survivors, one of them cut
     adds = [2, 0, 7, 1, 9]
-    aoff = _offsets(adds)
+    aoff = TS.offsets(adds)
     add = oracle_mod.fill_random(0xC60 + arity, int(aoff[-1]))
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 300, [KEEP_ALL, 60, 1, 17, 256], add, aoff, 300, oracle_up_to=300, old=old)
     assert M["n_new"] == [7, 60, 8, 18, 265] and M["n_bad"] == 0
@@ -202,7 +196,7 @@ def test_a_wide_dirty_level_across_the_scan_tiles(gpu_ctx, oracle_mod, arity):
     2 n_trees_new = 16,600 > 8,192 nodes, so k_fu_digest runs, not the 8-lane kernel — spans every tile boundary"""
     T = 8300
     assert T > 4 * SCAN_TILE and 2 * T > 8192
-    off = _offsets([5] * T)
+    off = TS.offsets([5] * T)
     flat = oracle_mod.fill_random(0xC70 + arity, 5 * T)
     old, M, out = _run(gpu_ctx, oracle_mod, arity, flat, off, 5, [3] * T, flat[:0], np.zeros(T + 1, np.uint64), 5, oracle_up_to=0)
     assert M["n_hashed"] == T * (1 if arity == 4 else 2) and [t for t, _ in M["dirty"][1]] == list(range(T))
@@ -219,7 +213,7 @@ def test_one_call_equals_resize_then_append_and_an_append_is_undone(gpu_ctx, ora
     keep = [1, 2, 5, 4, 0, 32, 63, 0, 100]
     adds = [3, 0, 1, 5, 2, 0, 1, 9, 4, 6]  # (the tenth tree is new)
     T, T2 = len(sizes), len(adds)
-    off, aoff = _offsets(sizes, start=3), _offsets(adds)
+    off, aoff = TS.offsets(sizes, start=3), TS.offsets(adds)
     flat, add = oracle_mod.fill_random(0xC80 + arity, int(off[-1])), oracle_mod.fill_random(0xC90 + arity, int(aoff[-1]))
     old, M, one = _run(gpu_ctx, oracle_mod, arity, flat, off, 257, keep + [0], add, aoff, 300)
     # the same in two calls: cut, then append to the result
@@ -252,7 +246,7 @@ def test_openings_of_the_resized_forest_verify(gpu_ctx, oracle_mod, arity):
     import torch
     from poseidon252_amd import merkle
     sizes, keep, adds = [40, 7, 1, 100, 16], [33, 7, 1, 16, 0], [0, 2, 0, 0, 3]
-    off, aoff = _offsets(sizes), _offsets(adds)
+    off, aoff = TS.offsets(sizes), TS.offsets(adds)
     flat, add = oracle_mod.fill_random(0xCA0 + arity, int(off[-1])), oracle_mod.fill_random(0xCB0 + arity, int(aoff[-1]))
     old = Old(gpu_ctx, arity, flat, off, 100)
     leaves, offsets, levels, roots, bad, hashed = merkle.forest_ragged_resize(gpu_ctx, None, old.d, old.d_off, 5, 100, old.d_lv, _torch(_keep(keep)),
@@ -285,7 +279,7 @@ def test_graph_capture_replays_on_new_leaves_and_new_kept_counts(gpu_ctx, oracle
     adds = rng.integers(0, 40, len(sizes) + 1).tolist()
     keep1 = [int(rng.integers(0, n + 2)) for n in sizes] + [0]
     keep2 = [int(rng.integers(0, n + 2)) for n in sizes] + [0]
-    off, aoff = _offsets(sizes), _offsets(adds)
+    off, aoff = TS.offsets(sizes), TS.offsets(adds)
     flat, add = oracle_mod.fill_random(0xCC0, int(off[-1])), oracle_mod.fill_random(0xCC1, int(aoff[-1]))
     old = Old(gpu_ctx, arity, flat, off, 1000)
     T, max_new = len(adds), 1040

@@ -14,6 +14,7 @@ import forestselect as FS
 from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: F401
 from helpers.kernel_resources import kernel_resources
 from helpers.percall import bench_tool_parses, build_cpp_mirror, check_abi_symbols
+from testsupport import treeshape as TS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
@@ -194,7 +195,7 @@ def test_identity_pick_reproduces_the_source(arity):
     assert np.array_equal(M["level_starts"], FS.level_starts_of(sizes, [], arity))
     from poseidon252_amd import _lib
     ll = _lib.lib().p252_merkle4_levels_len if arity == 4 else _lib.lib().p252_merkle2_levels_len
-    assert [FS.levels_len(n, arity) for n in sizes] == [ll(n) for n in sizes]
+    assert [TS.levels_len(n, arity) for n in sizes] == [ll(n) for n in sizes]
 
 
 @pytest.mark.parametrize("arity", [4, 2])
@@ -204,7 +205,7 @@ def test_duplicates_and_picks_from_b_land_where_levels_len_says(arity):
     M = FS.select_model(arity, sizes_a, [], sizes_b, [], pick, 1000)
     want = [3, 5, 5, 64, 17, 1, 64]
     assert M["n"] == want and M["source"] == [1, 0, 0, 1, 0, 0, 1] and M["tree"] == [1, 0, 0, 0, 2, 1, 0]
-    assert M["level_starts"].tolist() == np.concatenate([[0], np.cumsum([FS.levels_len(n, arity) for n in want])]).tolist()
+    assert M["level_starts"].tolist() == np.concatenate([[0], np.cumsum([TS.levels_len(n, arity) for n in want])]).tolist()
     # the gather, on arrays whose values name their place
     def forest(sizes, base):
         n, lo = sum(sizes), FS.level_starts_of(sizes, [], arity)
@@ -218,7 +219,7 @@ def test_duplicates_and_picks_from_b_land_where_levels_len_says(arity):
     assert np.array_equal(leaves[:3], B[0][64:67]) and np.array_equal(leaves[3:8], A[0][:5]) and np.array_equal(leaves[8:13], A[0][:5])
     j = 4  # tree 2 of A
     lo = int(M["level_starts"][j])
-    assert np.array_equal(levels[lo:lo + FS.levels_len(17, arity)], A[3][int(A[2][2]):int(A[2][3])])
+    assert np.array_equal(levels[lo:lo + TS.levels_len(17, arity)], A[3][int(A[2][2]):int(A[2][3])])
     assert np.array_equal(roots[3], B[4][0]) and np.array_equal(roots[5], A[4][1])
 
 

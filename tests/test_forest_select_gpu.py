@@ -14,9 +14,9 @@ import numpy as np
 import pytest
 
 import forestselect as FS
-from helpers.forest import (SENTINEL, Grown, _append, _build, _forest, _levels_bound, _mix, _np, _offsets, _open, _outputs, _tag, _torch, _tree,
-                            _update, _verify)
+from helpers.forest import SENTINEL, Grown, _append, _build, _forest, _mix, _np, _open, _outputs, _tag, _torch, _tree, _update, _verify
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
+from testsupport import treeshape as TS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,7 @@ class Src:
         sizes = [int(s) for s in sizes]
         self.arity, self.sizes, self.bad, self.n_trees = arity, sizes, set(bad) | {t for t, s in enumerate(sizes) if s == 0}, len(sizes)
         self.max_leaves = max_leaves or max(sizes)
-        self.flat, self.off = oracle_mod.fill_random(seed, sum(sizes)), _offsets(sizes)
+        self.flat, self.off = oracle_mod.fill_random(seed, sum(sizes)), TS.offsets(sizes)
         self.d, self.d_off, self.roots, self.d_lv = _forest(ctx, arity, self.flat, self.off, self.max_leaves)
         self.lo = FS.level_starts_of(sizes, self.bad, arity)
 
@@ -58,7 +58,7 @@ def _method(ctx, arity):
 
 def _select(ctx, arity, A, B, d_pick, n_pick, cap, out, bad):
     max_leaves = max(A.max_leaves, B.max_leaves if B is not None else 0)
-    bound = _levels_bound(cap, n_pick, max_leaves, arity)
+    bound = TS.levels_bound(cap, n_pick, max_leaves, arity)
     _method(ctx, arity)(A.view(), B.view() if B is not None else None, d_pick, n_pick, out[0][:cap], out[1][:n_pick + 1],
                         out[2][:bound] if bound else None, out[3][:n_pick], bad)
 
@@ -91,7 +91,7 @@ def _fresh_like(ctx, arity, out, n_pick, cap, max_leaves):
     import torch
     levels, roots = torch.full_like(out[2], SENTINEL), torch.full_like(out[3], SENTINEL)
     bad = torch.zeros(1, dtype=torch.int32, device="cuda:0")
-    bound = _levels_bound(cap, n_pick, max_leaves, arity)
+    bound = TS.levels_bound(cap, n_pick, max_leaves, arity)
     ctx.merkle_forest_ragged_device(_tag(arity), out[0][:cap], out[1][:n_pick + 1], n_pick, max_leaves, roots[:n_pick], levels[:bound], bad, arity=arity)
     torch.cuda.synchronize()
     return levels, roots, bad
@@ -184,7 +184,7 @@ def test_scan_width(gpu_ctx, arity):
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, T, f.max_leaves)
     pick = torch.arange(T - 1, -1, -1, dtype=torch.int64, device="cuda:0")
     out, bad = _buffers(arity, n_leaves, T, f.max_leaves)
-    bound = _levels_bound(n_leaves, T, f.max_leaves, arity)
+    bound = TS.levels_bound(n_leaves, T, f.max_leaves, arity)
     _method(gpu_ctx, arity)((d, d_off, T, f.max_leaves, d_lv, roots), None, pick, T, out[0][:n_leaves], out[1][:T + 1], out[2][:bound], out[3][:T], bad)
     sizes = _torch(f.sizes.astype(np.int64))
     new_sizes = sizes.flip(0)
@@ -205,20 +205,20 @@ def test_second_tree_past_4_gib(gpu_ctx):
     arity = 4
     n0, n1 = (1 << 27) + 8, 1000  # the second tree starts past 2^27 scalars (4 GiB) in the source; the first tree ends past them in the result
     n_leaves = n0 + n1
-    bound = _levels_bound(n_leaves, 2, n0, arity)
+    bound = TS.levels_bound(n_leaves, 2, n0, arity)
     need = 2 * (n_leaves + bound) * 32 + (2 << 30)
     free, _ = torch.cuda.mem_get_info()
     if free < need:
         pytest.skip("needs %d GiB of free HBM" % (need >> 30))
     d = torch.randint(0, 1 << 60, (n_leaves, 4), dtype=torch.int64, device="cuda:0")
-    d_off = _torch(_offsets([n0, n1]))
+    d_off = _torch(TS.offsets([n0, n1]))
     roots, d_lv = _build(gpu_ctx, arity, d, d_off, 2, n0)
     out = (torch.empty((n_leaves, 4), dtype=torch.int64, device="cuda:0"), torch.full((3 + TAIL,), SENTINEL, dtype=torch.int64, device="cuda:0"),
            torch.empty((bound, 4), dtype=torch.int64, device="cuda:0"), torch.full((2 + TAIL, 4), SENTINEL, dtype=torch.int64, device="cuda:0"))
     bad = torch.zeros(1, dtype=torch.int32, device="cuda:0")
     _method(gpu_ctx, arity)((d, d_off, 2, n0, d_lv, roots), None, _torch(np.array([1, 0], np.uint64)), 2, out[0], out[1][:3], out[2], out[3][:2], bad)
     torch.cuda.synchronize()
-    l0, l1 = FS.levels_len(n0, arity), FS.levels_len(n1, arity)
+    l0, l1 = TS.levels_len(n0, arity), TS.levels_len(n1, arity)
     assert int(bad) == 0 and out[1][:3].tolist() == [0, n1, n1 + n0] and bool((out[1][3:] == SENTINEL).all())
     assert torch.equal(out[3][:2], roots.flip(0)) and bool((out[3][2:] == SENTINEL).all())
     w = 4096
@@ -238,7 +238,7 @@ def test_result_is_an_ordinary_forest(gpu_ctx, oracle_mod, arity):
     cap = sum((A.sizes + B.sizes)[p] for p in pick)
     max_leaves = max(A.max_leaves, B.max_leaves)
     M, out = _run(gpu_ctx, arity, A, B, pick, cap)
-    bound = _levels_bound(cap, n, max_leaves, arity)
+    bound = TS.levels_bound(cap, n, max_leaves, arity)
     sel = Grown(arity, (out[0][:cap], out[1], out[2][:bound], out[3]), n, max_leaves)
     twin_leaves = out[0][:cap].clone()
     twin_roots, twin_lv = _build(gpu_ctx, arity, twin_leaves, sel.d_off, n, max_leaves)
@@ -344,7 +344,7 @@ def test_host_refusals(gpu_ctx, oracle_mod, arity):
     B = Src(gpu_ctx, oracle_mod, arity, [3, 30], 0x5E88 + arity)
     pick = _torch(np.array([5, 0, 3, 1, 1], np.uint64))
     n_pick, cap = 5, 30 + 5 + 9 + 17 + 17 + 2
-    need = _levels_bound(cap, n_pick, 30, arity)
+    need = TS.levels_bound(cap, n_pick, 30, arity)
     out, bad = _buffers(arity, cap, n_pick, 30)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     base = dict(d_leaves_a=A.d.data_ptr(), n_leaves_a=sum(A.sizes), d_offsets_a=A.d_off.data_ptr(), n_trees_a=4, max_leaves_a=17, d_levels_a=A.d_lv.data_ptr(),
@@ -408,7 +408,7 @@ def test_python_helper_allocates_the_new_forest(gpu_ctx, oracle_mod, arity):
     leaves, off, levels, roots, bad = merkle.forest_ragged_select(gpu_ctx, A.view(), pick, B.view(), arity=arity)
     torch.cuda.synchronize()
     want_leaves, want_levels, want_roots = FS.gather(M, arity, A.host(), B.host())
-    assert leaves.shape[0] == sum(A.sizes) + sum(B.sizes) and levels.shape[0] == _levels_bound(leaves.shape[0], len(pick), max(A.max_leaves, B.max_leaves), arity)
+    assert leaves.shape[0] == sum(A.sizes) + sum(B.sizes) and levels.shape[0] == TS.levels_bound(leaves.shape[0], len(pick), max(A.max_leaves, B.max_leaves), arity)
     assert int(bad) == 1 and np.array_equal(_np(off), M["offsets_new"]) and np.array_equal(_np(roots), want_roots)
     assert np.array_equal(_np(leaves)[:want_leaves.shape[0]], want_leaves) and np.array_equal(_np(levels)[:want_levels.shape[0]], want_levels)
     only_a = merkle.forest_ragged_select(gpu_ctx, A.view(), np.array([1, 0]), arity=arity)

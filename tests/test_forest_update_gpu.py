@@ -9,9 +9,10 @@ import sys
 import numpy as np
 import pytest
 
-from helpers.forest import (SENTINEL, _build, _check_against_fresh_build, _depth, _distinct_pairs, _forest, _levels_bound, _median_ms, _mix, _np,
-                            _offsets, _open, _tag, _torch, _tree, _update, _verify, dirty_count)
+from helpers.forest import (SENTINEL, _build, _check_against_fresh_build, _distinct_pairs, _forest, _median_ms, _mix, _np, _open, _tag, _torch,
+                            _tree, _update, _verify, dirty_count)
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +30,7 @@ def test_parity_with_a_fresh_build_and_the_oracle(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = _mix(arity) * 2
     np.random.default_rng(arity).shuffle(sizes)
-    off = _offsets(sizes, start=5)  # offsets[0] != 0
+    off = TS.offsets(sizes, start=5)  # offsets[0] != 0
     flat = oracle_mod.fill_random(0x0AD0 + arity, int(off[-1]) + 3)
     d, d_off, roots, d_lv = _forest(gpu_ctx, arity, flat, off)
     torch.cuda.synchronize()
@@ -59,7 +60,7 @@ def test_parity_with_a_fresh_build_and_the_oracle(gpu_ctx, oracle_mod, arity):
 def test_each_dirty_node_is_hashed_once(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = _mix(arity) * 3
-    off = _offsets(sizes, start=2)
+    off = TS.offsets(sizes, start=2)
     flat = oracle_mod.fill_random(0x0B00 + arity, int(off[-1]))
     rng = np.random.default_rng(7 + arity)
     big = int(np.argmax(sizes))
@@ -78,7 +79,7 @@ def test_each_dirty_node_is_hashed_once(gpu_ctx, oracle_mod, arity):
         if name == "every leaf":
             assert want == _used(sizes, arity)
         if name == "one node":
-            assert want == _depth(sizes[big], arity)
+            assert want == TS.depth(sizes[big], arity)
         _check_against_fresh_build(gpu_ctx, oracle_mod, arity, flat, off, tid, lid, new, d, d_lv, d_roots)
 
 
@@ -135,7 +136,7 @@ def test_edge_sizes(gpu_ctx, oracle_mod, arity):
     # D == 0: every tree a single leaf, no levels at all; the roots follow the leaves
     n_trees = 50
     flat = oracle_mod.fill_random(0x0D0 + arity, n_trees)
-    d, d_off = _torch(flat), _torch(_offsets([1] * n_trees))
+    d, d_off = _torch(flat), _torch(TS.offsets([1] * n_trees))
     d_roots = torch.full((n_trees, 4), SENTINEL, dtype=torch.int64, device=d.device)
     tid, lid = np.array([3, 49, 0, 50, 3 + 8]), np.array([0, 0, 0, 0, 1])
     new = oracle_mod.fill_random(0x0D1 + arity, tid.size)
@@ -153,7 +154,7 @@ def test_edge_sizes(gpu_ctx, oracle_mod, arity):
     assert fn(gpu_ctx._h, None, None, 0, None, 0, 0, None, None, None, None, 0, None, None, None, None) == 0
     # one tree of one leaf
     one = oracle_mod.fill_random(0x0D2 + arity, 1)
-    d1, d1_off = _torch(one), _torch(_offsets([1]))
+    d1, d1_off = _torch(one), _torch(TS.offsets([1]))
     r1 = torch.full((1, 4), SENTINEL, dtype=torch.int64, device=d.device)
     bad, hashed = _update(gpu_ctx, arity, d1, d1_off, 1, 1, None, [0], [0], new[:1], r1)
     torch.cuda.synchronize()
@@ -163,7 +164,7 @@ def test_edge_sizes(gpu_ctx, oracle_mod, arity):
 def test_one_tree_arity_2_against_the_oracle_with_levels(gpu_ctx, oracle_mod):
     import torch
     n = 1000
-    flat, off = oracle_mod.fill_random(0x0D20, n), _offsets([n])
+    flat, off = oracle_mod.fill_random(0x0D20, n), TS.offsets([n])
     d, d_off, roots, d_lv = _forest(gpu_ctx, 2, flat, off, tail=0)
     rng = np.random.default_rng(2)
     lid = rng.choice(n, 120, replace=False)
@@ -180,7 +181,7 @@ def test_one_tree_arity_2_against_the_oracle_with_levels(gpu_ctx, oracle_mod):
 def test_one_tree_arity_4_against_the_single_tree_update(gpu_ctx, oracle_mod):
     import torch
     n = 4 ** 6 + 77
-    flat, off = oracle_mod.fill_random(0x0D40, n), _offsets([n])
+    flat, off = oracle_mod.fill_random(0x0D40, n), TS.offsets([n])
     d, d_off, roots, d_lv = _forest(gpu_ctx, 4, flat, off, tail=0)
     d_b, lv_b = d.clone(), d_lv.clone()
     rng = np.random.default_rng(4)
@@ -196,7 +197,7 @@ def test_one_tree_arity_4_against_the_single_tree_update(gpu_ctx, oracle_mod):
 # ---- 5. both digest kernels ----
 def _wide(arity, oracle_mod):
     sizes = [(4 ** 8 if arity == 4 else 2 ** 16)] * 4 + _mix(arity)
-    off = _offsets(sizes, start=1)
+    off = TS.offsets(sizes, start=1)
     return sizes, off, oracle_mod.fill_random(0x0E00 + arity, int(off[-1]))
 
 
@@ -253,7 +254,7 @@ def test_both_digest_kernels_give_the_same_bytes(gpu_ctx, oracle_mod, tmp_path, 
 def test_openings_of_the_changed_leaves_verify_against_the_new_roots_only(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = _mix(arity) * 2
-    off = _offsets(sizes, start=4)
+    off = TS.offsets(sizes, start=4)
     flat = oracle_mod.fill_random(0x0F00 + arity, int(off[-1]))
     d, d_off, roots, d_lv = _forest(gpu_ctx, arity, flat, off)
     old_roots = roots.clone()
@@ -278,7 +279,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
     dev = torch.device("cuda:0")
     jobs = []
     for j, (arity, sizes) in enumerate(((4, [3000, 7, 900, 1] * 10), (2, [65, 1024, 2, 300] * 10))):
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         flat = oracle_mod.fill_random(0x5F0 + j, int(off[-1]))
         d, d_off, roots, d_lv = _forest(gpu_ctx, arity, flat, off)
         tid, lid = _distinct_pairs(sizes, np.random.default_rng(j), 12000)
@@ -311,7 +312,7 @@ def test_two_streams_of_one_context(gpu_ctx, oracle_mod):
 def test_graph_capture_replays_on_new_values(gpu_ctx, oracle_mod, arity):
     import torch
     sizes = [1, 5, 17, 256, 1000, 3, 64] * 20
-    off = _offsets(sizes)
+    off = TS.offsets(sizes)
     flat = oracle_mod.fill_random(0x0610 + arity, int(off[-1]))
     d, d_off, roots, d_lv = _forest(gpu_ctx, arity, flat, off)
     n_trees, max_leaves, k = len(sizes), 1000, 5000
@@ -353,7 +354,7 @@ def test_trim_gives_the_scratch_back(oracle_mod):
     ctx = P.Context(0)
     try:
         arity, sizes = 4, [4 ** 5] * 2048
-        off = _offsets(sizes)
+        off = TS.offsets(sizes)
         d = torch.randint(0, 1 << 60, (int(off[-1]), 4), dtype=torch.int64, device="cuda:0")
         d_off = _torch(off)
         roots, d_lv = _build(ctx, arity, d, d_off, len(sizes), max(sizes))
@@ -395,9 +396,9 @@ def test_leaf_buffer_past_4_gib(gpu_ctx, oracle_mod, arity):
     import torch
     start = (1 << 27) + 3  # more than 2^27 leaves (4 GiB) before the first tree
     sizes = [1, 9, 1000, 64, 4097]
-    off = _offsets(sizes, start=start)
+    off = TS.offsets(sizes, start=start)
     n_leaves = int(off[-1]) + 5
-    need = n_leaves * 32 + _levels_bound(n_leaves, len(sizes), 4097, arity) * 32 + (1 << 30)
+    need = n_leaves * 32 + TS.levels_bound(n_leaves, len(sizes), 4097, arity) * 32 + (1 << 30)
     free, _ = torch.cuda.mem_get_info()
     if free < need:
         pytest.skip("needs %d GiB of free HBM" % (need >> 30))
@@ -441,7 +442,7 @@ def test_u1_hashing_each_dirty_node_once_beats_k_digests_per_level(gpu_ctx):
     import torch
     n, k = 4 ** 11, 1 << 18
     d = torch.randint(0, 1 << 60, (n, 4), dtype=torch.int64, device="cuda:0")
-    d_off = _torch(_offsets([n]))
+    d_off = _torch(TS.offsets([n]))
     roots, d_lv = _build(gpu_ctx, 4, d, d_off, 1, n)
     lid = np.random.default_rng(1).choice(n, k, replace=False)
     d_tid, d_lid, d_idx = _torch(np.zeros(k, np.uint32)), _torch(lid.astype(np.uint64)), _torch(lid.astype(np.uint32))

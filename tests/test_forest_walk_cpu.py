@@ -1,8 +1,7 @@
 """The forest walk (tests/forestwalk.py) without a GPU: the conditions its plans must meet, asserted on the plans themselves; the host
-forest's resize against the numpy models of bench_tools at every step; the runner on HostBackend, a numpy-and-oracle stand-in with the
+forest's resize against the numpy models of testsupport/ at every step; the runner on HostBackend, a numpy-and-oracle stand-in with the
 call surface of Context; and four stand-ins that are each wrong in one way, which the runner must reject AT the step in which the
 fault first acts."""
-import os
 import sys
 
 import numpy as np
@@ -10,14 +9,10 @@ import pytest
 
 import edgecases as E
 import forestwalk as W
-from forestwalk import RESIZES, _depth, _lo, _offs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from forest_append_bench import forest_append_model, good_leaf_counts, level_widths, model_leaves  # noqa: E402
-from forest_multiproof_bench import (forest_multiproof_bound, forest_multiproof_counts, forest_multiproof_extract,  # noqa: E402
-                                     forest_multiproof_roots)
-from forest_resize_bench import forest_resize_model  # noqa: E402
+from testsupport.forestappend import forest_append_model, forest_resize_model, good_leaf_counts, model_leaves
+from forestwalk import RESIZES
+from testsupport.multiproofmodel import forest_multiproof_bound, forest_multiproof_counts, forest_multiproof_extract, forest_multiproof_roots
+from testsupport import treeshape as TS
 
 _PLANS = {}
 
@@ -81,7 +76,7 @@ def test_plans_meet_their_conditions(profile, arity):
           any(is_resize(s) and any(t not in s["changed"] and size(s, t, "after") and t - 1 in s["changed"] and t + 1 in s["changed"]
                                    for t in range(1, s["T_after"] - 1)) for s in S))
     holds(11, "max_leaves grows so that the stride D grows", any(s["maxl_after"] > s["maxl_before"] and s["D_after"] > s["D_before"] for s in S))
-    deepest = lambda sizes: max(_depth(n, a) for n in sizes)  # noqa: E731
+    deepest = lambda sizes: max(TS.depth(n, a) for n in sizes)  # noqa: E731
     holds(12, "the deepest actual tree gets shallower while D stays",
           any(deepest(s["sizes_after"]) < deepest(s["sizes_before"]) and s["D_after"] == s["D_before"] for s in S))
     ok13 = False
@@ -109,7 +104,7 @@ def test_plans_meet_their_conditions(profile, arity):
         holds(18, "multiproof pairs fall on both sides of every 2,048-tree tile border",
               all(W.borders(s["T_after"]) and set(W.borders(s["T_after"])) <= set(s["r_tid"].tolist()) for s in S))
         sizes0 = [t.shape[0] for t in P.trees]
-        level1 = sum(level_widths(n, a)[0] for n in sizes0 if n > 1)
+        level1 = sum(TS.level_widths(n, a)[0] for n in sizes0 if n > 1)
         assert len(S) >= 6 and len(sizes0) > 2 * W.SCAN_TILE and level1 > W.LANE_GROUPS and 35000 <= sum(sizes0) <= 50000
         assert all(s["T_after"] > 2 * W.SCAN_TILE + 1 for s in S) and all(35000 <= sum(s["sizes_after"]) <= 60000 for s in S)
         assert any(s["kind"] == "append" and s["dirty_bound_1"] > W.LANE_GROUPS for s in S)
@@ -132,18 +127,18 @@ def test_host_forest_agrees_with_the_numpy_models(arity):
             H.update(s["tid"], s["lid"], s["new"])
             continue
         sizes, flat, maxl = H.sizes(), H.flat(), H.max_leaves
-        off = _offs(sizes)
+        off = TS.offsets(sizes)
         aoff = np.zeros(s["n_trees_new"] + 1, np.uint64) if s["pure"] else s["add_offsets"]
         add = s["add"] if s["n_add"] else np.zeros((0, 4), np.uint64)
         H.resize(s["keep"], add, aoff, s["n_trees_new"], s["max_leaves_new"])
         M = forest_resize_model(off, flat.shape[0], maxl, s["keep"], aoff, s["n_add"], s["max_leaves_new"], arity)
-        assert M["n_new"] == H.sizes() == s["sizes_after"] and M["offsets_new"].tolist() == _offs(H.sizes()).tolist(), i
+        assert M["n_new"] == H.sizes() == s["sizes_after"] and M["offsets_new"].tolist() == TS.offsets(H.sizes()).tolist(), i
         assert np.array_equal(model_leaves(M, flat, add), H.flat()), i
         assert M["n_bad"] == sum(1 for n in H.sizes() if n == 0) and M["k"] == s["k"] and M["m"] == s["m"], i
         direct = 0
         for n, k, m in zip(sizes + [0] * s["n_trees_new"], M["k"], M["m"]):
             if k != n or m:
-                direct += sum(-(-(k + m) // arity ** l) - k // arity ** l for l in range(1, _depth(k + m, arity) + 1))
+                direct += sum(-(-(k + m) // arity ** l) - k // arity ** l for l in range(1, TS.depth(k + m, arity) + 1))
         assert M["n_hashed"] == direct, (i, M["n_hashed"], direct)
         if s["keep"] is None and s["n_trees_new"] >= len(sizes):
             A = forest_append_model(off, flat.shape[0], maxl, aoff, s["n_add"], s["max_leaves_new"], arity)
@@ -164,7 +159,7 @@ def _tree(tag, arity, raw):
 
 
 def _level_start(n, l, arity):
-    return sum(level_widths(n, arity)[:l - 1])
+    return sum(TS.level_widths(n, arity)[:l - 1])
 
 
 class HostBackend:
@@ -187,7 +182,7 @@ class HostBackend:
     # ---- build ----
     def merkle_forest_ragged_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_roots, d_levels=None, d_n_bad=None, arity=4):
         sizes = good_leaf_counts(d_offsets, d_leaves.shape[0], max_leaves)
-        lo = _lo(sizes, arity)
+        lo = TS.block_starts(sizes, arity)
         built = E._pmap(lambda t: _tree(tag, arity, d_leaves[int(d_offsets[t]):int(d_offsets[t]) + sizes[t]]), range(n_trees))
         for t, (root, lv) in enumerate(built):
             d_roots[t] = root
@@ -201,7 +196,7 @@ class HostBackend:
                                            d_roots=None, d_n_bad=None, d_n_hashed=None, arity=4):
         self.calls["update"] += 1
         sizes = good_leaf_counts(d_offsets, d_leaves.shape[0], max_leaves)
-        lo = _lo(sizes, arity)
+        lo = TS.block_starts(sizes, arity)
         dirty, bad = set(), 0
         for i in range(k):
             t, l = int(d_tree_ids[i]), int(d_leaf_ids[i])
@@ -209,7 +204,7 @@ class HostBackend:
                 bad += 1
                 continue
             d_leaves[int(d_offsets[t]) + l] = d_new_leaves[i]
-            for lv in range(1, _depth(sizes[t], arity) + 1):
+            for lv in range(1, TS.depth(sizes[t], arity) + 1):
                 dirty.add((t, lv, l // arity ** lv))
         touched = sorted({int(t) for t in d_tree_ids[:k] if t < n_trees and sizes[t]})
         built = dict(zip(touched, E._pmap(lambda t: _tree(tag, arity, d_leaves[int(d_offsets[t]):int(d_offsets[t]) + sizes[t]]), touched)))
@@ -217,7 +212,7 @@ class HostBackend:
         if self._acts("stale_top", "update"):
             stale = next(t for t in touched if sizes[t] > arity)
         for t, lv, j in dirty:
-            if t == stale and lv == _depth(sizes[t], arity):
+            if t == stale and lv == TS.depth(sizes[t], arity):
                 continue
             d_levels[lo[t] + _level_start(sizes[t], lv, arity) + j] = built[t][1][_level_start(sizes[t], lv, arity) + j]
         for t in touched:
@@ -235,7 +230,7 @@ class HostBackend:
                 d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed):
         self.calls[kind] += 1
         old = good_leaf_counts(d_offsets, d_leaves.shape[0], max_leaves) if n_trees else []
-        lo_old = _lo(old, arity)
+        lo_old = TS.block_starts(old, arity)
         n_add = d_add.shape[0] if d_add is not None else 0
         assert d_leaves_new.shape[0] >= d_leaves.shape[0] + n_add and d_offsets_new.shape[0] == n_trees_new + 1 and d_roots.shape[0] == n_trees_new
         new, ks, ms = [], [], []
@@ -249,7 +244,7 @@ class HostBackend:
             ks.append(k)
             ms.append(hi - lo)
         sizes = [x.shape[0] for x in new]
-        off, lo_new = _offs(sizes), _lo(sizes, arity)
+        off, lo_new = TS.offsets(sizes), TS.block_starts(sizes, arity)
         assert d_levels_new.shape[0] >= lo_new[-1]
         changed = [t for t in range(n_trees_new) if ms[t] or ks[t] != (old[t] if t < n_trees else 0)]
         built = dict(zip(changed, E._pmap(lambda t: _tree(tag, arity, new[t]), changed)))
@@ -264,7 +259,7 @@ class HostBackend:
                 d_levels_new[lo_new[t]:lo_new[t + 1]] = d_levels[lo_old[t]:lo_old[t + 1]]
             elif t in built:
                 at, n_old = int(lo_new[t]), old[t] if t < n_trees else 0
-                for l, w in enumerate(level_widths(n, arity), 1):
+                for l, w in enumerate(TS.level_widths(n, arity), 1):
                     clean = k // arity ** l
                     src = int(lo_old[t]) + _level_start(n_old, l, arity) if clean else 0
                     d_levels_new[at:at + clean] = d_levels[src:src + clean]
@@ -310,7 +305,7 @@ class HostBackend:
             d_add_offsets = np.zeros(n_trees_new + 1, np.uint64)
         total = d_leaves.shape[0] + n_add
         out = (np.zeros((total, 4), np.uint64), np.zeros(n_trees_new + 1, np.uint64),
-               np.zeros((total // (arity - 1) + n_trees_new * _depth(max_leaves_new, arity), 4), np.uint64), np.zeros((n_trees_new, 4), np.uint64),
+               np.zeros((TS.levels_bound(total, n_trees_new, max_leaves_new, arity), 4), np.uint64), np.zeros((n_trees_new, 4), np.uint64),
                np.zeros(1, np.int32), np.zeros(1, np.uint64))
         call(arity, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, *keep, d_add, d_add_offsets, n_trees_new, max_leaves_new, *out)
         return out
@@ -329,15 +324,15 @@ class HostBackend:
     def merkle_forest_ragged_openings_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k, out=None, d_n_bad=None,
                                              arity=4):
         sizes = good_leaf_counts(d_offsets, d_leaves.shape[0], max_leaves)
-        lo, D = _lo(sizes, arity), _depth(max_leaves, arity)
+        lo, D = TS.block_starts(sizes, arity), TS.depth(max_leaves, arity)
         lv, sib = np.zeros((k, 4), np.uint64), np.zeros((k, D, arity - 1, 4), np.uint64)
         pos, dep = np.zeros((k, D), np.uint8), np.zeros(k, np.uint8)
         for i in range(k):
             t, idx = int(d_tree_ids[i]), int(d_leaf_ids[i])
             assert t < n_trees and idx < sizes[t]  # (the plans ask for no bad opening)
             nodes = d_leaves[int(d_offsets[t]):int(d_offsets[t]) + sizes[t]]
-            lv[i], dep[i], at = nodes[idx], _depth(sizes[t], arity), int(lo[t])
-            for l, w in enumerate(level_widths(sizes[t], arity)):
+            lv[i], dep[i], at = nodes[idx], TS.depth(sizes[t], arity), int(lo[t])
+            for l, w in enumerate(TS.level_widths(sizes[t], arity)):
                 pos[i, l] = idx % arity
                 others = [c for c in range(idx - idx % arity, idx - idx % arity + arity) if c != idx]
                 for j, c in enumerate(others):
@@ -367,7 +362,7 @@ class HostBackend:
 
     def _mp(self, arity, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof, d_proof_offsets, d_n_bad=None):
         sizes = good_leaf_counts(d_offsets, d_leaves.shape[0], max_leaves)
-        off = _offs(sizes, int(d_offsets[0])).astype(np.int64)
+        off = TS.offsets(sizes, int(d_offsets[0])).astype(np.int64)
         out, proof, po = forest_multiproof_extract(d_leaves, off, d_levels, d_tree_ids[:k], d_leaf_ids[:k], arity)
         d_leaves_out[:k], d_proof_offsets[:] = out, po
         if proof.shape[0] <= (d_proof.shape[0] if d_proof is not None else 0):

@@ -1,6 +1,6 @@
 """One ragged Merkle forest carried through long mixed sequences of forest calls on the GPU (tests/forestwalk.py): built once, then
 updated, appended to, rolled back, reorganised, pruned, opened and proved again and again, each call reading what the call before it
-wrote — against the oracle's single-tree builds and the numpy models of bench_tools after EVERY step, never against the library itself
+wrote — against the oracle's single-tree builds and the numpy models of testsupport/ after EVERY step, never against the library itself
 (tests/test_forest_walk_cpu.py checks the plans, the host model and that the runner's checks bite, without a GPU).  On the default
 stream, on a side stream with p252_trim in the middle, on the one-lane kernels (a child process), and two walks interleaved on two
 streams of one context."""

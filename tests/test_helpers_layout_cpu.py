@@ -1,7 +1,9 @@
 """Where the scaffolding of the per-call test files lives, as far as the text of tests/ can show it: no module of tests/ is another
 one's library unless it is a helper (no import of a test module, scripts held in strings included); the compiler lines for tests/cpp
 and the parser of a refusal table are helpers/percall.py's alone; the harness of the refusal programs is tests/cpp/refusal_table.hpp's
-alone.  ("Adding a call: the test scaffolding", says which helper a new call's test files use.)"""
+alone; no module of tests/ imports a bench tool and no bench tool another, and the geometry of a tree (testsupport/treeshape.py) and
+the tools' clock probe (bench_tools/_common.py) are each defined once.  ("Adding a call: the test scaffolding", says which
+helper a new call's test files use and where its model and its bench tool go.)"""
 import os
 import re
 
@@ -49,3 +51,53 @@ def test_refusal_harness_is_in_the_header_only():
     assert len(programs) == 5
     for n in programs:
         assert '#include "refusal_table.hpp"' in open(os.path.join(CPP, n)).read(), n
+
+
+# ---- the numpy models live in testsupport/, the tools measure, and the geometry of a tree is testsupport/treeshape.py's alone ----
+BENCH_TOOLS = os.path.join(os.path.dirname(TESTS), "bench_tools")
+SUPPORT = os.path.join(os.path.dirname(TESTS), "testsupport")
+BENCH_IMPORT = re.compile(r"^[ \t]*(?:from[ \t]+\w+_bench[ \t]+import\b|import[ \t]+\w+_bench\b)", re.M)
+
+
+def _tool_sources():
+    return {os.path.join("bench_tools", n): open(os.path.join(BENCH_TOOLS, n)).read() for n in sorted(os.listdir(BENCH_TOOLS)) if n.endswith(".py")}
+
+
+def _support_sources():
+    return {os.path.join("testsupport", n): open(os.path.join(SUPPORT, n)).read() for n in sorted(os.listdir(SUPPORT)) if n.endswith(".py")}
+
+
+def test_no_test_module_imports_a_bench_tool():
+    """`from x_bench import ...`, `import x_bench` and a sys.path.insert that names bench_tools, at the start of any line: those of child
+    scripts kept in strings too.  A test reaches a tool by running it as a child process."""
+    path = re.compile(r"^[ \t]*sys\.path\.insert\(.*bench_tools", re.M)
+    sources = dict(_python_sources(), **_support_sources())
+    found = {n: BENCH_IMPORT.findall(s) + path.findall(s) for n, s in sources.items()}
+    assert {n: f for n, f in found.items() if f} == {}
+
+
+def test_no_bench_tool_imports_a_bench_tool():
+    tools = _tool_sources()
+    assert len(tools) > 20 and os.path.join("bench_tools", "_common.py") in tools
+    assert {n: BENCH_IMPORT.findall(s) for n, s in tools.items() if BENCH_IMPORT.search(s)} == {}
+
+
+def test_the_geometry_and_the_clock_probe_are_defined_once():
+    """over tests/**/*.py, bench_tools/*.py and testsupport/*.py together: one depth, one levels_len (edgecases._levels_len asks the library on purpose and is no
+    second definition of the arithmetic), one levels bound, one offsets-from-sizes, one clock_mhz"""
+    sources = dict(_tool_sources(), **_support_sources(), **{os.path.join("tests", n): s for n, s in _python_sources().items()})
+    for what, pat, home in (("depth", r"def _?depth\(", "testsupport/treeshape.py"), ("levels_len", r"def levels_len\(", "testsupport/treeshape.py"),
+                            ("levels bound", r"def _?levels_bound\(", "testsupport/treeshape.py"), ("offsets", r"def _?(?:offsets|offs)\(", "testsupport/treeshape.py"),
+                            ("clock_mhz", r"def _?clock_mhz\(", "bench_tools/_common.py")):
+        holders = sorted(n for n, s in sources.items() if re.search(r"^[ \t]*" + pat, s, re.M))
+        assert holders == [os.path.normpath(home)], (what, holders)
+    own_levels_len = sorted(n for n, s in sources.items() if re.search(r"^[ \t]*def _levels_len\(", s, re.M))
+    assert own_levels_len == [os.path.join("tests", "edgecases.py")] and "from poseidon252_amd import levels_len" in sources[own_levels_len[0]]
+
+
+def test_treeshape_and_the_models_ask_neither_the_library_nor_tests_nor_tools():
+    support = _support_sources()
+    assert "poseidon252_amd" not in support[os.path.join("testsupport", "treeshape.py")]
+    for name in ("treeshape.py", "forestappend.py", "forestupdate.py", "multiproofmodel.py"):
+        imports = re.findall(r"^[ \t]*(?:from|import)[ \t]+([\w.]+)", support[os.path.join("testsupport", name)], re.M)
+        assert set(imports) <= {"numpy", ".", ".treeshape"}, (name, imports)

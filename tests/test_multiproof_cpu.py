@@ -6,7 +6,6 @@ construction and, with the oracle's digest, reproduces the oracle's roots; the b
 mirror validates every buffer before it reaches the library; the C++ mirror test compiles."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -14,11 +13,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poseidon252_amd", "csrc")
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from multiproof_bench import multiproof_bound, multiproof_counts, multiproof_extract, multiproof_model, multiproof_root  # noqa: E402
 from helpers.binding import _dev, recorder  # noqa: E402,F401  (the stub library and the tensors that pass for device ones)
 from helpers.kernel_resources import kernel_resources  # noqa: E402
 from helpers.percall import bench_tool_parses, build_cpp_mirror, check_abi_symbols  # noqa: E402
+from testsupport.multiproofmodel import multiproof_bound, multiproof_counts, multiproof_extract, multiproof_model, multiproof_root  # noqa: E402
 
 ARGS = {"p252_merkle4_multiproof_bound": 2, "p252_merkle2_multiproof_bound": 2,
         "p252_merkle4_multiproof_device": 12, "p252_merkle2_multiproof_device": 12,

@@ -1,19 +1,15 @@
 """Many leaves of ONE stored tree behind one shared proof (p252_merkle{4,2}_multiproof_device / _verify_device; csrc/multiproof.hip)
 on the GPU: the proof's bytes and length, the leaves, the recomputed root and the digest count against the numpy model of the format
-(bench_tools/multiproof_bench.py), the roots against the oracle, k = 1 against the per-leaf openings, shapes that leave one scan tile
+(testsupport/multiproofmodel.py), the roots against the oracle, k = 1 against the per-leaf openings, shapes that leave one scan tile
 and the 8-lane digest, rejected proofs, bad positions, a short proof buffer, streams, p252_trim and a forest's tree block."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-from helpers.forest import SENTINEL, _build, _np, _offsets, _single_extract as _extract, _single_verify as _verify, _tag, _torch
+from helpers.forest import SENTINEL, _build, _np, _single_extract as _extract, _single_verify as _verify, _tag, _torch
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from multiproof_bench import multiproof_counts, multiproof_extract, tree_device  # noqa: E402  (the numpy model; tests/test_multiproof_cpu.py checks it)
+from testsupport.device import tree_device
+from testsupport.multiproofmodel import multiproof_counts, multiproof_extract  # (the numpy model; tests/test_multiproof_cpu.py checks it)
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -112,7 +108,7 @@ def test_more_than_one_scan_tile_and_both_digest_kernels(gpu_ctx, arity, n, what
     else:
         pos = np.sort(np.random.default_rng(5).choice(n, int(what.split()[1]), replace=False))
     if what == "random 40000":
-        from multiproof_bench import multiproof_model
+        from testsupport.multiproofmodel import multiproof_model
         assert multiproof_model(n, pos, arity)[1][1].size > 8192
     _round_trip(gpu_ctx, arity, n, pos)
 
@@ -226,7 +222,7 @@ def test_a_tree_block_of_a_ragged_forest_is_a_single_tree(gpu_ctx, oracle_mod, a
     import torch
     from poseidon252_amd import levels_len
     sizes = [5, 300, 1, 17, 66]
-    off = _offsets(sizes).astype(np.int64)
+    off = TS.offsets(sizes).astype(np.int64)
     lo = np.concatenate([[0], np.cumsum([levels_len(s, arity) for s in sizes])])
     flat = _leaves(sum(sizes), 77)
     d = _torch(flat)

@@ -1,15 +1,14 @@
 """The shapes of tests/scanwidth.py meet the conditions they are here for — every two-level scan makes three trips (a carry set on one
-trip and added to on the next) with real elements behind every trip border — asserted on the numpy models of bench_tools alone, no GPU;
+trip and added to on the next) with real elements behind every trip border — asserted on the numpy models of testsupport/ alone, no GPU;
 and scanwidth's own vectorised expectations are held to those models and to the oracle on forests small enough for them."""
 import numpy as np
 import pytest
 
 import edgecases as E
 import scanwidth as S
-from forest_append_bench import forest_append_model, level_widths, model_leaves
-from forest_multiproof_bench import forest_multiproof_counts, forest_multiproof_extract
-from forest_resize_bench import forest_resize_model
-from multiproof_bench import multiproof_model
+from testsupport.forestappend import forest_append_model, forest_resize_model, model_leaves
+from testsupport.multiproofmodel import forest_multiproof_counts, forest_multiproof_extract, multiproof_model
+from testsupport import treeshape as TS
 
 SMALL = 5000
 
@@ -35,7 +34,7 @@ def check_wide_forest(f):
     assert (np.abs(share - 1 / top) < 0.01).all()  # shuffled evenly: many one-leaf trees, most trees with two levels
     assert (f.sizes > a).mean() > 0.5
     for t in S.at_trip_borders(T):
-        assert S.depth(int(f.sizes[t]), a) >= 2, t
+        assert TS.depth(int(f.sizes[t]), a) >= 2, t
     assert len(S.at_trip_borders(T)) == 4 and len(S.trip_borders(T)) == 12
     # one-leaf trees with limbs >= p on both sides of every trip border
     assert len(f.unreduced) >= 4 and (f.sizes[f.unreduced] == 1).all() and not E.is_reduced(f.flat[f.off[f.unreduced]]).any()
@@ -107,13 +106,13 @@ def test_expected_forest_and_siblings_against_the_oracle(oracle_mod, arity):
     built = S.oracle_trees(arity, f.sizes, f.off, f.flat, list(range(SMALL)))
     for t in range(SMALL):
         assert np.array_equal(roots[t], built[t][0]) and np.array_equal(levels[lo[t]:lo[t + 1]], built[t][1]), t
-    assert E.is_reduced(roots).all() and lo[-1] == sum(sum(level_widths(int(n), arity)) for n in f.sizes)
+    assert E.is_reduced(roots).all() and lo[-1] == sum(sum(TS.level_widths(int(n), arity)) for n in f.sizes)
     rng = np.random.default_rng(arity)
     tid = np.sort(rng.choice(SMALL, 800, replace=False))
     lid = (rng.random(800) * f.sizes[tid]).astype(np.int64)
-    D = S.depth(f.max_leaves, arity)
+    D = TS.depth(f.max_leaves, arity)
     sib, pos, depths = S.expected_siblings(f.sizes, f.off, f.flat, lo, levels, tid, lid, arity, D)
-    assert np.array_equal(depths, [S.depth(int(n), arity) for n in f.sizes[tid]])
+    assert np.array_equal(depths, [TS.depth(int(n), arity) for n in f.sizes[tid]])
     raw = f.flat[f.off[tid] + lid]
     assert np.array_equal(E.rehash(E._mtag(arity), arity, E.reduce_mod_p(raw), sib, pos, depths), roots[tid])
 
@@ -167,7 +166,7 @@ def test_forest_multiproof_fast_against_the_model(arity):
     f = S.wide_forest(arity, SMALL)
     sizes = f.sizes.copy()
     sizes[[7, 4000]] = [300, 1000]  # two deeper trees, many pairs in each
-    off, lo = S.offsets(sizes), S.offsets(S.levels_len(sizes, arity))
+    off, lo = TS.offsets(sizes, dtype=np.int64), TS.block_starts(sizes, arity)
     flat, levels = S.leaves(off[-1], 1), S.leaves(lo[-1], 2)  # (extraction only copies: any bytes serve as levels)
     rng = np.random.default_rng(arity)
     tid, lid = S._small_pairs(sizes, np.nonzero(rng.random(SMALL) < 0.3)[0], rng)

@@ -1,6 +1,6 @@
 """Every two-level scan of the ragged calls driven past one block of tiles on the GPU (the shapes of tests/scanwidth.py, whose
 conditions tests/test_scan_width_cpu.py asserts), byte for byte against expectations that share none of those scans: the forest by size
-class through hash_batch, the numpy models of bench_tools, and the oracle on the trees at the trip borders.
+class through hash_batch, the numpy models of testsupport/, and the oracle on the trees at the trip borders.
 
 No difference from the models or the oracle was found at these widths.  The dense single-tree proofs hold 5,243 scalars only (the
 dropped leaves), so their rejected node is the proof's last one; the sparse proofs (112,842 and 90,393 scalars) have theirs beyond
@@ -14,8 +14,10 @@ import pytest
 
 import edgecases as E
 import scanwidth as S
-from forest_update_bench import dirty_nodes
-from multiproof_bench import multiproof_counts, multiproof_extract, tree_device
+from testsupport.forestupdate import dirty_nodes
+from testsupport.device import tree_device
+from testsupport.multiproofmodel import multiproof_counts, multiproof_extract
+from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +105,7 @@ def test_wide_forest_openings(gpu_ctx, arity):
     ctx.merkle_path_ragged_device(tag, o_l, o_s, o_p, o_d, D, back, k, d_n_bad=bad[1:], arity=arity)
     ctx.merkle_forest_ragged_verify_device(tag, o_l, o_s, o_p, o_d, D, d_tid, w.d_roots, T, ok, k, arity=arity)
     torch.cuda.synchronize()
-    assert D == S.depth(f.max_leaves, arity) and E._host(bad).tolist() == [0, 0]
+    assert D == TS.depth(f.max_leaves, arity) and E._host(bad).tolist() == [0, 0]
     sib, pos, depths = S.expected_siblings(f.sizes, f.off, f.flat, w.lo, w.levels, tid, lid, arity, D)
     _same(E._host(o_l), f.flat[f.off[tid] + lid], "the opened leaves")
     _same(E._host(o_d).astype(np.int64), depths, "depths")
@@ -154,14 +156,14 @@ def _against_fresh_build(ctx, arity, out, flat, off, max_leaves, model, what, rn
     assert (bad, hashed) == (want_bad, want_hashed), "%s: n_bad %d (model %d), n_hashed %d (model %d)" % (what, bad, want_bad, hashed, want_hashed)
     _, _, f_roots, f_lv, f_bad = S.run_build(ctx, arity, flat, off, max_leaves)
     assert f_bad == want_bad
-    used = int(S.levels_len(sizes, arity).sum())
+    used = int(TS.levels_len(sizes, arity).sum())
     got_lv, got_roots = E._host(o_lv), E._host(o_roots)
     _same(got_roots, E._host(f_roots), what + ": roots against a fresh build")
     _same(got_lv[:used], E._host(f_lv)[:used], what + ": levels against a fresh build")
     assert (got_lv[used:] == S.SENT64).all()
     T = sizes.size
     ids = [t for t in S.oracle_share(T, [T - 2, T - 3], rng, 100) if sizes[t]]
-    _oracle_check(arity, sizes, off, flat, S.offsets(S.levels_len(sizes, arity)), got_roots, got_lv, ids, what)
+    _oracle_check(arity, sizes, off, flat, TS.block_starts(sizes, arity), got_roots, got_lv, ids, what)
     assert not got_roots[sizes == 0].any()
 
 

@@ -2,17 +2,12 @@
 six streams of ONE context: the context keeps four pairs, so the fifth and sixth stream take a pair over behind its event, and with
 the assignment rotated each round every pair is taken over by a family that asks other sizes of it.  Each output must equal that of
 the same call made alone on the default stream."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-from helpers.forest import _depth, _offsets, _tag, _torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bench_tools"))
-from multiproof_bench import tree_device  # noqa: E402  (p252_merkle{4,2}_tree_device on the current stream)
+from helpers.forest import _tag, _torch
+from testsupport import treeshape as TS
+from testsupport.device import tree_device  # (p252_merkle{4,2}_tree_device on the current stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,14 +26,14 @@ def _families(ctx, oracle, arity):
     rng = np.random.default_rng(40 + arity)
     # the forest, built once with its levels: one copy that is only read, one that the update family rewrites (the same k updates
     # every time, so each run leaves the same leaves, levels and roots)
-    n_trees, max_leaves, n_leaves, D = len(SIZES), max(SIZES), sum(SIZES), _depth(max(SIZES), arity)
-    d_fl, d_off = _torch(oracle.fill_random(0x71, n_leaves)), _torch(_offsets(SIZES))
-    d_froots, d_flv = i64(n_trees, 4), i64(n_leaves // (arity - 1) + n_trees * D + 1, 4)
+    n_trees, max_leaves, n_leaves, D = len(SIZES), max(SIZES), sum(SIZES), TS.depth(max(SIZES), arity)
+    d_fl, d_off = _torch(oracle.fill_random(0x71, n_leaves)), _torch(TS.offsets(SIZES))
+    d_froots, d_flv = i64(n_trees, 4), i64(TS.levels_bound(n_leaves, n_trees, max_leaves, arity) + 1, 4)
     ctx.merkle_forest_ragged_device(tag, d_fl, d_off, n_trees, max_leaves, d_froots, d_flv, arity=arity)
     d_ul, d_ulv = d_fl.clone(), d_flv.clone()
     pairs = rng.permutation(n_leaves)[:K]  # distinct (tree, leaf) pairs
     tid = np.searchsorted(np.cumsum(SIZES), pairs, side="right")
-    lid = pairs - _offsets(SIZES)[tid].astype(np.int64)
+    lid = pairs - TS.offsets(SIZES)[tid].astype(np.int64)
     d_tid, d_lid, d_new = _torch(tid.astype(np.uint32)), _torch(lid.astype(np.uint64)), _torch(oracle.fill_random(0x72, K))
     # the stored tree of the shared proof
     n_mp, k_mp = 1000, 37
@@ -54,7 +49,7 @@ def _families(ctx, oracle, arity):
     n_tree = 4 ** 6 + 3
     d_tl = _torch(oracle.fill_random(0x74, n_tree))
     lens = 1 + np.arange(200) % 40
-    d_msg, d_moff = _torch(oracle.fill_random(0x75, int(lens.sum()))), _torch(_offsets(lens))
+    d_msg, d_moff = _torch(oracle.fill_random(0x75, int(lens.sum()))), _torch(TS.offsets(lens))
     d_tags = _torch(H.ragged_tags(H.Domain.Other, 1, 40))
 
     def tree(o):
