@@ -27,6 +27,8 @@
 //                                                   merkle_multiproof_bound: many leaves of one tree, one shared proof
 //   —                                               merkle_forest_ragged_multiproof_device / _verify_device / _bound: leaves of many
 //                                                   trees of a ragged forest, one tree-major shared proof
+//   —                                               merkle_forest_frontier_append_device / _extract_device / _bound: a forest of
+//                                                   append-only trees kept only as their frontiers
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -437,7 +439,8 @@ namespace detail {
     X(N, forest_ragged_resize_device_into) X(N, forest_ragged_journal_bound) X(N, forest_ragged_update_journaled_device_into)                    \
     X(N, forest_ragged_journal_swap_device_into) X(N, forest_ragged_select_device_into)                                                      \
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
-    X(N, forest_ragged_multiproof_verify_device_into)
+    X(N, forest_ragged_multiproof_verify_device_into) X(N, forest_frontier_bound) X(N, forest_frontier_append_device_into)                \
+    X(N, forest_frontier_extract_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -726,6 +729,41 @@ inline void merkle_forest_ragged_multiproof_verify_device(const ForestView& fore
                                                            forest.max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in, k, d_proof, proof_len,
                                                            d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad, stream),
                   ctx.get(), "merkle_forest_ragged_multiproof_verify_device");
+}
+
+// A forest of append-only trees kept ONLY as their frontiers (p252_merkle{4,2}_forest_frontier_*): per tree a leaf count, a root and
+// merkle_forest_frontier_bound(max_leaves) = (depth(max_leaves) + 1) * (arity - 1) scalars, all device-resident and owned by the caller;
+// all zero is a forest of empty trees.
+struct ForestFrontier {
+    void* d_counts;    // n_trees uint64
+    void* d_frontier;  // n_trees x merkle_forest_frontier_bound(max_leaves) scalars
+    void* d_roots;     // n_trees scalars
+    std::size_t n_trees, max_leaves;
+};
+inline std::size_t merkle_forest_frontier_bound(std::size_t max_leaves, unsigned arity = 4) {
+    return detail::merkle_abi("merkle_forest_frontier_bound", arity).forest_frontier_bound(max_leaves);
+}
+// Tree t receives d_add[d_add_offsets[t] .. d_add_offsets[t + 1]) (n_trees + 1 device uint64), in place: afterwards d_roots[t] is the
+// root of every leaf the tree was given so far.  A refused append leaves its tree untouched and is counted in *d_n_bad; *d_n_hashed
+// (device uint64, zeroed by the caller) receives the digests computed.
+inline void merkle_forest_frontier_append_device(const ForestFrontier& state, const void* d_add, std::size_t n_add, const void* d_add_offsets,
+                                                 unsigned arity = 4, Context& ctx = Context::default_context(), void* d_n_bad = nullptr,
+                                                 void* d_n_hashed = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_frontier_append_device", arity);
+    detail::check(m.forest_frontier_append_device_into(ctx.get(), m.tag().data(), state.d_counts, state.d_frontier, state.d_roots, state.n_trees,
+                                                       state.max_leaves, d_add, n_add, d_add_offsets, d_n_bad, d_n_hashed, stream),
+                  ctx.get(), "merkle_forest_frontier_append_device");
+}
+// The state of a BUILT forest (`forest` and d_roots_forest exactly as the build took and filled them), with no digest:
+// state.max_leaves >= forest.max_leaves.  A bad tree becomes an empty one and is counted in *d_n_bad.
+inline void merkle_forest_frontier_extract_device(const ForestView& forest, const void* d_roots_forest, const ForestFrontier& state,
+                                                  unsigned arity = 4, Context& ctx = Context::default_context(), void* d_n_bad = nullptr,
+                                                  void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_frontier_extract_device", arity);
+    detail::check(m.forest_frontier_extract_device_into(ctx.get(), forest.d_leaves, forest.n_leaves, forest.d_offsets, forest.n_trees,
+                                                        forest.max_leaves, forest.d_levels, d_roots_forest, state.max_leaves, state.d_counts,
+                                                        state.d_frontier, state.d_roots, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_frontier_extract_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

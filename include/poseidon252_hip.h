@@ -116,7 +116,10 @@ extern "C" {
  *      gathered into a new compact forest, in any order, with no digest: a prune in the middle, a merge, a split, a reorder;
  *      + p252_merkle{4,2}_forest_ragged_multiproof_bound, _multiproof_device_into, _multiproof_verify_device_into (additive, same
  *      version; `_into` as the append: every result goes into buffers the caller owns):
- *      leaves of many trees of such a forest behind one tree-major shared proof, each ancestor hashed once */
+ *      leaves of many trees of such a forest behind one tree-major shared proof, each ancestor hashed once;
+ *      + p252_merkle{4,2}_forest_frontier_bound, _forest_frontier_append_device_into, _forest_frontier_extract_device_into
+ *      (additive, same version; `_into`: the state is the caller's three buffers): leaves appended to a forest that is kept only
+ *      as its frontiers — a count, a root and depth + 1 short rows per tree — and that state taken out of a built forest */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -782,6 +785,74 @@ int p252_merkle2_forest_ragged_multiproof_verify_device_into(p252_ctx* ctx, cons
                                                         const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len,
                                                         const void* d_proof_offsets, const void* d_roots, void* d_ok, void* d_roots_out,
                                                         void* d_n_hashed, void* d_n_bad, void* hip_stream);
+
+/* ---- a forest of append-only trees kept ONLY as their frontiers.  Every ragged-forest call above acts on a stored forest: all
+ * leaves and all levels.  A consumer that appends and wants the roots (a note-commitment tree, a log per account, one tree too large
+ * for the card streamed in chunks) needs O(depth) state per tree.  With A = arity, f_l(n) = floor(n / A^l), c_l(n) = ceil(n / A^l)
+ * and d_l(n) = f_l(n) mod A (digit l of n): node j of level l of a tree of n leaves is final iff j < f_l(n), and the final nodes a
+ * later append still reads are, per level, the d_l(n) nodes [A f_{l+1}(n), f_l(n)) right of the last complete group.
+ * The state of n_trees trees, three device arrays the caller owns: d_counts = n_trees uint64 (8-byte aligned), the leaf counts;
+ * d_roots = n_trees scalars; d_frontier = n_trees x p252_merkle{4,2}_forest_frontier_bound(max_leaves) scalars — tree t's part holds
+ * rows l = 0 .. D = p252_merkle{4,2}_depth(max_leaves) of A - 1 scalars each (row 0: leaves as they were given; row D is used by a
+ * tree of exactly A^D leaves), row l = those d_l(n_t) nodes in index order, the slots past them ZERO: a state is byte-comparable.
+ * A count of 0 is an empty tree with a zero root and zero rows, so a caller adds trees by allocating zeroed state.  The bound is
+ * (D + 1)(A - 1) scalars per tree, 0 for max_leaves == 0. */
+size_t p252_merkle4_forest_frontier_bound(size_t max_leaves);
+size_t p252_merkle2_forest_frontier_bound(size_t max_leaves);
+/* The append, in place: tree t receives d_add[add_offsets[t] .. add_offsets[t + 1]) (d_add_offsets = n_trees + 1 uint64, device,
+ * 8-byte aligned; d_add = n_add scalars, may be NULL when n_add == 0), m_t = the difference.  A tree with m_t == 0 is untouched,
+ * root included.  A tree that grows from n to n' = n + m computes, level by level, the nodes [f_l(n), c_l(n')) of level l from the
+ * level below — the first d_{l-1}(n) children of node f_l(n) are the frontier's row l - 1, all others were just computed (or are
+ * the new leaves), children at or past c_{l-1}(n') are the zero scalar — up to the single node of level depth(n'), the root:
+ * sum over l >= 1 of c_l(n') - f_l(n) digests, the count of p252_merkle{4,2}_forest_ragged_append_device_into, with no old leaf
+ * or node resident and nothing relocated.  Then row l keeps its entries and gains the new final nodes when f_{l+1} did not move,
+ * and is the d_l(n') last final nodes otherwise; n' == 1 has no level: the root is the leaf mod p (as the forest build writes a
+ * one-leaf tree's), row 0 the leaf's bytes.  d_counts, d_frontier and d_roots end as the state of the grown trees: d_roots[t] is
+ * what p252_merkle{4,2}_tree returns for all leaves so far.
+ * An append is REFUSED — counted once in *d_n_bad (device uint32 the caller has zeroed; may be NULL), the tree's count, rows and
+ * root untouched — when its offsets decrease, when add_offsets[t + 1] > n_add, when n_t + m_t > max_leaves, when n_t > max_leaves
+ * already (a corrupt state is never indexed past its rows; it is counted whatever it is given), or when the appends accepted so
+ * far and this one together exceed n_add (the stored append's sum rule: only ranges that overlap behind decreasing offsets do
+ * that).  *d_n_hashed (device uint64 the caller has zeroed, 8-byte aligned; may be NULL) receives the digests computed: exactly
+ * the sum above over the accepted trees.  P252_ERR_INVALID_ARGUMENT, nothing enqueued: max_leaves == 0; n_add >= 2^32 (a record
+ * holds the start of its run of children in 32 bits — a caller with more streams it in smaller chunks, which is what the state is
+ * for); a NULL or misaligned buffer (scalars 16 bytes, d_counts / d_add_offsets / d_n_hashed 8, d_n_bad 4); size overflow; d_add or
+ * d_add_offsets overlapping d_counts, d_frontier, d_roots, d_n_bad or d_n_hashed.  n_trees == 0 -> P252_OK, nothing enqueued.
+ * Asynchronous on hip_stream: no host synchronisation, no allocation once the scratch is warm, no memset node.  Scratch, in the
+ * context's pair of THIS stream (p252_trim / p252_wipe cover it): 24 + 8 (D + 1) bytes per tree, and per computed node — at most
+ * n_add / A^l + 2 min(n_trees, n_add) on level l, hence n_add / (A - 1) + 2 min(n_trees, n_add) D in all — its 32-byte value, a
+ * 16-byte record and a 4-byte width.  Cost: 11 small launches plus one digest launch per level 1 .. D (the stored append: about 30
+ * plus one per level); the scans over the trees are the stored append's own, all digests run on the kernels of
+ * p252_merkle{4,2}_multiproof_verify_device.  n_trees >= 2^32 is refused as a size overflow (a record names its tree in 32 bits).
+ * Measured (profiles/forest_frontier.txt) against the stored append on the same appends in the same run, medians of 20: one
+ * 4^12-leaf tree + 1 / 2^16 / 2^20 leaves 1.59 / 1.60 / 2.14 ms against 1.96 / 1.97 / 2.51 ms (0.81-0.85 of it) on 1,384 bytes of state
+ * against 716-761 MB stored; arity 2 on 2^24 leaves 2.98 / 3.03 / 4.77 against 3.52 / 3.59 / 5.41 ms (0.84-0.88); 20,000 mixed trees with
+ * 1-16 leaves appended to each 1.25 against 1.93 ms, to 1 % of them 0.85 against 1.90 ms, on 16.2 MB against 1.46 GB; 6.9-29x ahead
+ * of a fresh build.  One appended leaf still costs one narrow digest launch per level.  Appends above 2^20 leaves were not measured. */
+int p252_merkle4_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
+                                                    size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                    const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream);
+/* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag) */
+int p252_merkle2_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
+                                                    size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                    const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream);
+/* The state of a BUILT ragged forest: d_leaves, n_leaves, d_offsets, n_trees, max_leaves_forest, d_levels and d_roots_forest exactly
+ * as p252_merkle{4,2}_forest_ragged_device was given and filled them (read-only; d_levels may be NULL when max_leaves_forest <= 1);
+ * the leaf counts come from the build's own validation.  Writes d_counts, d_frontier (rows for max_leaves >= max_leaves_forest, so
+ * the trees can grow) and d_roots for all n_trees trees: data movement only, nothing is hashed and there is no tag.  A tree the
+ * build calls bad gets count 0, zero rows and a zero root and is counted in *d_n_bad (device uint32 the caller has zeroed; may be
+ * NULL).  A stored forest can so be dropped down to its accumulator.  P252_ERR_INVALID_ARGUMENT, nothing enqueued:
+ * max_leaves_forest == 0, max_leaves < max_leaves_forest, a NULL or misaligned buffer, size overflow, or an output range that
+ * overlaps an input range.  n_trees == 0 -> P252_OK.  Asynchronous on hip_stream; scratch: the forest's index, 16 bytes per tree. */
+int p252_merkle4_forest_frontier_extract_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                     size_t n_trees, size_t max_leaves_forest, const void* d_levels,
+                                                     const void* d_roots_forest, size_t max_leaves, void* d_counts, void* d_frontier,
+                                                     void* d_roots, void* d_n_bad, void* hip_stream);
+/* the same for arity 2 (the level layout of merkle2 trees) */
+int p252_merkle2_forest_frontier_extract_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                     size_t n_trees, size_t max_leaves_forest, const void* d_levels,
+                                                     const void* d_roots_forest, size_t max_leaves, void* d_counts, void* d_frontier,
+                                                     void* d_roots, void* d_n_bad, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

@@ -15,6 +15,7 @@
 #include "blake2b.hpp"
 #include "ctx.hpp"
 #include "forest_append.h"
+#include "forest_frontier.h"
 #include "forest_journal.h"
 #include "forest_openings.h"
 #include "forest_ragged.h"
@@ -1582,6 +1583,121 @@ int p252_merkle2_forest_ragged_multiproof_verify_device_into(p252_ctx* ctx, cons
     return forest_ragged_multiproof_verify_device(ctx, 2, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
                                                   k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad,
                                                   hip_stream);
+}
+
+// ---- a forest kept only as its frontiers (forest_frontier.hip): the append updates the caller's counts, rows and roots in place and
+// hashes through the multiproof digest kernels; the extract takes that state out of a built forest.  The scratch — two words per tree,
+// one scan row per level, the records and widths; the computed nodes of every level in the second buffer — is the pair of the calling
+// stream ----
+size_t p252_merkle4_forest_frontier_bound(size_t max_leaves) { return forest_frontier_stride(4, max_leaves); }
+size_t p252_merkle2_forest_frontier_bound(size_t max_leaves) { return forest_frontier_stride(2, max_leaves); }
+
+// the sizes of the state: n_trees x stride scalars inside size_t, the per-tree bookkeeping as in every forest call
+static int forest_frontier_shape_check(p252_ctx* ctx, const std::string& who, unsigned arity, size_t n_trees, size_t max_leaves) {
+    const size_t stride = forest_frontier_stride(arity, max_leaves);
+    if (n_trees > SIZE_MAX / 8 / (FOREST_RAGGED_MAX_DEPTH + 2) || n_trees > SIZE_MAX / 64 / stride)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    return P252_OK;
+}
+
+static int forest_frontier_append_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
+                                         size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add, const void* d_add_offsets,
+                                         void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (n_trees == 0) return P252_OK;
+    const std::string who = "merkle_forest_frontier_append";
+    if (max_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves must be > 0");
+    if (n_add > 0xffffffffull) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_add must be below 2^32 (append in smaller chunks)");
+    if (int rc = forest_frontier_shape_check(ctx, who, arity, n_trees, max_leaves)) return rc;
+    if (n_trees > 0xffffffffull || (n_add && n_trees > (SIZE_MAX / 2) / n_add))  // (a record names its tree in 32 bits)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    if (!tag || !d_counts || !d_frontier || !d_roots || !d_add_offsets || (n_add && !d_add))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_frontier) || misaligned(d_roots) || misaligned(d_add)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_counts, 8) || misaligned_to(d_add_offsets, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_counts, d_add_offsets and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
+    const size_t stride = forest_frontier_stride(arity, max_leaves);
+    const ByteRange in[] = {{d_add, n_add * 32, "d_add"}, {d_add_offsets, (n_trees + 1) * 8, "d_add_offsets"}};
+    const ByteRange out[] = {{d_counts, n_trees * 8, "d_counts"}, {d_frontier, n_trees * stride * 32, "d_frontier"},
+                             {d_roots, n_trees * 32, "d_roots"},  {d_n_bad, 4, "d_n_bad"},
+                             {d_n_hashed, 8, "d_n_hashed"}};
+    for (const ByteRange& o : out)
+        for (const ByteRange& i : in)
+            if (ranges_overlap(o, i)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + o.name + " overlaps " + i.name);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestFrontierPlan plan = forest_frontier_plan(arity, n_trees, max_leaves, n_add);
+    return with_stream_scratch(ctx, who, st, plan.work_bytes(), plan.value_bytes(), [&](p252_ctx::LevelSet& set) {
+        return launch_forest_frontier_append(ctx->d_tab, tag_arg(tag), plan, d_counts, d_frontier, d_roots, d_add, d_add_offsets, d_n_bad,
+                                             d_n_hashed, set.buf[0], set.buf[1], st);
+    });
+}
+
+int p252_merkle4_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
+                                                    size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                    const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    return forest_frontier_append_device(ctx, 4, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, n_add, d_add_offsets, d_n_bad,
+                                         d_n_hashed, hip_stream);
+}
+
+int p252_merkle2_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
+                                                    size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                    const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    return forest_frontier_append_device(ctx, 2, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, n_add, d_add_offsets, d_n_bad,
+                                         d_n_hashed, hip_stream);
+}
+
+static int forest_frontier_extract_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                          size_t n_trees, size_t max_leaves_forest, const void* d_levels, const void* d_roots_forest,
+                                          size_t max_leaves, void* d_counts, void* d_frontier, void* d_roots, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (n_trees == 0) return P252_OK;
+    const std::string who = "merkle_forest_frontier_extract";
+    if (max_leaves_forest == 0 || max_leaves < max_leaves_forest)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves_forest must be > 0 and max_leaves >= max_leaves_forest");
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves_forest)) return rc;
+    if (int rc = forest_frontier_shape_check(ctx, who, arity, n_trees, max_leaves)) return rc;
+    if (!d_leaves || !d_offsets || !d_roots_forest || !d_counts || !d_frontier || !d_roots || (max_leaves_forest > 1 && !d_levels))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_roots_forest) || misaligned(d_frontier) || misaligned(d_roots))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_counts, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets and d_counts must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
+    const size_t stride = forest_frontier_stride(arity, max_leaves);
+    const size_t levels_forest = n_leaves / (arity - 1) + n_trees * forest_ragged_depth(max_leaves_forest, arity);
+    const ByteRange in[] = {{d_leaves, n_leaves * 32, "d_leaves"},
+                            {d_offsets, (n_trees + 1) * 8, "d_offsets"},
+                            {d_levels, levels_forest * 32, "d_levels"},
+                            {d_roots_forest, n_trees * 32, "d_roots_forest"}};
+    const ByteRange out[] = {{d_counts, n_trees * 8, "d_counts"}, {d_frontier, n_trees * stride * 32, "d_frontier"},
+                             {d_roots, n_trees * 32, "d_roots"},  {d_n_bad, 4, "d_n_bad"}};
+    for (const ByteRange& o : out)
+        for (const ByteRange& i : in)
+            if (ranges_overlap(o, i)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + o.name + " overlaps " + i.name);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    return with_stream_scratch(ctx, who, st, forest_ragged_index_bytes(n_trees), 0, [&](p252_ctx::LevelSet& set) {
+        return launch_forest_frontier_extract(arity, d_leaves, n_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest,
+                                              max_leaves, d_counts, d_frontier, d_roots, d_n_bad, set.buf[0], st);
+    });
+}
+
+int p252_merkle4_forest_frontier_extract_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                     size_t n_trees, size_t max_leaves_forest, const void* d_levels,
+                                                     const void* d_roots_forest, size_t max_leaves, void* d_counts, void* d_frontier,
+                                                     void* d_roots, void* d_n_bad, void* hip_stream) {
+    return forest_frontier_extract_device(ctx, 4, d_leaves, n_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest,
+                                          max_leaves, d_counts, d_frontier, d_roots, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_frontier_extract_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                     size_t n_trees, size_t max_leaves_forest, const void* d_levels,
+                                                     const void* d_roots_forest, size_t max_leaves, void* d_counts, void* d_frontier,
+                                                     void* d_roots, void* d_n_bad, void* hip_stream) {
+    return forest_frontier_extract_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest,
+                                          max_leaves, d_counts, d_frontier, d_roots, d_n_bad, hip_stream);
 }
 
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----

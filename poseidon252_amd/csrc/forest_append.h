@@ -45,4 +45,25 @@ hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const For
                                 void* offsets_new, void* levels_new, void* roots, void* n_bad, void* n_hashed, void* meta, void* lists,
                                 hipStream_t st);
 
+// The unit's scans over the trees for a caller that made the per-tree words itself (forest_frontier.hip: the same trees, the same
+// rules, no old forest): nold[t] = n_t, madd[t] = m_t or FOREST_APPEND_REFUSED, both n_trees uint64.  rows = (depth + 1) x
+// (n_trees + 1) uint64, tsum = (depth + 1) x tiles, tiles = ceil(n_trees / FOREST_APPEND_SCAN_TILE).
+constexpr uint64_t FOREST_APPEND_REFUSED = ~0ull;  // m_t of an append refused before the sum rule
+struct ForestAppendScan {
+    uint64_t* nold = nullptr;
+    uint64_t* madd = nullptr;
+    uint64_t* rows = nullptr;
+    uint64_t* tsum = nullptr;
+    size_t n_trees = 0, tiles = 0;
+    uint64_t n_add = 0;
+    unsigned log2a = 2, depth = 0;
+};
+// the sum rule: madd[t] becomes the accepted m_t (0 for a refused append).  never_zero = n_trees words, none of them 0, in the place
+// of the kept counts: no tree is empty to this scan, so it writes no root and counts nothing.
+hipError_t forest_append_scan_sum_rule(const ForestAppendScan& scan, const uint64_t* never_zero, hipStream_t st);
+// every level's dirty list of trees that keep all of their n_t leaves: rows[l][t] = where tree t's records start in list l (rows[l]
+// [n_trees] = the list's count), and record g of list l = (tree, floor(n_t / a^l) + g - rows[l][t]) in the 16-byte format of
+// forest_update.hip at lists[list_off[l] + g], for g < in[l] (l = 1 .. depth)
+hipError_t forest_append_scan_dirty_lists(const ForestAppendScan& scan, const size_t* in, const size_t* list_off, void* lists, hipStream_t st);
+
 }  // namespace p252

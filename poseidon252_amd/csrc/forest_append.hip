@@ -29,7 +29,8 @@
 //   k_fa_expand       every level at once (gridDim.y): record g of list l = (tree, floor(k / a^l) + g - row_l[t]), in the 16-byte
 //                     format of forest_update.hip; the list's count is row_l[n_trees]
 // then launch_forest_digest_list (forest_update.hip) per level: level l reads level l - 1 of the NEW forest only — moved or hashed
-// by an earlier launch.  No kernel here hashes.
+// by an earlier launch.  No kernel here hashes.  forest_append_scan_sum_rule / forest_append_scan_dirty_lists run the SUM scan and
+// the DIRTY scans with k_fa_expand on per-tree words their caller made: forest_frontier.hip, which appends to trees kept as frontiers.
 #include <hip/hip_runtime.h>
 
 #include "blockops.hpp"
@@ -44,7 +45,7 @@ namespace {
 constexpr unsigned FA_BLOCK = 256;
 constexpr unsigned FA_ITEMS = FOREST_APPEND_SCAN_TILE / FA_BLOCK;  // trees per thread of a scan block
 constexpr unsigned FA_MOVE = 2 * FOREST_APPEND_MOVE_TILE / FA_BLOCK;  // 16-byte halves per lane of a relocation block
-constexpr uint64_t FA_REFUSED = ~0ull;
+constexpr uint64_t FA_REFUSED = FOREST_APPEND_REFUSED;
 enum { FA_SUM = 0, FA_OFFS = 1, FA_DIRTY = 2 };
 
 struct FaTrees {
@@ -366,6 +367,46 @@ hipError_t launch_forest_append(const int32_t* tab, const TagArg& tag, const For
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ---- the same scans over per-tree words that the caller made (forest_frontier.hip): no old forest, every tree keeps its n_t leaves ----
+namespace {
+FaTrees scan_trees(const ForestAppendScan& s, const uint64_t* keep) {
+    FaTrees trees;
+    trees.nold = s.nold;
+    trees.keep = const_cast<uint64_t*>(keep);  // (read only by the scans)
+    trees.madd = s.madd;
+    trees.n_trees = s.n_trees;
+    trees.n_add = s.n_add;
+    trees.la = s.log2a;
+    return trees;
+}
+}  // namespace
+
+hipError_t forest_append_scan_sum_rule(const ForestAppendScan& s, const uint64_t* never_zero, hipStream_t st) {
+    const FaTrees trees = scan_trees(s, never_zero);
+    const dim3 blk(FA_BLOCK), tiles((unsigned)s.tiles);
+    hipLaunchKernelGGL(k_fa_tile_sums<FA_SUM>, tiles, blk, 0, st, trees, s.tsum);
+    hipLaunchKernelGGL(k_fa_scan_tiles, dim3(1), blk, 0, st, s.tsum, s.tiles);
+    // (keep + m is never zero: no tree is empty, no root is written, and without a counter nothing is counted)
+    hipLaunchKernelGGL(k_fa_scan_apply<FA_SUM>, tiles, blk, 0, st, trees, s.tsum, (uint64_t*)nullptr, (Scalar32*)nullptr, (unsigned*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t forest_append_scan_dirty_lists(const ForestAppendScan& s, const size_t* in, const size_t* list_off, void* lists, hipStream_t st) {
+    if (s.depth == 0) return hipSuccess;
+    const FaTrees trees = scan_trees(s, s.nold);
+    FaLists L = {};
+    for (unsigned l = 1; l <= s.depth; ++l) {
+        L.in[l] = in[l];
+        L.off[l] = list_off[l];
+    }
+    const dim3 blk(FA_BLOCK);
+    hipLaunchKernelGGL(k_fa_tile_sums<FA_DIRTY>, dim3((unsigned)s.tiles, s.depth), blk, 0, st, trees, s.tsum);
+    hipLaunchKernelGGL(k_fa_scan_tiles, dim3(s.depth), blk, 0, st, s.tsum, s.tiles);
+    hipLaunchKernelGGL(k_fa_scan_apply<FA_DIRTY>, dim3((unsigned)s.tiles, s.depth), blk, 0, st, trees, s.tsum, s.rows, (Scalar32*)nullptr, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k_fa_expand, dim3((unsigned)((in[1] + FA_BLOCK - 1) / FA_BLOCK), s.depth), blk, 0, st, s.rows, trees, L, static_cast<uint4*>(lists));
+    return hipGetLastError();
 }
 
 }  // namespace p252

@@ -852,6 +852,72 @@ class Context:
                        _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
+    # ---- a forest kept only as its frontiers (p252_merkle{4,2}_forest_frontier_*; csrc/forest_frontier.hip) ----
+    def merkle4_forest_frontier_bound(self, max_leaves):
+        """scalars of one tree's frontier, (depth(max_leaves) + 1) * 3 (p252_merkle4_forest_frontier_bound)"""
+        return int(_ARITIES[4].fn("forest_frontier_bound")(max_leaves))
+
+    def merkle2_forest_frontier_bound(self, max_leaves):
+        """the same for arity 2: depth(max_leaves) + 1"""
+        return int(_ARITIES[2].fn("forest_frontier_bound")(max_leaves))
+
+    def merkle4_forest_frontier_append_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                              d_n_bad=None, d_n_hashed=None):
+        """leaves appended to n_trees trees that are kept only as their frontiers, IN PLACE
+        (p252_merkle4_forest_frontier_append_device_into): d_counts (n_trees int64/uint64), d_frontier (n_trees x
+        merkle4_forest_frontier_bound(max_leaves) scalars) and d_roots (n_trees, 4) are the state — all zero for empty trees; tree t
+        receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (n_trees + 1 int64/uint64; d_add None: nothing appended).  Afterwards
+        d_roots[t] is the root of all leaves tree t was ever given.  A refused append leaves its tree untouched and is counted in
+        d_n_bad (a zeroed device int32/uint32, optional); d_n_hashed (a zeroed device int64/uint64, optional) receives the digests
+        computed.  Asynchronous on the current stream."""
+        self._forest_frontier_append_device("merkle4_forest_frontier_append_device", _ARITIES[4], tag, d_counts, d_frontier, d_roots, n_trees,
+                                            max_leaves, d_add, d_add_offsets, d_n_bad, d_n_hashed)
+
+    def merkle2_forest_frontier_append_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                              d_n_bad=None, d_n_hashed=None):
+        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
+        self._forest_frontier_append_device("merkle2_forest_frontier_append_device", _ARITIES[2], tag, d_counts, d_frontier, d_roots, n_trees,
+                                            max_leaves, d_add, d_add_offsets, d_n_bad, d_n_hashed)
+
+    def _forest_frontier_append_device(self, f, a, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets, d_n_bad,
+                                       d_n_hashed):
+        stride = (a.depth(max_leaves) + 1) * a.per if max_leaves else 0  # p252_merkle{4,2}_forest_frontier_bound
+        self._check(a.fn("forest_frontier_append_device_into")(
+            self._h, _tag(tag), _dev_ptr(self, f, "d_counts", d_counts, n_trees * 8, elem=8),
+            _dev_ptr(self, f, "d_frontier", d_frontier, n_trees * stride * 32), _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), n_trees,
+            max_leaves, _dev_ptr(self, f, "d_add", d_add, 0, null_ok=True), _n_scalars(d_add) if d_add is not None else 0,
+            _dev_ptr(self, f, "d_add_offsets", d_add_offsets, (n_trees + 1) * 8, elem=8),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
+            _stream(self)))
+
+    def merkle4_forest_frontier_extract_device(self, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
+                                               d_counts, d_frontier, d_roots, d_n_bad=None):
+        """the frontier state of a forest merkle_forest_ragged_device built with d_levels (p252_merkle4_forest_frontier_extract_device_into;
+        no hashing): d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest exactly as the build took and filled them;
+        writes d_counts (n_trees), d_frontier (n_trees x merkle4_forest_frontier_bound(max_leaves), max_leaves >= max_leaves_forest) and
+        d_roots (n_trees, 4).  A bad tree becomes an empty one and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
+        self._forest_frontier_extract_device("merkle4_forest_frontier_extract_device", _ARITIES[4], d_leaves, d_offsets, n_trees,
+                                             max_leaves_forest, d_levels, d_roots_forest, max_leaves, d_counts, d_frontier, d_roots, d_n_bad)
+
+    def merkle2_forest_frontier_extract_device(self, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
+                                               d_counts, d_frontier, d_roots, d_n_bad=None):
+        """the same for arity 2"""
+        self._forest_frontier_extract_device("merkle2_forest_frontier_extract_device", _ARITIES[2], d_leaves, d_offsets, n_trees,
+                                             max_leaves_forest, d_levels, d_roots_forest, max_leaves, d_counts, d_frontier, d_roots, d_n_bad)
+
+    def _forest_frontier_extract_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
+                                        d_counts, d_frontier, d_roots, d_n_bad):
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves_forest)
+        stride = (a.depth(max_leaves) + 1) * a.per if max_leaves else 0  # p252_merkle{4,2}_forest_frontier_bound
+        self._check(a.fn("forest_frontier_extract_device_into")(
+            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves_forest,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_roots_forest", d_roots_forest, n_trees * 32), max_leaves,
+            _dev_ptr(self, f, "d_counts", d_counts, n_trees * 8, elem=8), _dev_ptr(self, f, "d_frontier", d_frontier, n_trees * stride * 32),
+            _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
     # ---- the shared proof across a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_*; csrc/forest_multiproof.hip) ----
     def merkle4_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
         """upper bound, in scalars, of the shared proof of k pairs of a ragged forest (p252_merkle4_forest_ragged_multiproof_bound)"""

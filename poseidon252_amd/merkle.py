@@ -284,6 +284,65 @@ def forest_ragged_journal_swap(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_
     return n_bad
 
 
+class ForestFrontier:
+    """A forest of append-only trees kept only as their frontiers, on the device: counts (n_trees,) int64, frontier (n_trees, bound, 4)
+    int64 with bound = Context.merkle{4,2}_forest_frontier_bound(max_leaves), roots (n_trees, 4) int64 — O(depth) scalars per tree
+    whatever the trees hold.  ForestFrontier(ctx, n_trees, max_leaves) is a forest of empty trees; from_forest takes the state out of
+    a built ragged forest; append grows the trees in place."""
+
+    def __init__(self, ctx, n_trees, max_leaves, arity=4, device=None, counts=None, frontier=None, roots=None):
+        import torch
+        _arity("ForestFrontier", arity)
+        self.ctx = ctx or Context.default()
+        self.n_trees, self.max_leaves, self.arity = n_trees, max_leaves, arity
+        dev = device if device is not None else "cuda:%d" % self.ctx.device
+        bound = (self.ctx.merkle4_forest_frontier_bound if arity == 4 else self.ctx.merkle2_forest_frontier_bound)(max_leaves)
+        self.counts = torch.zeros(n_trees, dtype=torch.int64, device=dev) if counts is None else counts
+        self.frontier = torch.zeros((n_trees, bound, 4), dtype=torch.int64, device=dev) if frontier is None else frontier
+        self.roots = torch.zeros((n_trees, 4), dtype=torch.int64, device=dev) if roots is None else roots
+
+    @classmethod
+    def from_forest(cls, ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, max_leaves=None, arity=4):
+        """the state of a forest Context.merkle_forest_ragged_device built with d_levels -> (ForestFrontier, d_n_bad (1,) int32)"""
+        self = cls(ctx, n_trees, max_leaves_forest if max_leaves is None else max_leaves, arity, device=d_leaves.device)
+        return self, forest_frontier_extract(self.ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, self)
+
+    def append(self, d_add, d_add_offsets, tag=None):
+        """tree t receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] -> (d_n_bad (1,) int32, d_n_hashed (1,) int64); no synchronisation"""
+        return forest_frontier_append(self.ctx, tag, self, d_add, d_add_offsets)
+
+
+def forest_frontier_append(ctx, tag, state, d_add, d_add_offsets):
+    """Leaves appended to the trees of a ForestFrontier, in place (Context.merkle{4,2}_forest_frontier_append_device): tree t receives
+    d_add[d_add_offsets[t]:d_add_offsets[t+1]] (torch CUDA tensors; d_add None: nothing).  Returns (d_n_bad (1,) int32, d_n_hashed (1,)
+    int64) on the device: the refused appends, whose trees are untouched, and the digests computed.  No synchronisation."""
+    import torch
+    a = _arity("forest_frontier_append", state.arity)
+    ctx = ctx or state.ctx
+    dev = state.counts.device
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
+    call = ctx.merkle4_forest_frontier_append_device if state.arity == 4 else ctx.merkle2_forest_frontier_append_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves,
+         d_add, d_add_offsets, n_bad, n_hashed)
+    return n_bad, n_hashed
+
+
+def forest_frontier_extract(ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, state):
+    """The frontiers of a built ragged forest written into `state` (a ForestFrontier of n_trees trees with max_leaves >=
+    max_leaves_forest), with no digest (Context.merkle{4,2}_forest_frontier_extract_device).  Returns d_n_bad (1,) int32 on the device:
+    the trees the build calls bad, which become empty ones.  No synchronisation."""
+    import torch
+    _arity("forest_frontier_extract", state.arity)
+    ctx = ctx or state.ctx
+    if state.n_trees != n_trees:
+        raise ValueError("forest_frontier_extract: the state holds %d trees, the forest %d" % (state.n_trees, n_trees))
+    n_bad = torch.zeros(1, dtype=torch.int32, device=state.counts.device)
+    call = ctx.merkle4_forest_frontier_extract_device if state.arity == 4 else ctx.merkle2_forest_frontier_extract_device
+    call(d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, state.max_leaves, state.counts, state.frontier, state.roots, n_bad)
+    return n_bad
+
+
 def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
     as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are
