@@ -28,7 +28,9 @@
 //   —                                               merkle_forest_ragged_multiproof_device / _verify_device / _bound: leaves of many
 //                                                   trees of a ragged forest, one tree-major shared proof
 //   —                                               merkle_forest_frontier_append_device / _extract_device / _bound: a forest of
-//                                                   append-only trees kept only as their frontiers
+//                                                   append-only trees kept only as their frontiers;
+//                                                   merkle_forest_frontier_append_witness_device: the same with the openings of
+//                                                   marked leaves kept current
 //
 // A BlsScalar is 4 little-endian u64 Montgomery limbs (a * 2^256 mod p), exactly the reference's
 // memory layout, so buffers are interchangeable with a Rust &[BlsScalar].
@@ -440,7 +442,7 @@ namespace detail {
     X(N, forest_ragged_journal_swap_device_into) X(N, forest_ragged_select_device_into)                                                      \
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
     X(N, forest_ragged_multiproof_verify_device_into) X(N, forest_frontier_bound) X(N, forest_frontier_append_device_into)                \
-    X(N, forest_frontier_extract_device_into)
+    X(N, forest_frontier_extract_device_into) X(N, forest_frontier_append_witness_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -753,6 +755,33 @@ inline void merkle_forest_frontier_append_device(const ForestFrontier& state, co
     detail::check(m.forest_frontier_append_device_into(ctx.get(), m.tag().data(), state.d_counts, state.d_frontier, state.d_roots, state.n_trees,
                                                        state.max_leaves, d_add, n_add, d_add_offsets, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_frontier_append_device");
+}
+// The same append keeping the openings of k marked leaves current (p252_merkle{4,2}_forest_frontier_append_witness_device_into):
+// witness i names leaf d_leaf_ids[i] (uint64) of tree d_tree_ids[i] (uint32); d_leaves[k], d_siblings[k][D][arity - 1],
+// d_positions[k][D] and d_depths[k] at the stride D = forest_openings_stride(state.max_leaves, arity) are the layout of
+// merkle_forest_ragged_openings_device, read and updated in place.  A witness of a leaf below its tree's old count must be its opening
+// at that count; one of a leaf this call appends is written whole; one that names no leaf becomes all zero with depth 0xFF and is
+// counted in *d_n_bad_witness.  Every good witness then verifies against state.d_roots (merkle_forest_ragged_verify_device).
+struct ForestWitnesses {
+    const void* d_tree_ids;
+    const void* d_leaf_ids;
+    std::size_t k;
+    void* d_leaves;
+    void* d_siblings;
+    void* d_positions;
+    void* d_depths;
+};
+inline void merkle_forest_frontier_append_witness_device(const ForestFrontier& state, const void* d_add, std::size_t n_add,
+                                                         const void* d_add_offsets, const ForestWitnesses& witnesses, unsigned arity = 4,
+                                                         Context& ctx = Context::default_context(), void* d_n_bad = nullptr,
+                                                         void* d_n_hashed = nullptr, void* d_n_bad_witness = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_frontier_append_witness_device", arity);
+    detail::check(m.forest_frontier_append_witness_device_into(ctx.get(), m.tag().data(), state.d_counts, state.d_frontier, state.d_roots,
+                                                               state.n_trees, state.max_leaves, d_add, n_add, d_add_offsets, witnesses.d_tree_ids,
+                                                               witnesses.d_leaf_ids, witnesses.k, witnesses.d_leaves, witnesses.d_siblings,
+                                                               witnesses.d_positions, witnesses.d_depths, d_n_bad, d_n_hashed, d_n_bad_witness,
+                                                               stream),
+                  ctx.get(), "merkle_forest_frontier_append_witness_device");
 }
 // The state of a BUILT forest (`forest` and d_roots_forest exactly as the build took and filled them), with no digest:
 // state.max_leaves >= forest.max_leaves.  A bad tree becomes an empty one and is counted in *d_n_bad.

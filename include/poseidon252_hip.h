@@ -119,7 +119,9 @@ extern "C" {
  *      leaves of many trees of such a forest behind one tree-major shared proof, each ancestor hashed once;
  *      + p252_merkle{4,2}_forest_frontier_bound, _forest_frontier_append_device_into, _forest_frontier_extract_device_into
  *      (additive, same version; `_into`: the state is the caller's three buffers): leaves appended to a forest that is kept only
- *      as its frontiers — a count, a root and depth + 1 short rows per tree — and that state taken out of a built forest */
+ *      as its frontiers — a count, a root and depth + 1 short rows per tree — and that state taken out of a built forest;
+ *      + p252_merkle{4,2}_forest_frontier_append_witness_device_into (additive, same version): the same append keeping the
+ *      openings of marked leaves current, so that such a forest can prove membership without being stored */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -836,6 +838,59 @@ int p252_merkle4_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_
 int p252_merkle2_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
                                                     size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
                                                     const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream);
+/* The same append with INCREMENTAL WITNESSES: the openings of k marked leaves are kept current while the trees grow underneath them,
+ * so a forest kept only as its frontiers can still prove that a leaf is in it.  The state arguments, d_add, d_add_offsets, d_n_bad and
+ * d_n_hashed mean, refuse and end exactly as in p252_merkle{4,2}_forest_frontier_append_device_into (byte for byte on the same
+ * inputs); k == 0 IS that call (the witness buffers are not looked at and may be NULL).  The witnesses have the layout of
+ * p252_merkle{4,2}_forest_ragged_openings_device at the stride D = p252_merkle{4,2}_depth(max_leaves), A = arity: d_wit_tree_ids[k]
+ * (uint32) and d_wit_leaf_ids[k] (uint64) are read only; d_wit_leaves[k], d_wit_siblings[k][D][A - 1], d_wit_positions[k][D] and
+ * d_wit_depths[k] (uint8) are read and updated in place.  Duplicates and any order are fine: each witness has its own slots.
+ * Witness i names leaf p of tree t; n = the tree's count before the call, n' after it (n' == n where nothing was appended or the
+ * append was refused).  With f_l(n) = floor(n / A^l) and c_l(n) = ceil(n / A^l) the append computes V_l = the nodes [f_l(n), c_l(n'))
+ * of every level l (V_0 = the new leaves); the sibling x of an opening on level l is FINAL (x < f_l(n)), in V_l (x < c_l(n')) or zero.
+ *   BAD — t >= n_trees, or p >= n' (a leaf of a refused append included): the witness becomes all zero with depth 0xFF, as the
+ *     openings call writes a bad opening, and is counted once in *d_n_bad_witness (device uint32 the caller has zeroed; may be NULL).
+ *   CARRIED, p < n, the tree unchanged (n' == n): untouched byte for byte; one whose depth byte is 0xFF already is counted again.
+ *   CARRIED, p < n, the tree grown: the input must be the tree's opening at count n.  The one thing the call can check it checks:
+ *     d_wit_depths[i] == depth(n), otherwise (an input 0xFF included) the witness is BAD as above.  Rows l < depth(n'): with g = p >>
+ *     ((l + 1) log2 A) the path's group and (p >> l log2 A) mod A its slot (the position byte), a row whose whole group is final
+ *     (g < f_{l+1}(n)) stays; in any other row the final siblings stay, those below c_l(n') come from V_l, the rest are zero.  Rows
+ *     at or past depth(n') stay (they are zero in an opening at n), the leaf stays, the depth byte becomes depth(n').
+ *   MARKED in this call, n <= p < n': the input content is ignored.  The leaf is d_add[add_offsets[t] + p - n], bytes as given; a
+ *     final sibling x < f_l(n) is the frontier's OLD row l at slot x - A f_{l+1}(n) (the path's node is at or past f_l(n), so its
+ *     group is the partly filled one), the others as above; rows at or past depth(n') are zero.
+ * Afterwards every witness that is not bad is byte for byte what p252_merkle{4,2}_forest_ragged_openings_device writes for (t, p) on
+ * a stored forest of all leaves so far built with the same max_leaves, and goes into p252_merkle{4,2}_path_ragged_device and
+ * _forest_ragged_verify_device against d_roots of the state unchanged.  A stored forest hands over with two existing calls: the
+ * openings of the leaves to watch, then _forest_frontier_extract_device_into.  Keeping the witnesses current costs NO digest: one
+ * launch more between the last digest launch and the update of the state, which gathers out of scratch the append holds anyway — a
+ * block takes floor(256 / D) whole witnesses, one lane per (witness, row) — and no scratch of its own.
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: everything the plain call refuses; with k > 0 a NULL or misaligned witness buffer
+ * (scalars 16 bytes, d_wit_leaf_ids 8, d_wit_tree_ids and d_n_bad_witness 4; d_wit_siblings and d_wit_positions may be NULL when
+ * D == 0, i.e. max_leaves == 1: only leaves and depth bytes exist); size overflow of k D (A - 1) 32 or of the launch; d_wit_leaves,
+ * d_wit_siblings, d_wit_positions, d_wit_depths or d_n_bad_witness overlapping the state, d_add, d_add_offsets, the ids, d_n_bad,
+ * d_n_hashed or one another.  n_trees == 0 with k > 0 is a forest in which every witness is bad (the state may be NULL).
+ * Asynchronous on hip_stream: no host synchronisation, no allocation beyond the plain call's scratch.
+ * Measured (profiles/forest_witness.txt) in one run, medians of 20, as: with witnesses / the plain call / the stored append +
+ * p252_merkle{4,2}_forest_ragged_openings_device of the same pairs.  One 4^12-leaf tree + 2^16 leaves with 2^10, 2^16, 2^20 carried
+ * witnesses 1.63 / 1.61 / 2.04, 1.63 / 1.62 / 2.06 and 1.78 / 1.63 / 2.76 ms, with the 2^16 new leaves marked 1.67 / 1.61 / 2.05 ms;
+ * arity 2 on 2^24 leaves 3.09 / 3.06 / 3.71, 3.12 / 3.09 / 3.76, 3.38 / 3.10 / 4.34 and 3.13 / 3.08 / 3.74 ms; 20,000 mixed trees with
+ * 169,761 witnesses 1.30 / 1.27 / 2.06 ms.  The upkeep is one launch, under 10 % of the plain call on every row, but not a copy's
+ * speed: at 2^20 witnesses 0.16 ms (arity 2: 0.28 ms) against 0.04 ms (0.02 ms) for a device copy of the bytes it writes — it
+ * runs a lane for every row, changed or not. */
+int p252_merkle4_forest_frontier_append_witness_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier,
+                                                            void* d_roots, size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                            const void* d_add_offsets, const void* d_wit_tree_ids, const void* d_wit_leaf_ids,
+                                                            size_t k, void* d_wit_leaves, void* d_wit_siblings, void* d_wit_positions,
+                                                            void* d_wit_depths, void* d_n_bad, void* d_n_hashed, void* d_n_bad_witness,
+                                                            void* hip_stream);
+/* the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag) */
+int p252_merkle2_forest_frontier_append_witness_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier,
+                                                            void* d_roots, size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                            const void* d_add_offsets, const void* d_wit_tree_ids, const void* d_wit_leaf_ids,
+                                                            size_t k, void* d_wit_leaves, void* d_wit_siblings, void* d_wit_positions,
+                                                            void* d_wit_depths, void* d_n_bad, void* d_n_hashed, void* d_n_bad_witness,
+                                                            void* hip_stream);
 /* The state of a BUILT ragged forest: d_leaves, n_leaves, d_offsets, n_trees, max_leaves_forest, d_levels and d_roots_forest exactly
  * as p252_merkle{4,2}_forest_ragged_device was given and filled them (read-only; d_levels may be NULL when max_leaves_forest <= 1);
  * the leaf counts come from the build's own validation.  Writes d_counts, d_frontier (rows for max_leaves >= max_leaves_forest, so

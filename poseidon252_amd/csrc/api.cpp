@@ -16,6 +16,7 @@
 #include "ctx.hpp"
 #include "forest_append.h"
 #include "forest_frontier.h"
+#include "forest_witness.h"
 #include "forest_journal.h"
 #include "forest_openings.h"
 #include "forest_ragged.h"
@@ -1600,37 +1601,97 @@ static int forest_frontier_shape_check(p252_ctx* ctx, const std::string& who, un
     return P252_OK;
 }
 
+// the witnesses of p252_merkle{4,2}_forest_frontier_append_witness_device_into as the caller gave them (forest_witness.hip)
+namespace {
+struct WitnessArgs {
+    const void* tree_ids;
+    const void* leaf_ids;
+    size_t k;
+    void* leaves;
+    void* siblings;
+    void* positions;
+    void* depths;
+    void* n_bad;
+};
+}  // namespace
+
+// wit == nullptr or wit->k == 0: the plain append — the witness buffers are not looked at and nothing is launched for them
 static int forest_frontier_append_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
                                          size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add, const void* d_add_offsets,
-                                         void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+                                         void* d_n_bad, void* d_n_hashed, const WitnessArgs* wit, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_trees == 0) return P252_OK;
-    const std::string who = "merkle_forest_frontier_append";
+    const size_t k = wit ? wit->k : 0;
+    if (n_trees == 0 && k == 0) return P252_OK;
+    const std::string who = k ? "merkle_forest_frontier_append_witness" : "merkle_forest_frontier_append";
     if (max_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_leaves must be > 0");
     if (n_add > 0xffffffffull) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_add must be below 2^32 (append in smaller chunks)");
     if (int rc = forest_frontier_shape_check(ctx, who, arity, n_trees, max_leaves)) return rc;
     if (n_trees > 0xffffffffull || (n_add && n_trees > (SIZE_MAX / 2) / n_add))  // (a record names its tree in 32 bits)
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
-    if (!tag || !d_counts || !d_frontier || !d_roots || !d_add_offsets || (n_add && !d_add))
+    // (a forest of no tree has no state to name: all of its witnesses are bad ones)
+    if (!tag || (n_trees && (!d_counts || !d_frontier || !d_roots || !d_add_offsets)) || (n_add && !d_add))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
     if (misaligned(d_frontier) || misaligned(d_roots) || misaligned(d_add)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
     if (misaligned_to(d_counts, 8) || misaligned_to(d_add_offsets, 8) || misaligned_to(d_n_hashed, 8))
         return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_counts, d_add_offsets and d_n_hashed must be 8-byte aligned");
     if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
     const size_t stride = forest_frontier_stride(arity, max_leaves);
-    const ByteRange in[] = {{d_add, n_add * 32, "d_add"}, {d_add_offsets, (n_trees + 1) * 8, "d_add_offsets"}};
+    const ByteRange in[] = {{d_add, n_add * 32, "d_add"}, {d_add_offsets, n_trees ? (n_trees + 1) * 8 : 0, "d_add_offsets"}};
     const ByteRange out[] = {{d_counts, n_trees * 8, "d_counts"}, {d_frontier, n_trees * stride * 32, "d_frontier"},
                              {d_roots, n_trees * 32, "d_roots"},  {d_n_bad, 4, "d_n_bad"},
                              {d_n_hashed, 8, "d_n_hashed"}};
     for (const ByteRange& o : out)
         for (const ByteRange& i : in)
             if (ranges_overlap(o, i)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + o.name + " overlaps " + i.name);
+    ForestWitnesses witnesses;
+    if (k) {
+        const size_t depth = forest_ragged_depth(max_leaves, arity);
+        if (!wit->tree_ids || !wit->leaf_ids || !wit->leaves || !wit->depths || (depth && (!wit->siblings || !wit->positions)))
+            return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+        if (misaligned(wit->leaves) || (depth && misaligned(wit->siblings))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+        if (misaligned_to(wit->leaf_ids, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_wit_leaf_ids must be 8-byte aligned");
+        if (misaligned_to(wit->tree_ids, 4) || misaligned_to(wit->n_bad, 4))
+            return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_wit_tree_ids and d_n_bad_witness must be 4-byte aligned");
+        // k x D x (arity - 1) scalars inside size_t, and the blocks of the pass (floor(256 / D) witnesses each) inside a grid
+        if (k > SIZE_MAX / 128 / (depth ? depth : 1) || forest_witness_blocks(k, (unsigned)depth) > 0x7fffffffull)
+            return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+        // what the pass writes against everything the call reads or writes, and against each other
+        const ByteRange mine[] = {{wit->leaves, k * 32, "d_wit_leaves"},
+                                  {wit->siblings, k * depth * (arity - 1) * 32, "d_wit_siblings"},
+                                  {wit->positions, k * depth, "d_wit_positions"},
+                                  {wit->depths, k, "d_wit_depths"},
+                                  {wit->n_bad, 4, "d_n_bad_witness"}};
+        const ByteRange ids[] = {{wit->tree_ids, k * 4, "d_wit_tree_ids"}, {wit->leaf_ids, k * 8, "d_wit_leaf_ids"}};
+        for (size_t a = 0; a < sizeof mine / sizeof *mine; ++a) {
+            const ByteRange* hit = nullptr;
+            for (const ByteRange& o : out)
+                if (ranges_overlap(mine[a], o)) hit = &o;
+            for (const ByteRange& i : in)
+                if (ranges_overlap(mine[a], i)) hit = &i;
+            for (const ByteRange& i : ids)
+                if (ranges_overlap(mine[a], i)) hit = &i;
+            for (size_t b = 0; b < a; ++b)
+                if (ranges_overlap(mine[a], mine[b])) hit = &mine[b];
+            if (hit) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + mine[a].name + " overlaps " + hit->name);
+        }
+        witnesses.tree_ids = static_cast<const uint32_t*>(wit->tree_ids);
+        witnesses.leaf_ids = static_cast<const uint64_t*>(wit->leaf_ids);
+        witnesses.k = k;
+        witnesses.leaves = wit->leaves;
+        witnesses.siblings = wit->siblings;
+        witnesses.positions = static_cast<uint8_t*>(wit->positions);
+        witnesses.depths = static_cast<uint8_t*>(wit->depths);
+        witnesses.n_bad = static_cast<unsigned*>(wit->n_bad);
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const ForestFrontierPlan plan = forest_frontier_plan(arity, n_trees, max_leaves, n_add);
+    if (n_trees == 0)  // (no scratch: one launch that marks every witness bad)
+        return launched(ctx, who, launch_forest_frontier_append(ctx->d_tab, tag_arg(tag), plan, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                nullptr, nullptr, nullptr, &witnesses, st));
     return with_stream_scratch(ctx, who, st, plan.work_bytes(), plan.value_bytes(), [&](p252_ctx::LevelSet& set) {
         return launch_forest_frontier_append(ctx->d_tab, tag_arg(tag), plan, d_counts, d_frontier, d_roots, d_add, d_add_offsets, d_n_bad,
-                                             d_n_hashed, set.buf[0], set.buf[1], st);
+                                             d_n_hashed, set.buf[0], set.buf[1], k ? &witnesses : nullptr, st);
     });
 }
 
@@ -1638,14 +1699,37 @@ int p252_merkle4_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_
                                                     size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
                                                     const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
     return forest_frontier_append_device(ctx, 4, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, n_add, d_add_offsets, d_n_bad,
-                                         d_n_hashed, hip_stream);
+                                         d_n_hashed, nullptr, hip_stream);
 }
 
 int p252_merkle2_forest_frontier_append_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier, void* d_roots,
                                                     size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
                                                     const void* d_add_offsets, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
     return forest_frontier_append_device(ctx, 2, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, n_add, d_add_offsets, d_n_bad,
-                                         d_n_hashed, hip_stream);
+                                         d_n_hashed, nullptr, hip_stream);
+}
+
+// the same append with the openings of k marked leaves kept current (forest_witness.hip): one launch more, inside the call
+int p252_merkle4_forest_frontier_append_witness_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier,
+                                                            void* d_roots, size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                            const void* d_add_offsets, const void* d_wit_tree_ids, const void* d_wit_leaf_ids,
+                                                            size_t k, void* d_wit_leaves, void* d_wit_siblings, void* d_wit_positions,
+                                                            void* d_wit_depths, void* d_n_bad, void* d_n_hashed, void* d_n_bad_witness,
+                                                            void* hip_stream) {
+    const WitnessArgs wit = {d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions, d_wit_depths, d_n_bad_witness};
+    return forest_frontier_append_device(ctx, 4, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, n_add, d_add_offsets, d_n_bad,
+                                         d_n_hashed, &wit, hip_stream);
+}
+
+int p252_merkle2_forest_frontier_append_witness_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_counts, void* d_frontier,
+                                                            void* d_roots, size_t n_trees, size_t max_leaves, const void* d_add, size_t n_add,
+                                                            const void* d_add_offsets, const void* d_wit_tree_ids, const void* d_wit_leaf_ids,
+                                                            size_t k, void* d_wit_leaves, void* d_wit_siblings, void* d_wit_positions,
+                                                            void* d_wit_depths, void* d_n_bad, void* d_n_hashed, void* d_n_bad_witness,
+                                                            void* hip_stream) {
+    const WitnessArgs wit = {d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions, d_wit_depths, d_n_bad_witness};
+    return forest_frontier_append_device(ctx, 2, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, n_add, d_add_offsets, d_n_bad,
+                                         d_n_hashed, &wit, hip_stream);
 }
 
 static int forest_frontier_extract_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,

@@ -34,12 +34,32 @@ struct ForestFrontierPlan {
 size_t forest_frontier_stride(unsigned arity, size_t max_leaves);  // p252_merkle{4,2}_forest_frontier_bound
 ForestFrontierPlan forest_frontier_plan(unsigned arity, size_t n_trees, size_t max_leaves, size_t n_add);
 
+// What an append holds between its last digest launch and k_ff_finish, for a pass that reads it there (forest_witness.hip): per tree
+// n_t and the accepted m_t; rows[l][t] = where tree t's run of V_l = the nodes [f_l(n), c_l(n')) starts inside level l's values, which
+// begin at values + list_off[l] (l >= 1; V_0 = add + add_offsets[t]); the frontier with its OLD rows.  rows, values and add are read for
+// a tree with m_t > 0 only.
+struct ForestFrontierView {
+    const uint64_t* nold = nullptr;
+    const uint64_t* madd = nullptr;
+    const uint64_t* rows = nullptr;  // (depth + 1) x (n_trees + 1)
+    uint64_t list_off[FOREST_RAGGED_MAX_DEPTH + 1] = {};
+    const void* values = nullptr;
+    const void* add = nullptr;
+    const uint64_t* add_offsets = nullptr;
+    const void* frontier = nullptr;
+    uint64_t stride = 0;  // scalars of one tree's frontier
+    size_t n_trees = 0;
+    unsigned log2a = 2, depth = 0;
+};
+struct ForestWitnesses;  // forest_witness.h
+
 // The whole append on `st`: work = plan.work_bytes(), values = plan.value_bytes() of scratch.  counts (n_trees uint64), frontier
 // (n_trees x plan.stride scalars) and roots (n_trees scalars) are read and, once every digest launch is queued, updated in place.
-// add may be null when plan.n_add == 0; n_bad (uint32) and n_hashed (uint64) may be null.
+// add may be null when plan.n_add == 0; n_bad (uint32) and n_hashed (uint64) may be null.  witnesses (null: none, and no launch for
+// them) are refreshed behind the last digest launch and before the state changes (launch_forest_witness_refresh).
 hipError_t launch_forest_frontier_append(const int32_t* tab, const TagArg& tag, const ForestFrontierPlan& plan, void* counts, void* frontier,
                                          void* roots, const void* add, const void* add_offsets, void* n_bad, void* n_hashed, void* work,
-                                         void* values, hipStream_t st);
+                                         void* values, const ForestWitnesses* witnesses, hipStream_t st);
 
 // The state of a built ragged forest on `st`: meta = forest_ragged_index_bytes(n_trees) of scratch; the leaf counts are the build's
 // own validation (launch_forest_ragged_index).  A bad tree gets count 0, zero rows and a zero root and is counted in n_bad (uint32,

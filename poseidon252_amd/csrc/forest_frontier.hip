@@ -30,6 +30,7 @@
 #include "forest_append.h"
 #include "forest_frontier.h"
 #include "forest_node.hpp"
+#include "forest_witness.h"
 #include "multiproof.h"
 
 namespace p252 {
@@ -224,9 +225,13 @@ ForestFrontierPlan forest_frontier_plan(unsigned arity, size_t n_trees, size_t m
 
 hipError_t launch_forest_frontier_append(const int32_t* tab, const TagArg& tag, const ForestFrontierPlan& p, void* counts, void* frontier,
                                          void* roots, const void* add, const void* add_offsets, void* n_bad, void* n_hashed, void* work,
-                                         void* values, hipStream_t st) {
+                                         void* values, const ForestWitnesses* witnesses, hipStream_t st) {
     const size_t T = p.n_trees;
-    if (T == 0) return hipSuccess;
+    const bool watched = witnesses && witnesses->k;
+    ForestFrontierView view;  // (no tree: every witness is a bad one)
+    view.log2a = p.log2a;
+    view.depth = p.depth;
+    if (T == 0) return watched ? launch_forest_witness_refresh(view, *witnesses, st) : hipSuccess;
     uint64_t* w = static_cast<uint64_t*>(work);
     FfTrees trees;
     trees.nold = w;
@@ -260,12 +265,24 @@ hipError_t launch_forest_frontier_append(const int32_t* tab, const TagArg& tag, 
         hipLaunchKernelGGL(k_ff_refused, per_tree, blk, 0, st, trees, static_cast<unsigned*>(n_bad));
         e = hipGetLastError();
     }
-    if (e != hipSuccess || p.n_add == 0) return e;  // (nothing to append: the refusals are counted, no tree changes)
+    if (e != hipSuccess) return e;
+    view.nold = trees.nold;
+    view.madd = trees.madd;
+    view.rows = rows;
+    view.values = values;
+    view.add = add;
+    view.add_offsets = aoff;
+    view.frontier = frontier;
+    view.stride = p.stride;
+    view.n_trees = T;
+    // (nothing to append: the refusals are counted, no tree changes — every m_t is 0, and the witnesses' pass reads the counts alone)
+    if (p.n_add == 0) return watched ? launch_forest_witness_refresh(view, *witnesses, st) : hipSuccess;
 
     FfLists L = {};
     for (unsigned l = 1; l <= p.depth; ++l) {
         L.in[l] = p.in[l];
         L.off[l] = p.list_off[l];
+        view.list_off[l] = p.list_off[l];
     }
     if (p.depth) {
         e = forest_append_scan_dirty_lists(scan, p.in, p.list_off, lists, st);
@@ -287,6 +304,10 @@ hipError_t launch_forest_frontier_append(const int32_t* tab, const TagArg& tag, 
         d.w_node = wnode + p.list_off[l];
         d.bound = p.in[l];
         e = launch_multiproof_digest_list(tab, tag, p.arity, d, st);
+        if (e != hipSuccess) return e;
+    }
+    if (watched) {  // V_l of every level is in `values`, the frontier still holds the old rows
+        e = launch_forest_witness_refresh(view, *witnesses, st);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_ff_finish, dim3(per_tree.x, p.depth + 2), blk, 0, st, rows, aoff, trees, L, (uint64_t)p.stride,

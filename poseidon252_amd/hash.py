@@ -890,6 +890,49 @@ class Context:
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
             _stream(self)))
 
+    def merkle4_forest_frontier_append_witness_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                                      d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions,
+                                                      d_wit_depths, d_n_bad=None, d_n_hashed=None, d_n_bad_witness=None):
+        """merkle4_forest_frontier_append_device keeping the openings of k marked leaves current, IN PLACE
+        (p252_merkle4_forest_frontier_append_witness_device_into): witness i names leaf d_wit_leaf_ids[i] (int64/uint64) of tree
+        d_wit_tree_ids[i] (int32/uint32); d_wit_leaves (k, 4), d_wit_siblings (k, D, 3, 4), d_wit_positions (k, D) uint8 and
+        d_wit_depths (k,) uint8 with D = depth(max_leaves) are what merkle_forest_ragged_openings_device writes at that stride.  A
+        witness of a leaf below the tree's old count must be its opening at that count and becomes its opening in the grown tree; one
+        of a leaf this call appends is written whole; one that names no leaf becomes all zero with depth 0xFF and is counted in
+        d_n_bad_witness (a zeroed device int32/uint32, optional).  The siblings and positions may be None when D == 0.  Every good
+        witness verifies against d_roots (merkle_forest_ragged_verify_device).  Asynchronous on the current stream."""
+        self._forest_frontier_append_witness_device("merkle4_forest_frontier_append_witness_device", _ARITIES[4], tag, d_counts, d_frontier, d_roots,
+                                                    n_trees, max_leaves, d_add, d_add_offsets, d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves,
+                                                    d_wit_siblings, d_wit_positions, d_wit_depths, d_n_bad, d_n_hashed, d_n_bad_witness)
+
+    def merkle2_forest_frontier_append_witness_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                                      d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions,
+                                                      d_wit_depths, d_n_bad=None, d_n_hashed=None, d_n_bad_witness=None):
+        """the same for arity 2 (d_wit_siblings (k, D, 1, 4); pass the Merkle2 tag)"""
+        self._forest_frontier_append_witness_device("merkle2_forest_frontier_append_witness_device", _ARITIES[2], tag, d_counts, d_frontier, d_roots,
+                                                    n_trees, max_leaves, d_add, d_add_offsets, d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves,
+                                                    d_wit_siblings, d_wit_positions, d_wit_depths, d_n_bad, d_n_hashed, d_n_bad_witness)
+
+    def _forest_frontier_append_witness_device(self, f, a, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                               d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions, d_wit_depths,
+                                               d_n_bad, d_n_hashed, d_n_bad_witness):
+        depth = a.depth(max_leaves)
+        stride = (depth + 1) * a.per if max_leaves else 0  # p252_merkle{4,2}_forest_frontier_bound
+        none = k == 0  # (the plain call: no witness buffer is looked at)
+        self._check(a.fn("forest_frontier_append_witness_device_into")(
+            self._h, _tag(tag), _dev_ptr(self, f, "d_counts", d_counts, n_trees * 8, elem=8),
+            _dev_ptr(self, f, "d_frontier", d_frontier, n_trees * stride * 32), _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), n_trees,
+            max_leaves, _dev_ptr(self, f, "d_add", d_add, 0, null_ok=True), _n_scalars(d_add) if d_add is not None else 0,
+            _dev_ptr(self, f, "d_add_offsets", d_add_offsets, (n_trees + 1) * 8, elem=8),
+            _dev_ptr(self, f, "d_wit_tree_ids", d_wit_tree_ids, k * 4, elem=4, null_ok=none),
+            _dev_ptr(self, f, "d_wit_leaf_ids", d_wit_leaf_ids, k * 8, elem=8, null_ok=none), k,
+            _dev_ptr(self, f, "d_wit_leaves", d_wit_leaves, k * 32, null_ok=none),
+            _dev_ptr(self, f, "d_wit_siblings", d_wit_siblings, k * depth * a.per * 32, null_ok=none or depth == 0),
+            _dev_ptr(self, f, "d_wit_positions", d_wit_positions, k * depth, elem=1, null_ok=none or depth == 0),
+            _dev_ptr(self, f, "d_wit_depths", d_wit_depths, k, elem=1, null_ok=none),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
+            _dev_ptr(self, f, "d_n_bad_witness", d_n_bad_witness, 4, elem=4, null_ok=True), _stream(self)))
+
     def merkle4_forest_frontier_extract_device(self, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
                                                d_counts, d_frontier, d_roots, d_n_bad=None):
         """the frontier state of a forest merkle_forest_ragged_device built with d_levels (p252_merkle4_forest_frontier_extract_device_into;

@@ -307,25 +307,93 @@ class ForestFrontier:
         self = cls(ctx, n_trees, max_leaves_forest if max_leaves is None else max_leaves, arity, device=d_leaves.device)
         return self, forest_frontier_extract(self.ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, self)
 
-    def append(self, d_add, d_add_offsets, tag=None):
-        """tree t receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] -> (d_n_bad (1,) int32, d_n_hashed (1,) int64); no synchronisation"""
-        return forest_frontier_append(self.ctx, tag, self, d_add, d_add_offsets)
+    def append(self, d_add, d_add_offsets, tag=None, witnesses=None):
+        """tree t receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] -> (d_n_bad (1,) int32, d_n_hashed (1,) int64); with witnesses (a
+        ForestWitnesses) their openings are kept current in the same call and the bad ones are counted in a third (1,) int32; no
+        synchronisation"""
+        return forest_frontier_append(self.ctx, tag, self, d_add, d_add_offsets, witnesses)
 
 
-def forest_frontier_append(ctx, tag, state, d_add, d_add_offsets):
+class ForestWitnesses:
+    """The openings of k marked leaves of a ForestFrontier, kept current by ForestFrontier.append(..., witnesses=self): witness i names
+    leaf leaf_ids[i] of tree tree_ids[i] (sequences, numpy or torch; kept on the device as (k,) int32 and (k,) int64).  leaves (k, 4),
+    siblings (k, D, arity - 1, 4), positions (k, D) uint8 and depths (k,) uint8, D = depth(max_leaves), are the layout of
+    Context.merkle_forest_ragged_openings_device.  A new one is zeroed with depth 0xFF: right for leaves that a later append brings, and
+    bad until then.  Leaves that are in the trees already come from_openings of the stored forest."""
+
+    def __init__(self, ctx, k, max_leaves, arity, tree_ids, leaf_ids, device=None):
+        import torch
+        a = _arity("ForestWitnesses", arity)
+        self.ctx = ctx or Context.default()
+        self.k, self.max_leaves, self.arity, self.depth = k, max_leaves, arity, a.depth(max_leaves)
+        dev = device if device is not None else "cuda:%d" % self.ctx.device
+        ids = lambda x, dtype: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.int64))).to(device=dev, dtype=dtype).contiguous()  # noqa: E731
+        self.tree_ids, self.leaf_ids = ids(tree_ids, torch.int32), ids(leaf_ids, torch.int64)
+        if self.tree_ids.shape != (k,) or self.leaf_ids.shape != (k,):
+            raise ValueError("ForestWitnesses: tree_ids and leaf_ids must hold k = %d ids each" % k)
+        self.leaves = torch.zeros((k, 4), dtype=torch.int64, device=dev)
+        self.siblings = torch.zeros((k, self.depth, a.per, 4), dtype=torch.int64, device=dev)
+        self.positions = torch.zeros((k, self.depth), dtype=torch.uint8, device=dev)
+        self.depths = torch.full((k,), 0xFF, dtype=torch.uint8, device=dev)
+
+    @classmethod
+    def from_openings(cls, ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, tree_ids, leaf_ids, max_leaves=None, arity=4):
+        """the witnesses of leaves of a forest Context.merkle_forest_ragged_device built with d_levels, at the stride of max_leaves (>=
+        max_leaves_forest: the bound of the ForestFrontier that takes the forest over) -> (ForestWitnesses, d_n_bad (1,) int32)"""
+        import torch
+        top = max_leaves_forest if max_leaves is None else max_leaves
+        self = cls(ctx, len(tree_ids), top, arity, tree_ids, leaf_ids, device=d_leaves.device)
+        n_bad = torch.zeros(1, dtype=torch.int32, device=d_leaves.device)
+        if self.k:
+            inner = _arity("ForestWitnesses", arity).depth(max_leaves_forest)  # the openings come at the forest's own stride
+            lv, sib, pos, dep, _ = self.ctx.merkle_forest_ragged_openings_device(d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels,
+                                                                                 self.tree_ids, self.leaf_ids, self.k, d_n_bad=n_bad, arity=arity)
+            self.leaves.copy_(lv)
+            self.siblings[:, :inner] = sib
+            self.positions[:, :inner] = pos
+            self.depths.copy_(dep)
+        return self, n_bad
+
+    def verify(self, frontier, tag=None):
+        """d_ok (k,) uint8 on the device: 1 iff witness i re-hashes to the root of ITS tree in `frontier` (a ForestFrontier)
+        (Context.merkle_forest_ragged_verify_device); no synchronisation"""
+        import torch
+        a = _arity("ForestWitnesses.verify", self.arity)
+        ok = torch.zeros(self.k, dtype=torch.uint8, device=self.depths.device)
+        if self.k:
+            self.ctx.merkle_forest_ragged_verify_device(a.tag() if tag is None else _as_scalars(tag).reshape(4), self.leaves,
+                                                        self.siblings if self.depth else None, self.positions if self.depth else None, self.depths,
+                                                        self.depth, self.tree_ids, frontier.roots, frontier.n_trees, ok, self.k, arity=self.arity)
+        return ok
+
+
+def forest_frontier_append(ctx, tag, state, d_add, d_add_offsets, witnesses=None):
     """Leaves appended to the trees of a ForestFrontier, in place (Context.merkle{4,2}_forest_frontier_append_device): tree t receives
     d_add[d_add_offsets[t]:d_add_offsets[t+1]] (torch CUDA tensors; d_add None: nothing).  Returns (d_n_bad (1,) int32, d_n_hashed (1,)
-    int64) on the device: the refused appends, whose trees are untouched, and the digests computed.  No synchronisation."""
+    int64) on the device: the refused appends, whose trees are untouched, and the digests computed.  With witnesses (a ForestWitnesses
+    of the same arity and max_leaves) their openings are kept current by the same call
+    (Context.merkle{4,2}_forest_frontier_append_witness_device) and a third tensor, d_n_bad_witness (1,) int32, follows.
+    No synchronisation."""
     import torch
     a = _arity("forest_frontier_append", state.arity)
     ctx = ctx or state.ctx
     dev = state.counts.device
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
     n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
-    call = ctx.merkle4_forest_frontier_append_device if state.arity == 4 else ctx.merkle2_forest_frontier_append_device
-    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves,
-         d_add, d_add_offsets, n_bad, n_hashed)
-    return n_bad, n_hashed
+    tag = a.tag() if tag is None else _as_scalars(tag).reshape(4)
+    if witnesses is None:
+        call = ctx.merkle4_forest_frontier_append_device if state.arity == 4 else ctx.merkle2_forest_frontier_append_device
+        call(tag, state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves, d_add, d_add_offsets, n_bad, n_hashed)
+        return n_bad, n_hashed
+    if witnesses.arity != state.arity or witnesses.max_leaves != state.max_leaves:
+        raise ValueError("forest_frontier_append: the witnesses are of arity %d and max_leaves %d, the state of %d and %d"
+                         % (witnesses.arity, witnesses.max_leaves, state.arity, state.max_leaves))
+    n_bad_witness = torch.zeros(1, dtype=torch.int32, device=dev)
+    call = ctx.merkle4_forest_frontier_append_witness_device if state.arity == 4 else ctx.merkle2_forest_frontier_append_witness_device
+    w = witnesses
+    call(tag, state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves, d_add, d_add_offsets, w.tree_ids, w.leaf_ids, w.k,
+         w.leaves, w.siblings if w.depth else None, w.positions if w.depth else None, w.depths, n_bad, n_hashed, n_bad_witness)
+    return n_bad, n_hashed, n_bad_witness
 
 
 def forest_frontier_extract(ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, state):
