@@ -442,7 +442,8 @@ namespace detail {
     X(N, forest_ragged_journal_swap_device_into) X(N, forest_ragged_select_device_into)                                                      \
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
     X(N, forest_ragged_multiproof_verify_device_into) X(N, forest_frontier_bound) X(N, forest_frontier_append_device_into)                \
-    X(N, forest_frontier_extract_device_into) X(N, forest_frontier_append_witness_device_into)
+    X(N, forest_frontier_extract_device_into) X(N, forest_frontier_append_witness_device_into)                                            \
+    X(N, forest_ragged_consistency_device_into) X(N, forest_consistency_verify_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -793,6 +794,52 @@ inline void merkle_forest_frontier_extract_device(const ForestView& forest, cons
                                                         forest.max_leaves, forest.d_levels, d_roots_forest, state.max_leaves, state.d_counts,
                                                         state.d_frontier, state.d_roots, d_n_bad, stream),
                   ctx.get(), "merkle_forest_frontier_extract_device");
+}
+
+// Consistency proofs (p252_merkle{4,2}_forest_ragged_consistency_device_into / _forest_consistency_verify_device_into): that a tree of a
+// built forest, now of n_t leaves, is the tree it was at d_old_counts[i] (uint64) leaves with leaves appended and nothing before them
+// changed.  Proof i, for tree d_tree_ids[i] (uint32), is the opening of leaf index n of the tree — `proof` in the layout of
+// merkle_forest_ragged_openings_device at the stride forest_openings_stride(forest.max_leaves, arity) — and d_new_counts_out[i] = n_t.
+// n == n_t: zeros with the depth of n_t; a tree id out of range, a bad tree, n == 0 or n > n_t: zeros, depth 0xFF, new count 0, counted
+// in *d_n_bad.  No digest.
+struct ConsistencyProofs {
+    void* d_leaves;     // k scalars
+    void* d_siblings;   // k x stride x (arity - 1) scalars
+    void* d_positions;  // k x stride bytes
+    void* d_depths;     // k bytes
+    std::size_t stride_depth;
+};
+inline void merkle_forest_ragged_consistency_device(const ForestView& forest, const void* d_tree_ids, const void* d_old_counts, std::size_t k,
+                                                    void* d_new_counts_out, const ConsistencyProofs& proof, unsigned arity = 4,
+                                                    Context& ctx = Context::default_context(), void* d_n_bad = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_consistency_device", arity);
+    detail::check(m.forest_ragged_consistency_device_into(ctx.get(), forest.d_leaves, forest.n_leaves, forest.d_offsets, forest.n_trees,
+                                                          forest.max_leaves, forest.d_levels, d_tree_ids, d_old_counts, k, d_new_counts_out,
+                                                          proof.d_leaves, proof.d_siblings, proof.d_positions, proof.d_depths, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_consistency_device");
+}
+// The check: d_ok[i] = 1 iff proof i re-hashes to the new root and its left siblings alone to the old root, with its slots the digits of
+// the old count (the rules: poseidon252_hip.h).  The claims — old count, old root, new count, new root — are element i of the four
+// arrays, or element d_tree_ids[i] of arrays of n_trees entries when d_tree_ids is given: the d_counts / d_roots of a ForestFrontier serve
+// as the old claims as they stand.  d_old_roots_out / d_new_roots_out receive the recomputed roots, *d_n_hashed the digests computed.
+struct ConsistencyClaims {
+    const void* d_old_counts;
+    const void* d_old_roots;
+    const void* d_new_counts;
+    const void* d_new_roots;
+    const void* d_tree_ids = nullptr;
+    std::size_t n_trees = 0;
+};
+inline void merkle_forest_consistency_verify_device(const ConsistencyClaims& claims, const ConsistencyProofs& proof, std::size_t k, void* d_ok,
+                                                    unsigned arity = 4, Context& ctx = Context::default_context(),
+                                                    void* d_old_roots_out = nullptr, void* d_new_roots_out = nullptr,
+                                                    void* d_n_hashed = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_consistency_verify_device", arity);
+    detail::check(m.forest_consistency_verify_device_into(ctx.get(), m.tag().data(), claims.d_old_counts, claims.d_old_roots, claims.d_new_counts,
+                                                          claims.d_new_roots, proof.d_leaves, proof.d_siblings, proof.d_positions, proof.d_depths,
+                                                          proof.stride_depth, k, claims.d_tree_ids, claims.n_trees, d_ok, d_old_roots_out,
+                                                          d_new_roots_out, d_n_hashed, stream),
+                  ctx.get(), "merkle_forest_consistency_verify_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

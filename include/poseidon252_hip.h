@@ -121,7 +121,10 @@ extern "C" {
  *      (additive, same version; `_into`: the state is the caller's three buffers): leaves appended to a forest that is kept only
  *      as its frontiers — a count, a root and depth + 1 short rows per tree — and that state taken out of a built forest;
  *      + p252_merkle{4,2}_forest_frontier_append_witness_device_into (additive, same version): the same append keeping the
- *      openings of marked leaves current, so that such a forest can prove membership without being stored */
+ *      openings of marked leaves current, so that such a forest can prove membership without being stored;
+ *      + p252_merkle{4,2}_forest_ragged_consistency_device_into, _forest_consistency_verify_device_into (additive, same version;
+ *      `_into`: every result goes into buffers the caller owns): the proof that a tree of such a forest is the tree it was at an
+ *      older leaf count with leaves appended and nothing before them changed, and its check against the two roots */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -908,6 +911,70 @@ int p252_merkle2_forest_frontier_extract_device_into(p252_ctx* ctx, const void* 
                                                      size_t n_trees, size_t max_leaves_forest, const void* d_levels,
                                                      const void* d_roots_forest, size_t max_leaves, void* d_counts, void* d_frontier,
                                                      void* d_roots, void* d_n_bad, void* hip_stream);
+
+/* ---- consistency proofs: that a tree of a ragged forest, now of m leaves, is the tree it was at n <= m leaves with leaves appended
+ * and nothing before them changed.  With A the arity, f_l(n) = floor(n / A^l) and d_l(n) = f_l(n) mod A: the proof of (tree t, old
+ * count n) is the OPENING OF LEAF INDEX n of the tree as it is now, in the layout of p252_merkle{4,2}_forest_ragged_openings_device
+ * at stride D = p252_merkle{4,2}_depth(max_leaves).  Its slot on row l is d_l(n), and its siblings left of that slot are the nodes
+ * [A f_{l+1}(n), f_l(n)) of level l, which are final at count n — row l of the frontier of the tree at n leaves.  The whole opening
+ * re-hashes to the new root in the ordinary way; its left siblings alone re-hash to the old root.  O(depth) scalars per proof and
+ * O(depth) digests per check, where replaying the appended leaves through _forest_frontier_append_device_into costs O(m - n). ---- */
+/* Extraction.  The forest arguments d_leaves .. d_levels exactly as p252_merkle{4,2}_forest_ragged_openings_device takes them
+ * (read-only; n_t comes from the build's own validation).  Proof i is for tree d_tree_ids[i] (uint32) and old count d_old_counts[i]
+ * (uint64); it writes d_new_counts_out[i] (uint64), d_leaves_out[i], d_siblings[i][D][arity - 1], d_positions[i][D] (uint8) and
+ * d_depths[i] (uint8):
+ *   1 <= n < n_t: byte for byte what the openings call writes for (t, leaf id n); d_new_counts_out[i] = n_t.
+ *   n == n_t (the tree did not grow): a zero leaf, zero rows and zero positions; the depth byte is depth(n_t); d_new_counts_out[i] = n_t.
+ *   BAD — a tree id >= n_trees, a tree the build calls bad, n == 0 or n > n_t: all zero, depth 0xFF, new count 0, counted once in
+ *     *d_n_bad (device uint32 the caller has zeroed; may be NULL).
+ * Data movement only: nothing is hashed and there is no tag.  P252_ERR_INVALID_ARGUMENT, nothing enqueued: n_leaves, n_trees or
+ * max_leaves == 0, a NULL or misaligned buffer (scalars 16 bytes, d_offsets and the counts 8, d_tree_ids and d_n_bad 4; d_levels,
+ * d_siblings and d_positions may be NULL when max_leaves == 1), size overflow, or an output range that overlaps an input range or
+ * another output.  k == 0 -> P252_OK, nothing enqueued.  Asynchronous on hip_stream; scratch: the forest's index and 32 bytes per
+ * proof. */
+int p252_merkle4_forest_ragged_consistency_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                       size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                       const void* d_old_counts, size_t k, void* d_new_counts_out, void* d_leaves_out,
+                                                       void* d_siblings, void* d_positions, void* d_depths, void* d_n_bad, void* hip_stream);
+/* the same for arity 2 (the level layout of merkle2 trees) */
+int p252_merkle2_forest_ragged_consistency_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                       size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                       const void* d_old_counts, size_t k, void* d_new_counts_out, void* d_leaves_out,
+                                                       void* d_siblings, void* d_positions, void* d_depths, void* d_n_bad, void* hip_stream);
+/* Verification of k such proofs (the four opening arrays at stride_depth <= 64 rows) against claims (old count n, old root, new count
+ * m, new root).  d_tree_ids == NULL: claim i is element i of d_old_counts, d_old_roots, d_new_counts and d_new_roots (k entries
+ * each; n_trees is not looked at).  d_tree_ids != NULL (uint32[k]): the claim arrays hold n_trees entries and claim i is element
+ * d_tree_ids[i]; an id >= n_trees is refused.  So the d_counts / d_roots of a frontier state serve as the old claims and a
+ * publisher's counts and roots as the new ones, with no gather.  d_ok[i] (uint8) = 1 iff ALL of:
+ *   1 <= n <= m, and d_depths[i] == depth(m) <= stride_depth (otherwise the proof is REFUSED);
+ *   n == m: the old and the new root are the same 32 bytes; nothing is hashed and the opening is not read;
+ *   n < m: d_positions[i][l] == d_l(n) for every l < depth(m) — the verifier takes the slots from n, never from the proof; the NEW
+ *     CHAIN, the ordinary re-hash of the opening over all depth(m) rows, ends in the new root; and the OLD CHAIN ends in the old
+ *     root: the carry starts absent; on level l < depth(n), with d = d_l(n), nothing is hashed if d == 0 and there is no carry,
+ *     otherwise the carry becomes H(the first d siblings of row l, then the carry if there is one, then zero scalars); after level
+ *     depth(n) - 1 the carry is the old root.  n == A^depth(n) hashes nothing for the old side: the old root is sibling 0 of row
+ *     depth(n), the final node itself, reduced mod p as a one-leaf tree's root is (n == 1: row 0; a node is left as it is).
+ * The roots do not commit to the counts beyond the depth: a new count that differs from the tree's but has its depth describes the
+ * same tree followed by zero leaves, and passes.
+ * d_old_roots_out[k] / d_new_roots_out[k] (either may be NULL): the recomputed roots; for n == m the claimed roots; zero for a
+ * refused proof.  *d_n_hashed (device uint64 the caller has zeroed; may be NULL) gains, for every proof with n < m that was not
+ * refused, depth(m) plus the digests of its old chain.  Both chains are walks of the re-hash of p252_merkle{4,2}_path_ragged_device —
+ * the old one over a second opening the call lays out in scratch — each sorted by its depths (P252_RAGGED_SORT=0: not sorted).
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: stride_depth > 64, a NULL or misaligned buffer (scalars 16 bytes, the counts and
+ * d_n_hashed 8, d_tree_ids 4; d_siblings and d_positions may be NULL when stride_depth == 0, the claim arrays when d_tree_ids is
+ * given and n_trees == 0), size overflow, or an output range that overlaps an input range or another output.  k == 0 -> P252_OK,
+ * nothing enqueued.  Asynchronous on hip_stream; scratch: per proof a second opening at stride_depth, two roots and 8 bytes of order. */
+int p252_merkle4_forest_consistency_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_old_counts, const void* d_old_roots,
+                                                       const void* d_new_counts, const void* d_new_roots, const void* d_leaves_in,
+                                                       const void* d_siblings, const void* d_positions, const void* d_depths,
+                                                       size_t stride_depth, size_t k, const void* d_tree_ids, size_t n_trees, void* d_ok,
+                                                       void* d_old_roots_out, void* d_new_roots_out, void* d_n_hashed, void* hip_stream);
+/* the same for arity 2 */
+int p252_merkle2_forest_consistency_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_old_counts, const void* d_old_roots,
+                                                       const void* d_new_counts, const void* d_new_roots, const void* d_leaves_in,
+                                                       const void* d_siblings, const void* d_positions, const void* d_depths,
+                                                       size_t stride_depth, size_t k, const void* d_tree_ids, size_t n_trees, void* d_ok,
+                                                       void* d_old_roots_out, void* d_new_roots_out, void* d_n_hashed, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

@@ -15,6 +15,7 @@
 #include "blake2b.hpp"
 #include "ctx.hpp"
 #include "forest_append.h"
+#include "forest_consistency.h"
 #include "forest_frontier.h"
 #include "forest_witness.h"
 #include "forest_journal.h"
@@ -1782,6 +1783,152 @@ int p252_merkle2_forest_frontier_extract_device_into(p252_ctx* ctx, const void* 
                                                      void* d_roots, void* d_n_bad, void* hip_stream) {
     return forest_frontier_extract_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest,
                                           max_leaves, d_counts, d_frontier, d_roots, d_n_bad, hip_stream);
+}
+
+// ---- consistency proofs of a ragged forest (forest_consistency.hip): that a tree of m leaves is the tree it was at n <= m leaves with
+// leaves appended.  The extraction takes the forest's index and the proof records in the scratch pair of the calling stream, as the
+// openings call does; the verification the old chain's openings, both recomputed roots, the sort's order and counters ----
+// every output of a call against every input and against the outputs before it
+static int refuse_overlaps(p252_ctx* ctx, const std::string& who, const ByteRange* in, size_t n_in, const ByteRange* out, size_t n_out) {
+    for (size_t a = 0; a < n_out; ++a) {
+        const ByteRange* hit = nullptr;
+        for (size_t i = 0; i < n_in && !hit; ++i)
+            if (ranges_overlap(out[a], in[i])) hit = &in[i];
+        for (size_t b = 0; b < a && !hit; ++b)
+            if (ranges_overlap(out[a], out[b])) hit = &out[b];
+        if (hit) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + out[a].name + " overlaps " + hit->name);
+    }
+    return P252_OK;
+}
+
+static int forest_ragged_consistency_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                            size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                            const void* d_old_counts, size_t k, void* d_new_counts_out, void* d_leaves_out, void* d_siblings,
+                                            void* d_positions, void* d_depths, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (k == 0) return P252_OK;
+    const std::string who = "merkle_forest_ragged_consistency";
+    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves, n_trees and max_leaves must be > 0");
+    const size_t depth = forest_ragged_depth(max_leaves, arity);
+    if (!d_leaves || !d_offsets || !d_tree_ids || !d_old_counts || !d_new_counts_out || !d_leaves_out || !d_depths ||
+        (depth && (!d_levels || !d_siblings || !d_positions)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_siblings))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_old_counts, 8) || misaligned_to(d_new_counts_out, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets, d_old_counts and d_new_counts_out must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids and d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    if (k > SIZE_MAX / 128 / (depth ? depth : 1)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const size_t levels_forest = n_leaves / (arity - 1) + n_trees * depth;
+    const ByteRange in[] = {{d_leaves, n_leaves * 32, "d_leaves"},
+                            {d_offsets, (n_trees + 1) * 8, "d_offsets"},
+                            {d_levels, levels_forest * 32, "d_levels"},
+                            {d_tree_ids, k * 4, "d_tree_ids"},
+                            {d_old_counts, k * 8, "d_old_counts"}};
+    const ByteRange out[] = {{d_new_counts_out, k * 8, "d_new_counts_out"},
+                             {d_leaves_out, k * 32, "d_leaves_out"},
+                             {d_siblings, k * depth * (arity - 1) * 32, "d_siblings"},
+                             {d_positions, k * depth, "d_positions"},
+                             {d_depths, k, "d_depths"},
+                             {d_n_bad, 4, "d_n_bad"}};
+    if (int rc = refuse_overlaps(ctx, who, in, sizeof in / sizeof *in, out, sizeof out / sizeof *out)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t index_bytes = forest_ragged_index_bytes(n_trees);
+    return with_stream_scratch(ctx, who, st, index_bytes + forest_openings_record_bytes(k), 0, [&](p252_ctx::LevelSet& set) {
+        char* meta = static_cast<char*>(set.buf[0]);
+        const uint64_t *ntree = nullptr, *lo = nullptr;
+        const hipError_t e = launch_forest_ragged_index(arity, d_offsets, n_trees, n_leaves, max_leaves, meta, &ntree, &lo, st);
+        if (e != hipSuccess) return e;
+        return launch_forest_consistency_extract(arity, d_leaves, d_levels, d_offsets, ntree, lo, n_trees, d_tree_ids, d_old_counts, k,
+                                                 (unsigned)depth, meta + index_bytes, d_new_counts_out, d_leaves_out, d_siblings, d_positions,
+                                                 d_depths, d_n_bad, st);
+    });
+}
+
+static int forest_consistency_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_old_counts,
+                                            const void* d_old_roots, const void* d_new_counts, const void* d_new_roots, const void* d_leaves_in,
+                                            const void* d_siblings, const void* d_positions, const void* d_depths, size_t stride_depth, size_t k,
+                                            const void* d_tree_ids, size_t n_trees, void* d_ok, void* d_old_roots_out, void* d_new_roots_out,
+                                            void* d_n_hashed, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (k == 0) return P252_OK;
+    const std::string who = "merkle_forest_consistency_verify";
+    if (int rc = path_ragged_check(ctx, who.c_str(), tag, d_leaves_in, d_siblings, d_positions, d_depths, stride_depth, k)) return rc;
+    const size_t n_claims = d_tree_ids ? n_trees : k;  // (a forest of no tree has no claim to name: all of its proofs are refused)
+    if (!d_ok || (n_claims && (!d_old_counts || !d_old_roots || !d_new_counts || !d_new_roots)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_old_roots) || misaligned(d_new_roots) || misaligned(d_old_roots_out) || misaligned(d_new_roots_out))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_old_counts, 8) || misaligned_to(d_new_counts, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_old_counts, d_new_counts and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids must be 4-byte aligned");
+    // the claims, and the work area (two openings, two roots and the order per proof), inside size_t
+    if (n_claims > SIZE_MAX / 64 || k > SIZE_MAX / 512 / (stride_depth ? stride_depth : 1))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const ByteRange in[] = {{d_old_counts, n_claims * 8, "d_old_counts"},
+                            {d_old_roots, n_claims * 32, "d_old_roots"},
+                            {d_new_counts, n_claims * 8, "d_new_counts"},
+                            {d_new_roots, n_claims * 32, "d_new_roots"},
+                            {d_leaves_in, k * 32, "d_leaves_in"},
+                            {d_siblings, k * stride_depth * (arity - 1) * 32, "d_siblings"},
+                            {d_positions, k * stride_depth, "d_positions"},
+                            {d_depths, k, "d_depths"},
+                            {d_tree_ids, k * 4, "d_tree_ids"}};
+    const ByteRange out[] = {{d_ok, k, "d_ok"},
+                             {d_old_roots_out, k * 32, "d_old_roots_out"},
+                             {d_new_roots_out, k * 32, "d_new_roots_out"},
+                             {d_n_hashed, 8, "d_n_hashed"}};
+    if (int rc = refuse_overlaps(ctx, who, in, sizeof in / sizeof *in, out, sizeof out / sizeof *out)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const bool sort = ragged_sort_enabled();  // P252_RAGGED_SORT=0: identity order
+    return with_stream_scratch(ctx, who, st, forest_consistency_work(arity, k, (unsigned)stride_depth).bytes, forest_openings_hist_bytes(),
+                               [&](p252_ctx::LevelSet& set) {
+                                   return launch_forest_consistency_verify(arity, ctx->d_tab, tag_arg(tag), d_old_counts, d_old_roots, d_new_counts,
+                                                                           d_new_roots, d_leaves_in, d_siblings, d_positions, d_depths,
+                                                                           (unsigned)stride_depth, k, d_tree_ids, n_trees, d_ok, d_old_roots_out,
+                                                                           d_new_roots_out, d_n_hashed, set.buf[0], set.buf[1], sort, st);
+                               });
+}
+
+int p252_merkle4_forest_ragged_consistency_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                       size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                       const void* d_old_counts, size_t k, void* d_new_counts_out, void* d_leaves_out,
+                                                       void* d_siblings, void* d_positions, void* d_depths, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_consistency_device(ctx, 4, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
+                                            d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_consistency_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                       size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                       const void* d_old_counts, size_t k, void* d_new_counts_out, void* d_leaves_out,
+                                                       void* d_siblings, void* d_positions, void* d_depths, void* d_n_bad, void* hip_stream) {
+    return forest_ragged_consistency_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
+                                            d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad, hip_stream);
+}
+
+int p252_merkle4_forest_consistency_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_old_counts, const void* d_old_roots,
+                                                       const void* d_new_counts, const void* d_new_roots, const void* d_leaves_in,
+                                                       const void* d_siblings, const void* d_positions, const void* d_depths,
+                                                       size_t stride_depth, size_t k, const void* d_tree_ids, size_t n_trees, void* d_ok,
+                                                       void* d_old_roots_out, void* d_new_roots_out, void* d_n_hashed, void* hip_stream) {
+    return forest_consistency_verify_device(ctx, 4, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves_in, d_siblings, d_positions,
+                                            d_depths, stride_depth, k, d_tree_ids, n_trees, d_ok, d_old_roots_out, d_new_roots_out, d_n_hashed,
+                                            hip_stream);
+}
+
+int p252_merkle2_forest_consistency_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_old_counts, const void* d_old_roots,
+                                                       const void* d_new_counts, const void* d_new_roots, const void* d_leaves_in,
+                                                       const void* d_siblings, const void* d_positions, const void* d_depths,
+                                                       size_t stride_depth, size_t k, const void* d_tree_ids, size_t n_trees, void* d_ok,
+                                                       void* d_old_roots_out, void* d_new_roots_out, void* d_n_hashed, void* hip_stream) {
+    return forest_consistency_verify_device(ctx, 2, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves_in, d_siblings, d_positions,
+                                            d_depths, stride_depth, k, d_tree_ids, n_trees, d_ok, d_old_roots_out, d_new_roots_out, d_n_hashed,
+                                            hip_stream);
 }
 
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----

@@ -31,6 +31,15 @@ hipError_t launch_forest_openings(unsigned arity, const void* leaves, const void
                                   unsigned stride_depth, void* records, void* leaves_out, void* siblings, void* positions, void* depths,
                                   void* n_bad, hipStream_t st);
 
+// the second half of that extraction alone, for a caller that writes the records itself (forest_consistency.hip): records[i] =
+// {leaf start of the tree, n_t (0: nothing to open, all of opening i is written as zero), LO[t], leaf id} as k_fo_record lays them out
+hipError_t launch_forest_opening_pieces(unsigned arity, const void* leaves, const void* levels, const void* records, size_t k,
+                                        unsigned stride_depth, void* leaves_out, void* siblings, void* positions, hipStream_t st);
+
+// the depth sort alone: order[0 .. k) = the openings deepest first, those with depths[i] > stride_depth last; order =
+// forest_openings_order_bytes(k) and hist = forest_openings_hist_bytes() of scratch
+hipError_t launch_forest_depth_sort(const void* depths, size_t k, unsigned stride_depth, void* order, void* hist, hipStream_t st);
+
 // roots[i] = the re-hash of the first depths[i] levels of opening i; depths[i] > stride_depth: a zero root, counted in *n_bad.
 // order / hist: the depth sort's scratch, or null for the identity order.
 hipError_t launch_path_ragged(unsigned arity, const int32_t* tab, const TagArg& tag, const void* leaves, const void* siblings,

@@ -221,6 +221,7 @@ __global__ void __launch_bounds__(FO_BLOCK) k_compare_roots_gather(const uint4* 
 template <unsigned ARITY>
 static hipError_t launch_pieces(const void* leaves, const void* levels, const void* records, size_t k, unsigned D, void* leaves_out,
                                 void* siblings, void* positions, hipStream_t st) {
+    if (k == 0) return hipSuccess;
     const size_t lanes = D ? k * D * 2 * (ARITY - 1) : 2 * k;
     const dim3 grid((unsigned)((lanes + FO_BLOCK - 1) / FO_BLOCK));
     const unsigned long long inv_D = fast_div_reciprocal(D);
@@ -246,8 +247,26 @@ hipError_t launch_forest_openings(unsigned arity, const void* leaves, const void
                        static_cast<uint8_t*>(depths), static_cast<unsigned*>(n_bad));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_forest_opening_pieces(arity, leaves, levels, records, k, stride_depth, leaves_out, siblings, positions, st);
+}
+
+hipError_t launch_forest_opening_pieces(unsigned arity, const void* leaves, const void* levels, const void* records, size_t k,
+                                        unsigned stride_depth, void* leaves_out, void* siblings, void* positions, hipStream_t st) {
     return arity == 4 ? launch_pieces<4>(leaves, levels, records, k, stride_depth, leaves_out, siblings, positions, st)
                       : launch_pieces<2>(leaves, levels, records, k, stride_depth, leaves_out, siblings, positions, st);
+}
+
+hipError_t launch_forest_depth_sort(const void* depths, size_t k, unsigned stride_depth, void* order, void* hist, hipStream_t st) {
+    if (k == 0) return hipSuccess;
+    const uint8_t* dp = static_cast<const uint8_t*>(depths);
+    unsigned long long* h = static_cast<unsigned long long*>(hist);
+    const unsigned tiles = (unsigned)((k + FO_TILE - 1) / FO_TILE);
+    const hipError_t e = hipMemsetAsync(hist, 0, forest_openings_hist_bytes(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fo_depth_hist, dim3(tiles), dim3(FO_BLOCK), 0, st, dp, k, stride_depth, h);
+    hipLaunchKernelGGL(k_fo_depth_scan, dim3(1), dim3(64), 0, st, h);
+    hipLaunchKernelGGL(k_fo_depth_scatter, dim3(tiles), dim3(FO_BLOCK), 0, st, dp, k, stride_depth, h, static_cast<uint64_t*>(order));
+    return hipGetLastError();
 }
 
 hipError_t launch_path_ragged(unsigned arity, const int32_t* tab, const TagArg& tag, const void* leaves, const void* siblings,
@@ -257,14 +276,7 @@ hipError_t launch_path_ragged(unsigned arity, const int32_t* tab, const TagArg& 
     const uint8_t* dp = static_cast<const uint8_t*>(depths);
     const uint64_t* ord = nullptr;
     if (order && hist) {
-        unsigned long long* h = static_cast<unsigned long long*>(hist);
-        const unsigned tiles = (unsigned)((k + FO_TILE - 1) / FO_TILE);
-        hipError_t e = hipMemsetAsync(hist, 0, forest_openings_hist_bytes(), st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_fo_depth_hist, dim3(tiles), dim3(FO_BLOCK), 0, st, dp, k, stride_depth, h);
-        hipLaunchKernelGGL(k_fo_depth_scan, dim3(1), dim3(64), 0, st, h);
-        hipLaunchKernelGGL(k_fo_depth_scatter, dim3(tiles), dim3(FO_BLOCK), 0, st, dp, k, stride_depth, h, static_cast<uint64_t*>(order));
-        e = hipGetLastError();
+        const hipError_t e = launch_forest_depth_sort(depths, k, stride_depth, order, hist, st);
         if (e != hipSuccess) return e;
         ord = static_cast<const uint64_t*>(order);
     }

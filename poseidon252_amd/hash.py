@@ -961,6 +961,79 @@ class Context:
             _dev_ptr(self, f, "d_counts", d_counts, n_trees * 8, elem=8), _dev_ptr(self, f, "d_frontier", d_frontier, n_trees * stride * 32),
             _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
+    # ---- consistency proofs: a grown tree extends its old root (p252_merkle{4,2}_forest_ragged_consistency_device_into,
+    # _forest_consistency_verify_device_into; csrc/forest_consistency.hip) ----
+    def merkle4_forest_ragged_consistency_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
+                                                 d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad=None):
+        """k consistency proofs out of a forest merkle_forest_ragged_device built with d_levels
+        (p252_merkle4_forest_ragged_consistency_device_into; no hashing): proof i shows that tree d_tree_ids[i] (int32/uint32), now of
+        n_t leaves, is the tree it was at d_old_counts[i] (int64/uint64) leaves with leaves appended.  It is the opening of leaf index
+        n of the tree, in the layout merkle_forest_ragged_openings_device writes at D = depth(max_leaves): d_leaves_out (k, 4),
+        d_siblings (k, D, 3, 4), d_positions (k, D) uint8, d_depths (k,) uint8; d_new_counts_out (k,) receives n_t.  n == n_t: all
+        zero with the depth of n_t.  A tree id out of range, a bad tree, n == 0 or n > n_t: all zero, depth 0xFF, new count 0, counted
+        in d_n_bad (a zeroed device int32/uint32, optional).  The siblings and positions may be None when D == 0."""
+        self._forest_ragged_consistency_device("merkle4_forest_ragged_consistency_device", _ARITIES[4], d_leaves, d_offsets, n_trees, max_leaves,
+                                               d_levels, d_tree_ids, d_old_counts, k, d_new_counts_out, d_leaves_out, d_siblings, d_positions,
+                                               d_depths, d_n_bad)
+
+    def merkle2_forest_ragged_consistency_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
+                                                 d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad=None):
+        """the same for arity 2 (d_siblings (k, D, 1, 4))"""
+        self._forest_ragged_consistency_device("merkle2_forest_ragged_consistency_device", _ARITIES[2], d_leaves, d_offsets, n_trees, max_leaves,
+                                               d_levels, d_tree_ids, d_old_counts, k, d_new_counts_out, d_leaves_out, d_siblings, d_positions,
+                                               d_depths, d_n_bad)
+
+    def _forest_ragged_consistency_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
+                                          d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad):
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        self._check(a.fn("forest_ragged_consistency_device_into")(
+            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_old_counts", d_old_counts, k * 8, elem=8), k,
+            _dev_ptr(self, f, "d_new_counts_out", d_new_counts_out, k * 8, elem=8), _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32),
+            _dev_ptr(self, f, "d_siblings", d_siblings, k * depth * a.per * 32, null_ok=depth == 0),
+            _dev_ptr(self, f, "d_positions", d_positions, k * depth, elem=1, null_ok=depth == 0),
+            _dev_ptr(self, f, "d_depths", d_depths, k, elem=1), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
+    def merkle4_forest_consistency_verify_device(self, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
+                                                 d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids=None, n_trees=0,
+                                                 d_old_roots_out=None, d_new_roots_out=None, d_n_hashed=None):
+        """k consistency proofs checked against their claims (p252_merkle4_forest_consistency_verify_device_into): d_ok[i] (uint8) = 1
+        iff the opening i (the layout above, at stride_depth rows) re-hashes to the new root and its left siblings alone to the old
+        root, with its slots the digits of the old count.  Without d_tree_ids claim i is element i of d_old_counts, d_old_roots,
+        d_new_counts, d_new_roots (k entries each); with d_tree_ids (int32/uint32) they hold n_trees entries and claim i is element
+        d_tree_ids[i] — so the counts and roots of a ForestFrontier are the old claims as they stand.  d_old_roots_out /
+        d_new_roots_out (k, 4; optional) receive the recomputed roots, d_n_hashed (a zeroed device int64/uint64, optional) grows by
+        the digests computed.  Asynchronous on the current stream."""
+        self._forest_consistency_verify_device("merkle4_forest_consistency_verify_device", _ARITIES[4], tag, d_old_counts, d_old_roots, d_new_counts,
+                                               d_new_roots, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids, n_trees,
+                                               d_old_roots_out, d_new_roots_out, d_n_hashed)
+
+    def merkle2_forest_consistency_verify_device(self, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
+                                                 d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids=None, n_trees=0,
+                                                 d_old_roots_out=None, d_new_roots_out=None, d_n_hashed=None):
+        """the same for arity 2 (pass the Merkle2 tag)"""
+        self._forest_consistency_verify_device("merkle2_forest_consistency_verify_device", _ARITIES[2], tag, d_old_counts, d_old_roots, d_new_counts,
+                                               d_new_roots, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids, n_trees,
+                                               d_old_roots_out, d_new_roots_out, d_n_hashed)
+
+    def _forest_consistency_verify_device(self, f, a, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
+                                          d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids, n_trees, d_old_roots_out, d_new_roots_out,
+                                          d_n_hashed):
+        leaves, sib, pos, dep = self._ragged_opening_ptrs(f, a, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k)
+        claims = n_trees if d_tree_ids is not None else k
+        self._check(a.fn("forest_consistency_verify_device_into")(
+            self._h, _tag(tag), _dev_ptr(self, f, "d_old_counts", d_old_counts, claims * 8, elem=8, null_ok=claims == 0),
+            _dev_ptr(self, f, "d_old_roots", d_old_roots, claims * 32, null_ok=claims == 0),
+            _dev_ptr(self, f, "d_new_counts", d_new_counts, claims * 8, elem=8, null_ok=claims == 0),
+            _dev_ptr(self, f, "d_new_roots", d_new_roots, claims * 32, null_ok=claims == 0), leaves, sib, pos, dep, stride_depth, k,
+            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4, null_ok=True), n_trees, _dev_ptr(self, f, "d_ok", d_ok, k, elem=1),
+            _dev_ptr(self, f, "d_old_roots_out", d_old_roots_out, k * 32, null_ok=True),
+            _dev_ptr(self, f, "d_new_roots_out", d_new_roots_out, k * 32, null_ok=True),
+            _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
+
     # ---- the shared proof across a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_*; csrc/forest_multiproof.hip) ----
     def merkle4_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
         """upper bound, in scalars, of the shared proof of k pairs of a ragged forest (p252_merkle4_forest_ragged_multiproof_bound)"""

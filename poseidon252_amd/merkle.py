@@ -411,6 +411,56 @@ def forest_frontier_extract(ctx, d_leaves, d_offsets, n_trees, max_leaves_forest
     return n_bad
 
 
+def forest_ragged_consistency(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, old_counts, arity=4):
+    """Consistency proofs out of a built ragged forest, with no digest (Context.merkle{4,2}_forest_ragged_consistency_device): proof i
+    shows that tree tree_ids[i], as it is now, is the tree it was at old_counts[i] leaves with leaves appended (sequences, numpy or
+    torch; a (n_trees,) counts tensor of a ForestFrontier with tree_ids = arange serves as it stands).  Returns (d_new_counts (k,)
+    int64, (d_leaves_out (k, 4), d_siblings (k, D, arity - 1, 4), d_positions (k, D) uint8, d_depths (k,) uint8, D), d_n_bad (1,)
+    int32), all on the device: the proof tuple is what forest_consistency_verify takes.  No synchronisation."""
+    import torch
+    a = _arity("forest_ragged_consistency", arity)
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    ids = lambda x, dtype: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.int64))).to(device=dev, dtype=dtype).contiguous()  # noqa: E731
+    t, n = ids(tree_ids, torch.int32), ids(old_counts, torch.int64)
+    k = t.numel()
+    if n.numel() != k:
+        raise ValueError("forest_ragged_consistency: %d tree ids, %d old counts" % (k, n.numel()))
+    D = a.depth(max_leaves)
+    new_counts = torch.zeros(k, dtype=torch.int64, device=dev)
+    lv = torch.zeros((k, 4), dtype=torch.int64, device=dev)
+    sib = torch.zeros((k, D, a.per, 4), dtype=torch.int64, device=dev)
+    pos = torch.zeros((k, D), dtype=torch.uint8, device=dev)
+    dep = torch.full((k,), 0xFF, dtype=torch.uint8, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    call = ctx.merkle4_forest_ragged_consistency_device if arity == 4 else ctx.merkle2_forest_ragged_consistency_device
+    if k:
+        call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if D else None, t, n, k, new_counts, lv, sib if D else None, pos if D else None, dep, n_bad)
+    return new_counts, (lv, sib, pos, dep, D), n_bad
+
+
+def forest_consistency_verify(ctx, d_old_counts, d_old_roots, d_new_counts, d_new_roots, proof, d_tree_ids=None, tag=None, arity=4):
+    """Consistency proofs checked against (old count, old root, new count, new root) claims
+    (Context.merkle{4,2}_forest_consistency_verify_device): proof = (d_leaves, d_siblings, d_positions, d_depths, D) as
+    forest_ragged_consistency returns it; claim i is element i of the four claim tensors, or element d_tree_ids[i] (int32) when given —
+    then they hold one entry per tree, as the counts and roots of a ForestFrontier do.  Returns (d_ok (k,) uint8, d_old_roots_out (k, 4),
+    d_new_roots_out (k, 4), d_n_hashed (1,) int64) on the device: the verdicts, the recomputed roots, the digests computed.  No
+    synchronisation."""
+    import torch
+    a = _arity("forest_consistency_verify", arity)
+    ctx = ctx or Context.default()
+    lv, sib, pos, dep, D = proof
+    k, dev = dep.numel(), dep.device
+    ok = torch.zeros(k, dtype=torch.uint8, device=dev)
+    old_out, new_out = torch.zeros((k, 4), dtype=torch.int64, device=dev), torch.zeros((k, 4), dtype=torch.int64, device=dev)
+    n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
+    call = ctx.merkle4_forest_consistency_verify_device if arity == 4 else ctx.merkle2_forest_consistency_verify_device
+    if k:
+        call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_old_counts, d_old_roots, d_new_counts, d_new_roots, lv, sib if D else None,
+             pos if D else None, dep, D, k, ok, d_tree_ids, _n_scalars(d_old_roots) if d_tree_ids is not None else 0, old_out, new_out, n_hashed)
+    return ok, old_out, new_out, n_hashed
+
+
 def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
     as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are
