@@ -1,5 +1,6 @@
-// ctx.hpp — the context object and the few host-side helpers shared by api.cpp (the C ABI), host_io.cpp (its host-buffer entry
-// points) and comm.cpp (the RCCL communicator of the multi-GPU entry points).  Internal: nothing here is part of the ABI.
+// ctx.hpp — the context object and the few host-side helpers shared by api.cpp and api_forest.cpp (the C ABI; the latter its
+// ragged-forest family), host_io.cpp (its host-buffer entry points) and comm.cpp (the RCCL communicator of the multi-GPU entry
+// points).  Internal: nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,7 +26,7 @@ struct p252_ctx {
     // stream, so ONE pair per context would be shared by builds queued on different streams (round 4: silent wrong roots).  Each
     // caller stream therefore owns a pair (up to MAX_LEVEL_SETS); a further stream takes over the least recently used pair after
     // waiting on the event recorded behind that pair's last build — builds on different streams overlap, none ever shares scratch.
-    // Every call that uses a pair goes through api.cpp's with_stream_scratch, which records that event on every way out.
+    // Every call that uses a pair goes through api_util.hpp's with_stream_scratch, which records that event on every way out.
     struct LevelSet {
         hipStream_t st = nullptr;
         void* buf[2] = {nullptr, nullptr};

@@ -1,12 +1,14 @@
 // refusal_table.hpp — the harness of the refusal programs (api_refusals.cpp, journal_refusals.cpp, append_refusals.cpp,
-// resize_refusals.cpp, forest_multiproof_refusals.cpp): each prints the argument refusals of its entry points as a table,
+// resize_refusals.cpp, select_refusals.cpp, forest_multiproof_refusals.cpp and the frontier_, witness_ and
+// consistency_refusal_table.cpp): each prints the argument refusals of its entry points as a table,
 //   symbol <TAB> case <TAB> rc <TAB> p252_last_error
 // Every refusal happens before an entry point binds its device, so ONE context that never saw a device (device = -1) reaches all of
 // them on a machine with or without a GPU.  The control row of an entry point — an all-good argument set — must get past validation
 // and fail at hipSetDevice(ctx->device) with P252_ERR_HIP; every other row varies the control one way.  No pointer is dereferenced:
 // no row reaches a device.  The case tables and the adapters that call the library stay in the programs; two styles of table share
 // this file: the one of api_refusals.cpp (Arg / Combo / Entry: arguments by kind, varied one at a time) and the one of
-// append_refusals.cpp (a struct of named arguments, CaseOf / BufOf: each case a function that changes the control).
+// append_refusals.cpp and select_refusals.cpp (a struct of named arguments, CaseOf / BufOf: each case a function that changes the
+// control).
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -168,7 +170,7 @@ inline Arg p8(const char* name) { return {name, P8, 0, {}}; }
 inline Arg p4(const char* name) { return {name, P4, 0, {}}; }
 inline Arg p1(const char* name) { return {name, P1, 0, {}}; }
 
-// limits of the library's size checks (api.cpp): forest_shape_check, the `k > SIZE_MAX / 128 / depth` family, the ragged depths
+// limits of the library's size checks (api_forest.cpp): forest_shape_check, the `k > SIZE_MAX / 128 / depth` family, the ragged depths
 inline const uint64_t FOREST_MAX_DEPTH = 64;  // FOREST_RAGGED_MAX_DEPTH = FOREST_OPENINGS_MAX_DEPTH
 inline const uint64_t TREES_MAX = MAXZ / 8 / (FOREST_MAX_DEPTH + 2);
 

@@ -141,7 +141,7 @@ def test_own_translation_unit_and_nothing_is_copied():
         assert re.search(r"\b%s\(" % fn, code), fn
         assert not re.search(r"\b%s\s*\([^;{]*\)\s*\{" % fn, code), fn
     assert not re.search(r"\bk_f[ur]_\w+\s*[(<]", code)  # no kernel of the update's or the build's is launched or copied
-    assert "launch_forest_ragged_index" in open(os.path.join(CSRC, "api.cpp")).read()
+    assert "launch_forest_ragged_index" in open(os.path.join(CSRC, "api_forest.cpp")).read()
     assert "asm" not in src  # plain C++ and vector stores only
     for other in ("kernels.hip", "kernels.h", "forest_update.hip", "forest_update.h"):
         assert "forest_journal" not in open(os.path.join(CSRC, other)).read(), other

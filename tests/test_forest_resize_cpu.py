@@ -182,7 +182,7 @@ def test_kernels_meet_resource_targets_and_the_unit_is_one():
     assert len(re.findall(r"^hipError_t launch_\w+\(", src, flags=re.M)) == 1
     for word in ("hades_permute", "node_digest_coop", "asm"):
         assert word not in src, word
-    api = open(os.path.join(CSRC, "api.cpp")).read()
+    api = open(os.path.join(CSRC, "api.cpp")).read() + open(os.path.join(CSRC, "api_forest.cpp")).read()  # the host ABI, both files
     assert api.count("launch_forest_append(") == 1 and api.count("forest_append_plan(") == 1  # both entry points, one path
 
 

@@ -1,6 +1,7 @@
 """Trees of built forests gathered into a new forest (p252_merkle{4,2}_forest_ragged_select_device_into; the select of
 csrc/forest_ragged.hip) — what can be checked without a GPU: the two entry points are declared, exported and mirrored in the Rust FFI
-under ABI 9, under a name the refusal table of the `_device(` symbols does not catch; the select's kernels compile for gfx950 within
+under ABI 9, under a name the refusal table of the `_device(` symbols does not catch; the host refusals as a table of their own; the
+select's kernels compile for gfx950 within
 their resource targets and none of them hashes; the Python methods validate every buffer before the library is reached; the model
 the GPU tests compare the call with; the C++ mirror compiles; the bench tool parses."""
 import os
@@ -13,7 +14,7 @@ import torch
 import forestselect as FS
 from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: F401
 from helpers.kernel_resources import kernel_resources
-from helpers.percall import bench_tool_parses, build_cpp_mirror, check_abi_symbols
+from helpers.percall import ERR_HIP, assert_rows_equal_golden, bench_tool_parses, build_cpp_mirror, check_abi_symbols, refusal_table
 from testsupport import treeshape as TS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,6 +30,78 @@ def test_two_symbols_declared_exported_and_in_sys_rs():
     declared = set(re.findall(r"\b(p252_[a-z0-9_]+_device)\s*\(", header))
     table = {line.split("\t")[0] for line in open(os.path.join(ROOT, "tests", "golden", "api_refusals.txt")).read().splitlines()}
     assert declared == table and not any("select" in s for s in declared)
+
+
+# ---- the host refusals (the library's own: the table of the `_device(` symbols does not see a `_device_into` name) ----
+@pytest.fixture(scope="module")
+def table(tmp_path_factory):
+    return refusal_table("select_refusals", tmp_path_factory.mktemp("select_refusals"))
+
+
+def test_every_refusal_row_equals_the_recorded_one(table):
+    assert_rows_equal_golden(table, "select_refusals")
+
+
+SELECT_IN = ("d_leaves_a", "d_offsets_a", "d_levels_a", "d_roots_a", "d_leaves_b", "d_offsets_b", "d_levels_b", "d_roots_b", "d_pick")
+SELECT_OUT = ("d_leaves_new", "d_offsets_new", "d_levels_new", "d_roots_new", "d_n_bad")
+
+
+def test_refusal_table_has_a_control_row_and_every_host_refusal(table):
+    for arity in (4, 2):
+        by = {r[1]: r[2:] for r in table if r[0] == "p252_merkle%d_forest_ragged_select_device_into" % arity}
+        assert by["control"] == (ERR_HIP, "hipSetDevice(ctx->device)")  # past validation: without this the other rows prove nothing
+        refused = lambda case, word: by[case][0] == -3 and word in by[case][1]  # noqa: E731
+        accepted = lambda case: by[case] == by["control"]  # noqa: E731
+        assert by["ctx=NULL"][0] == -3 and refused("n_trees_a=0", "n_trees_a must be > 0")
+        assert by["n_pick=0"] == (0, "") and by["n_pick=0,n_leaves_a=0,buffers=NULL"] == (0, "")
+        # B absent: accepted whatever its pointers and sizes say
+        for case in ("n_trees_b=0,B=NULL", "n_trees_b=0", "n_trees_b=0,B misaligned", "n_trees_b=0,B on the outputs",
+                     "n_trees_b=0,n_leaves_b=0,max_leaves_b=0", "n_trees_b=0,max_leaves_b=17", "n_trees_b=0,n_pick*min(max_leaves_b,n_leaves_b)>SIZE_MAX/2"):
+            assert accepted(case) or (case.endswith("SIZE_MAX/2") and refused(case, "levels_cap must be >=")), (case, by[case])
+        assert refused("n_leaves_b=0", "n_leaves_b and max_leaves_b must be > 0") and refused("max_leaves_b=0", "n_leaves_b and max_leaves_b must be > 0")
+        assert refused("n_leaves_a=0", "n_leaves_a and max_leaves_a must be > 0") and refused("max_leaves_a=0", "n_leaves_a and max_leaves_a must be > 0")
+        assert refused("leaves_cap=0", "leaves_cap must be > 0")
+        # the levels' cap: one below the bound and at it, under the larger of the two max_leaves
+        for case in ("levels_cap=need-1", "levels_cap=0", "max_leaves_a=17", "max_leaves_a=17,levels_cap=need(17)-1", "max_leaves_b=17,levels_cap=need(17)-1"):
+            assert refused(case, "levels_cap must be >= leaves_cap / (arity - 1) + n_pick * depth(max_leaves)"), case
+        for case in ("levels_cap=need", "levels_cap=need+1", "max_leaves_a=17,levels_cap=need(17)", "max_leaves_b=17,levels_cap=need(17)"):
+            assert accepted(case), case
+        assert accepted("max_leaves_a=1,d_levels_a=NULL") and accepted("max_leaves_b=1,d_levels_b=NULL") and accepted("max_leaves_a=max_leaves_b=1,levels=NULL")
+        assert refused("max_leaves_a=2,d_levels_a=NULL", "NULL buffer of forest A") and refused("max_leaves_a=1,d_levels_new=NULL", "NULL output buffer")
+        for case in ("n_trees_a=SIZE_MAX,n_trees_b=1", "n_trees_a=n_trees_b=SIZE_MAX/2+1", "n_pick*min(max_leaves_a,n_leaves_a)>SIZE_MAX/2",
+                     "n_pick*min(max_leaves_b,n_leaves_b)>SIZE_MAX/2", "levels_cap=SIZE_MAX/64+1", "levels_cap=SIZE_MAX"):
+            assert refused(case, "size overflow"), case
+        assert not refused("n_pick*min(max_leaves_a,n_leaves_a)=SIZE_MAX/2", "size overflow") and not refused("levels_cap=SIZE_MAX/64", "size overflow")
+        # the shape check's edges for each of the three forests: the value at the limit passes it, the one past it does not
+        edges = [c for c in by if re.match(r"(A|B|new):", c)]
+        assert len(edges) == 3 * 7
+        for case in edges:
+            past = case.endswith("+1") or ">SIZE_MAX/2" in case
+            assert refused(case, "size overflow") == past, (case, by[case])
+        for buf in SELECT_IN[:2] + ("d_roots_a",):
+            assert refused(buf + "=NULL", "NULL buffer of forest A"), buf
+        assert refused("d_levels_a=NULL", "NULL buffer of forest A") and refused("d_pick=NULL", "NULL d_pick")
+        for buf in SELECT_IN[4:8]:
+            assert refused(buf + "=NULL", "NULL buffer of forest B"), buf
+        for buf in SELECT_OUT[:4]:
+            assert refused(buf + "=NULL", "NULL output buffer"), buf
+        assert accepted("d_n_bad=NULL")
+        misaligned = [c for c in by if re.fullmatch(r"d_\w+\+\d", c)]
+        assert len(misaligned) == 14 and all(refused(c, "aligned") for c in misaligned)
+        # every output on the last bytes of every input and of every output before it; where the other ends, it is accepted
+        n_in = n_out = 0
+        for x, o in enumerate(SELECT_OUT):
+            for i in SELECT_IN + SELECT_OUT[:x]:
+                assert by["%s=%s+last" % (o, i)] == (-3, "merkle_forest_ragged_select: %s overlaps %s" % (o, i)), (o, i)
+                assert accepted("%s=%s+end" % (o, i)), (o, i)
+                n_in += i in SELECT_IN
+                n_out += i in SELECT_OUT
+        assert (n_in, n_out) == (45, 10)
+        assert len([c for c in by if c.endswith("+last")]) == 55 and len([c for c in by if c.endswith("+end")]) == 55
+        assert refused("d_roots_new=d_pick-16", "d_roots_new overlaps d_pick") and accepted("d_roots_new=d_pick-4*32")
+        assert refused("d_leaves_new=d_leaves_b-leaves_cap*32+16", "d_leaves_new overlaps d_leaves_b") and accepted("d_leaves_new=d_leaves_b-leaves_cap*32")
+        assert refused("d_leaves_new=d_levels_new", "d_levels_new overlaps d_leaves_new")
+        assert refused("levels_cap=need+1,d_roots_new=d_levels_new+need*32", "d_roots_new overlaps d_levels_new") and accepted("d_roots_new=d_levels_new+need*32")
 
 
 # ---- the kernels ----

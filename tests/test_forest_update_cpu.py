@@ -61,7 +61,7 @@ def test_own_translation_unit_and_the_permutation_is_included():
     assert "forest_update" not in open(os.path.join(CSRC, "kernels.hip")).read()
     assert "forest_update" not in open(os.path.join(CSRC, "kernels.h")).read()
     # the forest's index comes from the build's own kernels, not from a copy of them
-    assert not re.search(r"\bk_fr_\w+\s*[(<]", src) and "launch_forest_ragged_index" in open(os.path.join(CSRC, "api.cpp")).read()
+    assert not re.search(r"\bk_fr_\w+\s*[(<]", src) and "launch_forest_ragged_index" in open(os.path.join(CSRC, "api_forest.cpp")).read()
 
 
 @pytest.mark.parametrize("arity", [4, 2])

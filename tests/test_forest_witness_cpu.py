@@ -243,7 +243,7 @@ def test_the_unit_hashes_nothing_and_the_append_calls_it_once():
     last = body.rindex("launch_forest_witness_refresh")
     assert body.rindex("launch_multiproof_digest_list") < last < body.index("k_ff_finish")
     assert "k_fw_" not in unit
-    api = open(os.path.join(CSRC, "api.cpp")).read()
+    api = open(os.path.join(CSRC, "api.cpp")).read() + open(os.path.join(CSRC, "api_forest.cpp")).read()  # the host ABI, both files
     assert api.count("launch_forest_frontier_append(") == 2 and "launch_forest_witness_refresh" not in api
 
 

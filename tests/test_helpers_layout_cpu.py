@@ -48,7 +48,7 @@ def test_refusal_harness_is_in_the_header_only():
     holders = {what: sorted(n for n in os.listdir(CPP) if what in open(os.path.join(CPP, n)).read()) for what in (row_format, kinds)}
     assert holders == {row_format: ["refusal_table.hpp"], kinds: ["refusal_table.hpp"]}
     programs = sorted(n for n in os.listdir(CPP) if n.endswith("_refusals.cpp"))
-    assert len(programs) == 5
+    assert len(programs) == 6
     for n in programs:
         assert '#include "refusal_table.hpp"' in open(os.path.join(CPP, n)).read(), n
 

@@ -1,4 +1,4 @@
-"""Every family of `_device` calls that works in the context's per-stream scratch pair (csrc/api.cpp with_stream_scratch), mixed on
+"""Every family of `_device` calls that works in the context's per-stream scratch pair (csrc/api_util.hpp with_stream_scratch, behind the entry points of csrc/api.cpp and csrc/api_forest.cpp), mixed on
 six streams of ONE context: the context keeps four pairs, so the fifth and sixth stream take a pair over behind its event, and with
 the assignment rotated each round every pair is taken over by a family that asks other sizes of it.  Each output must equal that of
 the same call made alone on the default stream."""
