@@ -901,6 +901,81 @@ inline std::vector<BlsScalar> decrypt(const std::vector<BlsScalar>& cipher, cons
     return m;
 }
 
+// ---- messages of DIFFERENT lengths in one call (p252_{encrypt,decrypt}_ragged*): each cipher equals encrypt_batch's at its length.
+// One array of n + 1 MESSAGE offsets serves both sides: message i = messages[offsets[i] .. offsets[i+1]), its cipher the L_i + 1
+// scalars at ciphers[offsets[i] + i ..].  Lengths 1 .. P252_CRYPT_RAGGED_MAX_LEN. ----
+inline std::vector<BlsScalar> encryption_tags(std::size_t max_len, int variant = P252_CRYPT_STREAM) {
+    std::vector<BlsScalar> t(max_len ? max_len : 1);
+    detail::check(p252_encryption_tags(variant, max_len, t[0].data()), nullptr, "encryption_tags");
+    return t;
+}
+namespace detail {
+inline std::size_t ragged_max_len(const std::vector<std::uint64_t>& offsets) {
+    std::size_t longest = 1;
+    for (std::size_t i = 0; i + 1 < offsets.size(); ++i)
+        if (offsets[i + 1] > offsets[i] && offsets[i + 1] - offsets[i] > longest) longest = offsets[i + 1] - offsets[i];
+    return longest;
+}
+}  // namespace detail
+// flat messages + offsets -> the flat ciphers (offsets.back() + n scalars); the library checks every length before it launches
+inline std::vector<BlsScalar> encrypt_ragged(const std::vector<BlsScalar>& messages, const std::vector<std::uint64_t>& offsets,
+                                             const std::vector<BlsScalar>& secrets, const std::vector<BlsScalar>& nonces,
+                                             int variant = P252_CRYPT_STREAM, Context& ctx = Context::default_context()) {
+    const std::size_t n = nonces.size();
+    if (offsets.size() != n + 1 || secrets.size() != 2 * n || (n && offsets.back() > messages.size())) throw std::invalid_argument("encrypt_ragged: sizes");
+    if (!n) return {};
+    const std::size_t max_len = detail::ragged_max_len(offsets);
+    const std::vector<BlsScalar> tags = encryption_tags(max_len, variant);
+    std::vector<BlsScalar> out(offsets.back() + n);
+    detail::check(p252_encrypt_ragged(ctx.get(), variant, tags[0].data(), max_len, messages.empty() ? nullptr : messages[0].data(), offsets.data(),
+                                      secrets[0].data(), nonces[0].data(), out[0].data(), n),
+                  ctx.get(), "encrypt_ragged");
+    return out;
+}
+// flat ciphers + the MESSAGE offsets -> the flat messages; ok[i] == 0 marks a message whose MAC did not verify (content unspecified)
+inline std::vector<BlsScalar> decrypt_ragged(const std::vector<BlsScalar>& ciphers, const std::vector<std::uint64_t>& offsets,
+                                             const std::vector<BlsScalar>& secrets, const std::vector<BlsScalar>& nonces,
+                                             std::vector<std::uint8_t>& ok, int variant = P252_CRYPT_STREAM,
+                                             Context& ctx = Context::default_context()) {
+    const std::size_t n = nonces.size();
+    if (offsets.size() != n + 1 || secrets.size() != 2 * n || (n && offsets.back() + n > ciphers.size())) throw std::invalid_argument("decrypt_ragged: sizes");
+    ok.assign(n, 0);
+    if (!n) return {};
+    const std::size_t max_len = detail::ragged_max_len(offsets);
+    const std::vector<BlsScalar> tags = encryption_tags(max_len, variant);
+    std::vector<BlsScalar> out(offsets.back() ? offsets.back() : 1);
+    detail::check(p252_decrypt_ragged(ctx.get(), variant, tags[0].data(), max_len, ciphers[0].data(), offsets.data(), secrets[0].data(),
+                                      nonces[0].data(), out[0].data(), ok.data(), n),
+                  ctx.get(), "decrypt_ragged");
+    out.resize(offsets.back());
+    return out;
+}
+// the same, throwing DecryptionFailed if any MAC failed — what decrypt is to decrypt_batch
+inline std::vector<BlsScalar> decrypt_ragged_checked(const std::vector<BlsScalar>& ciphers, const std::vector<std::uint64_t>& offsets,
+                                                     const std::vector<BlsScalar>& secrets, const std::vector<BlsScalar>& nonces,
+                                                     int variant = P252_CRYPT_STREAM, Context& ctx = Context::default_context()) {
+    std::vector<std::uint8_t> ok;
+    auto m = decrypt_ragged(ciphers, offsets, secrets, nonces, ok, variant, ctx);
+    for (std::uint8_t f : ok)
+        if (!f) throw DecryptionFailed();
+    return m;
+}
+// device buffers, asynchronous on `stream`: thin checked wrappers of p252_{encrypt,decrypt}_ragged_device (see poseidon252_hip.h)
+inline void encrypt_ragged_device(Context& ctx, int variant, const void* d_tags, std::size_t max_len, const void* d_messages, std::size_t n_scalars,
+                                  const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_ciphers, std::size_t n,
+                                  void* d_n_bad = nullptr, void* stream = nullptr) {
+    detail::check(p252_encrypt_ragged_device_into(ctx.get(), variant, d_tags, max_len, d_messages, n_scalars, d_offsets, d_secrets, d_nonces, d_ciphers, n,
+                                             d_n_bad, stream),
+                  ctx.get(), "encrypt_ragged_device");
+}
+inline void decrypt_ragged_device(Context& ctx, int variant, const void* d_tags, std::size_t max_len, const void* d_ciphers, std::size_t n_scalars,
+                                  const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_messages, void* d_ok, std::size_t n,
+                                  void* d_n_bad = nullptr, void* stream = nullptr) {
+    detail::check(p252_decrypt_ragged_device_into(ctx.get(), variant, d_tags, max_len, d_ciphers, n_scalars, d_offsets, d_secrets, d_nonces, d_messages, d_ok,
+                                             n, d_n_bad, stream),
+                  ctx.get(), "decrypt_ragged_device");
+}
+
 // ---- the canonical byte format: BlsScalar::to_bytes / from_bytes (src/hades/round_constants.rs:66-67) ----
 using ScalarBytes = std::array<std::uint8_t, 32>;  // little-endian bytes of the canonical value
 inline std::vector<ScalarBytes> to_bytes(const std::vector<BlsScalar>& scalars) {

@@ -124,7 +124,9 @@ extern "C" {
  *      openings of marked leaves current, so that such a forest can prove membership without being stored;
  *      + p252_merkle{4,2}_forest_ragged_consistency_device_into, _forest_consistency_verify_device_into (additive, same version;
  *      `_into`: every result goes into buffers the caller owns): the proof that a tree of such a forest is the tree it was at an
- *      older leaf count with leaves appended and nothing before them changed, and its check against the two roots */
+ *      older leaf count with leaves appended and nothing before them changed, and its check against the two roots;
+ *      + p252_encryption_tags, p252_{encrypt,decrypt}_ragged[_device_into] (additive, same version): encryption and decryption of
+ *      messages of different lengths in one call */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -334,6 +336,41 @@ int p252_encrypt_batch_device(p252_ctx* ctx, int variant, const uint64_t tag[4],
                               const void* d_nonces, size_t len, void* d_ciphers, size_t n, void* hip_stream);
 int p252_decrypt_batch_device(p252_ctx* ctx, int variant, const uint64_t tag[4], const void* d_ciphers, const void* d_secrets,
                               const void* d_nonces, size_t len, void* d_messages, void* d_ok, size_t n, void* hip_stream);
+
+/* The same for n messages of DIFFERENT lengths in one call (the reference's encrypt / decrypt take a message of any length).
+ * Layout: ONE array of n + 1 uint64 MESSAGE offsets serves both directions: message i = messages[offsets[i] .. offsets[i+1])
+ * (L_i scalars), its cipher the L_i + 1 scalars at ciphers[offsets[i] + i ..] — the cipher array holds n_scalars + n scalars and
+ * needs no offsets of its own; secrets[n][2], nonces[n], ok[n] bytes as above.  tags: max_len scalars, row L - 1 the tag of a
+ * message of L scalars (p252_encryption_tags fills it; a wrong table gives wrong ciphertexts, as a wrong `tag` does above).
+ * 1 <= max_len <= P252_CRYPT_RAGGED_MAX_LEN: the schedule keeps one counter per length (longer messages stay with the
+ * fixed-length call).  Every message's bytes are those of the fixed-length call at its length.
+ *
+ * `_device_into` (every result goes into buffers the caller owns, as the forest calls of that name): asynchronous on hip_stream, no
+ * host synchronisation, no allocation once the stream's scratch is warm.  n_scalars = the
+ * scalars of the message-side array.  Message i is BAD iff offsets[i+1] <= offsets[i] (empty or decreasing), L_i > max_len, or
+ * offsets[i+1] > n_scalars: it is counted once in *d_n_bad (a uint32 the caller has zeroed; may be NULL), its output region is left
+ * untouched, decrypt sets ok[i] = 0, nothing is read or written through it and its neighbours are unaffected.  Badness depends
+ * on the offsets alone, so a caller can find the bad messages itself.  Where offsets that are not non-decreasing make the regions of
+ * two valid messages overlap, the contents there are unspecified but stay inside the buffers.  Refused with
+ * P252_ERR_INVALID_ARGUMENT: max_len of 0 or above the cap, an unknown variant, a NULL or misaligned buffer (scalars 16 bytes,
+ * offsets 8, d_n_bad 4), a size overflow (n_scalars + n included), an output that overlaps any input — in-place use is not
+ * possible, the two sides are shifted against each other.  n == 0: P252_OK, nothing enqueued.
+ *
+ * Host twins: synchronous; the offsets are checked before anything is launched (an empty message: P252_ERR_INVALID_IO_PATTERN;
+ * decreasing offsets or a length above max_len: P252_ERR_INVALID_ARGUMENT; p252_last_error names the message), and every
+ * library-owned copy of what they were handed is cleared before they return, as p252_{encrypt,decrypt}_batch do. */
+#define P252_CRYPT_RAGGED_MAX_LEN 2048
+int p252_encryption_tags(int variant, size_t max_len, uint64_t* tags_out); /* row L-1 = p252_encryption_tag(variant, L) */
+int p252_encrypt_ragged_device_into(p252_ctx* ctx, int variant, const void* d_tags, size_t max_len, const void* d_messages, size_t n_scalars,
+                               const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_ciphers, size_t n,
+                               void* d_n_bad, void* hip_stream);
+int p252_decrypt_ragged_device_into(p252_ctx* ctx, int variant, const void* d_tags, size_t max_len, const void* d_ciphers, size_t n_scalars,
+                               const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_messages, void* d_ok, size_t n,
+                               void* d_n_bad, void* hip_stream);
+int p252_encrypt_ragged(p252_ctx* ctx, int variant, const uint64_t* tags, size_t max_len, const uint64_t* messages, const uint64_t* offsets,
+                        const uint64_t* secrets, const uint64_t* nonces, uint64_t* ciphers, size_t n);
+int p252_decrypt_ragged(p252_ctx* ctx, int variant, const uint64_t* tags, size_t max_len, const uint64_t* ciphers, const uint64_t* offsets,
+                        const uint64_t* secrets, const uint64_t* nonces, uint64_t* messages, uint8_t* ok, size_t n);
 
 /* Openings of a STORED tree, extracted on the device (no hashing; HBM-bound data movement): d_leaves[n_leaves] and d_levels as
  * p252_merkle4_tree_device filled them (all levels, bottom-up); d_indices = k leaf positions (uint32, device).  Writes, in exactly

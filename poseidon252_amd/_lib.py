@@ -76,6 +76,11 @@ PROTOTYPES = {
     "p252_decrypt_batch": _f(_vp, _int, _u64p, _u64p, _u64p, _u64p, _sz, _u64p, _u8p, _sz),
     "p252_encrypt_batch_device": _f(_vp, _int, _u64p, _vp, _vp, _vp, _sz, _vp, _sz, _vp),
     "p252_decrypt_batch_device": _f(_vp, _int, _u64p, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp),
+    "p252_encryption_tags": _f(_int, _sz, _u64p),
+    "p252_encrypt_ragged_device_into": _f(_vp, _int, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp),
+    "p252_decrypt_ragged_device_into": _f(_vp, _int, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp),
+    "p252_encrypt_ragged": _f(_vp, _int, _u64p, _sz, _u64p, _u64p, _u64p, _u64p, _u64p, _sz),
+    "p252_decrypt_ragged": _f(_vp, _int, _u64p, _sz, _u64p, _u64p, _u64p, _u64p, _u64p, _u8p, _sz),
     "p252_merkle4_depth": _f(_sz, ret=_sz),
     "p252_merkle4_openings_device": _f(_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp),
     "p252_merkle2_depth": _f(_sz, ret=_sz),

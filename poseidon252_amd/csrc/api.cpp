@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -15,6 +16,7 @@
 #include "../../include/poseidon252_hip.h"
 #include "api_util.hpp"
 #include "blake2b.hpp"
+#include "crypt_ragged.h"
 #include "ctx.hpp"
 #include "hades29.hpp"
 #include "kernels.h"
@@ -926,6 +928,54 @@ int p252_decrypt_batch_device(p252_ctx* ctx, int variant, const uint64_t tag[4],
     return crypt_device(ctx, variant, true, tag, d_ciphers, d_secrets, d_nonces, len, d_messages, d_ok, n, hip_stream);
 }
 
+// ---- messages of different lengths in one call (crypt_ragged.hip: the schedule; kernels.hip: k_crypt<*, true>).  The order array
+// and the bucket counters live in the scratch pair of the calling stream.  No call table, hence no prepare_prog and none of its
+// synchronisation: the kernels compute the calls from (variant, length).  in / out: the message and the cipher side. ----
+static int crypt_ragged_device(p252_ctx* ctx, int variant, bool decrypt, const void* d_tags, size_t max_len, const void* d_in, size_t n_scalars,
+                               const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_out, void* d_ok, size_t n,
+                               void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = decrypt ? "decrypt_ragged" : "encrypt_ragged";
+    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": unknown variant");
+    if (max_len == 0 || max_len > P252_CRYPT_RAGGED_MAX_LEN)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_len must be 1 .. P252_CRYPT_RAGGED_MAX_LEN = " + std::to_string(P252_CRYPT_RAGGED_MAX_LEN));
+    if (n == 0) return P252_OK;
+    if (!d_tags || !d_in || !d_offsets || !d_secrets || !d_nonces || !d_out || (decrypt && !d_ok)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_tags) || misaligned(d_in) || misaligned(d_secrets) || misaligned(d_nonces) || misaligned(d_out))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets must be 8-byte aligned");
+    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
+    if (n >= SIZE_MAX / 128 || n_scalars >= SIZE_MAX / 64 || n_scalars + n >= SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const size_t msg_bytes = n_scalars * 32, cph_bytes = (n_scalars + n) * 32;
+    const ByteRange in[] = {{d_tags, max_len * 32, "d_tags"},
+                            {d_in, decrypt ? cph_bytes : msg_bytes, decrypt ? "d_ciphers" : "d_messages"},
+                            {d_offsets, (n + 1) * 8, "d_offsets"},
+                            {d_secrets, n * 64, "d_secrets"},
+                            {d_nonces, n * 32, "d_nonces"}};
+    const ByteRange out[] = {{d_out, decrypt ? msg_bytes : cph_bytes, decrypt ? "d_messages" : "d_ciphers"}, {d_ok, decrypt ? n : 0, "d_ok"}, {d_n_bad, 4, "d_n_bad"}};
+    if (int rc = refuse_overlaps(ctx, who, in, std::size(in), out, std::size(out), true)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    return with_stream_scratch(ctx, who, st, crypt_ragged_order_bytes(n, max_len), crypt_ragged_hist_bytes(), [&](p252_ctx::LevelSet& set) {
+        return launch_crypt_ragged(decrypt, variant, ctx->d_tab, d_tags, max_len, d_in, (uint64_t)n_scalars, d_offsets, d_secrets, d_nonces, d_out, d_ok, n,
+                                   d_n_bad, set.buf[0], set.buf[1], st);
+    });
+}
+
+int p252_encrypt_ragged_device_into(p252_ctx* ctx, int variant, const void* d_tags, size_t max_len, const void* d_messages, size_t n_scalars,
+                               const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_ciphers, size_t n, void* d_n_bad,
+                               void* hip_stream) {
+    return crypt_ragged_device(ctx, variant, false, d_tags, max_len, d_messages, n_scalars, d_offsets, d_secrets, d_nonces, d_ciphers, nullptr, n,
+                               d_n_bad, hip_stream);
+}
+
+int p252_decrypt_ragged_device_into(p252_ctx* ctx, int variant, const void* d_tags, size_t max_len, const void* d_ciphers, size_t n_scalars,
+                               const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_messages, void* d_ok, size_t n,
+                               void* d_n_bad, void* hip_stream) {
+    return crypt_ragged_device(ctx, variant, true, d_tags, max_len, d_ciphers, n_scalars, d_offsets, d_secrets, d_nonces, d_messages, d_ok, n, d_n_bad,
+                               hip_stream);
+}
+
 // shared by p252_tag and p252_encryption_tag: tag = hash_to_scalar(io-words (BE u32) || domain separator (BE u64)),
 // hash_to_scalar = BLAKE2b-512 read as a 512-bit little-endian integer mod p.  UNPINNED recipe (header).
 static void tag_from_words(const std::vector<uint32_t>& words, uint64_t sep, uint64_t tag_out[4]) {
@@ -963,6 +1013,14 @@ int p252_encryption_tag(int variant, size_t message_len, uint64_t tag_out[4]) {
     uint64_t sep = 0;
     p252_domain_separator(P252_DOMAIN_ENCRYPTION, &sep);
     tag_from_words(words, sep, tag_out);
+    return P252_OK;
+}
+
+// the tag table of the ragged calls: row L - 1 = p252_encryption_tag(variant, L), L = 1 .. max_len
+int p252_encryption_tags(int variant, size_t max_len, uint64_t* tags_out) {
+    if (!tags_out || !crypt_variant_ok(variant) || max_len == 0 || max_len > P252_CRYPT_RAGGED_MAX_LEN) return P252_ERR_INVALID_ARGUMENT;
+    for (size_t len = 1; len <= max_len; ++len)
+        if (int rc = p252_encryption_tag(variant, len, tags_out + 4 * (len - 1))) return rc;
     return P252_OK;
 }
 

@@ -42,28 +42,7 @@ int with_forest_index(p252_ctx* ctx, const std::string& who, hipStream_t st, uns
     });
 }
 
-// the buffers of a call as byte ranges, for the calls that refuse overlapping ones (a null or empty range overlaps nothing)
-struct ByteRange {
-    const void* p;
-    size_t bytes;
-    const char* name;
-};
-bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-// each written range, in listed order, against the read ranges in listed order and then — `among` — against the written ranges before
-// it; the first hit is the refusal
-int refuse_overlaps(p252_ctx* ctx, const std::string& who, const ByteRange* read, size_t n_read, const ByteRange* written, size_t n_written,
-                    bool among) {
-    for (size_t a = 0; a < n_written; ++a)
-        for (size_t i = 0; i < n_read + (among ? a : 0); ++i) {
-            const ByteRange& other = i < n_read ? read[i] : written[i - n_read];
-            if (ranges_overlap(written[a], other)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": " + written[a].name + " overlaps " + other.name);
-        }
-    return P252_OK;
-}
+// (ByteRange / refuse_overlaps, the refusal of overlapping buffers: api_util.hpp)
 
 // the bound on the stored levels of a ragged forest, in scalars: what d_levels of these sizes holds
 size_t forest_levels_bound(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves) {

@@ -632,10 +632,12 @@ static int crypt_host_run(p252_ctx* ctx, int variant, bool decrypt, const uint64
 // the host-buffer encrypt / decrypt: whatever the call copied into library-owned memory — shared secrets, nonces, plaintexts
 // and ciphertexts in the context's device scratch or in the staging lanes (page-locked host + device chunks) — is cleared
 // before it returns, on success and on failure (the reference: zeroize, Cargo.toml:14; dusk-safe zeroizes a finished sponge)
-static int crypt_host(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const uint64_t* in, const uint64_t* secrets,
-                      const uint64_t* nonces, size_t len, uint64_t* out, uint8_t* ok, size_t n) {
+// (`run` is the call proper; stream_scratch: it also worked in the null stream's scratch pair — the ragged calls' order array and
+// counters, which hold no secret but are cleared with the rest)
+template <class Run>
+static int crypt_host_wiped(p252_ctx* ctx, bool stream_scratch, Run&& run) {
     if (ctx) ctx->io_used = {};
-    const int rc = crypt_host_run(ctx, variant, decrypt, tag, in, secrets, nonces, len, out, ok, n);
+    const int rc = run();
     if (!ctx) return rc;
     const p252_ctx::IoUse used = ctx->io_used;
     if (!used.in && !used.out && !used.lanes) return rc;
@@ -655,10 +657,64 @@ static int crypt_host(p252_ctx* ctx, int variant, bool decrypt, const uint64_t t
     if (used.lanes) keep(wipe_lanes(ctx, /*dirty_only=*/true));
     keep(wipe_span(ctx->d_in, used.in < ctx->d_in_cap ? used.in : ctx->d_in_cap));
     keep(wipe_span(ctx->d_out, used.out < ctx->d_out_cap ? used.out : ctx->d_out_cap));
+    if (stream_scratch)
+        for (auto& set : ctx->lvl)
+            if (set.st == nullptr)
+                for (int i = 0; i < 2; ++i) keep(wipe_span(set.buf[i], set.cap[i]));
     keep(hipStreamSynchronize(nullptr));
     if (e != hipSuccess && rc == P252_OK) return fail(ctx, P252_ERR_HIP, std::string("encrypt/decrypt: wiping the scratch failed: ") + hipGetErrorString(e));
     ctx->err = msg;
     return rc;
+}
+
+static int crypt_host(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const uint64_t* in, const uint64_t* secrets,
+                      const uint64_t* nonces, size_t len, uint64_t* out, uint8_t* ok, size_t n) {
+    return crypt_host_wiped(ctx, false, [&] { return crypt_host_run(ctx, variant, decrypt, tag, in, secrets, nonces, len, out, ok, n); });
+}
+
+// messages of different lengths: every message is checked here first (the codes of hash_ragged), then [message or cipher side |
+// tags | offsets rebased to 0 | secrets | nonces] go to the device in one copy each and the other side (and the flags) come back —
+// synchronous, no chunked pipeline.  The cipher of message i lies at offsets[i] + i, so the cipher side of a call whose offsets do
+// not start at 0 starts offsets[0] scalars into the caller's array, as the message side does.
+static int crypt_ragged_host_run(p252_ctx* ctx, int variant, bool decrypt, const uint64_t* tags, size_t max_len, const uint64_t* in,
+                                 const uint64_t* offsets, const uint64_t* secrets, const uint64_t* nonces, uint64_t* out, uint8_t* ok, size_t n) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = decrypt ? "decrypt_ragged" : "encrypt_ragged";
+    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": unknown variant");
+    if (max_len == 0 || max_len > P252_CRYPT_RAGGED_MAX_LEN)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_len must be 1 .. P252_CRYPT_RAGGED_MAX_LEN = " + std::to_string(P252_CRYPT_RAGGED_MAX_LEN));
+    if (n == 0) return P252_OK;
+    if (!tags || !offsets || !secrets || !nonces || !out || (decrypt && !ok)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    for (size_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i]) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": offsets decrease at message " + std::to_string(i));
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        if (len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, who + ": message " + std::to_string(i) + " is empty");
+        if (len > max_len) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": message " + std::to_string(i) + " is longer than max_len");
+    }
+    if (!in) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    const uint64_t total = offsets[n] - offsets[0];
+    if (total > SIZE_MAX / 128 || n > SIZE_MAX / 128) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> rebased(offsets, offsets + n + 1);
+    for (auto& o : rebased) o -= offsets[0];
+    const size_t msg_bytes = (size_t)total * 32, cph_bytes = ((size_t)total + n) * 32;
+    // the arrays are not per message: each is one item of its whole size
+    const std::vector<HostSpan> ins = {{reinterpret_cast<const char*>(in + offsets[0] * 4), nullptr, decrypt ? cph_bytes : msg_bytes},
+                                       {reinterpret_cast<const char*>(tags), nullptr, max_len * 32},
+                                       {reinterpret_cast<const char*>(rebased.data()), nullptr, (n + 1) * 8},
+                                       {reinterpret_cast<const char*>(secrets), nullptr, n * 64},
+                                       {reinterpret_cast<const char*>(nonces), nullptr, n * 32}};
+    std::vector<HostSpan> outs = {{nullptr, reinterpret_cast<char*>(out + offsets[0] * 4), decrypt ? msg_bytes : cph_bytes}};
+    if (decrypt) outs.push_back({nullptr, reinterpret_cast<char*>(ok), n});
+    int dev_rc = P252_OK;  // (the `_device` call takes the schedule's scratch pair of the stream; its status is an entry-point code)
+    const int rc = host_batch(ctx, Route::ONE_SHOT, 1, 1, ins, outs, [&](const void* const* d_in, void* const* d_out, size_t, size_t, hipStream_t st) {
+        dev_rc = decrypt ? p252_decrypt_ragged_device_into(ctx, variant, d_in[1], max_len, d_in[0], (size_t)total, d_in[2], d_in[3], d_in[4], d_out[0], d_out[1],
+                                                      n, nullptr, st)
+                         : p252_encrypt_ragged_device_into(ctx, variant, d_in[1], max_len, d_in[0], (size_t)total, d_in[2], d_in[3], d_in[4], d_out[0], n, nullptr,
+                                                      st);
+        return hipSuccess;
+    });
+    return dev_rc ? dev_rc : rc;
 }
 
 extern "C" {
@@ -671,6 +727,20 @@ int p252_encrypt_batch(p252_ctx* ctx, int variant, const uint64_t tag[4], const 
 int p252_decrypt_batch(p252_ctx* ctx, int variant, const uint64_t tag[4], const uint64_t* ciphers, const uint64_t* secrets,
                        const uint64_t* nonces, size_t len, uint64_t* messages, uint8_t* ok, size_t n) {
     return crypt_host(ctx, variant, true, tag, ciphers, secrets, nonces, len, messages, ok, n);
+}
+
+int p252_encrypt_ragged(p252_ctx* ctx, int variant, const uint64_t* tags, size_t max_len, const uint64_t* messages, const uint64_t* offsets,
+                        const uint64_t* secrets, const uint64_t* nonces, uint64_t* ciphers, size_t n) {
+    return crypt_host_wiped(ctx, true, [&] {
+        return crypt_ragged_host_run(ctx, variant, false, tags, max_len, messages, offsets, secrets, nonces, ciphers, nullptr, n);
+    });
+}
+
+int p252_decrypt_ragged(p252_ctx* ctx, int variant, const uint64_t* tags, size_t max_len, const uint64_t* ciphers, const uint64_t* offsets,
+                        const uint64_t* secrets, const uint64_t* nonces, uint64_t* messages, uint8_t* ok, size_t n) {
+    return crypt_host_wiped(ctx, true, [&] {
+        return crypt_ragged_host_run(ctx, variant, true, tags, max_len, ciphers, offsets, secrets, nonces, messages, ok, n);
+    });
 }
 
 }  // extern "C"

@@ -9,8 +9,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "coop29.hpp"
+#include "crypt_calls.hpp"
+#include "crypt_args.h"
 #include "hades29.hpp"
 #include "kernels.h"
 
@@ -493,25 +496,68 @@ __device__ __forceinline__ void lane_add(E29 s[WIDTH], unsigned pos, const E29& 
     }
 }
 
-template <bool DECRYPT>
+// RAGGED (the mixed-length encryption calls, crypt_args.h): the lane's message is order[slot], its length the difference of two
+// offsets, its tag tags[len - 1], and the call sequence is computed from (variant, len) (crypt_calls.hpp) instead of read from
+// `prog`.  The schedule hands every wave ONE length, read here through readfirstlane of the first live lane: the
+// positions stay wave-uniform and the control flow below is the fixed-length kernel's.  `len` arrives as max_len.
+template <bool RAGGED>
+using CryptExtra = std::conditional_t<RAGGED, CryptRaggedArgs, CryptFixedArgs>;
+
+// the message of a slot of the order array: false for a sentinel and for a bad message (counted, its flag cleared, by `leader`)
+__device__ __forceinline__ bool crypt_slot_message(const CryptRaggedArgs& rg, size_t slot, size_t n, unsigned max_len, bool leader,
+                                                     uint8_t* __restrict__ flags, size_t* m, uint64_t* lo, unsigned* len) {
+    if (slot >= rg.slots) return false;
+    const unsigned long long id = rg.order[slot];
+    if (id >= n) return false;  // the sentinel of a padding slot (all ones), or nothing the schedule wrote
+    const uint64_t a = rg.offsets[id], b = rg.offsets[id + 1];
+    if (crypt_span_bad(a, b, max_len, rg.n_scalars)) {
+        if (leader) {
+            if (rg.n_bad) atomicAdd(rg.n_bad, 1u);
+            if (flags) flags[id] = 0;
+        }
+        return false;
+    }
+    *m = (size_t)id;
+    *lo = a;
+    *len = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b - a));  // one length per wave: an SGPR
+    // (the schedule never mixes lengths in a wave; a lane that finds another length than its wave's leaves before it reads or
+    // writes anything, so the kernel stays inside the buffers whatever the order array holds)
+    return (unsigned)(b - a) == *len;
+}
+
+template <bool DECRYPT, bool RAGGED = false>
 __global__ void __launch_bounds__(P252_BLOCK) k_crypt(const int32_t* __restrict__ tab, TagArg tag,
                                                       const Scalar32* __restrict__ in,
                                                       const Scalar32* __restrict__ secrets,
                                                       const Scalar32* __restrict__ nonces, unsigned len,
                                                       Scalar32* out, uint8_t* __restrict__ flags, size_t n,
-                                                      const uint32_t* __restrict__ prog, unsigned n_calls) {
-    const size_t idx = (size_t)blockIdx.x * P252_BLOCK + threadIdx.x;
-    if (idx >= n) return;
-    const Scalar32* my_in = in + idx * (DECRYPT ? len + 1 : len);
-    Scalar32* my_out = out + idx * (DECRYPT ? len : len + 1);
+                                                      const uint32_t* __restrict__ prog, unsigned n_calls, CryptExtra<RAGGED> rg) {
+    size_t idx = (size_t)blockIdx.x * P252_BLOCK + threadIdx.x;
+    const Scalar32* my_in;
+    Scalar32* my_out;
     E29 s[WIDTH];
-    s[0] = from_mont4(tag.w);
+    int variant = 0;  // (RAGGED only)
+    if constexpr (RAGGED) {
+        uint64_t lo;
+        if (!crypt_slot_message(rg, idx, n, len, true, DECRYPT ? flags : nullptr, &idx, &lo, &len)) return;
+        my_in = in + lo + (DECRYPT ? idx : 0);  // the cipher side is shifted by one MAC per earlier message
+        my_out = out + lo + (DECRYPT ? 0 : idx);
+        variant = rg.variant;
+        n_calls = crypt_n_calls(variant, len);
+        s[0] = load_scalar(static_cast<const Scalar32*>(rg.tags) + (len - 1));
+    } else {
+        if (idx >= n) return;
+        my_in = in + idx * (DECRYPT ? len + 1 : len);
+        my_out = out + idx * (DECRYPT ? len : len + 1);
+        s[0] = from_mont4(tag.w);
+    }
 #pragma unroll
     for (int k = 1; k < WIDTH; ++k) s[k] = e29_zero();
     unsigned pos_absorb = 0, pos_squeeze = 0, masked = 0, absorbed = 0;
 #pragma unroll 1
     for (unsigned ci = 0; ci < n_calls; ++ci) {
-        const unsigned kind = prog[ci] >> 29, cnt = prog[ci] & 0x1fffffffu;
+        const uint32_t call = RAGGED ? crypt_call(variant, len, ci) : prog[ci];
+        const unsigned kind = call >> 29, cnt = call & 0x1fffffffu;
         const bool is_absorb = kind == 0 || kind == 1 || kind == 3;
 #pragma unroll 1
         for (unsigned e = 0; e < cnt; ++e) {
@@ -558,28 +604,46 @@ __global__ void __launch_bounds__(P252_BLOCK) k_crypt(const int32_t* __restrict_
 // k_crypt on lane groups (batches of <= 8,192 messages): lane 0 the capacity element, lane 1 + pos the rate position pos.
 // Every position is wave-uniform, so "the lane at this position" is one compare; a message element decrypted by one
 // lane and absorbed later by another travels through `out` (same wave, program order: the pointer is not __restrict__).
-template <bool DECRYPT>
+// RAGGED: as k_crypt; a wave holds eight groups, and the schedule aligns every length to eight messages.
+template <bool DECRYPT, bool RAGGED = false>
 __global__ void __launch_bounds__(P252_BLOCK) k_crypt_coop(const int32_t* __restrict__ tab, TagArg tag,
                                                            const Scalar32* __restrict__ in,
                                                            const Scalar32* __restrict__ secrets,
                                                            const Scalar32* __restrict__ nonces, unsigned len,
                                                            Scalar32* out, uint8_t* __restrict__ flags, size_t n,
-                                                           const uint32_t* __restrict__ prog, unsigned n_calls) {
+                                                           const uint32_t* __restrict__ prog, unsigned n_calls, CryptExtra<RAGGED> rg) {
     const size_t lane = (size_t)blockIdx.x * P252_BLOCK + threadIdx.x;
-    const size_t idx = lane / 8;
-    if (idx >= n) return;
+    size_t idx = lane / 8;
     const int j = (int)(threadIdx.x & 7u);
+    const Scalar32* my_in;
+    Scalar32* my_out;
+    int variant = 0;  // (RAGGED only)
+    if constexpr (RAGGED) {
+        uint64_t lo;
+        if (!crypt_slot_message(rg, idx, n, len, j == 0, DECRYPT ? flags : nullptr, &idx, &lo, &len)) return;
+        my_in = in + lo + (DECRYPT ? idx : 0);
+        my_out = out + lo + (DECRYPT ? 0 : idx);
+        variant = rg.variant;
+        n_calls = crypt_n_calls(variant, len);
+    } else {
+        if (idx >= n) return;
+        my_in = in + idx * (DECRYPT ? len + 1 : len);
+        my_out = out + idx * (DECRYPT ? len : len + 1);
+    }
     WaveComm8 cm{j, (int)(((threadIdx.x & 63u) & ~7u) * 4u)};
     CoopLane<8> L = coop_lane<8>(tab, cm);
-    const Scalar32* my_in = in + idx * (DECRYPT ? len + 1 : len);
-    Scalar32* my_out = out + idx * (DECRYPT ? len : len + 1);
-    E29 s = from_mont4(tag.w), unused;
+    E29 s, unused;
+    if constexpr (RAGGED)
+        s = load_scalar(static_cast<const Scalar32*>(rg.tags) + (len - 1));
+    else
+        s = from_mont4(tag.w);
     if (L.row > 0) s = e29_zero();
     unused = s;
     unsigned pos_absorb = 0, pos_squeeze = 0, masked = 0, absorbed = 0;
 #pragma unroll 1
     for (unsigned ci = 0; ci < n_calls; ++ci) {
-        const unsigned kind = prog[ci] >> 29, cnt = prog[ci] & 0x1fffffffu;
+        const uint32_t call = RAGGED ? crypt_call(variant, len, ci) : prog[ci];
+        const unsigned kind = call >> 29, cnt = call & 0x1fffffffu;
         const bool is_absorb = kind == 0 || kind == 1 || kind == 3;
 #pragma unroll 1
         for (unsigned e = 0; e < cnt; ++e) {
@@ -920,7 +984,19 @@ hipError_t launch_crypt(bool decrypt, const int32_t* tab, const TagArg& tag, con
     const bool coop = coop8(n);
     auto k = coop ? (decrypt ? k_crypt_coop<true> : k_crypt_coop<false>) : (decrypt ? k_crypt<true> : k_crypt<false>);
     return launch(k, coop ? n * 8 : n, st, tab, tag, static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
-                  static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out), static_cast<uint8_t*>(flags), n, prog, n_calls);
+                  static_cast<const Scalar32*>(nonces), len, static_cast<Scalar32*>(out), static_cast<uint8_t*>(flags), n, prog, n_calls,
+                  CryptFixedArgs{});
+}
+
+// the RAGGED instantiations over an order array of rg.slots slots (the schedule has filled it): one lane, or one group of eight
+// lanes, per slot; the tag and the call table of the fixed-length launch have no part in it
+hipError_t launch_crypt_mixed(bool decrypt, bool coop, const int32_t* tab, unsigned max_len, const void* in, const void* secrets,
+                                      const void* nonces, void* out, void* flags, size_t n, const CryptRaggedArgs& rg, hipStream_t st) {
+    if (rg.slots == 0) return hipSuccess;
+    auto k = coop ? (decrypt ? k_crypt_coop<true, true> : k_crypt_coop<false, true>) : (decrypt ? k_crypt<true, true> : k_crypt<false, true>);
+    return launch(k, coop ? rg.slots * 8 : rg.slots, st, tab, TagArg{}, static_cast<const Scalar32*>(in), static_cast<const Scalar32*>(secrets),
+                  static_cast<const Scalar32*>(nonces), max_len, static_cast<Scalar32*>(out), static_cast<uint8_t*>(flags), n,
+                  static_cast<const uint32_t*>(nullptr), 0u, rg);
 }
 
 hipError_t launch_truncate250(const void* in, void* out, size_t n, hipStream_t st) {

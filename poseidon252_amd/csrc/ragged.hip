@@ -18,12 +18,16 @@
 // Sponge.  k_sponge_ragged: one lane per message, the loop of k_sponge (kernels.hip) with a per-lane length and tag.
 // k_sponge_ragged_coop: eight lanes per message (coop29.hpp), for launches that cannot fill the chip, under the rule every entry
 // point of kernels.hip applies (coop8, kernels.h).  No whole-line fetch variant: the kernel is compute-bound.
+//
+// The exact-length sort of the encryption calls (k_crypt_ragged_*, crypt_ragged.h) stands here too, behind the sponge: the same two
+// passes over one bucket per length.  It hashes nothing; its sponge is k_crypt / k_crypt_coop of kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
 #include "blockops.hpp"
 #include "coop29.hpp"
+#include "crypt_ragged.h"
 #include "hades29.hpp"
 #include "kernels.h"
 #include "ragged.h"
@@ -209,6 +213,80 @@ __global__ void __launch_bounds__(P252_BLOCK) k_sponge_ragged_coop_trunc(const i
                                                                          const uint64_t* __restrict__ order, unsigned out_len,
                                                                          Scalar32* __restrict__ out, size_t n, unsigned* __restrict__ n_bad) {
     sponge_ragged_coop_body<true>(tab, tags, max_len, in, offsets, order, out_len, out, n, n_bad);
+}
+
+// ---- the exact-length sort of the encryption calls (p252_{encrypt,decrypt}_ragged*, crypt_ragged.h): the same two passes over one
+// bucket per LENGTH, with every bucket's size rounded up to a whole group of slots ----
+__device__ __forceinline__ unsigned crypt_bucket_of(const uint64_t* __restrict__ offsets, size_t i, uint64_t max_len, uint64_t n_scalars) {
+    const uint64_t a = offsets[i], b = offsets[i + 1];
+    return crypt_span_bad(a, b, max_len, n_scalars) ? 0u : (unsigned)(b - a);  // (max_len <= P252_CRYPT_RAGGED_MAX_LEN: the host refuses more)
+}
+
+
+// the counters to zero and the all-ones sentinel into every slot of the order array, in one launch.  (A kernel, not two
+// hipMemsetAsync: replayed from a captured graph, two adjacent memset nodes of different values did not reliably leave zeros in
+// the one buffer and ones in the other — the second replay's scatter then started from cursors that were not counts
+// (DESIGN.md §3.10).  A kernel node replays like every other launch of the call.)
+__global__ void __launch_bounds__(SORT_BLOCK) k_crypt_ragged_clear(unsigned long long* __restrict__ hist, uint64_t* __restrict__ order,
+                                                                   size_t slots) {
+    const size_t i = (size_t)blockIdx.x * SORT_BLOCK + threadIdx.x;
+    if (i < CRYPT_RAGGED_BUCKETS) hist[i] = 0ull;
+    if (i < slots) order[i] = CRYPT_RAGGED_SENTINEL;
+}
+
+__global__ void __launch_bounds__(SORT_BLOCK) k_crypt_ragged_hist(const uint64_t* __restrict__ offsets, size_t n, uint64_t max_len,
+                                                                  uint64_t n_scalars, unsigned long long* __restrict__ hist) {
+    bucket_hist<SORT_BLOCK, SORT_ITEMS, CRYPT_RAGGED_BUCKETS>(n, hist, [=](size_t i) { return crypt_bucket_of(offsets, i, max_len, n_scalars); });
+}
+
+// counts -> start of each bucket in the sorted order, buckets in DESCENDING order (longest first, bucket 0 last), in place.  Every
+// bucket takes its count rounded up to a multiple of `group` slots, so every start is a multiple of `group`.
+// (The padded sizes of n counted messages end within the `slots` the order array has.  Counters that add up to more are not what the
+// histogram pass leaves; every bucket then starts at 0, where the scatter pass stays below its own count of messages: in bounds.)
+__global__ void __launch_bounds__(SORT_BLOCK) k_crypt_ragged_scan(unsigned long long* __restrict__ hist, unsigned group, size_t slots) {
+    constexpr unsigned PER = (CRYPT_RAGGED_BUCKETS + SORT_BLOCK - 1) / SORT_BLOCK;
+    const unsigned t = threadIdx.x;
+    unsigned long long c[PER], sum = 0;
+#pragma unroll
+    for (unsigned k = 0; k < PER; ++k) {
+        const unsigned r = t * PER + k;  // rank in descending bucket order
+        const unsigned long long cnt = r < CRYPT_RAGGED_BUCKETS ? hist[CRYPT_RAGGED_BUCKETS - 1 - r] : 0ull;
+        c[k] = (cnt + group - 1) / group * group;
+        sum += c[k];
+    }
+    unsigned long long total;
+    unsigned long long run = block_exclusive<SORT_BLOCK>(sum, &total);
+    const bool sane = total <= slots;
+    if (!sane) run = 0;
+#pragma unroll
+    for (unsigned k = 0; k < PER; ++k) {
+        const unsigned r = t * PER + k;
+        if (r < CRYPT_RAGGED_BUCKETS) hist[CRYPT_RAGGED_BUCKETS - 1 - r] = run;
+        if (sane) run += c[k];
+    }
+}
+
+__global__ void __launch_bounds__(SORT_BLOCK) k_crypt_ragged_scatter(const uint64_t* __restrict__ offsets, size_t n, uint64_t max_len,
+                                                                     uint64_t n_scalars, unsigned long long* __restrict__ cursor,
+                                                                     uint64_t* __restrict__ order) {
+    bucket_scatter<SORT_BLOCK, SORT_ITEMS, CRYPT_RAGGED_BUCKETS>(n, cursor, order,
+                                                                 [=](size_t i) { return crypt_bucket_of(offsets, i, max_len, n_scalars); });
+}
+
+hipError_t launch_crypt_ragged_schedule(const void* offsets, size_t n, size_t max_len, uint64_t n_scalars, bool coop, void* order, void* hist,
+                                        hipStream_t st) {
+    const uint64_t* off = static_cast<const uint64_t*>(offsets);
+    unsigned long long* h = static_cast<unsigned long long*>(hist);
+    const unsigned tiles = (unsigned)((n + SORT_TILE - 1) / SORT_TILE);
+    const size_t slots = crypt_ragged_slots(n, max_len, coop);
+    const size_t cells = slots > CRYPT_RAGGED_BUCKETS ? slots : CRYPT_RAGGED_BUCKETS;
+    hipLaunchKernelGGL(k_crypt_ragged_clear, dim3((unsigned)((cells + SORT_BLOCK - 1) / SORT_BLOCK)), dim3(SORT_BLOCK), 0, st, h,
+                       static_cast<uint64_t*>(order), slots);
+    hipLaunchKernelGGL(k_crypt_ragged_hist, dim3(tiles), dim3(SORT_BLOCK), 0, st, off, n, (uint64_t)max_len, n_scalars, h);
+    hipLaunchKernelGGL(k_crypt_ragged_scan, dim3(1), dim3(SORT_BLOCK), 0, st, h, (unsigned)crypt_ragged_group(coop), slots);
+    hipLaunchKernelGGL(k_crypt_ragged_scatter, dim3(tiles), dim3(SORT_BLOCK), 0, st, off, n, (uint64_t)max_len, n_scalars, h,
+                       static_cast<uint64_t*>(order));
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -332,6 +332,34 @@ class Context:
         self._check(fn(self._h, _ptr(t), t.shape[0], _ptr(x), _ptr(off), out_len, _ptr(out), n))
         return out
 
+    def crypt_ragged(self, decrypt, variant, tags, flat, offsets, secrets, nonces):
+        """n messages of different lengths encrypted or decrypted from host buffers (p252_{encrypt,decrypt}_ragged): offsets are the
+        n + 1 MESSAGE offsets in both directions; message i = messages[offsets[i]:offsets[i+1]], its cipher the L_i + 1 scalars at
+        ciphers[offsets[i] + i:].  tags[L-1] = the tag of a message of length L (max_len = len(tags)).  flat = the messages
+        (encrypt) or the ciphers (decrypt) -> the other side, and the (n,) uint8 flags on decrypt.  The library checks every length
+        before it launches anything and clears its copies of what it was handed before it returns."""
+        f = "decrypt_ragged" if decrypt else "encrypt_ragged"
+        t = _as_scalars(tags).reshape(-1, 4)
+        x = _as_scalars(flat).reshape(-1, 4)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        n = max(off.shape[0] - 1, 0)
+        sec = _as_scalars(secrets).reshape(-1, 2, 4)
+        non = _as_scalars(nonces).reshape(-1, 4)
+        if sec.shape[0] != n or non.shape[0] != n:
+            raise ValueError("%s: %d messages, %d secrets, %d nonces" % (f, n, sec.shape[0], non.shape[0]))
+        total = int(off[-1]) if n else 0
+        if n and total + (n if decrypt else 0) > x.shape[0]:
+            raise ValueError("%s: offsets reach past the %d scalars given" % (f, x.shape[0]))
+        out = np.empty((total + (0 if decrypt else n), 4), dtype=np.uint64)
+        if decrypt:
+            ok = np.zeros(n, dtype=np.uint8)
+            self._check(_lib.lib().p252_decrypt_ragged(self._h, int(variant), _ptr(t), t.shape[0], _ptr(x), _ptr(off), _ptr(sec), _ptr(non),
+                                                       _ptr(out), _ptr(ok, _lib._u8p), n))
+            return out, ok
+        self._check(_lib.lib().p252_encrypt_ragged(self._h, int(variant), _ptr(t), t.shape[0], _ptr(x), _ptr(off), _ptr(sec), _ptr(non),
+                                                   _ptr(out), n))
+        return out
+
     def merkle4_tree(self, tag, leaves, want_levels=False):
         return self._tree(_ARITIES[4], tag, leaves, want_levels)
 
@@ -370,6 +398,31 @@ class Context:
                        _dev_ptr(self, f, "d_offsets", d_offsets, (n + 1) * 8, elem=8), out_len,
                        _dev_ptr(self, f, "d_out", d_out, n * out_len * 32), n,
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
+    def encrypt_ragged_device(self, variant, d_tags, max_len, d_messages, n_scalars, d_offsets, d_secrets, d_nonces, d_ciphers, n, d_n_bad=None):
+        """p252_encrypt_ragged_device_into on torch's current stream: d_offsets = n + 1 int64/uint64 MESSAGE offsets, d_tags = max_len
+        scalars (tags[L-1] for length L), d_messages n_scalars scalars, d_ciphers n_scalars + n (the cipher of message i at
+        offsets[i] + i).  A bad message (empty, longer than max_len, decreasing offsets, an end past n_scalars) leaves its output
+        untouched and increments d_n_bad (a zeroed device int32/uint32, optional); nothing is checked on the host."""
+        f = "encrypt_ragged_device"
+        self._check(_lib.lib().p252_encrypt_ragged_device_into(
+            self._h, int(variant), _dev_ptr(self, f, "d_tags", d_tags, max_len * 32), max_len,
+            _dev_ptr(self, f, "d_messages", d_messages, n_scalars * 32), n_scalars, _dev_ptr(self, f, "d_offsets", d_offsets, (n + 1) * 8, elem=8),
+            _dev_ptr(self, f, "d_secrets", d_secrets, n * 64), _dev_ptr(self, f, "d_nonces", d_nonces, n * 32),
+            _dev_ptr(self, f, "d_ciphers", d_ciphers, (n_scalars + n) * 32), n, _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+            _stream(self)))
+
+    def decrypt_ragged_device(self, variant, d_tags, max_len, d_ciphers, n_scalars, d_offsets, d_secrets, d_nonces, d_messages, d_ok, n,
+                              d_n_bad=None):
+        """p252_decrypt_ragged_device_into: the layout of encrypt_ragged_device read the other way; d_ok = n uint8 flags (1 = the MAC
+        verified; 0 = DecryptionFailed with that message unspecified, or a bad message, whose output is untouched)"""
+        f = "decrypt_ragged_device"
+        self._check(_lib.lib().p252_decrypt_ragged_device_into(
+            self._h, int(variant), _dev_ptr(self, f, "d_tags", d_tags, max_len * 32), max_len,
+            _dev_ptr(self, f, "d_ciphers", d_ciphers, (n_scalars + n) * 32), n_scalars, _dev_ptr(self, f, "d_offsets", d_offsets, (n + 1) * 8, elem=8),
+            _dev_ptr(self, f, "d_secrets", d_secrets, n * 64), _dev_ptr(self, f, "d_nonces", d_nonces, n * 32),
+            _dev_ptr(self, f, "d_messages", d_messages, n_scalars * 32), _dev_ptr(self, f, "d_ok", d_ok, n, elem=1), n,
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
     def merkle4_tree_device(self, tag, d_leaves, n_leaves, d_root, d_levels=None):
         f = "merkle4_tree_device"
