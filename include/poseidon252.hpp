@@ -443,7 +443,8 @@ namespace detail {
     X(N, multiproof_device) X(N, multiproof_verify_device) X(N, forest_ragged_multiproof_bound) X(N, forest_ragged_multiproof_device_into)        \
     X(N, forest_ragged_multiproof_verify_device_into) X(N, forest_frontier_bound) X(N, forest_frontier_append_device_into)                \
     X(N, forest_frontier_extract_device_into) X(N, forest_frontier_append_witness_device_into)                                            \
-    X(N, forest_ragged_consistency_device_into) X(N, forest_consistency_verify_device_into)
+    X(N, forest_ragged_consistency_device_into) X(N, forest_consistency_verify_device_into)                                              \
+    X(N, forest_ragged_anchor_openings_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -840,6 +841,42 @@ inline void merkle_forest_consistency_verify_device(const ConsistencyClaims& cla
                                                           proof.stride_depth, k, claims.d_tree_ids, claims.n_trees, d_ok, d_old_roots_out,
                                                           d_new_roots_out, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_consistency_verify_device");
+}
+
+// Anchors (p252_merkle{4,2}_forest_ragged_anchor_openings_device_into): the roots the trees of a built forest had at earlier leaf counts,
+// and openings of their leaves against those roots, with no second copy of the forest.  Anchor a is tree d_tree_ids[a] (uint32) at count
+// d_counts[a] (uint64): d_roots[a] receives the root of the tree's first c leaves, d_depths[a] (uint8) its depth; a bad anchor (unknown or
+// bad tree, c == 0, c > n_t) a zero root, depth 0xFF and one count in *d_n_bad_anchors.  Opening i is leaf d_leaf_ids[i] (uint64) under
+// anchor d_anchor_ids[i] (uint32), written into `openings` in the layout of merkle_forest_ragged_openings_device at the stride
+// forest_openings_stride(forest.max_leaves, arity), byte for byte what that call writes on a fresh build of the tree's first c leaves;
+// a bad opening (anchor id >= m, a bad anchor, leaf id >= c) is zeros with depth 0xFF, counted in *d_n_bad.  *d_n_hashed (device
+// uint64, zeroed by the caller) gains the digests the anchors need.  Verification needs nothing new: merkle_forest_ragged_verify_device
+// takes the openings with d_tree_ids = d_anchor_ids, d_roots = anchors.d_roots and n_trees = anchors.m.  k == 0: the roots alone.
+struct ForestAnchors {
+    const void* d_tree_ids;  // m uint32
+    const void* d_counts;    // m uint64
+    std::size_t m;
+    void* d_roots;   // m scalars
+    void* d_depths;  // m bytes
+};
+struct AnchorOpenings {
+    void* d_leaves;     // k scalars
+    void* d_siblings;   // k x stride x (arity - 1) scalars
+    void* d_positions;  // k x stride bytes
+    void* d_depths;     // k bytes
+};
+inline void merkle_forest_ragged_anchor_openings_device(const ForestView& forest, const ForestAnchors& anchors, const void* d_anchor_ids,
+                                                        const void* d_leaf_ids, std::size_t k, const AnchorOpenings& openings,
+                                                        unsigned arity = 4, Context& ctx = Context::default_context(),
+                                                        void* d_n_bad_anchors = nullptr, void* d_n_bad = nullptr, void* d_n_hashed = nullptr,
+                                                        void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_anchor_openings_device", arity);
+    detail::check(m.forest_ragged_anchor_openings_device_into(ctx.get(), m.tag().data(), forest.d_leaves, forest.n_leaves, forest.d_offsets,
+                                                              forest.n_trees, forest.max_leaves, forest.d_levels, anchors.d_tree_ids,
+                                                              anchors.d_counts, anchors.m, d_anchor_ids, d_leaf_ids, k, anchors.d_roots,
+                                                              anchors.d_depths, openings.d_leaves, openings.d_siblings, openings.d_positions,
+                                                              openings.d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed, stream),
+                  ctx.get(), "merkle_forest_ragged_anchor_openings_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

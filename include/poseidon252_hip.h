@@ -126,7 +126,10 @@ extern "C" {
  *      `_into`: every result goes into buffers the caller owns): the proof that a tree of such a forest is the tree it was at an
  *      older leaf count with leaves appended and nothing before them changed, and its check against the two roots;
  *      + p252_encryption_tags, p252_{encrypt,decrypt}_ragged[_device_into] (additive, same version): encryption and decryption of
- *      messages of different lengths in one call */
+ *      messages of different lengths in one call;
+ *      + p252_merkle{4,2}_forest_ragged_anchor_openings_device_into (additive, same version; `_into`: every result goes into buffers
+ *      the caller owns): the roots the trees of such a forest had at earlier leaf counts, and openings of their leaves against
+ *      those roots, with no second copy of the forest */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -1012,6 +1015,56 @@ int p252_merkle2_forest_consistency_verify_device_into(p252_ctx* ctx, const uint
                                                        const void* d_siblings, const void* d_positions, const void* d_depths,
                                                        size_t stride_depth, size_t k, const void* d_tree_ids, size_t n_trees, void* d_ok,
                                                        void* d_old_roots_out, void* d_new_roots_out, void* d_n_hashed, void* hip_stream);
+
+/* ---- anchors: roots and openings of the trees of a ragged forest AS THEY WERE at earlier leaf counts.  An append-only tree grows
+ * with every block, and a party that trusts the root the tree had at count c (its anchor) needs the opening of leaf i < c in the tree
+ * of c leaves; the route without this call is one p252_merkle{4,2}_forest_ragged_resize_device_into per distinct anchor into a second
+ * copy of the forest.  With A the arity and f_l(c) = floor(c / A^l): node j of level l of the tree at c leaves is the stored node
+ * while j < f_l(c); node j == f_l(c) exists iff c mod A^l != 0 and is the PARTIAL node P_l(c) = H(the stored nodes
+ * [A f_l(c), f_{l-1}(c)) of level l - 1, then P_{l-1}(c) if it exists, then zero scalars); right of it there is nothing.  The root at c is
+ * P_depth(c)(c), or the stored node when c == A^depth(c) (c == 1: the leaf, reduced mod p as a one-leaf tree's root is).  An anchor
+ * costs depth(c) - l0 digests, l0 the lowest level whose digit of c is not zero — none when c is a power of A — however many leaves
+ * are opened under it.
+ * The forest arguments d_leaves .. d_levels exactly as p252_merkle{4,2}_forest_ragged_openings_device takes them (read-only; n_t
+ * comes from the build's own validation); tag: the tree's (Merkle4 / Merkle2).
+ * ANCHORS.  Anchor a is tree d_anchor_tree_ids[a] (uint32[m]) at count c = d_anchor_counts[a] (uint64[m]); valid iff the tree id is
+ * < n_trees, the build does not call the tree bad, and 1 <= c <= n_t.  Then d_anchor_roots[a] is the 32 bytes a fresh build of the
+ * tree's first c leaves returns as its root, d_anchor_depths[a] (uint8) = depth(c), and *d_n_hashed (device uint64 the caller has
+ * zeroed; may be NULL) gains depth(c) - l0.  A BAD anchor: a zero root, depth 0xFF, counted once in *d_n_bad_anchors (device uint32
+ * the caller has zeroed; may be NULL).
+ * OPENINGS.  Opening i is leaf d_leaf_ids[i] (uint64[k]) under anchor d_anchor_ids[i] (uint32[k]); valid iff the anchor id is < m, the
+ * anchor is valid and the leaf id is < c.  d_leaves_out[i], d_siblings[i][D][arity - 1], d_positions[i][D] and d_depths[i], at stride
+ * D = p252_merkle{4,2}_depth(max_leaves), are byte for byte what p252_merkle{4,2}_forest_ragged_openings_device writes for that leaf
+ * on a fresh build of the tree's first c leaves: the depth byte is depth(c), rows at and past it are zero, siblings right of the last
+ * node of a level are zero, and at most one sibling is a partial node.  A BAD opening: all zero, depth 0xFF, counted once in *d_n_bad
+ * (device uint32 the caller has zeroed; may be NULL).
+ * VERIFICATION needs nothing new, which is the reason for this layout: the four opening arrays go into
+ * p252_merkle{4,2}_path_ragged_device as they stand, and into p252_merkle{4,2}_forest_ragged_verify_device with
+ * d_tree_ids := d_anchor_ids, d_roots := d_anchor_roots and n_trees := m.
+ * k == 0 with m > 0 is the roots-at-counts call: d_anchor_ids, d_leaf_ids and the four opening arrays may be NULL.  m == 0 with k > 0:
+ * every opening is bad (the four anchor arrays may be NULL).  m == 0 and k == 0 -> P252_OK, nothing enqueued.
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: n_leaves, n_trees or max_leaves == 0, a NULL or misaligned buffer (scalars 16 bytes,
+ * d_offsets, the counts, d_leaf_ids and d_n_hashed 8, the ids and the two uint32 counters 4; d_levels, d_siblings and d_positions
+ * may be NULL when max_leaves == 1), size overflow (m >= 2^32 among them), or an output range that overlaps an input range or
+ * another output.  Asynchronous on hip_stream, no host synchronisation; scratch of the calling stream: the forest's index, 32 bytes
+ * per anchor, the partial nodes (m x D x 32 bytes), 48 bytes per opening, one level's children (m x arity x 32 bytes).  The digests
+ * run level by level through the library's digest launch, m nodes per level (an anchor with no partial node on a level digests zero
+ * children there, and its result is not used); the lane-group or the one-lane build is chosen by m as for every digest batch. */
+int p252_merkle4_forest_ragged_anchor_openings_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                           const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                           const void* d_anchor_tree_ids, const void* d_anchor_counts, size_t m,
+                                                           const void* d_anchor_ids, const void* d_leaf_ids, size_t k, void* d_anchor_roots,
+                                                           void* d_anchor_depths, void* d_leaves_out, void* d_siblings, void* d_positions,
+                                                           void* d_depths, void* d_n_bad_anchors, void* d_n_bad, void* d_n_hashed,
+                                                           void* hip_stream);
+/* the same for arity 2 (the level layout of merkle2 trees; pass the Merkle2 tag) */
+int p252_merkle2_forest_ragged_anchor_openings_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                           const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                           const void* d_anchor_tree_ids, const void* d_anchor_counts, size_t m,
+                                                           const void* d_anchor_ids, const void* d_leaf_ids, size_t k, void* d_anchor_roots,
+                                                           void* d_anchor_depths, void* d_leaves_out, void* d_siblings, void* d_positions,
+                                                           void* d_depths, void* d_n_bad_anchors, void* d_n_bad, void* d_n_hashed,
+                                                           void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

@@ -11,6 +11,7 @@
 #include "../../include/poseidon252_hip.h"
 #include "api_util.hpp"
 #include "ctx.hpp"
+#include "forest_anchor.h"
 #include "forest_append.h"
 #include "forest_consistency.h"
 #include "forest_frontier.h"
@@ -974,6 +975,91 @@ int p252_merkle2_forest_consistency_verify_device_into(p252_ctx* ctx, const uint
     return forest_consistency_verify_device(ctx, 2, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves_in, d_siblings, d_positions,
                                             d_depths, stride_depth, k, d_tree_ids, n_trees, d_ok, d_old_roots_out, d_new_roots_out, d_n_hashed,
                                             hip_stream);
+}
+
+// ---- roots and openings of such a forest's trees as they were at earlier leaf counts (forest_anchor.hip): m anchors (tree, count), k
+// openings (anchor, leaf).  The scratch — the forest's index, a record per anchor, the partial nodes of every anchor and level, a record
+// per opening; one level's gathered children in the second buffer — is the pair of the calling stream ----
+static int forest_ragged_anchor_openings_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                const void* d_anchor_tree_ids, const void* d_anchor_counts, size_t m, const void* d_anchor_ids,
+                                                const void* d_leaf_ids, size_t k, void* d_anchor_roots, void* d_anchor_depths,
+                                                void* d_leaves_out, void* d_siblings, void* d_positions, void* d_depths, void* d_n_bad_anchors,
+                                                void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    if (m == 0 && k == 0) return P252_OK;
+    const std::string who = "merkle_forest_ragged_anchor_openings";
+    if (max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves, n_trees and max_leaves must be > 0");
+    const size_t depth = forest_ragged_depth(max_leaves, arity);
+    if (!tag || !d_leaves || !d_offsets || (depth && !d_levels) ||
+        (m && (!d_anchor_tree_ids || !d_anchor_counts || !d_anchor_roots || !d_anchor_depths)) ||
+        (k && (!d_anchor_ids || !d_leaf_ids || !d_leaves_out || !d_depths || (depth && (!d_siblings || !d_positions)))))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_anchor_roots) || misaligned(d_leaves_out) || misaligned(d_siblings))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_anchor_counts, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets, d_anchor_counts, d_leaf_ids and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_anchor_tree_ids, 4) || misaligned_to(d_anchor_ids, 4) || misaligned_to(d_n_bad_anchors, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT,
+                    who + ": d_anchor_tree_ids, d_anchor_ids, d_n_bad_anchors and d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    // an anchor id is 32 bits; the partial nodes (m x D scalars) and the openings (k x D x (arity - 1) scalars) inside size_t
+    if (m > 0xffffffffull || m > SIZE_MAX / 256 / (depth ? depth : 1) || k > SIZE_MAX / 128 / (depth ? depth : 1))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const size_t levels_forest = forest_levels_bound(arity, n_leaves, n_trees, max_leaves);
+    const ByteRange in[] = {{d_leaves, n_leaves * 32, "d_leaves"},
+                            {d_offsets, (n_trees + 1) * 8, "d_offsets"},
+                            {d_levels, levels_forest * 32, "d_levels"},
+                            {d_anchor_tree_ids, m * 4, "d_anchor_tree_ids"},
+                            {d_anchor_counts, m * 8, "d_anchor_counts"},
+                            {d_anchor_ids, k * 4, "d_anchor_ids"},
+                            {d_leaf_ids, k * 8, "d_leaf_ids"}};
+    const ByteRange out[] = {{d_anchor_roots, m * 32, "d_anchor_roots"},
+                             {d_anchor_depths, m, "d_anchor_depths"},
+                             {d_leaves_out, k * 32, "d_leaves_out"},
+                             {d_siblings, k * depth * (arity - 1) * 32, "d_siblings"},
+                             {d_positions, k * depth, "d_positions"},
+                             {d_depths, k, "d_depths"},
+                             {d_n_bad_anchors, 4, "d_n_bad_anchors"},
+                             {d_n_bad, 4, "d_n_bad"},
+                             {d_n_hashed, 8, "d_n_hashed"}};
+    if (int rc = refuse_overlaps(ctx, who, in, std::size(in), out, std::size(out), true)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestAnchorWork w = forest_anchor_work(arity, m, k, (unsigned)depth);
+    return with_forest_index(ctx, who, st, arity, d_offsets, n_trees, n_leaves, max_leaves, w.bytes, w.children_bytes,
+                             [&](const uint64_t* ntree, const uint64_t* lo, char* work, void* children) {
+                                 return launch_forest_anchor_openings(arity, ctx->d_tab, tag_arg(tag), d_leaves, d_levels, d_offsets, ntree, lo,
+                                                                      n_trees, d_anchor_tree_ids, d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k,
+                                                                      (unsigned)depth, d_anchor_roots, d_anchor_depths, d_leaves_out, d_siblings,
+                                                                      d_positions, d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed, work, children,
+                                                                      st);
+                             });
+}
+
+int p252_merkle4_forest_ragged_anchor_openings_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                           const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                           const void* d_anchor_tree_ids, const void* d_anchor_counts, size_t m,
+                                                           const void* d_anchor_ids, const void* d_leaf_ids, size_t k, void* d_anchor_roots,
+                                                           void* d_anchor_depths, void* d_leaves_out, void* d_siblings, void* d_positions,
+                                                           void* d_depths, void* d_n_bad_anchors, void* d_n_bad, void* d_n_hashed,
+                                                           void* hip_stream) {
+    return forest_ragged_anchor_openings_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
+                                                d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths, d_leaves_out,
+                                                d_siblings, d_positions, d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_anchor_openings_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
+                                                           const void* d_offsets, size_t n_trees, size_t max_leaves, const void* d_levels,
+                                                           const void* d_anchor_tree_ids, const void* d_anchor_counts, size_t m,
+                                                           const void* d_anchor_ids, const void* d_leaf_ids, size_t k, void* d_anchor_roots,
+                                                           void* d_anchor_depths, void* d_leaves_out, void* d_siblings, void* d_positions,
+                                                           void* d_depths, void* d_n_bad_anchors, void* d_n_bad, void* d_n_hashed,
+                                                           void* hip_stream) {
+    return forest_ragged_anchor_openings_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
+                                                d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths, d_leaves_out,
+                                                d_siblings, d_positions, d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed, hip_stream);
 }
 
 }  // (the C ABI)

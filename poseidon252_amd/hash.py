@@ -1087,6 +1087,62 @@ class Context:
             _dev_ptr(self, f, "d_new_roots_out", d_new_roots_out, k * 32, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
+    # ---- anchors: roots and openings of a forest's trees as they were at earlier leaf counts
+    # (p252_merkle{4,2}_forest_ragged_anchor_openings_device_into; csrc/forest_anchor.hip) ----
+    def merkle4_forest_ragged_anchor_openings_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
+                                                     d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths,
+                                                     d_leaves_out=None, d_siblings=None, d_positions=None, d_depths=None,
+                                                     d_n_bad_anchors=None, d_n_bad=None, d_n_hashed=None):
+        """m anchors and k openings against them out of a forest merkle_forest_ragged_device built with d_levels
+        (p252_merkle4_forest_ragged_anchor_openings_device_into).  Anchor a is tree d_anchor_tree_ids[a] (int32/uint32) as it was at
+        d_anchor_counts[a] (int64/uint64) leaves: d_anchor_roots (m, 4) receives the root a fresh build of those leaves returns,
+        d_anchor_depths (m,) uint8 its depth.  Opening i is leaf d_leaf_ids[i] (int64/uint64) under anchor d_anchor_ids[i]
+        (int32/uint32), written in the layout of merkle_forest_ragged_openings_device at D = depth(max_leaves): d_leaves_out (k, 4),
+        d_siblings (k, D, 3, 4), d_positions (k, D) uint8, d_depths (k,) uint8 — what that call writes on a fresh build of the tree's
+        first c leaves, so merkle_forest_ragged_verify_device takes them with d_tree_ids = d_anchor_ids, d_roots = d_anchor_roots,
+        n_trees = m.  A bad anchor (unknown or bad tree, count 0 or above n_t): a zero root, depth 0xFF, counted in d_n_bad_anchors; a
+        bad opening (anchor id >= m, a bad anchor, leaf id >= count): zeros, depth 0xFF, counted in d_n_bad (zeroed device
+        int32/uint32, optional).  d_n_hashed (a zeroed device int64/uint64, optional) grows by the digests the anchors need.  k == 0:
+        the roots alone, the opening tensors may be None; the siblings and positions may be None when D == 0.  Asynchronous on the
+        current stream."""
+        self._forest_ragged_anchor_openings_device("merkle4_forest_ragged_anchor_openings_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees,
+                                                   max_leaves, d_levels, d_anchor_tree_ids, d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k,
+                                                   d_anchor_roots, d_anchor_depths, d_leaves_out, d_siblings, d_positions, d_depths,
+                                                   d_n_bad_anchors, d_n_bad, d_n_hashed)
+
+    def merkle2_forest_ragged_anchor_openings_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
+                                                     d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths,
+                                                     d_leaves_out=None, d_siblings=None, d_positions=None, d_depths=None,
+                                                     d_n_bad_anchors=None, d_n_bad=None, d_n_hashed=None):
+        """the same for arity 2 (d_siblings (k, D, 1, 4); pass the Merkle2 tag)"""
+        self._forest_ragged_anchor_openings_device("merkle2_forest_ragged_anchor_openings_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees,
+                                                   max_leaves, d_levels, d_anchor_tree_ids, d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k,
+                                                   d_anchor_roots, d_anchor_depths, d_leaves_out, d_siblings, d_positions, d_depths,
+                                                   d_n_bad_anchors, d_n_bad, d_n_hashed)
+
+    def _forest_ragged_anchor_openings_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
+                                              d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths, d_leaves_out,
+                                              d_siblings, d_positions, d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed):
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        self._check(a.fn("forest_ragged_anchor_openings_device_into")(
+            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
+            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
+            _dev_ptr(self, f, "d_anchor_tree_ids", d_anchor_tree_ids, m * 4, elem=4, null_ok=m == 0),
+            _dev_ptr(self, f, "d_anchor_counts", d_anchor_counts, m * 8, elem=8, null_ok=m == 0), m,
+            _dev_ptr(self, f, "d_anchor_ids", d_anchor_ids, k * 4, elem=4, null_ok=k == 0),
+            _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8, null_ok=k == 0), k,
+            _dev_ptr(self, f, "d_anchor_roots", d_anchor_roots, m * 32, null_ok=m == 0),
+            _dev_ptr(self, f, "d_anchor_depths", d_anchor_depths, m, elem=1, null_ok=m == 0),
+            _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32, null_ok=k == 0),
+            _dev_ptr(self, f, "d_siblings", d_siblings, k * depth * a.per * 32, null_ok=k == 0 or depth == 0),
+            _dev_ptr(self, f, "d_positions", d_positions, k * depth, elem=1, null_ok=k == 0 or depth == 0),
+            _dev_ptr(self, f, "d_depths", d_depths, k, elem=1, null_ok=k == 0),
+            _dev_ptr(self, f, "d_n_bad_anchors", d_n_bad_anchors, 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
+
     # ---- the shared proof across a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_*; csrc/forest_multiproof.hip) ----
     def merkle4_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
         """upper bound, in scalars, of the shared proof of k pairs of a ragged forest (p252_merkle4_forest_ragged_multiproof_bound)"""

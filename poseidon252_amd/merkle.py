@@ -461,6 +461,42 @@ def forest_consistency_verify(ctx, d_old_counts, d_old_roots, d_new_counts, d_ne
     return ok, old_out, new_out, n_hashed
 
 
+def forest_ragged_anchor_openings(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, anchor_tree_ids, anchor_counts, anchor_ids,
+                                  leaf_ids, arity=4):
+    """Roots and openings of the trees of a built ragged forest as they WERE at earlier leaf counts
+    (Context.merkle{4,2}_forest_ragged_anchor_openings_device): anchor a is tree anchor_tree_ids[a] at anchor_counts[a] leaves, opening i
+    is leaf leaf_ids[i] under anchor anchor_ids[i] (sequences, numpy or torch; empty leaf_ids: the roots alone).  tag = None: the arity's
+    own.  Returns (d_anchor_roots (m, 4), d_anchor_depths (m,) uint8, openings, (d_n_bad_anchors, d_n_bad) (1,) int32 each, d_n_hashed
+    (1,) int64), all on the device, with openings = (d_leaves_out (k, 4), d_siblings (k, D, arity - 1, 4), d_positions (k, D) uint8,
+    d_depths (k,) uint8, D): merkle_forest_ragged_verify_device(tag, *openings, d_anchor_ids, d_anchor_roots, m, d_ok, k) takes it as it
+    stands, and so does merkle_path_ragged_device.  No synchronisation."""
+    import torch
+    a = _arity("forest_ragged_anchor_openings", arity)
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    ids = lambda x, dtype: (x if _is_torch(x) else torch.from_numpy(np.asarray(x).astype(np.int64))).to(device=dev, dtype=dtype).contiguous()  # noqa: E731
+    at, ac = ids(anchor_tree_ids, torch.int32), ids(anchor_counts, torch.int64)
+    oa, ol = ids(anchor_ids, torch.int32), ids(leaf_ids, torch.int64)
+    m, k = at.numel(), oa.numel()
+    if ac.numel() != m or ol.numel() != k:
+        raise ValueError("forest_ragged_anchor_openings: %d anchor trees, %d counts; %d anchor ids, %d leaf ids" % (m, ac.numel(), k, ol.numel()))
+    D = a.depth(max_leaves)
+    roots = torch.zeros((m, 4), dtype=torch.int64, device=dev)
+    depths = torch.full((m,), 0xFF, dtype=torch.uint8, device=dev)
+    lv = torch.zeros((k, 4), dtype=torch.int64, device=dev)
+    sib = torch.zeros((k, D, a.per, 4), dtype=torch.int64, device=dev)
+    pos = torch.zeros((k, D), dtype=torch.uint8, device=dev)
+    dep = torch.full((k,), 0xFF, dtype=torch.uint8, device=dev)
+    bad_anchors, bad = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
+    call = ctx.merkle4_forest_ragged_anchor_openings_device if arity == 4 else ctx.merkle2_forest_ragged_anchor_openings_device
+    if m or k:
+        call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if D else None,
+             at if m else None, ac if m else None, m, oa if k else None, ol if k else None, k, roots if m else None, depths if m else None,
+             lv if k else None, sib if k and D else None, pos if k and D else None, dep if k else None, bad_anchors, bad, n_hashed)
+    return roots, depths, (lv, sib, pos, dep, D), (bad_anchors, bad), n_hashed
+
+
 def merkle_multiproof(d_leaves, d_levels, indices, arity=4, ctx=None):
     """One shared proof for many leaves of ONE stored tree (Context.merkle_multiproof_device): d_leaves / d_levels = torch CUDA tensors
     as merkle4_tree(..., want_levels=True) fills them, indices = leaf positions in any order (a sequence, numpy or torch); they are
