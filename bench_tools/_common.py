@@ -114,12 +114,12 @@ class Case:
         self.b_leaves, self.b_lv, self.b_roots = new()
         self.a_off = torch.zeros(self.T + 1, dtype=torch.int64, device=device)
         self.hashed = torch.zeros(1, dtype=torch.int64, device=device)
-        self.call = ctx.merkle4_forest_ragged_append_device if arity == 4 else ctx.merkle2_forest_ragged_append_device
         self.bytes_moved = None
 
     def append(self, count=False):
-        self.call(self.tag, self.d, self.d_off, self.T, self.max_old, self.lv, self.d_add, self.d_aoff, self.T, self.max_new, self.a_leaves, self.a_off,
-                  self.a_lv, self.a_roots, None, self.hashed if count else None)
+        self.ctx.merkle_forest_ragged_append_device(self.tag, self.d, self.d_off, self.T, self.max_old, self.lv, self.d_add, self.d_aoff, self.T,
+                                                    self.max_new, self.a_leaves, self.a_off, self.a_lv, self.a_roots, None,
+                                                    self.hashed if count else None, arity=self.arity)
 
     def rebuild(self):
         """the fresh build of the new forest, from the append's own leaves and offsets"""

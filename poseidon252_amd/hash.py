@@ -11,6 +11,7 @@ Scalars are numpy uint64 arrays whose last axis is the 4 little-endian limbs of 
 """
 import ctypes
 import enum
+import inspect
 
 import numpy as np
 
@@ -488,6 +489,16 @@ class Context:
                        _dev_ptr(self, f, "d_levels", d_levels, need, null_ok=True),
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
+    def _built_forest(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels):
+        """the six leading C arguments of a call that takes a forest merkle_forest_ragged_device built with d_levels (leaves, n_leaves,
+        offsets, n_trees, max_leaves, levels), and depth(max_leaves): d_levels must hold the build's bound, None only at depth 0"""
+        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
+        n_leaves = _n_scalars(d_leaves)
+        depth = a.depth(max_leaves)
+        offsets = _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8)
+        levels = _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0)
+        return (leaves, n_leaves, offsets, n_trees, max_leaves, levels), depth
+
     def merkle_forest_ragged_openings_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
                                              out=None, d_n_bad=None, arity=4):
         """openings out of a forest merkle_forest_ragged_device built with d_levels (p252_merkle{4,2}_forest_ragged_openings_device):
@@ -499,11 +510,7 @@ class Context:
         import torch
         f = "merkle_forest_ragged_openings_device"
         a = _arity(f, arity)
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
-        offsets = _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8)
-        levels = _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0)
+        forest, depth = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         tree_ids = _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4)
         leaf_ids = _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8)
         if out is not None:
@@ -515,7 +522,7 @@ class Context:
             pos = torch.empty((k, depth), dtype=torch.uint8, device=dev)
             dep = torch.empty((k,), dtype=torch.uint8, device=dev)
         self._check(a.fn("forest_ragged_openings_device")(
-            self._h, leaves, n_leaves, offsets, n_trees, max_leaves, levels, tree_ids, leaf_ids, k,
+            self._h, *forest, tree_ids, leaf_ids, k,
             _dev_ptr(self, f, "d_leaves_out", lv, k * 32), _dev_ptr(self, f, "d_siblings", sib, k * depth * 32 * a.per) if depth else None,
             _dev_ptr(self, f, "d_positions", pos, k * depth, elem=1) if depth else None, _dev_ptr(self, f, "d_depths", dep, k, elem=1),
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
@@ -562,59 +569,36 @@ class Context:
         d_n_hashed (a zeroed device int64/uint64, optional) grows by the number of digests computed."""
         f = "merkle_forest_ragged_update_device"
         a = _arity(f, arity)
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
+        forest, _ = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         self._check(a.fn("forest_ragged_update_device")(
-            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
+            self._h, _tag(tag), *forest, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
+            _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
             _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32), k, _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
     # ---- the update with a journal, and the swap that undoes and redoes it (p252_merkle{4,2}_forest_ragged_journal_*, _update_journaled_device_into;
     # csrc/forest_journal.hip) ----
-    def merkle4_forest_ragged_journal_bound(self, n_leaves, n_trees, max_leaves, k):
-        """the most journal entries one journaled update of k leaves writes (p252_merkle4_forest_ragged_journal_bound): the capacity
-        merkle4_forest_ragged_update_journaled_device asks of its journal"""
-        return int(_ARITIES[4].fn("forest_ragged_journal_bound")(n_leaves, n_trees, max_leaves, k))
+    def merkle_forest_ragged_journal_bound(self, n_leaves, n_trees, max_leaves, k, arity=4):
+        """the most journal entries one journaled update of k leaves writes (p252_merkle{4,2}_forest_ragged_journal_bound): the capacity
+        merkle_forest_ragged_update_journaled_device asks of its journal"""
+        return int(_arity("merkle_forest_ragged_journal_bound", arity).fn("forest_ragged_journal_bound")(n_leaves, n_trees, max_leaves, k))
 
-    def merkle2_forest_ragged_journal_bound(self, n_leaves, n_trees, max_leaves, k):
-        """the same for arity 2"""
-        return int(_ARITIES[2].fn("forest_ragged_journal_bound")(n_leaves, n_trees, max_leaves, k))
-
-    def merkle4_forest_ragged_update_journaled_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
-                                                      d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len,
-                                                      d_roots=None, d_n_bad=None, d_n_hashed=None):
+    def merkle_forest_ragged_update_journaled_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                                     d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len,
+                                                     d_roots=None, d_n_bad=None, d_n_hashed=None, arity=4):
         """merkle_forest_ragged_update_device keeping a journal of every leaf and node it overwrites
-        (p252_merkle4_forest_ragged_update_journaled_device_into): the update's arguments with its meaning, except that of a (tree, leaf) pair
-        given several times exactly one update is applied, whole, and the others are dropped without a count.  The journal is the
-        caller's: d_journal_ids (journal_cap x 4 int32/uint32), d_journal_values (journal_cap scalars), d_journal_len (one device
-        int64/uint64, set by the call); journal_cap >= merkle4_forest_ragged_journal_bound(..), else the library refuses the call.
-        merkle4_forest_ragged_journal_swap_device plays it back."""
-        self._forest_ragged_update_journaled_device("merkle4_forest_ragged_update_journaled_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees,
-                                                    max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves, k, d_journal_ids, d_journal_values,
-                                                    journal_cap, d_journal_len, d_roots, d_n_bad, d_n_hashed)
-
-    def merkle2_forest_ragged_update_journaled_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
-                                                      d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len,
-                                                      d_roots=None, d_n_bad=None, d_n_hashed=None):
-        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
-        self._forest_ragged_update_journaled_device("merkle2_forest_ragged_update_journaled_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees,
-                                                    max_leaves, d_levels, d_tree_ids, d_leaf_ids, d_new_leaves, k, d_journal_ids, d_journal_values,
-                                                    journal_cap, d_journal_len, d_roots, d_n_bad, d_n_hashed)
-
-    def _forest_ragged_update_journaled_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
-                                               d_new_leaves, k, d_journal_ids, d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad,
-                                               d_n_hashed):
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
+        (p252_merkle{4,2}_forest_ragged_update_journaled_device_into; pass the tag of that arity): the update's arguments with its
+        meaning, except that of a (tree, leaf) pair given several times exactly one update is applied, whole, and the others are dropped
+        without a count.  The journal is the caller's: d_journal_ids (journal_cap x 4 int32/uint32), d_journal_values (journal_cap
+        scalars), d_journal_len (one device int64/uint64, set by the call); journal_cap >= merkle_forest_ragged_journal_bound(..), else
+        the library refuses the call.  merkle_forest_ragged_journal_swap_device plays it back."""
+        f = "merkle_forest_ragged_update_journaled_device"
+        a = _arity(f, arity)
+        forest, _ = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         self._check(a.fn("forest_ragged_update_journaled_device_into")(
-            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
+            self._h, _tag(tag), *forest, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
+            _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
             _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32), k, _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
@@ -622,81 +606,54 @@ class Context:
             _dev_ptr(self, f, "d_journal_values", d_journal_values, journal_cap * 32, null_ok=journal_cap == 0), journal_cap,
             _dev_ptr(self, f, "d_journal_len", d_journal_len, 8, elem=8), _stream(self)))
 
-    def merkle4_forest_ragged_journal_swap_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
-                                                  journal_cap, d_journal_len, d_roots=None, d_n_bad=None):
-        """the journal of merkle4_forest_ragged_update_journaled_device played back (p252_merkle4_forest_ragged_journal_swap_device_into; no
-        tag, nothing is hashed): each of the first min(d_journal_len, journal_cap) entries changes places with the node it names, so
+    def merkle_forest_ragged_journal_swap_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
+                                                 journal_cap, d_journal_len, d_roots=None, d_n_bad=None, arity=4):
+        """the journal of merkle_forest_ragged_update_journaled_device played back (p252_merkle{4,2}_forest_ragged_journal_swap_device_into;
+        no tag, nothing is hashed): each of the first min(d_journal_len, journal_cap) entries changes places with the node it names, so
         one call undoes the update byte for byte and a second one redoes it; d_roots (n_trees, 4; optional) follows for the touched
         trees.  The forest arguments exactly as the update took them — a journal is void on any other shape.  An entry that names no
         node of this forest writes nothing and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
-        self._forest_ragged_journal_swap_device("merkle4_forest_ragged_journal_swap_device", _ARITIES[4], d_leaves, d_offsets, n_trees, max_leaves,
-                                                d_levels, d_journal_ids, d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad)
-
-    def merkle2_forest_ragged_journal_swap_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
-                                                  journal_cap, d_journal_len, d_roots=None, d_n_bad=None):
-        """the same for arity 2"""
-        self._forest_ragged_journal_swap_device("merkle2_forest_ragged_journal_swap_device", _ARITIES[2], d_leaves, d_offsets, n_trees, max_leaves,
-                                                d_levels, d_journal_ids, d_journal_values, journal_cap, d_journal_len, d_roots, d_n_bad)
-
-    def _forest_ragged_journal_swap_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_journal_ids, d_journal_values,
-                                           journal_cap, d_journal_len, d_roots, d_n_bad):
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
+        f = "merkle_forest_ragged_journal_swap_device"
+        a = _arity(f, arity)
+        forest, _ = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         self._check(a.fn("forest_ragged_journal_swap_device_into")(
-            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_journal_ids", d_journal_ids, journal_cap * 16, elem=4, null_ok=journal_cap == 0),
+            self._h, *forest, _dev_ptr(self, f, "d_journal_ids", d_journal_ids, journal_cap * 16, elem=4, null_ok=journal_cap == 0),
             _dev_ptr(self, f, "d_journal_values", d_journal_values, journal_cap * 32, null_ok=journal_cap == 0), journal_cap,
             _dev_ptr(self, f, "d_journal_len", d_journal_len, 8, elem=8), _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
-    def merkle4_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
-                                            max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None):
+    def merkle_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
+                                           max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None,
+                                           arity=4):
         """leaves appended to the trees of a forest merkle_forest_ragged_device built with d_levels, written INTO a new compact forest
-        (p252_merkle4_forest_ragged_append_device_into): d_leaves, d_offsets, n_trees, max_leaves, d_levels exactly as the build took
-        them (read-only; None when n_trees == 0); tree t of the n_trees_new >= n_trees new trees receives
+        (p252_merkle{4,2}_forest_ragged_append_device_into; pass the tag of that arity): d_leaves, d_offsets, n_trees, max_leaves, d_levels
+        exactly as the build took them (read-only; None when n_trees == 0); tree t of the n_trees_new >= n_trees new trees receives
         d_add[d_add_offsets[t]:d_add_offsets[t+1]] (n_trees_new + 1 int64/uint64; d_add None: a compaction copy).  Written: d_leaves_new
         (its length is the capacity, at least the old leaves plus d_add), d_offsets_new (n_trees_new + 1), d_levels_new (the bound of
         merkle_forest_ragged_device for the new shape), d_roots (n_trees_new, 4) — byte for byte a fresh build of the new forest,
         with the unchanged nodes moved and only the others hashed.  A refused append or an empty new tree is counted in d_n_bad (a
         zeroed device int32/uint32, optional); d_n_hashed (a zeroed device int64/uint64, optional) receives the digests computed."""
-        self._forest_ragged_append_device("merkle4_forest_ragged_append_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees, max_leaves,
-                                          d_levels, None, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
-                                          d_levels_new, d_roots, d_n_bad, d_n_hashed)
+        self._forest_ragged_regrow("merkle_forest_ragged_append_device", arity, False, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels,
+                                   None, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots,
+                                   d_n_bad, d_n_hashed)
 
-    def merkle2_forest_ragged_append_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new,
-                                            max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None, d_n_hashed=None):
-        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
-        self._forest_ragged_append_device("merkle2_forest_ragged_append_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees, max_leaves,
-                                          d_levels, None, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
-                                          d_levels_new, d_roots, d_n_bad, d_n_hashed)
+    def merkle_forest_ragged_resize_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+                                           n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None,
+                                           d_n_hashed=None, arity=4):
+        """such a forest rolled back and forward in one call (p252_merkle{4,2}_forest_ragged_resize_device_into; pass the tag of that
+        arity): the append above after tree t was cut to its first min(d_keep[t], n_t) leaves.  d_keep = n_trees_new int64/uint64 on the
+        device (-1, i.e. UINT64_MAX, or any value >= n_t keeps the tree whole; None keeps every tree whole).  n_trees_new may be smaller
+        than n_trees: the trailing trees are dropped.  d_add None: a pure rollback, at most one node per tree and level hashed.  A refused
+        append still leaves its tree cut.  Everything else, the sizes of the outputs included, as merkle_forest_ragged_append_device."""
+        self._forest_ragged_regrow("merkle_forest_ragged_resize_device", arity, True, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels,
+                                   d_keep, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots,
+                                   d_n_bad, d_n_hashed)
 
-    def merkle4_forest_ragged_resize_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
-                                            n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None,
-                                            d_n_hashed=None):
-        """such a forest rolled back and forward in one call (p252_merkle4_forest_ragged_resize_device_into): the append above after
-        tree t was cut to its first min(d_keep[t], n_t) leaves.  d_keep = n_trees_new int64/uint64 on the device (-1, i.e. UINT64_MAX,
-        or any value >= n_t keeps the tree whole; None keeps every tree whole).  n_trees_new may be smaller than n_trees: the
-        trailing trees are dropped.  d_add None: a pure rollback, at most one node per tree and level hashed.  A refused append
-        still leaves its tree cut.  Everything else, the sizes of the outputs included, as merkle4_forest_ragged_append_device."""
-        self._forest_ragged_append_device("merkle4_forest_ragged_resize_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees, max_leaves,
-                                          d_levels, d_keep, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
-                                          d_levels_new, d_roots, d_n_bad, d_n_hashed, stem="forest_ragged_resize_device_into")
-
-    def merkle2_forest_ragged_resize_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
-                                            n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad=None,
-                                            d_n_hashed=None):
-        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
-        self._forest_ragged_append_device("merkle2_forest_ragged_resize_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees, max_leaves,
-                                          d_levels, d_keep, d_add, d_add_offsets, n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new,
-                                          d_levels_new, d_roots, d_n_bad, d_n_hashed, stem="forest_ragged_resize_device_into")
-
-    def _forest_ragged_append_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
-                                     n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed,
-                                     stem="forest_ragged_append_device_into"):
+    def _forest_ragged_regrow(self, f, arity, resize, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+                              n_trees_new, max_leaves_new, d_leaves_new, d_offsets_new, d_levels_new, d_roots, d_n_bad, d_n_hashed):
         """the append and the resize: one set of checks; the resize's C call takes d_keep after d_levels"""
-        resize = stem == "forest_ragged_resize_device_into"
+        a = _arity(f, arity)
+        stem = "forest_ragged_resize_device_into" if resize else "forest_ragged_append_device_into"
         keep = (_dev_ptr(self, f, "d_keep", d_keep, n_trees_new * 8, elem=8, null_ok=True),) if resize else ()
         none = n_trees == 0  # no old forest
         leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 0, null_ok=none)
@@ -717,27 +674,19 @@ class Context:
             _dev_ptr(self, f, "d_roots", d_roots, n_trees_new * 32), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
-    def merkle4_forest_ragged_select_device(self, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
-                                            d_n_bad=None):
+    def merkle_forest_ragged_select_device(self, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
+                                           d_n_bad=None, arity=4):
         """any trees of one or two built forests gathered INTO a new compact forest, with no digest
-        (p252_merkle4_forest_ragged_select_device_into).  forest_a, forest_b = (d_leaves, d_offsets, n_trees, max_leaves, d_levels,
-        d_roots), each exactly what merkle_forest_ragged_device took and filled (read-only); forest_b may be None.  d_pick = n_pick
-        int64/uint64 ids on the device: below n_trees_a a tree of A, then a tree of B; any order, repeats allowed.  Written:
-        d_leaves_new (its length is leaves_cap), d_offsets_new (n_pick + 1), d_levels_new (at least the bound of
-        merkle_forest_ragged_device for leaves_cap leaves, n_pick trees and the larger max_leaves), d_roots_new (n_pick, 4) — byte
-        for byte a fresh build of the new forest.  A pick out of range, of a bad tree, or past leaves_cap (and every non-empty one
-        after it) becomes an empty tree and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
-        self._forest_ragged_select_device("merkle4_forest_ragged_select_device", _ARITIES[4], forest_a, forest_b, d_pick, n_pick, d_leaves_new,
-                                          d_offsets_new, d_levels_new, d_roots_new, d_n_bad)
+        (p252_merkle{4,2}_forest_ragged_select_device_into; arity 2: the level layout of merkle2 trees).  forest_a, forest_b =
+        (d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots), each exactly what merkle_forest_ragged_device took and filled
+        (read-only); forest_b may be None.  d_pick = n_pick int64/uint64 ids on the device: below n_trees_a a tree of A, then a tree of B;
+        any order, repeats allowed.  Written: d_leaves_new (its length is leaves_cap), d_offsets_new (n_pick + 1), d_levels_new (at least
+        the bound of merkle_forest_ragged_device for leaves_cap leaves, n_pick trees and the larger max_leaves), d_roots_new (n_pick, 4)
+        — byte for byte a fresh build of the new forest.  A pick out of range, of a bad tree, or past leaves_cap (and every non-empty
+        one after it) becomes an empty tree and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
+        f = "merkle_forest_ragged_select_device"
+        a = _arity(f, arity)
 
-    def merkle2_forest_ragged_select_device(self, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
-                                            d_n_bad=None):
-        """the same for arity 2 (the level layout of merkle2 trees)"""
-        self._forest_ragged_select_device("merkle2_forest_ragged_select_device", _ARITIES[2], forest_a, forest_b, d_pick, n_pick, d_leaves_new,
-                                          d_offsets_new, d_levels_new, d_roots_new, d_n_bad)
-
-    def _forest_ragged_select_device(self, f, a, forest_a, forest_b, d_pick, n_pick, d_leaves_new, d_offsets_new, d_levels_new, d_roots_new,
-                                     d_n_bad):
         def source(which, forest):
             """the seven C arguments of one source forest, and its byte ranges"""
             if forest is None:
@@ -906,34 +855,21 @@ class Context:
                        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
     # ---- a forest kept only as its frontiers (p252_merkle{4,2}_forest_frontier_*; csrc/forest_frontier.hip) ----
-    def merkle4_forest_frontier_bound(self, max_leaves):
-        """scalars of one tree's frontier, (depth(max_leaves) + 1) * 3 (p252_merkle4_forest_frontier_bound)"""
-        return int(_ARITIES[4].fn("forest_frontier_bound")(max_leaves))
+    def merkle_forest_frontier_bound(self, max_leaves, arity=4):
+        """scalars of one tree's frontier, (depth(max_leaves) + 1) * (arity - 1) (p252_merkle{4,2}_forest_frontier_bound)"""
+        return int(_arity("merkle_forest_frontier_bound", arity).fn("forest_frontier_bound")(max_leaves))
 
-    def merkle2_forest_frontier_bound(self, max_leaves):
-        """the same for arity 2: depth(max_leaves) + 1"""
-        return int(_ARITIES[2].fn("forest_frontier_bound")(max_leaves))
-
-    def merkle4_forest_frontier_append_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
-                                              d_n_bad=None, d_n_hashed=None):
+    def merkle_forest_frontier_append_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                             d_n_bad=None, d_n_hashed=None, arity=4):
         """leaves appended to n_trees trees that are kept only as their frontiers, IN PLACE
-        (p252_merkle4_forest_frontier_append_device_into): d_counts (n_trees int64/uint64), d_frontier (n_trees x
-        merkle4_forest_frontier_bound(max_leaves) scalars) and d_roots (n_trees, 4) are the state — all zero for empty trees; tree t
-        receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (n_trees + 1 int64/uint64; d_add None: nothing appended).  Afterwards
+        (p252_merkle{4,2}_forest_frontier_append_device_into; pass the tag of that arity): d_counts (n_trees int64/uint64), d_frontier
+        (n_trees x merkle_forest_frontier_bound(max_leaves) scalars) and d_roots (n_trees, 4) are the state — all zero for empty trees;
+        tree t receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (n_trees + 1 int64/uint64; d_add None: nothing appended).  Afterwards
         d_roots[t] is the root of all leaves tree t was ever given.  A refused append leaves its tree untouched and is counted in
         d_n_bad (a zeroed device int32/uint32, optional); d_n_hashed (a zeroed device int64/uint64, optional) receives the digests
         computed.  Asynchronous on the current stream."""
-        self._forest_frontier_append_device("merkle4_forest_frontier_append_device", _ARITIES[4], tag, d_counts, d_frontier, d_roots, n_trees,
-                                            max_leaves, d_add, d_add_offsets, d_n_bad, d_n_hashed)
-
-    def merkle2_forest_frontier_append_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
-                                              d_n_bad=None, d_n_hashed=None):
-        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
-        self._forest_frontier_append_device("merkle2_forest_frontier_append_device", _ARITIES[2], tag, d_counts, d_frontier, d_roots, n_trees,
-                                            max_leaves, d_add, d_add_offsets, d_n_bad, d_n_hashed)
-
-    def _forest_frontier_append_device(self, f, a, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets, d_n_bad,
-                                       d_n_hashed):
+        f = "merkle_forest_frontier_append_device"
+        a = _arity(f, arity)
         stride = (a.depth(max_leaves) + 1) * a.per if max_leaves else 0  # p252_merkle{4,2}_forest_frontier_bound
         self._check(a.fn("forest_frontier_append_device_into")(
             self._h, _tag(tag), _dev_ptr(self, f, "d_counts", d_counts, n_trees * 8, elem=8),
@@ -943,32 +879,19 @@ class Context:
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
             _stream(self)))
 
-    def merkle4_forest_frontier_append_witness_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
-                                                      d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions,
-                                                      d_wit_depths, d_n_bad=None, d_n_hashed=None, d_n_bad_witness=None):
-        """merkle4_forest_frontier_append_device keeping the openings of k marked leaves current, IN PLACE
-        (p252_merkle4_forest_frontier_append_witness_device_into): witness i names leaf d_wit_leaf_ids[i] (int64/uint64) of tree
-        d_wit_tree_ids[i] (int32/uint32); d_wit_leaves (k, 4), d_wit_siblings (k, D, 3, 4), d_wit_positions (k, D) uint8 and
-        d_wit_depths (k,) uint8 with D = depth(max_leaves) are what merkle_forest_ragged_openings_device writes at that stride.  A
-        witness of a leaf below the tree's old count must be its opening at that count and becomes its opening in the grown tree; one
-        of a leaf this call appends is written whole; one that names no leaf becomes all zero with depth 0xFF and is counted in
+    def merkle_forest_frontier_append_witness_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
+                                                     d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions,
+                                                     d_wit_depths, d_n_bad=None, d_n_hashed=None, d_n_bad_witness=None, arity=4):
+        """merkle_forest_frontier_append_device keeping the openings of k marked leaves current, IN PLACE
+        (p252_merkle{4,2}_forest_frontier_append_witness_device_into; pass the tag of that arity): witness i names leaf d_wit_leaf_ids[i]
+        (int64/uint64) of tree d_wit_tree_ids[i] (int32/uint32); d_wit_leaves (k, 4), d_wit_siblings (k, D, arity-1, 4), d_wit_positions
+        (k, D) uint8 and d_wit_depths (k,) uint8 with D = depth(max_leaves) are what merkle_forest_ragged_openings_device writes at that
+        stride.  A witness of a leaf below the tree's old count must be its opening at that count and becomes its opening in the grown
+        tree; one of a leaf this call appends is written whole; one that names no leaf becomes all zero with depth 0xFF and is counted in
         d_n_bad_witness (a zeroed device int32/uint32, optional).  The siblings and positions may be None when D == 0.  Every good
         witness verifies against d_roots (merkle_forest_ragged_verify_device).  Asynchronous on the current stream."""
-        self._forest_frontier_append_witness_device("merkle4_forest_frontier_append_witness_device", _ARITIES[4], tag, d_counts, d_frontier, d_roots,
-                                                    n_trees, max_leaves, d_add, d_add_offsets, d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves,
-                                                    d_wit_siblings, d_wit_positions, d_wit_depths, d_n_bad, d_n_hashed, d_n_bad_witness)
-
-    def merkle2_forest_frontier_append_witness_device(self, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
-                                                      d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions,
-                                                      d_wit_depths, d_n_bad=None, d_n_hashed=None, d_n_bad_witness=None):
-        """the same for arity 2 (d_wit_siblings (k, D, 1, 4); pass the Merkle2 tag)"""
-        self._forest_frontier_append_witness_device("merkle2_forest_frontier_append_witness_device", _ARITIES[2], tag, d_counts, d_frontier, d_roots,
-                                                    n_trees, max_leaves, d_add, d_add_offsets, d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves,
-                                                    d_wit_siblings, d_wit_positions, d_wit_depths, d_n_bad, d_n_hashed, d_n_bad_witness)
-
-    def _forest_frontier_append_witness_device(self, f, a, tag, d_counts, d_frontier, d_roots, n_trees, max_leaves, d_add, d_add_offsets,
-                                               d_wit_tree_ids, d_wit_leaf_ids, k, d_wit_leaves, d_wit_siblings, d_wit_positions, d_wit_depths,
-                                               d_n_bad, d_n_hashed, d_n_bad_witness):
+        f = "merkle_forest_frontier_append_witness_device"
+        a = _arity(f, arity)
         depth = a.depth(max_leaves)
         stride = (depth + 1) * a.per if max_leaves else 0  # p252_merkle{4,2}_forest_frontier_bound
         none = k == 0  # (the plain call: no witness buffer is looked at)
@@ -986,95 +909,56 @@ class Context:
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
             _dev_ptr(self, f, "d_n_bad_witness", d_n_bad_witness, 4, elem=4, null_ok=True), _stream(self)))
 
-    def merkle4_forest_frontier_extract_device(self, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
-                                               d_counts, d_frontier, d_roots, d_n_bad=None):
-        """the frontier state of a forest merkle_forest_ragged_device built with d_levels (p252_merkle4_forest_frontier_extract_device_into;
-        no hashing): d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest exactly as the build took and filled them;
-        writes d_counts (n_trees), d_frontier (n_trees x merkle4_forest_frontier_bound(max_leaves), max_leaves >= max_leaves_forest) and
-        d_roots (n_trees, 4).  A bad tree becomes an empty one and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
-        self._forest_frontier_extract_device("merkle4_forest_frontier_extract_device", _ARITIES[4], d_leaves, d_offsets, n_trees,
-                                             max_leaves_forest, d_levels, d_roots_forest, max_leaves, d_counts, d_frontier, d_roots, d_n_bad)
-
-    def merkle2_forest_frontier_extract_device(self, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
-                                               d_counts, d_frontier, d_roots, d_n_bad=None):
-        """the same for arity 2"""
-        self._forest_frontier_extract_device("merkle2_forest_frontier_extract_device", _ARITIES[2], d_leaves, d_offsets, n_trees,
-                                             max_leaves_forest, d_levels, d_roots_forest, max_leaves, d_counts, d_frontier, d_roots, d_n_bad)
-
-    def _forest_frontier_extract_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
-                                        d_counts, d_frontier, d_roots, d_n_bad):
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves_forest)
+    def merkle_forest_frontier_extract_device(self, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots_forest, max_leaves,
+                                              d_counts, d_frontier, d_roots, d_n_bad=None, arity=4):
+        """the frontier state of a forest merkle_forest_ragged_device built with d_levels
+        (p252_merkle{4,2}_forest_frontier_extract_device_into; no hashing): d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels,
+        d_roots_forest exactly as the build took and filled them; writes d_counts (n_trees), d_frontier (n_trees x
+        merkle_forest_frontier_bound(max_leaves), max_leaves >= max_leaves_forest) and d_roots (n_trees, 4).  A bad tree becomes an empty
+        one and is counted in d_n_bad (a zeroed device int32/uint32, optional)."""
+        f = "merkle_forest_frontier_extract_device"
+        a = _arity(f, arity)
+        forest, _ = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels)
         stride = (a.depth(max_leaves) + 1) * a.per if max_leaves else 0  # p252_merkle{4,2}_forest_frontier_bound
         self._check(a.fn("forest_frontier_extract_device_into")(
-            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves_forest,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_roots_forest", d_roots_forest, n_trees * 32), max_leaves,
+            self._h, *forest, _dev_ptr(self, f, "d_roots_forest", d_roots_forest, n_trees * 32), max_leaves,
             _dev_ptr(self, f, "d_counts", d_counts, n_trees * 8, elem=8), _dev_ptr(self, f, "d_frontier", d_frontier, n_trees * stride * 32),
             _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
     # ---- consistency proofs: a grown tree extends its old root (p252_merkle{4,2}_forest_ragged_consistency_device_into,
     # _forest_consistency_verify_device_into; csrc/forest_consistency.hip) ----
-    def merkle4_forest_ragged_consistency_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
-                                                 d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad=None):
+    def merkle_forest_ragged_consistency_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
+                                                d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad=None, arity=4):
         """k consistency proofs out of a forest merkle_forest_ragged_device built with d_levels
-        (p252_merkle4_forest_ragged_consistency_device_into; no hashing): proof i shows that tree d_tree_ids[i] (int32/uint32), now of
+        (p252_merkle{4,2}_forest_ragged_consistency_device_into; no hashing): proof i shows that tree d_tree_ids[i] (int32/uint32), now of
         n_t leaves, is the tree it was at d_old_counts[i] (int64/uint64) leaves with leaves appended.  It is the opening of leaf index
         n of the tree, in the layout merkle_forest_ragged_openings_device writes at D = depth(max_leaves): d_leaves_out (k, 4),
-        d_siblings (k, D, 3, 4), d_positions (k, D) uint8, d_depths (k,) uint8; d_new_counts_out (k,) receives n_t.  n == n_t: all
+        d_siblings (k, D, arity-1, 4), d_positions (k, D) uint8, d_depths (k,) uint8; d_new_counts_out (k,) receives n_t.  n == n_t: all
         zero with the depth of n_t.  A tree id out of range, a bad tree, n == 0 or n > n_t: all zero, depth 0xFF, new count 0, counted
         in d_n_bad (a zeroed device int32/uint32, optional).  The siblings and positions may be None when D == 0."""
-        self._forest_ragged_consistency_device("merkle4_forest_ragged_consistency_device", _ARITIES[4], d_leaves, d_offsets, n_trees, max_leaves,
-                                               d_levels, d_tree_ids, d_old_counts, k, d_new_counts_out, d_leaves_out, d_siblings, d_positions,
-                                               d_depths, d_n_bad)
-
-    def merkle2_forest_ragged_consistency_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
-                                                 d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad=None):
-        """the same for arity 2 (d_siblings (k, D, 1, 4))"""
-        self._forest_ragged_consistency_device("merkle2_forest_ragged_consistency_device", _ARITIES[2], d_leaves, d_offsets, n_trees, max_leaves,
-                                               d_levels, d_tree_ids, d_old_counts, k, d_new_counts_out, d_leaves_out, d_siblings, d_positions,
-                                               d_depths, d_n_bad)
-
-    def _forest_ragged_consistency_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_old_counts, k,
-                                          d_new_counts_out, d_leaves_out, d_siblings, d_positions, d_depths, d_n_bad):
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
+        f = "merkle_forest_ragged_consistency_device"
+        a = _arity(f, arity)
+        forest, depth = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         self._check(a.fn("forest_ragged_consistency_device_into")(
-            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_old_counts", d_old_counts, k * 8, elem=8), k,
+            self._h, *forest, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
+            _dev_ptr(self, f, "d_old_counts", d_old_counts, k * 8, elem=8), k,
             _dev_ptr(self, f, "d_new_counts_out", d_new_counts_out, k * 8, elem=8), _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32),
             _dev_ptr(self, f, "d_siblings", d_siblings, k * depth * a.per * 32, null_ok=depth == 0),
             _dev_ptr(self, f, "d_positions", d_positions, k * depth, elem=1, null_ok=depth == 0),
             _dev_ptr(self, f, "d_depths", d_depths, k, elem=1), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
-    def merkle4_forest_consistency_verify_device(self, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
-                                                 d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids=None, n_trees=0,
-                                                 d_old_roots_out=None, d_new_roots_out=None, d_n_hashed=None):
-        """k consistency proofs checked against their claims (p252_merkle4_forest_consistency_verify_device_into): d_ok[i] (uint8) = 1
-        iff the opening i (the layout above, at stride_depth rows) re-hashes to the new root and its left siblings alone to the old
-        root, with its slots the digits of the old count.  Without d_tree_ids claim i is element i of d_old_counts, d_old_roots,
-        d_new_counts, d_new_roots (k entries each); with d_tree_ids (int32/uint32) they hold n_trees entries and claim i is element
-        d_tree_ids[i] — so the counts and roots of a ForestFrontier are the old claims as they stand.  d_old_roots_out /
-        d_new_roots_out (k, 4; optional) receive the recomputed roots, d_n_hashed (a zeroed device int64/uint64, optional) grows by
-        the digests computed.  Asynchronous on the current stream."""
-        self._forest_consistency_verify_device("merkle4_forest_consistency_verify_device", _ARITIES[4], tag, d_old_counts, d_old_roots, d_new_counts,
-                                               d_new_roots, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids, n_trees,
-                                               d_old_roots_out, d_new_roots_out, d_n_hashed)
-
-    def merkle2_forest_consistency_verify_device(self, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
-                                                 d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids=None, n_trees=0,
-                                                 d_old_roots_out=None, d_new_roots_out=None, d_n_hashed=None):
-        """the same for arity 2 (pass the Merkle2 tag)"""
-        self._forest_consistency_verify_device("merkle2_forest_consistency_verify_device", _ARITIES[2], tag, d_old_counts, d_old_roots, d_new_counts,
-                                               d_new_roots, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids, n_trees,
-                                               d_old_roots_out, d_new_roots_out, d_n_hashed)
-
-    def _forest_consistency_verify_device(self, f, a, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
-                                          d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids, n_trees, d_old_roots_out, d_new_roots_out,
-                                          d_n_hashed):
+    def merkle_forest_consistency_verify_device(self, tag, d_old_counts, d_old_roots, d_new_counts, d_new_roots, d_leaves, d_siblings,
+                                                d_positions, d_depths, stride_depth, k, d_ok, d_tree_ids=None, n_trees=0,
+                                                d_old_roots_out=None, d_new_roots_out=None, d_n_hashed=None, arity=4):
+        """k consistency proofs checked against their claims (p252_merkle{4,2}_forest_consistency_verify_device_into; pass the tag of
+        that arity): d_ok[i] (uint8) = 1 iff the opening i (the layout above, at stride_depth rows) re-hashes to the new root and its
+        left siblings alone to the old root, with its slots the digits of the old count.  Without d_tree_ids claim i is element i of
+        d_old_counts, d_old_roots, d_new_counts, d_new_roots (k entries each); with d_tree_ids (int32/uint32) they hold n_trees entries
+        and claim i is element d_tree_ids[i] — so the counts and roots of a ForestFrontier are the old claims as they stand.
+        d_old_roots_out / d_new_roots_out (k, 4; optional) receive the recomputed roots, d_n_hashed (a zeroed device int64/uint64,
+        optional) grows by the digests computed.  Asynchronous on the current stream."""
+        f = "merkle_forest_consistency_verify_device"
+        a = _arity(f, arity)
         leaves, sib, pos, dep = self._ragged_opening_ptrs(f, a, d_leaves, d_siblings, d_positions, d_depths, stride_depth, k)
         claims = n_trees if d_tree_ids is not None else k
         self._check(a.fn("forest_consistency_verify_device_into")(
@@ -1089,47 +973,27 @@ class Context:
 
     # ---- anchors: roots and openings of a forest's trees as they were at earlier leaf counts
     # (p252_merkle{4,2}_forest_ragged_anchor_openings_device_into; csrc/forest_anchor.hip) ----
-    def merkle4_forest_ragged_anchor_openings_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
-                                                     d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths,
-                                                     d_leaves_out=None, d_siblings=None, d_positions=None, d_depths=None,
-                                                     d_n_bad_anchors=None, d_n_bad=None, d_n_hashed=None):
+    def merkle_forest_ragged_anchor_openings_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
+                                                    d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths,
+                                                    d_leaves_out=None, d_siblings=None, d_positions=None, d_depths=None,
+                                                    d_n_bad_anchors=None, d_n_bad=None, d_n_hashed=None, arity=4):
         """m anchors and k openings against them out of a forest merkle_forest_ragged_device built with d_levels
-        (p252_merkle4_forest_ragged_anchor_openings_device_into).  Anchor a is tree d_anchor_tree_ids[a] (int32/uint32) as it was at
-        d_anchor_counts[a] (int64/uint64) leaves: d_anchor_roots (m, 4) receives the root a fresh build of those leaves returns,
-        d_anchor_depths (m,) uint8 its depth.  Opening i is leaf d_leaf_ids[i] (int64/uint64) under anchor d_anchor_ids[i]
-        (int32/uint32), written in the layout of merkle_forest_ragged_openings_device at D = depth(max_leaves): d_leaves_out (k, 4),
-        d_siblings (k, D, 3, 4), d_positions (k, D) uint8, d_depths (k,) uint8 — what that call writes on a fresh build of the tree's
-        first c leaves, so merkle_forest_ragged_verify_device takes them with d_tree_ids = d_anchor_ids, d_roots = d_anchor_roots,
-        n_trees = m.  A bad anchor (unknown or bad tree, count 0 or above n_t): a zero root, depth 0xFF, counted in d_n_bad_anchors; a
-        bad opening (anchor id >= m, a bad anchor, leaf id >= count): zeros, depth 0xFF, counted in d_n_bad (zeroed device
-        int32/uint32, optional).  d_n_hashed (a zeroed device int64/uint64, optional) grows by the digests the anchors need.  k == 0:
-        the roots alone, the opening tensors may be None; the siblings and positions may be None when D == 0.  Asynchronous on the
-        current stream."""
-        self._forest_ragged_anchor_openings_device("merkle4_forest_ragged_anchor_openings_device", _ARITIES[4], tag, d_leaves, d_offsets, n_trees,
-                                                   max_leaves, d_levels, d_anchor_tree_ids, d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k,
-                                                   d_anchor_roots, d_anchor_depths, d_leaves_out, d_siblings, d_positions, d_depths,
-                                                   d_n_bad_anchors, d_n_bad, d_n_hashed)
-
-    def merkle2_forest_ragged_anchor_openings_device(self, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
-                                                     d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths,
-                                                     d_leaves_out=None, d_siblings=None, d_positions=None, d_depths=None,
-                                                     d_n_bad_anchors=None, d_n_bad=None, d_n_hashed=None):
-        """the same for arity 2 (d_siblings (k, D, 1, 4); pass the Merkle2 tag)"""
-        self._forest_ragged_anchor_openings_device("merkle2_forest_ragged_anchor_openings_device", _ARITIES[2], tag, d_leaves, d_offsets, n_trees,
-                                                   max_leaves, d_levels, d_anchor_tree_ids, d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k,
-                                                   d_anchor_roots, d_anchor_depths, d_leaves_out, d_siblings, d_positions, d_depths,
-                                                   d_n_bad_anchors, d_n_bad, d_n_hashed)
-
-    def _forest_ragged_anchor_openings_device(self, f, a, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
-                                              d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths, d_leaves_out,
-                                              d_siblings, d_positions, d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed):
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
+        (p252_merkle{4,2}_forest_ragged_anchor_openings_device_into; pass the tag of that arity).  Anchor a is tree d_anchor_tree_ids[a]
+        (int32/uint32) as it was at d_anchor_counts[a] (int64/uint64) leaves: d_anchor_roots (m, 4) receives the root a fresh build of
+        those leaves returns, d_anchor_depths (m,) uint8 its depth.  Opening i is leaf d_leaf_ids[i] (int64/uint64) under anchor
+        d_anchor_ids[i] (int32/uint32), written in the layout of merkle_forest_ragged_openings_device at D = depth(max_leaves):
+        d_leaves_out (k, 4), d_siblings (k, D, arity-1, 4), d_positions (k, D) uint8, d_depths (k,) uint8 — what that call writes on a
+        fresh build of the tree's first c leaves, so merkle_forest_ragged_verify_device takes them with d_tree_ids = d_anchor_ids, d_roots =
+        d_anchor_roots, n_trees = m.  A bad anchor (unknown or bad tree, count 0 or above n_t): a zero root, depth 0xFF, counted in
+        d_n_bad_anchors; a bad opening (anchor id >= m, a bad anchor, leaf id >= count): zeros, depth 0xFF, counted in d_n_bad (zeroed
+        device int32/uint32, optional).  d_n_hashed (a zeroed device int64/uint64, optional) grows by the digests the anchors need.
+        k == 0: the roots alone, the opening tensors may be None; the siblings and positions may be None when D == 0.  Asynchronous on
+        the current stream."""
+        f = "merkle_forest_ragged_anchor_openings_device"
+        a = _arity(f, arity)
+        forest, depth = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         self._check(a.fn("forest_ragged_anchor_openings_device_into")(
-            self._h, _tag(tag), leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_anchor_tree_ids", d_anchor_tree_ids, m * 4, elem=4, null_ok=m == 0),
+            self._h, _tag(tag), *forest, _dev_ptr(self, f, "d_anchor_tree_ids", d_anchor_tree_ids, m * 4, elem=4, null_ok=m == 0),
             _dev_ptr(self, f, "d_anchor_counts", d_anchor_counts, m * 8, elem=8, null_ok=m == 0), m,
             _dev_ptr(self, f, "d_anchor_ids", d_anchor_ids, k * 4, elem=4, null_ok=k == 0),
             _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8, null_ok=k == 0), k,
@@ -1144,70 +1008,43 @@ class Context:
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _stream(self)))
 
     # ---- the shared proof across a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_*; csrc/forest_multiproof.hip) ----
-    def merkle4_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
-        """upper bound, in scalars, of the shared proof of k pairs of a ragged forest (p252_merkle4_forest_ragged_multiproof_bound)"""
-        return int(_ARITIES[4].fn("forest_ragged_multiproof_bound")(n_leaves, n_trees, max_leaves, k))
+    def merkle_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k, arity=4):
+        """upper bound, in scalars, of the shared proof of k pairs of a ragged forest (p252_merkle{4,2}_forest_ragged_multiproof_bound)"""
+        a = _arity("merkle_forest_ragged_multiproof_bound", arity)
+        return int(a.fn("forest_ragged_multiproof_bound")(n_leaves, n_trees, max_leaves, k))
 
-    def merkle2_forest_ragged_multiproof_bound(self, n_leaves, n_trees, max_leaves, k):
-        """the same for arity 2"""
-        return int(_ARITIES[2].fn("forest_ragged_multiproof_bound")(n_leaves, n_trees, max_leaves, k))
-
-    def merkle4_forest_ragged_multiproof_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
-                                                d_leaves_out, d_proof, d_proof_offsets, d_n_bad=None):
+    def merkle_forest_ragged_multiproof_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
+                                               d_leaves_out, d_proof, d_proof_offsets, d_n_bad=None, arity=4):
         """one shared, tree-major proof for k (tree id, leaf id) pairs anywhere in a forest merkle_forest_ragged_device built with d_levels
-        (p252_merkle4_forest_ragged_multiproof_device_into; no hashing): d_leaves, d_offsets, n_trees, max_leaves, d_levels exactly as the
+        (p252_merkle{4,2}_forest_ragged_multiproof_device_into; no hashing): d_leaves, d_offsets, n_trees, max_leaves, d_levels exactly as the
         build took them; d_tree_ids (int32/uint32) and d_leaf_ids (int64/uint64) STRICTLY ASCENDING in (tree, leaf).  d_leaves_out (k, 4)
         receives the leaves, d_proof the proof — its capacity is the tensor's length, nothing is written past it (None: capacity 0) —
         and d_proof_offsets (n_trees + 1 int64/uint64) where each tree's single-tree proof starts, the last entry the length the
         proof needs.  A bad pair is counted in d_n_bad (a zeroed device int32/uint32, optional) and makes every offset 0.
         Asynchronous on the current stream."""
-        self._forest_ragged_multiproof_device("merkle4_forest_ragged_multiproof_device", _ARITIES[4], d_leaves, d_offsets, n_trees, max_leaves,
-                                              d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof, d_proof_offsets, d_n_bad)
-
-    def merkle2_forest_ragged_multiproof_device(self, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
-                                                d_leaves_out, d_proof, d_proof_offsets, d_n_bad=None):
-        """the same for arity 2"""
-        self._forest_ragged_multiproof_device("merkle2_forest_ragged_multiproof_device", _ARITIES[2], d_leaves, d_offsets, n_trees, max_leaves,
-                                              d_levels, d_tree_ids, d_leaf_ids, k, d_leaves_out, d_proof, d_proof_offsets, d_n_bad)
-
-    def _forest_ragged_multiproof_device(self, f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids, k,
-                                         d_leaves_out, d_proof, d_proof_offsets, d_n_bad):
-        leaves = _dev_ptr(self, f, "d_leaves", d_leaves, 32)
-        n_leaves = _n_scalars(d_leaves)
-        depth = a.depth(max_leaves)
+        f = "merkle_forest_ragged_multiproof_device"
+        a = _arity(f, arity)
+        forest, _ = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
         proof_cap = _n_scalars(d_proof) if hasattr(d_proof, "element_size") else 0
         self._check(a.fn("forest_ragged_multiproof_device_into")(
-            self._h, leaves, n_leaves, _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_trees, max_leaves,
-            _dev_ptr(self, f, "d_levels", d_levels, a.forest_levels_bytes(n_leaves, n_trees, depth), null_ok=depth == 0),
-            _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8), k,
+            self._h, *forest, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
+            _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8), k,
             _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32), _dev_ptr(self, f, "d_proof", d_proof, proof_cap * 32, null_ok=True),
             proof_cap, _dev_ptr(self, f, "d_proof_offsets", d_proof_offsets, (n_trees + 1) * 8, elem=8),
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
-    def merkle4_forest_ragged_multiproof_verify_device(self, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
-                                                       k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out=None,
-                                                       d_n_hashed=None, d_n_bad=None):
-        """checks such a proof with every ancestor hashed ONCE (p252_merkle4_forest_ragged_multiproof_verify_device_into; tag = the Merkle4
-        tag); needs neither leaves nor levels: d_offsets and n_leaves, n_trees, max_leaves as the build took them, the pairs and
+    def merkle_forest_ragged_multiproof_verify_device(self, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
+                                                      k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out=None,
+                                                      d_n_hashed=None, d_n_bad=None, arity=4):
+        """checks such a proof with every ancestor hashed ONCE (p252_merkle{4,2}_forest_ragged_multiproof_verify_device_into; pass the tag
+        of that arity); needs neither leaves nor levels: d_offsets and n_leaves, n_trees, max_leaves as the build took them, the pairs and
         d_leaves_in (k, 4) as extraction returned them, proof_len scalars of d_proof (None when 0), d_proof_offsets (n_trees + 1),
         d_roots (n_trees, 4).  d_ok[t] (n_trees uint8) = 1 iff tree t has a pair, no pair is bad, its offsets are in order and inside
         proof_len, its structure consumes exactly its part and the recomputed root equals d_roots[t].  Optional outputs: d_roots_out
         (n_trees, 4) the recomputed roots, d_n_hashed (one int64/uint64) the digests computed, d_n_bad (a zeroed int32/uint32) the bad
         pairs.  Asynchronous on the current stream."""
-        self._forest_ragged_multiproof_verify_device("merkle4_forest_ragged_multiproof_verify_device", _ARITIES[4], tag, d_offsets, n_leaves,
-                                                     n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in, k, d_proof, proof_len,
-                                                     d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad)
-
-    def merkle2_forest_ragged_multiproof_verify_device(self, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
-                                                       k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out=None,
-                                                       d_n_hashed=None, d_n_bad=None):
-        """the same for arity 2 (Domain::Merkle2 nodes; pass the Merkle2 tag)"""
-        self._forest_ragged_multiproof_verify_device("merkle2_forest_ragged_multiproof_verify_device", _ARITIES[2], tag, d_offsets, n_leaves,
-                                                     n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in, k, d_proof, proof_len,
-                                                     d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad)
-
-    def _forest_ragged_multiproof_verify_device(self, f, a, tag, d_offsets, n_leaves, n_trees, max_leaves, d_tree_ids, d_leaf_ids, d_leaves_in,
-                                                k, d_proof, proof_len, d_proof_offsets, d_roots, d_ok, d_roots_out, d_n_hashed, d_n_bad):
+        f = "merkle_forest_ragged_multiproof_verify_device"
+        a = _arity(f, arity)
         self._check(a.fn("forest_ragged_multiproof_verify_device_into")(
             self._h, _tag(tag), _dev_ptr(self, f, "d_offsets", d_offsets, (n_trees + 1) * 8, elem=8), n_leaves, n_trees, max_leaves,
             _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4), _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8),
@@ -1219,14 +1056,11 @@ class Context:
             _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
             _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
 
-    def merkle2_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
-        """re-hash of n arity-2 openings (Domain::Merkle2; pass the Merkle2 tag): d_siblings (n,depth[,1],4), d_positions (n,depth) in 0..1"""
-        self._path_batch_device("merkle2_path_batch_device", _ARITIES[2], tag, d_leaves, d_siblings, d_positions, depth, d_roots, n)
-
-    def merkle4_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
-        self._path_batch_device("merkle4_path_batch_device", _ARITIES[4], tag, d_leaves, d_siblings, d_positions, depth, d_roots, n)
-
-    def _path_batch_device(self, f, a, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n):
+    def merkle_path_batch_device(self, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n, arity=4):
+        """re-hash of n openings of one depth (p252_merkle{4,2}_path_batch_device; pass the tag of that arity): d_siblings
+        (n,depth,arity-1,4), for arity 2 also (n,depth,4); d_positions (n,depth) in 0..arity-1"""
+        f = "merkle_path_batch_device"
+        a = _arity(f, arity)
         self._check(a.fn("path_batch_device")(self._h, _tag(tag), _dev_ptr(self, f, "d_leaves", d_leaves, n * 32),
             _dev_ptr(self, f, "d_siblings", d_siblings, n * depth * a.per * 32) if depth else None,
             _dev_ptr(self, f, "d_positions", d_positions, n * depth) if depth else None, depth,
@@ -1271,6 +1105,38 @@ class Context:
     def tables_import(self, buf):
         buf = np.ascontiguousarray(buf, dtype=np.int32)
         self._check(_lib.lib().p252_tables_import(self._h, _ptr(buf, ctypes.c_void_p), buf.nbytes))
+
+
+# the calls that are also published per arity: Context.merkle4_<stem> and Context.merkle2_<stem> (bench.py, the per-call tests and the
+# bench tools call them) are Context.merkle_<stem>(..., arity=4) and (..., arity=2)
+_PER_ARITY_STEMS = (
+    "forest_ragged_journal_bound", "forest_ragged_update_journaled_device", "forest_ragged_journal_swap_device",
+    "forest_ragged_append_device", "forest_ragged_resize_device", "forest_ragged_select_device",
+    "forest_frontier_bound", "forest_frontier_append_device", "forest_frontier_append_witness_device", "forest_frontier_extract_device",
+    "forest_ragged_consistency_device", "forest_consistency_verify_device", "forest_ragged_anchor_openings_device",
+    "forest_ragged_multiproof_bound", "forest_ragged_multiproof_device", "forest_ragged_multiproof_verify_device",
+    "path_batch_device")
+
+
+def _publish_per_arity(cls, stems):
+    def forwarder(unified, arity):
+        def call(self, *args, **kw):
+            return unified(self, *args, arity=arity, **kw)
+        return call
+    for stem in stems:
+        unified = getattr(cls, "merkle_" + stem)
+        sig = inspect.signature(unified)
+        sig = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "arity"])
+        for arity in (4, 2):
+            call = forwarder(unified, arity)
+            call.__name__ = "merkle%d_%s" % (arity, stem)
+            call.__qualname__ = "%s.%s" % (cls.__qualname__, call.__name__)
+            call.__doc__ = "%s.%s(..., arity=%d): see there" % (cls.__qualname__, unified.__name__, arity)
+            call.__signature__ = sig
+            setattr(cls, call.__name__, call)
+
+
+_publish_per_arity(Context, _PER_ARITY_STEMS)
 
 
 class PinnedScalars:

@@ -125,7 +125,7 @@ def merkle4_openings(leaves, levels, indices):
 
 def forest_ragged_append(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets, n_trees_new=None,
                          max_leaves_new=None, arity=4):
-    """Leaves appended to the trees of a built forest (Context.merkle{4,2}_forest_ragged_append_device): the forest = torch CUDA tensors
+    """Leaves appended to the trees of a built forest (Context.merkle_forest_ragged_append_device): the forest = torch CUDA tensors
     as Context.merkle_forest_ragged_device took and filled them; tree t receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (d_add None:
     a compaction copy).  n_trees_new defaults to the trees d_add_offsets names, max_leaves_new to max_leaves plus the scalars of d_add (no
     append can then be too long).  Sizes and allocates the new forest and returns (d_leaves_new, d_offsets_new, d_levels_new, d_roots,
@@ -148,15 +148,16 @@ def forest_ragged_append(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_l
     roots = torch.empty((n_trees_new, 4), dtype=torch.int64, device=dev)
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
     n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
-    call = ctx.merkle4_forest_ragged_append_device if arity == 4 else ctx.merkle2_forest_ragged_append_device
-    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets,
-         n_trees_new, max_leaves_new, leaves_new if total else None, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad, n_hashed)
+    ctx.merkle_forest_ragged_append_device(
+        a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_add, d_add_offsets,
+        n_trees_new, max_leaves_new, leaves_new if total else None, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad, n_hashed,
+        arity=arity)
     return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
 
 
 def forest_ragged_resize(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep=None, d_add=None, d_add_offsets=None,
                          n_trees_new=None, max_leaves_new=None, arity=4):
-    """A built forest rolled back and forward in one call (Context.merkle{4,2}_forest_ragged_resize_device): tree t keeps its first
+    """A built forest rolled back and forward in one call (Context.merkle_forest_ragged_resize_device): tree t keeps its first
     min(d_keep[t], n_t) leaves (d_keep: int64/uint64 on the device, -1 or any value >= n_t keeps the tree whole; None: every tree) and
     then receives d_add[d_add_offsets[t]:d_add_offsets[t+1]] (both None: a pure rollback).  n_trees_new defaults to the trees
     d_add_offsets names, else d_keep, else n_trees; smaller than n_trees it drops the trailing trees.  max_leaves_new defaults as in
@@ -184,15 +185,16 @@ def forest_ragged_resize(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_l
     roots = torch.empty((n_trees_new, 4), dtype=torch.int64, device=dev)
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
     n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
-    call = ctx.merkle4_forest_ragged_resize_device if arity == 4 else ctx.merkle2_forest_ragged_resize_device
-    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
-         n_trees_new, max_leaves_new, leaves_new if total else None, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad, n_hashed)
+    ctx.merkle_forest_ragged_resize_device(
+        a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_keep, d_add, d_add_offsets,
+        n_trees_new, max_leaves_new, leaves_new if total else None, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad, n_hashed,
+        arity=arity)
     return leaves_new, offsets_new, levels_new, roots, n_bad, n_hashed
 
 
 def forest_ragged_select(ctx, forest_a, pick, forest_b=None, arity=4, leaves_cap=None):
     """Any trees of one or two built forests gathered into a new compact forest, with no digest
-    (Context.merkle{4,2}_forest_ragged_select_device): forest_a, forest_b = (d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots),
+    (Context.merkle_forest_ragged_select_device): forest_a, forest_b = (d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots),
     torch CUDA tensors as Context.merkle_forest_ragged_device took and filled them; pick = the ids of the new forest's trees in order
     (a device int64 tensor, or anything numpy takes): below n_trees_a a tree of A, then a tree of B.  leaves_cap defaults to the leaves
     of both sources, enough when no tree is named twice; a pick past it is refused and counted, never written.  Sizes and allocates
@@ -221,8 +223,8 @@ def forest_ragged_select(ctx, forest_a, pick, forest_b=None, arity=4, leaves_cap
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
     if n_pick == 0:  # (the library enqueues nothing: the one offset is written here)
         offsets_new.zero_()
-    call = ctx.merkle4_forest_ragged_select_device if arity == 4 else ctx.merkle2_forest_ragged_select_device
-    call(forest_a, forest_b, pick, n_pick, leaves_new, offsets_new, levels_new if levels_new.numel() else None, roots, n_bad)
+    ctx.merkle_forest_ragged_select_device(forest_a, forest_b, pick, n_pick, leaves_new, offsets_new, levels_new if levels_new.numel() else None,
+                                           roots, n_bad, arity=arity)
     return leaves_new, offsets_new, levels_new, roots, n_bad
 
 
@@ -241,7 +243,7 @@ class ForestJournal:
 
 def forest_ragged_update_journaled(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, leaf_ids, new_leaves, d_roots=None,
                                    arity=4):
-    """Leaf updates of a built forest that can be undone (Context.merkle{4,2}_forest_ragged_update_journaled_device): the forest = torch
+    """Leaf updates of a built forest that can be undone (Context.merkle_forest_ragged_update_journaled_device): the forest = torch
     CUDA tensors as Context.merkle_forest_ragged_device took and filled them, updated in place; (tree_ids[i], leaf_ids[i]) receives
     new_leaves[i] (sequences, numpy or torch).  Allocates the journal at its bound and returns it as a ForestJournal; its counters are
     on the device.  No synchronisation."""
@@ -257,36 +259,36 @@ def forest_ragged_update_journaled(ctx, tag, d_leaves, d_offsets, n_trees, max_l
     k = t.numel()
     if l.numel() != k or _n_scalars(new) != k:
         raise ValueError("%s: %d tree ids, %d leaf ids, %d new leaves" % (f, k, l.numel(), _n_scalars(new)))
-    four = arity == 4
-    cap = (ctx.merkle4_forest_ragged_journal_bound if four else ctx.merkle2_forest_ragged_journal_bound)(_n_scalars(d_leaves), n_trees, max_leaves, k)
+    cap = ctx.merkle_forest_ragged_journal_bound(_n_scalars(d_leaves), n_trees, max_leaves, k, arity=arity)
     j = ForestJournal(torch.empty((cap, 4), dtype=torch.int32, device=dev), torch.empty((cap, 4), dtype=torch.int64, device=dev),
                       torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
                       torch.zeros(1, dtype=torch.int64, device=dev))
-    call = ctx.merkle4_forest_ragged_update_journaled_device if four else ctx.merkle2_forest_ragged_update_journaled_device
-    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None,
-         (t & 0xFFFFFFFF).to(torch.int32), l, new, k, j.ids if cap else None, j.values if cap else None, cap, j.len, d_roots, j.n_bad, j.n_hashed)
+    ctx.merkle_forest_ragged_update_journaled_device(
+        a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None,
+        (t & 0xFFFFFFFF).to(torch.int32), l, new, k, j.ids if cap else None, j.values if cap else None, cap, j.len, d_roots, j.n_bad, j.n_hashed,
+        arity=arity)
     return j
 
 
 def forest_ragged_journal_swap(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, journal, d_roots=None, arity=4):
     """The update behind `journal` (a ForestJournal) undone — or, after an undo, redone — with no hashing
-    (Context.merkle{4,2}_forest_ragged_journal_swap_device): the forest exactly as the update took it, changed in place; d_roots follows for
+    (Context.merkle_forest_ragged_journal_swap_device): the forest exactly as the update took it, changed in place; d_roots follows for
     the touched trees.  Journals stack: undo the latest first, redo the earliest first.  Returns the entries that named no node of this
     forest as a (1,) int32 device tensor: 0 for a journal used on its own forest.  No synchronisation."""
     import torch
     a = _arity("forest_ragged_journal_swap", arity)
     ctx = ctx or Context.default()
     n_bad = torch.zeros(1, dtype=torch.int32, device=d_leaves.device)
-    call = ctx.merkle4_forest_ragged_journal_swap_device if arity == 4 else ctx.merkle2_forest_ragged_journal_swap_device
     cap = journal.cap
-    call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None, journal.ids if cap else None,
-         journal.values if cap else None, cap, journal.len, d_roots, n_bad)
+    ctx.merkle_forest_ragged_journal_swap_device(d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None,
+                                                 journal.ids if cap else None, journal.values if cap else None, cap, journal.len, d_roots, n_bad,
+                                                 arity=arity)
     return n_bad
 
 
 class ForestFrontier:
     """A forest of append-only trees kept only as their frontiers, on the device: counts (n_trees,) int64, frontier (n_trees, bound, 4)
-    int64 with bound = Context.merkle{4,2}_forest_frontier_bound(max_leaves), roots (n_trees, 4) int64 — O(depth) scalars per tree
+    int64 with bound = Context.merkle_forest_frontier_bound(max_leaves), roots (n_trees, 4) int64 — O(depth) scalars per tree
     whatever the trees hold.  ForestFrontier(ctx, n_trees, max_leaves) is a forest of empty trees; from_forest takes the state out of
     a built ragged forest; append grows the trees in place."""
 
@@ -296,7 +298,7 @@ class ForestFrontier:
         self.ctx = ctx or Context.default()
         self.n_trees, self.max_leaves, self.arity = n_trees, max_leaves, arity
         dev = device if device is not None else "cuda:%d" % self.ctx.device
-        bound = (self.ctx.merkle4_forest_frontier_bound if arity == 4 else self.ctx.merkle2_forest_frontier_bound)(max_leaves)
+        bound = self.ctx.merkle_forest_frontier_bound(max_leaves, arity=arity)
         self.counts = torch.zeros(n_trees, dtype=torch.int64, device=dev) if counts is None else counts
         self.frontier = torch.zeros((n_trees, bound, 4), dtype=torch.int64, device=dev) if frontier is None else frontier
         self.roots = torch.zeros((n_trees, 4), dtype=torch.int64, device=dev) if roots is None else roots
@@ -368,11 +370,11 @@ class ForestWitnesses:
 
 
 def forest_frontier_append(ctx, tag, state, d_add, d_add_offsets, witnesses=None):
-    """Leaves appended to the trees of a ForestFrontier, in place (Context.merkle{4,2}_forest_frontier_append_device): tree t receives
+    """Leaves appended to the trees of a ForestFrontier, in place (Context.merkle_forest_frontier_append_device): tree t receives
     d_add[d_add_offsets[t]:d_add_offsets[t+1]] (torch CUDA tensors; d_add None: nothing).  Returns (d_n_bad (1,) int32, d_n_hashed (1,)
     int64) on the device: the refused appends, whose trees are untouched, and the digests computed.  With witnesses (a ForestWitnesses
     of the same arity and max_leaves) their openings are kept current by the same call
-    (Context.merkle{4,2}_forest_frontier_append_witness_device) and a third tensor, d_n_bad_witness (1,) int32, follows.
+    (Context.merkle_forest_frontier_append_witness_device) and a third tensor, d_n_bad_witness (1,) int32, follows.
     No synchronisation."""
     import torch
     a = _arity("forest_frontier_append", state.arity)
@@ -382,23 +384,23 @@ def forest_frontier_append(ctx, tag, state, d_add, d_add_offsets, witnesses=None
     n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
     tag = a.tag() if tag is None else _as_scalars(tag).reshape(4)
     if witnesses is None:
-        call = ctx.merkle4_forest_frontier_append_device if state.arity == 4 else ctx.merkle2_forest_frontier_append_device
-        call(tag, state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves, d_add, d_add_offsets, n_bad, n_hashed)
+        ctx.merkle_forest_frontier_append_device(tag, state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves, d_add, d_add_offsets,
+                                                 n_bad, n_hashed, arity=state.arity)
         return n_bad, n_hashed
     if witnesses.arity != state.arity or witnesses.max_leaves != state.max_leaves:
         raise ValueError("forest_frontier_append: the witnesses are of arity %d and max_leaves %d, the state of %d and %d"
                          % (witnesses.arity, witnesses.max_leaves, state.arity, state.max_leaves))
     n_bad_witness = torch.zeros(1, dtype=torch.int32, device=dev)
-    call = ctx.merkle4_forest_frontier_append_witness_device if state.arity == 4 else ctx.merkle2_forest_frontier_append_witness_device
     w = witnesses
-    call(tag, state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves, d_add, d_add_offsets, w.tree_ids, w.leaf_ids, w.k,
-         w.leaves, w.siblings if w.depth else None, w.positions if w.depth else None, w.depths, n_bad, n_hashed, n_bad_witness)
+    ctx.merkle_forest_frontier_append_witness_device(
+        tag, state.counts, state.frontier, state.roots, state.n_trees, state.max_leaves, d_add, d_add_offsets, w.tree_ids, w.leaf_ids, w.k,
+        w.leaves, w.siblings if w.depth else None, w.positions if w.depth else None, w.depths, n_bad, n_hashed, n_bad_witness, arity=state.arity)
     return n_bad, n_hashed, n_bad_witness
 
 
 def forest_frontier_extract(ctx, d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, state):
     """The frontiers of a built ragged forest written into `state` (a ForestFrontier of n_trees trees with max_leaves >=
-    max_leaves_forest), with no digest (Context.merkle{4,2}_forest_frontier_extract_device).  Returns d_n_bad (1,) int32 on the device:
+    max_leaves_forest), with no digest (Context.merkle_forest_frontier_extract_device).  Returns d_n_bad (1,) int32 on the device:
     the trees the build calls bad, which become empty ones.  No synchronisation."""
     import torch
     _arity("forest_frontier_extract", state.arity)
@@ -406,13 +408,13 @@ def forest_frontier_extract(ctx, d_leaves, d_offsets, n_trees, max_leaves_forest
     if state.n_trees != n_trees:
         raise ValueError("forest_frontier_extract: the state holds %d trees, the forest %d" % (state.n_trees, n_trees))
     n_bad = torch.zeros(1, dtype=torch.int32, device=state.counts.device)
-    call = ctx.merkle4_forest_frontier_extract_device if state.arity == 4 else ctx.merkle2_forest_frontier_extract_device
-    call(d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, state.max_leaves, state.counts, state.frontier, state.roots, n_bad)
+    ctx.merkle_forest_frontier_extract_device(d_leaves, d_offsets, n_trees, max_leaves_forest, d_levels, d_roots, state.max_leaves, state.counts,
+                                              state.frontier, state.roots, n_bad, arity=state.arity)
     return n_bad
 
 
 def forest_ragged_consistency(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, old_counts, arity=4):
-    """Consistency proofs out of a built ragged forest, with no digest (Context.merkle{4,2}_forest_ragged_consistency_device): proof i
+    """Consistency proofs out of a built ragged forest, with no digest (Context.merkle_forest_ragged_consistency_device): proof i
     shows that tree tree_ids[i], as it is now, is the tree it was at old_counts[i] leaves with leaves appended (sequences, numpy or
     torch; a (n_trees,) counts tensor of a ForestFrontier with tree_ids = arange serves as it stands).  Returns (d_new_counts (k,)
     int64, (d_leaves_out (k, 4), d_siblings (k, D, arity - 1, 4), d_positions (k, D) uint8, d_depths (k,) uint8, D), d_n_bad (1,)
@@ -433,15 +435,15 @@ def forest_ragged_consistency(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_l
     pos = torch.zeros((k, D), dtype=torch.uint8, device=dev)
     dep = torch.full((k,), 0xFF, dtype=torch.uint8, device=dev)
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    call = ctx.merkle4_forest_ragged_consistency_device if arity == 4 else ctx.merkle2_forest_ragged_consistency_device
     if k:
-        call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if D else None, t, n, k, new_counts, lv, sib if D else None, pos if D else None, dep, n_bad)
+        ctx.merkle_forest_ragged_consistency_device(d_leaves, d_offsets, n_trees, max_leaves, d_levels if D else None, t, n, k, new_counts, lv,
+                                                    sib if D else None, pos if D else None, dep, n_bad, arity=arity)
     return new_counts, (lv, sib, pos, dep, D), n_bad
 
 
 def forest_consistency_verify(ctx, d_old_counts, d_old_roots, d_new_counts, d_new_roots, proof, d_tree_ids=None, tag=None, arity=4):
     """Consistency proofs checked against (old count, old root, new count, new root) claims
-    (Context.merkle{4,2}_forest_consistency_verify_device): proof = (d_leaves, d_siblings, d_positions, d_depths, D) as
+    (Context.merkle_forest_consistency_verify_device): proof = (d_leaves, d_siblings, d_positions, d_depths, D) as
     forest_ragged_consistency returns it; claim i is element i of the four claim tensors, or element d_tree_ids[i] (int32) when given —
     then they hold one entry per tree, as the counts and roots of a ForestFrontier do.  Returns (d_ok (k,) uint8, d_old_roots_out (k, 4),
     d_new_roots_out (k, 4), d_n_hashed (1,) int64) on the device: the verdicts, the recomputed roots, the digests computed.  No
@@ -454,17 +456,18 @@ def forest_consistency_verify(ctx, d_old_counts, d_old_roots, d_new_counts, d_ne
     ok = torch.zeros(k, dtype=torch.uint8, device=dev)
     old_out, new_out = torch.zeros((k, 4), dtype=torch.int64, device=dev), torch.zeros((k, 4), dtype=torch.int64, device=dev)
     n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
-    call = ctx.merkle4_forest_consistency_verify_device if arity == 4 else ctx.merkle2_forest_consistency_verify_device
     if k:
-        call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_old_counts, d_old_roots, d_new_counts, d_new_roots, lv, sib if D else None,
-             pos if D else None, dep, D, k, ok, d_tree_ids, _n_scalars(d_old_roots) if d_tree_ids is not None else 0, old_out, new_out, n_hashed)
+        ctx.merkle_forest_consistency_verify_device(
+            a.tag() if tag is None else _as_scalars(tag).reshape(4), d_old_counts, d_old_roots, d_new_counts, d_new_roots, lv, sib if D else None,
+            pos if D else None, dep, D, k, ok, d_tree_ids, _n_scalars(d_old_roots) if d_tree_ids is not None else 0, old_out, new_out, n_hashed,
+            arity=arity)
     return ok, old_out, new_out, n_hashed
 
 
 def forest_ragged_anchor_openings(ctx, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, anchor_tree_ids, anchor_counts, anchor_ids,
                                   leaf_ids, arity=4):
     """Roots and openings of the trees of a built ragged forest as they WERE at earlier leaf counts
-    (Context.merkle{4,2}_forest_ragged_anchor_openings_device): anchor a is tree anchor_tree_ids[a] at anchor_counts[a] leaves, opening i
+    (Context.merkle_forest_ragged_anchor_openings_device): anchor a is tree anchor_tree_ids[a] at anchor_counts[a] leaves, opening i
     is leaf leaf_ids[i] under anchor anchor_ids[i] (sequences, numpy or torch; empty leaf_ids: the roots alone).  tag = None: the arity's
     own.  Returns (d_anchor_roots (m, 4), d_anchor_depths (m,) uint8, openings, (d_n_bad_anchors, d_n_bad) (1,) int32 each, d_n_hashed
     (1,) int64), all on the device, with openings = (d_leaves_out (k, 4), d_siblings (k, D, arity - 1, 4), d_positions (k, D) uint8,
@@ -489,11 +492,11 @@ def forest_ragged_anchor_openings(ctx, tag, d_leaves, d_offsets, n_trees, max_le
     dep = torch.full((k,), 0xFF, dtype=torch.uint8, device=dev)
     bad_anchors, bad = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
     n_hashed = torch.zeros(1, dtype=torch.int64, device=dev)
-    call = ctx.merkle4_forest_ragged_anchor_openings_device if arity == 4 else ctx.merkle2_forest_ragged_anchor_openings_device
     if m or k:
-        call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if D else None,
-             at if m else None, ac if m else None, m, oa if k else None, ol if k else None, k, roots if m else None, depths if m else None,
-             lv if k else None, sib if k and D else None, pos if k and D else None, dep if k else None, bad_anchors, bad, n_hashed)
+        ctx.merkle_forest_ragged_anchor_openings_device(
+            a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if D else None,
+            at if m else None, ac if m else None, m, oa if k else None, ol if k else None, k, roots if m else None, depths if m else None,
+            lv if k else None, sib if k and D else None, pos if k and D else None, dep if k else None, bad_anchors, bad, n_hashed, arity=arity)
     return roots, depths, (lv, sib, pos, dep, D), (bad_anchors, bad), n_hashed
 
 
@@ -536,7 +539,7 @@ def merkle_multiproof_verify(n_leaves, indices, leaves, proof, root, arity=4, ta
 
 
 def forest_ragged_multiproof(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, leaf_ids, arity=4):
-    """One shared, tree-major proof for leaves of many trees of a ragged forest (Context.merkle{4,2}_forest_ragged_multiproof_device):
+    """One shared, tree-major proof for leaves of many trees of a ragged forest (Context.merkle_forest_ragged_multiproof_device):
     d_leaves, d_offsets, n_trees, max_leaves, d_levels as merkle_forest_ragged_device took and filled them; (tree_ids[i], leaf_ids[i])
     in any order (sequences, numpy or torch): they are sorted and de-duplicated on the device.  Returns (tree_ids (k,) int32, leaf_ids
     (k,) int64, leaves (k, 4), proof (len, 4), proof_offsets (n_trees + 1,) int64), all on the device — what
@@ -562,13 +565,13 @@ def forest_ragged_multiproof(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_le
     k = key.numel()
     tid, lid = (key >> 32).to(torch.int32), key & 0xFFFFFFFF
     n_leaves = _n_scalars(d_leaves)
-    bound = (ctx.merkle4_forest_ragged_multiproof_bound if arity == 4 else ctx.merkle2_forest_ragged_multiproof_bound)(n_leaves, n_trees, max_leaves, k)
+    bound = ctx.merkle_forest_ragged_multiproof_bound(n_leaves, n_trees, max_leaves, k, arity=arity)
     out = torch.empty((k, 4), dtype=torch.int64, device=dev)
     proof = torch.empty((bound, 4), dtype=torch.int64, device=dev)
     offs = torch.empty(n_trees + 1, dtype=torch.int64, device=dev)
     n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    call = ctx.merkle4_forest_ragged_multiproof_device if arity == 4 else ctx.merkle2_forest_ragged_multiproof_device
-    call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None, tid, lid, k, out, proof if bound else None, offs, n_bad)
+    ctx.merkle_forest_ragged_multiproof_device(d_leaves, d_offsets, n_trees, max_leaves, d_levels if a.depth(max_leaves) else None, tid, lid, k, out,
+                                               proof if bound else None, offs, n_bad, arity=arity)
     bad, length = int(n_bad.item()), int(offs[-1].item())
     if bad:
         raise ValueError("%s: %d pair(s) outside the forest (a bad tree, or a leaf id past its tree)" % (f, bad))
@@ -579,16 +582,16 @@ def forest_ragged_multiproof_verify(ctx, d_offsets, n_leaves, n_trees, max_leave
                                     arity=4, tag=None):
     """The n_trees verdicts (a torch bool tensor on the host) of (tree_ids, leaf_ids, leaves, proof, proof_offsets) — torch CUDA tensors as
     forest_ragged_multiproof returns them — against d_roots (n_trees, 4) for a forest of the shape (d_offsets, n_leaves, n_trees,
-    max_leaves), every ancestor hashed once (Context.merkle{4,2}_forest_ragged_multiproof_verify_device): entry t is True iff tree t has a
+    max_leaves), every ancestor hashed once (Context.merkle_forest_ragged_multiproof_verify_device): entry t is True iff tree t has a
     pair and its part of the proof re-hashes to d_roots[t].  Synchronises to read the verdicts."""
     import torch
     a = _arity("forest_ragged_multiproof_verify", arity)
     ctx = ctx or Context.default()
     ok = torch.zeros(n_trees, dtype=torch.uint8, device=leaves.device)
     proof_len = _n_scalars(proof)
-    call = ctx.merkle4_forest_ragged_multiproof_verify_device if arity == 4 else ctx.merkle2_forest_ragged_multiproof_verify_device
-    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_offsets, n_leaves, n_trees, max_leaves, tree_ids, leaf_ids, leaves,
-         tree_ids.numel(), proof if proof_len else None, proof_len, proof_offsets, d_roots, ok)
+    ctx.merkle_forest_ragged_multiproof_verify_device(
+        a.tag() if tag is None else _as_scalars(tag).reshape(4), d_offsets, n_leaves, n_trees, max_leaves, tree_ids, leaf_ids, leaves,
+        tree_ids.numel(), proof if proof_len else None, proof_len, proof_offsets, d_roots, ok, arity=arity)
     return ok.cpu().to(torch.bool)
 
 

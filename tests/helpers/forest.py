@@ -151,9 +151,8 @@ def _outputs(arity, total, n_trees_new, max_new, tail=7):
 
 
 def _append(ctx, old, d_add, d_aoff, n_trees_new, max_new, out, bad=None, hashed=None):
-    call = ctx.merkle4_forest_ragged_append_device if old.arity == 4 else ctx.merkle2_forest_ragged_append_device
-    call(_tag(old.arity), old.d, old.d_off, old.n_trees, old.max_leaves, old.d_lv, d_add, d_aoff, n_trees_new, max_new, out[0], out[1][:n_trees_new + 1],
-         out[2], out[3][:n_trees_new], bad, hashed)
+    ctx.merkle_forest_ragged_append_device(_tag(old.arity), old.d, old.d_off, old.n_trees, old.max_leaves, old.d_lv, d_add, d_aoff, n_trees_new, max_new,
+                                           out[0], out[1][:n_trees_new + 1], out[2], out[3][:n_trees_new], bad, hashed, arity=old.arity)
 
 
 def _fresh(ctx, arity, M, old_flat, add, n_trees_new, max_new, like):

@@ -12,7 +12,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from helpers.binding import _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
+from helpers.binding import HOST_HELPERS, _no_device_context, dev, recorder, with_cpu_tensor  # noqa: E402,F401
 
 
 def _c_kind(ctype):
@@ -44,6 +44,78 @@ def test_prototypes_match_the_header():
         assert _c_kind(ret) == _ctypes_kind(restype), "%s returns %s, bound as %s" % (name, ret, restype)
 
 
+def per_arity_cases():
+    """{stem of a call that Context publishes as merkle_<stem>(..., arity=) and as merkle{4,2}_<stem>: (the stem of its C entry points,
+    its positional arguments out of the tensors, the tensors)}: 2 trees of at most 4 leaves, k = m = 2, the sizes of the per-call tests"""
+    tag = np.zeros(4, dtype=np.uint64)
+    i32, u8 = torch.int32, torch.uint8
+    forest = dict(d_leaves=dev(), d_offsets=dev(), d_levels=dev(n=256))
+    built = lambda a: (a["d_leaves"], a["d_offsets"], 2, 4, a["d_levels"])  # noqa: E731
+    journal = dict(d_journal_ids=dev(i32), d_journal_values=dev(), d_journal_len=dev())
+    new = dict(d_leaves_new=dev(n=128), d_offsets_new=dev(), d_levels_new=dev(n=256))
+    grown = dict(forest, d_add=dev(), d_add_offsets=dev(), **new, d_roots=dev(), d_n_bad=dev(i32), d_n_hashed=dev())
+    grow = lambda a: (a["d_add"], a["d_add_offsets"], 2, 8, a["d_leaves_new"], a["d_offsets_new"], a["d_levels_new"], a["d_roots"],  # noqa: E731
+                      a["d_n_bad"], a["d_n_hashed"])
+    source = lambda a, w: (a["d_leaves_" + w], a["d_offsets_" + w], 2, 4, a["d_levels_" + w], a["d_roots_" + w])  # noqa: E731
+    sources = {"%s_%s" % (k, w): dev(n=256 if k == "d_levels" else 64) for w in "ab" for k in ("d_leaves", "d_offsets", "d_levels", "d_roots")}
+    state = dict(d_counts=dev(), d_frontier=dev(), d_roots=dev())
+    frontier = lambda a: (tag, a["d_counts"], a["d_frontier"], a["d_roots"], 2, 4, a["d_add"], a["d_add_offsets"])  # noqa: E731
+    opening = dict(d_siblings=dev(), d_positions=dev(u8), d_depths=dev(u8))
+    return {
+        "forest_ragged_journal_bound": ("forest_ragged_journal_bound", lambda a: (16, 2, 4, 2), {}),  # (no buffer)
+        "forest_ragged_update_journaled_device": ("forest_ragged_update_journaled_device_into", lambda a: (
+            tag, *built(a), a["d_tree_ids"], a["d_leaf_ids"], a["d_new_leaves"], 2, a["d_journal_ids"], a["d_journal_values"], 4,
+            a["d_journal_len"], a["d_roots"], a["d_n_bad"], a["d_n_hashed"]),
+            dict(forest, d_tree_ids=dev(i32), d_leaf_ids=dev(), d_new_leaves=dev(), **journal, d_roots=dev(), d_n_bad=dev(i32), d_n_hashed=dev())),
+        "forest_ragged_journal_swap_device": ("forest_ragged_journal_swap_device_into", lambda a: (
+            *built(a), a["d_journal_ids"], a["d_journal_values"], 4, a["d_journal_len"], a["d_roots"], a["d_n_bad"]),
+            dict(forest, **journal, d_roots=dev(), d_n_bad=dev(i32))),
+        "forest_ragged_append_device": ("forest_ragged_append_device_into", lambda a: (tag, *built(a), *grow(a)), grown),
+        "forest_ragged_resize_device": ("forest_ragged_resize_device_into", lambda a: (tag, *built(a), a["d_keep"], *grow(a)),
+                                        dict(grown, d_keep=dev())),
+        "forest_ragged_select_device": ("forest_ragged_select_device_into", lambda a: (
+            source(a, "a"), source(a, "b"), a["d_pick"], 2, a["d_leaves_new"], a["d_offsets_new"], a["d_levels_new"], a["d_roots_new"], a["d_n_bad"]),
+            dict(sources, d_pick=dev(), **new, d_roots_new=dev(), d_n_bad=dev(i32))),
+        "forest_frontier_bound": ("forest_frontier_bound", lambda a: (4,), {}),  # (no buffer)
+        "forest_frontier_append_device": ("forest_frontier_append_device_into", lambda a: (*frontier(a), a["d_n_bad"], a["d_n_hashed"]),
+                                          dict(state, d_add=dev(), d_add_offsets=dev(), d_n_bad=dev(i32), d_n_hashed=dev())),
+        "forest_frontier_append_witness_device": ("forest_frontier_append_witness_device_into", lambda a: (
+            *frontier(a), a["d_wit_tree_ids"], a["d_wit_leaf_ids"], 2, a["d_wit_leaves"], a["d_wit_siblings"], a["d_wit_positions"],
+            a["d_wit_depths"], a["d_n_bad"], a["d_n_hashed"], a["d_n_bad_witness"]),
+            dict(state, d_add=dev(), d_add_offsets=dev(), d_wit_tree_ids=dev(i32), d_wit_leaf_ids=dev(), d_wit_leaves=dev(), d_wit_siblings=dev(),
+                 d_wit_positions=dev(u8), d_wit_depths=dev(u8), d_n_bad=dev(i32), d_n_hashed=dev(), d_n_bad_witness=dev(i32))),
+        "forest_frontier_extract_device": ("forest_frontier_extract_device_into", lambda a: (
+            *built(a), a["d_roots_forest"], 4, a["d_counts"], a["d_frontier"], a["d_roots"], a["d_n_bad"]),
+            dict(forest, d_roots_forest=dev(), **state, d_n_bad=dev(i32))),
+        "forest_ragged_consistency_device": ("forest_ragged_consistency_device_into", lambda a: (
+            *built(a), a["d_tree_ids"], a["d_old_counts"], 2, a["d_new_counts_out"], a["d_leaves_out"], a["d_siblings"], a["d_positions"],
+            a["d_depths"], a["d_n_bad"]),
+            dict(forest, d_tree_ids=dev(i32), d_old_counts=dev(), d_new_counts_out=dev(), d_leaves_out=dev(), **opening, d_n_bad=dev(i32))),
+        "forest_consistency_verify_device": ("forest_consistency_verify_device_into", lambda a: (
+            tag, a["d_old_counts"], a["d_old_roots"], a["d_new_counts"], a["d_new_roots"], a["d_leaves"], a["d_siblings"], a["d_positions"],
+            a["d_depths"], 2, 2, a["d_ok"], a["d_tree_ids"], 2, a["d_old_roots_out"], a["d_new_roots_out"], a["d_n_hashed"]),
+            dict(d_old_counts=dev(), d_old_roots=dev(), d_new_counts=dev(), d_new_roots=dev(), d_leaves=dev(), **opening, d_ok=dev(u8),
+                 d_tree_ids=dev(i32), d_old_roots_out=dev(), d_new_roots_out=dev(), d_n_hashed=dev())),
+        "forest_ragged_anchor_openings_device": ("forest_ragged_anchor_openings_device_into", lambda a: (
+            tag, *built(a), a["d_anchor_tree_ids"], a["d_anchor_counts"], 2, a["d_anchor_ids"], a["d_leaf_ids"], 2, a["d_anchor_roots"],
+            a["d_anchor_depths"], a["d_leaves_out"], a["d_siblings"], a["d_positions"], a["d_depths"], a["d_n_bad_anchors"], a["d_n_bad"],
+            a["d_n_hashed"]),
+            dict(forest, d_anchor_tree_ids=dev(i32), d_anchor_counts=dev(), d_anchor_ids=dev(i32), d_leaf_ids=dev(), d_anchor_roots=dev(),
+                 d_anchor_depths=dev(u8), d_leaves_out=dev(), **opening, d_n_bad_anchors=dev(i32), d_n_bad=dev(i32), d_n_hashed=dev())),
+        "forest_ragged_multiproof_bound": ("forest_ragged_multiproof_bound", lambda a: (16, 2, 4, 2), {}),  # (no buffer)
+        "forest_ragged_multiproof_device": ("forest_ragged_multiproof_device_into", lambda a: (
+            *built(a), a["d_tree_ids"], a["d_leaf_ids"], 2, a["d_leaves_out"], a["d_proof"], a["d_proof_offsets"], a["d_n_bad"]),
+            dict(forest, d_tree_ids=dev(i32), d_leaf_ids=dev(), d_leaves_out=dev(), d_proof=dev(), d_proof_offsets=dev(), d_n_bad=dev(i32))),
+        "forest_ragged_multiproof_verify_device": ("forest_ragged_multiproof_verify_device_into", lambda a: (
+            tag, a["d_offsets"], 16, 2, 4, a["d_tree_ids"], a["d_leaf_ids"], a["d_leaves_in"], 2, a["d_proof"], 4, a["d_proof_offsets"],
+            a["d_roots"], a["d_ok"], a["d_roots_out"], a["d_n_hashed"], a["d_n_bad"]),
+            dict(d_offsets=dev(), d_tree_ids=dev(i32), d_leaf_ids=dev(), d_leaves_in=dev(), d_proof=dev(), d_proof_offsets=dev(), d_roots=dev(),
+                 d_ok=dev(u8), d_roots_out=dev(), d_n_hashed=dev(), d_n_bad=dev(i32))),
+        "path_batch_device": ("path_batch_device", lambda a: (tag, a["d_leaves"], a["d_siblings"], a["d_positions"], 2, a["d_roots"], 2),
+                              dict(d_leaves=dev(), d_siblings=dev(), d_positions=dev(), d_roots=dev())),
+    }
+
+
 def arity_cases(c):
     """{method of Context that takes arity=: (the stem of its C entry points p252_merkle{4,2}_<stem>, the call, its arguments)}.  A
     forest's d_leaves is 16 scalars long, which sets the bound of its d_levels: 16 // (arity - 1) + n_trees * depth scalars."""
@@ -51,7 +123,10 @@ def arity_cases(c):
     i32, u8 = torch.int32, torch.uint8
     forest = dict(d_leaves=dev(), d_offsets=dev(), d_levels=dev(n=256))
     opening = dict(d_leaves=dev(), d_siblings=dev(), d_positions=dev(u8), d_depths=dev(u8))
+    published = {"merkle_" + stem: (c_stem, lambda a, arity, m=getattr(c, "merkle_" + stem), p=positional: m(*p(a), arity=arity), tensors)
+                 for stem, (c_stem, positional, tensors) in per_arity_cases().items()}
     return {
+        **published,
         "merkle4_forest_device": ("forest_device", lambda a, arity: c.merkle4_forest_device(
             tag, a["d_leaves"], 2, 4, a["d_roots"], a["d_levels"], arity=arity), dict(d_leaves=dev(), d_roots=dev(), d_levels=dev())),
         "merkle_forest_ragged": ("forest_ragged", lambda a, arity: c.merkle_forest_ragged(
@@ -151,9 +226,10 @@ def cases():
     ]
 
 
-# the tensors of cases(): 67 in the rows that take an arity, once per arity, and 73 in the others (the 68 of the round-5 surface and
-# the 5 of hash_ragged_device with truncated=True)
-N_REFUSED = 2 * 67 + 73
+# the tensors of cases(): in the rows that take an arity, once per arity, the 67 of the twelve older methods and those of
+# per_arity_cases() in its order (the three _bound rows have none); 73 in the others (the 68 of the round-5 surface and the 5 of
+# hash_ragged_device with truncated=True)
+N_REFUSED = 2 * (67 + (0 + 12 + 8 + 11 + 12 + 14 + 0 + 7 + 14 + 8 + 11 + 13 + 16 + 0 + 9 + 11 + 4)) + 73
 
 
 def test_every_device_pointer_refuses_a_cpu_tensor(recorder):
@@ -179,7 +255,7 @@ def test_every_arity_parameter_refuses_what_is_not_4_or_2(recorder):
     from poseidon252_amd import Context
     calls = arity_cases(_no_device_context())
     methods = [name for name, m in inspect.getmembers(Context, inspect.isfunction) if "arity" in inspect.signature(m).parameters]
-    assert sorted(m for m in methods if not m.startswith("_")) == sorted(calls) and len(calls) == 12, (methods, sorted(calls))
+    assert sorted(m for m in methods if not m.startswith("_")) == sorted(calls) and len(calls) == 29, (methods, sorted(calls))
     for name, (stem, call, args) in calls.items():
         cpu = {k: None for k in args}  # no tensor at all: the arity is refused first
         for arity in (3, 0, 8, None):
@@ -187,6 +263,40 @@ def test_every_arity_parameter_refuses_what_is_not_4_or_2(recorder):
                 with pytest.raises(ValueError, match="%s: arity must be 4 or 2, not %r" % (name, arity)):
                     call(a, arity)
     assert recorder.calls == []
+
+
+def test_per_arity_names_are_the_arity_methods(recorder, monkeypatch):
+    """Context.merkle{4,2}_<stem>, made from one table, is merkle_<stem>(..., arity=): a function with that signature less arity=, which
+    hands the same arguments to the same C symbol, p252_merkle<arity>_<C stem>, and takes no arity= of its own"""
+    import inspect
+    from poseidon252_amd import Context, _lib, hash as H
+    seen = []
+
+    class Spy:
+        def __getattr__(self, name):
+            if name in HOST_HELPERS:
+                return getattr(recorder.real, name)
+            return lambda *a: seen.append((name, tuple(ctypes.cast(v, ctypes.c_void_p).value if isinstance(v, ctypes._Pointer) else v
+                                                       for v in a))) or 0
+    monkeypatch.setattr(_lib, "_lib", Spy())
+    c, rows = _no_device_context(), per_arity_cases()
+    assert sorted(rows) == sorted(H._PER_ARITY_STEMS) and len(rows) == 17
+    for stem, (c_stem, positional, tensors) in rows.items():
+        unified = getattr(Context, "merkle_" + stem)
+        params = list(inspect.signature(unified).parameters.values())
+        assert params[-1].name == "arity" and params[-1].default == 4, stem
+        for arity in (4, 2):
+            name = "merkle%d_%s" % (arity, stem)
+            m = getattr(Context, name)
+            assert inspect.isfunction(m) and m.__name__ == name and m.__qualname__ == "Context." + name and "merkle_" + stem in m.__doc__
+            assert list(inspect.signature(m).parameters.values()) == params[:-1], name
+            getattr(c, name)(*positional(tensors))
+            unified(c, *positional(tensors), arity=arity)
+            assert len(seen) == 2 and seen[0] == seen[1] and seen[0][0] == "p252_merkle%d_%s" % (arity, c_stem), (name, seen)
+            del seen[:]
+            with pytest.raises(TypeError, match="arity"):
+                getattr(c, name)(*positional(tensors), arity=arity)
+            assert seen == []
 
 
 def test_refusals_survive_python_O():

@@ -258,8 +258,9 @@ def test_public_methods_are_per_arity_without_an_arity_parameter():
         for stem in STEMS:
             m = getattr(Context, "merkle%d_forest_ragged_%s" % (arity, stem))
             assert "arity" not in inspect.signature(m).parameters, m
-    for stem in STEMS[1:]:  # one private body each, which takes the arity's table
-        assert list(inspect.signature(getattr(Context, "_forest_ragged_" + stem)).parameters)[:3] == ["self", "f", "a"]
+    for stem in STEMS:  # one method each behind the two names, which takes the arity last
+        last = list(inspect.signature(getattr(Context, "merkle_forest_ragged_" + stem)).parameters.values())[-1]
+        assert last.name == "arity" and last.default == 4, stem
     import poseidon252_amd as P
     from poseidon252_amd import merkle as M
     assert list(inspect.signature(M.forest_ragged_update_journaled).parameters) == [
