@@ -302,7 +302,12 @@ int p252_from_bytes_device(p252_ctx* ctx, const void* d_bytes, void* d_scalars, 
  * level l, node = Hash::digest(Domain::Merkle4, children) where children[positions[l]] is the value
  * coming from below and the 3 siblings fill the other slots in order.  Layouts: leaves[n],
  * siblings[n][depth][3] scalars, positions[n][depth] bytes in 0..3, roots[n].  depth == 0 copies the
- * leaves.  positions outside 0..3 -> P252_ERR_INVALID_ARGUMENT (host variant; the device variant masks). */
+ * leaves.  positions outside 0..3 -> P252_ERR_INVALID_ARGUMENT (host variant; the device variant masks).
+ * THE POSITION BYTE (every device call that re-hashes an opening: p252_merkle{4,2}_path_batch_device, _path_ragged_device,
+ * _verify_batch_device, _forest_ragged_verify_device): only the low two bits of a position byte are read (arity 2: the low bit), so
+ * a byte of 5 re-hashes — and verifies — as 1; the extraction calls write values below the arity only.  A caller for whom the
+ * byte itself is a claim must check its high bits.  p252_merkle{4,2}_forest_consistency_verify_device_into alone compares whole
+ * bytes: a position byte with a high bit set is refused there. */
 int p252_merkle4_path_batch(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* siblings,
                             const uint8_t* positions, size_t depth, uint64_t* roots, size_t n);
 int p252_merkle4_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
@@ -386,7 +391,8 @@ int p252_merkle4_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_l
                                  void* d_leaves_out, void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream);
 /* The arity-2 twins (Domain::Merkle2 trees as p252_merkle2_tree_device builds them; pass the Merkle2 tag): ONE sibling per level —
  * d_siblings[k][depth], d_positions[k][depth] in 0..1 (1 = the path's node is the right child), depth = p252_merkle2_depth(n_leaves);
- * p252_merkle2_path_batch_device re-hashes n such openings (depth sequential Hash::digest(Domain::Merkle2, [left, right]) per lane). */
+ * p252_merkle2_path_batch_device re-hashes n such openings (depth sequential Hash::digest(Domain::Merkle2, [left, right]) per lane); of a
+ * position byte it reads the low bit only (THE POSITION BYTE, at p252_merkle4_path_batch_device). */
 size_t p252_merkle2_depth(size_t n_leaves);
 int p252_merkle2_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
                                  void* d_leaves_out, void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream);
@@ -395,8 +401,9 @@ int p252_merkle2_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const v
 
 /* Opening::verify in bulk (the downstream poseidon-merkle verifier, AGENTS.md:62-66): the n openings are re-hashed exactly as
  * p252_merkle{4,2}_path_batch_device does and each result is compared with the ONE expected root at d_root (32 bytes, device):
- * d_ok[i] = 1 iff opening i leads to that root — n bytes leave the device instead of n x 32.  The recomputed roots live in the
- * context's scratch of `hip_stream`.  Asynchronous. */
+ * d_ok[i] = 1 iff opening i leads to that root — n bytes leave the device instead of n x 32.  Position bytes are masked as there
+ * (THE POSITION BYTE, at p252_merkle4_path_batch_device).  The recomputed roots live in the context's scratch of `hip_stream`.
+ * Asynchronous. */
 int p252_merkle4_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
                                      const void* d_positions, size_t depth, const void* d_root, void* d_ok, size_t n, void* hip_stream);
 int p252_merkle2_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
@@ -477,7 +484,8 @@ int p252_merkle2_forest_ragged_openings_device(p252_ctx* ctx, const void* d_leav
                                                size_t k, void* d_leaves_out, void* d_siblings, void* d_positions, void* d_depths,
                                                void* d_n_bad, void* hip_stream);
 /* The re-hash with a depth per opening: d_roots_out[i] = the root recomputed from the first d_depths[i] levels of opening i (the
- * layout above at stride_depth <= 64; the rows past the depth are not read).  d_depths[i] == 0 copies the leaf; d_depths[i] >
+ * layout above at stride_depth <= 64; the rows past the depth are not read; position bytes are masked: THE POSITION BYTE, at
+ * p252_merkle4_path_batch_device).  d_depths[i] == 0 copies the leaf; d_depths[i] >
  * stride_depth (the 0xFF of a bad opening included) writes a zero root and is counted in *d_n_bad (zeroed by the caller; may be
  * NULL).  With d_depths[i] == stride_depth everywhere the roots are those of p252_merkle{4,2}_path_batch_device.  The openings are
  * sorted by depth on the device first (a wave runs to its deepest lane; P252_RAGGED_SORT=0 turns that off); the order lives in the
@@ -489,7 +497,8 @@ int p252_merkle2_path_ragged_device(p252_ctx* ctx, const uint64_t tag[4], const 
                                     const void* d_positions, const void* d_depths, size_t stride_depth, void* d_roots_out, size_t k,
                                     void* d_n_bad, void* hip_stream);
 /* Opening::verify across a forest: d_ok[i] = 1 iff d_depths[i] <= stride_depth, d_tree_ids[i] < n_trees and opening i re-hashes to
- * d_roots[d_tree_ids[i]] (the n_trees roots of the build, device) — k bytes leave the device.  The recomputed roots live in the
+ * d_roots[d_tree_ids[i]] (the n_trees roots of the build, device) — k bytes leave the device; the re-hash is that of
+ * p252_merkle{4,2}_path_ragged_device, masked position bytes included.  The recomputed roots live in the
  * context's scratch of this stream, as in p252_merkle{4,2}_verify_batch_device.  Asynchronous. */
 int p252_merkle4_forest_ragged_verify_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves_in, const void* d_siblings,
                                              const void* d_positions, const void* d_depths, size_t stride_depth, const void* d_tree_ids,
@@ -756,7 +765,8 @@ int p252_merkle2_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n
 /* Verification: the structure is derived from (n_leaves, d_indices) alone; every node of S_1, S_2, .. is hashed ONCE with
  * Hash::digest(Domain::Merkle4 / Merkle2, children) (pass that domain's tag), each child taken from the level below, from the
  * proof stream, or as zero.  *d_ok (device, 1 byte) = 1 iff no position is bad, the structure consumes exactly proof_len scalars,
- * and the recomputed root equals *d_root (device, 1 scalar); 0 otherwise.  Positions and proof are untrusted: nothing is read at
+ * and the recomputed root equals *d_root (device, 1 scalar); 0 otherwise (n_leaves == 1: the leaf IS the root and is compared as
+ * the 32 bytes it is, so leaf + p is refused; the forest call below compares it mod p).  Positions and proof are untrusted: nothing is read at
  * or past proof_len or k whatever they contain.  d_root_out (device, 1 scalar; may be NULL) receives the recomputed root when the
  * first two conditions hold and is left alone otherwise; *d_n_hashed (device uint64, 8-byte aligned; may be NULL) receives the
  * digests computed, sum over l >= 1 of |S_l| (0 after a bad position); *d_n_bad as above.  d_proof may be NULL when

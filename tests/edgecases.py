@@ -333,29 +333,11 @@ def sponges(run, n, shapes, truncated=False, seed=0x4000):
 
 
 # ---------------------------------------------------------------------------------------------- openings re-hashed
-def _children(cur, sib_level, pos_level, arity):
-    """the node's children: the siblings in ascending slot order with `cur` inserted at its position"""
-    n = cur.shape[0]
-    ch = np.empty((n, arity, 4), dtype=np.uint64)
-    rows = np.arange(n)
-    for s in range(arity):
-        si = np.minimum(np.where(s > pos_level, s - 1, s), arity - 2)
-        ch[:, s] = np.where((pos_level == s)[:, None], cur, sib_level[rows, si])
-    return ch
-
-
 def rehash(tag_red, arity, leaves, sib, pos, depths=None):
-    """roots of openings, level by level through oracle.hash_batch (opening i stops after depths[i] levels) — on reduced values"""
-    cur = np.array(leaves, dtype=np.uint64).reshape(-1, 4)
-    n, depth = cur.shape[0], pos.shape[1]
-    sib = np.asarray(sib, dtype=np.uint64).reshape(n, depth, arity - 1, 4)
-    for l in range(depth):
-        live = np.arange(n) if depths is None else np.nonzero(depths > l)[0]
-        if live.size == 0:
-            break
-        ch = _children(cur[live], sib[live, l], pos[live, l].astype(np.int64), arity)
-        cur[live] = oracle.hash_batch(tag_red, ch, arity, 1, threads=ORACLE_THREADS).reshape(-1, 4)
-    return cur
+    """roots of openings, level by level through oracle.hash_batch (opening i stops after depths[i] levels) — on reduced values; the
+    re-hash itself is testsupport/soundness.py's, the one numpy model of an opening"""
+    from testsupport.soundness import rehash as model_rehash
+    return model_rehash(lambda ch: oracle.hash_batch(tag_red, ch, arity, 1, threads=ORACLE_THREADS), arity, leaves, sib, pos, depths)
 
 
 def paths(run, n, depth, arity, seed=0x5000):

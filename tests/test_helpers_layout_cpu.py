@@ -98,6 +98,6 @@ def test_the_geometry_and_the_clock_probe_are_defined_once():
 def test_treeshape_and_the_models_ask_neither_the_library_nor_tests_nor_tools():
     support = _support_sources()
     assert "poseidon252_amd" not in support[os.path.join("testsupport", "treeshape.py")]
-    for name in ("treeshape.py", "forestappend.py", "forestupdate.py", "multiproofmodel.py"):
+    for name in ("treeshape.py", "forestappend.py", "forestupdate.py", "multiproofmodel.py", "soundness.py"):
         imports = re.findall(r"^[ \t]*(?:from|import)[ \t]+([\w.]+)", support[os.path.join("testsupport", name)], re.M)
         assert set(imports) <= {"numpy", ".", ".treeshape"}, (name, imports)

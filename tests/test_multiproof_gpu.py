@@ -9,6 +9,7 @@ from helpers.forest import SENTINEL, _build, _np, _single_extract as _extract, _
 from helpers.percall import build_cpp_mirror, run_cpp_mirror
 from testsupport.device import tree_device
 from testsupport.multiproofmodel import multiproof_counts, multiproof_extract  # (the numpy model; tests/test_multiproof_cpu.py checks it)
+from testsupport.soundness import index_sets as _index_sets  # (the position sets: the soundness sweep's too)
 from testsupport import treeshape as TS
 
 pytestmark = pytest.mark.gpu
@@ -52,14 +53,6 @@ def _round_trip(ctx, arity, n, pos):
     assert (ok, hashed, bad) == (1, want_hashed, 0)
     assert root_out is not None and np.array_equal(root_out, root)
     return out, proof[:plen]
-
-
-def _index_sets(n, arity):
-    last_pair = (n - 1) // arity * arity  # the last parent's first child; with its neighbour when the tree has one
-    pair = [last_pair, last_pair + 1] if last_pair + 1 < n else [0, 1] if n > 1 else [0]
-    sets = {"first": [0], "last": [n - 1], "ends": sorted({0, n - 1}), "one parent": pair, "every other": list(range(0, n, 2)),
-            "all": list(range(n))}
-    return sets
 
 
 SHAPES = [(4, n) for n in (1, 2, 4, 5, 16, 17, 21, 64, 1000)] + [(2, n) for n in (1, 2, 3, 7, 33, 1000)]
