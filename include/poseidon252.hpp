@@ -444,7 +444,8 @@ namespace detail {
     X(N, forest_ragged_multiproof_verify_device_into) X(N, forest_frontier_bound) X(N, forest_frontier_append_device_into)                \
     X(N, forest_frontier_extract_device_into) X(N, forest_frontier_append_witness_device_into)                                            \
     X(N, forest_ragged_consistency_device_into) X(N, forest_consistency_verify_device_into)                                              \
-    X(N, forest_ragged_anchor_openings_device_into)
+    X(N, forest_ragged_anchor_openings_device_into) X(N, forest_range_stride) X(N, forest_ragged_range_proofs_device_into)               \
+    X(N, forest_range_verify_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -877,6 +878,50 @@ inline void merkle_forest_ragged_anchor_openings_device(const ForestView& forest
                                                               anchors.d_depths, openings.d_leaves, openings.d_siblings, openings.d_positions,
                                                               openings.d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_anchor_openings_device");
+}
+
+// Runs (p252_merkle{4,2}_forest_range_stride, _forest_ragged_range_proofs_device_into, _forest_range_verify_device_into): whole runs of
+// leaves [first, first + len) of the trees of a built forest proved by closed-form proofs and checked, many runs of many trees in one
+// call.  Run r is tree d_tree_ids[r] (uint32), leaves d_first[r] (uint64) .. with len = d_leaf_offsets[r + 1] - d_leaf_offsets[r]
+// (m + 1 uint64, k leaves in all, flat at those offsets).  Row r of the proofs (m rows of merkle_forest_range_stride(max_leaves, arity)
+// scalars) is byte for byte the shared proof of merkle_multiproof_device for the run's positions, zeros behind it; a bad run: a zero
+// row, length 0xFFFFFFFF, count 0, one count in *d_n_bad.  The verification needs no forest, only the claimed leaf counts.
+inline std::size_t merkle_forest_range_stride(std::size_t max_leaves, unsigned arity = 4) {
+    return detail::merkle_abi("merkle_forest_range_stride", arity).forest_range_stride(max_leaves);
+}
+struct ForestRuns {
+    const void* d_tree_ids;      // m uint32
+    const void* d_first;         // m uint64
+    const void* d_leaf_offsets;  // m + 1 uint64
+    std::size_t m, k;
+};
+struct RangeProofs {
+    void* d_leaves;      // k scalars (extraction: may be null)
+    void* d_proof;       // m x stride scalars
+    std::size_t stride;  // scalars a row (extraction writes at merkle_forest_range_stride(forest.max_leaves, arity))
+    void* d_proof_lens;  // m uint32
+    void* d_counts;      // m uint64: the leaf count of every run's tree
+};
+inline void merkle_forest_ragged_range_proofs_device(const ForestView& forest, const ForestRuns& runs, const RangeProofs& out, unsigned arity = 4,
+                                                     Context& ctx = Context::default_context(), void* d_n_bad = nullptr,
+                                                     void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_range_proofs_device", arity);
+    detail::check(m.forest_ragged_range_proofs_device_into(ctx.get(), forest.d_leaves, forest.n_leaves, forest.d_offsets, forest.n_trees,
+                                                           forest.max_leaves, forest.d_levels, runs.d_tree_ids, runs.d_first,
+                                                           runs.d_leaf_offsets, runs.m, runs.k, out.d_leaves, out.d_proof, out.d_proof_lens,
+                                                           out.d_counts, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_ragged_range_proofs_device");
+}
+// d_ok[r] (uint8) = 1 iff run r, with its leaves and row r of the proofs, re-hashes to d_roots[d_tree_ids[r]] (n_trees roots)
+inline void merkle_forest_range_verify_device(const ForestRuns& runs, const RangeProofs& proofs, std::size_t max_leaves, const void* d_roots,
+                                              std::size_t n_trees, void* d_ok, unsigned arity = 4, Context& ctx = Context::default_context(),
+                                              void* d_roots_out = nullptr, void* d_n_hashed = nullptr, void* d_n_bad = nullptr,
+                                              void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_range_verify_device", arity);
+    detail::check(m.forest_range_verify_device_into(ctx.get(), m.tag().data(), runs.d_tree_ids, proofs.d_counts, runs.d_first, runs.d_leaf_offsets,
+                                                    runs.m, max_leaves, proofs.d_leaves, runs.k, proofs.d_proof, proofs.stride,
+                                                    proofs.d_proof_lens, d_roots, n_trees, d_ok, d_roots_out, d_n_hashed, d_n_bad, stream),
+                  ctx.get(), "merkle_forest_range_verify_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

@@ -129,7 +129,11 @@ extern "C" {
  *      messages of different lengths in one call;
  *      + p252_merkle{4,2}_forest_ragged_anchor_openings_device_into (additive, same version; `_into`: every result goes into buffers
  *      the caller owns): the roots the trees of such a forest had at earlier leaf counts, and openings of their leaves against
- *      those roots, with no second copy of the forest */
+ *      those roots, with no second copy of the forest;
+ *      + p252_merkle{4,2}_forest_range_stride, p252_merkle{4,2}_forest_ragged_range_proofs_device_into,
+ *      p252_merkle{4,2}_forest_range_verify_device_into (additive, same version; `_into`: every result goes into buffers the caller
+ *      owns): whole runs of leaves [a, b) of the trees of such a forest proved by closed-form proofs and checked, many runs of many
+ *      trees in one call */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -1075,6 +1079,68 @@ int p252_merkle2_forest_ragged_anchor_openings_device_into(p252_ctx* ctx, const 
                                                            void* d_anchor_depths, void* d_leaves_out, void* d_siblings, void* d_positions,
                                                            void* d_depths, void* d_n_bad_anchors, void* d_n_bad, void* d_n_hashed,
                                                            void* hip_stream);
+
+/* ---- runs: whole runs of leaves of the trees of a ragged forest, proved and checked in one call.  What the readers of a log fetch is
+ * chunks: leaves [a, b) of a tree, checked against a root they trust.  Run r is leaves [a, a + len) of tree d_tree_ids[r] (uint32[m])
+ * with a = d_first[r] (uint64[m]) and len = d_leaf_offsets[r + 1] - d_leaf_offsets[r] (uint64[m + 1]); its leaves sit at
+ * d_leaf_offsets[r] of a flat array of k scalars, the layout of the ragged hash.  With A the arity, a_l = floor(a / A^l),
+ * b_l = ceil(b / A^l) and w_l = ceil(n_t / A^l), the nodes of level l that a verifier knows or computes are the interval [a_l, b_l),
+ * and the proof holds, level by level from the leaves up, the nodes [A a_{l+1}, a_l) left of it and then [b_l, min(A b_{l+1}, w_l))
+ * right of it: at most 2 (A - 1) scalars a level.  That is byte for byte the proof p252_merkle{4,2}_multiproof_device writes for the
+ * positions a .. b - 1 of the tree, and p252_merkle{4,2}_multiproof_verify_device accepts it; a run [0, n_t) has an empty proof.
+ * A run is BAD when its leaf offsets are bad by the ragged forest's rule for tree offsets with k in the place of n_leaves (decreasing,
+ * past k, the cumulative length of the runs before it and itself above k), len == 0, the tree id is >= n_trees, the tree is bad
+ * (verification: the claimed count is not in 1 .. max_leaves), or a + len > n_t. */
+/* P = 2 (arity - 1) * p252_merkle{4,2}_depth(max_leaves) scalars: room for the proof of any run of a tree of at most max_leaves leaves */
+size_t p252_merkle4_forest_range_stride(size_t max_leaves);
+size_t p252_merkle2_forest_range_stride(size_t max_leaves);
+/* EXTRACTION (no hashing) out of a forest p252_merkle{4,2}_forest_ragged_device built with d_levels: d_leaves, n_leaves, d_offsets,
+ * n_trees, max_leaves, d_levels exactly as the build took and filled them.  Row r of d_proof ([m][P] scalars, P = the stride above)
+ * receives the proof of run r and zeros behind it, d_proof_lens[r] (uint32[m]) its length in scalars, d_counts_out[r] (uint64[m])
+ * n_t, and d_leaves_out (k scalars, may be NULL), at d_leaf_offsets[r], the run's leaves byte for byte.  A BAD run: a zero row,
+ * length 0xFFFFFFFF, count 0, no leaf written, counted once in *d_n_bad (device uint32 the caller has zeroed; may be NULL); its
+ * neighbours are untouched.
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: m, k, n_leaves, n_trees or max_leaves == 0; k, m, k + 2 m or max_leaves >= 2^32
+ * (record words are 32-bit); a NULL or misaligned buffer (scalars 16 bytes, d_offsets, d_first, d_leaf_offsets and d_counts_out 8,
+ * d_tree_ids, d_proof_lens and d_n_bad 4; d_levels and d_proof may be NULL when max_leaves == 1); size overflow.  Asynchronous on
+ * hip_stream, no host synchronisation; scratch of the calling stream (covered by p252_trim / p252_wipe): the forest's index
+ * (16 bytes a tree), the runs' index and counts (32 bytes a run), 1 KiB. */
+int p252_merkle4_forest_ragged_range_proofs_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                        size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                        const void* d_first, const void* d_leaf_offsets, size_t m, size_t k,
+                                                        void* d_leaves_out, void* d_proof, void* d_proof_lens, void* d_counts_out,
+                                                        void* d_n_bad, void* hip_stream);
+/* the same for arity 2 (the level layout of merkle2 trees) */
+int p252_merkle2_forest_ragged_range_proofs_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                        size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                        const void* d_first, const void* d_leaf_offsets, size_t m, size_t k,
+                                                        void* d_leaves_out, void* d_proof, void* d_proof_lens, void* d_counts_out,
+                                                        void* d_n_bad, void* hip_stream);
+/* VERIFICATION needs no forest, only the claimed leaf count of every run's tree: d_counts[r] (uint64[m]).  Every input is untrusted;
+ * nothing is read outside row r's proof_stride scalars of d_proof, the k scalars of d_leaves_in or the m entries of the per-run arrays.
+ * d_ok[r] (uint8[m]) = 1 iff run r is good against d_counts[r] (in 1 .. max_leaves), d_proof_lens[r] equals the closed-form length
+ * and that length is <= proof_stride, and the run re-hashes to d_roots[d_tree_ids[r]] (n_trees roots) as 32 bytes; a one-leaf tree's
+ * root is its leaf mod p, the forest's convention.  d_roots_out[r] ([m] scalars, may be NULL) is written when everything but the
+ * comparison holds.  *d_n_hashed (device uint64, may be NULL) is SET to the digests computed: the nodes of [a_l, b_l), l >= 1, summed
+ * over the runs that pass the first two conditions; a bad run is counted once in *d_n_bad (device uint32 the caller has zeroed; may
+ * be NULL).  A claimed count that differs from the tree's own and leaves every w_l on the run's path alone changes nothing.
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: m, k, n_trees or max_leaves == 0; k, m, k + 2 m or max_leaves >= 2^32; a NULL or
+ * misaligned buffer (scalars 16 bytes, d_counts, d_first, d_leaf_offsets and d_n_hashed 8, d_tree_ids, d_proof_lens and d_n_bad 4;
+ * d_proof may be NULL when proof_stride == 0); size overflow.  Asynchronous on hip_stream, no host synchronisation, one record
+ * launch and one digest launch per level of depth(max_leaves) whatever m is; scratch of the calling stream (covered by p252_trim /
+ * p252_wipe): (64 + 8 depth) bytes a run, 84 bytes per node of the widest level above the leaves — at most
+ * min(k + m, k / arity + 2 m) nodes —, 1 KiB. */
+int p252_merkle4_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_tree_ids, const void* d_counts,
+                                                 const void* d_first, const void* d_leaf_offsets, size_t m, size_t max_leaves,
+                                                 const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_stride,
+                                                 const void* d_proof_lens, const void* d_roots, size_t n_trees, void* d_ok,
+                                                 void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream);
+/* the same for arity 2 (pass the Merkle2 tag) */
+int p252_merkle2_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_tree_ids, const void* d_counts,
+                                                 const void* d_first, const void* d_leaf_offsets, size_t m, size_t max_leaves,
+                                                 const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_stride,
+                                                 const void* d_proof_lens, const void* d_roots, size_t n_trees, void* d_ok,
+                                                 void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

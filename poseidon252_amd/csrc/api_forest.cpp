@@ -1,5 +1,5 @@
 // api_forest.cpp — the ragged-forest family of the C ABI (include/poseidon252_hip.h): every entry point whose name holds
-// _forest_ragged_, _path_ragged_, _forest_frontier_ or _forest_consistency_, with the checks they share.  Host side only, as api.cpp:
+// _forest_ragged_, _path_ragged_, _forest_frontier_, _forest_consistency_ or _forest_range_, with the checks they share.  Host side only, as api.cpp:
 // argument rules and launch sequencing; the kernels are in the forest_*.hip files.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,7 @@
 #include "forest_multiproof.h"
 #include "forest_openings.h"
 #include "forest_ragged.h"
+#include "forest_range.h"
 #include "forest_update.h"
 #include "forest_witness.h"
 #include "kernels.h"
@@ -1060,6 +1061,117 @@ int p252_merkle2_forest_ragged_anchor_openings_device_into(p252_ctx* ctx, const 
     return forest_ragged_anchor_openings_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_anchor_tree_ids,
                                                 d_anchor_counts, m, d_anchor_ids, d_leaf_ids, k, d_anchor_roots, d_anchor_depths, d_leaves_out,
                                                 d_siblings, d_positions, d_depths, d_n_bad_anchors, d_n_bad, d_n_hashed, hip_stream);
+}
+
+// ---- whole runs of leaves of such a forest's trees proved and checked in one call (forest_range.hip): m runs [first, first + len) with
+// their k leaves flat behind d_leaf_offsets.  The proofs are closed forms, so the extraction is the forest's index, the runs' index
+// and a gather; the verification needs no forest: the runs' index, one count and one scan row per level, the records and widths of
+// one level in the first buffer, two lists of node values in the second — the pair of the calling stream ----
+size_t p252_merkle4_forest_range_stride(size_t max_leaves) { return forest_range_stride(4, max_leaves); }
+size_t p252_merkle2_forest_range_stride(size_t max_leaves) { return forest_range_stride(2, max_leaves); }
+
+// what both calls ask of (m, k, max_leaves): a run start in a value list and a node index are 32-bit record words
+static int forest_range_shape_check(p252_ctx* ctx, const std::string& who, size_t m, size_t k, size_t max_leaves, size_t n_trees) {
+    if (m == 0 || k == 0 || max_leaves == 0 || n_trees == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": m, k, n_trees and max_leaves must be > 0");
+    if (k > 0xffffffffu || m > 0xffffffffu || max_leaves > 0xffffffffu || (uint64_t)k + 2 * (uint64_t)m > 0xffffffffu)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k, m, k + 2 m and max_leaves must be below 2^32 (record words are 32-bit)");
+    return P252_OK;
+}
+
+static int forest_ragged_range_proofs_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                             size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                             const void* d_first, const void* d_leaf_offsets, size_t m, size_t k, void* d_leaves_out,
+                                             void* d_proof, void* d_proof_lens, void* d_counts_out, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_forest_ragged_range_proofs" : "merkle2_forest_ragged_range_proofs";
+    if (n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves must be > 0");
+    if (int rc = forest_range_shape_check(ctx, who, m, k, max_leaves, n_trees)) return rc;
+    const size_t stride = forest_range_stride(arity, max_leaves);
+    if (!d_leaves || !d_offsets || !d_tree_ids || !d_first || !d_leaf_offsets || !d_proof_lens || !d_counts_out ||
+        (stride && (!d_levels || !d_proof)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_first, 8) || misaligned_to(d_leaf_offsets, 8) || misaligned_to(d_counts_out, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets, d_first, d_leaf_offsets and d_counts_out must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_proof_lens, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids, d_proof_lens and d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestRangePlan plan = forest_range_plan(arity, max_leaves, m, k);
+    return with_forest_index(ctx, who, st, arity, d_offsets, n_trees, n_leaves, max_leaves, plan.extract_bytes, 0,
+                             [&](const uint64_t* ntree, const uint64_t* lo, char* work, void*) {
+                                 return launch_forest_range_proofs(plan, d_leaves, d_offsets, d_levels, ntree, lo, n_trees, d_tree_ids, d_first,
+                                                                   d_leaf_offsets, d_leaves_out, d_proof, d_proof_lens, d_counts_out, d_n_bad,
+                                                                   work, st);
+                             });
+}
+
+static int forest_range_verify_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_tree_ids, const void* d_counts,
+                                      const void* d_first, const void* d_leaf_offsets, size_t m, size_t max_leaves, const void* d_leaves_in,
+                                      size_t k, const void* d_proof, size_t proof_stride, const void* d_proof_lens, const void* d_roots,
+                                      size_t n_trees, void* d_ok, void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_forest_range_verify" : "merkle2_forest_range_verify";
+    if (int rc = forest_range_shape_check(ctx, who, m, k, max_leaves, n_trees)) return rc;
+    if (!tag || !d_tree_ids || !d_counts || !d_first || !d_leaf_offsets || !d_leaves_in || !d_proof_lens || !d_roots || !d_ok ||
+        (proof_stride && !d_proof))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves_in) || misaligned(d_proof) || misaligned(d_roots) || misaligned(d_roots_out))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_counts, 8) || misaligned_to(d_first, 8) || misaligned_to(d_leaf_offsets, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_counts, d_first, d_leaf_offsets and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_proof_lens, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids, d_proof_lens and d_n_bad must be 4-byte aligned");
+    // a proof offset (row times stride, plus a place in the row) is 60 bits of a record; the rows' bytes inside size_t
+    if (n_trees > SIZE_MAX / 32 || (proof_stride && m > (SIZE_MAX >> 8) / proof_stride))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestRangePlan plan = forest_range_plan(arity, max_leaves, m, k);
+    return with_stream_scratch(ctx, who, st, plan.verify_bytes, plan.values_bytes, [&](p252_ctx::LevelSet& set) {
+        return launch_forest_range_verify(ctx->d_tab, tag_arg(tag), plan, d_tree_ids, d_counts, d_first, d_leaf_offsets, d_leaves_in, d_proof,
+                                          proof_stride, d_proof_lens, d_roots, n_trees, d_ok, d_roots_out, d_n_hashed, d_n_bad, set.buf[0],
+                                          set.buf[1], st);
+    });
+}
+
+int p252_merkle4_forest_ragged_range_proofs_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                        size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                        const void* d_first, const void* d_leaf_offsets, size_t m, size_t k,
+                                                        void* d_leaves_out, void* d_proof, void* d_proof_lens, void* d_counts_out,
+                                                        void* d_n_bad, void* hip_stream) {
+    return forest_ragged_range_proofs_device(ctx, 4, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_first,
+                                             d_leaf_offsets, m, k, d_leaves_out, d_proof, d_proof_lens, d_counts_out, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_range_proofs_device_into(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_offsets,
+                                                        size_t n_trees, size_t max_leaves, const void* d_levels, const void* d_tree_ids,
+                                                        const void* d_first, const void* d_leaf_offsets, size_t m, size_t k,
+                                                        void* d_leaves_out, void* d_proof, void* d_proof_lens, void* d_counts_out,
+                                                        void* d_n_bad, void* hip_stream) {
+    return forest_ragged_range_proofs_device(ctx, 2, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_first,
+                                             d_leaf_offsets, m, k, d_leaves_out, d_proof, d_proof_lens, d_counts_out, d_n_bad, hip_stream);
+}
+
+int p252_merkle4_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_tree_ids, const void* d_counts,
+                                                 const void* d_first, const void* d_leaf_offsets, size_t m, size_t max_leaves,
+                                                 const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_stride,
+                                                 const void* d_proof_lens, const void* d_roots, size_t n_trees, void* d_ok,
+                                                 void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    return forest_range_verify_device(ctx, 4, tag, d_tree_ids, d_counts, d_first, d_leaf_offsets, m, max_leaves, d_leaves_in, k, d_proof,
+                                      proof_stride, d_proof_lens, d_roots, n_trees, d_ok, d_roots_out, d_n_hashed, d_n_bad, hip_stream);
+}
+
+int p252_merkle2_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t tag[4], const void* d_tree_ids, const void* d_counts,
+                                                 const void* d_first, const void* d_leaf_offsets, size_t m, size_t max_leaves,
+                                                 const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_stride,
+                                                 const void* d_proof_lens, const void* d_roots, size_t n_trees, void* d_ok,
+                                                 void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream) {
+    return forest_range_verify_device(ctx, 2, tag, d_tree_ids, d_counts, d_first, d_leaf_offsets, m, max_leaves, d_leaves_in, k, d_proof,
+                                      proof_stride, d_proof_lens, d_roots, n_trees, d_ok, d_roots_out, d_n_hashed, d_n_bad, hip_stream);
 }
 
 }  // (the C ABI)

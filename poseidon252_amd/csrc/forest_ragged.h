@@ -45,6 +45,12 @@ size_t forest_ragged_index_bytes(size_t n_trees);
 hipError_t launch_forest_ragged_index(unsigned arity, const void* offsets, size_t n_trees, size_t n_leaves, size_t max_leaves, void* meta,
                                       const uint64_t** ntree, const uint64_t** lo, hipStream_t st);
 
+// The build's three-pass scan over `rows` rows of n uint64 values each that the CALLER wrote (values[row * n + i]): in place, every value
+// becomes the sum of its row's values before it, and totals[row] (device) the row's sum.  tsum = rows * forest_scan_rows_tiles(n) words
+// of scratch.  Three launches whatever rows is.
+size_t forest_scan_rows_tiles(size_t n);
+hipError_t launch_forest_scan_rows(uint64_t* values, size_t rows, size_t n, unsigned long long* totals, uint64_t* tsum, hipStream_t st);
+
 // Trees of one or two BUILT forests gathered into a new compact forest (p252_merkle{4,2}_forest_ragged_select_device_into): nothing is
 // hashed, leaves, level blocks and roots move.  The relocation is balanced over tiles of FOREST_SELECT_MOVE_TILE scalars of the new
 // arrays, not over trees.

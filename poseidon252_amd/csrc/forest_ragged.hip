@@ -15,6 +15,8 @@
 //                      leaf, reduced).  Then over
 //                      every level l at once: C_l = the scan of s_l (row l), and LO = the scan of levels_len(n_t) (row 0,
 //                      only when the caller's d_levels is written).
+//   k_fr_rows_tile_sums / k_fr_rows_apply   the same three-pass scan (with k_fr_scan_tiles between them) over rows of values that
+//                      ANOTHER unit wrote — launch_forest_scan_rows: forest_range.hip's per-level node counts of its runs
 //   k_fr_block_first   per level and 256-node block b: the tree that holds node 256 b — so a digest lane looks for its tree
 //                      only between the first trees of its block and of the next one (<= 8 probes on a dense level)
 //   k_fr_digest / k_fr_digest_coop   lane (group of 8 lanes) g hashes node g of level l: t with C_l[t] <= g < C_l[t+1],
@@ -131,6 +133,42 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_scan_apply(uint64_t* __restrict
             if (t == n_trees - 1) Crow[n_trees] = run + v[k];
         }
         run += v[k];
+    }
+}
+
+// ---- the same scan over rows of values that a caller wrote (launch_forest_scan_rows): row blockIdx.y of v, n values a row, in place ----
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_rows_tile_sums(const uint64_t* __restrict__ v, size_t n, uint64_t* __restrict__ tsum) {
+    const uint64_t* __restrict__ row = v + (size_t)blockIdx.y * n;
+    const size_t t0 = (size_t)blockIdx.x * FR_TILE + (size_t)threadIdx.x * FR_ITEMS;
+    uint64_t sum = 0;
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k)
+        if (t0 + k < n) sum += row[t0 + k];
+    uint64_t total;
+    (void)block_exclusive<FR_BLOCK>(sum, &total);
+    if (threadIdx.x == 0) tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// v[row][i] becomes the sum of the row's values before i, totals[row] the row's sum
+__global__ void __launch_bounds__(FR_BLOCK) k_fr_rows_apply(uint64_t* __restrict__ v, size_t n, const uint64_t* __restrict__ tsum,
+                                                            unsigned long long* __restrict__ totals) {
+    uint64_t* __restrict__ row = v + (size_t)blockIdx.y * n;
+    const size_t t0 = (size_t)blockIdx.x * FR_TILE + (size_t)threadIdx.x * FR_ITEMS;
+    uint64_t x[FR_ITEMS], sum = 0;
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k) {
+        x[k] = t0 + k < n ? row[t0 + k] : 0ull;
+        sum += x[k];
+    }
+    uint64_t total;
+    uint64_t run = tsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive<FR_BLOCK>(sum, &total);
+#pragma unroll
+    for (unsigned k = 0; k < FR_ITEMS; ++k) {
+        const size_t t = t0 + k;
+        if (t >= n) break;
+        row[t] = run;
+        run += x[k];
+        if (t == n - 1) totals[blockIdx.y] = run;
     }
 }
 
@@ -408,6 +446,18 @@ hipError_t launch_forest_ragged_index(unsigned arity, const void* offsets, size_
     hipLaunchKernelGGL(k_fr_scan_tiles, dim3(1), blk, 0, st, tsum, (size_t)tiles);
     hipLaunchKernelGGL(k_fr_scan_apply<false>, dim3(tiles, 1), blk, 0, st, ntree, n, 0u, la, tsum, LO, (uint64_t)n_leaves, off,
                        (const Scalar32*)nullptr, (Scalar32*)nullptr, (unsigned*)nullptr);
+    return hipGetLastError();
+}
+
+size_t forest_scan_rows_tiles(size_t n) { return (n + FR_TILE - 1) / FR_TILE; }
+
+hipError_t launch_forest_scan_rows(uint64_t* values, size_t rows, size_t n, unsigned long long* totals, uint64_t* tsum, hipStream_t st) {
+    if (rows == 0 || n == 0) return hipSuccess;
+    const size_t tiles = forest_scan_rows_tiles(n);
+    const dim3 blk(FR_BLOCK), grid((unsigned)tiles, (unsigned)rows);
+    hipLaunchKernelGGL(k_fr_rows_tile_sums, grid, blk, 0, st, values, n, tsum);
+    hipLaunchKernelGGL(k_fr_scan_tiles, dim3((unsigned)rows), blk, 0, st, tsum, tiles);
+    hipLaunchKernelGGL(k_fr_rows_apply, grid, blk, 0, st, values, n, tsum, totals);
     return hipGetLastError();
 }
 

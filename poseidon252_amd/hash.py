@@ -1139,6 +1139,76 @@ def _publish_per_arity(cls, stems):
 _publish_per_arity(Context, _PER_ARITY_STEMS)
 
 
+# ---- whole runs of leaves of a ragged forest (p252_merkle{4,2}_forest_ragged_range_proofs_device_into, _forest_range_verify_device_into;
+# csrc/forest_range.hip): Context.merkle4_<call> and Context.merkle2_<call> take no arity=, each pair is made from one private
+# implementation; the arity-taking forms are merkle.forest_ragged_range_proofs / merkle.forest_range_verify ----
+def _forest_ragged_range_proofs_device(self, a, f, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_first, d_leaf_offsets, m, k,
+                                       d_proof, d_proof_lens, d_counts_out, d_leaves_out=None, d_n_bad=None):
+    forest, depth = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
+    stride = 2 * a.per * depth  # p252_merkle{4,2}_forest_range_stride
+    self._check(a.fn("forest_ragged_range_proofs_device_into")(
+        self._h, *forest, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, m * 4, elem=4), _dev_ptr(self, f, "d_first", d_first, m * 8, elem=8),
+        _dev_ptr(self, f, "d_leaf_offsets", d_leaf_offsets, (m + 1) * 8, elem=8), m, k,
+        _dev_ptr(self, f, "d_leaves_out", d_leaves_out, k * 32, null_ok=True),
+        _dev_ptr(self, f, "d_proof", d_proof, m * stride * 32, null_ok=stride == 0),
+        _dev_ptr(self, f, "d_proof_lens", d_proof_lens, m * 4, elem=4), _dev_ptr(self, f, "d_counts_out", d_counts_out, m * 8, elem=8),
+        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _stream(self)))
+
+
+def _forest_range_verify_device(self, a, f, tag, d_tree_ids, d_counts, d_first, d_leaf_offsets, m, max_leaves, d_leaves_in, k, d_proof,
+                                proof_stride, d_proof_lens, d_roots, n_trees, d_ok, d_roots_out=None, d_n_hashed=None, d_n_bad=None):
+    self._check(a.fn("forest_range_verify_device_into")(
+        self._h, _tag(tag), _dev_ptr(self, f, "d_tree_ids", d_tree_ids, m * 4, elem=4), _dev_ptr(self, f, "d_counts", d_counts, m * 8, elem=8),
+        _dev_ptr(self, f, "d_first", d_first, m * 8, elem=8), _dev_ptr(self, f, "d_leaf_offsets", d_leaf_offsets, (m + 1) * 8, elem=8), m,
+        max_leaves, _dev_ptr(self, f, "d_leaves_in", d_leaves_in, k * 32), k,
+        _dev_ptr(self, f, "d_proof", d_proof, m * proof_stride * 32, null_ok=proof_stride == 0), proof_stride,
+        _dev_ptr(self, f, "d_proof_lens", d_proof_lens, m * 4, elem=4), _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32), n_trees,
+        _dev_ptr(self, f, "d_ok", d_ok, m, elem=1), _dev_ptr(self, f, "d_roots_out", d_roots_out, m * 32, null_ok=True),
+        _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True), _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True),
+        _stream(self)))
+
+
+_RANGE_DOCS = {
+    "forest_ragged_range_proofs_device":
+        """the proofs of m whole runs of leaves out of a forest merkle_forest_ragged_device built with d_levels
+        (p252_merkle%d_forest_ragged_range_proofs_device_into; no hashing): d_leaves, d_offsets, n_trees, max_leaves, d_levels exactly as the
+        build took and filled them.  Run r is leaves [d_first[r], d_first[r] + len) of tree d_tree_ids[r] (int32/uint32; d_first
+        int64/uint64) with len = d_leaf_offsets[r + 1] - d_leaf_offsets[r] (m + 1 int64/uint64, k leaves in all).  Row r of d_proof
+        (m, P, 4), P = 2 (arity - 1) depth(max_leaves), receives the proof and zeros behind it, d_proof_lens (m,) int32/uint32 its
+        length, d_counts_out (m,) int64/uint64 the tree's leaf count, d_leaves_out (k, 4; optional) the runs' leaves at their offsets.
+        A bad run: a zero row, length 0xFFFFFFFF, count 0, counted in d_n_bad (a zeroed device int32/uint32, optional).  d_levels and
+        d_proof may be None when max_leaves == 1.  Asynchronous on the current stream.""",
+    "forest_range_verify_device":
+        """checks such proofs against the claimed leaf counts alone (p252_merkle%d_forest_range_verify_device_into; pass the tag of that
+        arity): d_ok[r] (m uint8) = 1 iff run r is good against d_counts[r] (m int64/uint64, in 1 .. max_leaves), d_proof_lens[r] is
+        the closed-form length and at most proof_stride, and the run's leaves — d_leaves_in (k, 4) at d_leaf_offsets[r] — and row r of
+        d_proof (m, proof_stride, 4) re-hash to d_roots[d_tree_ids[r]] (n_trees, 4).  Optional outputs: d_roots_out (m, 4) the
+        recomputed roots, d_n_hashed (one int64/uint64) the digests computed, d_n_bad (a zeroed int32/uint32) the bad runs.  d_proof
+        may be None when proof_stride == 0.  Asynchronous on the current stream."""}
+
+
+def _publish_range_calls(cls):
+    def bound(impl, a, name):
+        def call(self, *args, **kw):
+            return impl(self, a, name, *args, **kw)
+        return call
+    for stem, impl in (("forest_ragged_range_proofs_device", _forest_ragged_range_proofs_device),
+                       ("forest_range_verify_device", _forest_range_verify_device)):
+        sig = inspect.signature(impl)
+        sig = sig.replace(parameters=[p for p in sig.parameters.values() if p.name not in ("a", "f")])
+        for arity in (4, 2):
+            name = "merkle%d_%s" % (arity, stem)
+            call = bound(impl, _ARITIES[arity], name)
+            call.__name__ = name
+            call.__qualname__ = "%s.%s" % (cls.__qualname__, name)
+            call.__doc__ = _RANGE_DOCS[stem] % arity
+            call.__signature__ = sig
+            setattr(cls, name, call)
+
+
+_publish_range_calls(Context)
+
+
 class PinnedScalars:
     """n_scalars BlsScalars in page-locked host memory (p252_host_alloc); `.array` is a numpy view
     (n_scalars, 4) uint64.  Host-buffer entry points fed from/into such buffers copy at PCIe speed."""

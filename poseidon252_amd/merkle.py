@@ -595,6 +595,71 @@ def forest_ragged_multiproof_verify(ctx, d_offsets, n_leaves, n_trees, max_leave
     return ok.cpu().to(torch.bool)
 
 
+def forest_range_stride(max_leaves, arity=4):
+    """scalars of one row of range proofs, 2 (arity - 1) depth(max_leaves): room for the proof of any run
+    (p252_merkle{4,2}_forest_range_stride)"""
+    return int(_arity("forest_range_stride", arity).fn("forest_range_stride")(max_leaves))
+
+
+def forest_ragged_range_proofs(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, first, lengths, arity=4):
+    """The proofs of whole runs of leaves of a ragged forest (Context.merkle{4,2}_forest_ragged_range_proofs_device): d_leaves, d_offsets,
+    n_trees, max_leaves, d_levels as merkle_forest_ragged_device took and filled them; run r is leaves [first[r], first[r] + lengths[r])
+    of tree tree_ids[r] (sequences, numpy or torch).  Returns (tree_ids (m,) int32, first (m,) int64, leaf_offsets (m + 1,) int64,
+    leaves (k, 4), proof (m, P, 4), proof_lens (m,) int32, counts (m,) int64), all on the device — what forest_range_verify takes; row r
+    of the proof is the shared proof of merkle_multiproof for the positions of run r.  One synchronisation, to read the count of bad
+    runs.  A run outside its tree: ValueError."""
+    import torch
+    f = "forest_ragged_range_proofs"
+    a = _arity(f, arity)
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    t = torch.as_tensor(tree_ids, device=dev).to(torch.int64).reshape(-1)
+    s = torch.as_tensor(first, device=dev).to(torch.int64).reshape(-1)
+    n = torch.as_tensor(lengths, device=dev).to(torch.int64).reshape(-1)
+    if not t.numel() == s.numel() == n.numel():
+        raise ValueError("%s: %d tree ids, %d first leaves, %d lengths" % (f, t.numel(), s.numel(), n.numel()))
+    m = t.numel()
+    if m == 0:
+        raise ValueError("%s: no runs" % f)
+    outside = int(((t < 0) | (t >= n_trees) | (s < 0) | (n < 1) | (n > max_leaves)).sum())
+    if outside:
+        raise ValueError("%s: %d run(s) outside the forest (%d trees of at most %d leaves)" % (f, outside, n_trees, max_leaves))
+    offs = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    offs[1:] = torch.cumsum(n, 0)
+    k = int(offs[-1].item())
+    stride = forest_range_stride(max_leaves, arity)
+    out = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    proof = torch.empty((m, stride, 4), dtype=torch.int64, device=dev)
+    lens = torch.empty(m, dtype=torch.int32, device=dev)
+    counts = torch.empty(m, dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    tid = t.to(torch.int32)
+    call = ctx.merkle4_forest_ragged_range_proofs_device if a.arity == 4 else ctx.merkle2_forest_ragged_range_proofs_device
+    call(d_leaves, d_offsets, n_trees, max_leaves, d_levels if stride else None, tid, s, offs, m, k, proof if stride else None, lens, counts,
+         d_leaves_out=out, d_n_bad=n_bad)
+    bad = int(n_bad.item())
+    if bad:
+        raise ValueError("%s: %d run(s) outside the forest (a bad tree, or a run past its tree's leaves)" % (f, bad))
+    return tid, s, offs, out, proof, lens, counts
+
+
+def forest_range_verify(ctx, tree_ids, counts, first, leaf_offsets, leaves, proof, proof_lens, d_roots, max_leaves, arity=4, tag=None):
+    """The m verdicts (a torch bool tensor on the host) of (tree_ids, first, leaf_offsets, leaves, proof, proof_lens) — torch CUDA tensors
+    as forest_ragged_range_proofs returns them — with the claimed leaf counts `counts` (m,) against d_roots (n_trees, 4)
+    (Context.merkle{4,2}_forest_range_verify_device): entry r is True iff run r re-hashes to d_roots[tree_ids[r]].  Needs no forest.
+    Synchronises to read the verdicts."""
+    import torch
+    a = _arity("forest_range_verify", arity)
+    ctx = ctx or Context.default()
+    m, k = tree_ids.numel(), _n_scalars(leaves)
+    stride = _n_scalars(proof) // m if m else 0
+    ok = torch.zeros(m, dtype=torch.uint8, device=leaves.device)
+    call = ctx.merkle4_forest_range_verify_device if a.arity == 4 else ctx.merkle2_forest_range_verify_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), tree_ids, counts, first, leaf_offsets, m, max_leaves, leaves, k,
+         proof if stride else None, stride, proof_lens, d_roots, _n_scalars(d_roots), ok)
+    return ok.cpu().to(torch.bool)
+
+
 def merkle4_path_roots(leaves, siblings, positions, tag=None, ctx=None):
     """Roots recomputed from n openings (numpy host buffers); compare with the tree root to verify."""
     ctx = ctx or Context.default()
