@@ -445,7 +445,7 @@ namespace detail {
     X(N, forest_frontier_extract_device_into) X(N, forest_frontier_append_witness_device_into)                                            \
     X(N, forest_ragged_consistency_device_into) X(N, forest_consistency_verify_device_into)                                              \
     X(N, forest_ragged_anchor_openings_device_into) X(N, forest_range_stride) X(N, forest_ragged_range_proofs_device_into)               \
-    X(N, forest_range_verify_device_into)
+    X(N, forest_range_verify_device_into) X(N, forest_ragged_update_sequential_device_into)
 #define P252_MEMBER(N, f) decltype(&p252_merkle##N##_##f) f;
 #define P252_SYMBOL(N, f) p252_merkle##N##_##f,
 struct MerkleAbi {
@@ -922,6 +922,41 @@ inline void merkle_forest_range_verify_device(const ForestRuns& runs, const Rang
                                                     runs.m, max_leaves, proofs.d_leaves, runs.k, proofs.d_proof, proofs.stride,
                                                     proofs.d_proof_lens, d_roots, n_trees, d_ok, d_roots_out, d_n_hashed, d_n_bad, stream),
                   ctx.get(), "merkle_forest_range_verify_device");
+}
+
+// Sequential updates (p252_merkle{4,2}_forest_ragged_update_sequential_device_into): k leaf updates of a built forest applied IN ORDER in
+// one call, the same (tree, leaf) pair any number of times, the forest updated in place as merkle_forest_ragged_update_device does.
+// d_order (k uint32) is the indices sorted by (tree id, leaf id, index) — a stable sort by pair; the library checks it and sorts
+// nothing.  Witness i, in the layout of merkle_forest_ragged_openings_device at stride depth(max_leaves): the leaf as stored just before
+// update i, its opening in that state, the tree's root just before and just after.  A bad update: zero rows, depth 0xFF, zero roots,
+// one count in *d_n_bad; an invalid order: every depth 0xFF, *d_n_bad += k, nothing else written.
+struct SequentialUpdates {
+    const void* d_tree_ids;    // k uint32
+    const void* d_leaf_ids;    // k uint64
+    const void* d_new_leaves;  // k scalars
+    const void* d_order;       // k uint32
+    std::size_t k;
+};
+struct SequentialWitnesses {
+    void* d_old_leaves;    // k scalars (may be null)
+    void* d_siblings;      // k x stride x (arity - 1) scalars
+    void* d_positions;     // k x stride bytes
+    void* d_depths;        // k bytes
+    void* d_roots_before;  // k scalars (may be null)
+    void* d_roots_after;   // k scalars
+};
+inline void merkle_forest_ragged_update_sequential_device(void* d_leaves, std::size_t n_leaves, const void* d_offsets, std::size_t n_trees,
+                                                          std::size_t max_leaves, void* d_levels, const SequentialUpdates& updates,
+                                                          const SequentialWitnesses& out, unsigned arity = 4,
+                                                          Context& ctx = Context::default_context(), void* d_roots = nullptr,
+                                                          void* d_n_bad = nullptr, void* d_n_hashed = nullptr, void* stream = nullptr) {
+    const detail::MerkleAbi& m = detail::merkle_abi("merkle_forest_ragged_update_sequential_device", arity);
+    detail::check(m.forest_ragged_update_sequential_device_into(ctx.get(), m.tag().data(), d_leaves, n_leaves, d_offsets, n_trees, max_leaves,
+                                                                d_levels, updates.d_tree_ids, updates.d_leaf_ids, updates.d_new_leaves,
+                                                                updates.d_order, updates.k, out.d_old_leaves, out.d_siblings, out.d_positions,
+                                                                out.d_depths, out.d_roots_before, out.d_roots_after, d_roots, d_n_bad,
+                                                                d_n_hashed, stream),
+                  ctx.get(), "merkle_forest_ragged_update_sequential_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

@@ -133,7 +133,10 @@ extern "C" {
  *      + p252_merkle{4,2}_forest_range_stride, p252_merkle{4,2}_forest_ragged_range_proofs_device_into,
  *      p252_merkle{4,2}_forest_range_verify_device_into (additive, same version; `_into`: every result goes into buffers the caller
  *      owns): whole runs of leaves [a, b) of the trees of such a forest proved by closed-form proofs and checked, many runs of many
- *      trees in one call */
+ *      trees in one call;
+ *      + p252_merkle{4,2}_forest_ragged_update_sequential_device_into (additive, same version; `_into`: every witness goes into buffers
+ *      the caller owns): leaf updates of such a forest applied in order, the same leaf any number of times, each with the leaf it
+ *      replaces, that leaf's opening in the state just before it and the root just after it */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -1141,6 +1144,48 @@ int p252_merkle2_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t t
                                                  const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_stride,
                                                  const void* d_proof_lens, const void* d_roots, size_t n_trees, void* d_ok,
                                                  void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream);
+
+/* ---- sequential updates: k leaf updates of a forest p252_merkle{4,2}_forest_ragged_device built with d_levels, applied IN ORDER in
+ * one call, each with its witness — a block of transactions.  d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_roots
+ * exactly as p252_merkle{4,2}_forest_ragged_update_device takes them; the forest is updated in place.  Update i writes d_new_leaves[i]
+ * to leaf d_leaf_ids[i] (uint64[k], a position inside the tree) of tree d_tree_ids[i] (uint32[k]) and sees the forest as updates
+ * 0 .. i - 1 left it; the same pair may occur any number of times.  d_order (uint32[k]) is the indices 0 .. k - 1 sorted by (tree id,
+ * leaf id, index) — the stable sort by pair; the library holds no sort and checks the order on the device: every entry < k and
+ * (tree id, leaf id, index) strictly ascending along it, which makes it a permutation.
+ * The witness of update i, in the layout of p252_merkle{4,2}_forest_ragged_openings_device at stride D = depth(max_leaves):
+ * d_old_leaves[i] ([k] scalars, may be NULL) the leaf as stored just before update i, byte for byte; d_siblings ([k][D][arity - 1]
+ * scalars) and d_positions (uint8[k][D]) its opening in that state, rows at or past the tree's depth zero; d_depths[i] (uint8[k]) =
+ * depth(n_t); d_roots_before[i] ([k] scalars, may be NULL) and d_roots_after[i] ([k] scalars) the tree's root just before and just
+ * after update i: p252_merkle{4,2}_path_ragged_device over (old leaf, opening) gives the first and over (new leaf, the same opening)
+ * the second, and d_roots_before[i] is d_roots_after of the previous update of that tree, or the built root.  A one-leaf tree's root
+ * is its leaf mod p, the forest's convention.  Afterwards d_leaves and the used part of d_levels are byte for byte a fresh build of
+ * the final leaves, and d_roots[t] ([n_trees] scalars, may be NULL) is rewritten for the trees that received a good update.
+ * A BAD update (tree id >= n_trees, a bad tree, leaf id >= n_t) is skipped: zero witness rows and old leaf, depth 0xFF, both roots
+ * zero, counted once in *d_n_bad (device uint32 the caller has zeroed; may be NULL); it changes nothing for the others.  An INVALID
+ * d_order makes the batch one object: every d_depths[i] = 0xFF, *d_n_bad += k, the forest and every other output untouched.
+ * *d_n_hashed (device uint64 the caller has zeroed; may be NULL) grows by depth(n_t) per good update — the digests the result needs;
+ * the call computes k per level of D (updates of shallower trees and bad ones digest zeros above their root, results dropped).
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: k, n_leaves, n_trees or max_leaves == 0; k or max_leaves >= 2^32 (an index and a
+ * node are 32-bit words of the sorted list); a NULL or misaligned buffer (scalars 16 bytes, d_offsets, d_leaf_ids and d_n_hashed 8,
+ * d_tree_ids, d_order and d_n_bad 4; d_levels, d_siblings and d_positions may be NULL when max_leaves == 1); size overflow; an
+ * output that overlaps an input, the forest or another output.  Asynchronous on hip_stream, no host synchronisation, no allocation
+ * once the stream's scratch is warm: three launches per level of D (gather, digest, merge rank) and three more whatever k is.
+ * Scratch of the calling stream (covered by p252_trim / p252_wipe): the forest's index (16 bytes a tree) and, per update, two sorted
+ * lists of 16-byte keys with their 32-byte values, the parents' values, the gathered children and two rank words per child slot:
+ * 128 + 40 arity bytes an update (288 at arity 4, 208 at arity 2), 256 bytes. */
+int p252_merkle4_forest_ragged_update_sequential_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                             const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                             const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves,
+                                                             const void* d_order, size_t k, void* d_old_leaves, void* d_siblings,
+                                                             void* d_positions, void* d_depths, void* d_roots_before, void* d_roots_after,
+                                                             void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream);
+/* the same for arity 2 (the level layout of merkle2 trees; pass the Merkle2 tag) */
+int p252_merkle2_forest_ragged_update_sequential_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                             const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                             const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves,
+                                                             const void* d_order, size_t k, void* d_old_leaves, void* d_siblings,
+                                                             void* d_positions, void* d_depths, void* d_roots_before, void* d_roots_after,
+                                                             void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

@@ -20,6 +20,7 @@
 #include "forest_openings.h"
 #include "forest_ragged.h"
 #include "forest_range.h"
+#include "forest_sequential.h"
 #include "forest_update.h"
 #include "forest_witness.h"
 #include "kernels.h"
@@ -1172,6 +1173,86 @@ int p252_merkle2_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t t
                                                  void* d_roots_out, void* d_n_hashed, void* d_n_bad, void* hip_stream) {
     return forest_range_verify_device(ctx, 2, tag, d_tree_ids, d_counts, d_first, d_leaf_offsets, m, max_leaves, d_leaves_in, k, d_proof,
                                       proof_stride, d_proof_lens, d_roots, n_trees, d_ok, d_roots_out, d_n_hashed, d_n_bad, hip_stream);
+}
+
+// ---- leaf updates of such a forest applied in order, each with its witness (forest_sequential.hip).  The scratch — the forest's
+// index, two sorted lists of keys and values, the parents' values and the rank words; one level's gathered children in the second
+// buffer — is the pair of the calling stream ----
+static int forest_ragged_update_sequential_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                  const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                  const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves, const void* d_order,
+                                                  size_t k, void* d_old_leaves, void* d_siblings, void* d_positions, void* d_depths,
+                                                  void* d_roots_before, void* d_roots_after, void* d_roots, void* d_n_bad, void* d_n_hashed,
+                                                  void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = arity == 4 ? "merkle4_forest_ragged_update_sequential" : "merkle2_forest_ragged_update_sequential";
+    if (k == 0 || max_leaves == 0 || n_trees == 0 || n_leaves == 0)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k, n_leaves, n_trees and max_leaves must be > 0");
+    if (k > 0xffffffffu || max_leaves > 0xffffffffu)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k and max_leaves must be below 2^32 (an index and a node are 32-bit words)");
+    const size_t depth = forest_ragged_depth(max_leaves, arity);
+    if (!tag || !d_leaves || !d_offsets || !d_tree_ids || !d_leaf_ids || !d_new_leaves || !d_order || !d_depths || !d_roots_after ||
+        (depth && (!d_levels || !d_siblings || !d_positions)))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_new_leaves) || misaligned(d_old_leaves) || misaligned(d_siblings) ||
+        misaligned(d_roots_before) || misaligned(d_roots_after) || misaligned(d_roots))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (misaligned_to(d_offsets, 8) || misaligned_to(d_leaf_ids, 8) || misaligned_to(d_n_hashed, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets, d_leaf_ids and d_n_hashed must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4) || misaligned_to(d_order, 4) || misaligned_to(d_n_bad, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids, d_order and d_n_bad must be 4-byte aligned");
+    if (int rc = forest_shape_check(ctx, who.c_str(), n_leaves, n_trees, max_leaves)) return rc;  // (the build's own limits)
+    const size_t levels_forest = forest_levels_bound(arity, n_leaves, n_trees, max_leaves);
+    const ByteRange in[] = {{d_leaves, n_leaves * 32, "d_leaves"},
+                            {d_offsets, (n_trees + 1) * 8, "d_offsets"},
+                            {d_levels, levels_forest * 32, "d_levels"},
+                            {d_roots, n_trees * 32, "d_roots"},
+                            {d_tree_ids, k * 4, "d_tree_ids"},
+                            {d_leaf_ids, k * 8, "d_leaf_ids"},
+                            {d_new_leaves, k * 32, "d_new_leaves"},
+                            {d_order, k * 4, "d_order"}};
+    const ByteRange out[] = {{d_old_leaves, k * 32, "d_old_leaves"},
+                             {d_siblings, k * depth * (arity - 1) * 32, "d_siblings"},
+                             {d_positions, k * depth, "d_positions"},
+                             {d_depths, k, "d_depths"},
+                             {d_roots_before, k * 32, "d_roots_before"},
+                             {d_roots_after, k * 32, "d_roots_after"},
+                             {d_n_bad, 4, "d_n_bad"},
+                             {d_n_hashed, 8, "d_n_hashed"}};
+    if (int rc = refuse_overlaps(ctx, who, in, std::size(in), out, std::size(out), true)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const ForestSequentialWork w = forest_sequential_work(arity, k);
+    return with_forest_index(ctx, who, st, arity, d_offsets, n_trees, n_leaves, max_leaves, w.bytes, depth ? w.children_bytes : 0,
+                             [&](const uint64_t* ntree, const uint64_t* lo, char* work, void* children) {
+                                 return launch_forest_update_sequential(arity, ctx->d_tab, tag_arg(tag), d_leaves, d_offsets, ntree, lo, n_trees,
+                                                                        d_levels, d_tree_ids, d_leaf_ids, d_new_leaves, d_order, k,
+                                                                        (unsigned)depth, d_old_leaves, d_siblings, d_positions, d_depths,
+                                                                        d_roots_before, d_roots_after, d_roots, d_n_bad, d_n_hashed, work,
+                                                                        children, st);
+                             });
+}
+
+int p252_merkle4_forest_ragged_update_sequential_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                             const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                             const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves,
+                                                             const void* d_order, size_t k, void* d_old_leaves, void* d_siblings,
+                                                             void* d_positions, void* d_depths, void* d_roots_before, void* d_roots_after,
+                                                             void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    return forest_ragged_update_sequential_device(ctx, 4, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
+                                                  d_leaf_ids, d_new_leaves, d_order, k, d_old_leaves, d_siblings, d_positions, d_depths,
+                                                  d_roots_before, d_roots_after, d_roots, d_n_bad, d_n_hashed, hip_stream);
+}
+
+int p252_merkle2_forest_ragged_update_sequential_device_into(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves,
+                                                             const void* d_offsets, size_t n_trees, size_t max_leaves, void* d_levels,
+                                                             const void* d_tree_ids, const void* d_leaf_ids, const void* d_new_leaves,
+                                                             const void* d_order, size_t k, void* d_old_leaves, void* d_siblings,
+                                                             void* d_positions, void* d_depths, void* d_roots_before, void* d_roots_after,
+                                                             void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream) {
+    return forest_ragged_update_sequential_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
+                                                  d_leaf_ids, d_new_leaves, d_order, k, d_old_leaves, d_siblings, d_positions, d_depths,
+                                                  d_roots_before, d_roots_after, d_roots, d_n_bad, d_n_hashed, hip_stream);
 }
 
 }  // (the C ABI)

@@ -36,6 +36,27 @@ __device__ __forceinline__ uint64_t level_start(uint64_t n, unsigned l, unsigned
     return w;
 }
 __device__ __forceinline__ uint64_t u64_of(unsigned lo, unsigned hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+// the eight words of a stored scalar, reduced: V < 2^256 < 3 p, so two conditional subtractions (what store_scalar(load_scalar())
+// gives, without the change of radix) — the forest's convention for a one-leaf tree: its root is its leaf mod p
+__device__ __forceinline__ void words_mod_p(uint4& lo, uint4& hi) {
+    const uint64_t P0 = 0xffffffff00000001ull, P1 = 0x53bda402fffe5bfeull, P2 = 0x3339d80809a1d805ull, P3 = 0x73eda753299d7d48ull;
+    uint64_t v0 = u64_of(lo.x, lo.y), v1 = u64_of(lo.z, lo.w), v2 = u64_of(hi.x, hi.y), v3 = u64_of(hi.z, hi.w);
+#pragma unroll 1
+    for (int rep = 0; rep < 2; ++rep) {
+        const bool ge = v3 != P3 ? v3 > P3 : v2 != P2 ? v2 > P2 : v1 != P1 ? v1 > P1 : v0 >= P0;
+        if (ge) {  // V -= p, limb by limb with the borrow
+            const uint64_t b0 = v0 < P0, t1 = v1 - P1, t2 = v2 - P2;
+            const uint64_t b1 = (v1 < P1) | (t1 < b0);
+            v0 -= P0;
+            v1 = t1 - b0;
+            const uint64_t b2 = (v2 < P2) | (t2 < b1);
+            v2 = t2 - b1;
+            v3 = v3 - P3 - b2;
+        }
+    }
+    lo = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
+    hi = make_uint4((unsigned)v2, (unsigned)(v2 >> 32), (unsigned)v3, (unsigned)(v3 >> 32));
+}
 // a record of the level lists (16 bytes: tree id, valid, node index low and high), as k_fu_claim writes it and k_fu_digest reads it
 // (forest_update.h); a void record is all zero
 __device__ __forceinline__ uint4 record(uint32_t t, uint64_t i) { return make_uint4(t, 1u, (unsigned)i, (unsigned)(i >> 32)); }

@@ -22,7 +22,7 @@
 //   k_rg_leaf_roots  one lane per run: a one-leaf tree's root, its leaf mod p (the forest's convention), deposited like the others
 //   k_rg_finish      one lane per run: the verdict byte, the recomputed root, the digest count
 // The digests run through launch_multiproof_digest_list (multiproof.hip's k_mp_digest / k_mp_digest_coop on this unit's records): no
-// kernel here runs the permutation.  ceil_shift and u64_of are forest_node.hpp's; the scans are forest_ragged.hip's.
+// kernel here runs the permutation.  ceil_shift, u64_of and words_mod_p are forest_node.hpp's; the scans are forest_ragged.hip's.
 #include <hip/hip_runtime.h>
 
 #include "forest_node.hpp"
@@ -83,28 +83,6 @@ __device__ __forceinline__ size_t run_of(const uint64_t* __restrict__ row, size_
             hi = mid - 1;
     }
     return lo;
-}
-
-// the eight words of a stored scalar, reduced: V < 2^256 < 3 p, so two conditional subtractions (what store_scalar(load_scalar())
-// gives, without the change of radix)
-__device__ __forceinline__ void words_mod_p(uint4& lo, uint4& hi) {
-    const uint64_t P0 = 0xffffffff00000001ull, P1 = 0x53bda402fffe5bfeull, P2 = 0x3339d80809a1d805ull, P3 = 0x73eda753299d7d48ull;
-    uint64_t v0 = u64_of(lo.x, lo.y), v1 = u64_of(lo.z, lo.w), v2 = u64_of(hi.x, hi.y), v3 = u64_of(hi.z, hi.w);
-#pragma unroll 1
-    for (int rep = 0; rep < 2; ++rep) {
-        const bool ge = v3 != P3 ? v3 > P3 : v2 != P2 ? v2 > P2 : v1 != P1 ? v1 > P1 : v0 >= P0;
-        if (ge) {  // V -= p, limb by limb with the borrow
-            const uint64_t b0 = v0 < P0, t1 = v1 - P1, t2 = v2 - P2;
-            const uint64_t b1 = (v1 < P1) | (t1 < b0);
-            v0 -= P0;
-            v1 = t1 - b0;
-            const uint64_t b2 = (v2 < P2) | (t2 < b1);
-            v2 = t2 - b1;
-            v3 = v3 - P3 - b2;
-        }
-    }
-    lo = make_uint4((unsigned)v0, (unsigned)(v0 >> 32), (unsigned)v1, (unsigned)(v1 >> 32));
-    hi = make_uint4((unsigned)v2, (unsigned)(v2 >> 32), (unsigned)v3, (unsigned)(v3 >> 32));
 }
 
 }  // namespace

@@ -1187,13 +1187,13 @@ _RANGE_DOCS = {
         may be None when proof_stride == 0.  Asynchronous on the current stream."""}
 
 
-def _publish_range_calls(cls):
+def _publish_pairs(cls, impls, docs):
+    """Context.merkle4_<stem> and Context.merkle2_<stem>, neither taking arity=, from one private implementation per stem"""
     def bound(impl, a, name):
         def call(self, *args, **kw):
             return impl(self, a, name, *args, **kw)
         return call
-    for stem, impl in (("forest_ragged_range_proofs_device", _forest_ragged_range_proofs_device),
-                       ("forest_range_verify_device", _forest_range_verify_device)):
+    for stem, impl in impls:
         sig = inspect.signature(impl)
         sig = sig.replace(parameters=[p for p in sig.parameters.values() if p.name not in ("a", "f")])
         for arity in (4, 2):
@@ -1201,12 +1201,50 @@ def _publish_range_calls(cls):
             call = bound(impl, _ARITIES[arity], name)
             call.__name__ = name
             call.__qualname__ = "%s.%s" % (cls.__qualname__, name)
-            call.__doc__ = _RANGE_DOCS[stem] % arity
+            call.__doc__ = docs[stem] % arity
             call.__signature__ = sig
             setattr(cls, name, call)
 
 
-_publish_range_calls(Context)
+_publish_pairs(Context, (("forest_ragged_range_proofs_device", _forest_ragged_range_proofs_device),
+                         ("forest_range_verify_device", _forest_range_verify_device)), _RANGE_DOCS)
+
+
+# ---- leaf updates of a ragged forest applied in order, each with its witness (p252_merkle{4,2}_forest_ragged_update_sequential_device_into;
+# csrc/forest_sequential.hip): published as the range calls are, one private implementation per pair; the arity-taking form is
+# merkle.forest_ragged_update_sequential ----
+def _forest_ragged_update_sequential_device(self, a, f, tag, d_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids, d_leaf_ids,
+                                            d_new_leaves, d_order, k, d_siblings, d_positions, d_depths, d_roots_after, d_old_leaves=None,
+                                            d_roots_before=None, d_roots=None, d_n_bad=None, d_n_hashed=None):
+    forest, depth = self._built_forest(f, a, d_leaves, d_offsets, n_trees, max_leaves, d_levels)
+    self._check(a.fn("forest_ragged_update_sequential_device_into")(
+        self._h, _tag(tag), *forest, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4),
+        _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8), _dev_ptr(self, f, "d_new_leaves", d_new_leaves, k * 32),
+        _dev_ptr(self, f, "d_order", d_order, k * 4, elem=4), k, _dev_ptr(self, f, "d_old_leaves", d_old_leaves, k * 32, null_ok=True),
+        _dev_ptr(self, f, "d_siblings", d_siblings, k * depth * a.per * 32, null_ok=depth == 0),
+        _dev_ptr(self, f, "d_positions", d_positions, k * depth, elem=1, null_ok=depth == 0),
+        _dev_ptr(self, f, "d_depths", d_depths, k, elem=1), _dev_ptr(self, f, "d_roots_before", d_roots_before, k * 32, null_ok=True),
+        _dev_ptr(self, f, "d_roots_after", d_roots_after, k * 32), _dev_ptr(self, f, "d_roots", d_roots, n_trees * 32, null_ok=True),
+        _dev_ptr(self, f, "d_n_bad", d_n_bad, 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_hashed", d_n_hashed, 8, elem=8, null_ok=True),
+        _stream(self)))
+
+
+_SEQUENTIAL_DOC = """k leaf updates of a forest merkle_forest_ragged_device built with d_levels, applied IN ORDER in one call, each with
+    its witness (p252_merkle%d_forest_ragged_update_sequential_device_into; pass the tag of that arity): update i writes d_new_leaves[i]
+    (k, 4) to leaf d_leaf_ids[i] (int64/uint64) of tree d_tree_ids[i] (int32/uint32) and sees the forest as updates 0 .. i - 1 left it;
+    the same pair may occur any number of times.  d_order (k,) int32/uint32 is the indices sorted by (tree id, leaf id, index) — the
+    stable sort by pair; the library checks it and sorts nothing.  The witness of update i, at stride D = depth(max_leaves): d_siblings
+    (k, D, arity - 1, 4) and d_positions (k, D) uint8 the leaf's opening in the state just before the update, d_depths (k,) uint8,
+    d_roots_after (k, 4) the tree's root just after it; optional d_old_leaves (k, 4) the leaf it replaces, d_roots_before (k, 4).  The
+    forest is updated in place: afterwards a fresh build of the final leaves; d_roots (n_trees, 4; optional) is rewritten for the trees
+    that received a good update.  A bad update is skipped: zero rows, depth 0xFF, zero roots, counted in d_n_bad (a zeroed device
+    int32/uint32, optional).  An invalid order: every depth 0xFF, d_n_bad += k, nothing else written.  d_n_hashed (a zeroed device
+    int64/uint64, optional) grows by depth(n_t) per good update.  d_levels, d_siblings and d_positions may be None when max_leaves == 1.
+    Asynchronous on the current stream."""
+
+
+_publish_pairs(Context, (("forest_ragged_update_sequential_device", _forest_ragged_update_sequential_device),),
+               {"forest_ragged_update_sequential_device": _SEQUENTIAL_DOC})
 
 
 class PinnedScalars:

@@ -660,6 +660,57 @@ def forest_range_verify(ctx, tree_ids, counts, first, leaf_offsets, leaves, proo
     return ok.cpu().to(torch.bool)
 
 
+def forest_ragged_update_sequential(ctx, d_leaves, d_offsets, n_trees, max_leaves, d_levels, tree_ids, leaf_ids, new_leaves, d_roots=None,
+                                    arity=4, tag=None):
+    """Leaf updates of a ragged forest applied IN ORDER, each with its witness (Context.merkle{4,2}_forest_ragged_update_sequential_device):
+    d_leaves, d_offsets, n_trees, max_leaves, d_levels as merkle_forest_ragged_device took and filled them, updated in place (and d_roots
+    (n_trees, 4), if given); update i writes new_leaves[i] (k, 4) to leaf leaf_ids[i] of tree tree_ids[i] (sequences, numpy or torch) and
+    sees the forest as updates 0 .. i - 1 left it, so a pair may repeat.  The order the call needs — the stable sort by pair — is made
+    here, on the device.  Returns (d_old_leaves (k, 4), d_siblings (k, D, arity - 1, 4), d_positions (k, D) uint8, d_depths (k,) uint8,
+    d_roots_before (k, 4), d_roots_after (k, 4), D), all on the device: (old leaf, opening) re-hashes to the root before update i, (new
+    leaf, the same opening) to the root after it.  One synchronisation, to read the count of bad updates.  An id outside the forest:
+    ValueError before anything is enqueued; a bad tree or a leaf past its tree's leaves: ValueError after the call, which skipped that
+    update alone and applied the others."""
+    import torch
+    f = "forest_ragged_update_sequential"
+    a = _arity(f, arity)
+    ctx = ctx or Context.default()
+    dev = d_leaves.device
+    t = torch.as_tensor(tree_ids, device=dev).to(torch.int64).reshape(-1)
+    j = torch.as_tensor(leaf_ids, device=dev).to(torch.int64).reshape(-1)
+    if isinstance(new_leaves, torch.Tensor):
+        v = new_leaves.to(dev).contiguous()
+    else:
+        v = torch.from_numpy(_as_scalars(new_leaves).view(np.int64)).to(dev)
+    k = t.numel()
+    if k == 0:
+        raise ValueError("%s: no updates" % f)
+    if j.numel() != k or _n_scalars(v) != k:
+        raise ValueError("%s: %d tree ids, %d leaf ids, %d new leaves" % (f, k, j.numel(), _n_scalars(v)))
+    outside = int(((t < 0) | (t >= n_trees) | (j < 0) | (j >= max_leaves)).sum())
+    if outside:
+        raise ValueError("%s: %d update(s) outside the forest (%d trees of at most %d leaves)" % (f, outside, n_trees, max_leaves))
+    # the stable sort by (tree id, leaf id): by leaf, then — stable — by tree; ties keep their index order
+    by_leaf = torch.sort(j, stable=True).indices
+    order = by_leaf[torch.sort(t[by_leaf], stable=True).indices].to(torch.int32)
+    depth = a.depth(max_leaves)
+    old = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    sib = torch.empty((k, depth, a.per, 4), dtype=torch.int64, device=dev)
+    pos = torch.empty((k, depth), dtype=torch.uint8, device=dev)
+    dep = torch.empty((k,), dtype=torch.uint8, device=dev)
+    before = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    after = torch.empty((k, 4), dtype=torch.int64, device=dev)
+    n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    call = ctx.merkle4_forest_ragged_update_sequential_device if a.arity == 4 else ctx.merkle2_forest_ragged_update_sequential_device
+    call(a.tag() if tag is None else _as_scalars(tag).reshape(4), d_leaves, d_offsets, n_trees, max_leaves, d_levels if depth else None,
+         t.to(torch.int32), j, v, order, k, sib if depth else None, pos if depth else None, dep, after, d_old_leaves=old, d_roots_before=before,
+         d_roots=d_roots, d_n_bad=n_bad)
+    bad = int(n_bad.item())
+    if bad:
+        raise ValueError("%s: %d update(s) outside the forest (a bad tree, or a leaf past its tree's leaves)" % (f, bad))
+    return old, sib, pos, dep, before, after, depth
+
+
 def merkle4_path_roots(leaves, siblings, positions, tag=None, ctx=None):
     """Roots recomputed from n openings (numpy host buffers); compare with the tree root to verify."""
     ctx = ctx or Context.default()
