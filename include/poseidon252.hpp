@@ -926,8 +926,8 @@ inline void merkle_forest_range_verify_device(const ForestRuns& runs, const Rang
 
 // Sequential updates (p252_merkle{4,2}_forest_ragged_update_sequential_device_into): k leaf updates of a built forest applied IN ORDER in
 // one call, the same (tree, leaf) pair any number of times, the forest updated in place as merkle_forest_ragged_update_device does.
-// d_order (k uint32) is the indices sorted by (tree id, leaf id, index) — a stable sort by pair; the library checks it and sorts
-// nothing.  Witness i, in the layout of merkle_forest_ragged_openings_device at stride depth(max_leaves): the leaf as stored just before
+// d_order (k uint32) is the indices sorted by (tree id, leaf id, index) — a stable sort by pair (pairs_order_device makes it); this call
+// checks it and sorts nothing.  Witness i, in the layout of merkle_forest_ragged_openings_device at stride depth(max_leaves): the leaf as stored just before
 // update i, its opening in that state, the tree's root just before and just after.  A bad update: zero rows, depth 0xFF, zero roots,
 // one count in *d_n_bad; an invalid order: every depth 0xFF, *d_n_bad += k, nothing else written.
 struct SequentialUpdates {
@@ -957,6 +957,29 @@ inline void merkle_forest_ragged_update_sequential_device(void* d_leaves, std::s
                                                                 out.d_depths, out.d_roots_before, out.d_roots_after, d_roots, d_n_bad,
                                                                 d_n_hashed, stream),
                   ctx.get(), "merkle_forest_ragged_update_sequential_device");
+}
+
+// The order of (tree id, leaf id) pairs, made on the device (p252_pairs_order_device_into, p252_pairs_unique_device_into; no arity):
+// pairs_order_device fills d_order (k uint32) — SequentialUpdates::d_order — with the indices sorted by (tree id, leaf id, index);
+// pairs_unique_device writes the distinct pairs, ascending, into the first *d_n_unique (a device uint64) entries of every output that
+// is not null: what merkle_forest_ragged_multiproof_device takes as its pairs and, with d_indices, merkle_multiproof_device as its
+// positions.  d_tree_ids (k uint32) may be null: every pair is of tree 0.  d_leaf_ids: k uint64.  Both parts compare as unsigned.
+struct UniquePairs {
+    void* d_tree_ids;  // k uint32 (may be null)
+    void* d_leaf_ids;  // k uint64 (may be null)
+    void* d_indices;   // k uint32, the low word of the leaf id (may be null)
+    void* d_first;     // k uint32, the lowest input index that holds the pair (may be null)
+    void* d_n_unique;  // one uint64
+};
+inline void pairs_order_device(const void* d_tree_ids, const void* d_leaf_ids, std::size_t k, void* d_order,
+                               Context& ctx = Context::default_context(), void* stream = nullptr) {
+    detail::check(p252_pairs_order_device_into(ctx.get(), d_tree_ids, d_leaf_ids, k, d_order, stream), ctx.get(), "pairs_order_device");
+}
+inline void pairs_unique_device(const void* d_tree_ids, const void* d_leaf_ids, std::size_t k, const UniquePairs& out,
+                                Context& ctx = Context::default_context(), void* stream = nullptr) {
+    detail::check(p252_pairs_unique_device_into(ctx.get(), d_tree_ids, d_leaf_ids, k, out.d_tree_ids, out.d_leaf_ids, out.d_indices, out.d_first,
+                                                out.d_n_unique, stream),
+                  ctx.get(), "pairs_unique_device");
 }
 
 // `Opening::verify` of the downstream poseidon-merkle consumer (AGENTS.md:62-66) for n device-resident arity-4 openings against ONE

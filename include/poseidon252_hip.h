@@ -136,7 +136,10 @@ extern "C" {
  *      trees in one call;
  *      + p252_merkle{4,2}_forest_ragged_update_sequential_device_into (additive, same version; `_into`: every witness goes into buffers
  *      the caller owns): leaf updates of such a forest applied in order, the same leaf any number of times, each with the leaf it
- *      replaces, that leaf's opening in the state just before it and the root just after it */
+ *      replaces, that leaf's opening in the state just before it and the root just after it;
+ *      + p252_pairs_order_device_into, p252_pairs_unique_device_into (additive, same version; `_into`: every result goes into buffers
+ *      the caller owns): the stable sort of (tree id, leaf id) pairs that the sequential updates take as d_order, and the ascending
+ *      distinct pairs that the shared proofs take, made on the device by the library itself */
 #define P252_ABI_VERSION 9
 
 #define P252_OK 0
@@ -1150,7 +1153,7 @@ int p252_merkle2_forest_range_verify_device_into(p252_ctx* ctx, const uint64_t t
  * exactly as p252_merkle{4,2}_forest_ragged_update_device takes them; the forest is updated in place.  Update i writes d_new_leaves[i]
  * to leaf d_leaf_ids[i] (uint64[k], a position inside the tree) of tree d_tree_ids[i] (uint32[k]) and sees the forest as updates
  * 0 .. i - 1 left it; the same pair may occur any number of times.  d_order (uint32[k]) is the indices 0 .. k - 1 sorted by (tree id,
- * leaf id, index) — the stable sort by pair; the library holds no sort and checks the order on the device: every entry < k and
+ * leaf id, index) — the stable sort by pair, which p252_pairs_order_device_into makes; this call sorts nothing and checks the order on the device: every entry < k and
  * (tree id, leaf id, index) strictly ascending along it, which makes it a permutation.
  * The witness of update i, in the layout of p252_merkle{4,2}_forest_ragged_openings_device at stride D = depth(max_leaves):
  * d_old_leaves[i] ([k] scalars, may be NULL) the leaf as stored just before update i, byte for byte; d_siblings ([k][D][arity - 1]
@@ -1186,6 +1189,32 @@ int p252_merkle2_forest_ragged_update_sequential_device_into(p252_ctx* ctx, cons
                                                              const void* d_order, size_t k, void* d_old_leaves, void* d_siblings,
                                                              void* d_positions, void* d_depths, void* d_roots_before, void* d_roots_after,
                                                              void* d_roots, void* d_n_bad, void* d_n_hashed, void* hip_stream);
+
+/* ---- the order of (tree id, leaf id) pairs, made on the device: what p252_merkle{4,2}_forest_ragged_update_sequential_device_into
+ * takes as d_order, what p252_merkle{4,2}_multiproof_device takes as d_indices and what the forest's shared proofs take as their
+ * pairs, from pairs in any order with any repeats.  Neither call depends on an arity.  d_leaf_ids is uint64[k]; d_tree_ids is
+ * uint32[k], or NULL: every pair is of tree 0 (a single tree's positions).  The key of pair i is the 96-bit number (tree id, leaf
+ * id), both parts compared as UNSIGNED, the full width counted: nothing is assumed about the values — a pair outside a forest is
+ * its consumer's business.
+ * p252_pairs_order_device_into writes d_order (uint32[k]): the indices 0 .. k - 1 sorted by (tree id, leaf id, index), the stable
+ * sort by pair — the one permutation the sequential call checks and accepts.
+ * p252_pairs_unique_device_into writes the distinct pairs, ascending, into the first *d_n_unique entries of every output that is
+ * not NULL: d_tree_ids_out (uint32[k]) and d_leaf_ids_out (uint64[k]) the pair; d_indices_out (uint32[k]) the low word of its leaf
+ * id, as the single tree's multiproof takes its positions; d_first (uint32[k]) the lowest input index that holds the pair — gather
+ * through it whatever belongs to the pair.  *d_n_unique (a device uint64, required) is always written; entries at and past it are
+ * left alone.  At least one of the four arrays must be given.
+ * P252_ERR_INVALID_ARGUMENT, nothing enqueued: k == 0; k >= 2^32 (an index is a 32-bit word; no size overflows below that); a NULL
+ * required buffer; a misaligned one (d_tree_ids, d_tree_ids_out, d_order, d_indices_out and d_first 4 bytes, d_leaf_ids,
+ * d_leaf_ids_out and d_n_unique 8); an output that overlaps an input or another output.
+ * The method is a stable radix sort over the 12 bytes of the key, least significant first; a byte that has one value in all k keys
+ * costs no pass: its kernels leave at once on a device word (tree ids below 2^16 and leaf ids below 2^24: 5 passes of 12).
+ * Asynchronous on hip_stream, no host synchronisation, no allocation once the stream's scratch is warm.  The number and the grids
+ * of the launches depend on k alone — 3 + 3 * 12, and 3 more for the distinct pairs — never on the keys: a captured graph replays
+ * correctly on other contents of the same buffers.  Scratch of the calling stream (covered by p252_trim / p252_wipe): two arrays of
+ * 16-byte records {tree, index, leaf} and the per-tile digit counts, 256 words per 2,048 pairs: 32.5 bytes a pair, 1,280 bytes. */
+int p252_pairs_order_device_into(p252_ctx* ctx, const void* d_tree_ids, const void* d_leaf_ids, size_t k, void* d_order, void* hip_stream);
+int p252_pairs_unique_device_into(p252_ctx* ctx, const void* d_tree_ids, const void* d_leaf_ids, size_t k, void* d_tree_ids_out,
+                                  void* d_leaf_ids_out, void* d_indices_out, void* d_first, void* d_n_unique, void* hip_stream);
 
 /* ---- multi-device: an array of contexts, one per GPU.  Shards are contiguous and independent: no
  * inter-GPU dependence and no collective on the data path.  The calls are synchronous; inside, one host thread drives

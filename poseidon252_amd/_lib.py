@@ -149,6 +149,8 @@ PROTOTYPES = {
     "p252_merkle2_forest_range_verify_device_into": _f(_vp, _u64p, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp),
     "p252_merkle4_forest_ragged_update_sequential_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
     "p252_merkle2_forest_ragged_update_sequential_device_into": _f(_vp, _u64p, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
+    "p252_pairs_order_device_into": _f(_vp, _vp, _vp, _sz, _vp, _vp),
+    "p252_pairs_unique_device_into": _f(_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp),
     "p252_hash_batch_multi": _f(_vpp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz),
     "p252_hash_batch_multi_device": _f(_vpp, _sz, _u64p, _vpp, _sz, _sz, _vpp, _szp, _vpp),
     "p252_merkle4_tree_multi": _f(_vpp, _sz, _u64p, _u64p, _sz, _u64p),

@@ -15,14 +15,14 @@ HIPCC_FLAGS = [
     # silently turns them into scratch-indexed loops
     "-mllvm", "-pragma-unroll-threshold=1000000",
 ]
-SOURCES = ["kernels.hip", "openings.hip", "merkle2.hip", "ragged.hip", "crypt_ragged.hip", "forest_ragged.hip", "forest_openings.hip", "forest_update.hip", "forest_journal.hip", "forest_append.hip", "multiproof.hip", "forest_multiproof.hip", "forest_frontier.hip", "forest_witness.hip", "forest_consistency.hip", "forest_anchor.hip", "forest_range.hip", "forest_sequential.hip", "api.cpp", "api_forest.cpp", "host_io.cpp", "comm.cpp", "rccl_dyn.cpp"]
+SOURCES = ["kernels.hip", "openings.hip", "merkle2.hip", "ragged.hip", "crypt_ragged.hip", "forest_ragged.hip", "forest_openings.hip", "forest_update.hip", "forest_journal.hip", "forest_append.hip", "multiproof.hip", "forest_multiproof.hip", "forest_frontier.hip", "forest_witness.hip", "forest_consistency.hip", "forest_anchor.hip", "forest_range.hip", "forest_sequential.hip", "pairs.hip", "api.cpp", "api_forest.cpp", "host_io.cpp", "comm.cpp", "rccl_dyn.cpp"]
 # comm.cpp: the RCCL communicator of the multi-GPU entry points (ncclBroadcast of the constants, ncclAllGather of subtree roots).
 # RCCL is NOT linked: rccl_dyn.cpp resolves it with dlopen on first use (a hashing-only deployment needs no RCCL, and a
 # process that already holds a copy — torch's — gets that one); only its header is needed at build time.
 # (ROCM_PATH / HIP_PATH name the ROCm prefix when it is not /opt/rocm — ADVICE r4)
 ROCM = os.environ.get("ROCM_PATH") or os.environ.get("HIP_PATH") or "/opt/rocm"
 LINK_FLAGS = ["-ldl"]
-HEADERS = ["fr29.hpp", "fr_host.hpp", "hades29.hpp", "coop29.hpp", "tables.hpp", "kernels.h", "blake2b.hpp", "ctx.hpp", "api_util.hpp", "openings.h", "ragged.h", "crypt_ragged.h", "crypt_args.h", "crypt_calls.hpp", "forest_ragged.h", "forest_openings.h", "forest_update.h", "forest_journal.h", "forest_append.h", "multiproof.h", "forest_multiproof.h", "forest_frontier.h", "forest_witness.h", "forest_consistency.h", "forest_anchor.h", "forest_range.h", "forest_sequential.h", "forest_node.hpp", "blockops.hpp", "fastdiv.hpp", "rccl_dyn.hpp",
+HEADERS = ["fr29.hpp", "fr_host.hpp", "hades29.hpp", "coop29.hpp", "tables.hpp", "kernels.h", "blake2b.hpp", "ctx.hpp", "api_util.hpp", "openings.h", "ragged.h", "crypt_ragged.h", "crypt_args.h", "crypt_calls.hpp", "forest_ragged.h", "forest_openings.h", "forest_update.h", "forest_journal.h", "forest_append.h", "multiproof.h", "forest_multiproof.h", "forest_frontier.h", "forest_witness.h", "forest_consistency.h", "forest_anchor.h", "forest_range.h", "forest_sequential.h", "pairs.h", "forest_node.hpp", "blockops.hpp", "fastdiv.hpp", "rccl_dyn.hpp",
            os.path.join("..", "..", "include", "poseidon252_hip.h")]
 
 

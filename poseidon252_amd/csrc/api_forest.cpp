@@ -24,6 +24,7 @@
 #include "forest_update.h"
 #include "forest_witness.h"
 #include "kernels.h"
+#include "pairs.h"
 #include "ragged.h"
 
 using namespace p252;
@@ -1253,6 +1254,60 @@ int p252_merkle2_forest_ragged_update_sequential_device_into(p252_ctx* ctx, cons
     return forest_ragged_update_sequential_device(ctx, 2, tag, d_leaves, n_leaves, d_offsets, n_trees, max_leaves, d_levels, d_tree_ids,
                                                   d_leaf_ids, d_new_leaves, d_order, k, d_old_leaves, d_siblings, d_positions, d_depths,
                                                   d_roots_before, d_roots_after, d_roots, d_n_bad, d_n_hashed, hip_stream);
+}
+
+// ---- the order and the distinct pairs the calls above take, made on the device (pairs.hip): neither depends on an arity.  The
+// scratch — the plan, two arrays of records and the per-tile digit counts — is the first buffer of the calling stream's pair ----
+static int pairs_common_check(p252_ctx* ctx, const std::string& who, const void* d_tree_ids, const void* d_leaf_ids, size_t k) {
+    if (k == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k must be > 0");
+    if (k > 0xffffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": k must be below 2^32 (an index is a 32-bit word)");
+    if (!d_leaf_ids) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned_to(d_leaf_ids, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_leaf_ids must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids must be 4-byte aligned");
+    if (pairs_work(k).bytes > SIZE_MAX / 2) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");  // (never, below 2^32)
+    return P252_OK;
+}
+
+int p252_pairs_order_device_into(p252_ctx* ctx, const void* d_tree_ids, const void* d_leaf_ids, size_t k, void* d_order, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = "pairs_order";
+    if (int rc = pairs_common_check(ctx, who, d_tree_ids, d_leaf_ids, k)) return rc;
+    if (!d_order) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (misaligned_to(d_order, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_order must be 4-byte aligned");
+    const ByteRange in[] = {{d_tree_ids, k * 4, "d_tree_ids"}, {d_leaf_ids, k * 8, "d_leaf_ids"}};
+    const ByteRange out[] = {{d_order, k * 4, "d_order"}};
+    if (int rc = refuse_overlaps(ctx, who, in, std::size(in), out, std::size(out), true)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    return with_stream_scratch(ctx, who, st, pairs_work(k).bytes, 0, [&](p252_ctx::LevelSet& set) {
+        return launch_pairs_order(d_tree_ids, d_leaf_ids, k, d_order, set.buf[0], st);
+    });
+}
+
+int p252_pairs_unique_device_into(p252_ctx* ctx, const void* d_tree_ids, const void* d_leaf_ids, size_t k, void* d_tree_ids_out,
+                                  void* d_leaf_ids_out, void* d_indices_out, void* d_first, void* d_n_unique, void* hip_stream) {
+    if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const std::string who = "pairs_unique";
+    if (int rc = pairs_common_check(ctx, who, d_tree_ids, d_leaf_ids, k)) return rc;
+    if (!d_n_unique) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (!d_tree_ids_out && !d_leaf_ids_out && !d_indices_out && !d_first)
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": at least one of d_tree_ids_out, d_leaf_ids_out, d_indices_out and d_first must be given");
+    if (misaligned_to(d_leaf_ids_out, 8) || misaligned_to(d_n_unique, 8))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_leaf_ids_out and d_n_unique must be 8-byte aligned");
+    if (misaligned_to(d_tree_ids_out, 4) || misaligned_to(d_indices_out, 4) || misaligned_to(d_first, 4))
+        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_tree_ids_out, d_indices_out and d_first must be 4-byte aligned");
+    const ByteRange in[] = {{d_tree_ids, k * 4, "d_tree_ids"}, {d_leaf_ids, k * 8, "d_leaf_ids"}};
+    const ByteRange out[] = {{d_tree_ids_out, k * 4, "d_tree_ids_out"},
+                             {d_leaf_ids_out, k * 8, "d_leaf_ids_out"},
+                             {d_indices_out, k * 4, "d_indices_out"},
+                             {d_first, k * 4, "d_first"},
+                             {d_n_unique, 8, "d_n_unique"}};
+    if (int rc = refuse_overlaps(ctx, who, in, std::size(in), out, std::size(out), true)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    return with_stream_scratch(ctx, who, st, pairs_work(k).bytes, 0, [&](p252_ctx::LevelSet& set) {
+        return launch_pairs_unique(d_tree_ids, d_leaf_ids, k, d_tree_ids_out, d_leaf_ids_out, d_indices_out, d_first, d_n_unique, set.buf[0], st);
+    });
 }
 
 }  // (the C ABI)

@@ -734,6 +734,35 @@ class Context:
         self._check(a.fn("forest_ragged_select_device_into")(self._h, *args_a, *args_b, pick, n_pick, leaves_new, leaves_cap, offsets_new,
                                                              levels_new, levels_cap, roots_new, n_bad, _stream(self)))
 
+    # ---- the order and the distinct (tree id, leaf id) pairs that the sequential updates and the shared proofs take (csrc/pairs.hip) ----
+    def pairs_order_device(self, d_tree_ids, d_leaf_ids, k, d_order, stream=None):
+        """d_order (k,) int32/uint32 = the indices 0 .. k - 1 sorted by (tree id, leaf id, index): the stable sort by pair, on the
+        device (p252_pairs_order_device_into) — what merkle{4,2}_forest_ragged_update_sequential_device takes.  d_leaf_ids (k,)
+        int64/uint64; d_tree_ids (k,) int32/uint32, or None: every pair is of tree 0.  Both parts compare as unsigned.  Asynchronous
+        on `stream` (a torch stream; default the current one), no synchronisation: the call can be captured into a graph."""
+        f = "pairs_order_device"
+        self._check(_lib.lib().p252_pairs_order_device_into(
+            self._h, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8), k, _dev_ptr(self, f, "d_order", d_order, k * 4, elem=4),
+            stream.cuda_stream if stream is not None else _stream(self)))
+
+    def pairs_unique_device(self, d_tree_ids, d_leaf_ids, k, d_n_unique, d_tree_ids_out=None, d_leaf_ids_out=None, d_indices_out=None,
+                            d_first=None, stream=None):
+        """the distinct pairs of (d_tree_ids, d_leaf_ids), ascending, into the first d_n_unique[0] entries of every output given
+        (p252_pairs_unique_device_into): d_tree_ids_out (k,) int32/uint32 and d_leaf_ids_out (k,) int64/uint64 the pair, d_indices_out
+        (k,) int32/uint32 the low word of its leaf id (the positions merkle_multiproof_device takes), d_first (k,) int32/uint32 the
+        lowest input index that holds it.  d_n_unique: a device int64/uint64, always written; entries at and past it are left alone.
+        d_tree_ids may be None: every pair is of tree 0.  Asynchronous on `stream` (default the current one)."""
+        f = "pairs_unique_device"
+        self._check(_lib.lib().p252_pairs_unique_device_into(
+            self._h, _dev_ptr(self, f, "d_tree_ids", d_tree_ids, k * 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_leaf_ids", d_leaf_ids, k * 8, elem=8), k,
+            _dev_ptr(self, f, "d_tree_ids_out", d_tree_ids_out, k * 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_leaf_ids_out", d_leaf_ids_out, k * 8, elem=8, null_ok=True),
+            _dev_ptr(self, f, "d_indices_out", d_indices_out, k * 4, elem=4, null_ok=True),
+            _dev_ptr(self, f, "d_first", d_first, k * 4, elem=4, null_ok=True), _dev_ptr(self, f, "d_n_unique", d_n_unique, 8, elem=8),
+            stream.cuda_stream if stream is not None else _stream(self)))
+
     # ---- SURVEY §8(f) rows: truncated outputs on the device, batched Merkle openings ----
     def truncate250_device(self, d_scalars, d_out, n):
         f = "truncate250_device"

@@ -711,6 +711,60 @@ def forest_ragged_update_sequential(ctx, d_leaves, d_offsets, n_trees, max_leave
     return old, sib, pos, dep, before, after, depth
 
 
+def _pairs_on_device(f, tree_ids, leaf_ids, ctx):
+    """(d_tree_ids int32 or None, d_leaf_ids int64, k) on ctx's device: the bit patterns of uint32 tree ids and uint64 leaf ids"""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+
+    def words(x, wide):
+        if isinstance(x, torch.Tensor):
+            return x.to(dev).to(torch.int64 if wide else torch.int32).reshape(-1).contiguous()
+        a = np.asarray(x)
+        if a.size == 0:
+            raise ValueError("%s: no pairs" % f)
+        if a.dtype.kind not in "iu":
+            raise ValueError("%s: ids must be integers, not %s" % (f, a.dtype))
+        a = np.ascontiguousarray(a.astype(np.uint64 if wide else np.uint32).reshape(-1))
+        return torch.from_numpy(a.view(np.int64 if wide else np.int32)).to(dev)
+    j = words(leaf_ids, True)
+    t = None if tree_ids is None else words(tree_ids, False)
+    k = j.numel()
+    if k == 0:
+        raise ValueError("%s: no pairs" % f)
+    if t is not None and t.numel() != k:
+        raise ValueError("%s: %d tree ids, %d leaf ids" % (f, t.numel(), k))
+    return t, j, k
+
+
+def pairs_order(tree_ids, leaf_ids, ctx=None):
+    """The indices 0 .. k - 1 sorted by (tree id, leaf id, index) — the stable sort by pair that
+    Context.merkle{4,2}_forest_ragged_update_sequential_device takes as d_order — as an int32 tensor on the device, made by the library
+    (Context.pairs_order_device).  tree_ids, leaf_ids: sequences, numpy or torch; tree_ids None: every pair is of tree 0.  Both parts
+    compare as unsigned (uint32, uint64).  No synchronisation."""
+    import torch
+    ctx = ctx or Context.default()
+    t, j, k = _pairs_on_device("pairs_order", tree_ids, leaf_ids, ctx)
+    order = torch.empty(k, dtype=torch.int32, device=j.device)
+    ctx.pairs_order_device(t, j, k, order)
+    return order
+
+
+def pairs_unique(tree_ids, leaf_ids, ctx=None):
+    """The distinct pairs of (tree_ids, leaf_ids), ascending, as the shared proofs take them (Context.pairs_unique_device): returns
+    (tree_ids int32 (n,), leaf_ids int64 (n,), first int32 (n,)) on the device, first[i] the lowest input index that holds pair i.
+    tree_ids None: every pair is of tree 0 (the tree ids returned are zeros).  One synchronisation, to read the count."""
+    import torch
+    ctx = ctx or Context.default()
+    t, j, k = _pairs_on_device("pairs_unique", tree_ids, leaf_ids, ctx)
+    t_out = torch.empty(k, dtype=torch.int32, device=j.device)
+    j_out = torch.empty(k, dtype=torch.int64, device=j.device)
+    first = torch.empty(k, dtype=torch.int32, device=j.device)
+    n = torch.zeros(1, dtype=torch.int64, device=j.device)
+    ctx.pairs_unique_device(t, j, k, n, d_tree_ids_out=t_out, d_leaf_ids_out=j_out, d_first=first)
+    n = int(n.item())
+    return t_out[:n], j_out[:n], first[:n]
+
+
 def merkle4_path_roots(leaves, siblings, positions, tag=None, ctx=None):
     """Roots recomputed from n openings (numpy host buffers); compare with the tree root to verify."""
     ctx = ctx or Context.default()
