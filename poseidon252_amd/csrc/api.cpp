@@ -192,9 +192,10 @@ size_t p252host::levels_len(size_t n_leaves, size_t arity) {
 int p252host::merkle_tree_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
                               void* d_root, void* d_levels, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: n_leaves must be > 0");
-    if (!tag || !d_leaves || !d_root) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: NULL buffer");
-    if (misaligned(d_leaves) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);  // d_root: plain copy
+    const Refusal refuse{ctx, "merkle_tree"};
+    if (n_leaves == 0) return refuse("n_leaves must be > 0");
+    if (!tag || !d_leaves || !d_root) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_leaves, d_levels})) return rc;  // d_root: plain copy
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const TagArg t = tag_arg(tag);
@@ -415,7 +416,7 @@ int p252_wipe(p252_ctx* ctx) {
 }
 
 int p252_scratch_residue(p252_ctx* ctx, uint64_t* nonzero_bytes) {
-    if (!ctx || !nonzero_bytes) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "scratch_residue: NULL argument");
+    if (!ctx || !nonzero_bytes) return Refusal{ctx, "scratch_residue"}("NULL argument");
     *nonzero_bytes = 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -439,9 +440,10 @@ int p252_scratch_residue(p252_ctx* ctx, uint64_t* nonzero_bytes) {
 // ------------------------------------------------------------------------------------------
 int p252_permute_batch_device(p252_ctx* ctx, const void* d_states, void* d_out, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "permute"};
     if (n == 0) return P252_OK;
-    if (!d_states || !d_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "permute: NULL buffer");
-    if (misaligned(d_states) || misaligned(d_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!d_states || !d_out) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_states, d_out})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_permute(ctx->d_tab, d_states, d_out, n, (hipStream_t)hip_stream));
     return P252_OK;
@@ -452,14 +454,14 @@ int p252_permute_batch_device(p252_ctx* ctx, const void* d_states, void* d_out, 
 static int hash_batch_device_impl(p252_ctx* ctx, const uint64_t tag[4], const void* d_in, size_t in_len,
                                   size_t out_len, void* d_out, size_t n, void* hip_stream, bool trunc250) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "hash"};
     // dusk-safe rejects io-patterns with an empty absorb or squeeze -> Hash::finalize panics (hash.rs:134-137)
     if (in_len == 0 || out_len == 0)
         return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash: in_len and out_len must be > 0");
-    if (in_len > 0x7fffffffu || out_len > 0x7fffffffu)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash: length too large");
+    if (in_len > 0x7fffffffu || out_len > 0x7fffffffu) return refuse("length too large");
     if (n == 0) return P252_OK;
-    if (!tag || !d_in || !d_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash: NULL buffer");
-    if (misaligned(d_in) || misaligned(d_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!tag || !d_in || !d_out) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_in, d_out})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (in_len == 4 && out_len == 1)
@@ -481,13 +483,11 @@ int p252_hash_batch_truncated_device(p252_ctx* ctx, const uint64_t tag[4], const
     return hash_batch_device_impl(ctx, tag, d_in, in_len, out_len, d_out_raw, n, hip_stream, true);
 }
 
-size_t p252_merkle4_levels_len(size_t n_leaves) { return levels_len(n_leaves, 4); }
-size_t p252_merkle2_levels_len(size_t n_leaves) { return levels_len(n_leaves, 2); }
+P252_MERKLE_PAIR(size_t, levels_len, (size_t n_leaves), levels_len(n_leaves, arity))
 
-int p252_merkle4_tree_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
-                             void* d_root, void* d_levels, void* hip_stream) {
-    return merkle_tree_device(ctx, 4, tag, d_leaves, n_leaves, d_root, d_levels, hip_stream);
-}
+P252_MERKLE_PAIR(int, tree_device,
+                 (p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves, void* d_root, void* d_levels, void* hip_stream),
+                 merkle_tree_device(ctx, arity, tag, d_leaves, n_leaves, d_root, d_levels, hip_stream))
 
 // A forest of n_trees independent complete arity-4 trees of leaves_per_tree = 4^k leaves each, tree-major in d_leaves
 // (the shape of the downstream poseidon-merkle consumers, AGENTS.md:62-66: many small trees).  Level l of ALL trees is one
@@ -497,12 +497,13 @@ int p252_merkle4_tree_device(p252_ctx* ctx, const uint64_t tag[4], const void* d
 static int forest_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, size_t n_trees, size_t leaves_per_tree,
                          void* d_roots, void* d_levels, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "merkle_forest"};
     if (n_trees == 0) return P252_OK;
     const bool pow_ok = arity == 4 ? power_of_4(leaves_per_tree) : (leaves_per_tree != 0 && (leaves_per_tree & (leaves_per_tree - 1)) == 0);
-    if (!pow_ok) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: leaves_per_tree must be arity^k");
-    if (n_trees > (SIZE_MAX / 32) / leaves_per_tree) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: size overflow");
-    if (!tag || !d_leaves || !d_roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: NULL buffer");
-    if (misaligned(d_leaves) || misaligned(d_roots) || misaligned(d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!pow_ok) return refuse("leaves_per_tree must be arity^k");
+    if (n_trees > (SIZE_MAX / 32) / leaves_per_tree) return refuse("size overflow");
+    if (!tag || !d_leaves || !d_roots) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_leaves, d_roots, d_levels})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t cur_n = n_trees * leaves_per_tree;
@@ -537,35 +538,26 @@ static int forest_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], c
                                [&](p252_ctx::LevelSet& set) { return build(set.buf); });
 }
 
-int p252_merkle4_forest_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_trees, size_t leaves_per_tree,
-                               void* d_roots, void* d_levels, void* hip_stream) {
-    return forest_device(ctx, 4, tag, d_leaves, n_trees, leaves_per_tree, d_roots, d_levels, hip_stream);
-}
-
-int p252_merkle2_forest_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_trees, size_t leaves_per_tree,
-                               void* d_roots, void* d_levels, void* hip_stream) {
-    return forest_device(ctx, 2, tag, d_leaves, n_trees, leaves_per_tree, d_roots, d_levels, hip_stream);
-}
-
-int p252_merkle2_tree_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_leaves,
-                             void* d_root, void* d_levels, void* hip_stream) {
-    return merkle_tree_device(ctx, 2, tag, d_leaves, n_leaves, d_root, d_levels, hip_stream);
-}
+P252_MERKLE_PAIR(int, forest_device,
+                 (p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, size_t n_trees, size_t leaves_per_tree, void* d_roots, void* d_levels,
+                  void* hip_stream),
+                 forest_device(ctx, arity, tag, d_leaves, n_trees, leaves_per_tree, d_roots, d_levels, hip_stream))
 
 // ---- messages of different lengths in one call (ragged.hip): the sort's order array and bucket counters live in the scratch
 // pair of the calling stream (as the verify path's re-hashed roots), so calls on different streams of one context never share them
 static int hash_ragged_device_impl(p252_ctx* ctx, const void* d_tags, size_t max_len, const void* d_in, const void* d_offsets,
                                    size_t out_len, void* d_out, size_t n, void* d_n_bad, void* hip_stream, bool trunc250) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "hash_ragged"};
     if (out_len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: out_len must be > 0");
-    if (out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: out_len too large");
+    if (out_len > 0x7fffffffu) return refuse("out_len too large");
     if (n == 0) return P252_OK;
-    if (max_len == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: max_len must be > 0");
-    if (!d_tags || !d_in || !d_offsets || !d_out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
-    if (misaligned(d_tags) || misaligned(d_in) || misaligned(d_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if (misaligned_to(d_offsets, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_offsets must be 8-byte aligned");
-    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: d_n_bad must be 4-byte aligned");
-    if (n >= SIZE_MAX / 8 / (out_len > 8 ? out_len : 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: size overflow");
+    if (max_len == 0) return refuse("max_len must be > 0");
+    if (!d_tags || !d_in || !d_offsets || !d_out) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_tags, d_in, d_out})) return rc;
+    if (int rc = refuse.unless_aligned(8, {P252_NAMED(d_offsets)})) return rc;
+    if (int rc = refuse.unless_aligned(4, {P252_NAMED(d_n_bad)})) return rc;
+    if (n >= SIZE_MAX / 8 / (out_len > 8 ? out_len : 8)) return refuse("size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (!ragged_sort_enabled()) {  // P252_RAGGED_SORT=0: identity order, no scratch
@@ -631,9 +623,10 @@ int p252_host_unregister(void* p) {
 // ------------------------------------------------------------------------------------------
 int p252_truncate250_device(p252_ctx* ctx, const void* d_scalars, void* d_out_raw, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "truncate250"};
     if (n == 0) return P252_OK;
-    if (!d_scalars || !d_out_raw) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "truncate250: NULL buffer");
-    if (misaligned(d_scalars) || misaligned(d_out_raw)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!d_scalars || !d_out_raw) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_scalars, d_out_raw})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_truncate250(d_scalars, d_out_raw, n, (hipStream_t)hip_stream));
     return P252_OK;
@@ -645,10 +638,11 @@ int p252_truncate250_device(p252_ctx* ctx, const void* d_scalars, void* d_out_ra
 static int merkle4_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, void* d_levels,
                                  const void* d_indices, const void* d_new_leaves, size_t k, void* d_root, void* d_n_bad, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_leaves == 0 || n_leaves > 0xffffffffULL) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update: n_leaves must be in 1 .. 2^32 - 1");
-    if (!tag || !d_leaves || (n_leaves > 1 && !d_levels)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update: NULL buffer");
-    if (k && (!d_indices || !d_new_leaves)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update: NULL update list");
-    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_new_leaves)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    const Refusal refuse{ctx, "merkle4_update"};
+    if (n_leaves == 0 || n_leaves > 0xffffffffULL) return refuse("n_leaves must be in 1 .. 2^32 - 1");
+    if (!tag || !d_leaves || (n_leaves > 1 && !d_levels)) return refuse("NULL buffer");
+    if (k && (!d_indices || !d_new_leaves)) return refuse("NULL update list");
+    if (int rc = refuse.unless_aligned({d_leaves, d_levels, d_new_leaves})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const TagArg t = tag_arg(tag);
@@ -677,8 +671,9 @@ int p252_merkle4_update_device(p252_ctx* ctx, const uint64_t tag[4], void* d_lea
 int p252_merkle4_update_checked_device(p252_ctx* ctx, const uint64_t tag[4], void* d_leaves, size_t n_leaves, void* d_levels,
                                        const void* d_indices, const void* d_new_leaves, size_t k, void* d_root, void* d_n_bad,
                                        void* hip_stream) {
-    if (!d_n_bad) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update_checked: d_n_bad is NULL");
-    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_update_checked: d_n_bad must be 4-byte aligned");
+    const Refusal refuse{ctx, "merkle4_update_checked"};  // (before `!ctx`, as ever: without a context the message goes to p252_last_error(NULL))
+    if (!d_n_bad) return refuse("d_n_bad is NULL");
+    if (int rc = refuse.unless_aligned(4, {P252_NAMED(d_n_bad)})) return rc;
     return merkle4_update_device(ctx, tag, d_leaves, n_leaves, d_levels, d_indices, d_new_leaves, k, d_root, d_n_bad, hip_stream);
 }
 
@@ -686,9 +681,10 @@ int p252_merkle4_update_checked_device(p252_ctx* ctx, const uint64_t tag[4], voi
 // constants through the pair, src/hades/round_constants.rs:66-67, and reads its KAT inputs with from_hex_str, src/hades.rs:131)
 int p252_to_bytes_device(p252_ctx* ctx, const void* d_scalars, void* d_bytes, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "to_bytes"};
     if (n == 0) return P252_OK;
-    if (!d_scalars || !d_bytes) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "to_bytes: NULL buffer");
-    if (misaligned(d_scalars) || misaligned(d_bytes)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!d_scalars || !d_bytes) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_scalars, d_bytes})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_to_canonical(d_scalars, d_bytes, n, (hipStream_t)hip_stream));
     return P252_OK;
@@ -696,9 +692,10 @@ int p252_to_bytes_device(p252_ctx* ctx, const void* d_scalars, void* d_bytes, si
 
 int p252_from_bytes_device(p252_ctx* ctx, const void* d_bytes, void* d_scalars, void* d_ok, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "from_bytes"};
     if (n == 0) return P252_OK;
-    if (!d_scalars || !d_bytes) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "from_bytes: NULL buffer");
-    if (misaligned(d_scalars) || misaligned(d_bytes)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!d_scalars || !d_bytes) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_scalars, d_bytes})) return rc;
     static const Digits9 r2 = [] {
         Digits9 d;
         encode_balanced29(FrHost::pow2(517), d.d);  // v * 2^517 / 2^261 = v * 2^256: the Montgomery form
@@ -712,10 +709,10 @@ int p252_from_bytes_device(p252_ctx* ctx, const void* d_bytes, void* d_scalars, 
 // the argument checks of the fixed-depth re-hash (shared with the verify call)
 static int path_batch_check(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
                             const void* d_positions, size_t depth, const void* d_roots) {
-    const std::string who = arity == 4 ? "merkle4_path" : "merkle2_path";
-    if (!tag || !d_leaves || !d_roots || (depth && (!d_siblings || !d_positions))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
-    if (depth > 0xffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": depth too large");
-    if (misaligned(d_leaves) || misaligned(d_roots) || (depth && misaligned(d_siblings))) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    const Refusal refuse{ctx, arity == 4 ? "merkle4_path" : "merkle2_path"};
+    if (!tag || !d_leaves || !d_roots || (depth && (!d_siblings || !d_positions))) return refuse("NULL buffer");
+    if (depth > 0xffffu) return refuse("depth too large");
+    if (int rc = refuse.unless_aligned({d_leaves, d_roots, depth ? d_siblings : nullptr})) return rc;
     return P252_OK;
 }
 
@@ -735,46 +732,36 @@ static int path_batch_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4
     return P252_OK;
 }
 
-int p252_merkle4_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
-                                   const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
-    return path_batch_device(ctx, 4, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n, hip_stream);
-}
-
-int p252_merkle2_path_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
-                                   const void* d_positions, size_t depth, void* d_roots, size_t n, void* hip_stream) {
-    return path_batch_device(ctx, 2, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n, hip_stream);
-}
+P252_MERKLE_PAIR(int, path_batch_device,
+                 (p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings, const void* d_positions, size_t depth,
+                  void* d_roots, size_t n, void* hip_stream),
+                 path_batch_device(ctx, arity, tag, d_leaves, d_siblings, d_positions, depth, d_roots, n, hip_stream))
 
 // Opening::verify in bulk: re-hash (either arity) into this stream's scratch, then one byte per opening
 static int verify_batch_device(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
                                const void* d_positions, size_t depth, const void* d_root, void* d_ok, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
     if (n == 0) return P252_OK;
-    const std::string who = arity == 4 ? "merkle4_verify" : "merkle2_verify";
-    if (!d_root || !d_ok) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
-    if (misaligned(d_root)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if (n > (SIZE_MAX / 32)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    const Refusal refuse{ctx, arity == 4 ? "merkle4_verify" : "merkle2_verify"};
+    if (!d_root || !d_ok) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_root})) return rc;
+    if (n > (SIZE_MAX / 32)) return refuse("size overflow");
     // the re-hash's own refusals, before any scratch is taken (its output is the scratch: d_root, checked above, stands in for it)
     if (int rc = path_batch_check(ctx, arity, tag, d_leaves, d_siblings, d_positions, depth, d_root)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     // the recomputed roots live in the scratch pair of THIS stream (ctx.hpp): n x 32 bytes
-    return with_stream_scratch(ctx, who, st, n * 32, 0, [&](p252_ctx::LevelSet& set) {
+    return with_stream_scratch(ctx, refuse.who, st, n * 32, 0, [&](p252_ctx::LevelSet& set) {
         const hipError_t e = launch_path(arity, ctx->d_tab, tag_arg(tag), d_leaves, d_siblings, d_positions, depth, set.buf[0], n, st);
         if (e != hipSuccess) return e;
         return launch_compare_roots(set.buf[0], d_root, d_ok, n, st);
     });
 }
 
-int p252_merkle4_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
-                                     const void* d_positions, size_t depth, const void* d_root, void* d_ok, size_t n, void* hip_stream) {
-    return verify_batch_device(ctx, 4, tag, d_leaves, d_siblings, d_positions, depth, d_root, d_ok, n, hip_stream);
-}
-
-int p252_merkle2_verify_batch_device(p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings,
-                                     const void* d_positions, size_t depth, const void* d_root, void* d_ok, size_t n, void* hip_stream) {
-    return verify_batch_device(ctx, 2, tag, d_leaves, d_siblings, d_positions, depth, d_root, d_ok, n, hip_stream);
-}
+P252_MERKLE_PAIR(int, verify_batch_device,
+                 (p252_ctx* ctx, const uint64_t tag[4], const void* d_leaves, const void* d_siblings, const void* d_positions, size_t depth,
+                  const void* d_root, void* d_ok, size_t n, void* hip_stream),
+                 verify_batch_device(ctx, arity, tag, d_leaves, d_siblings, d_positions, depth, d_root, d_ok, n, hip_stream))
 
 // depth of the tree over n_leaves = number of levels above the leaves (an arity^k-leaf tree: k; a single leaf: 0).  The sum wraps
 // at the top of size_t, which callers see (ABI): the depth of SIZE_MAX leaves is 1.
@@ -783,8 +770,7 @@ static size_t tree_depth(size_t n_leaves, size_t arity) {
     for (size_t c = n_leaves; c > 1; c = (c + arity - 1) / arity) ++d;
     return d;
 }
-size_t p252_merkle4_depth(size_t n_leaves) { return tree_depth(n_leaves, 4); }
-size_t p252_merkle2_depth(size_t n_leaves) { return tree_depth(n_leaves, 2); }
+P252_MERKLE_PAIR(size_t, depth, (size_t n_leaves), tree_depth(n_leaves, arity))
 
 // Openings of a STORED tree, extracted on the device (openings.hip: pure data movement): for each of the k leaf positions the
 // leaf, the three siblings per level and the position bytes, in exactly the layout p252_merkle4_path_batch_device takes — build
@@ -793,14 +779,12 @@ static int openings_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, 
                            void* d_leaves_out, void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
     if (k == 0) return P252_OK;
-    const std::string who = arity == 4 ? "merkle4_openings" : "merkle2_openings";
-    if (n_leaves == 0 || n_leaves > 0xffffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves must be in 1 .. 2^32 - 1 (positions are uint32)");
+    const Refusal refuse{ctx, arity == 4 ? "merkle4_openings" : "merkle2_openings"};
+    if (n_leaves == 0 || n_leaves > 0xffffffffu) return refuse("n_leaves must be in 1 .. 2^32 - 1 (positions are uint32)");
     const size_t depth = tree_depth(n_leaves, arity);
-    if (!d_leaves || !d_indices || !d_leaves_out || (depth && (!d_levels || !d_siblings || !d_positions)))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
-    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_siblings)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / counter must be 4-byte aligned");
+    if (!d_leaves || !d_indices || !d_leaves_out || (depth && (!d_levels || !d_siblings || !d_positions))) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_leaves, d_levels, d_leaves_out, d_siblings})) return rc;
+    if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4)) return refuse("indices / counter must be 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (d_n_bad) HIP_TRY(ctx, hipMemsetAsync(d_n_bad, 0, 4, st));
@@ -809,26 +793,19 @@ static int openings_device(p252_ctx* ctx, unsigned arity, const void* d_leaves, 
     return P252_OK;
 }
 
-int p252_merkle4_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
-                                 void* d_leaves_out, void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream) {
-    return openings_device(ctx, 4, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_siblings, d_positions, d_n_bad, hip_stream);
-}
-
-int p252_merkle2_openings_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
-                                 void* d_leaves_out, void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream) {
-    return openings_device(ctx, 2, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_siblings, d_positions, d_n_bad, hip_stream);
-}
+P252_MERKLE_PAIR(int, openings_device,
+                 (p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k, void* d_leaves_out,
+                  void* d_siblings, void* d_positions, void* d_n_bad, void* hip_stream),
+                 openings_device(ctx, arity, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_siblings, d_positions, d_n_bad, hip_stream))
 
 // ---- many leaves of ONE stored tree behind one shared proof (multiproof.hip): a sibling that another leaf of the batch determines
 // is not stored, and verification hashes every ancestor once.  The scratch — the counters, the scan tiles and two work lists in the
 // first buffer; the verify's two lists of node values in the second — is the pair of the calling stream ----
-size_t p252_merkle4_multiproof_bound(size_t n_leaves, size_t k) { return n_leaves && k ? multiproof_plan(4, n_leaves, k).bound : 0; }
-size_t p252_merkle2_multiproof_bound(size_t n_leaves, size_t k) { return n_leaves && k ? multiproof_plan(2, n_leaves, k).bound : 0; }
+P252_MERKLE_PAIR(size_t, multiproof_bound, (size_t n_leaves, size_t k), n_leaves && k ? multiproof_plan(arity, n_leaves, k).bound : 0)
 
-static int multiproof_shape_check(p252_ctx* ctx, const std::string& who, size_t n_leaves, size_t k) {
-    if (k == 0 || n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves and k must be > 0");
-    if (n_leaves > 0xffffffffu || k > 0xffffffffu)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": n_leaves and k must be below 2^32 (positions are uint32)");
+static int multiproof_shape_check(const Refusal& refuse, size_t n_leaves, size_t k) {
+    if (k == 0 || n_leaves == 0) return refuse("n_leaves and k must be > 0");
+    if (n_leaves > 0xffffffffu || k > 0xffffffffu) return refuse("n_leaves and k must be below 2^32 (positions are uint32)");
     return P252_OK;
 }
 
@@ -836,18 +813,17 @@ static int multiproof_device(p252_ctx* ctx, unsigned arity, const void* d_leaves
                              const void* d_indices, size_t k, void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len,
                              void* d_n_bad, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    const std::string who = arity == 4 ? "merkle4_multiproof" : "merkle2_multiproof";
-    if (int rc = multiproof_shape_check(ctx, who, n_leaves, k)) return rc;
+    const Refusal refuse{ctx, arity == 4 ? "merkle4_multiproof" : "merkle2_multiproof"};
+    if (int rc = multiproof_shape_check(refuse, n_leaves, k)) return rc;
     const MultiproofPlan plan = multiproof_plan(arity, n_leaves, k);
     if (!d_leaves || !d_indices || !d_leaves_out || !d_proof_len || (plan.depth && !d_levels) || (proof_cap && !d_proof))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
-    if (misaligned(d_leaves) || misaligned(d_levels) || misaligned(d_leaves_out) || misaligned(d_proof))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+        return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_leaves, d_levels, d_leaves_out, d_proof})) return rc;
     if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4) || misaligned_to(d_proof_len, 8))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / d_n_bad must be 4-byte, d_proof_len 8-byte aligned");
+        return refuse("indices / d_n_bad must be 4-byte, d_proof_len 8-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    return with_stream_scratch(ctx, who, st, plan.work_bytes(), 0, [&](p252_ctx::LevelSet& set) {
+    return with_stream_scratch(ctx, refuse.who, st, plan.work_bytes(), 0, [&](p252_ctx::LevelSet& set) {
         return launch_multiproof(plan, d_leaves, d_levels, d_indices, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, set.buf[0], st);
     });
 }
@@ -856,59 +832,46 @@ static int multiproof_verify_device(p252_ctx* ctx, unsigned arity, const uint64_
                                     const void* d_leaves_in, size_t k, const void* d_proof, size_t proof_len, const void* d_root,
                                     void* d_ok, void* d_root_out, void* d_n_hashed, void* d_n_bad, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    const std::string who = arity == 4 ? "merkle4_multiproof_verify" : "merkle2_multiproof_verify";
-    if (int rc = multiproof_shape_check(ctx, who, n_leaves, k)) return rc;
-    if (!tag || !d_indices || !d_leaves_in || !d_root || !d_ok || (proof_len && !d_proof))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
-    if (misaligned(d_leaves_in) || misaligned(d_proof) || misaligned(d_root) || misaligned(d_root_out))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    const Refusal refuse{ctx, arity == 4 ? "merkle4_multiproof_verify" : "merkle2_multiproof_verify"};
+    if (int rc = multiproof_shape_check(refuse, n_leaves, k)) return rc;
+    if (!tag || !d_indices || !d_leaves_in || !d_root || !d_ok || (proof_len && !d_proof)) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_leaves_in, d_proof, d_root, d_root_out})) return rc;
     if (misaligned_to(d_indices, 4) || misaligned_to(d_n_bad, 4) || misaligned_to(d_n_hashed, 8))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": indices / d_n_bad must be 4-byte, d_n_hashed 8-byte aligned");
-    if (proof_len > SIZE_MAX / 32) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+        return refuse("indices / d_n_bad must be 4-byte, d_n_hashed 8-byte aligned");
+    if (proof_len > SIZE_MAX / 32) return refuse("size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const MultiproofPlan plan = multiproof_plan(arity, n_leaves, k);
-    return with_stream_scratch(ctx, who, st, plan.work_bytes(), plan.values_bytes(), [&](p252_ctx::LevelSet& set) {
+    return with_stream_scratch(ctx, refuse.who, st, plan.work_bytes(), plan.values_bytes(), [&](p252_ctx::LevelSet& set) {
         return launch_multiproof_verify(ctx->d_tab, tag_arg(tag), plan, d_indices, d_leaves_in, d_proof, proof_len, d_root, d_ok, d_root_out,
                                         d_n_hashed, d_n_bad, set.buf[0], set.buf[1], st);
     });
 }
 
-int p252_merkle4_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
-                                   void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream) {
-    return multiproof_device(ctx, 4, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, hip_stream);
-}
+P252_MERKLE_PAIR(int, multiproof_device,
+                 (p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k, void* d_leaves_out,
+                  void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream),
+                 multiproof_device(ctx, arity, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad,
+                                   hip_stream))
 
-int p252_merkle2_multiproof_device(p252_ctx* ctx, const void* d_leaves, size_t n_leaves, const void* d_levels, const void* d_indices, size_t k,
-                                   void* d_leaves_out, void* d_proof, size_t proof_cap, void* d_proof_len, void* d_n_bad, void* hip_stream) {
-    return multiproof_device(ctx, 2, d_leaves, n_leaves, d_levels, d_indices, k, d_leaves_out, d_proof, proof_cap, d_proof_len, d_n_bad, hip_stream);
-}
-
-int p252_merkle4_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
-                                          size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
-                                          void* d_n_hashed, void* d_n_bad, void* hip_stream) {
-    return multiproof_verify_device(ctx, 4, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
-                                    d_n_bad, hip_stream);
-}
-
-int p252_merkle2_multiproof_verify_device(p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in,
-                                          size_t k, const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out,
-                                          void* d_n_hashed, void* d_n_bad, void* hip_stream) {
-    return multiproof_verify_device(ctx, 2, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out, d_n_hashed,
-                                    d_n_bad, hip_stream);
-}
+P252_MERKLE_PAIR(int, multiproof_verify_device,
+                 (p252_ctx* ctx, const uint64_t tag[4], size_t n_leaves, const void* d_indices, const void* d_leaves_in, size_t k,
+                  const void* d_proof, size_t proof_len, const void* d_root, void* d_ok, void* d_root_out, void* d_n_hashed, void* d_n_bad,
+                  void* hip_stream),
+                 multiproof_verify_device(ctx, arity, tag, n_leaves, d_indices, d_leaves_in, k, d_proof, proof_len, d_root, d_ok, d_root_out,
+                                          d_n_hashed, d_n_bad, hip_stream))
 
 // ---- encryption row (src/encryption.rs:62-95 -> dusk_safe::encrypt / decrypt) ----
 static int crypt_device(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const void* d_in, const void* d_secrets,
                         const void* d_nonces, size_t len, void* d_out, void* d_ok, size_t n, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: unknown variant");
+    const Refusal refuse{ctx, "encrypt/decrypt"};
+    if (!crypt_variant_ok(variant)) return refuse("unknown variant");
     if (len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "encrypt/decrypt: empty message");
-    if (len >= 0x1ffffff0u) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: message too long");
+    if (len >= 0x1ffffff0u) return refuse("message too long");
     if (n == 0) return P252_OK;
-    if (!tag || !d_in || !d_secrets || !d_nonces || !d_out || (decrypt && !d_ok))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: NULL buffer");
-    if (misaligned(d_in) || misaligned(d_secrets) || misaligned(d_nonces) || misaligned(d_out)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
+    if (!tag || !d_in || !d_secrets || !d_nonces || !d_out || (decrypt && !d_ok)) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_in, d_secrets, d_nonces, d_out})) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
     int rc = prepare_prog(ctx, variant, len);
@@ -935,17 +898,16 @@ static int crypt_ragged_device(p252_ctx* ctx, int variant, bool decrypt, const v
                                const void* d_offsets, const void* d_secrets, const void* d_nonces, void* d_out, void* d_ok, size_t n,
                                void* d_n_bad, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    const std::string who = decrypt ? "decrypt_ragged" : "encrypt_ragged";
-    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": unknown variant");
+    const Refusal refuse{ctx, decrypt ? "decrypt_ragged" : "encrypt_ragged"};
+    if (!crypt_variant_ok(variant)) return refuse("unknown variant");
     if (max_len == 0 || max_len > P252_CRYPT_RAGGED_MAX_LEN)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_len must be 1 .. P252_CRYPT_RAGGED_MAX_LEN = " + std::to_string(P252_CRYPT_RAGGED_MAX_LEN));
+        return refuse("max_len must be 1 .. P252_CRYPT_RAGGED_MAX_LEN = " + std::to_string(P252_CRYPT_RAGGED_MAX_LEN));
     if (n == 0) return P252_OK;
-    if (!d_tags || !d_in || !d_offsets || !d_secrets || !d_nonces || !d_out || (decrypt && !d_ok)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
-    if (misaligned(d_tags) || misaligned(d_in) || misaligned(d_secrets) || misaligned(d_nonces) || misaligned(d_out))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, ALIGN_MSG);
-    if (misaligned_to(d_offsets, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_offsets must be 8-byte aligned");
-    if (misaligned_to(d_n_bad, 4)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": d_n_bad must be 4-byte aligned");
-    if (n >= SIZE_MAX / 128 || n_scalars >= SIZE_MAX / 64 || n_scalars + n >= SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    if (!d_tags || !d_in || !d_offsets || !d_secrets || !d_nonces || !d_out || (decrypt && !d_ok)) return refuse("NULL buffer");
+    if (int rc = refuse.unless_aligned({d_tags, d_in, d_secrets, d_nonces, d_out})) return rc;
+    if (int rc = refuse.unless_aligned(8, {P252_NAMED(d_offsets)})) return rc;
+    if (int rc = refuse.unless_aligned(4, {P252_NAMED(d_n_bad)})) return rc;
+    if (n >= SIZE_MAX / 128 || n_scalars >= SIZE_MAX / 64 || n_scalars + n >= SIZE_MAX / 64) return refuse("size overflow");
     const size_t msg_bytes = n_scalars * 32, cph_bytes = (n_scalars + n) * 32;
     const ByteRange in[] = {{d_tags, max_len * 32, "d_tags"},
                             {d_in, decrypt ? cph_bytes : msg_bytes, decrypt ? "d_ciphers" : "d_messages"},
@@ -953,10 +915,10 @@ static int crypt_ragged_device(p252_ctx* ctx, int variant, bool decrypt, const v
                             {d_secrets, n * 64, "d_secrets"},
                             {d_nonces, n * 32, "d_nonces"}};
     const ByteRange out[] = {{d_out, decrypt ? msg_bytes : cph_bytes, decrypt ? "d_messages" : "d_ciphers"}, {d_ok, decrypt ? n : 0, "d_ok"}, {d_n_bad, 4, "d_n_bad"}};
-    if (int rc = refuse_overlaps(ctx, who, in, std::size(in), out, std::size(out), true)) return rc;
+    if (int rc = refuse_overlaps(refuse, in, std::size(in), out, std::size(out), true)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    return with_stream_scratch(ctx, who, st, crypt_ragged_order_bytes(n, max_len), crypt_ragged_hist_bytes(), [&](p252_ctx::LevelSet& set) {
+    return with_stream_scratch(ctx, refuse.who, st, crypt_ragged_order_bytes(n, max_len), crypt_ragged_hist_bytes(), [&](p252_ctx::LevelSet& set) {
         return launch_crypt_ragged(decrypt, variant, ctx->d_tab, d_tags, max_len, d_in, (uint64_t)n_scalars, d_offsets, d_secrets, d_nonces, d_out, d_ok, n,
                                    d_n_bad, set.buf[0], set.buf[1], st);
     });
@@ -1159,8 +1121,9 @@ int p252_merkle4_tree_multi_device(p252_ctx* const* ctxs, size_t n_ctx, const ui
 // ------------------------------------------------------------------------------------------
 int p252_clock_probe_device(p252_ctx* ctx, void* d_out6, unsigned spin_us, void* hip_stream) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (!d_out6 || misaligned_to(d_out6, 8)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "clock_probe: d_out6 must be an 8-byte aligned device buffer of 6 x uint64");
-    if (spin_us > 1000000u) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "clock_probe: spin_us > 1 s");
+    const Refusal refuse{ctx, "clock_probe"};
+    if (!d_out6 || misaligned_to(d_out6, 8)) return refuse("d_out6 must be an 8-byte aligned device buffer of 6 x uint64");
+    if (spin_us > 1000000u) return refuse("spin_us > 1 s");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_clock_probe(d_out6, spin_us * 100u, (hipStream_t)hip_stream));  // real-time counter: 100 MHz
     return P252_OK;
@@ -1174,19 +1137,20 @@ int p252_staging_lanes(size_t n_ctx) { return staging_lanes_per_ctx(n_ctx ? n_ct
 size_t p252_tables_size(void) { return (size_t)Tab29Layout::TOTAL * sizeof(int32_t); }
 
 int p252_tables_export(p252_ctx* ctx, void* host_buf, size_t len) {
-    if (!ctx || !host_buf || len != p252_tables_size()) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "tables_export: bad args");
+    if (!ctx || !host_buf || len != p252_tables_size()) return Refusal{ctx, "tables_export"}("bad args");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpy(host_buf, ctx->d_tab, len, hipMemcpyDeviceToHost));
     return P252_OK;
 }
 
 int p252_tables_import(p252_ctx* ctx, const void* host_buf, size_t len) {
-    if (!ctx || !host_buf || len != p252_tables_size()) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "tables_import: bad args");
+    const Refusal refuse{ctx, "tables_import"};
+    if (!ctx || !host_buf || len != p252_tables_size()) return refuse("bad args");
     // The table is a pure function of arc.bin / mds.bin, which are compiled in: anything else than what this library
     // derives itself (with its Cauchy-structure and column-bound checks) is a corrupted or mismatched broadcast and
     // would give silently wrong digests — refuse it.
     if (std::memcmp(host_buf, host_tables().data(), len) != 0)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "tables_import: the table differs from the one this library derives from its arc.bin / mds.bin");
+        return refuse("the table differs from the one this library derives from its arc.bin / mds.bin");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpy(ctx->d_tab, host_buf, len, hipMemcpyHostToDevice));
     std::memcpy(ctx->h_tab.data(), host_buf, len);

@@ -1,4 +1,4 @@
-// forest_append.h — launch interface between api.cpp and forest_append.hip: leaves appended to the trees of a built forest of trees
+// forest_append.h — launch interface between api_forest.cpp and forest_append.hip: leaves appended to the trees of a built forest of trees
 // of DIFFERENT sizes, written as a new compact forest (p252_merkle{4,2}_forest_ragged_append_device_into), and the same after each
 // tree was cut to its first k_t leaves (p252_merkle{4,2}_forest_ragged_resize_device_into).  Clean nodes are moved, only the nodes
 // above a new leaf or a cut are hashed (by forest_update.hip's digest kernels, on lists this unit makes).

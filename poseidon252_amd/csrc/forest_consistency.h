@@ -1,4 +1,4 @@
-// forest_consistency.h — launch interface between api.cpp and forest_consistency.hip: the proof that a tree of a ragged forest, now
+// forest_consistency.h — launch interface between api_forest.cpp and forest_consistency.hip: the proof that a tree of a ragged forest, now
 // of m leaves, is the tree it was at n <= m leaves with leaves appended and nothing before them changed
 // (p252_merkle{4,2}_forest_ragged_consistency_device_into), and its check against the two roots
 // (p252_merkle{4,2}_forest_consistency_verify_device_into).  The proof of (tree t, old count n) is the opening of leaf index n of the

@@ -1,4 +1,4 @@
-// forest_frontier.h — launch interface between api.cpp and forest_frontier.hip: leaves appended to a forest of Merkle trees that is
+// forest_frontier.h — launch interface between api_forest.cpp and forest_frontier.hip: leaves appended to a forest of Merkle trees that is
 // kept ONLY as its frontiers (p252_merkle{4,2}_forest_frontier_append_device: per tree a leaf count, a root and (depth + 1) rows of
 // arity - 1 scalars, updated in place), and that state taken out of a built ragged forest
 // (p252_merkle{4,2}_forest_frontier_extract_device_into: data movement only).  The digests of an append run on multiproof.hip's

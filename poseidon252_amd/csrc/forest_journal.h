@@ -1,4 +1,4 @@
-// forest_journal.h — launch interface between api.cpp and forest_journal.hip: the journaled leaf update of a ragged forest
+// forest_journal.h — launch interface between api_forest.cpp and forest_journal.hip: the journaled leaf update of a ragged forest
 // (p252_merkle{4,2}_forest_ragged_update_journaled_device_into: the update of forest_update.h that first saves every leaf and node it
 // overwrites) and the swap that undoes, and then redoes, it without one digest (p252_merkle{4,2}_forest_ragged_journal_swap_device_into).
 #pragma once

@@ -1,4 +1,4 @@
-// forest_multiproof.h — launch interface between api.cpp and forest_multiproof.hip: k (tree id, leaf id) pairs anywhere in a built
+// forest_multiproof.h — launch interface between api_forest.cpp and forest_multiproof.hip: k (tree id, leaf id) pairs anywhere in a built
 // forest of trees of DIFFERENT sizes proved by one shared, tree-major proof (p252_merkle{4,2}_forest_ragged_multiproof_device_into: data
 // movement only) and checked with every ancestor hashed once (p252_merkle{4,2}_forest_ragged_multiproof_verify_device_into).  Each
 // tree's part of the proof is the single-tree proof of multiproof.h; the format is in include/poseidon252_hip.h and DESIGN.md.

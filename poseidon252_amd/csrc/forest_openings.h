@@ -1,4 +1,4 @@
-// forest_openings.h — launch interface between api.cpp and forest_openings.hip: openings out of a forest of trees of DIFFERENT
+// forest_openings.h — launch interface between api_forest.cpp and forest_openings.hip: openings out of a forest of trees of DIFFERENT
 // sizes (p252_merkle{4,2}_forest_ragged_openings_device), their re-hash with a depth per opening
 // (p252_merkle{4,2}_path_ragged_device) and the comparison with a root per opening (p252_merkle{4,2}_forest_ragged_verify_device).
 // Layout of k openings at stride D: leaves[k], siblings[k][D][arity - 1], positions[k][D], depths[k] (uint8; rows l >= depths[i]

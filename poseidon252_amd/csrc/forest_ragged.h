@@ -1,4 +1,4 @@
-// forest_ragged.h — launch interface between api.cpp and forest_ragged.hip: a forest of Merkle trees of DIFFERENT sizes in one
+// forest_ragged.h — launch interface between api_forest.cpp and forest_ragged.hip: a forest of Merkle trees of DIFFERENT sizes in one
 // call (p252_merkle{4,2}_forest_ragged*).  Tree t = leaves[offsets[t] .. offsets[t+1]); each tree is exactly what
 // p252_merkle{4,2}_tree builds (levels zero-padded to a multiple of the arity, a single leaf is its own root).
 // Also the select of such forests (p252_merkle{4,2}_forest_ragged_select_device_into): trees gathered into a new forest, nothing hashed.
@@ -27,7 +27,7 @@ struct ForestRaggedPlan {
     size_t meta_bytes = 0;  // the bookkeeping: per-tree leaf counts, the scans, the first-tree rows (a multiple of 256 bytes)
 };
 
-// levels above the leaves of a tree of n leaves, for the plans and api.cpp's checks: p252_merkle{4,2}_depth without its wrap-around at SIZE_MAX
+// levels above the leaves of a tree of n leaves, for the plans and api_forest.cpp's checks: p252_merkle{4,2}_depth without its wrap-around at SIZE_MAX
 unsigned forest_ragged_depth(size_t n, unsigned arity);
 ForestRaggedPlan forest_ragged_plan(unsigned arity, size_t n_leaves, size_t n_trees, size_t max_leaves, bool levels);
 

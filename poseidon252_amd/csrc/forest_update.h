@@ -1,4 +1,4 @@
-// forest_update.h — launch interface between api.cpp and forest_update.hip: k leaf updates (tree id, leaf id, new leaf) anywhere
+// forest_update.h — launch interface between api_forest.cpp and forest_update.hip: k leaf updates (tree id, leaf id, new leaf) anywhere
 // in a built forest of trees of DIFFERENT sizes (p252_merkle{4,2}_forest_ragged_update_device), every dirty node hashed once.
 #pragma once
 #include <hip/hip_runtime.h>

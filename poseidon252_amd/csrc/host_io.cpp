@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/poseidon252_hip.h"
+#include "api_util.hpp"
 #include "ctx.hpp"
 #include "kernels.h"
 
@@ -364,12 +365,13 @@ static int leaves_to_device(p252_ctx* ctx, Route route, unsigned arity, const ui
 static int hash_batch_host_impl(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* in, size_t in_len, size_t out_len,
                                 uint64_t* out, size_t n, bool trunc250) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "hash"};
     // dusk-safe rejects io-patterns with an empty absorb or squeeze -> Hash::finalize panics (hash.rs:134-137)
     if (in_len == 0 || out_len == 0)
         return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash: in_len and out_len must be > 0");
-    if (in_len > 0x7fffffffu || out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash: length too large");
+    if (in_len > 0x7fffffffu || out_len > 0x7fffffffu) return refuse("length too large");
     if (n == 0) return P252_OK;
-    if (!tag || !in || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash: NULL buffer");
+    if (!tag || !in || !out) return refuse("NULL buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const TagArg targ = tag_arg(tag);
     const bool single = in_len == 4 && out_len == 1, pair = in_len == 2 && out_len == 1;
@@ -391,24 +393,22 @@ static int hash_batch_host_impl(p252_ctx* ctx, const uint64_t tag[4], const uint
 static int hash_ragged_host_impl(p252_ctx* ctx, const uint64_t* tags, size_t max_len, const uint64_t* in, const uint64_t* offsets,
                                  size_t out_len, uint64_t* out, size_t n, bool trunc250) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "hash_ragged"};
     if (out_len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: out_len must be > 0");
-    if (out_len > 0x7fffffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: out_len too large");
+    if (out_len > 0x7fffffffu) return refuse("out_len too large");
     if (n == 0) return P252_OK;
-    if (max_len == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: max_len must be > 0");
-    if (!tags || !offsets || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
+    if (max_len == 0) return refuse("max_len must be > 0");
+    if (!tags || !offsets || !out) return refuse("NULL buffer");
     for (size_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i])
-            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: offsets decrease at message " + std::to_string(i));
+        if (offsets[i + 1] < offsets[i]) return refuse("offsets decrease at message " + std::to_string(i));
         const uint64_t len = offsets[i + 1] - offsets[i];
         if (len == 0)  // a zero-length absorb is an invalid io-pattern (dusk-safe; Hash::finalize panics, hash.rs:134-137)
             return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "hash_ragged: message " + std::to_string(i) + " is empty");
-        if (len > max_len)
-            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: message " + std::to_string(i) + " is longer than max_len");
+        if (len > max_len) return refuse("message " + std::to_string(i) + " is longer than max_len");
     }
-    if (!in) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: NULL buffer");
+    if (!in) return refuse("NULL buffer");
     const uint64_t total = offsets[n] - offsets[0];
-    if (total > SIZE_MAX / 64 || max_len > SIZE_MAX / 64 || n > SIZE_MAX / 64 / out_len)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "hash_ragged: size overflow");
+    if (total > SIZE_MAX / 64 || max_len > SIZE_MAX / 64 || n > SIZE_MAX / 64 / out_len) return refuse("size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> rebased(offsets, offsets + n + 1);
     for (auto& o : rebased) o -= offsets[0];
@@ -431,18 +431,18 @@ static int hash_ragged_host_impl(p252_ctx* ctx, const uint64_t* tags, size_t max
 static int forest_ragged_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets,
                               size_t n_trees, uint64_t* roots, uint64_t* levels) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "merkle_forest_ragged"};
     if (n_trees == 0) return P252_OK;
-    if (!tag || !leaves || !offsets || !roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: NULL buffer");
+    if (!tag || !leaves || !offsets || !roots) return refuse("NULL buffer");
     size_t max_leaves = 0, lvl_n = 0;
     for (size_t t = 0; t < n_trees; ++t) {
-        if (offsets[t + 1] < offsets[t])
-            return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: offsets decrease at tree " + std::to_string(t));
+        if (offsets[t + 1] < offsets[t]) return refuse("offsets decrease at tree " + std::to_string(t));
         const uint64_t n = offsets[t + 1] - offsets[t];
-        if (n == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: tree " + std::to_string(t) + " is empty");
+        if (n == 0) return refuse("tree " + std::to_string(t) + " is empty");
         if (n > max_leaves) max_leaves = n;
     }
     const uint64_t total = offsets[n_trees] - offsets[0];
-    if (total > SIZE_MAX / 64 || n_trees > SIZE_MAX / 64) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest_ragged: size overflow");
+    if (total > SIZE_MAX / 64 || n_trees > SIZE_MAX / 64) return refuse("size overflow");
     if (levels)
         for (size_t t = 0; t < n_trees; ++t) lvl_n += levels_len(offsets[t + 1] - offsets[t], arity);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -467,8 +467,9 @@ static int forest_ragged_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[
 static int merkle_tree_host(p252_ctx* ctx, unsigned arity, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
                             uint64_t root[4], uint64_t* levels) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (n_leaves == 0) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: n_leaves must be > 0");
-    if (!tag || !leaves || !root) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_tree: NULL buffer");
+    const Refusal refuse{ctx, "merkle_tree"};
+    if (n_leaves == 0) return refuse("n_leaves must be > 0");
+    if (!tag || !leaves || !root) return refuse("NULL buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t lvl_bytes = levels_len(n_leaves, arity) * 32, n_l1 = n_leaves / arity;
     int rc = scratch(ctx, 0, (levels ? lvl_bytes : 0) + 32);
@@ -494,8 +495,9 @@ extern "C" {
 
 int p252_permute_batch(p252_ctx* ctx, const uint64_t* states, uint64_t* out, size_t n) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "permute"};
     if (n == 0) return P252_OK;
-    if (!states || !out) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "permute: NULL buffer");
+    if (!states || !out) return refuse("NULL buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t chunk = staging_chunk_items(P252_HADES_WIDTH * 32);
     const Route route = host_pipeline() && n >= 2 * chunk && !(is_pinned(states) && is_pinned(out)) ? Route::STAGED : Route::ONE_SHOT;
@@ -526,25 +528,14 @@ int p252_hash_ragged_truncated(p252_ctx* ctx, const uint64_t* tags, size_t max_l
     return hash_ragged_host_impl(ctx, tags, max_len, in, offsets, out_len, out_raw, n, true);
 }
 
-int p252_merkle4_tree(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
-                      uint64_t root[4], uint64_t* levels) {
-    return merkle_tree_host(ctx, 4, tag, leaves, n_leaves, root, levels);
-}
+P252_MERKLE_PAIR(int, tree,
+                 (p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves, uint64_t root[4], uint64_t* levels),
+                 merkle_tree_host(ctx, arity, tag, leaves, n_leaves, root, levels))
 
-int p252_merkle2_tree(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_leaves,
-                      uint64_t root[4], uint64_t* levels) {
-    return merkle_tree_host(ctx, 2, tag, leaves, n_leaves, root, levels);
-}
-
-int p252_merkle4_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets, size_t n_trees,
-                               uint64_t* roots, uint64_t* levels) {
-    return forest_ragged_host(ctx, 4, tag, leaves, offsets, n_trees, roots, levels);
-}
-
-int p252_merkle2_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets, size_t n_trees,
-                               uint64_t* roots, uint64_t* levels) {
-    return forest_ragged_host(ctx, 2, tag, leaves, offsets, n_trees, roots, levels);
-}
+P252_MERKLE_PAIR(int, forest_ragged,
+                 (p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* offsets, size_t n_trees, uint64_t* roots,
+                  uint64_t* levels),
+                 forest_ragged_host(ctx, arity, tag, leaves, offsets, n_trees, roots, levels))
 
 // Forest from HOST leaves (pageable memory is fine).  Large forests stream the FIRST level — three quarters of all permutations —
 // through the staging lanes (leaves_to_device), then the upper levels run ONCE, one launch per level across all trees, so their
@@ -552,10 +543,11 @@ int p252_merkle2_forest_ragged(p252_ctx* ctx, const uint64_t tag[4], const uint6
 // 32-MiB chunk ran at 2.5e8 perm/s: every chunk paid the five narrow levels).  Trees are independent: no exchange.
 int p252_merkle4_forest(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, size_t n_trees, size_t leaves_per_tree, uint64_t* roots) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "merkle_forest"};
     if (n_trees == 0) return P252_OK;
-    if (!power_of_4(leaves_per_tree)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: leaves_per_tree must be arity^k");
-    if (n_trees > (SIZE_MAX / 32) / leaves_per_tree) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: size overflow");
-    if (!tag || !leaves || !roots) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle_forest: NULL buffer");
+    if (!power_of_4(leaves_per_tree)) return refuse("leaves_per_tree must be arity^k");
+    if (n_trees > (SIZE_MAX / 32) / leaves_per_tree) return refuse("size overflow");
+    if (!tag || !leaves || !roots) return refuse("NULL buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n_leaves = n_trees * leaves_per_tree;
     int rc = scratch(ctx, 0, n_trees * 32);
@@ -575,13 +567,13 @@ int p252_merkle4_forest(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* le
 int p252_merkle4_path_batch(p252_ctx* ctx, const uint64_t tag[4], const uint64_t* leaves, const uint64_t* siblings,
                             const uint8_t* positions, size_t depth, uint64_t* roots, size_t n) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
+    const Refusal refuse{ctx, "merkle4_path"};
     if (n == 0) return P252_OK;
-    if (!tag || !leaves || !roots || (depth && (!siblings || !positions)))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: NULL buffer");
+    if (!tag || !leaves || !roots || (depth && (!siblings || !positions))) return refuse("NULL buffer");
     for (size_t i = 0; i < n * depth; ++i)
-        if (positions[i] > 3) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: position outside 0..3");
+        if (positions[i] > 3) return refuse("position outside 0..3");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (depth > 0xffffu) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "merkle4_path: depth too large");
+    if (depth > 0xffffu) return refuse("depth too large");
     const TagArg targ = tag_arg(tag);
     const size_t chunk = staging_chunk_items(64 + depth * 97);
     // (a large batch: leaves, sibling blocks and positions stream through the staging lanes, whether page-locked or not)
@@ -602,12 +594,12 @@ int p252_merkle4_path_batch(p252_ctx* ctx, const uint64_t tag[4], const uint64_t
 static int crypt_host_run(p252_ctx* ctx, int variant, bool decrypt, const uint64_t tag[4], const uint64_t* in, const uint64_t* secrets,
                           const uint64_t* nonces, size_t len, uint64_t* out, uint8_t* ok, size_t n) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: unknown variant");
+    const Refusal refuse{ctx, "encrypt/decrypt"};
+    if (!crypt_variant_ok(variant)) return refuse("unknown variant");
     if (len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, "encrypt/decrypt: empty message");
     if (n == 0) return P252_OK;
-    if (!tag || !in || !secrets || !nonces || !out || (decrypt && !ok))
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: NULL buffer");
-    if (len >= 0x1ffffff0u) return fail(ctx, P252_ERR_INVALID_ARGUMENT, "encrypt/decrypt: message too long");
+    if (!tag || !in || !secrets || !nonces || !out || (decrypt && !ok)) return refuse("NULL buffer");
+    if (len >= 0x1ffffff0u) return refuse("message too long");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the call table is uploaded once, here; the launches only read it (no shared state between the lanes, no lock)
     int rc = prepare_prog(ctx, variant, len);
@@ -679,21 +671,21 @@ static int crypt_host(p252_ctx* ctx, int variant, bool decrypt, const uint64_t t
 static int crypt_ragged_host_run(p252_ctx* ctx, int variant, bool decrypt, const uint64_t* tags, size_t max_len, const uint64_t* in,
                                  const uint64_t* offsets, const uint64_t* secrets, const uint64_t* nonces, uint64_t* out, uint8_t* ok, size_t n) {
     if (!ctx) return P252_ERR_INVALID_ARGUMENT;
-    const std::string who = decrypt ? "decrypt_ragged" : "encrypt_ragged";
-    if (!crypt_variant_ok(variant)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": unknown variant");
+    const Refusal refuse{ctx, decrypt ? "decrypt_ragged" : "encrypt_ragged"};
+    if (!crypt_variant_ok(variant)) return refuse("unknown variant");
     if (max_len == 0 || max_len > P252_CRYPT_RAGGED_MAX_LEN)
-        return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": max_len must be 1 .. P252_CRYPT_RAGGED_MAX_LEN = " + std::to_string(P252_CRYPT_RAGGED_MAX_LEN));
+        return refuse("max_len must be 1 .. P252_CRYPT_RAGGED_MAX_LEN = " + std::to_string(P252_CRYPT_RAGGED_MAX_LEN));
     if (n == 0) return P252_OK;
-    if (!tags || !offsets || !secrets || !nonces || !out || (decrypt && !ok)) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (!tags || !offsets || !secrets || !nonces || !out || (decrypt && !ok)) return refuse("NULL buffer");
     for (size_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": offsets decrease at message " + std::to_string(i));
+        if (offsets[i + 1] < offsets[i]) return refuse("offsets decrease at message " + std::to_string(i));
         const uint64_t len = offsets[i + 1] - offsets[i];
-        if (len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, who + ": message " + std::to_string(i) + " is empty");
-        if (len > max_len) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": message " + std::to_string(i) + " is longer than max_len");
+        if (len == 0) return fail(ctx, P252_ERR_INVALID_IO_PATTERN, std::string(refuse.who) + ": message " + std::to_string(i) + " is empty");
+        if (len > max_len) return refuse("message " + std::to_string(i) + " is longer than max_len");
     }
-    if (!in) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": NULL buffer");
+    if (!in) return refuse("NULL buffer");
     const uint64_t total = offsets[n] - offsets[0];
-    if (total > SIZE_MAX / 128 || n > SIZE_MAX / 128) return fail(ctx, P252_ERR_INVALID_ARGUMENT, who + ": size overflow");
+    if (total > SIZE_MAX / 128 || n > SIZE_MAX / 128) return refuse("size overflow");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> rebased(offsets, offsets + n + 1);
     for (auto& o : rebased) o -= offsets[0];

@@ -7,6 +7,11 @@
 // check of the library.  One line per case:   symbol <TAB> case <TAB> rc <TAB> p252_last_error
 // (tests/test_api_refusals_cpu.py compares the lines with tests/golden/api_refusals.txt).  No pointer is dereferenced: no case
 // reaches a device.
+// `api_refusals --pairs` prints other rows instead, which no file records: two arguments varied at once, for every pair of arguments of
+// every entry point (refusal_table.hpp run_pairs) — what a change that must keep the order of the checks is compared on, old library
+// against new.
+#include <cstring>
+
 #include "refusal_table.hpp"
 
 using namespace refusal;
@@ -200,7 +205,7 @@ std::vector<Entry> entries() {
 }
 
 // the two multi-context entry points take an ARRAY of contexts: the one device-less context, once or twice
-void multi_rows() {
+void multi_rows(bool pairs) {
     static p252_ctx* one[1];
     static p252_ctx* twice[2];
     static const void* d_in[1] = {g_buf + 64};
@@ -225,7 +230,8 @@ void multi_rows() {
                                                             reinterpret_cast<uint64_t*>(v[5]));
                   },
                   dup, true});
-    for (Entry& e : es) run(e);
+    for (Entry& e : es) pairs ? run_pairs(e) : run(e);
+    if (pairs) return;
     // the sharded build takes a communicator, which only RCCL ranks can make: its one reachable refusal
     const int rc = p252_merkle4_tree_sharded_device(nullptr, g_tag, g_buf + 64, 16, g_buf + 128, nullptr);
     std::printf("p252_merkle4_tree_sharded_device\tcomm=NULL\t%d\t\n", rc);
@@ -233,10 +239,11 @@ void multi_rows() {
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    const bool pairs = argc > 1 && !std::strcmp(argv[1], "--pairs");
     g_ctx = new p252_ctx();  // device = -1: never bound
-    for (Entry& e : entries()) run(e);
-    multi_rows();
+    for (Entry& e : entries()) pairs ? run_pairs(e) : run(e);
+    multi_rows(pairs);
     delete g_ctx;
     return 0;
 }

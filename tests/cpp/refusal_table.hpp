@@ -121,7 +121,8 @@ inline void row(const Entry& e, const std::string& what, const std::vector<uint6
     print_row(e.sym, what, rc, p252_last_error(e.ctx_array ? g_ctx : C(v[0])));
 }
 
-inline void run(Entry& e) {
+// the all-good argument set of the control row (fills in the pointers' good values)
+inline std::vector<uint64_t> good_values(Entry& e) {
     std::vector<uint64_t> good;
     for (size_t i = 0; i < e.args.size(); ++i) {
         Arg& a = e.args[i];
@@ -130,6 +131,11 @@ inline void run(Entry& e) {
         if (a.kind == P16 || a.kind == P8 || a.kind == P4 || a.kind == P1) a.good = reinterpret_cast<uint64_t>(g_buf + 64 * (i + 1));
         good.push_back(a.good);
     }
+    return good;
+}
+
+inline void run(Entry& e) {
+    const std::vector<uint64_t> good = good_values(e);
     row(e, "control", good);
     for (size_t i = 0; i < e.args.size(); ++i) {
         const Arg& a = e.args[i];
@@ -161,6 +167,34 @@ inline void run(Entry& e) {
         }
         row(e, c.name, v);
     }
+}
+
+// The ORDER of an entry point's checks, which rows that vary one argument cannot show: for every unordered pair of its arguments, both
+// varied at once — a pointer NULL and (where it has an alignment) off by half of it, a count 0 and SIZE_MAX, a selector at its own
+// edges — in every combination.  The row names the check that fails first.  Two libraries agree on the order of their checks when
+// they print the same rows; nothing records these (a program's --pairs mode prints them).
+inline std::vector<std::pair<std::string, uint64_t>> pair_variants(const Arg& a) {
+    std::vector<std::pair<std::string, uint64_t>> vs;
+    if (a.kind != CNT && a.kind != INT) vs.push_back({"=NULL", 0});
+    if (a.kind == P16) vs.push_back({"+8", a.good + 8});
+    if (a.kind == P8) vs.push_back({"+4", a.good + 4});
+    if (a.kind == P4) vs.push_back({"+2", a.good + 2});
+    if (a.kind == CNT) vs.insert(vs.end(), {{"=0", 0}, {"=SIZE_MAX", MAXZ}});
+    if (a.kind == INT)
+        for (uint64_t x : a.edges) vs.push_back({"=" + hex(x), x});
+    return vs;
+}
+
+inline void run_pairs(Entry& e) {
+    const std::vector<uint64_t> good = good_values(e);
+    for (size_t i = 0; i < e.args.size(); ++i)
+        for (size_t j = i + 1; j < e.args.size(); ++j)
+            for (const auto& x : pair_variants(e.args[i]))
+                for (const auto& y : pair_variants(e.args[j])) {
+                    std::vector<uint64_t> v = good;
+                    v[i] = x.second, v[j] = y.second;
+                    row(e, e.args[i].name + x.first + "," + e.args[j].name + y.first, v);
+                }
 }
 
 inline const Arg CTXA = {"ctx", CTX, 0, {}}, TAGA = {"tag", HOST, 0, {}};

@@ -203,7 +203,7 @@ def test_the_unit_hashes_through_the_librarys_digest_launch_and_the_forests_own_
     assert set(edgecases.hashing_kernels()) <= set(edgecases.named_kernels())
     assert {"k_merkle4_coop", "k_merkle4_lat", "k_merkle4"} <= set(edgecases.named_kernels())
     api = open(os.path.join(CSRC, "api_forest.cpp")).read()
-    body = api[api.index("static int forest_ragged_anchor_openings_device"):api.index("int p252_merkle4_forest_ragged_anchor_openings_device_into")]
+    body = api[api.index("static int forest_ragged_anchor_openings_device"):api.index("P252_MERKLE_PAIR(int, forest_ragged_anchor_openings_device_into")]
     assert body.count("with_forest_index(") == 1 and "with_stream_scratch(" not in body and "hipMalloc" not in body and "Synchronize" not in body
     assert "refuse_overlaps(" in body and "forest_shape_check(" in body
 

@@ -263,7 +263,7 @@ def test_the_unit_hashes_through_the_path_kernel_and_shares_the_extraction_and_t
     assert not re.search(r"\bk_(fo|fr|path)_\w+\s*[(<]", code)  # the neighbours' kernels through their launchers only
     assert set(edgecases.hashing_kernels()) <= set(edgecases.named_kernels()) and "k_path_ragged" in edgecases.named_kernels()
     api = open(os.path.join(CSRC, "api_forest.cpp")).read()
-    body = api[api.index("static int forest_consistency_verify_device"):api.index("int p252_merkle4_forest_ragged_consistency_device_into")]
+    body = api[api.index("static int forest_consistency_verify_device"):api.index("P252_MERKLE_PAIR(int, forest_ragged_consistency_device_into")]
     assert "ragged_sort_enabled()" in body and body.count("with_stream_scratch(") == 1 and "hipMalloc" not in body
 
 

@@ -260,7 +260,7 @@ def test_the_unit_hashes_through_the_multiproofs_digest_launch_and_the_streams_s
     assert not re.search(r"\bk_(fm|mp|fr|fo)_\w+\s*[(<]", code)  # the neighbours' kernels through their launchers only
     api = open(os.path.join(CSRC, "api_forest.cpp")).read()
     extract = api[api.index("static int forest_ragged_range_proofs_device"):api.index("static int forest_range_verify_device")]
-    verify = api[api.index("static int forest_range_verify_device"):api.index("int p252_merkle4_forest_ragged_range_proofs_device_into")]
+    verify = api[api.index("static int forest_range_verify_device"):api.index("P252_MERKLE_PAIR(int, forest_ragged_range_proofs_device_into")]
     assert extract.count("with_forest_index(") == 1 and "with_stream_scratch(" not in extract and "forest_shape_check(" in extract
     assert verify.count("with_stream_scratch(") == 1 and "with_forest_index(" not in verify
     for body in (extract, verify):

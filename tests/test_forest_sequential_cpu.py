@@ -221,7 +221,7 @@ def test_the_unit_hashes_through_one_digest_launch_and_the_streams_scratch():
         body = body[:body.index("\n}\n")]
         assert "ctr[SQ_BAD]" in body, name
     api = open(os.path.join(CSRC, "api_forest.cpp")).read()
-    body = api[api.index("static int forest_ragged_update_sequential_device"):api.index("int p252_merkle4_forest_ragged_update_sequential_device_into")]
+    body = api[api.index("static int forest_ragged_update_sequential_device"):api.index("P252_MERKLE_PAIR(int, forest_ragged_update_sequential_device_into")]
     assert body.count("with_forest_index(") == 1 and "with_stream_scratch(" not in body and "forest_shape_check(" in body
     assert "refuse_overlaps(" in body and "hipMalloc" not in body and "Synchronize" not in body
 
